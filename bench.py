@@ -18,7 +18,8 @@ device-resident whole-job rate.  SURVEY.md 8(d)'s end-to-end metric (host ASCII 
 host memory, i.e. H2D + pack + scan + D2H) is measured in the same run through the library's batch stream and reported
 beside it as `value_end_to_end` -- never as `value`.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  --dump-outputs DIR (region workloads) also writes what the last timed step computed on
+rank 0 as DIR/<name>.npy, so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import json
@@ -213,6 +214,28 @@ def _nccl_version(torch):
         return f"unknown ({type(e).__name__})"
 
 
+DUMP_HIT_BYTES = 60 << 20          # --dump-outputs: the hit samples of all region sets together (the rest stays far below 4 MB)
+
+
+def dump_outputs(out_dir, results, counts):
+    """What one step of the timed path hands its caller, as float64 .npy files: region_counts [sets, P] (the step's
+    all-reduced per-motif counts of regions with >= 1 site), and per region set k: set<k>_motif_offsets [P + 1] and
+    set<k>_hits [n, 6] with rows (index in the hit list, motif, seq_idx, pos, strand, score) -- every hit when they fit in
+    DUMP_HIT_BYTES, else a sample of hit indices drawn with seed k (a function of the hit count only)."""
+    os.makedirs(out_dir, exist_ok=True)
+    P = results[0].n_pwms
+    np.save(os.path.join(out_dir, "region_counts.npy"), counts.reshape(len(results), P).astype(np.float64))
+    cap = DUMP_HIT_BYTES // len(results) // (6 * 8)
+    for k, res in enumerate(results):
+        n = res.n_hits
+        idx = np.arange(n) if n <= cap else np.sort(np.random.default_rng(k).choice(n, cap, replace=False))
+        h = res.hits(copy=False, motif=False)
+        motif = np.searchsorted(res.motif_offsets, idx, side="right") - 1
+        rows = np.stack([idx, motif, h["seq_idx"][idx], h["pos"][idx], h["strand"][idx], h["score"][idx]], axis=1).astype(np.float64)
+        np.save(os.path.join(out_dir, f"set{k}_motif_offsets.npy"), res.motif_offsets.astype(np.float64))
+        np.save(os.path.join(out_dir, f"set{k}_hits.npy"), rows)
+
+
 class _DevicePtr:
     """Lets torch wrap the library's device-resident count vector without a copy (CUDA array interface)."""
 
@@ -244,7 +267,15 @@ def main():
     ap.add_argument("--host-pack", action="store_true", help="end-to-end legs: convert_seq on the stream's host threads (MS_STREAM_HOST_PACK: 0.69 B/base over the link "
                     "instead of 1, no pack kernel) -- an option for multi-GPU nodes whose host link is the bound; slower at N = 1 (profiles/r05_host_packed_upload.log)")
     ap.add_argument("--extra-widths", default="", help="comma list: append one synthetic motif of each of these widths (side workload: motifs wider than the set holds)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy, float64, "
+                         "under 64 MB in all (a seeded sample of the hits when there are more); with --gpus N > 1 the region counts are the "
+                         "all-reduced sum and the hits rank 0's shard only: see dump_outputs()")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.workload in ("c5", "c5shard"):
+        ap.error("--dump-outputs covers the region workloads (c4, c3, c2, tiny), not the window sweeps")
     strand_mask = {"both": 3, "+": 1, "-": 2}[a.strand]
     side = a.p_value != "1e-4" or a.strand != "both" or bool(a.extra_widths) or a.motif_set != "benchmark"
 
@@ -315,7 +346,7 @@ def main():
 
     ar_events = []                                  # (start, end) CUDA events around the path's one collective, per timed step
 
-    def step(timed=False):
+    def step(timed=False, keep=None):
         stats = []
         for s, sq in enumerate(seqsets):
             sq.repack()                            # extraction: resident ASCII -> 2-bit codes + N mask
@@ -324,7 +355,10 @@ def main():
             # the library's own device vector, wrapped in place: device -> device, no trip through the host
             counts[s * P:(s + 1) * P].copy_(torch.as_tensor(_DevicePtr(res.region_counts_device_ptr(), P), device=dev))
             torch.cuda.current_stream().synchronize()          # the result block returns to the pool on close()
-            res.close()
+            if keep is None:
+                res.close()
+            else:
+                keep.append(res)                   # --dump-outputs: closed once written, after the timed region
         local_counts.copy_(counts)
         if use_pg:
             if timed:
@@ -353,15 +387,26 @@ def main():
             more = bool(flag.item())
         if not more:
             break
+    last_results = [] if a.dump_outputs else None
+    if last_results is not None:
+        # the last timed step keeps every set's result open until it is dumped, where a step otherwise returns each result block to the
+        # pool before the next scan: one more untimed step that holds them all leaves the pool enough blocks, so no timed scan goes to the driver
+        held = []
+        step(keep=held)
+        n_warm += 1
+        for res in held:
+            res.close()
     fence()
+    pool0 = _lib.pool_stats()
     t0 = time.perf_counter()
     all_stats = []
-    for _ in range(a.steps):
-        all_stats.extend(step(timed=True))
+    for k in range(a.steps):
+        all_stats.extend(step(timed=True, keep=last_results if k == a.steps - 1 else None))
     torch.cuda.synchronize()
     own_elapsed = time.perf_counter() - t0          # this rank's own K steps (its last collective included), before the closing barrier
     fence()
     elapsed = time.perf_counter() - t0
+    pool1 = _lib.pool_stats()
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     units = torch.tensor([float(wl["units"])], dtype=torch.float64, device=dev)
     if use_pg:
@@ -369,6 +414,11 @@ def main():
         dist.all_reduce(units, op=dist.ReduceOp.SUM)
     elapsed = float(tmax.item())
     total_units = float(units.item())
+    if last_results is not None:
+        if rank == 0:
+            dump_outputs(a.dump_outputs, last_results, counts.cpu().numpy())
+        for res in last_results:
+            res.close()
 
     # the collective, checked: all-reduced vector == sum over ranks of the vectors each rank's library handed over
     counts_check = None
@@ -522,6 +572,8 @@ def main():
             "n_pwms_exact_only": int(all_stats[-1]["n_pwms_exact"]),
             # the path's one collective per step, slowest rank's mean (device events around dist.all_reduce); 0 at N = 1: no collective runs
             "allreduce_ms": max(ranks_report["allreduce_ms_mean_by_rank"]) if ranks_report is not None else 0.0,
+            # rank 0's HBM block cache over the timed steps: a miss is a driver allocation inside the timed region
+            "hbm_pool_timed": {k: pool1[k] - pool0[k] for k in ("hits", "misses", "driver_frees", "driver_ms")},
         }
         if counts_check is not None:
             line["counts_check"] = counts_check

@@ -113,6 +113,16 @@ def test_sweep_shards_cover_every_window_once():
                     assert b == begin + k0 * stride and e == begin + (k1 - 1) * stride + window and e <= end
                     assert (e - b - window) // stride + 1 == k1 - k0          # the span holds exactly the rank's windows
             assert seen == list(range(n))
+    # the spans of a host-streamed genome sweep (bench.py --workload c5 --genome-mbp 240), shared by up to eight ranks: every rank
+    # gets spans, and their window ranges tile the sweep in rank order
+    from motifscan_amd import _lib, synth
+    spans = _lib.sweep_spans(synth.c5_chrom_lengths(240_000_000), 200, 50, 375_000_000)
+    n_windows = spans[-1][3] + spans[-1][4]
+    for world in (1, 2, 4, 8):
+        mine = [msdist.span_shard(spans, rank, world) for rank in range(world)]
+        assert all(mine) and sum(mine, []) == spans
+        ranges = [(m[0][3], m[-1][3] + m[-1][4]) for m in mine]
+        assert ranges[0][0] == 0 and ranges[-1][1] == n_windows and all(x[1] == y[0] for x, y in zip(ranges[:-1], ranges[1:]))
 
 
 def test_batch_bounds_cover_every_region_once_with_and_without_ramp():

@@ -946,34 +946,73 @@ def _bench_ranks_on_one_gpu(args, timeout=1500):
     return json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
 
 
-def test_bench_world_of_eight_on_one_gpu():
-    """The shape the driver's 8-GPU SCALE run has -- eight fresh ranks, eight shards of both region sets of configs[3] (here 160k
-    regions per set), 8 stream pipelines (24 host threads) and 8 block pools, one all-reduce per step -- on the one GPU of this box
-    over gloo: n_gpus = 8, the all-reduced vector == the sum of the ranks' vectors, the eight shards tile both sets in rank order,
-    and 2000 regions of EVERY rank's own shard are bit-identical to the oracle."""
-    line = _bench_ranks_on_one_gpu(["--gpus", "8", "--regions-per-set", "160000", "--steps", "3", "--warmup", "1", "--min-warm-seconds", "0"])
-    assert line["n_gpus"] == 8 and line["scaling"] == "strong" and line["value"] > 0
+# Four ranks at most on the one GPU: a shared device is held open by no more than six processes at once, and this test's own
+# process and bench.py's launcher count besides the ranks.  The shards of eight ranks are checked on the host (tests/test_dist_gloo.py).
+def test_bench_world_of_four_on_one_gpu():
+    """The multi-GPU shape -- four fresh ranks, four shards of both region sets of configs[3] (here 160k regions per set), 4 stream
+    pipelines (12 host threads) and 4 block pools, one all-reduce per step -- on the one GPU of this box over gloo: n_gpus = 4,
+    the all-reduced vector == the sum of the ranks' vectors, the four shards tile both sets in rank order, and 2000 regions of
+    EVERY rank's own shard are bit-identical to the oracle."""
+    line = _bench_ranks_on_one_gpu(["--gpus", "4", "--regions-per-set", "160000", "--steps", "3", "--warmup", "1", "--min-warm-seconds", "0"])
+    assert line["n_gpus"] == 4 and line["scaling"] == "strong" and line["value"] > 0
     assert line["counts_check"]["allreduce_equals_sum_of_rank_counts"] is True
     rk = line["ranks"]
-    assert rk["shards_tile_every_set"] is True and len(rk["shard_by_rank"]) == 8
-    assert [b - a for a, b in rk["shard_by_rank"]] == [20_000] * 8
+    assert rk["shards_tile_every_set"] is True and len(rk["shard_by_rank"]) == 4
+    assert [b - a for a, b in rk["shard_by_rank"]] == [40_000] * 4
     ps = rk["parity_sample"]
-    assert ps["ranks"] == 8 and ps["ranks_identical_to_oracle"] == 8 and ps["regions_per_rank"] == 2000 and ps["hits_checked"] > 100_000
-    assert line["allreduce_ms"] >= 0 and len(rk["allreduce_ms_mean_by_rank"]) == 8
+    assert ps["ranks"] == 4 and ps["ranks_identical_to_oracle"] == 4 and ps["regions_per_rank"] == 2000 and ps["hits_checked"] > 100_000
+    assert line["allreduce_ms"] >= 0 and len(rk["allreduce_ms_mean_by_rank"]) == 4
     e2e = line["value_end_to_end"]
     assert e2e["pipelined"] > 0 and e2e["hits_per_pass_per_gpu"] > 0
     assert e2e["pipelined_sustained"] > 0 and e2e["sustained_hits_check"] is True      # one stream over four passes: four times the hits
 
 
-def test_bench_sweep_world_of_eight_on_one_gpu():
-    """configs[4] (host-streamed sweep) with the spans sharded over eight ranks on one GPU: the ranks' window ranges tile the
+def test_bench_sweep_world_of_four_on_one_gpu():
+    """configs[4] (host-streamed sweep) with the spans sharded over four ranks on one GPU: the ranks' window ranges tile the
     sweep, the all-reduced per-motif window counts == the sum of the ranks' own."""
-    line = _bench_ranks_on_one_gpu(["--gpus", "8", "--workload", "c5", "--genome-mbp", "240", "--steps", "1", "--warmup", "1",
+    line = _bench_ranks_on_one_gpu(["--gpus", "4", "--workload", "c5", "--genome-mbp", "240", "--steps", "1", "--warmup", "1",
                                     "--min-warm-seconds", "0"])
-    assert line["n_gpus"] == 8 and line["value"] > 0
+    assert line["n_gpus"] == 4 and line["value"] > 0
     cc = line["counts_check"]
-    assert cc["allreduce_equals_sum_of_rank_counts"] is True and cc["window_ranges_tile_the_sweep"] is True and cc["ranks_with_spans"] == 8
+    assert cc["allreduce_equals_sum_of_rank_counts"] is True and cc["window_ranges_tile_the_sweep"] is True and cc["ranks_with_spans"] == 4
     assert line["modes"]["hits_packed"]["sites_per_step_per_gpu"] > 0
+
+
+def test_bench_dump_outputs_repeat_and_match_the_oracle(tmp_path, oracle):
+    """--dump-outputs DIR: what the last timed step computed, as float64 .npy files under 64 MB, the same in two runs (seeded
+    inputs) and equal to the oracle's scan of the same inputs -- every hit of both sets (tiny: all fit) with its motif, region,
+    position, strand and fp64 score, the motif offsets, and the per-motif counts of regions with a site.  Holding the last step's
+    results for the dump costs the timed steps no driver allocation."""
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1",
+                              "--min-warm-seconds", "0", "--no-cpu-baseline", "--no-api", "--no-end-to-end", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-3000:]
+        line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        assert line["hbm_pool_timed"]["misses"] == 0 and line["hbm_pool_timed"]["hits"] > 0
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+        dumps.append({f.name: np.load(f) for f in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert sorted(a) == ["region_counts.npy", "set0_hits.npy", "set0_motif_offsets.npy", "set1_hits.npy", "set1_motif_offsets.npy"]
+    assert sorted(b) == sorted(a) and all(a[k].dtype == np.float64 and np.array_equal(a[k], b[k]) for k in a)
+    wl = synth.workload("tiny")                                          # bench.py's inputs at --gpus 1
+    P = len(wl["widths"])
+    assert a["region_counts.npy"].shape == (2, P)
+    for s, (bases, offsets) in enumerate(wl["sets"]):
+        want = oracle.scan_arrays(wl["pwm_values"], wl["widths"], wl["cutoffs"], bases.tobytes(), offsets, 3, 8)
+        hits, offs = a[f"set{s}_hits.npy"], a[f"set{s}_motif_offsets.npy"]
+        n = int(want["motif_offsets"][-1])
+        assert n > 0 and np.array_equal(offs, want["motif_offsets"])
+        assert np.array_equal(hits[:, 0], np.arange(n))
+        assert np.array_equal(hits[:, 1], np.repeat(np.arange(P), np.diff(want["motif_offsets"])))
+        assert np.array_equal(hits[:, 2], want["seq_idx"]) and np.array_equal(hits[:, 3], want["pos"])
+        assert np.array_equal(hits[:, 4], want["strand"]) and np.array_equal(hits[:, 5], want["score"])
+        mo = want["motif_offsets"]
+        regions = [len(np.unique(want["seq_idx"][mo[m]:mo[m + 1]])) for m in range(P)]
+        assert np.array_equal(a["region_counts.npy"][s], regions)
 
 
 def test_bench_collectives_over_rccl_on_a_one_rank_communicator():
