@@ -101,7 +101,7 @@ typedef struct ms_scan_stats {
     double  ms_total;           /* first launch -> last kernel done                                  */
     int64_t lds_bytes_read;     /* bytes the pre-filter reads from LDS (operand tables)              */
     int64_t hbm_bytes_algorithmic; /* codes + mask + offsets + PWMs + 16 B/hit + 8 B/PWM */
-    double  pf_clock_mhz;       /* shader clock held inside the pre-filter kernel; 0 unless MS_PF_CLOCK=1 */
+    double  pf_clock_mhz;       /* always 0 (reserved) */
     int64_t mfma_ops;           /* multiply-adds x 2 the pre-filter issues on the matrix cores (one-hot zeros and width padding included) */
     int64_t mfma_ops_algorithmic; /* 2 x windows x strands x W: the adds the reference performs */
     int32_t pf_engine;          /* 3: the fp6 x fp4 one-hot product on the matrix cores, candidates parked and decoded later; 4: the same with the flags decoded in place (chosen when the previous scan of the PWM set found many hits per row tile: p >= ~5e-4) */
@@ -110,9 +110,6 @@ typedef struct ms_scan_stats {
 
 const char *ms_last_error(void);
 int ms_version(void);
-/* Bit 0: the library's pre-filter holds the hand-written gfx950 asm blocks (the variant libmotifscan_amd_asm.so, csrc/Makefile); 0 for the
- * product library, whose pre-filter is built from compiler builtins only.  Identical results either way.  No reference counterpart. */
-int ms_build_flags(void);
 
 /* Device selection is per calling thread (like hipSetDevice).  Handles remember their device. */
 int ms_device_count(int *count);

@@ -13,12 +13,7 @@ import subprocess
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# MS_LIB_VARIANT=asm loads the variant whose pre-filter holds the hand-written gfx950 blocks of rounds 4-5 (csrc/Makefile, ms_kernels.hip
-# "the two builds"): same C-ABI, same results, same speed as measured in round 6 -- kept for A/B runs; the GPU suite runs the goldens on both.
-LIB_VARIANT = os.environ.get("MS_LIB_VARIANT", "")
-if LIB_VARIANT not in ("", "asm"):
-    raise RuntimeError(f"MS_LIB_VARIANT={LIB_VARIANT!r}: known variants are '' (default) and 'asm'")
-LIB_PATH = os.path.join(_HERE, "libmotifscan_amd_asm.so" if LIB_VARIANT == "asm" else "libmotifscan_amd.so")
+LIB_PATH = os.path.join(_HERE, "libmotifscan_amd.so")
 
 MS_OK, MS_ERR_INVALID, MS_ERR_NOMEM, MS_ERR_RUNTIME = 0, 1, 2, 3
 MS_SCAN_DEFAULT, MS_SCAN_EXACT_ONLY, MS_SCAN_COUNTS_ONLY = 0, 1, 2
@@ -92,7 +87,6 @@ def lib():
     sig = {
         "ms_last_error": (ctypes.c_char_p, []),
         "ms_version": (c_int, []),
-        "ms_build_flags": (c_int, []),
         "ms_device_count": (c_int, [ctypes.POINTER(c_int)]),
         "ms_set_device": (c_int, [c_int]),
         "ms_device_name": (c_int, [ctypes.c_char_p, c_int]),
@@ -159,8 +153,6 @@ def lib():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = res, args
     _lib = L
-    if bool(L.ms_build_flags() & 1) != (LIB_VARIANT == "asm"):
-        raise RuntimeError(f"{LIB_PATH}: ms_build_flags() = {L.ms_build_flags()} does not match the variant asked for ({LIB_VARIANT or 'default'}): rebuild (make -C motifscan_amd/csrc)")
     return L
 
 

@@ -63,19 +63,8 @@ int get_ctx(int device, DeviceCtx **out) {
     if (c->lds_max < 65536) c->lds_max = 65536;
     if (c->lds_max > 163840) c->lds_max = 163840;
     MS_HIP(hipStreamCreateWithFlags(&c->stream.whole, hipStreamNonBlocking));
-    {
-        // MS_MEASURE=1 MS_COPY_PRIORITY=1 (A/B): the copy streams at the device's highest priority -- a copy-out that runs as a blit kernel then wins freed CUs
-        // over the pre-filter's pending blocks
-        int lo = 0, hi = 0;
-        const bool prio = measure_env("MS_COPY_PRIORITY") && atoi(measure_env("MS_COPY_PRIORITY")) != 0 && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo;
-        if (prio) {
-            MS_HIP(hipStreamCreateWithPriority(&c->stream_up.whole, hipStreamNonBlocking, hi));
-            MS_HIP(hipStreamCreateWithPriority(&c->stream_down.whole, hipStreamNonBlocking, hi));
-        } else {
-            MS_HIP(hipStreamCreateWithFlags(&c->stream_up.whole, hipStreamNonBlocking));
-            MS_HIP(hipStreamCreateWithFlags(&c->stream_down.whole, hipStreamNonBlocking));
-        }
-    }
+    MS_HIP(hipStreamCreateWithFlags(&c->stream_up.whole, hipStreamNonBlocking));
+    MS_HIP(hipStreamCreateWithFlags(&c->stream_down.whole, hipStreamNonBlocking));
     for (StreamSel *s : {&c->stream, &c->stream_up, &c->stream_down}) s->n_streams = &c->n_streams;
     if (measure_env("MS_CU_PARTITION")) {
         // A/B switch (MS_MEASURE=1 MS_CU_PARTITION=1); off by default, see StreamSel.
@@ -748,9 +737,9 @@ static int seqset_alloc_packed(ms_seqset *s, bool pads_by_copy = false, bool def
     if (!pads_by_copy) {                                  // (host-packed: the offsets travel in the one copy of the whole block)
         // through pinned words, so that the copy runs on the SDMA engines like the sequence's: from the pageable vector the runtime copies with a one-workgroup
         // KERNEL, which in a batch stream waits for a CU while the previous batch's pre-filter holds them all (profiles/r06z_trace_e2e_gaps_sdma.log: 3.5 ms
-        // per batch on the upload stream).  MS_MEASURE=1 MS_OFFSETS_PAGEABLE=1: the old way, for A/B runs.
+        // per batch on the upload stream).  Pageable memory only if no pinned words can be had.
         const void *src = s->offsets.data();
-        if (!measure_env("MS_OFFSETS_PAGEABLE") && (s->h_off_pin = pinned_alloc(b_off, &s->h_off_pin_bytes))) {
+        if ((s->h_off_pin = pinned_alloc(b_off, &s->h_off_pin_bytes))) {
             std::memcpy(s->h_off_pin, s->offsets.data(), b_off);
             src = s->h_off_pin;
         }
@@ -1263,9 +1252,7 @@ static void finish_scan(ms_result *raw, hipEvent_t *ev, ms_pwmset *pwms, int64_t
         (void) hipEventElapsedTime(&ms05, ev[0], ev[5]);
         stt.ms_sort = ms34; stt.ms_finalize = ms45; stt.ms_total = ms05;
     }
-    if (measure_env("MS_TRACE_BLOCKS"))                  // measurement: which device blocks a scan worked on, beside its stage times (tools/e2e_block_probe.py)
-        fprintf(stderr, "MSBLK done res=%p bases=%lld pf=%.3f fp64=%.3f sort=%.3f fin=%.3f\n", raw->block, (long long) n_bases, ms01, ms12, ms34, ms45);
-    if (stt.n_windows > 0 && !raw->invalid) {            // what the next scan of this set of PWMs may expect (scan_locked)
+    if (stt.n_windows > 0) {            // what the next scan of this set of PWMs may expect (scan_locked)
         pwms->pred_density = (double) n_hits / (double) stt.n_windows;
         pwms->pred_strand = strand_mask;
         pwms->pred_cutoff_version = pwms->cutoff_version;
@@ -1283,14 +1270,9 @@ int scan_complete(DeviceCtx *c, ms_pwmset *pwms, PendingScan *p, ms_result **out
     if (he != hipSuccess) { set_error("scan kernels failed: %s", hipGetErrorString(he)); ms_result_free(raw); return MS_ERR_RUNTIME; }
     const unsigned long long n_cand = p->cand_static + p->h_counters[0], n_hits = p->h_counters[1];
     if (n_cand <= p->cand_cap && n_hits <= p->hit_cap && n_hits <= p->n_pred) {
-        if (p->offsets_queued) {                       // (copied in stream order, in front of `done`: scan_locked)
-            const size_t n_off = raw->motif_offsets.size();
-            std::memcpy(raw->motif_offsets.data(), p->h_offsets, n_off * sizeof(int64_t));
-            try { raw->h_region_counts.assign(p->h_offsets + n_off, p->h_offsets + n_off + raw->P); } catch (const std::bad_alloc &) { raw->h_region_counts.clear(); }
-        } else {
-            he = hipMemcpy(raw->motif_offsets.data(), raw->d_motif_first, raw->motif_offsets.size() * sizeof(int64_t), hipMemcpyDeviceToHost);
-            if (he != hipSuccess) { set_error("copy failed: %s", hipGetErrorString(he)); ms_result_free(raw); return MS_ERR_RUNTIME; }
-        }
+        const size_t n_off = raw->motif_offsets.size();      // (copied in stream order, in front of `done`: scan_locked)
+        std::memcpy(raw->motif_offsets.data(), p->h_offsets, n_off * sizeof(int64_t));
+        try { raw->h_region_counts.assign(p->h_offsets + n_off, p->h_offsets + n_off + raw->P); } catch (const std::bad_alloc &) { raw->h_region_counts.clear(); }
         pwms->pred_margin = std::max(0.04, pwms->pred_margin * 0.9);
         finish_scan(raw, p->ev, pwms, p->n_bases, p->R, p->strand_mask, p->exact_only, n_cand, n_hits, true);
         *out = raw;
@@ -1447,16 +1429,6 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
         if (const char *e = measure_env("MS_PF_RARE_CAP")) rare_cap = (uint32_t) std::max(kRareCapMin, std::min((int) rare_cap, atoi(e)));    // test aid
         lds_bytes += (size_t) (rare_cap - (uint32_t) kRareCapMin) * per_entry;
     }
-    int pf_no_emit = 0;
-    if (const char *e = measure_env("MS_PF_NOEMIT")) pf_no_emit = atoi(e);
-    const bool pf_clock = measure_env("MS_PF_CLOCK") && atoi(measure_env("MS_PF_CLOCK")) != 0;
-    unsigned long long *d_clk = nullptr;
-    int clk_blocks = 0;
-    const bool pf_meas = pf_no_emit != 0 || pf_clock;              // the measurement instantiation of the kernel
-    int pf_floor = 0;                                              // MS_MEASURE=1 MS_PF_FLOOR=1..4: a compile-time cut of the product kernel (ms_kernels.hip, FLOOR)
-    if (const char *e = measure_env("MS_PF_FLOOR")) pf_floor = std::max(0, std::min(4, atoi(e)));
-    if (pf_meas) pf_floor = 0;
-    raw->invalid = pf_no_emit != 0 || pf_floor != 0;               // stage times only: the hit accessors refuse such a result
 
     // ---- the pre-filter's launch geometry
     const int n_tiles = (int) plan.tiles.size();
@@ -1490,10 +1462,6 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
             counter_used = false;
         }
         pf_wave_passes = wp;
-        if (counter_used && pf_wave_passes < 2) {                     // the kernel's hand-written atomic needs a second pass before its value is read (ms_kernels.hip)
-            set_error("internal: a dynamic hand-out of single-pass units (wave_passes %lld)", (long long) pf_wave_passes);
-            return MS_ERR_RUNTIME;
-        }
     }
 
     // counters: [0] candidate record slots, [1] hits
@@ -1505,11 +1473,9 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
         he = hipMemsetAsync(sc.counters, 0, 8 * sizeof(unsigned long long), c->stream);
         if (he != hipSuccess) { set_error("memset failed: %s", hipGetErrorString(he)); return MS_ERR_RUNTIME; }
         (void) hipEventRecord(ev[0], c->stream);
-        if (const char *e = measure_env("MS_EXTRA_MEMSETS"))       // measurement: what a tiny kernel costs at this point of a batch stream
-            for (int i = 0; i < atoi(e); i++) (void) hipMemsetAsync(sc.counters + 4, 0, 8, c->stream);
         if (n_tiles > 0) {
             PfArgs A;
-            A.codes = S.codes; A.nmask = S.nmask; A.n_bases = S.n_bases; A.no_emit = pf_no_emit; A.skip_alln = plan.alln_can_hit ? 0 : 1;
+            A.codes = S.codes; A.nmask = S.nmask; A.n_bases = S.n_bases; A.skip_alln = plan.alln_can_hit ? 0 : 1;
             A.tables = pwms->d_tables; A.tiles = pwms->d_tiles; A.lut_off16 = lut_off16; A.stage_off16 = lut_off16 + (uint32_t) (kF6LutBytes / 16);
             A.emit_off16 = A.stage_off16 + (uint32_t) (kPfStageBytes / 16);
             A.onehot_off16 = A.emit_off16 + (uint32_t) (kPfEmitBytes / 16);
@@ -1530,14 +1496,6 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
                 he = hipMemsetAsync(A.chunk_counter, 0, sizeof(unsigned int) * counter_words, c->stream);
                 if (he != hipSuccess) { set_error("memset failed: %s", hipGetErrorString(he)); return MS_ERR_RUNTIME; }
             }
-            A.clk = nullptr;
-            A.cls_clk = pf_clock && atoi(measure_env("MS_PF_CLOCK")) == 2;
-            if (pf_clock) {
-                clk_blocks = bpt * n_tiles;
-                if (!d_clk && (rc = dev_alloc(&d_clk, (size_t) kPfClkWords * clk_blocks))) return rc;
-                (void) hipMemsetAsync(d_clk, 0, sizeof(unsigned long long) * kPfClkWords * clk_blocks, c->stream);
-                A.clk = d_clk;
-            }
             {
                 const int64_t n_chunks = (S.n_bases + kPfThreads - 1) / kPfThreads;
                 cand_static = (uint64_t) std::min<int64_t>(bpt, n_chunks) * n_tiles * (kPfThreads / 64) * cand_block;
@@ -1545,14 +1503,13 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
             }
             bool wide = false;
             for (const TileDesc &t : plan.tiles) wide = wide || t.max_nk > 2;
-            const int floor_ = wide ? 0 : pf_floor;
-            const bool dense = pf_dense && !wide && !pf_meas && !floor_;
-            const int li = (wide ? 2 : 0) + (pf_meas ? 1 : 0) + (dense ? 4 : 0) + 8 * floor_;
+            const bool dense = pf_dense && !wide;
+            const int li = wide ? 2 : dense ? 1 : 0;
             if (lds_bytes > c->lds_set[li]) {
-                if ((rc = prefilter_set_lds(wide, pf_meas, dense, lds_bytes, floor_))) return rc;
+                if ((rc = prefilter_set_lds(wide, dense, lds_bytes))) return rc;
                 c->lds_set[li] = lds_bytes;
             }
-            if ((rc = launch_prefilter(A, wide, pf_meas, dense, bpt, n_tiles, lds_bytes, c->stream, floor_))) return rc;
+            if ((rc = launch_prefilter(A, wide, dense, bpt, n_tiles, lds_bytes, c->stream))) return rc;
             stt.pf_engine = dense ? 4 : 3;
         }
         (void) hipEventRecord(ev[1], c->stream);
@@ -1667,32 +1624,6 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
         result_carve(raw, blk, n);
         return MS_OK;
     };
-    auto read_clock = [&]() {
-        if (!d_clk) return;                                  // median over blocks of cycles per 10 ns tick
-        std::vector<unsigned long long> h((size_t) kPfClkWords * clk_blocks);
-        if (hipMemcpy(h.data(), d_clk, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess) {
-            std::vector<double> mhz;
-            for (int b = 0; b < clk_blocks; b++)
-                if (h[(size_t) kPfClkWords * b + 1] > 0) mhz.push_back(100.0 * (double) h[(size_t) kPfClkWords * b] / (double) h[(size_t) kPfClkWords * b + 1]);
-            if (!mhz.empty()) { std::sort(mhz.begin(), mhz.end()); stt.pf_clock_mhz = mhz[mhz.size() / 2]; }
-            if (atoi(measure_env("MS_PF_CLOCK")) == 2) {              // where a wave's cycles go: per class of the first LDS tile, and outside the classes
-                double tot = 0, cls[kMaxClasses] = {0, 0, 0, 0, 0, 0};
-                for (int b = 0; b < clk_blocks / (int) plan.tiles.size(); b++) {
-                    tot += (double) h[(size_t) kPfClkWords * b];
-                    for (int i = 0; i < kMaxClasses; i++) cls[i] += (double) h[(size_t) kPfClkWords * b + 2 + i];
-                }
-                fprintf(stderr, "pf wave-0 cycles:");
-                double in = 0;
-                const TileDesc &t0 = plan.tiles[0];
-                for (int i = 0; i < t0.n_classes; i++) {
-                    fprintf(stderr, " [%s nk %d x %d row tiles] %.1f %%", t0.cls[i].paired ? "paired" : "plain", t0.cls[i].nk, t0.cls[i].n_row_tiles, 100.0 * cls[i] / tot);
-                    in += cls[i];
-                }
-                fprintf(stderr, " [outside the classes] %.1f %%\n", 100.0 * (tot - in) / tot);
-            }
-        }
-        dev_free(d_clk);
-    };
     auto finish = [&](unsigned long long n_cand, unsigned long long n_hits, bool with_back) {
         finish_scan(raw, ev, pwms, seqs->n_bases, seqs->R, strand_mask, exact_only, n_cand, n_hits, with_back);
     };
@@ -1705,7 +1636,7 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
     // synchronisation at the very end validates the prediction.  A wrong prediction (count above the margin, or a scratch buffer
     // too small) costs a second, exactly-sized run below and doubles the margin of the next scans.
     const bool predicted = pwms->pred_density >= 0 && pwms->pred_strand == strand_mask && pwms->pred_cutoff_version == pwms->cutoff_version &&
-                           pwms->pred_exact_only == exact_only && !(flags & (MS_SCAN_RAW_INTERNAL | MS_SCAN_NO_PREDICT_INTERNAL)) && !pf_meas &&
+                           pwms->pred_exact_only == exact_only && !(flags & (MS_SCAN_RAW_INTERNAL | MS_SCAN_NO_PREDICT_INTERNAL)) &&
                            !measure_env("MS_NO_PREDICT");
     if (predicted) {
         if (pend) ev = pend->ev;
@@ -1718,9 +1649,6 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
         stt.n_passes = 1;
         HitOut H;
         H.keys = sc.keys; H.vals = sc.vals; H.n_hits = sc.counters + 1; H.cap = sc.hit_cap; H.gbits = gbits; H.pbits = pbits;
-        if (measure_env("MS_TRACE_BLOCKS"))
-            fprintf(stderr, "MSBLK launch res=%p (%zu bytes) codes=%p nmask=%p blkinfo=%p offsets=%p cand=%p keys=%p\n", raw->block, raw->block_bytes, (const void *) S.codes, (const void *) S.nmask,
-                    (const void *) S.blkinfo, (const void *) S.offsets, (void *) sc.cand, (void *) sc.keys);
         if ((rc = front(H))) return fail(rc);
         if ((rc = launch_fill_tail(sc.keys, sc.counters + 1, n_pred, c->stream))) return fail(rc);
         queue_only = pend != nullptr;
@@ -1737,16 +1665,15 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
             // ride along: the stream's copy-out stage brings them to the host with every batch, and its own small copy is one more blit kernel that
             // has to find a CU beside the running pre-filter
             const size_t n_off = raw->motif_offsets.size(), n_words = n_off + (size_t) pwms->P;
-            pend->offsets_queued = !measure_env("MS_OFFSETS_BLOCKING");
-            if (pend->offsets_queued && pend->h_offsets_cap < n_words) {
+            if (pend->h_offsets_cap < n_words) {
                 if (pend->h_offsets) (void) hipHostFree(pend->h_offsets);
                 pend->h_offsets = nullptr; pend->h_offsets_cap = 0;
                 he = hipHostMalloc(&pend->h_offsets, (n_words + 64) * sizeof(int64_t));
                 if (he != hipSuccess) { set_error("out of pinned host memory"); return fail(MS_ERR_NOMEM); }
                 pend->h_offsets_cap = n_words + 64;
             }
-            he = pend->offsets_queued ? hipMemcpyAsync(pend->h_offsets, raw->d_motif_first, n_off * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-            if (he == hipSuccess && pend->offsets_queued && pwms->P > 0)
+            he = hipMemcpyAsync(pend->h_offsets, raw->d_motif_first, n_off * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
+            if (he == hipSuccess && pwms->P > 0)
                 he = hipMemcpyAsync(pend->h_offsets + n_off, raw->d_region_counts, (size_t) pwms->P * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
             if (he == hipSuccess) he = hipMemcpyAsync(pend->h_counters, sc.counters, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
             if (he == hipSuccess) he = hipEventRecord(pend->done, c->stream);
@@ -1770,7 +1697,6 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
         const unsigned long long n_cand = cand_static + sc.h_counters[0], n_hits = sc.h_counters[1];
         if (n_cand <= sc.cand_cap && n_hits <= sc.hit_cap && n_hits <= n_pred) {
             pwms->pred_margin = std::max(0.04, pwms->pred_margin * 0.9);
-            read_clock();
             finish(n_cand, n_hits, true);
             *out = raw;
             return MS_OK;
@@ -1807,7 +1733,6 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
         const unsigned long long hit_need = n_cand > sc.cand_cap ? std::max<unsigned long long>(n_hits, 2 * n_cand) : n_hits;
         want_hits = std::max<size_t>(sc.hit_cap, (size_t) (hit_need + hit_need / 16 + 1024));
     }
-    read_clock();
 
     if (flags & MS_SCAN_RAW_INTERNAL) {                      // the caller takes the unordered hits from the scratch
         finish(n_cand, n_hits, false);
@@ -1862,7 +1787,6 @@ int ms_result_motif_offsets(const ms_result *r, int64_t *out) {
 
 int ms_result_hits(const ms_result *r, int64_t *seq_idx, int64_t *pos, double *score, int8_t *strand) {
     if (!r) { set_error("NULL argument"); return MS_ERR_INVALID; }
-    if (r->invalid) { set_error("result of a no-emit measurement run (MS_MEASURE=1 MS_PF_NOEMIT=1) holds no hits"); return MS_ERR_INVALID; }
     if (r->counts_only) { set_error("a counts-only result (MS_SCAN_COUNTS_ONLY, a counts-only batch or sweep span of a stream) holds the per-motif region counts and site numbers, no site arrays"); return MS_ERR_INVALID; }
     if (r->n_hits == 0) return MS_OK;
     MS_HIP(hipSetDevice(r->device));
@@ -1880,7 +1804,6 @@ int ms_result_hits(const ms_result *r, int64_t *seq_idx, int64_t *pos, double *s
 int ms_result_hits_host(ms_result *r, const int64_t **seq_idx, const int64_t **pos, const double **score,
                         const int8_t **strand) {
     if (!r) { set_error("NULL argument"); return MS_ERR_INVALID; }
-    if (r->invalid) { set_error("result of a no-emit measurement run (MS_MEASURE=1 MS_PF_NOEMIT=1) holds no hits"); return MS_ERR_INVALID; }
     if (r->counts_only) { set_error("a counts-only result (MS_SCAN_COUNTS_ONLY, a counts-only batch or sweep span of a stream) holds the per-motif region counts and site numbers, no site arrays"); return MS_ERR_INVALID; }
     const size_t n = (size_t) r->n_hits;
     const size_t n_round = (n + 65535) & ~(size_t) 65535;
@@ -1920,7 +1843,6 @@ int ms_result_hits_host(ms_result *r, const int64_t **seq_idx, const int64_t **p
 // coordinate arrays into one word per hit first, so only 16 of the 25 bytes cross the host link.
 int ms_result_hits_packed_host(ms_result *r, const uint64_t **coord, const double **score) {
     if (!r) { set_error("NULL argument"); return MS_ERR_INVALID; }
-    if (r->invalid) { set_error("result of a no-emit measurement run (MS_MEASURE=1 MS_PF_NOEMIT=1) holds no hits"); return MS_ERR_INVALID; }
     if (r->counts_only) { set_error("a counts-only result (MS_SCAN_COUNTS_ONLY, a counts-only batch or sweep span of a stream) holds the per-motif region counts and site numbers, no site arrays"); return MS_ERR_INVALID; }
     if (r->d_coord && r->coord_shift) { set_error("this result holds the 12-byte compact form (MS_STREAM_PACKED12): read it with ms_result_hits_packed12_host"); return MS_ERR_INVALID; }
     const size_t n = (size_t) r->n_hits;
@@ -1982,7 +1904,6 @@ int ms_result_hits_packed_host(ms_result *r, const uint64_t **coord, const doubl
 // produced the words during the scan when the batch fits (copies only here); a result that holds none is packed now if it fits.
 int ms_result_hits_packed12_host(ms_result *r, const uint32_t **coord, const double **score, int32_t *shift_out) {
     if (!r) { set_error("NULL argument"); return MS_ERR_INVALID; }
-    if (r->invalid) { set_error("result of a no-emit measurement run (MS_MEASURE=1 MS_PF_NOEMIT=1) holds no hits"); return MS_ERR_INVALID; }
     if (r->counts_only) { set_error("a counts-only result (MS_SCAN_COUNTS_ONLY, a counts-only batch or sweep span of a stream) holds the per-motif region counts and site numbers, no site arrays"); return MS_ERR_INVALID; }
     if (r->d_coord && !r->coord_shift) { set_error("this result holds the 16-byte compact form (its batch did not fit 31 bits of region index and position): read it with ms_result_hits_packed_host"); return MS_ERR_INVALID; }
     const size_t n = (size_t) r->n_hits;
@@ -2263,7 +2184,6 @@ int sweep_handout_locked(DeviceCtx *c, ms_pwmset *pwms, ms_result *r1, int64_t s
     res->P = pwms->P;
     res->R = n_windows;
     res->stats = r1->stats;
-    res->invalid = r1->invalid;
     res->motif_offsets.assign((size_t) pwms->P + 1, 0);
     ms_result *raw = res.release();
     auto fail2 = [&](int code) { ms_result_free(raw); return fail(code); };

@@ -71,7 +71,7 @@ struct DeviceCtx {
     std::atomic<int> n_streams{0};           // live batch streams on this device
     size_t lds_max = 0;
     bool rc_lds_set = false;                // rescore_carry_kernel's dynamic-LDS attribute raised
-    size_t lds_set[128] = {};               // dynamic-LDS attribute already raised to this, per kernel variant (+64: measurement instantiation)
+    size_t lds_set[3] = {};                 // dynamic-LDS attribute already raised to this, per pre-filter kernel (parked, dense, wide)
     Scratch sc;
     std::mutex mu;               // one scan at a time per device (shared scratch)
     // the pending-scan slots (events + pinned counter words) of batch streams that have ended, for the next stream on this device: a pass that
@@ -214,7 +214,6 @@ struct ms_result {
     int64_t n_hits = 0;
     bool deduped = false;
     int raw_gbits = 0, raw_pbits = 0;                 // MS_SCAN_RAW_INTERNAL: layout of the unordered hit keys left in the device scratch
-    bool invalid = false;                             // a no-emit measurement run (MS_MEASURE=1 MS_PF_NOEMIT=1): stage times only, no hits
     bool counts_only = false;                         // a sweep span of a counts-only stream: per-motif window counts and the number of sites, NO site arrays
     void *block = nullptr;                            // one device block holding everything below
     size_t block_bytes = 0;
@@ -270,7 +269,6 @@ struct PendingScan {
     unsigned long long *h_counters = nullptr;   // pinned, 8 words
     int64_t *h_offsets = nullptr;               // pinned: the queued scan's per-motif offsets land here, in stream order, in front of `done`
     size_t h_offsets_cap = 0;                   // (words; grown to P + 1)
-    bool offsets_queued = false;                // (false only under MS_MEASURE=1 MS_OFFSETS_BLOCKING=1: round 5's blocking fetch in scan_complete, for A/B runs)
     size_t cand_cap = 0, hit_cap = 0;           // the scratch capacities at queue time
     bool active = false;
     ms_result *raw = nullptr;

@@ -13,7 +13,6 @@ constexpr int kPfStageWords = 24;            // per wave: the current pass's cod
 constexpr size_t kPfStageBytes = (size_t) (kPfThreads / 64) * kPfStageWords * sizeof(uint32_t);
 // per wave: the lanes that hold a candidate park their 16 result registers here; the flag words are decoded later, one parked entry
 // per lane (ms_kernels.hip, "candidate hand-off")
-constexpr int kPfClkWords = 2 + kMaxClasses;
 constexpr int kRareCapMin = 16;              // entries per wave: whatever LDS the tile's tables leave, between these two (PfArgs::rare_cap)
 constexpr int kRareCapMax = 64;              // (a wave has 64 lanes: an event never needs more)
 constexpr int kRareEntryWords = 12;          // the flag bytes of the 16 result registers (8 words for paired rows, 4 for plain ones) + {position low word, position high bits | group << 8 | paired << 31} at byte 32 + 2 spare: 48 bytes (ms_kernels.hip, park_store)
@@ -83,9 +82,6 @@ struct PfArgs {
     uint32_t cand_block;      // >= 64
     uint64_t cand_static;     // slots [0, cand_static) are the launch's waves' own first blocks (wave w: [w, w + 1) * cand_block)
     int skip_alln;            // != 0: no motif of the plan reports a window made of non-ACGT bases only: such windows are dropped unseen
-    int no_emit;              // measurement only (MEAS instantiations): run the filter, drop the candidates
-    int cls_clk;              // measurement only: also time the classes (MS_PF_CLOCK=2: the stamps themselves cost a few per cent)
-    unsigned long long *clk;  // measurement only: per block kPfClkWords words {shader cycles, 100 MHz ticks, wave 0's cycles inside each class}, or nullptr
     unsigned int *chunk_counter;   // [LDS tiles][kPfCounters] words 64 bytes apart, zeroed: the units behind the waves' own first ones
     int use_counters;              // 0: a small input, one even unit per wave and no atomics
     int wave_passes;               // per-wave hand-out: passes of 64 window starts a wave takes per atomic (scan_locked sizes it)
@@ -93,8 +89,8 @@ struct PfArgs {
 
 
 int launch_pack(const uint8_t *ascii, int64_t n_bases, uint32_t *codes, uint32_t *nmask, hipStream_t st);
-int prefilter_set_lds(bool wide, bool meas, bool dense, size_t bytes, int floor_ = 0);
-int launch_prefilter(const PfArgs &A, bool wide, bool meas, bool dense, int blocks_per_tile, int n_tiles, size_t lds_bytes, hipStream_t st, int floor_ = 0);
+int prefilter_set_lds(bool wide, bool dense, size_t bytes);
+int launch_prefilter(const PfArgs &A, bool wide, bool dense, int blocks_per_tile, int n_tiles, size_t lds_bytes, hipStream_t st);
 int launch_exact_all(const DevSeq &S, const DevPwm &Pw, const int32_t *motifs, int32_t n_motifs, int strand_mask,
                      const HitOut &H, hipStream_t st, int max_width);
 // the same for long lists: chunks of the list in motif order, the window carried along (rescore_carry_kernel); one 1024-thread block per CU

@@ -360,7 +360,7 @@ struct PfLive {                 // which of the lane's two windows lie inside th
     unsigned long long m0, m1;
 };
 __device__ __forceinline__ bool park_both(MfWave &W, PfResume &R, const f32x16 &c0, const f32x16 &c1, const PfLive &L, bool cand0, bool cand1, int64_t g0,
-                                          int32_t group, uint32_t paired, bool no_stores = false) {      // no_stores: measurement only (MS_PF_NOEMIT=5)
+                                          int32_t group, uint32_t paired) {
     // (the two conditions' masks ANDed as masks: a ballot of `live && cand` turns the AND into a register of 0 / 1 and compares that again --
     // four vector instructions per event, found in the ISA in round 5)
     const unsigned long long m0 = __builtin_amdgcn_ballot_w64(cand0) & L.m0, m1 = __builtin_amdgcn_ballot_w64(cand1) & L.m1;
@@ -371,8 +371,8 @@ __device__ __forceinline__ bool park_both(MfWave &W, PfResume &R, const f32x16 &
     const uint32_t rank0 = __builtin_amdgcn_mbcnt_hi((uint32_t) (m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m0, 0u));
     const uint32_t rank1 = __builtin_amdgcn_mbcnt_hi((uint32_t) (m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m1, n0));
     const uint32_t hi = (uint32_t) ((uint64_t) g0 >> 32) | ((uint32_t) group << 8) | (paired << 31);     // (g0 + 32 never carries into bit 32: g0 < 2^34 is a multiple-of-64 base plus lane & 31)
-    if (hit0 && !no_stores) park_store(W.rq + __umul24(W.rq_n + rank0, (uint32_t) (kRareEntryWords * 4)), c0, paired, (uint32_t) g0, hi);
-    if (hit1 && !no_stores) park_store(W.rq + __umul24(W.rq_n + rank1, (uint32_t) (kRareEntryWords * 4)), c1, paired, (uint32_t) g0 + 32u, hi);
+    if (hit0) park_store(W.rq + __umul24(W.rq_n + rank0, (uint32_t) (kRareEntryWords * 4)), c0, paired, (uint32_t) g0, hi);
+    if (hit1) park_store(W.rq + __umul24(W.rq_n + rank1, (uint32_t) (kRareEntryWords * 4)), c1, paired, (uint32_t) g0 + 32u, hi);
     W.rq_n += n0 + n1;
     return false;
 }
@@ -484,41 +484,13 @@ __device__ __forceinline__ uint32_t staged_nw(const uint32_t *stg, uint32_t r, i
     return __builtin_amdgcn_alignbit(stg[9 + i], stg[8 + i], r);
 }
 
-// The matrix work of a row tile of TWO blocks, by name (round 4).  Such a tile lies in LDS lane-major, 48 bytes per lane (ms_internal.h,
-// f6_word_off): three 16-byte reads land in TWELVE CONSECUTIVE registers, of which the first six are the block-0 operand and the last
-// six the block-1 operand.  hipcc cannot place two 6-register operands on one run (its operands are separate 8-wide values) and moved
-// four registers per row tile into place: 76 of a pass's ~940 vector instructions (profiles/r04_isa_account.md).  The reads are
+// The matrix work of a row tile of TWO blocks.  Such a tile lies in LDS lane-major, 48 bytes per lane (ms_internal.h, f6_word_off): three
+// 16-byte reads, of which the first six registers are the block-0 operand and the last six the block-1 operand.  The reads are
 // ds_read_b128 because the LDS array is this kernel's second-busiest unit (SQ_LDS_IDX_ACTIVE ~70 % of the CU's cycles): the same 48
 // bytes per lane as three strided pair reads (ds_read2st64_b64 on a plane-major tile) take the array 24 cycles instead of 12 -- 16.5-16.6
-// against 17.0 ms per 500 Mbase on one box, six ds_read_b64 16.8 (profiles/r04d_a_reads_ab.log).  Registers v[112:123] are this block's
-// alone (clobbered); the waits are the compiler's own pattern -- `lgkmcnt(1)` before the first operand is needed (its six registers are
-// the first two reads'), `lgkmcnt(0)` before the second's, and the 12 wait states (`s_nop 11`: hipcc's own pattern for this instruction in this binary) an 8-pass matrix instruction needs before a vector
-// instruction reads its result.
-// Round 5: the reads of the NEXT row tile's operand are issued inside the same block, right behind the last matrix instruction (which has
-// read v[118:123] long before LDS data can come back), so that their latency -- a third of a wave's cycles were spent parked at
-// s_waitcnt (SQ_WAIT_ANY, profiles/r05b_pmc_sq1.csv) -- runs beside the 12 wait states, the inspection and the loop branch instead of in
-// front of the next products.  In C++ this was measured twice and lost (a second set of operand registers, moves); here the twelve
-// registers are the same ones: the operand is dead once its instructions have issued.  The registers are an OPERAND of the blocks
-// (`areg`, tied to v[112:123]), not a clobber: the compiler must keep them free between the blocks while the reads are in flight, and
-// nothing but these blocks may touch them -- a_reads_begin starts the first row tile's reads, a_reads_drain waits for the last (unused)
-// ones before the class returns and the registers go back to the compiler.  tests/test_host_cabi.py checks the built code for both.
-// ---- the two builds of the pre-filter (round 6) ----
-// DEFAULT (this macro undefined): NO hand-written blocks.  Row tiles of two blocks go through the same builtins the one-block tiles use (the
-// A operand read per row tile with three ds_read_b128 by the compiler, its own waits, its own register allocation) and the hand-out uses the
-// compiler's atomicAdd.  -DMS_PF_ASM builds the variant library (libmotifscan_amd_asm.so, MS_LIB_VARIANT=asm) WITH the blocks of rounds
-// 4-5 above and below: they pin v[112:123] across compiler-made code and issue the hand-out's atomic behind the compiler's back, and what
-// guards them is csrc/check_isa.py, a mandatory step of that variant's build that reads the code object back.
-// Why the default flipped: measured side by side on two boxes in round 6 (profiles/r06a_bench_c4_noasm.json / _asm_same_box.json,
-// profiles/r06b_e2e_ab_summary.log: kernel 15.72 / 15.72 ms, 15.34 / 15.34, 15.32 / 15.31; p = 1e-3 24.61 / 24.64) the two builds run the
-// pre-filter in the same time -- the kernel is power-limited, and what the blocks saved in rounds 4-5 (register moves,
-// exposed LDS latency) no longer shows -- while the asm form carries a hazard no test can rule out for a future compiler.  Same
-// tables, same results bit for bit (tests/test_gpu_parity.py runs the goldens and configs[1] on both).  ms_build_flags() bit 0 = the blocks are in.
-#ifdef MS_PF_ASM
-constexpr bool kPfAsm = true;
-#else
-constexpr bool kPfAsm = false;
-#endif
-extern "C" int ms_build_flags(void) { return kPfAsm ? 1 : 0; }
+// against 17.0 ms per 500 Mbase on one box, six ds_read_b64 16.8 (profiles/r04d_a_reads_ab.log).  Rounds 4-5 wrote these products and the
+// work hand-out's atomic as hand-written asm blocks; measured side by side in round 6 (profiles/r06b_e2e_ab_summary.log) the compiler's
+// form below runs the pre-filter in the same time, so it is the only one.
 
 // a two-block row tile's operands (lane-major, 48 bytes per lane: ms_internal.h) through ordinary LDS reads
 __device__ __forceinline__ void load_a2(uint32_t pa, i32x8 &a0, i32x8 &a1) {
@@ -544,122 +516,8 @@ __device__ __forceinline__ void plain_product2_intr(const i32x8 &a0, const i32x8
     c1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a1, b_of(b11), c1, 2, 4, 0, 0, 0, 0);
 }
 
-typedef int i32x12 __attribute__((ext_vector_type(12)));
-__device__ __forceinline__ void a_reads_begin(uint32_t pa, i32x12 &areg) {
-    asm volatile("ds_read_b128 v[112:115], %[pa]\n\t"
-                 "ds_read_b128 v[116:119], %[pa] offset:16\n\t"
-                 "ds_read_b128 v[120:123], %[pa] offset:32"
-                 : "={v[112:123]}"(areg) : [pa] "v"(pa) : "memory");
-}
-__device__ __forceinline__ void a_reads_drain(i32x12 &areg) {
-    asm volatile("s_waitcnt lgkmcnt(0)" : "={v[112:123]}"(areg) : "0"(areg) : "memory");
-}
-// NEXT = byte distance to the next row tile's operand (the ds_read offset field: 16 bits)
-// The single-pass form (the kernels WITH wide classes keep it): the row tile's reads, waits and products in one block, v[112:123] clobbered
-// (the compiler may use them between the blocks: nothing is in flight there).
-__device__ __forceinline__ void pair_product2_asm(uint32_t pa, const i32x4 &b00, const i32x4 &b10, const i32x4 &b01, const i32x4 &b11, int scale0, int scale1,
-                                                  f32x16 &c0, f32x16 &c1) {
-    const int one = 127;
-    asm volatile("ds_read_b128 v[112:115], %[pa]\n\t"
-                 "ds_read_b128 v[116:119], %[pa] offset:16\n\t"
-                 "ds_read_b128 v[120:123], %[pa] offset:32\n\t"
-                 "s_waitcnt lgkmcnt(1)\n\t"
-                 "v_mfma_scale_f32_32x32x64_f8f6f4 %[c0], v[112:117], %[b00], 4.0, %[s0], %[s1] op_sel_hi:[0,0,0] cbsz:2 blgp:4\n\t"
-                 "v_mfma_scale_f32_32x32x64_f8f6f4 %[c1], v[112:117], %[b10], 2.0, %[s0m], %[s1] op_sel_hi:[0,0,0] cbsz:2 blgp:4\n\t"
-                 "s_waitcnt lgkmcnt(0)\n\t"
-                 "v_mfma_scale_f32_32x32x64_f8f6f4 %[c0], v[118:123], %[b01], %[c0], %[s0], %[s1] op_sel_hi:[0,0,0] cbsz:2 blgp:4\n\t"
-                 "v_mfma_scale_f32_32x32x64_f8f6f4 %[c1], v[118:123], %[b11], %[c1], %[s0m], %[s1] op_sel_hi:[0,0,0] cbsz:2 blgp:4\n\t"
-                 "s_nop 11"
-                 : [c0] "=&v"(c0), [c1] "=&v"(c1)
-                 : [pa] "v"(pa), [b00] "v"(b00), [b10] "v"(b10), [b01] "v"(b01), [b11] "v"(b11), [s0] "v"(scale0), [s0m] "v"(scale1), [s1] "v"(one)
-                 : "v112", "v113", "v114", "v115", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "memory");
-}
-// ... and of plain rows: accumulators from 0, the instruction WITHOUT block scales (the scaled form is two instructions, v_mfma_ld_scale_b32 + the
-// product, 16 bytes of code and two more register reads, for a scale of 2^0: -0.15 ms per 500 Mbase, profiles/r05_double_pass.log)
-__device__ __forceinline__ void plain_product2_asm(uint32_t pa, const i32x4 &b00, const i32x4 &b10, const i32x4 &b01, const i32x4 &b11, f32x16 &c0, f32x16 &c1) {
-    asm volatile("ds_read_b128 v[112:115], %[pa]\n\t"
-                 "ds_read_b128 v[116:119], %[pa] offset:16\n\t"
-                 "ds_read_b128 v[120:123], %[pa] offset:32\n\t"
-                 "s_waitcnt lgkmcnt(1)\n\t"
-                 "v_mfma_f32_32x32x64_f8f6f4 %[c0], v[112:117], %[b00], 0 cbsz:2 blgp:4\n\t"
-                 "v_mfma_f32_32x32x64_f8f6f4 %[c1], v[112:117], %[b10], 0 cbsz:2 blgp:4\n\t"
-                 "s_waitcnt lgkmcnt(0)\n\t"
-                 "v_mfma_f32_32x32x64_f8f6f4 %[c0], v[118:123], %[b01], %[c0] cbsz:2 blgp:4\n\t"
-                 "v_mfma_f32_32x32x64_f8f6f4 %[c1], v[118:123], %[b11], %[c1] cbsz:2 blgp:4\n\t"
-                 "s_nop 11"
-                 : [c0] "=&v"(c0), [c1] "=&v"(c1)
-                 : [pa] "v"(pa), [b00] "v"(b00), [b10] "v"(b10), [b01] "v"(b01), [b11] "v"(b11)
-                 : "v112", "v113", "v114", "v115", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", "memory");
-}
-
-// ---- the double pass (kernels without wide classes, round 5) ----
-// A row tile's operand is read ONCE for 128 window starts: block a multiplies it with the B operands of the windows from pass0 and from
-// pass0 + 32, the results are inspected, block b multiplies the SAME registers with those of pass0 + 64 and pass0 + 96 and then starts the
-// next row tile's reads.  Why: the pre-filter is power-limited (tools/power_probe.py: ~1240 W of the board's 1400 W over a scan loop, the
-// shader clock at 2.25 instead of 2.40 GHz), and with the operand reads of the two-block paired row tiles taken out the SAME cycle count ran
-// at 2343 instead of 2188 MHz (profiles/r05_double_pass.log): the LDS reads cost clock, not cycles.  Half the reads, half the row-tile loop
-// trips.  The accumulators are the same 32 registers for both halves.
-__device__ __forceinline__ void pair_product2a_asm(i32x12 &areg, const i32x4 &b00, const i32x4 &b10, const i32x4 &b01, const i32x4 &b11, int scale0, int scale1,
-                                                   f32x16 &c0, f32x16 &c1) {
-    const int one = 127;
-    asm volatile("s_waitcnt lgkmcnt(1)\n\t"
-                 "v_mfma_scale_f32_32x32x64_f8f6f4 %[c0], v[112:117], %[b00], 4.0, %[s0], %[s1] op_sel_hi:[0,0,0] cbsz:2 blgp:4\n\t"
-                 "v_mfma_scale_f32_32x32x64_f8f6f4 %[c1], v[112:117], %[b10], 2.0, %[s0m], %[s1] op_sel_hi:[0,0,0] cbsz:2 blgp:4\n\t"
-                 "s_waitcnt lgkmcnt(0)\n\t"
-                 "v_mfma_scale_f32_32x32x64_f8f6f4 %[c0], v[118:123], %[b01], %[c0], %[s0], %[s1] op_sel_hi:[0,0,0] cbsz:2 blgp:4\n\t"
-                 "v_mfma_scale_f32_32x32x64_f8f6f4 %[c1], v[118:123], %[b11], %[c1], %[s0m], %[s1] op_sel_hi:[0,0,0] cbsz:2 blgp:4\n\t"
-                 "s_nop 11"
-                 : [c0] "=&v"(c0), [c1] "=&v"(c1), "={v[112:123]}"(areg)
-                 : [b00] "v"(b00), [b10] "v"(b10), [b01] "v"(b01), [b11] "v"(b11), [s0] "v"(scale0), [s0m] "v"(scale1), [s1] "v"(one), "2"(areg)
-                 : "memory");
-}
-template <int NEXT>
-__device__ __forceinline__ void pair_product2b_asm(uint32_t pa, i32x12 &areg, const i32x4 &b00, const i32x4 &b10, const i32x4 &b01, const i32x4 &b11, int scale0, int scale1,
-                                                   f32x16 &c0, f32x16 &c1) {
-    const int one = 127;
-    asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %[c0], v[112:117], %[b00], 4.0, %[s0], %[s1] op_sel_hi:[0,0,0] cbsz:2 blgp:4\n\t"
-                 "v_mfma_scale_f32_32x32x64_f8f6f4 %[c1], v[112:117], %[b10], 2.0, %[s0m], %[s1] op_sel_hi:[0,0,0] cbsz:2 blgp:4\n\t"
-                 "v_mfma_scale_f32_32x32x64_f8f6f4 %[c0], v[118:123], %[b01], %[c0], %[s0], %[s1] op_sel_hi:[0,0,0] cbsz:2 blgp:4\n\t"
-                 "v_mfma_scale_f32_32x32x64_f8f6f4 %[c1], v[118:123], %[b11], %[c1], %[s0m], %[s1] op_sel_hi:[0,0,0] cbsz:2 blgp:4\n\t"
-                 "ds_read_b128 v[112:115], %[pa] offset:%[n0]\n\t"
-                 "ds_read_b128 v[116:119], %[pa] offset:%[n1]\n\t"
-                 "ds_read_b128 v[120:123], %[pa] offset:%[n2]\n\t"
-                 "s_nop 11"
-                 : [c0] "=&v"(c0), [c1] "=&v"(c1), "={v[112:123]}"(areg)
-                 : [pa] "v"(pa), [b00] "v"(b00), [b10] "v"(b10), [b01] "v"(b01), [b11] "v"(b11), [s0] "v"(scale0), [s0m] "v"(scale1), [s1] "v"(one), "2"(areg),
-                   [n0] "n"(NEXT), [n1] "n"(NEXT + 16), [n2] "n"(NEXT + 32)
-                 : "memory");
-}
-__device__ __forceinline__ void plain_product2a_asm(i32x12 &areg, const i32x4 &b00, const i32x4 &b10, const i32x4 &b01, const i32x4 &b11, f32x16 &c0, f32x16 &c1) {
-    asm volatile("s_waitcnt lgkmcnt(1)\n\t"
-                 "v_mfma_f32_32x32x64_f8f6f4 %[c0], v[112:117], %[b00], 0 cbsz:2 blgp:4\n\t"
-                 "v_mfma_f32_32x32x64_f8f6f4 %[c1], v[112:117], %[b10], 0 cbsz:2 blgp:4\n\t"
-                 "s_waitcnt lgkmcnt(0)\n\t"
-                 "v_mfma_f32_32x32x64_f8f6f4 %[c0], v[118:123], %[b01], %[c0] cbsz:2 blgp:4\n\t"
-                 "v_mfma_f32_32x32x64_f8f6f4 %[c1], v[118:123], %[b11], %[c1] cbsz:2 blgp:4\n\t"
-                 "s_nop 11"
-                 : [c0] "=&v"(c0), [c1] "=&v"(c1), "={v[112:123]}"(areg)
-                 : [b00] "v"(b00), [b10] "v"(b10), [b01] "v"(b01), [b11] "v"(b11), "2"(areg)
-                 : "memory");
-}
-template <int NEXT>
-__device__ __forceinline__ void plain_product2b_asm(uint32_t pa, i32x12 &areg, const i32x4 &b00, const i32x4 &b10, const i32x4 &b01, const i32x4 &b11, f32x16 &c0, f32x16 &c1) {
-    asm volatile("v_mfma_f32_32x32x64_f8f6f4 %[c0], v[112:117], %[b00], 0 cbsz:2 blgp:4\n\t"
-                 "v_mfma_f32_32x32x64_f8f6f4 %[c1], v[112:117], %[b10], 0 cbsz:2 blgp:4\n\t"
-                 "v_mfma_f32_32x32x64_f8f6f4 %[c0], v[118:123], %[b01], %[c0] cbsz:2 blgp:4\n\t"
-                 "v_mfma_f32_32x32x64_f8f6f4 %[c1], v[118:123], %[b11], %[c1] cbsz:2 blgp:4\n\t"
-                 "ds_read_b128 v[112:115], %[pa] offset:%[n0]\n\t"
-                 "ds_read_b128 v[116:119], %[pa] offset:%[n1]\n\t"
-                 "ds_read_b128 v[120:123], %[pa] offset:%[n2]\n\t"
-                 "s_nop 11"
-                 : [c0] "=&v"(c0), [c1] "=&v"(c1), "={v[112:123]}"(areg)
-                 : [pa] "v"(pa), [b00] "v"(b00), [b10] "v"(b10), [b01] "v"(b01), [b11] "v"(b11), "2"(areg),
-                   [n0] "n"(NEXT), [n1] "n"(NEXT + 16), [n2] "n"(NEXT + 32)
-                 : "memory");
-}
-
 // All row tiles of one class of plain rows (NK k-blocks each).
-template <int NK, bool MEAS>
+template <int NK>
 __device__ __forceinline__ void f6_class(const PfArgs &A, MfWave &W, const char *__restrict__ lds, const char *__restrict__ lut,
                                          uint32_t byte_off, int n_row_tiles, int32_t first_group, const PassSeq &Q,
                                          int64_t pass0, const PfLive &L, PfResume &R) {
@@ -718,8 +576,6 @@ __device__ __forceinline__ void f6_class(const PfArgs &A, MfWave &W, const char 
     // 32 accumulators (round 2's two tiles in flight for the narrow classes) costs the whole kernel its registers
     // (ONE loop exit: a class that must leave early -- the parking space ran full inside row tile t: come back to it; or runs low:
     // come back to t + 1 -- sets `back` and ends the loop through its counter, so the hot path is product, inspection, one branch)
-    int n_run = n_row_tiles;
-    if constexpr (MEAS) { if (A.no_emit == 2) n_run = 0; }                          // measurement: the per-pass and per-class set-up alone
     int back = n_row_tiles;
     [[maybe_unused]] uint32_t pa = (uint32_t) (uintptr_t) (__attribute__((address_space(3))) const char *) p;       // the row tile's LDS address
     [[maybe_unused]] i32x4 bq[4];
@@ -727,19 +583,15 @@ __device__ __forceinline__ void f6_class(const PfArgs &A, MfWave &W, const char 
         bq[0] = i32x4{b0[0][0], b0[0][1], b0[0][2], b0[0][3]}; bq[1] = i32x4{b1[0][0], b1[0][1], b1[0][2], b1[0][3]};
         bq[2] = i32x4{b0[1][0], b0[1][1], b0[1][2], b0[1][3]}; bq[3] = i32x4{b1[1][0], b1[1][1], b1[1][2], b1[1][3]};
     }
-    for (int t = R.t; t < n_run; t++, p += kStep, pa += (uint32_t) kStep) {
+    for (int t = R.t; t < n_row_tiles; t++, p += kStep, pa += (uint32_t) kStep) {
         f32x16 c0, c1;
-        if constexpr (NK == 2 && kPfAsm) plain_product2_asm(pa, bq[0], bq[1], bq[2], bq[3], c0, c1);
-        else if constexpr (NK == 2) { i32x8 a0, a1; load_a2(pa, a0, a1); plain_product2_intr(a0, a1, bq[0], bq[1], bq[2], bq[3], c0, c1); }
+        if constexpr (NK == 2) { i32x8 a0, a1; load_a2(pa, a0, a1); plain_product2_intr(a0, a1, bq[0], bq[1], bq[2], bq[3], c0, c1); }
         else product(p, c0, c1);
-        if constexpr (MEAS) { if (A.no_emit == 3) { asm volatile("" : : "v"(c0), "v"(c1)); continue; } }      // measurement: operand reads + products, no inspection
         const uint32_t x0 = all_negative(c0), x1 = all_negative(c1);
-        if (__builtin_expect(__any((int) (x0 & x1) >= 0) && !(MEAS && A.no_emit >= 1 && A.no_emit <= 3), 0)) {
+        if (__builtin_expect(__any((int) (x0 & x1) >= 0), 0)) {
             // rare path (about one row tile in four holds a candidate in some lane): the candidate lanes park their results
-            const bool full = park_both(W, R, c0, c1, L, (int) x0 >= 0, (int) x1 >= 0, pass0 + (lane & 31u), first_group + 2 * t + (int32_t) h, 0u,
-                                        MEAS && A.no_emit == 5);
-            if constexpr (MEAS) { if (A.no_emit >= 4) W.rq_n = 0; }              // measurement: the events run, their entries are dropped (4), nor stored at all (5): no decode
-            if (full || W.rq_n >= W.rq_flush) { back = full ? t : t + 1; t = n_run; }
+            const bool full = park_both(W, R, c0, c1, L, (int) x0 >= 0, (int) x1 >= 0, pass0 + (lane & 31u), first_group + 2 * t + (int32_t) h, 0u);
+            if (full || W.rq_n >= W.rq_flush) { back = full ? t : t + 1; t = n_row_tiles; }
         }
     }
     R.t = back;
@@ -749,7 +601,7 @@ __device__ __forceinline__ void f6_class(const PfArgs &A, MfWave &W, const char 
 // scales 2^-6 / 2^-18), both k-halves of the B operand = the same 8 bases, accumulators started at the inline constant 4.0, the bias
 // column's B slots constant.  A row tile answers for 32 motifs x 2 strands with the 32 result registers that answer for 16 in a
 // plain row tile.
-template <int NK, bool MEAS>
+template <int NK>
 __device__ __forceinline__ void f6_pair_class(const PfArgs &A, MfWave &W, const char *__restrict__ lds, const char *__restrict__ lut,
                                               uint32_t byte_off, int n_row_tiles, int32_t first_group, const PassSeq &Q,
                                               int64_t pass0, const PfLive &L, PfResume &R) {
@@ -800,8 +652,6 @@ __device__ __forceinline__ void f6_pair_class(const PfArgs &A, MfWave &W, const 
             c1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b1[kb], c1, 2, 4, 0, scale1, 0, 127);
         }
     };
-    int n_run = n_row_tiles;
-    if constexpr (MEAS) { if (A.no_emit == 2) n_run = 0; }
     int back = n_row_tiles;                                                         // (one loop exit: see f6_class)
     [[maybe_unused]] uint32_t pa = (uint32_t) (uintptr_t) (__attribute__((address_space(3))) const char *) p;       // the row tile's LDS address
     [[maybe_unused]] i32x4 bq[4];
@@ -809,19 +659,16 @@ __device__ __forceinline__ void f6_pair_class(const PfArgs &A, MfWave &W, const 
         bq[0] = i32x4{b0[0][0], b0[0][1], b0[0][2], b0[0][3]}; bq[1] = i32x4{b1[0][0], b1[0][1], b1[0][2], b1[0][3]};
         bq[2] = i32x4{b0[1][0], b0[1][1], b0[1][2], b0[1][3]}; bq[3] = i32x4{b1[1][0], b1[1][1], b1[1][2], b1[1][3]};
     }
-    for (int t = R.t; t < n_run; t++, p += kStep, pa += (uint32_t) kStep) {
+    for (int t = R.t; t < n_row_tiles; t++, p += kStep, pa += (uint32_t) kStep) {
         f32x16 c0, c1;
-        if constexpr (NK == 2 && kPfAsm) pair_product2_asm(pa, bq[0], bq[1], bq[2], bq[3], scale0, scale1, c0, c1);
-        else if constexpr (NK == 2) { i32x8 a0, a1; load_a2(pa, a0, a1); pair_product2_intr(a0, a1, bq[0], bq[1], bq[2], bq[3], scale0, scale1, cc0, cc1, c0, c1); }
+        if constexpr (NK == 2) { i32x8 a0, a1; load_a2(pa, a0, a1); pair_product2_intr(a0, a1, bq[0], bq[1], bq[2], bq[3], scale0, scale1, cc0, cc1, c0, c1); }
         else product(p, c0, c1);
-        if constexpr (MEAS) { if (A.no_emit == 3) { asm volatile("" : : "v"(c0), "v"(c1)); continue; } }
         const uint32_t x0 = or16(c0), x1 = or16(c1);
-        if (__builtin_expect(__any(((x0 | x1) & kPairMask) != 0u) && !(MEAS && A.no_emit >= 1 && A.no_emit <= 3), 0)) {
+        if (__builtin_expect(__any(((x0 | x1) & kPairMask) != 0u), 0)) {
             // rare path: the candidate lanes park their results (table groups 4 t + 2 h for field X and + 1 for field Y)
             const bool full = park_both(W, R, c0, c1, L, (x0 & kPairMask) != 0u, (x1 & kPairMask) != 0u, pass0 + (lane & 31u),
-                                        first_group + 4 * t + 2 * (int32_t) h, 1u, MEAS && A.no_emit == 5);
-            if constexpr (MEAS) { if (A.no_emit >= 4) W.rq_n = 0; }
-            if (full || W.rq_n >= W.rq_flush) { back = full ? t : t + 1; t = n_run; }
+                                        first_group + 4 * t + 2 * (int32_t) h, 1u);
+            if (full || W.rq_n >= W.rq_flush) { back = full ? t : t + 1; t = n_row_tiles; }
         }
     }
     R.t = back;
@@ -876,23 +723,27 @@ __device__ __forceinline__ void dense_event(const PfArgs &A, PfOut &O, const f32
     }
 }
 
-// ---- classes of a double pass ----
+// ---- classes of a double pass (kernels without wide classes, round 5) ----
+// A row tile's operand is read ONCE for 128 window starts: it is multiplied with the B operands of the windows from pass0 and from
+// pass0 + 32, the results are inspected, then the SAME registers are multiplied with those of pass0 + 64 and pass0 + 96.  Why: the pre-filter is power-limited (tools/power_probe.py: ~1240 W of the board's 1400 W over a scan loop, the
+// shader clock at 2.25 instead of 2.40 GHz), and with the operand reads of the two-block paired row tiles taken out the SAME cycle count ran
+// at 2343 instead of 2188 MHz (profiles/r05_double_pass.log): the LDS reads cost clock, not cycles.  Half the reads, half the row-tile loop
+// trips.  The accumulators are the same 32 registers for both halves.
 struct PfLive2 { PfLive h[2]; };       // the halves of a double pass: windows from pass0 / from pass0 + 64
 
 // What the halves of a row tile share: inspection result -> the candidate lanes park.  Returns true when the parking space ran full
 // inside this half (the class leaves and comes back to row tile t, half s); sets `low` when the space runs low (the class leaves after t).
-template <bool PAIRED, bool MEAS>
-__device__ __forceinline__ bool half_event(const PfArgs &A, MfWave &W, PfResume &R, const f32x16 &c0, const f32x16 &c1, const PfLive &L, uint32_t x0, uint32_t x1,
+template <bool PAIRED>
+__device__ __forceinline__ bool half_event(MfWave &W, PfResume &R, const f32x16 &c0, const f32x16 &c1, const PfLive &L, uint32_t x0, uint32_t x1,
                                            int64_t g0, int32_t group, bool &low) {
     const bool cand0 = PAIRED ? (x0 & kPairMask) != 0u : (int) x0 >= 0, cand1 = PAIRED ? (x1 & kPairMask) != 0u : (int) x1 >= 0;
-    const bool full = park_both(W, R, c0, c1, L, cand0, cand1, g0, group, PAIRED ? 1u : 0u, MEAS && A.no_emit == 5);
-    if constexpr (MEAS) { if (A.no_emit >= 4) W.rq_n = 0; }                       // measurement: the events run, their entries are dropped (4), nor stored at all (5): no decode
+    const bool full = park_both(W, R, c0, c1, L, cand0, cand1, g0, group, PAIRED ? 1u : 0u);
     low = low || W.rq_n >= W.rq_flush;
     return full;
 }
 
 // All row tiles of one class of PAIRED rows against the 128 window starts of a double pass (hw: the wave's one-hot array of the pass).
-template <int NK, bool MEAS, bool DENSE, int FLOOR = 0>
+template <int NK, bool DENSE>
 __device__ __forceinline__ void f6_pair_class2(const PfArgs &A, MfWave &W, PfOut &O, const char *__restrict__ lds, uint32_t byte_off, int n_row_tiles, int32_t first_group,
                                                uint32_t hw, int64_t pass0, const PfLive2 &L, PfResume &R) {
     static_assert(NK == 1 || NK == 2, "paired rows have one or two half-blocks");
@@ -917,71 +768,49 @@ __device__ __forceinline__ void f6_pair_class2(const PfArgs &A, MfWave &W, PfOut
     f32x16 cc0, cc1;
 #pragma unroll
     for (int j = 0; j < 16; j++) { cc0[j] = kPairC; cc1[j] = 0.5f * kPairC; }
-    int n_run = n_row_tiles;
-    if constexpr (MEAS) { if (A.no_emit == 2) n_run = 0; }
-    if constexpr (FLOOR == 4) n_run = 0;                                             // floor instantiation: the per-pass and per-class set-up alone
     int back = n_row_tiles;
     [[maybe_unused]] uint32_t pa = (uint32_t) (uintptr_t) (__attribute__((address_space(3))) const char *) p;
-    [[maybe_unused]] i32x12 areg;
-    if constexpr (NK == 2 && kPfAsm) a_reads_begin(pa, areg);
-    const bool skip_events = MEAS && A.no_emit >= 1 && A.no_emit <= 3;
-    [[maybe_unused]] i32x8 a_fix, a1_fix;                                            // FLOOR 3: ONE operand read per class, the matrix instructions alone in the loop
-    if constexpr (FLOOR == 3) { if constexpr (NK == 2) load_a2(pa, a_fix, a1_fix); else { const int2 w0 = *reinterpret_cast<const int2 *>(p), w1 = *reinterpret_cast<const int2 *>(p + 512), w2 = *reinterpret_cast<const int2 *>(p + 1024); a_fix = i32x8{w0.x, w0.y, w1.x, w1.y, w2.x, w2.y, 0, 0}; a1_fix = a_fix; } }
-    for (int t = R.t; t < n_run; t++, p += kStep, pa += (uint32_t) kStep) {
+    for (int t = R.t; t < n_row_tiles; t++, p += kStep, pa += (uint32_t) kStep) {
         f32x16 c0, c1;
         [[maybe_unused]] i32x8 a, a1;
         bool stop = false, low = false;
-        if constexpr (NK == 2 && kPfAsm) pair_product2a_asm(areg, b[0][0][0], b[0][1][0], b[0][0][1], b[0][1][1], scale0, scale1, c0, c1);
-        else if constexpr (NK == 2) { if constexpr (FLOOR == 3) { a = a_fix; a1 = a1_fix; } else load_a2(pa, a, a1); pair_product2_intr(a, a1, b[0][0][0], b[0][1][0], b[0][0][1], b[0][1][1], scale0, scale1, cc0, cc1, c0, c1); }
+        if constexpr (NK == 2) { load_a2(pa, a, a1); pair_product2_intr(a, a1, b[0][0][0], b[0][1][0], b[0][0][1], b[0][1][1], scale0, scale1, cc0, cc1, c0, c1); }
         else {
-            if constexpr (FLOOR == 3) a = a_fix;
-            else {
-                const int2 w0 = *reinterpret_cast<const int2 *>(p), w1 = *reinterpret_cast<const int2 *>(p + 512), w2 = *reinterpret_cast<const int2 *>(p + 1024);
-                a = i32x8{w0.x, w0.y, w1.x, w1.y, w2.x, w2.y, 0, 0};
-            }
+            const int2 w0 = *reinterpret_cast<const int2 *>(p), w1 = *reinterpret_cast<const int2 *>(p + 512), w2 = *reinterpret_cast<const int2 *>(p + 1024);
+            a = i32x8{w0.x, w0.y, w1.x, w1.y, w2.x, w2.y, 0, 0};
             c0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, i32x8{b[0][0][0][0], b[0][0][0][1], b[0][0][0][2], b[0][0][0][3], 0, 0, 0, 0}, cc0, 2, 4, 0, scale0, 0, 127);
             c1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, i32x8{b[0][1][0][0], b[0][1][0][1], b[0][1][0][2], b[0][1][0][3], 0, 0, 0, 0}, cc1, 2, 4, 0, scale1, 0, 127);
         }
-        if constexpr (MEAS) { if (A.no_emit == 3) asm volatile("" : : "v"(c0), "v"(c1)); }
-        if constexpr (FLOOR >= 2) asm volatile("" : : "v"(c0), "v"(c1));          // floor instantiations (below): no inspection
-        else if constexpr (FLOOR == 1) { const uint32_t x0 = or16(c0), x1 = or16(c1); asm volatile("" : : "s"(__builtin_amdgcn_ballot_w64(((x0 | x1) & kPairMask) != 0u))); }   // inspection, no hand-off
-        else if (R.sub == 0u && !(MEAS && A.no_emit == 3)) {
+        if (R.sub == 0u) {
             const uint32_t x0 = or16(c0), x1 = or16(c1);
-            if (__builtin_expect(__any(((x0 | x1) & kPairMask) != 0u) && !skip_events, DENSE ? 1 : 0)) {
+            if (__builtin_expect(__any(((x0 | x1) & kPairMask) != 0u), DENSE ? 1 : 0)) {
                 if constexpr (DENSE) dense_event<true>(A, O, c0, c1, L.h[0], pass0 + r, first_group + 4 * t + 2 * (int32_t) h);
-                else if (half_event<true, MEAS>(A, W, R, c0, c1, L.h[0], x0, x1, pass0 + r, first_group + 4 * t + 2 * (int32_t) h, low)) { back = t; R.sub = 0u; stop = true; }
+                else if (half_event<true>(W, R, c0, c1, L.h[0], x0, x1, pass0 + r, first_group + 4 * t + 2 * (int32_t) h, low)) { back = t; R.sub = 0u; stop = true; }
             }
         }
         if (!stop) {
-            if constexpr (NK == 2 && kPfAsm) pair_product2b_asm<kStep>(pa, areg, b[1][0][0], b[1][1][0], b[1][0][1], b[1][1][1], scale0, scale1, c0, c1);
-            else if constexpr (NK == 2) pair_product2_intr(a, a1, b[1][0][0], b[1][1][0], b[1][0][1], b[1][1][1], scale0, scale1, cc0, cc1, c0, c1);
+            if constexpr (NK == 2) pair_product2_intr(a, a1, b[1][0][0], b[1][1][0], b[1][0][1], b[1][1][1], scale0, scale1, cc0, cc1, c0, c1);
             else {
                 c0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, i32x8{b[1][0][0][0], b[1][0][0][1], b[1][0][0][2], b[1][0][0][3], 0, 0, 0, 0}, cc0, 2, 4, 0, scale0, 0, 127);
                 c1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, i32x8{b[1][1][0][0], b[1][1][0][1], b[1][1][0][2], b[1][1][0][3], 0, 0, 0, 0}, cc1, 2, 4, 0, scale1, 0, 127);
             }
-            if constexpr (MEAS) { if (A.no_emit == 3) asm volatile("" : : "v"(c0), "v"(c1)); }
-            if constexpr (FLOOR >= 2) asm volatile("" : : "v"(c0), "v"(c1));
-            else if constexpr (FLOOR == 1) { const uint32_t x0 = or16(c0), x1 = or16(c1); asm volatile("" : : "s"(__builtin_amdgcn_ballot_w64(((x0 | x1) & kPairMask) != 0u))); }
-            else if (!(MEAS && A.no_emit == 3)) {
-                const uint32_t x0 = or16(c0), x1 = or16(c1);
-                if (__builtin_expect(__any(((x0 | x1) & kPairMask) != 0u) && !skip_events, DENSE ? 1 : 0)) {
-                    if constexpr (DENSE) dense_event<true>(A, O, c0, c1, L.h[1], pass0 + 64 + r, first_group + 4 * t + 2 * (int32_t) h);
-                    else if (half_event<true, MEAS>(A, W, R, c0, c1, L.h[1], x0, x1, pass0 + 64 + r, first_group + 4 * t + 2 * (int32_t) h, low)) { back = t; R.sub = 1u; stop = true; }
-                }
+            const uint32_t x0 = or16(c0), x1 = or16(c1);
+            if (__builtin_expect(__any(((x0 | x1) & kPairMask) != 0u), DENSE ? 1 : 0)) {
+                if constexpr (DENSE) dense_event<true>(A, O, c0, c1, L.h[1], pass0 + 64 + r, first_group + 4 * t + 2 * (int32_t) h);
+                else if (half_event<true>(W, R, c0, c1, L.h[1], x0, x1, pass0 + 64 + r, first_group + 4 * t + 2 * (int32_t) h, low)) { back = t; R.sub = 1u; stop = true; }
             }
             if (!stop) {
                 R.sub = 0u;
                 if (low) { back = t + 1; stop = true; }
             }
         }
-        if (stop) t = n_run;
+        if (stop) t = n_row_tiles;
     }
-    if constexpr (NK == 2 && kPfAsm) a_reads_drain(areg);
     R.t = back;
 }
 
 // ... and of plain rows (one or two k-blocks)
-template <int NK, bool MEAS, bool DENSE, int FLOOR = 0>
+template <int NK, bool DENSE>
 __device__ __forceinline__ void f6_class2(const PfArgs &A, MfWave &W, PfOut &O, const char *__restrict__ lds, uint32_t byte_off, int n_row_tiles, int32_t first_group,
                                           uint32_t hw, bool any_n, int64_t pass0, const PfLive2 &L, PfResume &R) {
     static_assert(NK == 1 || NK == 2, "the double pass knows row tiles of one or two k-blocks");
@@ -1004,66 +833,44 @@ __device__ __forceinline__ void f6_class2(const PfArgs &A, MfWave &W, PfOut &O, 
             }
     }
     const f32x16 z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int n_run = n_row_tiles;
-    if constexpr (MEAS) { if (A.no_emit == 2) n_run = 0; }
-    if constexpr (FLOOR == 4) n_run = 0;                                             // floor instantiation: the per-pass and per-class set-up alone
     int back = n_row_tiles;
     [[maybe_unused]] uint32_t pa = (uint32_t) (uintptr_t) (__attribute__((address_space(3))) const char *) p;
-    [[maybe_unused]] i32x12 areg;
-    if constexpr (NK == 2 && kPfAsm) a_reads_begin(pa, areg);
-    const bool skip_events = MEAS && A.no_emit >= 1 && A.no_emit <= 3;
-    [[maybe_unused]] i32x8 a_fix, a1_fix;                                            // FLOOR 3: ONE operand read per class, the matrix instructions alone in the loop
-    if constexpr (FLOOR == 3) { if constexpr (NK == 2) load_a2(pa, a_fix, a1_fix); else { const int2 w0 = *reinterpret_cast<const int2 *>(p), w1 = *reinterpret_cast<const int2 *>(p + 512), w2 = *reinterpret_cast<const int2 *>(p + 1024); a_fix = i32x8{w0.x, w0.y, w1.x, w1.y, w2.x, w2.y, 0, 0}; a1_fix = a_fix; } }
-    for (int t = R.t; t < n_run; t++, p += kStep, pa += (uint32_t) kStep) {
+    for (int t = R.t; t < n_row_tiles; t++, p += kStep, pa += (uint32_t) kStep) {
         f32x16 c0, c1;
         [[maybe_unused]] i32x8 a, a1;
         bool stop = false, low = false;
-        if constexpr (NK == 2 && kPfAsm) plain_product2a_asm(areg, b[0][0][0], b[0][1][0], b[0][0][1], b[0][1][1], c0, c1);
-        else if constexpr (NK == 2) { if constexpr (FLOOR == 3) { a = a_fix; a1 = a1_fix; } else load_a2(pa, a, a1); plain_product2_intr(a, a1, b[0][0][0], b[0][1][0], b[0][0][1], b[0][1][1], c0, c1); }
+        if constexpr (NK == 2) { load_a2(pa, a, a1); plain_product2_intr(a, a1, b[0][0][0], b[0][1][0], b[0][0][1], b[0][1][1], c0, c1); }
         else {
-            if constexpr (FLOOR == 3) a = a_fix;
-            else {
-                const int2 w0 = *reinterpret_cast<const int2 *>(p), w1 = *reinterpret_cast<const int2 *>(p + 512), w2 = *reinterpret_cast<const int2 *>(p + 1024);
-                a = i32x8{w0.x, w0.y, w1.x, w1.y, w2.x, w2.y, 0, 0};
-            }
+            const int2 w0 = *reinterpret_cast<const int2 *>(p), w1 = *reinterpret_cast<const int2 *>(p + 512), w2 = *reinterpret_cast<const int2 *>(p + 1024);
+            a = i32x8{w0.x, w0.y, w1.x, w1.y, w2.x, w2.y, 0, 0};
             c0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, i32x8{b[0][0][0][0], b[0][0][0][1], b[0][0][0][2], b[0][0][0][3], 0, 0, 0, 0}, z, 2, 4, 0, 0, 0, 0);
             c1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, i32x8{b[0][1][0][0], b[0][1][0][1], b[0][1][0][2], b[0][1][0][3], 0, 0, 0, 0}, z, 2, 4, 0, 0, 0, 0);
         }
-        if constexpr (MEAS) { if (A.no_emit == 3) asm volatile("" : : "v"(c0), "v"(c1)); }
-        if constexpr (FLOOR >= 2) asm volatile("" : : "v"(c0), "v"(c1));
-        else if constexpr (FLOOR == 1) { const uint32_t x0 = all_negative(c0), x1 = all_negative(c1); asm volatile("" : : "s"(__builtin_amdgcn_ballot_w64((int) (x0 & x1) >= 0))); }
-        else if (R.sub == 0u && !(MEAS && A.no_emit == 3)) {
+        if (R.sub == 0u) {
             const uint32_t x0 = all_negative(c0), x1 = all_negative(c1);
-            if (__builtin_expect(__any((int) (x0 & x1) >= 0) && !skip_events, DENSE ? 1 : 0)) {
+            if (__builtin_expect(__any((int) (x0 & x1) >= 0), DENSE ? 1 : 0)) {
                 if constexpr (DENSE) dense_event<false>(A, O, c0, c1, L.h[0], pass0 + r, first_group + 2 * t + (int32_t) h);
-                else if (half_event<false, MEAS>(A, W, R, c0, c1, L.h[0], x0, x1, pass0 + r, first_group + 2 * t + (int32_t) h, low)) { back = t; R.sub = 0u; stop = true; }
+                else if (half_event<false>(W, R, c0, c1, L.h[0], x0, x1, pass0 + r, first_group + 2 * t + (int32_t) h, low)) { back = t; R.sub = 0u; stop = true; }
             }
         }
         if (!stop) {
-            if constexpr (NK == 2 && kPfAsm) plain_product2b_asm<kStep>(pa, areg, b[1][0][0], b[1][1][0], b[1][0][1], b[1][1][1], c0, c1);
-            else if constexpr (NK == 2) plain_product2_intr(a, a1, b[1][0][0], b[1][1][0], b[1][0][1], b[1][1][1], c0, c1);
+            if constexpr (NK == 2) plain_product2_intr(a, a1, b[1][0][0], b[1][1][0], b[1][0][1], b[1][1][1], c0, c1);
             else {
                 c0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, i32x8{b[1][0][0][0], b[1][0][0][1], b[1][0][0][2], b[1][0][0][3], 0, 0, 0, 0}, z, 2, 4, 0, 0, 0, 0);
                 c1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, i32x8{b[1][1][0][0], b[1][1][0][1], b[1][1][0][2], b[1][1][0][3], 0, 0, 0, 0}, z, 2, 4, 0, 0, 0, 0);
             }
-            if constexpr (MEAS) { if (A.no_emit == 3) asm volatile("" : : "v"(c0), "v"(c1)); }
-            if constexpr (FLOOR >= 2) asm volatile("" : : "v"(c0), "v"(c1));
-            else if constexpr (FLOOR == 1) { const uint32_t x0 = all_negative(c0), x1 = all_negative(c1); asm volatile("" : : "s"(__builtin_amdgcn_ballot_w64((int) (x0 & x1) >= 0))); }
-            else if (!(MEAS && A.no_emit == 3)) {
-                const uint32_t x0 = all_negative(c0), x1 = all_negative(c1);
-                if (__builtin_expect(__any((int) (x0 & x1) >= 0) && !skip_events, DENSE ? 1 : 0)) {
-                    if constexpr (DENSE) dense_event<false>(A, O, c0, c1, L.h[1], pass0 + 64 + r, first_group + 2 * t + (int32_t) h);
-                    else if (half_event<false, MEAS>(A, W, R, c0, c1, L.h[1], x0, x1, pass0 + 64 + r, first_group + 2 * t + (int32_t) h, low)) { back = t; R.sub = 1u; stop = true; }
-                }
+            const uint32_t x0 = all_negative(c0), x1 = all_negative(c1);
+            if (__builtin_expect(__any((int) (x0 & x1) >= 0), DENSE ? 1 : 0)) {
+                if constexpr (DENSE) dense_event<false>(A, O, c0, c1, L.h[1], pass0 + 64 + r, first_group + 2 * t + (int32_t) h);
+                else if (half_event<false>(W, R, c0, c1, L.h[1], x0, x1, pass0 + 64 + r, first_group + 2 * t + (int32_t) h, low)) { back = t; R.sub = 1u; stop = true; }
             }
             if (!stop) {
                 R.sub = 0u;
                 if (low) { back = t + 1; stop = true; }
             }
         }
-        if (stop) t = n_run;
+        if (stop) t = n_row_tiles;
     }
-    if constexpr (NK == 2 && kPfAsm) a_reads_drain(areg);
     R.t = back;
 }
 
@@ -1079,20 +886,15 @@ __device__ __forceinline__ void f6_class2(const PfArgs &A, MfWave &W, PfOut &O, 
 // stream's kernel starts late and simply takes fewer units (profiles/r02_stream_coexistence.log, r02_wave_occupancy_ab.log).
 // MAXNK: 2 = the kernel for plans whose row tiles all have 1 or 2 k-blocks (motifs of up to 31 columns: every JASPAR-like set);
 // 4 = the kernel that also knows row tiles of 3 and 4 k-blocks (its register allocation spills in rare paths).
-// MEAS: the measurement-only instantiation (drop candidates, clock stamps); the product kernel carries neither.
-// (Measured and dropped in rounds 1-2, tools/pf_variants.py history: fetching the next pass's sequence words early, class
+// DENSE: the dense-candidate form (above), for plans without wide classes.
+// (Measured and dropped in rounds 1-2: fetching the next pass's sequence words early, class
 // descriptors in registers, waves walking the classes in rotated order, A operands fetched one row tile ahead (again in round 3, for the
 // one-k-block class only, after tools/ubench/insp_probe.hip modes 6 / 7 promised -7 %: +6 % in the kernel), s_setprio around the
 // matrix instructions, 12 / 20 / 24 waves per CU, 128 windows per wave, a block-wide hand-out behind barriers, one branch per pair
 // of row tiles, a real function call for the rare path.)
-// FLOOR (measurement only, MS_MEASURE=1 MS_PF_FLOOR=n; round 6): compile-time cuts of the PRODUCT kernel -- no run-time switch inside, so what is
-// left runs exactly as it does in the product -- for the floor table of DESIGN.md section 7: 1 = inspection but no hand-off (no event is ever
-// parked), 2 = no inspection either (operand reads + matrix instructions), 3 = the matrix instructions alone (one operand read per class),
-// 4 = set-up only (staging, one-hot array, class loop without row tiles).  Their results are void (ms_result::invalid).
-template <int MAXNK, bool MEAS, bool DENSE = false, int FLOOR = 0>
+template <int MAXNK, bool DENSE>
 __global__ void __launch_bounds__(kPfThreads, 4) prefilter_f6_kernel(const PfArgs A) {
-    static_assert(!DENSE || (MAXNK == 2 && !MEAS), "the dense-candidate form exists for the double-pass product kernel");
-    static_assert(FLOOR == 0 || (MAXNK == 2 && !MEAS && !DENSE), "the floor instantiations are cuts of the double-pass product kernel");
+    static_assert(!DENSE || MAXNK == 2, "the dense-candidate form exists for the double-pass kernel");
     extern __shared__ uint4 lds4[];
     constexpr int NT = kPfThreads;
     const TileDesc *__restrict__ T = A.tiles + blockIdx.y;
@@ -1147,9 +949,6 @@ __global__ void __launch_bounds__(kPfThreads, 4) prefilter_f6_kernel(const PfArg
         O.left = A.cand_block;
     }
     const uint32_t lane = threadIdx.x & 63u, r = lane & 31u;
-    unsigned long long t0 = 0, r0 = 0;
-    unsigned long long cls_cyc[kMaxClasses] = {0, 0, 0, 0, 0, 0};               // measurement only: this wave's cycles inside each class
-    if constexpr (MEAS) { if (A.clk) { t0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); } }
 
     // The sequence words of a pass, staged per wave in LDS: the wave's window starts and the 32 (wide tiles: 64) bases behind the
     // last one span 16 code words and 8 non-ACGT words from pass0 on in a double pass (8 and 4 in a 64-window pass), which lanes
@@ -1215,24 +1014,21 @@ __global__ void __launch_bounds__(kPfThreads, 4) prefilter_f6_kernel(const PfArg
             if (i + 1 < n_classes) { cd4 = read_cd(i + 1); cdp = cls_lds[8 * (i + 1) + 4]; }      // the next class's, while this one runs
             const uint32_t off = cd.base16 * 16u;
             PfResume R{0, 0u, 0u};
-            unsigned long long tc0 = 0;
-            if constexpr (MEAS) { if (A.cls_clk) tc0 = __builtin_amdgcn_s_memtime(); }
             while (R.t < cd.n_row_tiles) {                                        // a class comes back early when the parking space runs low
                 if (cd.paired) {
-                    if (cd.nk == 1) f6_pair_class<1, MEAS>(A, W, lds, lut, off, cd.n_row_tiles, cd.first_group, Q, pass0, L, R);
-                    else f6_pair_class<2, MEAS>(A, W, lds, lut, off, cd.n_row_tiles, cd.first_group, Q, pass0, L, R);
+                    if (cd.nk == 1) f6_pair_class<1>(A, W, lds, lut, off, cd.n_row_tiles, cd.first_group, Q, pass0, L, R);
+                    else f6_pair_class<2>(A, W, lds, lut, off, cd.n_row_tiles, cd.first_group, Q, pass0, L, R);
                 } else {
                     switch (cd.nk) {
-                        case 1: f6_class<1, MEAS>(A, W, lds, lut, off, cd.n_row_tiles, cd.first_group, Q, pass0, L, R); break;
-                        case 2: f6_class<2, MEAS>(A, W, lds, lut, off, cd.n_row_tiles, cd.first_group, Q, pass0, L, R); break;
-                        case 3: if constexpr (MAXNK > 2) f6_class<3, MEAS>(A, W, lds, lut, off, cd.n_row_tiles, cd.first_group, Q, pass0, L, R); else R.t = cd.n_row_tiles; break;
-                        case 4: if constexpr (MAXNK > 2) f6_class<4, MEAS>(A, W, lds, lut, off, cd.n_row_tiles, cd.first_group, Q, pass0, L, R); else R.t = cd.n_row_tiles; break;
+                        case 1: f6_class<1>(A, W, lds, lut, off, cd.n_row_tiles, cd.first_group, Q, pass0, L, R); break;
+                        case 2: f6_class<2>(A, W, lds, lut, off, cd.n_row_tiles, cd.first_group, Q, pass0, L, R); break;
+                        case 3: if constexpr (MAXNK > 2) f6_class<3>(A, W, lds, lut, off, cd.n_row_tiles, cd.first_group, Q, pass0, L, R); else R.t = cd.n_row_tiles; break;
+                        case 4: if constexpr (MAXNK > 2) f6_class<4>(A, W, lds, lut, off, cd.n_row_tiles, cd.first_group, Q, pass0, L, R); else R.t = cd.n_row_tiles; break;
                         default: R.t = cd.n_row_tiles; break;
                     }
                 }
                 if (W.rq_n >= W.rq_flush) { pf_flush(em_lds, rq_lds, W.rq_n); W.rq_n = 0; }
             }
-            if constexpr (MEAS) { if (A.cls_clk) cls_cyc[i] += __builtin_amdgcn_s_memtime() - tc0; }
         }
     };
     auto scan_pass2 = [&](int64_t pass0, bool any_n) {                        // the double pass: 128 window starts of this wave (pass0 ... + 127, wave-uniform) against every class
@@ -1278,18 +1074,15 @@ __global__ void __launch_bounds__(kPfThreads, 4) prefilter_f6_kernel(const PfArg
             if (i + 1 < n_classes) { cd4 = read_cd(i + 1); cdp = cls_lds[8 * (i + 1) + 4]; }      // the next class's, while this one runs
             const uint32_t off = cd.base16 * 16u;
             PfResume R{0, 0u, 0u, 0u};
-            unsigned long long tc0 = 0;
-            if constexpr (MEAS) { if (A.cls_clk) tc0 = __builtin_amdgcn_s_memtime(); }
             while (R.t < cd.n_row_tiles) {                                        // a class comes back early when the parking space runs low
                 if (cd.paired) {
-                    if (cd.nk == 1) f6_pair_class2<1, MEAS, DENSE, FLOOR>(A, W, O, lds, off, cd.n_row_tiles, cd.first_group, hw_lds, pass0, L, R);
-                    else f6_pair_class2<2, MEAS, DENSE, FLOOR>(A, W, O, lds, off, cd.n_row_tiles, cd.first_group, hw_lds, pass0, L, R);
-                } else if (cd.nk == 1) f6_class2<1, MEAS, DENSE, FLOOR>(A, W, O, lds, off, cd.n_row_tiles, cd.first_group, hw_lds, any_n, pass0, L, R);
-                else if (cd.nk == 2) f6_class2<2, MEAS, DENSE, FLOOR>(A, W, O, lds, off, cd.n_row_tiles, cd.first_group, hw_lds, any_n, pass0, L, R);
+                    if (cd.nk == 1) f6_pair_class2<1, DENSE>(A, W, O, lds, off, cd.n_row_tiles, cd.first_group, hw_lds, pass0, L, R);
+                    else f6_pair_class2<2, DENSE>(A, W, O, lds, off, cd.n_row_tiles, cd.first_group, hw_lds, pass0, L, R);
+                } else if (cd.nk == 1) f6_class2<1, DENSE>(A, W, O, lds, off, cd.n_row_tiles, cd.first_group, hw_lds, any_n, pass0, L, R);
+                else if (cd.nk == 2) f6_class2<2, DENSE>(A, W, O, lds, off, cd.n_row_tiles, cd.first_group, hw_lds, any_n, pass0, L, R);
                 else R.t = cd.n_row_tiles;
                 if (W.rq_n >= W.rq_flush) { pf_flush(em_lds, rq_lds, W.rq_n); W.rq_n = 0; }
             }
-            if constexpr (MEAS) { if (A.cls_clk) cls_cyc[i] += __builtin_amdgcn_s_memtime() - tc0; }
         }
     };
     {
@@ -1310,9 +1103,7 @@ __global__ void __launch_bounds__(kPfThreads, 4) prefilter_f6_kernel(const PfArg
         PassWords words = v < units_g ? fetch((v * K + g) * wave_passes) : PassWords{0u, 0u};
         while (v < units_g) {
             uint32_t next = 0xFFFFFFFFu;
-            // the next unit: asked for before this one is scanned, looked at in its last pass.  The instruction by name: hipcc's atomicAdd is
-            // followed at once by s_waitcnt vmcnt(0) (its wave-aggregated form broadcasts the result), which exposed the counter's round
-            // trip once per unit
+            // the next unit: asked for before this one is scanned, looked at in its last pass
             unsigned int u = 0;
             const uint32_t uid = v * K + g;                                       // the unit: window starts [uid, uid + 1) * PW * wave_passes
             const uint32_t p0 = uid * wave_passes;
@@ -1320,23 +1111,12 @@ __global__ void __launch_bounds__(kPfThreads, 4) prefilter_f6_kernel(const PfArg
                 if (lane < 3u * CWP) stg[lane] = lane < 2u * CWP ? words.c : words.n;       // (the wave's LDS operations execute in order: no barrier)
                 [[maybe_unused]] const bool pass_any_n = SH && __any((lane & (2u * NWP - 1u)) < 6u && words.n != 0u);      // (double pass: a non-ACGT base among the 192 staged)
                 // (behind the staging, which waits for every vector-memory operation in flight)
-                // INVARIANT: the compiler believes `u` is ready at once, the value arrives with the atomic's return.  Nothing may read,
-                // copy or spill u's register before a vmcnt(0) wait has retired the atomic: with wave_passes >= 2 that is pass 1's staging wait
-                // (every later copy is then harmless), and pass 0's scan must not touch the register -- checked on the built code object by
-                // tests/test_host_cabi.py::test_prefilter_isa_resources_and_the_atomic_register.  The host never launches wave_passes == 1 with
-                // the counters on (scan_locked refuses it); if it ever did, the compiler's own atomicAdd (waited for at once) takes over.
-                if (j == 0 && dyn && lane == 0) {
-                    if (kPfAsm && wave_passes >= 2) asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(u) : "v"(word), "v"(1u) : "memory");
-                    else u = atomicAdd(word, 1u);                                  // (the default build: the compiler's atomic, waited for where it is used)
-                }
+                if (j == 0 && dyn && lane == 0) u = atomicAdd(word, 1u);
                 // the next pass's words -- of this unit, or the first of the wave's NEXT unit (its number arrived long ago) -- are in
                 // flight while this pass is scanned
                 if (j + 1 < wave_passes) words = fetch(p0 + j + 1);
                 else {
-                    if (dyn) {
-                        if constexpr (kPfAsm) asm volatile("s_waitcnt vmcnt(0)" : "+v"(u) : : "memory");     // (the compiler does not know the atomic is in flight)
-                        next = waves_g + (uint32_t) __builtin_amdgcn_readfirstlane((int) u);
-                    }
+                    if (dyn) next = waves_g + (uint32_t) __builtin_amdgcn_readfirstlane((int) u);
                     if (next < units_g) words = fetch((next * K + g) * wave_passes);
                 }
                 if constexpr (SH) scan_pass2((int64_t) (p0 + j) * 128, pass_any_n);
@@ -1352,15 +1132,6 @@ __global__ void __launch_bounds__(kPfThreads, 4) prefilter_f6_kernel(const PfArg
         for (uint32_t i = 0; i < left; i += 64) {
             const unsigned long long j = base + i + lane;
             if (i + lane < left && j < A.cand_cap) A.cand[j] = 0ULL;
-        }
-    }
-    if constexpr (MEAS) {
-        if (A.clk && threadIdx.x == 0) {
-            const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-            const size_t b = (size_t) blockIdx.y * gridDim.x + blockIdx.x;
-            A.clk[kPfClkWords * b] = t1 - t0;
-            A.clk[kPfClkWords * b + 1] = r1 - r0;
-            for (int i = 0; i < kMaxClasses; i++) A.clk[kPfClkWords * b + 2 + i] = cls_cyc[i];
         }
     }
 }
@@ -2032,26 +1803,21 @@ int launch_pack(const uint8_t *ascii, int64_t n_bases, uint32_t *codes, uint32_t
 }
 
 typedef void (*PfKernel)(const PfArgs);
-static PfKernel pf_kernel(bool wide, bool meas, bool dense, int floor_ = 0) {                  // (dense: only without wide classes and outside the measurement instantiation)
-    if (wide) return meas ? prefilter_f6_kernel<4, true> : prefilter_f6_kernel<4, false>;
-    if (floor_ == 1) return prefilter_f6_kernel<2, false, false, 1>;
-    if (floor_ == 2) return prefilter_f6_kernel<2, false, false, 2>;
-    if (floor_ == 3) return prefilter_f6_kernel<2, false, false, 3>;
-    if (floor_ == 4) return prefilter_f6_kernel<2, false, false, 4>;
-    if (dense && !meas) return prefilter_f6_kernel<2, false, true>;
-    return meas ? prefilter_f6_kernel<2, true> : prefilter_f6_kernel<2, false>;
+static PfKernel pf_kernel(bool wide, bool dense) {                  // (dense: only without wide classes)
+    if (wide) return prefilter_f6_kernel<4, false>;
+    return dense ? prefilter_f6_kernel<2, true> : prefilter_f6_kernel<2, false>;
 }
 
-int prefilter_set_lds(bool wide, bool meas, bool dense, size_t bytes, int floor_) {
-    MS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(pf_kernel(wide, meas, dense, floor_)), hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes));
+int prefilter_set_lds(bool wide, bool dense, size_t bytes) {
+    MS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(pf_kernel(wide, dense)), hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes));
     return MS_OK;
 }
 
 // wide: the plan holds row tiles of 3 or 4 k-blocks; dense: the form that decodes candidates in place (many hits per row tile)
-int launch_prefilter(const PfArgs &A, bool wide, bool meas, bool dense, int blocks_per_tile, int n_tiles, size_t lds_bytes, hipStream_t st, int floor_) {
+int launch_prefilter(const PfArgs &A, bool wide, bool dense, int blocks_per_tile, int n_tiles, size_t lds_bytes, hipStream_t st) {
     const int64_t n_chunks = (A.n_bases + kPfThreads - 1) / kPfThreads;
     if (blocks_per_tile > n_chunks) blocks_per_tile = (int) n_chunks;
-    hipLaunchKernelGGL(pf_kernel(wide, meas, dense, floor_), dim3((unsigned) blocks_per_tile, (unsigned) n_tiles), dim3(kPfThreads), lds_bytes, st, A);
+    hipLaunchKernelGGL(pf_kernel(wide, dense), dim3((unsigned) blocks_per_tile, (unsigned) n_tiles), dim3(kPfThreads), lds_bytes, st, A);
     MS_HIP(hipGetLastError());
     return MS_OK;
 }

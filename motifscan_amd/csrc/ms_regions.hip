@@ -295,7 +295,6 @@ extern "C" int ms_scan_regions_once(const ms_pwmset *pwms_c, const ms_genome *g,
     res->P = pwms->P;
     res->R = n_regions;
     res->stats = r1->stats;
-    res->invalid = r1->invalid;
     res->motif_offsets.assign((size_t) pwms->P + 1, 0);
     ms_result *raw = res.release();
     auto fail2 = [&](int code) { ms_result_free(raw); return fail(code); };

@@ -562,47 +562,30 @@ def _check_isa():
     return mod
 
 
-def test_prefilter_isa_resources_and_the_atomic_register():
-    """The build-time checks on the gfx950 code objects of the pre-filter are a MANDATORY step of
-    the build since round 6 (csrc/check_isa.py, run by the Makefile right after each object is compiled: an object that fails is never
-    linked; the rules are in that file's docstring).  Since round 6 the PRODUCT library holds no hand-written asm blocks at all (same
-    speed, measured side by side: ms_kernels.hip "the two builds"); the blocks of rounds 4-5 live in the variant libmotifscan_amd_asm.so,
-    and the rules they rest on -- operand registers that carry data in flight, the hand-out atomic's register, no scalar loads in the
-    pass body -- guard THAT object.  This test re-runs both checks on the objects the two shipped libraries were linked from, and shows
-    that the rules bite: the product object, which has none of the blocks, fails the asm rules."""
+def test_prefilter_isa_resource_rules():
+    """The build-time check on the gfx950 code object of the pre-filter is a MANDATORY step of
+    the build since round 6 (csrc/check_isa.py, run by the Makefile right after the object is compiled: an object that fails is never
+    linked; the rules are in that file's docstring).  This test re-runs it on the object the shipped library was linked from -- exactly
+    three instantiations, all within the limits -- and shows that the rules bite: the same disassembly fails with one instantiation
+    missing, or with one kernel's vector registers above 128."""
     ci = _check_isa()
     obj = os.path.join(ROOT, "motifscan_amd", "csrc", "ms_kernels.o")
-    obj_asm = os.path.join(ROOT, "motifscan_amd", "csrc", "ms_kernels_asm.o")
     assert os.path.exists(obj), "the build leaves the object in csrc/ (it travels to the GPU box with the library)"
     if not ci.tools_present():
         pytest.skip("no ROCm llvm tools here: the build itself would have refused to link (check_isa.main)")
-    assert _lib.lib().ms_build_flags() & 1 == (1 if _lib.LIB_VARIANT == "asm" else 0)
-    print(ci.check(obj, no_asm=True))
-    with pytest.raises(ci.IsaCheckError):
-        ci.check(obj, no_asm=False)
-    assert os.path.exists(obj_asm) == os.path.exists(os.path.join(ROOT, "motifscan_amd", "libmotifscan_amd_asm.so"))
-    if os.path.exists(obj_asm):                                          # (absent only if this compiler tripped the asm rules: the build said so)
-        print(ci.check(obj_asm, no_asm=False))
-
-
-def test_both_library_variants_export_the_same_cabi():
-    """libmotifscan_amd_asm.so (the variant with the hand-written blocks, csrc/Makefile) is the same library but for the pre-filter's object."""
-    import shutil
-    import subprocess
-    nm = shutil.which("nm")
-    if not nm:
-        pytest.skip("no nm")
-    if not os.path.exists(os.path.join(ROOT, "motifscan_amd", "libmotifscan_amd_asm.so")):
-        pytest.skip("the asm variant was not built (its object failed the ISA check)")
-    sets = []
-    for name in ("libmotifscan_amd.so", "libmotifscan_amd_asm.so"):
-        out = subprocess.run([nm, "-D", "--defined-only", os.path.join(ROOT, "motifscan_amd", name)], capture_output=True, text=True, check=True).stdout
-        sets.append({l.split()[-1] for l in out.splitlines() if " T " in l and l.split()[-1].startswith("ms_")})
-    assert sets[0] == sets[1] and "ms_build_flags" in sets[0]
-    for variant, flag, so in (("", "0", "libmotifscan_amd.so"), ("asm", "1", "libmotifscan_amd_asm.so")):
-        out = subprocess.run([sys.executable, "-c", "from motifscan_amd import _lib; print(_lib.lib().ms_build_flags(), _lib.LIB_PATH)"],
-                             env=dict(os.environ, MS_LIB_VARIANT=variant, PYTHONPATH=ROOT), capture_output=True, text=True, check=True).stdout.split()
-        assert out[0] == flag and out[1].endswith(so)
+    funcs, notes = ci.disassemble(obj)
+    summary = ci.check_code(funcs, notes)
+    print(summary)
+    kernels = [k for k in funcs if "prefilter_f6_kernel" in k]
+    assert len(kernels) == 3 and summary.count(" vgprs, ") == 3
+    with pytest.raises(ci.IsaCheckError, match="expected 3 instantiations"):
+        ci.check_code({k: v for k, v in funcs.items() if k != kernels[0]}, notes)
+    at = notes.index(".name:           " + kernels[0] + "\n")
+    end = notes.index(".wavefront_size", at)
+    over = notes[:at] + re.sub(r"(\.vgpr_count:\s+)\d+", r"\g<1>129", notes[at:end], count=1) + notes[end:]
+    assert over != notes
+    with pytest.raises(ci.IsaCheckError, match="more than 128 vector registers"):
+        ci.check_code(funcs, over)
 
 
 def test_measurement_switches_need_the_explicit_opt_in(monkeypatch):

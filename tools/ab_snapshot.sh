@@ -9,5 +9,5 @@ rm -rf "$d"; mkdir -p "$d/motifscan_amd" "$d/tools" "$d/include"
 cp "$root"/motifscan_amd/*.py "$root"/motifscan_amd/libmotifscan_amd.so "$d/motifscan_amd/"
 cp -r "$root/motifscan_amd/data" "$d/motifscan_amd/"
 cp "$root"/include/*.h "$d/include/"
-cp "$root/tools/ab_full.py" "$root/tools/pf_account.py" "$d/tools/"
+cp "$root/tools/ab_full.py" "$d/tools/"
 echo "snapshot $name: $(sha256sum "$root/motifscan_amd/csrc/ms_kernels.hip" | cut -c1-16)"

@@ -32,9 +32,6 @@ $T python bench.py --no-cpu-baseline --no-api --no-scale-projection --batch-regi
 $T python bench.py --no-cpu-baseline --no-end-to-end --extra-widths 33,40 > $OUT/bench_c4_plus_w33_w40.json 2> /dev/null
 # what the all-fp64 kernel costs (the fence of VERDICT r5 #8): two motifs the pre-filter cannot take, on one GPU's shard of an 8-GPU run
 $T python bench.py --no-cpu-baseline --no-end-to-end --no-api --extra-widths 70,90 --regions-per-set 125000 --steps 3 > $OUT/bench_c4shard_plus_w70_w90.json 2> $OUT/bench_c4shard_plus_w70_w90.err
-$T python tools/pf_account.py 1e-4 full 2>&1 | grep -v amdgpu.ids > $OUT/pf_account.log
-$T python tools/pf_account.py 1e-3 2>&1 | grep -v amdgpu.ids >> $OUT/pf_account.log
-$T python tools/pf_class_clock.py 3 1e-4 2>&1 | grep -v amdgpu.ids > $OUT/class_clock.log
 $T python tools/e2e_bounds.py 2>&1 | grep -v amdgpu.ids > $OUT/e2e_bounds.log
 for i in 1 2; do
 $T python tools/ab_full.py 3 1e-4 2>&1 | grep Mbase | sed "s/^/this build: /" >> $OUT/full_size_stage_times.log
@@ -67,12 +64,7 @@ rm -rf $P
 # rewritten from the copied-back summaries by tools/pmc_traffic_update.py)
 python3 tools/pmc_traffic_update.py c4 $OUT/pmc_fetch.csv $OUT/pmc_write.csv "evidence round $TAG" > /dev/null
 $T python bench.py > $OUT/bench_c4_with_traffic.json 2> /dev/null
-# round 6: the floor table of the pre-filter, the asm variant beside the product, the 8-rank end-to-end leg on this one GPU
-$T python tools/pf_floor.py 1e-4 3 > $OUT/pf_floor.log 2>&1
-for i in 1 2; do
-MS_LIB_VARIANT=asm $T python bench.py --no-cpu-baseline --no-end-to-end --no-api --no-scale-projection > $OUT/bench_c4_asm_variant_$i.json 2> /dev/null
-$T python bench.py --no-cpu-baseline --no-end-to-end --no-api --no-scale-projection > $OUT/bench_c4_product_same_box_$i.json 2> /dev/null
-done
+# round 6: the 8-rank end-to-end leg on this one GPU
 timeout 300 ./tools/ubench/shape_probe16.bin > $OUT/shape_probe16.log 2>&1
 $T python tools/e2e_cli_probe.py 2>&1 | grep -v amdgpu.ids > $OUT/e2e_cli_probe.log
 bash tools/r06_ranks_one_gpu.sh evidence_$TAG/ranks > $OUT/ranks_one_gpu_summary.log 2>&1
