@@ -53,6 +53,11 @@
  *                         host-streamed window sweep (BASELINE configs[4]: cli/scan.py:43-48 over a whole genome)
  *   ms_sweep_spans        the windows of a fixed-stride sweep over all chromosomes (Scanner._extract_seq per window,
  *                         scanner.py:71-87) cut into spans of bounded size, each with the global index of its first window
+ *   ms_result_site_histogram  the distance histogram of plot_motif_sites_dist     plot.py:43-92 (the loop at :65-70)
+ *                         (site centre - summit in bins of 10 bp; the counts only: the / n and the smoothing stay on the host)
+ *   ms_result_rank_profile    the ranked fold-change profile of plot_motif_sites_enrich   plot.py:95-153 (the loop at :133-141)
+ *                         and its smoothing, smooth() plot.py:34-40
+ *   ms_result_from_hits   a result made of hit arrays that are on the host (the sites of a view that no longer owns its result)
  */
 #ifndef MOTIFSCAN_AMD_H
 #define MOTIFSCAN_AMD_H
@@ -306,6 +311,32 @@ int ms_score_ranks(const ms_pwmset *pwms, const ms_seqset *seqs, int strand_mask
 int ms_dedup_hits(const int64_t *motif_offsets, int32_t n_pwms, const int32_t *widths,
                   const int64_t *seq_idx, const int64_t *pos, const double *score,
                   const int8_t *strand, uint8_t *keep);
+
+/* ---- plot data (motifscan scan --plot-dist: plot.py:43-153) -------------------------------- */
+/* A result made of hit arrays in ms_result order (per motif: region, position, '+' (1) before '-' (2)), uploaded to the calling
+ * thread's device: what the plot data below read when the hits are no longer on the device.  motif_offsets[P+1]; every seq_idx must
+ * lie in [0, n_regions) (MS_ERR_INVALID otherwise).  The per-motif region counts are made on the host. */
+int ms_result_from_hits(int32_t n_pwms, int64_t n_regions, const int64_t *motif_offsets, const int64_t *seq_idx, const int64_t *pos,
+                        const double *score, const int8_t *strand, ms_result **out);
+/* plot.py:60-70: for motifs m0 <= m < m1, the histogram of d = pos + W/2 - summit_rel[seq_idx] over the result's sites (which are counted as
+ * they are: a scan with remove_dup de-duplicates first, ms_result_dedup) in the bins of np.arange(-extend - 5, extend + 6, 10) --
+ * edge[i] <= d < edge[i + 1], the last bin closed, everything else dropped; n_bins = ceil((2 * extend + 11) / 10) - 1.  The bin is taken
+ * from 2d = 2 * (pos - summit_rel) + W in integers, so the counts are exact.  summit_rel[R] = summit - sequence start, host.
+ * counts: host [(m1 - m0) x n_bins]; n_sites: host [m1 - m0], all sites of the motif (len(distances), in range or not).
+ * MS_ERR_INVALID on a counts-only result, as the other hit accessors. */
+int ms_result_site_histogram(const ms_result *res, const ms_pwmset *pwms, const int64_t *summit_rel, int64_t extend, int32_t m0, int32_t m1,
+                             int64_t *counts, int64_t *n_sites);
+#define MS_PROFILE_UNSMOOTHED 1   /* ms_result_rank_profile: the fold changes as plot.py:141 appends them, without smooth() */
+/* plot.py:120-142 for motifs m0 <= m < m1 of a result over R regions: rank_order[R] (host) = the region at each rank (a permutation of
+ * [0, R): plot.py:121-122's stable descending sort, made by the caller); f = R / 100; for every rank idx, head = max(0, idx - f),
+ * tail = min(idx + f, R), ratio_input = (ranks in [head, tail) whose region holds >= 1 site) / (tail - head), and
+ * out = ratio_input / ratio_control[m - m0] -- two IEEE fp64 divisions in this order.  ratio_control [m1 - m0] must be > 0 (the caller
+ * applies plot.py:130-132's 0 -> 1).  Unless MS_PROFILE_UNSMOOTHED, each row is then smoothed as plot.py:34-40 does for R > 11: reflected
+ * at both ends, out[i] = sum_j kernel[j] * ratio[i - 5 + j], kernel = (w / w.sum()) reversed, w = np.hanning(11) (host, 11 doubles).
+ * out: [(m1 - m0) x R] doubles, host or device memory of the result's device.  MS_ERR_INVALID for R < 100 (plot.py:138 divides by zero
+ * there) and on a counts-only result. */
+int ms_result_rank_profile(const ms_result *res, const int64_t *rank_order, const double *ratio_control, const double *kernel, int32_t m0,
+                           int32_t m1, int flags, double *out);
 
 #ifdef __cplusplus
 }

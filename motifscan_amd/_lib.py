@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libmotifscan_amd.so")
 MS_OK, MS_ERR_INVALID, MS_ERR_NOMEM, MS_ERR_RUNTIME = 0, 1, 2, 3
 MS_SCAN_DEFAULT, MS_SCAN_EXACT_ONLY, MS_SCAN_COUNTS_ONLY = 0, 1, 2
 MS_STREAM_DEDUP, MS_STREAM_NO_HITS, MS_STREAM_EXACT_ONLY, MS_STREAM_PACKED, MS_STREAM_HOST_PACK, MS_STREAM_PACKED12 = 1, 2, 4, 8, 16, 32
+MS_PROFILE_UNSMOOTHED = 1
 
 
 class ScanStats(ctypes.Structure):
@@ -141,6 +142,9 @@ def lib():
         "ms_result_dedup": (c_int, [vp, vp]),
         "ms_result_site_tables": (c_int, [vp, pi32, pd]),
         "ms_result_free": (None, [vp]),
+        "ms_result_from_hits": (c_int, [c_i32, c_i64, pi64, pi64, pi64, pd, pi8, pvp]),
+        "ms_result_site_histogram": (c_int, [vp, vp, pi64, c_i64, c_i32, c_i32, pi64, pi64]),
+        "ms_result_rank_profile": (c_int, [vp, pi64, pd, pd, c_i32, c_i32, c_int, vp]),
         "ms_score": (c_int, [vp, vp, c_int, pd]),
         "ms_score_ranks": (c_int, [vp, vp, c_int, pi64, c_i32, pd]),
         "ms_dedup_hits": (c_int, [pi64, c_i32, pi32, pi64, pi64, pd, pi8, pu8]),
@@ -581,12 +585,67 @@ class ScanResult:
         check(lib().ms_result_stats(self.h, ctypes.byref(s)))
         return s.as_dict()
 
+    def site_histogram(self, pwms, summit_rel, extend, m0=0, m1=None):
+        """plot.py:60-70 on the device (ms_result_site_histogram): (counts int64 [m1 - m0][n_bins], n_sites int64 [m1 - m0]) of the
+        distance site centre - summit in the bins of np.arange(-extend - 5, extend + 6, 10).  summit_rel [R]: summit - sequence start."""
+        m1 = self.n_pwms if m1 is None else int(m1)
+        m0, extend = int(m0), int(extend)
+        summit_rel = np.ascontiguousarray(summit_rel, dtype=np.int64)
+        n_bins = len(np.arange(-extend - 5, extend + 6, 10)) - 1 if extend >= 0 else 0
+        counts = np.zeros((max(m1 - m0, 0), max(n_bins, 0)), dtype=np.int64)
+        n_sites = np.zeros(max(m1 - m0, 0), dtype=np.int64)
+        check(lib().ms_result_site_histogram(self.h, pwms.h, ptr(summit_rel, ctypes.c_int64), extend, m0, m1,
+                                             ptr(counts, ctypes.c_int64), ptr(n_sites, ctypes.c_int64)))
+        return counts, n_sites
+
+    def rank_profile(self, rank_order, ratio_control, kernel=None, m0=0, m1=None, smoothed=True, out=None):
+        """plot.py:120-142 on the device (ms_result_rank_profile): the fold-change profile [m1 - m0][R] over the ranks of rank_order,
+        smoothed with the 11 `kernel` weights unless smoothed=False.  ratio_control [m1 - m0], each > 0.  out: a float64 numpy array
+        of that shape, or None (a new one); the device pointer of a torch tensor may be passed as an int instead (then it is returned)."""
+        m1 = self.n_pwms if m1 is None else int(m1)
+        m0 = int(m0)
+        rank_order = np.ascontiguousarray(rank_order, dtype=np.int64)
+        ratio_control = np.ascontiguousarray(ratio_control, dtype=np.float64)
+        if ratio_control.shape != (max(m1 - m0, 0),):
+            raise ValueError("need one ratio_control per motif of [m0, m1)")
+        k = None if kernel is None else np.ascontiguousarray(kernel, dtype=np.float64)
+        if smoothed and (k is None or k.shape != (11,)):
+            raise ValueError("smoothing needs 11 kernel weights")
+        if isinstance(out, int):
+            dst = out
+        else:
+            if out is None:
+                out = np.empty((max(m1 - m0, 0), len(rank_order)), dtype=np.float64)
+            if out.dtype != np.float64 or out.shape != (max(m1 - m0, 0), len(rank_order)) or not out.flags.c_contiguous:
+                raise ValueError("out must be a C-contiguous float64 array of shape (m1 - m0, R)")
+            dst = out.ctypes.data
+        check(lib().ms_result_rank_profile(self.h, ptr(rank_order, ctypes.c_int64), ptr(ratio_control, ctypes.c_double),
+                                           None if k is None else ptr(k, ctypes.c_double), m0, m1,
+                                           0 if smoothed else MS_PROFILE_UNSMOOTHED, ctypes.c_void_p(dst)))
+        return out
+
     def close(self):
         if getattr(self, "h", None):
             lib().ms_result_free(self.h)
             self.h = None
 
     __del__ = close
+
+
+def result_from_hits(n_pwms, n_regions, motif_offsets, seq_idx, pos, score_, strand):
+    """A ScanResult made of host hit arrays in ms_result order (ms_result_from_hits), on the current device."""
+    motif_offsets = np.ascontiguousarray(motif_offsets, dtype=np.int64)
+    seq_idx = np.ascontiguousarray(seq_idx, dtype=np.int64)
+    pos = np.ascontiguousarray(pos, dtype=np.int64)
+    score_ = np.ascontiguousarray(score_, dtype=np.float64)
+    strand = np.ascontiguousarray(strand, dtype=np.int8)
+    n = int(motif_offsets[-1]) if len(motif_offsets) else 0
+    if len(motif_offsets) != int(n_pwms) + 1 or not len(seq_idx) == len(pos) == len(score_) == len(strand) == n:
+        raise ValueError("need motif_offsets[n_pwms + 1] and motif_offsets[-1] hits in every array")
+    h = ctypes.c_void_p()
+    check(lib().ms_result_from_hits(int(n_pwms), int(n_regions), ptr(motif_offsets, ctypes.c_int64), ptr(seq_idx, ctypes.c_int64),
+                                    ptr(pos, ctypes.c_int64), ptr(score_, ctypes.c_double), ptr(strand, ctypes.c_int8), ctypes.byref(h)))
+    return ScanResult(h, int(n_pwms))
 
 
 def host_pack(bases, offsets):
