@@ -29,7 +29,7 @@ class ScanStats(ctypes.Structure):
                 ("ms_total", ctypes.c_double), ("lds_bytes_read", ctypes.c_int64),
                 ("hbm_bytes_algorithmic", ctypes.c_int64), ("pf_clock_mhz", ctypes.c_double),
                 ("mfma_ops", ctypes.c_int64), ("mfma_ops_algorithmic", ctypes.c_int64), ("pf_engine", ctypes.c_int32),
-                ("reserved", ctypes.c_int32)]
+                ("order_overflow_runs", ctypes.c_int32)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}

@@ -1233,8 +1233,9 @@ void pending_scan_destroy(PendingScan *p) {
 
 // stage times, counts and the next scan's prediction, once a scan's kernels are known to be done
 static void finish_scan(ms_result *raw, hipEvent_t *ev, ms_pwmset *pwms, int64_t n_bases, int64_t R, int strand_mask, bool exact_only,
-                        unsigned long long n_cand, unsigned long long n_hits, bool with_back) {
+                        unsigned long long n_cand, unsigned long long n_hits, bool with_back, unsigned long long n_overflow) {
     ms_scan_stats &stt = raw->stats;
+    stt.order_overflow_runs = (int32_t) std::min<unsigned long long>(n_overflow, INT32_MAX);
     stt.n_candidates = (int64_t) n_cand;
     stt.n_hits = (int64_t) n_hits;
     raw->n_hits = (int64_t) n_hits;
@@ -1274,7 +1275,7 @@ int scan_complete(DeviceCtx *c, ms_pwmset *pwms, PendingScan *p, ms_result **out
         std::memcpy(raw->motif_offsets.data(), p->h_offsets, n_off * sizeof(int64_t));
         try { raw->h_region_counts.assign(p->h_offsets + n_off, p->h_offsets + n_off + raw->P); } catch (const std::bad_alloc &) { raw->h_region_counts.clear(); }
         pwms->pred_margin = std::max(0.04, pwms->pred_margin * 0.9);
-        finish_scan(raw, p->ev, pwms, p->n_bases, p->R, p->strand_mask, p->exact_only, n_cand, n_hits, true);
+        finish_scan(raw, p->ev, pwms, p->n_bases, p->R, p->strand_mask, p->exact_only, n_cand, n_hits, true, p->h_counters[2]);
         *out = raw;
         return MS_OK;
     }
@@ -1464,7 +1465,7 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
         pf_wave_passes = wp;
     }
 
-    // counters: [0] candidate record slots, [1] hits
+    // counters: [0] candidate record slots, [1] hits, [2] runs ordered by order_overflow_kernel
     // pre-filter + fp64 stage of one pass, queued on the scan stream (events 0, 1, 2 around the two stages)
     hipEvent_t *ev = c->ev;                                        // stage events of this scan (a pending scan's own set, below)
     uint64_t cand_static = 0;                                      // the pre-filter waves' own first candidate blocks (set by front)
@@ -1536,8 +1537,23 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
     // only the device knows how many of them are hits (the rest are all-ones keys, which sort behind every hit)
     const int end_bit = gbits + 1 + mbits;
     // the radix passes cover the key bits above kSortLowBits, sort_fixup_kernel the rest (MS_SORT_FULL: all bits by radix passes;
-    // a short hit list is ordered by launch latencies, not passes: one kernel fewer matters more there)
-    const int sort_begin_large = (end_bit > 2 * kSortLowBits && !measure_env("MS_SORT_FULL")) ? kSortLowBits : 0;
+    // a short hit list is ordered by launch latencies, not passes: one kernel fewer matters more there).  With region coordinates
+    // (pbits > 0) order_finalize_kernel sorts the runs below L = order_low_bits(n) bits instead, and writes the result arrays (L > 0).
+    const bool sort_full = measure_env("MS_SORT_FULL") != nullptr;
+    const int sort_begin_large = (end_bit > 2 * kSortLowBits && !sort_full) ? kSortLowBits : 0;
+    const char *low_bits_env = measure_env("MS_SORT_LOW_BITS");          // test aid: force L (the motif bits stay above it)
+    auto order_low_bits = [&](size_t n) -> int {
+        if (low_bits_env) return std::max(0, std::min(atoi(low_bits_env), gbits + 1));
+        if (sort_begin_large == 0) return 0;
+        // one radix pass fewer per eight bits, as long as the expected run n / (P x 2^(gbits + 1 - L)) stays short enough for the
+        // rank sort in LDS (the motif bits stay above L: each run's first hit is then decided on any hit of the run before it)
+        int L = 0;
+        for (int b = kSortLowBits; b <= kOrderMaxLowBits && b <= gbits + 1; b += 8)
+            if (b == kSortLowBits || std::ldexp((double) n / (double) std::max(pwms->P, 1), b - gbits - 1) <= kOrderMeanRun) L = b;
+        return L;
+    };
+    int order_run_cap = 1 << 30;
+    if (const char *e = measure_env("MS_ORDER_RUN_CAP")) order_run_cap = std::max(1, atoi(e));     // test aid: longer runs take the overflow path
     bool queue_only = false;                     // this back() belongs to a scan that is only queued (scan_complete finishes it)
     // counts only: the flag map costs ~2 x P x R bytes of traffic (clear + count), the ordering it replaces ~200 bytes per hit -- so the map is
     // taken where the set holds at least one hit per ~50 (motif, region) cells (configs[3]: one per 9; a million 50-bp regions: one per 100,
@@ -1568,10 +1584,14 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
         }
         size_t fixup_min = (size_t) 1 << 20;
         if (const char *e = measure_env("MS_SORT_FIXUP_MIN")) fixup_min = (size_t) std::max(0, atoi(e));     // test aid: the fix-up form on short lists too
-        const int sort_begin = n_sort >= fixup_min ? sort_begin_large : 0;
+        const int sort_begin = pbits > 0 ? (n_sort >= fixup_min || low_bits_env ? order_low_bits(n_sort) : 0)
+                                         : (n_sort >= fixup_min ? sort_begin_large : 0);
+        // (the radix temp storage is free once the passes are done: order_finalize_kernel's overflow list goes there)
+        const size_t ovf_bytes = pbits > 0 && sort_begin > 0 ? order_overflow_bytes(n_sort, order_run_cap) : 0;
         if (n_sort > 0) {
             size_t need = 0;
             if ((rc = sort_hit_pairs(nullptr, &need, sc.keys, sc.keys_sorted, sc.vals, raw->d_score, n_sort, sort_begin, end_bit, c->stream))) return rc;
+            need = std::max(need, ovf_bytes);
             if (need > sc.sort_tmp_bytes) {
                 if (sc.sort_tmp) (void) hipFree(sc.sort_tmp);
                 sc.sort_tmp = nullptr; sc.sort_tmp_bytes = 0;
@@ -1582,11 +1602,17 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
             }
             size_t have = sc.sort_tmp_bytes;
             if ((rc = sort_hit_pairs(sc.sort_tmp, &have, sc.keys, sc.keys_sorted, sc.vals, raw->d_score, n_sort, sort_begin, end_bit, c->stream))) return rc;
-            if (sort_begin && (rc = launch_sort_fixup(sc.keys_sorted, raw->d_score, (int64_t) n_sort, n_dev, c->stream))) return rc;
+            if (pbits == 0 && sort_begin && (rc = launch_sort_fixup(sc.keys_sorted, raw->d_score, (int64_t) n_sort, n_dev, c->stream))) return rc;
         }
         (void) hipEventRecord(ev[4], c->stream);
-        if ((rc = launch_finalize(sc.keys_sorted, (int64_t) n_sort, n_dev, gbits, rbits, pbits, pwms->P, S, raw->d_seq_idx, raw->d_pos,
-                                  raw->d_strand, raw->d_motif_first, raw->d_region_counts, c->stream))) return rc;
+        if (pbits > 0 && sort_begin > 0) {
+            // counters[2]: the runs order_finalize_kernel leaves to its overflow launch (zeroed with the others in front of the pre-filter).
+            // (A list sorted over every bit -- a short one: launch latencies, not bytes -- keeps the lighter finalize_rp_kernel.)
+            if ((rc = launch_order_finalize(sc.keys_sorted, raw->d_score, (int64_t) n_sort, n_dev, sort_begin, rbits, pbits, pwms->P, raw->d_seq_idx,
+                                            raw->d_pos, raw->d_strand, raw->d_motif_first, raw->d_region_counts, sc.keys, sc.vals, sc.sort_tmp,
+                                            ovf_bytes, sc.counters + 2, order_run_cap, c->stream))) return rc;
+        } else if ((rc = launch_finalize(sc.keys_sorted, (int64_t) n_sort, n_dev, gbits, rbits, pbits, pwms->P, S, raw->d_seq_idx, raw->d_pos,
+                                         raw->d_strand, raw->d_motif_first, raw->d_region_counts, c->stream))) return rc;
         if ((flags & (MS_SCAN_PACK_INTERNAL | MS_SCAN_PACK12_INTERNAL)) && n_sort > 0) {
             const size_t n_round = (n_sort + 65535) & ~(size_t) 65535;
             if ((rc = pool_alloc(c, 8 * n_round + 256, &raw->coord_blk, &raw->coord_bytes))) return rc;
@@ -1625,7 +1651,7 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
         return MS_OK;
     };
     auto finish = [&](unsigned long long n_cand, unsigned long long n_hits, bool with_back) {
-        finish_scan(raw, ev, pwms, seqs->n_bases, seqs->R, strand_mask, exact_only, n_cand, n_hits, with_back);
+        finish_scan(raw, ev, pwms, seqs->n_bases, seqs->R, strand_mask, exact_only, n_cand, n_hits, with_back, with_back ? sc.h_counters[2] : 0);
     };
 
     // ---- one-sync form: sizes PREDICTED from the previous scan of these PWMs.  The hit density of a motif set at its cutoffs is a
@@ -1746,7 +1772,8 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
     decide_counts((size_t) n_hits);
     if ((rc = result_block(counts_fast ? 1 : (size_t) n_hits))) return fail(rc);
     if ((rc = back((size_t) n_hits, nullptr))) return fail(rc);
-    he = hipStreamSynchronize(c->stream);
+    he = hipMemcpyAsync(sc.h_counters, sc.counters, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
     if (he != hipSuccess) { set_error("finalize failed: %s", hipGetErrorString(he)); return fail(MS_ERR_RUNTIME); }
     finish(n_cand, n_hits, true);
     *out = raw;

@@ -23,7 +23,7 @@ void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
         }                                                                                   \
     } while (0)
 
-// Measurement switches (MS_PF_MAX_BLOCKS, MS_SORT_FULL, MS_SORT_FIXUP_MIN, MS_RESCORE_SORTED_MIN, MS_BLKINFO_FAR, MS_HIT_COORD, MS_CU_PARTITION) are honoured only when
+// Measurement switches (MS_PF_MAX_BLOCKS, MS_SORT_FULL, MS_SORT_FIXUP_MIN, MS_SORT_LOW_BITS, MS_ORDER_RUN_CAP, MS_RESCORE_SORTED_MIN, MS_BLKINFO_FAR, MS_HIT_COORD, MS_CU_PARTITION) are honoured only when
 // MS_MEASURE=1 is set as well: a stray variable in the environment must never change what the product does (tests/ and tools/
 // opt in explicitly).
 inline const char *measure_env(const char *name) {
@@ -229,6 +229,8 @@ int build_plan(const double *values, const int64_t *val_off, const int32_t *widt
 
 // Sort (ms_sort.hip): keys ascending over bits [begin_bit, end_bit) (stable).  Query temp size with temp == nullptr.
 constexpr int kSortLowBits = 8;        // a scan's hits are radix-sorted over the key bits above these; sort_fixup_kernel orders the rest
+constexpr int kOrderMaxLowBits = 24;   // region coordinates: order_finalize_kernel (ms_order.hip) orders up to this many low bits ...
+constexpr double kOrderMeanRun = 128.0;    // ... the most whose expected run of equal higher bits is at most this many hits
 int sort_hit_pairs(void *temp, size_t *temp_bytes, const uint64_t *keys_in, uint64_t *keys_out,
                    const double *vals_in, double *vals_out, size_t n, int begin_bit, int end_bit, hipStream_t stream);
 

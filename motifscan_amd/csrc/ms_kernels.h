@@ -105,6 +105,14 @@ int launch_sort_fixup(uint64_t *keys, double *vals, int64_t n, const unsigned lo
 int launch_finalize(const uint64_t *keys, int64_t n, const unsigned long long *n_dev, int gbits, int rbits, int pbits, int32_t P, const DevSeq &S,
                     int64_t *seq_idx, int64_t *pos, int8_t *strand, int64_t *motif_first, unsigned long long *region_counts,
                     hipStream_t st);
+// ms_order.hip: keys sorted over the bits [L, end_bit) -> every run of equal key >> L into full key order, decoded like launch_finalize's
+// region form (pbits > 0), scores moved within d_score.  Runs the kernel cannot sort in LDS are listed in ovf_buf (order_overflow_bytes(n,
+// run_cap) bytes; *ovf_n zero on entry, the number listed on exit) and sorted by a second launch, through tmp_keys / tmp_vals ([n] each).
+size_t order_overflow_bytes(size_t n, int run_cap);
+int launch_order_finalize(uint64_t *keys, double *score, int64_t n, const unsigned long long *n_dev, int L, int rbits, int pbits, int32_t P,
+                          int64_t *seq_idx, int64_t *pos, int8_t *strand, int64_t *motif_first, unsigned long long *region_counts,
+                          uint64_t *tmp_keys, double *tmp_vals, void *ovf_buf, size_t ovf_bytes, unsigned long long *ovf_n, int run_cap,
+                          hipStream_t st);
 int launch_fill_tail(uint64_t *keys, const unsigned long long *n_dev, uint64_t cap, hipStream_t st);
 int launch_extract(const uint32_t *gcodes, const uint32_t *gnmask, const int64_t *src_start, const int64_t *dst_off,
                    int64_t R, int64_t n_out, uint32_t *codes, uint32_t *nmask, hipStream_t st);

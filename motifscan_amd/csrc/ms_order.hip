@@ -1,0 +1,291 @@
+// ms_order.hip -- the last step of a scan's ordering when the hit keys carry (region, position inside the region) (pbits > 0).
+//
+// The radix passes (ms_sort.hip) order the keys over the bits [L, end_bit) only.  Hits that agree in those bits -- a RUN -- are then
+// neighbours, in no particular order among themselves.  order_finalize_kernel finishes the order of every run in LDS and writes the
+// result arrays in the same pass: seq_idx, pos and strand, the score moved to its final slot of d_score, the per-motif offsets and
+// the per-motif region counts (the semantics of finalize_rp_kernel, ms_kernels.hip).  This replaces a fix-up kernel plus a finalize
+// kernel (one read of keys and scores fewer), and L up to 24 lets the radix sort drop up to two of its eight-bit passes.
+//
+//   order_finalize_kernel  block b owns the runs that START in slots [b * kOrderTile, (b + 1) * kOrderTile); it stages those slots and
+//                          the kOrderExt after them in LDS, ranks each element inside its run (a scan's keys are distinct: no ties),
+//                          and decodes.  A run that does not close inside the staged window, or that is longer than run_cap, goes to
+//                          the overflow list instead (an atomic append of its first slot).
+//   order_overflow_kernel  one block per listed run (grid-stride over the list): finds the run's end, sorts it by an LSD radix sort
+//                          of eight-bit digits in global memory (ping-pong with the scan's spare key / score buffers, stable by wave
+//                          ballots), then decodes it like the kernel above.  Correct for a run as long as the whole list.
+//
+// Per-motif offsets and region counts need each hit's predecessor in the FINAL order.  Inside a run that is the sorted neighbour.  For
+// the first hit of a run it is the last hit of the previous run -- but every test made on it (motif changed? (motif, region) pair
+// changed?) gives the same answer for ANY hit of the previous run: with L <= gbits + 1 the motif bits are above L, so they are the
+// same for the whole run; the pair bits are either above L too (L <= pbits + 1), or they include bits above L, which differ between
+// two runs, so the pair changes.  The radix-order predecessor is therefore enough, and no block depends on another block's output.
+#include <algorithm>
+
+#include "ms_kernels.h"
+
+namespace ms {
+
+namespace {
+
+constexpr int kOrderThreads = 256;
+constexpr int kOrderTile = 1024;                 // slots a block owns the run starts of
+constexpr int kOrderExt = 256;                   // slots staged past the tile to close its last run: every run of <= kOrderExt hits is
+constexpr int kOrderWin = kOrderTile + kOrderExt;    // sorted in LDS (31.5 KB per block: five blocks per CU)
+constexpr int kOverflowBlocks = 256;
+
+struct OrderRun {
+    int64_t start;      // first slot of the run
+    uint64_t prev;      // a key of the run in front of it (start > 0)
+};
+
+struct OrderOut {
+    int64_t *seq_idx;
+    int64_t *pos;
+    int8_t *strand;
+    double *score;
+    int64_t *motif_first;
+    unsigned long long *region_counts;
+    int rbits, pbits;
+    int32_t P;
+};
+
+// one hit at final slot g: key k, score v, predecessor pk (has_prev: g > 0).  Returns whether it opens a (motif, region) pair.
+__device__ __forceinline__ bool decode_hit(const OrderOut &O, int64_t g, int64_t n, uint64_t k, double v, bool has_prev, uint64_t pk,
+                                           uint32_t *motif_out) {
+    const int ms = O.rbits + O.pbits + 1;
+    const uint64_t pair = k >> (O.pbits + 1);
+    const uint32_t motif = (uint32_t) (k >> ms);
+    O.seq_idx[g] = (int64_t) (pair & ((1ULL << O.rbits) - 1ULL));
+    O.pos[g] = (int64_t) ((k >> 1) & ((1ULL << O.pbits) - 1ULL));
+    O.strand[g] = (int8_t) ((k & 1ULL) ? 2 : 1);
+    O.score[g] = v;
+    const uint32_t pm = has_prev ? (uint32_t) (pk >> ms) : 0u;
+    if (!has_prev || pm != motif)                                       // every motif after the previous hit's up to this one starts here
+        for (int64_t q = has_prev ? (int64_t) pm + 1 : 0; q <= (int64_t) motif; q++) O.motif_first[q] = g;
+    if (g == n - 1)                                                    // motifs after the last hit: empty
+        for (int64_t q = (int64_t) motif + 1; q <= O.P; q++) O.motif_first[q] = n;
+    *motif_out = motif;
+    return !has_prev || (pk >> (O.pbits + 1)) != pair;
+}
+
+// regions with >= 1 hit per motif (stats.py:29-31): one add per (wave, motif), into the block's LDS counters for the motifs
+// [m_base, m_base + kOrderMotifSlots) (lds != nullptr), else straight to the global ones.  Every lane of the wave calls this.
+constexpr int kOrderMotifSlots = 8;
+__device__ __forceinline__ void count_pairs(unsigned long long *region_counts, bool new_pair, uint32_t motif, unsigned int *lds, uint32_t m_base) {
+    unsigned long long todo = __ballot(new_pair);
+    while (todo) {
+        const int leader = __ffsll((long long) todo) - 1;
+        const uint32_t m = __shfl(motif, leader);
+        const unsigned long long same = __ballot(new_pair && motif == m);
+        if ((int) (threadIdx.x & 63) == leader) {
+            if (lds && m - m_base < (uint32_t) kOrderMotifSlots) atomicAdd(&lds[m - m_base], (unsigned int) __popcll(same));
+            else atomicAdd(&region_counts[m], (unsigned long long) __popcll(same));
+        }
+        todo &= ~same;
+    }
+}
+
+// Slot i = tid + kOrderThreads * k of the staged window is thread tid's k-th: its key and score stay in registers from the load to the
+// scatter, and its wave's ballot of run starts (one 64-slot segment) gives the run's bounds without walking the keys.
+__global__ void __launch_bounds__(kOrderThreads) order_finalize_kernel(const uint64_t *__restrict__ keys, int64_t n, const unsigned long long *__restrict__ n_dev,
+                                                                      int L, int run_cap, OrderOut O, OrderRun *__restrict__ ovf,
+                                                                      unsigned long long *__restrict__ ovf_n, uint64_t ovf_cap) {
+    constexpr int kPer = kOrderWin / kOrderThreads, kSegs = kOrderWin / 64;
+    __shared__ uint64_t K[kOrderWin];          // radix order
+    __shared__ uint64_t S[kOrderWin];          // final order
+    __shared__ double V[kOrderWin];
+    __shared__ uint8_t D[kOrderWin];           // slot sorted here
+    __shared__ int seg_first[kSegs], seg_last[kSegs];                // first / last run start of each 64-slot segment (none: kOrderWin / -1)
+    __shared__ unsigned int rc[kOrderMotifSlots];                    // the block's region counts of its first motifs (a block of a long list spans one or two)
+    if (n_dev) { const unsigned long long nd = *n_dev; if ((unsigned long long) n > nd) n = (int64_t) nd; }
+    const int64_t s0 = (int64_t) blockIdx.x * kOrderTile;
+    if (s0 >= n) return;
+    const int tid = (int) threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int wn = (int) std::min<int64_t>(kOrderWin, n - s0);      // staged slots
+    const int tn = std::min(kOrderTile, wn);                          // owned run starts lie in [0, tn)
+    uint64_t kr[kPer];
+    double vr[kPer];                           // (scores of slots another block owns are read too, and never used)
+#pragma unroll
+    for (int k = 0; k < kPer; k++) {
+        const int i = tid + kOrderThreads * k;
+        kr[k] = i < wn ? keys[s0 + i] : ~0ULL;
+        vr[k] = i < wn ? O.score[s0 + i] : 0.0;
+        K[i] = kr[k];
+        D[i] = 0;
+    }
+    if (tid < kOrderMotifSlots) rc[tid] = 0;
+    const uint64_t prevk = s0 > 0 ? keys[s0 - 1] : 0ULL;
+    __syncthreads();
+    unsigned long long msk[kPer];              // run starts of each of this thread's segments
+#pragma unroll
+    for (int k = 0; k < kPer; k++) {
+        const int i = tid + kOrderThreads * k;
+        const bool start = i < wn && (i == 0 ? (s0 == 0 || (prevk >> L) != (kr[k] >> L)) : (K[i - 1] >> L) != (kr[k] >> L));
+        msk[k] = __ballot(start);
+        if (lane == 0) {
+            const int seg = w + (kOrderThreads / 64) * k;
+            seg_first[seg] = msk[k] ? seg * 64 + __ffsll((long long) msk[k]) - 1 : kOrderWin;
+            seg_last[seg] = msk[k] ? seg * 64 + 63 - __clzll((long long) msk[k]) : -1;
+        }
+    }
+    __syncthreads();
+    int lo = kOrderWin, hi = wn;               // owned slots: [lo, hi) -- from the first run start in the tile to the first one past it
+    for (int q = 0; q < kSegs; q++) lo = std::min(lo, seg_first[q]);
+    if (tn == kOrderTile)
+        for (int q = kOrderTile / 64; q < kSegs; q++) hi = std::min(hi, seg_first[q]);
+    if (lo >= tn) return;                      // no run starts in this tile
+    const bool closed = hi < wn || s0 + wn == n;                      // else the last owned run runs on past the window
+    const int ms = O.rbits + O.pbits + 1;
+    const uint32_t m_base = (uint32_t) (K[lo] >> ms);
+    const unsigned long long le = lane == 63 ? ~0ULL : (2ULL << lane) - 1ULL;
+#pragma unroll
+    for (int k = 0; k < kPer; k++) {
+        const int i = tid + kOrderThreads * k, seg = w + (kOrderThreads / 64) * k;
+        if (i < lo || i >= hi) continue;
+        int a = -1, b = wn;
+        if (msk[k] & le) a = seg * 64 + 63 - __clzll((long long) (msk[k] & le));
+        else for (int q = seg - 1; q >= 0 && a < 0; q--) a = seg_last[q];
+        if (msk[k] & ~le) b = seg * 64 + __ffsll((long long) (msk[k] & ~le)) - 1;
+        else for (int q = seg + 1; q < kSegs && b == wn; q++) b = std::min(wn, seg_first[q]);
+        if ((b == hi && !closed) || b - a > run_cap) {
+            if (i == a) {
+                const unsigned long long e = atomicAdd(ovf_n, 1ULL);
+                if (e < ovf_cap) ovf[e] = OrderRun{s0 + a, a > 0 ? K[a - 1] : prevk};
+            }
+            continue;
+        }
+        int rank = 0;
+        for (int j = a; j < b; j++) rank += K[j] < kr[k] ? 1 : 0;
+        S[a + rank] = kr[k];
+        V[a + rank] = vr[k];
+        D[a + rank] = 1;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kPer; k++) {           // whole waves: count_pairs
+        const int j = tid + kOrderThreads * k;
+        bool new_pair = false;
+        uint32_t motif = 0;
+        if (j >= lo && j < hi && D[j]) {
+            const bool run_start = (msk[k] >> lane) & 1ULL;
+            const uint64_t pk = run_start ? (j == 0 ? prevk : K[j - 1]) : S[j - 1];
+            new_pair = decode_hit(O, s0 + j, n, S[j], V[j], s0 + j > 0, pk, &motif);
+        }
+        count_pairs(O.region_counts, new_pair, motif, rc, m_base);
+    }
+    __syncthreads();
+    if (tid < kOrderMotifSlots && rc[tid]) atomicAdd(&O.region_counts[m_base + tid], (unsigned long long) rc[tid]);
+}
+
+__global__ void __launch_bounds__(kOrderThreads) order_overflow_kernel(uint64_t *keys, uint64_t *tmp_keys, double *tmp_vals,
+                                                                      int64_t n, const unsigned long long *__restrict__ n_dev, int L, OrderOut O,
+                                                                      const OrderRun *__restrict__ ovf, const unsigned long long *__restrict__ ovf_n,
+                                                                      uint64_t ovf_cap) {
+    __shared__ uint32_t base[256];
+    __shared__ uint32_t wcnt[kOrderThreads / 64][256];
+    __shared__ int64_t s_end;
+    if (n_dev) { const unsigned long long nd = *n_dev; if ((unsigned long long) n > nd) n = (int64_t) nd; }
+    const unsigned long long cnt = std::min<unsigned long long>(*ovf_n, ovf_cap);
+    const int tid = (int) threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const unsigned long long lt = (1ULL << lane) - 1ULL;
+    for (unsigned long long e = blockIdx.x; e < cnt; e += gridDim.x) {
+        const int64_t s = ovf[e].start;
+        const uint64_t prev = ovf[e].prev;
+        const uint64_t h = keys[s] >> L;       // (only this block moves the run's keys; another block's run never holds these bits)
+        if (tid == 0) s_end = n;
+        __syncthreads();
+        for (int64_t c = s + 1; c < n; c += kOrderThreads) {
+            const int64_t j = c + tid;
+            if (j < n && (keys[j] >> L) != h) atomicMin((unsigned long long *) &s_end, (unsigned long long) j);
+            __syncthreads();
+            if (s_end < n) break;
+            __syncthreads();
+        }
+        const int64_t b = s_end;
+        uint64_t *sk = keys, *dk = tmp_keys;
+        double *sv = O.score, *dv = tmp_vals;
+        for (int shift = 0; shift < L; shift += 8) {
+            base[tid] = 0;
+            for (int q = 0; q < kOrderThreads / 64; q++) wcnt[q][tid] = 0;
+            __syncthreads();
+            for (int64_t j = s + tid; j < b; j += kOrderThreads) atomicAdd(&base[(uint32_t) (sk[j] >> shift) & 255u], 1u);
+            __syncthreads();
+            if (tid == 0) {
+                uint32_t acc = 0;
+                for (int d = 0; d < 256; d++) { const uint32_t c = base[d]; base[d] = acc; acc += c; }
+            }
+            __syncthreads();
+            for (int64_t c = s; c < b; c += kOrderThreads) {          // stable scatter, 256 hits at a time
+                const int64_t j = c + tid;
+                const bool live = j < b;
+                const uint64_t k = live ? sk[j] : 0ULL;
+                const double v = live ? sv[j] : 0.0;
+                const uint32_t d = (uint32_t) (k >> shift) & 255u;
+                unsigned long long peers = __ballot(live);
+#pragma unroll
+                for (int bit = 0; bit < 8; bit++) {
+                    const unsigned long long m = __ballot((d >> bit) & 1u);
+                    peers &= ((d >> bit) & 1u) ? m : ~m;
+                }
+                if (live && (peers >> lane) == 1ULL) wcnt[w][d] = (uint32_t) __popcll(peers);   // the last lane of its digit in the wave
+                __syncthreads();
+                if (live) {
+                    uint32_t off = base[d] + (uint32_t) __popcll(peers & lt);
+                    for (int q = 0; q < w; q++) off += wcnt[q][d];
+                    dk[s + off] = k;
+                    dv[s + off] = v;
+                }
+                __syncthreads();
+                uint32_t add = 0;
+                for (int q = 0; q < kOrderThreads / 64; q++) { add += wcnt[q][tid]; wcnt[q][tid] = 0; }
+                base[tid] += add;
+                __syncthreads();
+            }
+            uint64_t *tk = sk; sk = dk; dk = tk;
+            double *tv = sv; sv = dv; dv = tv;
+        }
+        for (int64_t c = s; c < b; c += kOrderThreads) {              // whole waves: count_pairs
+            const int64_t j = c + tid;
+            bool new_pair = false;
+            uint32_t motif = 0;
+            if (j < b) new_pair = decode_hit(O, j, n, sk[j], sv[j], j > 0, j == s ? prev : sk[j - 1], &motif);
+            count_pairs(O.region_counts, new_pair, motif, nullptr, 0);
+        }
+        __syncthreads();                       // (s_end and the LDS counters are reused by the next run)
+    }
+}
+
+}  // namespace
+
+size_t order_overflow_bytes(size_t n, int run_cap) {
+    const size_t min_len = (size_t) std::min(std::max(run_cap, 1), kOrderExt) + 1;     // every listed run is longer than this minus one
+    return (n / min_len + 1) * sizeof(OrderRun);
+}
+
+int launch_order_finalize(uint64_t *keys, double *score, int64_t n, const unsigned long long *n_dev, int L, int rbits, int pbits, int32_t P,
+                          int64_t *seq_idx, int64_t *pos, int8_t *strand, int64_t *motif_first, unsigned long long *region_counts,
+                          uint64_t *tmp_keys, double *tmp_vals, void *ovf_buf, size_t ovf_bytes, unsigned long long *ovf_n, int run_cap,
+                          hipStream_t st) {
+    if (n == 0 || n_dev) {                           // no hits: every per-motif offset is 0 (with n_dev the kernel overwrites them unless the count is 0)
+        MS_HIP(hipMemsetAsync(motif_first, 0, ((size_t) P + 1) * sizeof(int64_t), st));
+        if (n == 0) return MS_OK;
+    }
+    run_cap = std::max(run_cap, 1);
+    OrderOut O;
+    O.seq_idx = seq_idx; O.pos = pos; O.strand = strand; O.score = score; O.motif_first = motif_first; O.region_counts = region_counts;
+    O.rbits = rbits; O.pbits = pbits; O.P = P;
+    OrderRun *ovf = static_cast<OrderRun *>(ovf_buf);
+    const uint64_t ovf_cap = ovf_bytes / sizeof(OrderRun);
+    hipLaunchKernelGGL(order_finalize_kernel, dim3((unsigned) ((n + kOrderTile - 1) / kOrderTile)), dim3(kOrderThreads), 0, st, keys, n, n_dev,
+                       L, run_cap, O, ovf, ovf_n, ovf_cap);
+    MS_HIP(hipGetLastError());
+    // a run is only listed when it is longer than run_cap or than kOrderExt: with at most 2^L hits per run, not at L = 8 by default
+    if (L < 63 && (1ULL << L) > (unsigned long long) std::min(run_cap, kOrderExt)) {
+        hipLaunchKernelGGL(order_overflow_kernel, dim3(kOverflowBlocks), dim3(kOrderThreads), 0, st, keys, tmp_keys, tmp_vals, n, n_dev, L, O,
+                           ovf, ovf_n, ovf_cap);
+        MS_HIP(hipGetLastError());
+    }
+    return MS_OK;
+}
+
+}  // namespace ms
