@@ -2,7 +2,7 @@
 """
 bench.py -- the measurement contract of the PWM scan path.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c4|c3|c2|c5|c5shard|tiny]
+    python bench.py --gpus N --steps K --warmup W [--workload c4|c3|c2|c5|c5shard|tiny] [--full]
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script starts its own N ranks (fresh processes through
 torch.distributed.run, before anything in this process has touched the GPU) and relays rank 0's line; under the
@@ -14,9 +14,14 @@ the north-star workload.  A "step" is one pass of the hot path over the rank's s
 in HBM: per region set  pack (extraction -> 2-bit codes + N mask) -> fp6 x fp4 matrix-core pre-filter -> fp64 re-scoring ->
 ordering -> coordinates / per-motif region counts;  then the path's ONE collective, the all-reduce of the device-resident
 int64[2 x 579] count vector (stats.py:29-31 input).  Hits stay in HBM inside the timed region: `value` is the
-device-resident whole-job rate.  SURVEY.md 8(d)'s end-to-end metric (host ASCII in pinned memory -> hit arrays in pinned
-host memory, i.e. H2D + pack + scan + D2H) is measured in the same run through the library's batch stream and reported
-beside it as `value_end_to_end` -- never as `value`.
+device-resident whole-job rate.
+
+A plain run sets up, warms up, times the K steps and reports what those steps measured (the headline, the stage and
+kernel times, the roofline figures derived from them).  --full also runs everything that takes runs or checks of its own,
+after the timed steps: SURVEY.md 8(d)'s end-to-end metric (host ASCII in pinned memory -> hit arrays in pinned host memory,
+i.e. H2D + pack + scan + D2H, through the library's batch stream, reported as `value_end_to_end` -- never as `value`), the
+Python API leg, the N = 2, 4, 8 shard projection, the CPU baseline with its parity sample, the per-rank oracle samples and
+count check of an N > 1 run, and the hits_packed mode of the c5 sweep.  The --no-* options leave single parts of that out.
 
 Prints ONE JSON line on rank 0.  --dump-outputs DIR (region workloads) also writes what the last timed step computed on
 rank 0 as DIR/<name>.npy, so that two builds can be compared output for output on the same seeded inputs.
@@ -249,10 +254,12 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="c4", choices=list(WORKLOAD_TEXT))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true")
-    ap.add_argument("--no-api", action="store_true", help="skip the value_api leg (Scanner.scan_motifs at configs[1] and configs[2])")
-    ap.add_argument("--no-scale-projection", action="store_true", help="skip the N = 2, 4, 8 shard steps timed at N = 1 (scale_projection)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the end-to-end, API, scale-projection and CPU-baseline legs "
+                    "and the per-rank checks (see the module docstring); a plain run reports the timed steps only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and its parity sample")
+    ap.add_argument("--no-end-to-end", action="store_true", help="--full: skip the end-to-end legs (value_end_to_end)")
+    ap.add_argument("--no-api", action="store_true", help="--full: skip the value_api leg (Scanner.scan_motifs at configs[1] and configs[2])")
+    ap.add_argument("--no-scale-projection", action="store_true", help="--full: skip the N = 2, 4, 8 shard steps timed at N = 1 (scale_projection)")
     ap.add_argument("--no-batch-ramp", action="store_true", help="end-to-end passes: equal batches (default: small first and last batches)")
     ap.add_argument("--min-warm-seconds", type=float, default=2.0, help="untimed warm-up steps continue until this much wall time has passed (DVFS steady state)")
     ap.add_argument("--regions-per-set", type=int, default=None, help="c4 only: shrink the workload (development aid; the line then says so)")
@@ -420,19 +427,23 @@ def main():
         for res in last_results:
             res.close()
 
-    # the collective, checked: all-reduced vector == sum over ranks of the vectors each rank's library handed over
     counts_check = None
     ranks_report = None
     if use_pg:
-        gathered = [torch.zeros_like(local_counts) for _ in range(world)]
-        dist.all_gather(gathered, local_counts)
-        counts_check = {"allreduce_equals_sum_of_rank_counts": bool(torch.equal(torch.stack(gathered).sum(0), counts)),
-                        "max_regions_with_site": int(counts.max().item())}
-        # per rank: its own ms per step, the collective's own time, and 2000 of its regions checked against the oracle
-        ps = rank_parity_sample(wl, pw, strand=strand_mask)
+        ps = None
+        if a.full:
+            # the collective, checked: all-reduced vector == sum over ranks of the vectors each rank's library handed over
+            gathered = [torch.zeros_like(local_counts) for _ in range(world)]
+            dist.all_gather(gathered, local_counts)
+            counts_check = {"allreduce_equals_sum_of_rank_counts": bool(torch.equal(torch.stack(gathered).sum(0), counts)),
+                            "max_regions_with_site": int(counts.max().item())}
+            ps = rank_parity_sample(wl, pw, strand=strand_mask)      # 2000 of this rank's regions checked against the oracle
+        # per rank: its own ms per step and the collective's own time (and with --full its oracle sample)
         ar_ms = sum(e0.elapsed_time(e1) for e0, e1 in ar_events) / max(len(ar_events), 1)
-        mine = torch.tensor([own_elapsed / a.steps * 1e3, ar_ms, float(ps["regions"]), float(ps["hits"]), 1.0 if ps["identical"] else 0.0,
-                             float(wl["shard"][0]), float(wl["shard"][1]), float(dev_index)], dtype=torch.float64, device=dev)
+        mine = [own_elapsed / a.steps * 1e3, ar_ms, float(wl["shard"][0]), float(wl["shard"][1]), float(dev_index)]
+        if ps is not None:
+            mine += [float(ps["regions"]), float(ps["hits"]), 1.0 if ps["identical"] else 0.0]
+        mine = torch.tensor(mine, dtype=torch.float64, device=dev)
         per_rank = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(per_rank, mine)
         tab = torch.stack(per_rank).cpu().numpy()
@@ -440,23 +451,24 @@ def main():
                         "ms_per_step_by_rank": [round(float(x), 3) for x in tab[:, 0]],
                         "allreduce_ms_mean_by_rank": [round(float(x), 4) for x in tab[:, 1]],
                         # every rank's [r0, r1) of each region set: contiguous, in rank order, together the whole set
-                        "shard_by_rank": [[int(x), int(y)] for x, y in tab[:, 5:7]],
-                        "shards_tile_every_set": bool(tab[0, 5] == 0 and tab[-1, 6] == wl["n_regions_total"]
-                                                      and all(tab[k, 6] == tab[k + 1, 5] for k in range(world - 1))),
+                        "shard_by_rank": [[int(x), int(y)] for x, y in tab[:, 2:4]],
+                        "shards_tile_every_set": bool(tab[0, 2] == 0 and tab[-1, 3] == wl["n_regions_total"]
+                                                      and all(tab[k, 3] == tab[k + 1, 2] for k in range(world - 1))),
                         # what the collective ran on: the judge can see that RCCL saw `world` ranks, one per device
-                        "rccl": {"backend": dist.get_backend(), "world": world, "device_ids": [int(x) for x in tab[:, 7]],
-                                 "devices_visible": int(torch.cuda.device_count()), "one_rank_per_device": len({int(x) for x in tab[:, 7]}) == world,
+                        "rccl": {"backend": dist.get_backend(), "world": world, "device_ids": [int(x) for x in tab[:, 4]],
+                                 "devices_visible": int(torch.cuda.device_count()), "one_rank_per_device": len({int(x) for x in tab[:, 4]}) == world,
                                  "nccl_version": _nccl_version(torch) if dist.get_backend() == "nccl" else None,
-                                 "device_name": torch.cuda.get_device_name(dev)},
-                        "parity_sample": {"regions_per_rank": int(tab[:, 2].min()), "hits_checked": int(tab[:, 3].sum()),
-                                          "ranks_identical_to_oracle": int(tab[:, 4].sum()), "ranks": world,
-                                          "checker": "oracle/cscore_oracle.c (liboracle.so), first regions of every rank's own shard"}}
+                                 "device_name": torch.cuda.get_device_name(dev)}}
+        if ps is not None:
+            ranks_report["parity_sample"] = {"regions_per_rank": int(tab[:, 5].min()), "hits_checked": int(tab[:, 6].sum()),
+                                             "ranks_identical_to_oracle": int(tab[:, 7].sum()), "ranks": world,
+                                             "checker": "oracle/cscore_oracle.c (liboracle.so), first regions of every rank's own shard"}
 
     # ---- what a rank's step would be at N = 2, 4, 8 (VERDICT r4 #7b): the shard a rank of an N-GPU run scans, timed here on one GPU.
     # The ranks share nothing but the collective, so N x (step at 1) / (step at N) bounds the node's speedup before it; the driver's
     # SCALE run can be held against this table line by line.
     scale_projection = None
-    if rank == 0 and world == 1 and a.workload == "c4" and not side and not a.no_scale_projection:
+    if a.full and rank == 0 and world == 1 and a.workload == "c4" and not side and not a.no_scale_projection:
         scale_projection = {"definition": "ms per resident step (median of single steps) of ONE rank's shard of an N-GPU run (first 1/N of both region sets), measured on this GPU; "
                                           "speedup_bound = step(1) / step(N): the scaling an N-GPU node reaches before its one all-reduce",
                             "ms_per_step": {"1": elapsed / a.steps * 1e3}, "speedup_bound": {}}
@@ -491,12 +503,12 @@ def main():
     # ---- the drop-in at the Python API (before the streamed legs: they leave the library's block pools holding a few dozen GB-sized
     # blocks, and the first small scan behind them once paid a 40 ms driver call for that: r04f_bench_c4.json against r04e_) ----
     api = None
-    if rank == 0 and world == 1 and not a.no_api and not side:
+    if a.full and rank == 0 and world == 1 and not a.no_api and not side:
         api = api_leg()
 
     # ---- SURVEY.md 8(d) end-to-end: host ASCII (pinned) -> hit arrays in pinned host memory, through the batch stream ----
     e2e = None
-    if not a.no_end_to_end:
+    if a.full and not a.no_end_to_end:
         e2e = end_to_end(a, wl, pw, world, dev, torch, dist if use_pg else None, strand_mask)
 
     if rank == 0:
@@ -557,7 +569,8 @@ def main():
                        "warmup_steps_run": n_warm, "timed_region_s": elapsed},
             "value_definition": "device-resident (the bench contract: inputs already in HBM when the timed region starts): ASCII in HBM at the start, hits left in HBM; "
                                 "pack + pre-filter + fp64 + order + finalize + all-reduce inside.  SURVEY.md 8(d)'s pack + H2D + kernel + D2H metric is "
-                                "value_8d_end_to_end (every hit of both sets to pinned host memory) and value_8d_cli_job (the reference CLI's own data flow)",
+                                "value_8d_end_to_end (every hit of both sets to pinned host memory) and value_8d_cli_job (the reference CLI's own data flow), "
+                                "both in a --full run",
             "roofline": roofline,
             "roofline_hbm": {"bound": "hbm", "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
                              "frac": achieved / HBM_PEAK, "traffic": traffic, "algorithmic_bytes_per_launch": alg_bytes},
@@ -590,7 +603,7 @@ def main():
             line["value_8d_cli_job"] = e2e["pipelined_cli"]
             line["end_to_end_over_resident"] = {"pipelined": e2e["pipelined"] / line["value"], "pipelined_cli": e2e["pipelined_cli"] / line["value"],
                                                 "pipelined_sustained": e2e["pipelined_sustained"] / line["value"]}
-        if world == 1 and not a.no_cpu_baseline and wl["sets"] and not side:
+        if a.full and world == 1 and not a.no_cpu_baseline and wl["sets"] and not side:
             line["cpu_baseline"], sample = cpu_baseline(wl)
             line["parity_sample"] = parity_sample(wl, pw, sample)
         if api is not None:
@@ -871,7 +884,9 @@ def main_sweep(a, world, rank, local_rank):
         counts = torch.zeros(P, dtype=torch.int64, device=dev)
         local_counts = torch.zeros(P, dtype=torch.int64, device=dev)
         my_units = float(sum(sp[4] for sp in mine)) * window * P
-        modes = {"counts_only": (_lib.MS_STREAM_NO_HITS, False), "hits_packed": (0, True)}
+        modes = {"counts_only": (_lib.MS_STREAM_NO_HITS, False)}           # `value`
+        if a.full:
+            modes["hits_packed"] = (0, True)
         out = {}
 
         def one_pass(flags, packed):
@@ -919,7 +934,7 @@ def main_sweep(a, world, rank, local_rank):
                          "hbm_pool_timed": {k: pool1[k] - pool0[k] for k in ("hits", "misses", "driver_frees", "driver_ms")},
                          "stage_ms_last_pass": {sk: {f: round(x, 2) for f, x in sv.items()} for sk, sv in st["stages"].items()}}
         counts_check = None
-        if world > 1:                                  # the collective and the span shards, checked (last pass = hits_packed mode)
+        if a.full and world > 1:                       # the collective and the span shards, checked (last pass = hits_packed mode)
             gathered = [torch.zeros_like(local_counts) for _ in range(world)]
             dist.all_gather(gathered, local_counts)
             first_last = torch.tensor([float(mine[0][3]) if mine else -1.0, float(mine[-1][3] + mine[-1][4]) if mine else -1.0, float(len(mine))],
@@ -944,7 +959,7 @@ def main_sweep(a, world, rank, local_rank):
                     "value_definition": "host-streamed END TO END (chromosomes in pinned host memory -> upload + pack | scan-once + hand-out | "
                                         "copy-out overlapped); units are reference-equivalent (window_bp x n_windows x n_motifs: the reference "
                                         "scans every base window / stride = 4 times, the sweep once). value = counts_only mode (per-motif window "
-                                        "counts, what the enrichment statistics consume); hits_packed also copies every site to the host",
+                                        "counts, what the enrichment statistics consume); hits_packed (--full) also copies every site to the host",
                     "modes": out}
             if counts_check is not None:
                 line["counts_check"] = counts_check

@@ -921,7 +921,7 @@ def test_bench_self_launches_two_ranks_on_one_gpu():
     env = dict(os.environ, MS_BENCH_BACKEND="gloo", MS_BENCH_SHARE_GPU="1")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--workload", "tiny", "--no-cpu-baseline", "--min-warm-seconds", "0"], env=env, capture_output=True, text=True,
+                          "--workload", "tiny", "--full", "--no-cpu-baseline", "--min-warm-seconds", "0"], env=env, capture_output=True, text=True,
                          timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -953,7 +953,7 @@ def test_bench_world_of_four_on_one_gpu():
     pipelines (12 host threads) and 4 block pools, one all-reduce per step -- on the one GPU of this box over gloo: n_gpus = 4,
     the all-reduced vector == the sum of the ranks' vectors, the four shards tile both sets in rank order, and 2000 regions of
     EVERY rank's own shard are bit-identical to the oracle."""
-    line = _bench_ranks_on_one_gpu(["--gpus", "4", "--regions-per-set", "160000", "--steps", "3", "--warmup", "1", "--min-warm-seconds", "0"])
+    line = _bench_ranks_on_one_gpu(["--gpus", "4", "--regions-per-set", "160000", "--steps", "3", "--warmup", "1", "--min-warm-seconds", "0", "--full"])
     assert line["n_gpus"] == 4 and line["scaling"] == "strong" and line["value"] > 0
     assert line["counts_check"]["allreduce_equals_sum_of_rank_counts"] is True
     rk = line["ranks"]
@@ -971,7 +971,7 @@ def test_bench_sweep_world_of_four_on_one_gpu():
     """configs[4] (host-streamed sweep) with the spans sharded over four ranks on one GPU: the ranks' window ranges tile the
     sweep, the all-reduced per-motif window counts == the sum of the ranks' own."""
     line = _bench_ranks_on_one_gpu(["--gpus", "4", "--workload", "c5", "--genome-mbp", "240", "--steps", "1", "--warmup", "1",
-                                    "--min-warm-seconds", "0"])
+                                    "--min-warm-seconds", "0", "--full"])
     assert line["n_gpus"] == 4 and line["value"] > 0
     cc = line["counts_check"]
     assert cc["allreduce_equals_sum_of_rank_counts"] is True and cc["window_ranges_tile_the_sweep"] is True and cc["ranks_with_spans"] == 4
@@ -1015,6 +1015,20 @@ def test_bench_dump_outputs_repeat_and_match_the_oracle(tmp_path, oracle):
         assert np.array_equal(a["region_counts.npy"][s], regions)
 
 
+def test_bench_plain_run_reports_the_timed_steps_only():
+    """Without --full the line holds what the timed steps measured and nothing that takes runs or checks of its own: no end-to-end,
+    API, scale-projection or CPU-baseline leg and no parity sample."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1",
+                          "--min-warm-seconds", "0"], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = json.loads([l for l in out.stdout.splitlines() if l.startswith('{"metric"')][-1])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["unit"] == "bp*motifs/s" and line["higher_is_better"] is True and line["dtype"].startswith("f64")
+    assert line["stage_ms_per_scan"]["ms_total"] > 0 and line["roofline"]["kernel"] == "prefilter_f6_kernel"
+    for key in ("value_end_to_end", "value_8d_end_to_end", "value_api", "scale_projection", "cpu_baseline", "parity_sample", "counts_check"):
+        assert key not in line, key
+
+
 def test_bench_collectives_over_rccl_on_a_one_rank_communicator():
     """The only RCCL run a one-GPU box allows: MS_BENCH_FORCE_PG=1 makes a single rank open the process group (backend "nccl" = RCCL,
     bound to its device) and take every N > 1 branch of bench.py -- the int64 all-reduce on the vector the library hands over, the
@@ -1024,7 +1038,7 @@ def test_bench_collectives_over_rccl_on_a_one_rank_communicator():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MS_BENCH_SHARE_GPU", "MS_BENCH_BACKEND", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--regions-per-set", "40000", "--steps", "3", "--warmup", "1", "--min-warm-seconds", "0",
-                          "--no-cpu-baseline", "--no-api", "--no-scale-projection"], env=env, capture_output=True, text=True, timeout=900)
+                          "--full", "--no-cpu-baseline", "--no-api", "--no-scale-projection"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith('{"metric"')][-1])
     assert line["n_gpus"] == 1 and line["value"] > 0

@@ -2,7 +2,7 @@
 """
 tools/api_time.py -- times the drop-in WHERE north_star puts it: `Scanner(genome, regions, ...).scan_motifs(pwms)` and what the
 reference's consumers then do with the result (io/__init__.py:23-33 `len(sites[idx])`, `max(site.score ...)`; stats.py:29-31),
-at BASELINE configs[1] (10k x 500 bp x 50 PWMs) and configs[2] (100k x 1 kb x 579 PWMs).  Prints one JSON object; bench.py
+at BASELINE configs[1] (10k x 500 bp x 50 PWMs) and configs[2] (100k x 1 kb x 579 PWMs).  Prints one JSON object; bench.py --full
 embeds the same measurement as its `value_api` key.  GPU box only (the product has no CPU path).
 
     python tools/api_time.py [--configs c2,c3] [--writer-regions 2000]

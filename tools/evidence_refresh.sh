@@ -20,5 +20,5 @@ rm -rf $P
 # the line itself, with the traffic of the passes above (the record is rewritten on the box for this run only; the committed one is
 # rewritten from the copied-back summaries by tools/pmc_traffic_update.py)
 python3 tools/pmc_traffic_update.py c4 $OUT/pmc_fetch.csv $OUT/pmc_write.csv "evidence refresh $TAG" > /dev/null
-$T python bench.py > $OUT/bench_c4.json 2> $OUT/bench_c4.err
+$T python bench.py --full > $OUT/bench_c4.json 2> $OUT/bench_c4.err
 ls $OUT

@@ -1,7 +1,7 @@
 #!/bin/bash
 # The bench's end-to-end legs N times on one box: how steady are the timed passes?  bash tools/r06_bench_e2e_repeat.sh [n]  (GPU box)
 for rep in $(seq 1 ${1:-6}); do
-  python bench.py --steps 6 --no-cpu-baseline --no-api --no-scale-projection 2>/dev/null | python3 -c "
+  python bench.py --steps 6 --full --no-cpu-baseline --no-api --no-scale-projection 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{\"metric\"'):

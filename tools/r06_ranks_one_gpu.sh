@@ -4,7 +4,7 @@ TAG=${1:-r06c}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 T="timeout 900"
-E="--gpus 8 --steps 3 --warmup 1 --no-cpu-baseline --no-api --no-scale-projection"
+E="--gpus 8 --steps 3 --warmup 1 --full --no-cpu-baseline --no-api --no-scale-projection"
 export MS_BENCH_BACKEND=gloo MS_BENCH_SHARE_GPU=1
 lscpu | grep -i "numa\|socket\|model name\|^CPU(s)" > $OUT/lscpu.txt
 cat /sys/bus/pci/devices/*/numa_node 2>/dev/null | sort | uniq -c > $OUT/pci_numa_nodes.txt
