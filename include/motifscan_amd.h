@@ -26,6 +26,10 @@
  *   ms_genome_create_packed / ms_genome_packed_host / ms_pack_bases_host
  *                         Genome.__init__ -> pysam.FastaFile (genome/__init__.py:61-83): the FASTA is packed ONCE into a genome
  *                         file (motifscan_amd/genome.py) whose planes are uploaded as they are
+ *   ms_genome_base_counts cal_bg_freq's per-chromosome A / C / G / T counts     genome/__init__.py:179-220
+ *   ms_genome_window_filter / ms_randint_replay_host
+ *                         Genome.random_sequences (genome/__init__.py:137-176): the seeded start draws replayed on the host, the
+ *                         N filter + first-n_times compaction of the candidate windows on the device (motif --build's background)
  *   ms_scan_sweep         the same extraction + scan for the windows of a fixed-stride sweep of one chromosome
  *                         (BASELINE configs[4]); every base is scored once instead of window / stride times
  *   ms_scan_regions_once  the same extraction + scan for region lists that overlap (peaks +- window/2, random controls:
@@ -180,6 +184,27 @@ int ms_genome_size(const ms_genome *genome, int32_t *n_chroms, int64_t *n_bases)
 void ms_genome_free(ms_genome *genome);
 int ms_seqset_from_genome(const ms_genome *genome, const int32_t *chrom, const int64_t *start,
                           const int64_t *end, int64_t n_regions, ms_seqset **out);
+
+/* ---- the genome-wide jobs of `motif --build` / `genome --install` (ms_background.hip) ------ */
+/* cal_bg_freq (genome/__init__.py:179-220) per chromosome: counts[c][0..3] = the numbers of A, C, G, T of chromosome c in either
+ * case (the reference's .upper() + count); N and every other non-ACGT byte count for nothing.  counts: host [n_chroms][4]. */
+int ms_genome_base_counts(const ms_genome *genome, int64_t *counts);
+/* The N filter of Genome.random_sequences (genome/__init__.py:137-176) over candidate windows [gstart[k], gstart[k] + length) in
+ * GENOME coordinates (chromosome offset + start; each window must lie inside the genome), taken in attempt order k = 0, 1, ...:
+ * a window is accepted when its count of N / n bytes is <= max_n.  That count is the window's non-ACGT bases (the nmask plane)
+ * minus the entries of exc_pos (host, ascending genome positions of the non-ACGT bytes that are NOT N / n -- the IUPAC letters a
+ * genome file keeps; PackedGenome.exc_pos) inside the window: a window holding an R but no N passes at max_n = 0.
+ * taken_idx (host, >= n_want entries) receives the candidate indices of the FIRST n_want accepted windows in attempt order (a stable
+ * compaction); *n_taken = min(n_want, accepted windows). */
+int ms_genome_window_filter(const ms_genome *genome, const int64_t *gstart, int64_t n_cand, int32_t length, int32_t max_n,
+                            const int64_t *exc_pos, int64_t n_exc, int64_t n_want, int64_t *taken_idx, int64_t *n_taken);
+/* Host only, no device: n_att sequential calls of numpy's legacy RandomState.randint(high[k]) replayed from the raw 32-bit words
+ * that the same state would give (np.random.randint(0, 2**32, dtype=np.uint32)), for 1 <= high[k] <= 2^32: with rng = high - 1,
+ * rng == 0 consumes no word and returns 0; otherwise words w are taken in order until (w & mask) <= rng, mask = 2^bitlen(rng) - 1.
+ * start[k] = the value drawn, words_used[k] = words consumed by calls 0 .. k.  Stops when the words run out: *n_done = calls
+ * completed.  MS_ERR_INVALID for a high outside [1, 2^32] (numpy raises for high <= 0 and draws 64-bit words above 2^32). */
+int ms_randint_replay_host(const uint32_t *words, int64_t n_words, const int64_t *high, int64_t n_att, int64_t *start,
+                           int64_t *words_used, int64_t *n_done);
 
 /* ---- scan (c_scan_motif) ---------------------------------------------------------------- */
 int ms_scan(const ms_pwmset *pwms, const ms_seqset *seqs, int strand_mask, uint32_t flags,

@@ -111,6 +111,9 @@ def lib():
         "ms_pack_bases_host": (c_int, [ctypes.c_char_p, c_i64, c_int, pu32, pu32]),
         "ms_genome_free": (None, [vp]),
         "ms_seqset_from_genome": (c_int, [vp, pi32, pi64, pi64, c_i64, pvp]),
+        "ms_genome_base_counts": (c_int, [vp, pi64]),
+        "ms_genome_window_filter": (c_int, [vp, pi64, c_i64, c_i32, c_i32, pi64, c_i64, c_i64, pi64, pi64]),
+        "ms_randint_replay_host": (c_int, [pu32, c_i64, pi64, c_i64, pi64, pi64, pi64]),
         "ms_scan": (c_int, [vp, vp, c_int, c_u32, pvp]),
         "ms_scan_sweep": (c_int, [vp, vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_int, c_u32, pvp]),
         "ms_scan_regions_once": (c_int, [vp, vp, pi32, pi64, pi64, c_i64, c_int, c_u32, pvp]),
@@ -453,12 +456,67 @@ class ResidentGenome:
         sq.n_bases = nb.value
         return sq
 
+    # ---- the genome-wide jobs of motif --build / genome --install (genome/__init__.py:137-220; motifscan_amd/genome.py) ----
+    def base_counts(self):
+        """[n_chroms, 4] int64: A, C, G, T of every chromosome (file order), either case; N / IUPAC bytes count for nothing."""
+        out = np.zeros((len(self.names), 4), dtype=np.int64)
+        check(lib().ms_genome_base_counts(self.h, ptr(out, ctypes.c_int64)))
+        return out
+
+    def _exceptions(self):
+        """The ascending genome positions of the non-ACGT bytes that are not N / n: the device planes mark them as N, the reference's
+        sampler does not count them, and only the host side knows where they are."""
+        if getattr(self, "_packed", None) is not None:
+            return self._packed.exc_pos
+        if self._host is not None:
+            if getattr(self, "_host_exc", None) is None:
+                self._host_exc = self.packed().exc_pos
+            return self._host_exc
+        raise RuntimeError("ResidentGenome was created without keep_host: the positions of its IUPAC letters (which Genome.random_sequences "
+                           "does not count as N) live only on the host, so windows cannot be sampled as the reference samples them")
+
+    def random_windows(self, n_times, length, max_n=0, random_seed=None, max_attempts=None):
+        """Genome.random_sequences' draws (genome/__init__.py:137-176) as (chrom_idx, start) arrays, chromosome indices in file order;
+        numpy's global RandomState ends where the reference leaves it.  See motifscan_amd.genome.sample_windows."""
+        from . import genome as _genome
+        return _genome.sample_windows(self, self._exceptions(), n_times, length, max_n, random_seed, max_attempts)
+
+    def random_sequences(self, n_times, length, max_n=0, random_seed=None):
+        """Genome.random_sequences: the same strings under the same seed, case and IUPAC letters included."""
+        ci, st = self.random_windows(n_times, length, max_n, random_seed)
+        for c, s in zip(ci.tolist(), st.tolist()):
+            yield self.fetch_sequence(self.names[c], s, s + length)
+
     def close(self):
         if getattr(self, "h", None):
             lib().ms_genome_free(self.h)
             self.h = None
 
     __del__ = close
+
+
+def window_filter(genome, gstart, length, max_n, exc_pos, n_want):
+    """Candidate indices of the first n_want windows [gstart[k], gstart[k] + length) of a ResidentGenome with at most max_n N / n bytes,
+    in candidate order (ms_genome_window_filter)."""
+    gstart = np.ascontiguousarray(gstart, dtype=np.int64)
+    exc = np.ascontiguousarray(exc_pos, dtype=np.int64)
+    n_want = int(n_want)
+    taken = np.zeros(max(1, min(n_want, gstart.size)), dtype=np.int64)
+    nt = ctypes.c_int64()
+    check(lib().ms_genome_window_filter(genome.h, ptr(gstart, ctypes.c_int64), gstart.size, int(length), int(min(max_n, length)),
+                                        ptr(exc, ctypes.c_int64), exc.size, n_want, ptr(taken, ctypes.c_int64), ctypes.byref(nt)))
+    return taken[:nt.value]
+
+
+def randint_replay(words, high):
+    """ms_randint_replay_host: (start, words_used, n_done) of len(high) sequential legacy randint(high[k]) calls replayed from raw words."""
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    high = np.ascontiguousarray(high, dtype=np.int64)
+    start, used = np.zeros(high.size, dtype=np.int64), np.zeros(high.size, dtype=np.int64)
+    done = ctypes.c_int64()
+    check(lib().ms_randint_replay_host(ptr(words, ctypes.c_uint32), words.size, ptr(high, ctypes.c_int64), high.size,
+                                       ptr(start, ctypes.c_int64), ptr(used, ctypes.c_int64), ctypes.byref(done)))
+    return start, used, done.value
 
 
 def _owned_array(address, ctype, n, dtype, owner):

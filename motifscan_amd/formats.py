@@ -2,6 +2,7 @@
 motifscan_amd.formats -- the on-disk formats either side of the scan path:
 
   in   read_jaspar_pfms(path)                 JASPAR PFM text            motif/__init__.py:70-140
+       read_bg_freq(path) / write_bg_freq(path, bg)   background frequencies   genome/__init__.py:223-269
        read_motifscan_pwms(path)              built PWMs + cutoffs       motif/__init__.py:219-319
        write_motifscan_pwms(path, pwms)                                  motif/__init__.py:200-217
   out  write_sites_table(dir, pwms, regions, ...)   motif_sites_number.xls / motif_sites_score.xls  io/__init__.py:12-38
@@ -31,6 +32,15 @@ class PfmsJasparFormatError(Exception):
 class PwmsMotifScanFormatError(Exception):
     def __init__(self, line_num, line):
         super().__init__(f"Invalid MotifScan PWMs format at line {line_num}: {line!r}")
+        self.line_num = line_num
+
+
+class BackgroundFormatError(ValueError):
+    """A background frequency file that is not four '<base>\\t<freq>' lines for A, C, G, T (exceptions.py:43-46).  A ValueError as well:
+    where the reference's read_bg_freq fails to split a line it raises a plain ValueError."""
+
+    def __init__(self, line_num, line):
+        super().__init__(f"Invalid background format at line {line_num}: {line!r}")
         self.line_num = line_num
 
 
@@ -141,6 +151,29 @@ def write_motifscan_pwms(path, pwms):
                 out.write(base + " [" + "\t".join(f"{v:8.5f}" for v in row) + "]\n")
             for p, cutoff in pwm.cutoffs.items():
                 out.write(f"Cutoff_p{p}\t{cutoff}\n")
+
+
+def write_bg_freq(path, bg_freq):
+    """genome/__init__.py:223-238: one '<base>\\t<freq>' line each for A, C, G, T."""
+    with open(path, "w") as out:
+        for base in BASES:
+            out.write(f"{base}\t{bg_freq[base]}\n")
+
+
+def read_bg_freq(path):
+    """genome/__init__.py:241-269: {base: float} from the four lines, in A, C, G, T order; BackgroundFormatError otherwise."""
+    bg = {}
+    with open(path, "r") as fh:
+        for idx, expected in enumerate(BASES):
+            line = fh.readline().strip()
+            fields = line.split("\t")
+            if len(fields) != 2 or fields[0] != expected:
+                raise BackgroundFormatError(idx + 1, line)
+            try:
+                bg[expected] = float(fields[1])
+            except (ValueError, TypeError):
+                raise BackgroundFormatError(idx + 1, line)
+    return bg
 
 
 # ------------------------------------------------------------------------ result writers --

@@ -271,3 +271,183 @@ class PackedGenome:
         """Upload the planes: the genome resident in HBM (a `_lib.ResidentGenome` whose host side is this object)."""
         from . import _lib
         return _lib.ResidentGenome.from_packed(self)
+
+    # ---- Genome.random_sequences (genome/__init__.py:137-176) ----
+    def random_windows(self, n_times, length, max_n=0, random_seed=None, max_attempts=None):
+        """(chrom_idx, start): the reference's draws under the same seed, chromosome indices in file order.  The planes are uploaded for the
+        call; a `_lib.ResidentGenome` made once (to_resident) samples without that upload."""
+        check_sampling(self.chrom_sizes, length, max_n)
+        resident = self.to_resident()
+        try:
+            return sample_windows(resident, self.exc_pos, n_times, length, max_n, random_seed, max_attempts)
+        finally:
+            resident.close()
+
+    def random_sequences(self, n_times, length, max_n=0, random_seed=None):
+        """Genome.random_sequences: the same strings byte for byte under the same seed (case and IUPAC letters included)."""
+        ci, st = self.random_windows(n_times, length, max_n, random_seed)
+        for c, s in zip(ci.tolist(), st.tolist()):
+            yield self.fetch_sequence(self.names[c], s, s + length)
+
+
+# --------------------------------------------------------------------------- background sampling --
+#
+# Genome.random_sequences (genome/__init__.py:137-176) draws, from numpy's GLOBAL legacy RandomState (seeded only if a seed is given):
+#   1. random_chroms = np.random.choice(chroms, size=n_times, p=[size_c / total ...]), chroms = sorted names;
+#   2. attempt k takes chromosome random_chroms[k % n_times] and start = np.random.randint(size_c - length);
+#   3. the window is kept if it holds at most max_n N / n bytes;   4. it stops at the n_times-th kept window.
+# Step 1 is the same numpy call here.  Step 2's randint(high), high <= 2^32, is numpy's masked rejection over raw 32-bit words (rng =
+# high - 1 == 0 takes no word): the words are drawn in bulk (np.random.randint(0, 2**32, dtype=np.uint32) yields exactly those words)
+# and the starts replayed from them on the host (ms_randint_replay_host); step 3 runs on the device over the candidate windows
+# (ms_genome_window_filter), which also returns the first accepted ones in attempt order.  At the end the global state is rewound and
+# advanced by exactly the words the reference would have consumed up to its n_times-th kept window.
+
+MAX_DRAW_HIGH = 1 << 32
+
+
+def check_sampling(chrom_sizes, length, max_n):
+    if int(max_n) < 0:
+        raise ValueError(f"max_n = {max_n}: must be >= 0 (the reference's sampling loop never ends for a negative max_n)")
+    if int(length) < 1:
+        raise ValueError(f"length = {length}: must be >= 1")
+    big = [c for c, s in chrom_sizes.items() if s - int(length) > MAX_DRAW_HIGH]
+    if big:
+        raise ValueError(f"chromosome {big[0]!r} is longer than 2^32 + length bases: numpy draws its starts from 64-bit words, which "
+                         "this sampler does not replay")
+
+
+class RandintReplay:
+    """Sequential np.random.randint(high) calls of the global legacy RandomState, replayed from raw 32-bit words drawn in bulk.
+    Made right where the reference's first randint call would happen; commit(n) leaves the global state as if exactly the words of the
+    replayed calls up to the one that consumed word n had been drawn."""
+
+    def __init__(self):
+        self.state0 = np.random.get_state()
+        self.words = np.zeros(0, dtype=np.uint32)
+        self.pos = 0                                  # words consumed by the calls replayed so far
+
+    def _more(self, n):
+        self.words = np.concatenate([self.words, np.random.randint(0, 1 << 32, size=int(n), dtype=np.uint32)])
+
+    def draw(self, high):
+        """The next len(high) calls: (start, words_used), words_used[k] = words consumed from the initial state through call k."""
+        from . import _lib
+        high = np.ascontiguousarray(high, dtype=np.int64)
+        n = high.size
+        start, used = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        done = 0
+        while done < n:
+            want = 2 * (n - done) + 64                # a call takes fewer than 2 words on average (the mask keeps more than half)
+            if self.words.size - self.pos < want:
+                self._more(want)
+            s, u, nd = _lib.randint_replay(self.words[self.pos:], high[done:])
+            start[done:done + nd] = s[:nd]
+            used[done:done + nd] = u[:nd] + self.pos
+            if nd:
+                self.pos = int(used[done + nd - 1])
+            done += nd
+            if done < n:                              # the words ran out inside call `done`: it starts again from self.pos
+                self._more(want)
+        return start, used
+
+    def commit(self, n_words):
+        np.random.set_state(self.state0)
+        if n_words:
+            np.random.randint(0, 1 << 32, size=int(n_words), dtype=np.uint32)
+
+
+def sample_windows(resident, exc_pos, n_times, length, max_n=0, random_seed=None, max_attempts=None):
+    """Genome.random_sequences' windows over a `_lib.ResidentGenome`: (chrom_idx int32 in file order, start int64), n_times of them in
+    the reference's order; the global RandomState ends where the reference leaves it.  exc_pos: the genome's IUPAC positions
+    (PackedGenome.exc_pos).  Errors: max_n < 0 or length < 1 -> ValueError (the reference loops forever / cuts empty windows);
+    drawing a chromosome of size <= length -> numpy's ValueError('high <= 0') at the attempt where the reference raises it, with the
+    state the reference leaves; more than max_attempts attempts (default 100 * n_times + 10^6) -> RuntimeError instead of a hang."""
+    from . import _lib
+    n_times, length, max_n = int(n_times), int(length), int(max_n)
+    check_sampling(resident.chrom_sizes, length, max_n)
+    if random_seed is not None:
+        np.random.seed(random_seed)
+    chroms = sorted(resident.names)
+    sizes = [resident.chrom_sizes[c] for c in chroms]
+    total = sum(sizes)
+    weight = [s / total for s in sizes]
+    random_chroms = np.random.choice(len(chroms), size=n_times, p=weight)   # the reference draws names: the same stream, as indices
+    empty = np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int64)
+    if n_times <= 0:
+        return empty
+    file_idx = np.array([resident.index[c] for c in chroms], dtype=np.int32)
+    high = (np.array(sizes, dtype=np.int64) - length)[random_chroms]
+    goff = np.asarray(resident.offsets, dtype=np.int64)[file_idx][random_chroms]
+    cap = int(max_attempts) if max_attempts is not None else 100 * n_times + 1_000_000
+    replay = RandintReplay()
+    got_c, got_s = [], []
+    n_got, k0 = 0, 0
+    while True:
+        need = n_times - n_got
+        n_new = min(max(need + need // 4, 64), cap - k0)
+        if n_new <= 0:
+            replay.commit(replay.pos)
+            raise RuntimeError(f"{cap} sampling attempts gave {n_got} of {n_times} windows with at most {max_n} N: "
+                               f"the genome has too few such windows of length {length} (raise max_attempts or max_n)")
+        att = np.arange(k0, k0 + n_new, dtype=np.int64) % n_times
+        h = high[att]
+        bad = np.flatnonzero(h <= 0)
+        if bad.size:
+            att, h = att[:bad[0]], h[:bad[0]]
+        start, used = replay.draw(h)
+        if att.size:
+            taken = _lib.window_filter(resident, goff[att] + start, length, max_n, exc_pos, need)
+            got_c.append(file_idx[random_chroms[att[taken]]])
+            got_s.append(start[taken])
+            n_got += taken.size
+            if n_got == n_times:
+                replay.commit(int(used[taken[-1]]))
+                return np.concatenate(got_c).astype(np.int32), np.concatenate(got_s)
+        if bad.size:                                  # the reference reaches the attempt whose chromosome is too short: numpy raises there
+            replay.commit(replay.pos)
+            raise ValueError("high <= 0")
+        k0 += att.size
+
+
+# --------------------------------------------------------------------------- background frequencies --
+
+SKIP_KEYWORDS = ("chrX", "chrY", "chrM", "chrUn_", "_random", "_hap", "_alt")
+
+
+def is_non_autosome(name):
+    """cal_bg_freq's skip rule (genome/__init__.py:199-211): a substring match of any of SKIP_KEYWORDS."""
+    return any(k in name for k in SKIP_KEYWORDS)
+
+
+def open_resident(source):
+    """(ResidentGenome, owned) for a FASTA path, a genome file, a PackedGenome or a ResidentGenome; owned: made here, close it after."""
+    from . import _lib
+    if isinstance(source, _lib.ResidentGenome):
+        return source, False
+    if isinstance(source, PackedGenome):
+        return source.to_resident(), True
+    path = os.fspath(source)
+    with open(path, "rb") as fh:
+        magic = fh.read(len(MAGIC))
+    packed = PackedGenome.load(path) if magic == MAGIC else PackedGenome.from_fasta(path)
+    return packed.to_resident(), True
+
+
+def cal_bg_freq(source, skip_non_autosomes=True):
+    """The reference's cal_bg_freq (genome/__init__.py:179-220) on the device: {base: round(count / total, 5)} over A, C, G, T in either
+    case, chromosomes matching the skip rule left out unless skip_non_autosomes is False.  ZeroDivisionError when nothing is counted,
+    as the reference raises."""
+    resident, owned = open_resident(source)
+    try:
+        counts = resident.base_counts()
+        names = list(resident.names)
+    finally:
+        if owned:
+            resident.close()
+    tot = [0, 0, 0, 0]
+    for name, row in zip(names, counts.tolist()):
+        if skip_non_autosomes and is_non_autosome(name):
+            continue
+        tot = [a + b for a, b in zip(tot, row)]
+    total = sum(tot)
+    return {b: round(tot[i] / total, 5) for i, b in enumerate("ACGT")}
