@@ -30,6 +30,10 @@
  *   ms_genome_window_filter / ms_randint_replay_host
  *                         Genome.random_sequences (genome/__init__.py:137-176): the seeded start draws replayed on the host, the
  *                         N filter + first-n_times compaction of the candidate windows on the device (motif --build's background)
+ *   ms_genes_create / ms_genes_nearest_tss / ms_genes_promoter_overlap / ms_control_regions_replay_host
+ *                         Genes (genome/annotation.py:32-54) as arrays; dis_to_nearest_gene, subset_by_location's overlap test and
+ *                         generate_control_regions (region/utils.py:16-180): the walks over a chromosome's genes on the device,
+ *                         the seeded randint / choice draws replayed on the host (cli/scan.py:60-79)
  *   ms_scan_sweep         the same extraction + scan for the windows of a fixed-stride sweep of one chromosome
  *                         (BASELINE configs[4]); every base is scored once instead of window / stride times
  *   ms_scan_regions_once  the same extraction + scan for region lists that overlap (peaks +- window/2, random controls:
@@ -205,6 +209,57 @@ int ms_genome_window_filter(const ms_genome *genome, const int64_t *gstart, int6
  * completed.  MS_ERR_INVALID for a high outside [1, 2^32] (numpy raises for high <= 0 and draws 64-bit words above 2^32). */
 int ms_randint_replay_host(const uint32_t *words, int64_t n_words, const int64_t *high, int64_t n_att, int64_t *start,
                            int64_t *words_used, int64_t *n_done);
+
+/* ---- gene annotation: control regions and promoter / distal subsets (ms_annotation.hip) ---- */
+/* A gene table in the reference's order (genome/annotation.py:32-54, Genes._genes): chromosome c (indexed by first appearance in the
+ * file) owns genes [chrom_offsets[c], chrom_offsets[c + 1]) of tss / strand (MS_STRAND_FWD '+', MS_STRAND_REV '-'), in FILE order.
+ * Creating one touches no device; its device copy is made by the first call below, on the calling thread's device. */
+typedef struct ms_genes ms_genes;
+int ms_genes_create(const int64_t *chrom_offsets, int32_t n_chroms, const int64_t *tss, const int8_t *strand, ms_genes **out);
+void ms_genes_free(ms_genes *genes);
+/* dis_to_nearest_gene (region/utils.py:148-180) for n regions (chromosome index of the gene table, start): the reference's recurrence
+ * over the chromosome's genes in file order -- m = cutoff; d = start - tss; |d| < m: m = d (SIGNED), target = gene -- so the first
+ * accepted d <= 0 ends the walk, ties and |d| == cutoff are not accepted.  found[r] = 0 where the reference returns None (also for
+ * chrom < 0, a chromosome index past the table and a chromosome without genes; distance[r] = 0 then); otherwise distance[r] = m, negated
+ * for a target on the '-' strand (0 is a distance, not None).  Host arrays in the caller's order, regions in any chromosome order. */
+int ms_genes_nearest_tss(const ms_genes *genes, const int32_t *chrom, const int64_t *start, int64_t n, int64_t cutoff,
+                         int64_t *distance, uint8_t *found);
+/* The overlap test of subset_by_location (region/utils.py:51-86): the promoters [tss - upstream, tss + downstream] ('+') /
+ * [tss - downstream, tss + upstream] ('-') of the region's chromosome (Gene.promoter, genome/annotation.py:25-29), sorted as Python
+ * sorts lists of pairs, searched with the literal binary search of overlap_with (region/utils.py:16-48).  overlap[r] = 1 / 0 (0 for a
+ * chromosome without genes).  The sorted table of one (upstream, downstream) pair is kept in the handle until another is asked for. */
+int ms_genes_promoter_overlap(const ms_genes *genes, int64_t upstream, int64_t downstream, const int32_t *chrom,
+                              const int64_t *start, const int64_t *end, int64_t n, uint8_t *overlap);
+/* Host only, no device: the draws of generate_control_regions (region/utils.py:112-145) for n_regions regions in order, replayed from
+ * the raw 32-bit words Python's generator would give next (random.getrandbits(32 * n), least significant word first).  randint(a, b)
+ * is a + _randbelow(b - a + 1), choice(seq) is seq[_randbelow(len(seq))], and _randbelow(n) takes words w until w >> (32 - bitlen(n))
+ * is < n (n == 1 consumes words too).
+ *   tss == NULL  the no-annotation path: n_random times randint(0, chrom_size[r] - length[r]) per region.
+ *   otherwise    tss / strand are the gene table's arrays and region r's chromosome owns genes [gene_lo[r], gene_hi[r]): an empty
+ *                range skips the region (nothing drawn, nothing written); distance[r] / found[r] are ms_genes_nearest_tss's, and
+ *                !found[r] draws randint(10000, 100000) once, in front of the first choice; every attempt draws a gene and keeps
+ *                start = tss + distance ('+') / tss - distance ('-') iff start >= 0 and start + length[r] <= chrom_size[r].
+ * start_out[r * n_random + j] = the j-th start kept for region r; words_used[r] = words consumed by regions 0 .. r; attempts[r]
+ * (may be NULL) = draws of a start / a gene made for region r.  *n_done = regions completed; *stop says why the replay ended and
+ * *stop_words how many words the reference would have consumed by then:
+ *   MS_REPLAY_DONE         every region is complete
+ *   MS_REPLAY_WORDS        the words ran out inside region *n_done: call again for the regions from there with more words
+ *                          (*stop_words = words_used of the last complete region)
+ *   MS_REPLAY_ATTEMPTS     region *n_done made max_attempts attempts without keeping n_random starts (the reference never ends)
+ *   MS_REPLAY_NO_SIZE      region *n_done has chrom_size == MS_REPLAY_SIZE_MISSING where the reference looks it up (KeyError)
+ *   MS_REPLAY_EMPTY_RANGE  chrom_size - length < 0 (randint raises ValueError)      MS_REPLAY_WIDE  a width >= 2^32 (not replayed) */
+#define MS_REPLAY_DONE         0
+#define MS_REPLAY_WORDS        1
+#define MS_REPLAY_ATTEMPTS     2
+#define MS_REPLAY_NO_SIZE      3
+#define MS_REPLAY_EMPTY_RANGE  4
+#define MS_REPLAY_WIDE         5
+#define MS_REPLAY_SIZE_MISSING INT64_MIN
+int ms_control_regions_replay_host(const uint32_t *words, int64_t n_words, int64_t n_regions, const int64_t *chrom_size,
+                                   const int64_t *length, const int64_t *gene_lo, const int64_t *gene_hi, const int64_t *distance,
+                                   const uint8_t *found, const int64_t *tss, const int8_t *strand, int32_t n_random, int64_t max_attempts,
+                                   int64_t *start_out, int64_t *words_used, int64_t *attempts, int64_t *n_done, int32_t *stop,
+                                   int64_t *stop_words);
 
 /* ---- scan (c_scan_motif) ---------------------------------------------------------------- */
 int ms_scan(const ms_pwmset *pwms, const ms_seqset *seqs, int strand_mask, uint32_t flags,

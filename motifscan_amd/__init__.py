@@ -6,6 +6,8 @@ motifscan_amd -- MI355X-native drop-in for ONE hot path of shao-lab/MotifScan: t
     motifscan_amd.cscore    c_scan_motif / c_score with the reference's signatures
     motifscan_amd.scanner   Scanner / MotifSite / make_motif_sites / deduplicate_motif_sites
     motifscan_amd.matrix    PFM -> PPM -> PWM log-odds definitions
+    motifscan_amd.annotation  Gene / Genes / RefGeneTxtParser / read_gene_annotation (genome/annotation.py)
+    motifscan_amd.regions   GenomicRegion / RegionArray / subset_by_location / generate_control_regions / dis_to_nearest_gene
     motifscan_amd.dist      region sharding over the GPUs of a node + the one all-reduce
     motifscan_amd.synth     seeded synthetic workloads (bench.py, tests)
 

@@ -19,6 +19,8 @@ MS_OK, MS_ERR_INVALID, MS_ERR_NOMEM, MS_ERR_RUNTIME = 0, 1, 2, 3
 MS_SCAN_DEFAULT, MS_SCAN_EXACT_ONLY, MS_SCAN_COUNTS_ONLY = 0, 1, 2
 MS_STREAM_DEDUP, MS_STREAM_NO_HITS, MS_STREAM_EXACT_ONLY, MS_STREAM_PACKED, MS_STREAM_HOST_PACK, MS_STREAM_PACKED12 = 1, 2, 4, 8, 16, 32
 MS_PROFILE_UNSMOOTHED = 1
+MS_REPLAY_DONE, MS_REPLAY_WORDS, MS_REPLAY_ATTEMPTS, MS_REPLAY_NO_SIZE, MS_REPLAY_EMPTY_RANGE, MS_REPLAY_WIDE = 0, 1, 2, 3, 4, 5
+MS_REPLAY_SIZE_MISSING = -(1 << 63)
 
 
 class ScanStats(ctypes.Structure):
@@ -114,6 +116,12 @@ def lib():
         "ms_genome_base_counts": (c_int, [vp, pi64]),
         "ms_genome_window_filter": (c_int, [vp, pi64, c_i64, c_i32, c_i32, pi64, c_i64, c_i64, pi64, pi64]),
         "ms_randint_replay_host": (c_int, [pu32, c_i64, pi64, c_i64, pi64, pi64, pi64]),
+        "ms_genes_create": (c_int, [pi64, c_i32, pi64, pi8, pvp]),
+        "ms_genes_free": (None, [vp]),
+        "ms_genes_nearest_tss": (c_int, [vp, pi32, pi64, c_i64, c_i64, pi64, pu8]),
+        "ms_genes_promoter_overlap": (c_int, [vp, c_i64, c_i64, pi32, pi64, pi64, c_i64, pu8]),
+        "ms_control_regions_replay_host": (c_int, [pu32, c_i64, c_i64, pi64, pi64, pi64, pi64, pi64, pu8, pi64, pi8, c_i32, c_i64,
+                                                   pi64, pi64, pi64, pi64, pi32, pi64]),
         "ms_scan": (c_int, [vp, vp, c_int, c_u32, pvp]),
         "ms_scan_sweep": (c_int, [vp, vp, c_i32, c_i64, c_i64, c_i32, c_i32, c_int, c_u32, pvp]),
         "ms_scan_regions_once": (c_int, [vp, vp, pi32, pi64, pi64, c_i64, c_int, c_u32, pvp]),
@@ -517,6 +525,82 @@ def randint_replay(words, high):
     check(lib().ms_randint_replay_host(ptr(words, ctypes.c_uint32), words.size, ptr(high, ctypes.c_int64), high.size,
                                        ptr(start, ctypes.c_int64), ptr(used, ctypes.c_int64), ctypes.byref(done)))
     return start, used, done.value
+
+
+class GeneTable:
+    """ms_genes: a gene table (chromosome offsets, tss, strand 1 '+' / 2 '-', file order per chromosome).  Made on the host; the device
+    copy is made by the first nearest_tss / promoter_overlap call (which need a device, as every compute entry does)."""
+
+    def __init__(self, chrom_offsets, tss, strand):
+        self.chrom_offsets = np.ascontiguousarray(chrom_offsets, dtype=np.int64)
+        self.tss = np.ascontiguousarray(tss, dtype=np.int64)
+        self.strand = np.ascontiguousarray(strand, dtype=np.int8)
+        if self.chrom_offsets.ndim != 1 or self.chrom_offsets.size < 1 or not (self.tss.size == self.strand.size == int(self.chrom_offsets[-1])):
+            raise ValueError("need chrom_offsets[n_chroms + 1] and chrom_offsets[-1] genes in tss and strand")
+        h = ctypes.c_void_p()
+        check(lib().ms_genes_create(ptr(self.chrom_offsets, ctypes.c_int64), self.chrom_offsets.size - 1, ptr(self.tss, ctypes.c_int64),
+                                    ptr(self.strand, ctypes.c_int8), ctypes.byref(h)))
+        self.h = h
+
+    def nearest_tss(self, chrom_idx, start, cutoff=10000):
+        """(distance int64, found bool) of dis_to_nearest_gene for every region (ms_genes_nearest_tss)."""
+        ci = np.ascontiguousarray(chrom_idx, dtype=np.int32)
+        st = np.ascontiguousarray(start, dtype=np.int64)
+        if ci.shape != st.shape or ci.ndim != 1:
+            raise ValueError("chrom_idx and start must have one entry per region")
+        dist, found = np.zeros(ci.size, dtype=np.int64), np.zeros(ci.size, dtype=np.uint8)
+        check(lib().ms_genes_nearest_tss(self.h, ptr(ci, ctypes.c_int32), ptr(st, ctypes.c_int64), ci.size, int(cutoff),
+                                         ptr(dist, ctypes.c_int64), ptr(found, ctypes.c_uint8)))
+        return dist, found.astype(bool)
+
+    def promoter_overlap(self, chrom_idx, start, end, upstream=2000, downstream=2000):
+        """bool per region: subset_by_location's overlap with the chromosome's promoters (ms_genes_promoter_overlap)."""
+        ci = np.ascontiguousarray(chrom_idx, dtype=np.int32)
+        st = np.ascontiguousarray(start, dtype=np.int64)
+        en = np.ascontiguousarray(end, dtype=np.int64)
+        if not (ci.shape == st.shape == en.shape) or ci.ndim != 1:
+            raise ValueError("chrom_idx, start and end must have one entry per region")
+        out = np.zeros(ci.size, dtype=np.uint8)
+        check(lib().ms_genes_promoter_overlap(self.h, int(upstream), int(downstream), ptr(ci, ctypes.c_int32), ptr(st, ctypes.c_int64),
+                                              ptr(en, ctypes.c_int64), ci.size, ptr(out, ctypes.c_uint8)))
+        return out.astype(bool)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ms_genes_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+
+def control_regions_replay(words, chrom_size, length, n_random, max_attempts=1, gene_lo=None, gene_hi=None, distance=None, found=None,
+                           tss=None, strand=None):
+    """ms_control_regions_replay_host over the regions given: (start [n, n_random], words_used [n], attempts [n], n_done, stop,
+    stop_words).  tss=None is the no-annotation path.  No device."""
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    chrom_size = np.ascontiguousarray(chrom_size, dtype=np.int64)
+    length = np.ascontiguousarray(length, dtype=np.int64)
+    n, n_random = chrom_size.size, int(n_random)
+    if length.size != n:
+        raise ValueError("need one chromosome size and one length per region")
+    args = [None] * 6
+    if tss is not None:
+        args = [np.ascontiguousarray(gene_lo, dtype=np.int64), np.ascontiguousarray(gene_hi, dtype=np.int64),
+                np.ascontiguousarray(distance, dtype=np.int64), np.ascontiguousarray(found, dtype=np.uint8),
+                np.ascontiguousarray(tss, dtype=np.int64), np.ascontiguousarray(strand, dtype=np.int8)]
+        if any(a.size != n for a in args[:4]) or args[4].size != args[5].size:
+            raise ValueError("need one gene range, distance and found flag per region, and one strand per tss")
+        if n and (args[0].min() < 0 or args[1].max() > args[4].size):
+            raise ValueError("gene range outside the gene table")
+    start = np.zeros((n, max(n_random, 0)), dtype=np.int64)
+    used, attempts = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    done, stop, stop_words = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int64()
+    cts = (ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint8, ctypes.c_int64, ctypes.c_int8)
+    check(lib().ms_control_regions_replay_host(ptr(words, ctypes.c_uint32), words.size, n, ptr(chrom_size, ctypes.c_int64),
+                                               ptr(length, ctypes.c_int64), *[None if a is None else ptr(a, ct) for a, ct in zip(args, cts)],
+                                               n_random, int(max_attempts), ptr(start, ctypes.c_int64), ptr(used, ctypes.c_int64),
+                                               ptr(attempts, ctypes.c_int64), ctypes.byref(done), ctypes.byref(stop), ctypes.byref(stop_words)))
+    return start, used, attempts, done.value, stop.value, stop_words.value
 
 
 def _owned_array(address, ctype, n, dtype, owner):

@@ -25,6 +25,7 @@ import os
 import numpy as np
 
 from . import _lib
+from .regions import RegionArray
 from .sites import MotifSite, MotifSites, RegionSites  # noqa: F401  (MotifSite is part of this module's surface, scanner.py:16)
 
 logger = logging.getLogger(__name__)
@@ -96,6 +97,24 @@ class Scanner:
         logger.debug("Extracting sequences")
         whole = self.window_size <= 0
         resident = isinstance(genome, _lib.ResidentGenome)
+        if resident and isinstance(regions, RegionArray):
+            # a region list that is already arrays (regions.generate_control_regions): the same starts and ends by array arithmetic.
+            # Only the chromosome names some region uses are looked up, as in the loop below.
+            sizes = np.zeros(len(regions.chroms), dtype=np.int64)
+            to_genome = np.zeros(len(regions.chroms), dtype=np.int32)
+            for k in np.unique(regions.chrom_idx).tolist():
+                to_genome[k] = genome.index[regions.chroms[k]]
+                if not whole:
+                    sizes[k] = genome.chrom_sizes[regions.chroms[k]]
+            if whole:
+                lo, hi = regions.start, regions.end
+            else:
+                lo = np.maximum(regions.summit - self.extend, 0)
+                hi = np.minimum(regions.summit + self.extend, sizes[regions.chrom_idx])
+            self._starts, self._ends = lo.tolist(), hi.tolist()
+            self._resident = (genome, to_genome[regions.chrom_idx])
+            self._sequences = None
+            return
         chrom_idx = []
         for region in regions:
             if whole:
