@@ -1,5 +1,6 @@
 // ms_handles.h -- private to libmotifscan_amd: per-device state and the structs behind the opaque handles of
-// include/motifscan_amd.h, shared by ms_api.hip (scan pipeline) and ms_stream.hip (batch streams, host-streamed sweeps).
+// include/motifscan_amd.h, shared by the library's translation units: ms_context.hip (device contexts, pools), ms_pwmset.hip, ms_seqset.hip,
+// ms_result.hip (one per handle), ms_scan.hip (scan pipeline), ms_regions.hip and ms_stream.hip (batch streams, host-streamed sweeps).
 #pragma once
 #include <sched.h>
 #include <atomic>
@@ -21,7 +22,7 @@ struct Scratch {                 // grow-only work buffers of the scan pipeline
     uint64_t *keys = nullptr;     double *vals = nullptr;   uint64_t *keys_sorted = nullptr;  size_t hit_cap = 0;
     void *sort_tmp = nullptr;     size_t sort_tmp_bytes = 0;
     unsigned int *chunk_counters = nullptr;    size_t chunk_counters_cap = 0;   // per LDS tile: the pre-filter's chunk dispenser
-    unsigned long long *counters = nullptr;      // 8 words, see scan_locked
+    unsigned long long *counters = nullptr;      // 8 words: [0] candidate record slots, [1] hits, [2] runs ordered by order_overflow_kernel (ms_scan.hip)
     unsigned long long *h_counters = nullptr;    // pinned
 };
 
@@ -85,7 +86,7 @@ int get_ctx(int device, DeviceCtx **out);
 int current_device();                 // the calling thread's device (ms_set_device)
 void set_current_device(int device);  // thread-local only; no HIP call
 
-// Give every cached block of the calling thread's device back to the driver (ms_api.hip); returns the bytes released.
+// Give every cached block of the calling thread's device back to the driver (ms_context.hip); returns the bytes released.
 size_t pool_trim_current_device();
 // ms_hostpack.cpp: convert_seq and the region hints on host threads (units of 32 bases / blocks of 64 positions [u0, u1) / [b0, b1))
 void host_pack_units(const uint8_t *bases, int64_t n_bases, int64_t u0, int64_t u1, uint32_t *codes, uint32_t *nmask);
@@ -131,6 +132,14 @@ void pool_free(DeviceCtx *c, void *p, size_t bytes);
 void *pinned_alloc(size_t bytes, size_t *got);
 void pinned_free(void *p, size_t bytes);
 
+// (strand mask, cutoffs, exact-only): what a PWM set's memos about its scans -- the hit density, "plans without a wide tile" -- are keyed by
+struct ScanKey {
+    int strand = -1;
+    uint64_t cutoff_version = 0;
+    bool exact_only = false;
+    bool operator==(const ScanKey &o) const { return strand == o.strand && cutoff_version == o.cutoff_version && exact_only == o.exact_only; }
+};
+
 }  // namespace ms
 
 // ------------------------------------------------------------------------- handles --
@@ -158,12 +167,10 @@ struct ms_pwmset {
     double *d_max_raw = nullptr;
     double *d_cutoff = nullptr;
     double *d_raw_floor = nullptr;
-    // what the last scan with these PWMs found, for the one-sync form of the next (scan_locked): hits per window, and how far
-    // above it the next count may be before the prediction counts as failed
+    // what the last scan with these PWMs (the one pred_key names) found, for the one-sync form of the next (ms_scan.hip, scan_locked):
+    // hits per window, and how far above it the next count may be before the prediction counts as failed
     double pred_density = -1.0, pred_margin = 0.06;
-    int pred_strand = -1;
-    uint64_t pred_cutoff_version = 0;
-    bool pred_exact_only = false;
+    ms::ScanKey pred_key;
     // pre-filter plan (lazy, keyed by strand mask / cutoffs / LDS budget / exact-only)
     ms::PrefilterPlan plan;
     int plan_strand = -1;
@@ -172,10 +179,8 @@ struct ms_pwmset {
     bool plan_exact_only = false;
     bool plan_pair = true;                        // paired rows in the plan (always, but for MS_MEASURE=1 MS_PF_PAIR=0)
     int plan_device = -1;
-    // (strand, cutoffs, exact-only) for which a set WITH motifs of >= 32 columns is known to plan without a wide tile (scan_locked)
-    int narrow_strand = -1;
-    uint64_t narrow_cutoff_version = 0;
-    bool narrow_exact_only = false;
+    // (strand, cutoffs, exact-only) for which a set WITH motifs of >= 32 columns is known to plan without a wide tile (ms_scan.hip, scan_plan)
+    ms::ScanKey narrow_key;
     uint4 *d_tables = nullptr;
     ms::TileDesc *d_tiles = nullptr;
     int32_t *d_group_fields = nullptr;            // [table groups][kGroupFields] motif of the field, -1 = empty
@@ -281,17 +286,17 @@ struct PendingScan {
 constexpr int MS_SCAN_PENDING = 1000;        // scan_locked: queued, call scan_complete
 constexpr int MS_SCAN_RETRY = 1001;          // scan_complete: the prediction failed, run scan_locked(..., MS_SCAN_NO_PREDICT_INTERNAL) again
 int pending_scan_init(PendingScan *p);
-// a slot from the device's cache (or a new one), and back (ms_api.hip); a slot that holds an unfinished scan must not be released
+// a slot from the device's cache (or a new one), and back (ms_scan.hip); a slot that holds an unfinished scan must not be released
 PendingScan *pending_scan_acquire(DeviceCtx *c);
 void pending_scan_release(DeviceCtx *c, PendingScan *p);
 void pending_scan_destroy(PendingScan *p);
 // waits for a pending scan; MS_OK: *out is the result; MS_SCAN_RETRY: nothing was produced.  The caller holds pwms->mu.
 int scan_complete(DeviceCtx *c, ms_pwmset *pwms, PendingScan *p, ms_result **out);
 
-// The scan pipeline proper (ms_api.hip); the caller holds c->mu and pwms->mu.  pend != nullptr: if the sizes can be predicted the
+// The scan pipeline proper (ms_scan.hip); the caller holds c->mu and pwms->mu.  pend != nullptr: if the sizes can be predicted the
 // scan is only QUEUED (returns MS_SCAN_PENDING, finish with scan_complete); otherwise it runs to the end as usual.
 int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand_mask, uint32_t flags, ms_result **out, PendingScan *pend = nullptr);
-// Hand the hits of a span scan (one region) to the windows of a fixed-stride sweep, in place of *span_res (ms_api.hip);
+// Hand the hits of a span scan (one region) to the windows of a fixed-stride sweep, in place of *span_res (ms_scan.hip);
 // the caller holds c->mu and pwms->mu.
 // counts_only: only the per-motif window counts and the number of sites are made (ms_result::counts_only: the hit accessors refuse it)
 int sweep_handout_locked(DeviceCtx *c, ms_pwmset *pwms, ms_result *span_res, int64_t span_bases, int32_t window, int32_t stride,
@@ -300,5 +305,15 @@ int pwmset_upload(ms_pwmset *p, int device, hipStream_t st);
 // One pooled device block holds everything a result owns: [counts P+1][offsets P+1][seq_idx n][pos n][score n][strand n]
 size_t result_block_bytes(int32_t P, size_t n);
 void result_carve(ms_result *r, void *blk, size_t n);
+
+// Helpers of one handle's translation unit that another unit needs (MS_HIDDEN: not exported from the shared object)
+// a block for n hits from the device's pool, carved: r->block, r->block_bytes and the array pointers (ms_result.hip; r->P is set)
+MS_HIDDEN int result_block_alloc(DeviceCtx *c, ms_result *r, size_t n);
+// the pre-filter plan for (strand mask, cutoffs, LDS budget, exact-only), cached in the set; need_device: with its device copies (ms_pwmset.hip)
+MS_HIDDEN int pwmset_plan(ms_pwmset *p, int strand_mask, size_t lds_budget, bool exact_only, bool need_device, int device);
+MS_HIDDEN DevPwm dev_pwm(const ms_pwmset *p);
+MS_HIDDEN DevSeq dev_seq(const ms_seqset *s);
+// sum_r max(L_r - W + 1, 0) from the set's sorted lengths (ms_seqset.hip)
+MS_HIDDEN int64_t windows_for_width(const ms_seqset *s, int W);
 
 }  // namespace ms

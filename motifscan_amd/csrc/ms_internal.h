@@ -13,6 +13,8 @@ namespace ms {
 
 void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 
+#define MS_HIDDEN __attribute__((visibility("hidden")))      // shared between translation units, not exported from the shared object
+
 #define MS_HIP(call)                                                                        \
     do {                                                                                    \
         hipError_t e__ = (call);                                                            \
@@ -153,6 +155,7 @@ struct PrefilterPlan {
     std::vector<GroupInfo> group_info;   // [n_groups]
     std::vector<uint32_t> tables;        // the operand image, row tile after row tile
     std::vector<TileDesc> tiles;
+    bool wide = false;                   // some tile holds a plain class of more than 2 k-blocks (a motif of 32 ... 63 columns): the single-pass kernels
     int64_t lds_bytes_per_position = 0;  // A-operand bytes read per window start
     int64_t kb_total = 0;                // k-blocks over all row tiles
     bool alln_can_hit = false;           // some pre-filter motif reports windows made of non-ACGT bases only (threshold <= 0)

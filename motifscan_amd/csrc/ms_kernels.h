@@ -84,7 +84,7 @@ struct PfArgs {
     int skip_alln;            // != 0: no motif of the plan reports a window made of non-ACGT bases only: such windows are dropped unseen
     unsigned int *chunk_counter;   // [LDS tiles][kPfCounters] words 64 bytes apart, zeroed: the units behind the waves' own first ones
     int use_counters;              // 0: a small input, one even unit per wave and no atomics
-    int wave_passes;               // per-wave hand-out: passes of 64 window starts a wave takes per atomic (scan_locked sizes it)
+    int wave_passes;               // per-wave hand-out: passes of 64 window starts a wave takes per atomic (sized on the host: ms_scan_geom.cpp)
 };
 
 

@@ -1,6 +1,6 @@
 // ms_kernels.hip -- the gfx950 kernels of the PWM scan path and their launchers.
 //
-// Data in HBM (all owned by ms_seqset / ms_pwmset, see ms_api.hip):
+// Data in HBM (all owned by ms_seqset / ms_pwmset, see ms_handles.h):
 //   codes   uint32 words, 16 bases per word, base i at bits [2*(i%16), 2*(i%16)+1]; A0 C1 G2 T3,
 //           non-ACGT stored as 0.  Regions are concatenated with no padding in between
 //           (region r = bases [offsets[r], offsets[r+1])).  kPadWords zero words follow.
@@ -50,7 +50,7 @@ __device__ __forceinline__ void emit_hit(const HitOut &H, uint32_t motif, int64_
 __device__ __forceinline__ void test_and_emit(const HitOut &H, const DevPwm &Pw, uint32_t motif, int64_t g,
                                               double fwd, double rev, int strand_mask) {
     // raw_floor: (cutoff - 1e-10) * max_raw minus 2000x the worst fp64 rounding of the sum, the divide and
-    // the subtract (ms_api.hip): below it the reference's test is false whatever the roundings do, so the
+    // the subtract (ms_pwmset.hip, pwmset_upload): below it the reference's test is false whatever the roundings do, so the
     // two IEEE divides are only paid by windows that can actually be hits
     const double floor_ = Pw.raw_floor[motif];
     const bool try_f = (strand_mask & 1) && !(fwd < floor_);
@@ -680,7 +680,7 @@ __device__ __forceinline__ void f6_pair_class(const PfArgs &A, MfWave &W, const 
 // space is decoded after every event and the hand-off is most of the kernel.  There the flags are decoded IN PLACE for the whole wave -- the
 // vector work that costs the same for one lane or 64 is well used -- and the records go straight into the wave's block of the list, its
 // place kept in scalar registers (no parking space, no pf_flush): 5.7 against 9.5 ms on the 62.5-Mbase shard (profiles/r05_dense_form.log).
-// scan_locked launches this instantiation when the PREVIOUS scan of the PWM set at these cutoffs and strands found more than
+// A scan launches this instantiation (ScanGeom::dense, ms_scan_geom.cpp) when the PREVIOUS scan of the PWM set at these cutoffs and strands found more than
 // kDenseHitsPerHalfTile hits per row tile and 64 windows.
 struct PfOut {
     unsigned long long base;   // next free slot of this wave's block in the global candidate list
@@ -882,7 +882,7 @@ __device__ __forceinline__ void f6_class2(const PfArgs &A, MfWave &W, PfOut &O, 
 // Work is handed out per WAVE, without a barrier in the loop: a wave's first unit is its own number, every further unit one
 // atomicAdd on one of the tile's kPfCounters counter words (64 bytes apart; the blocks are dealt round-robin onto them and a word
 // hands out every kPfCounters-th unit), requested before the current unit is scanned (the atomic's latency hides behind the unit);
-// a unit = wave_passes x 64 consecutive window starts, sized on the host (scan_locked).  A block whose CU is still busy with another
+// a unit = wave_passes x 64 consecutive window starts, sized on the host (ms_scan_geom.cpp).  A block whose CU is still busy with another
 // stream's kernel starts late and simply takes fewer units (profiles/r02_stream_coexistence.log, r02_wave_occupancy_ab.log).
 // MAXNK: 2 = the kernel for plans whose row tiles all have 1 or 2 k-blocks (motifs of up to 31 columns: every JASPAR-like set);
 // 4 = the kernel that also knows row tiles of 3 and 4 k-blocks (its register allocation spills in rare paths).

@@ -311,6 +311,7 @@ int build_plan(const double *values, const int64_t *val_off, const int32_t *widt
                 q++;
             }
             t.table_len16 = (uint32_t) (used / 16);
+            plan->wide = plan->wide || t.max_nk > 2;
             plan->tiles.push_back(t);
         }
     }

@@ -1,0 +1,748 @@
+// ms_scan.hip -- the scan pipeline: pre-filter -> fp64 re-score of the candidates (+ motifs the filter cannot take) -> order ->
+// coordinates.  scan_locked is a driver over named stages (scan_plan, scan_front, scan_back, ...) that share one ScanCtx; what a scan
+// decides before its first launch is ScanGeom (ms_scan_geom.cpp: host arithmetic on sizes).  Also the scans that are queued and
+// finished later (PendingScan), ms_scan, and the window sweep's hand-out with ms_scan_sweep.
+#include <algorithm>
+#include <cmath>
+#include <climits>
+#include <cstring>
+#include <memory>
+#include <mutex>
+
+#include "ms_handles.h"
+#include "ms_scan_geom.h"
+
+namespace ms {
+
+static int scratch_reserve(Scratch &sc, size_t cand_cap, size_t hit_cap) {
+    int rc;
+    if (cand_cap > sc.cand_cap) {
+        dev_free(sc.cand);
+        sc.cand_cap = 0;
+        if ((rc = dev_alloc(&sc.cand, cand_cap))) return rc;
+        sc.cand_cap = cand_cap;
+    }
+    if (hit_cap > sc.hit_cap) {
+        dev_free(sc.keys); dev_free(sc.vals); dev_free(sc.keys_sorted);
+        sc.hit_cap = 0;
+        if ((rc = dev_alloc(&sc.keys, hit_cap))) return rc;
+        if ((rc = dev_alloc(&sc.vals, hit_cap))) return rc;
+        if ((rc = dev_alloc(&sc.keys_sorted, hit_cap))) return rc;
+        sc.hit_cap = hit_cap;
+    }
+    return MS_OK;
+}
+
+// ------------------------------------------------------------------- pending scans --
+
+int pending_scan_init(PendingScan *p) {
+    for (auto &e : p->ev) MS_HIP(hipEventCreate(&e));
+    MS_HIP(hipEventCreateWithFlags(&p->done, hipEventDisableTiming));
+    MS_HIP(hipHostMalloc(&p->h_counters, 8 * sizeof(unsigned long long)));
+    return MS_OK;
+}
+
+PendingScan *pending_scan_acquire(DeviceCtx *c) {
+    {
+        std::lock_guard<std::mutex> lk(c->pend_mu);
+        if (!c->pend_cache.empty()) { PendingScan *p = c->pend_cache.back(); c->pend_cache.pop_back(); return p; }
+    }
+    PendingScan *p = new (std::nothrow) PendingScan();
+    if (!p) { set_error("out of host memory"); return nullptr; }
+    if (pending_scan_init(p) != MS_OK) { pending_scan_destroy(p); delete p; return nullptr; }
+    return p;
+}
+
+void pending_scan_release(DeviceCtx *c, PendingScan *p) {
+    if (!p) return;
+    if (p->raw) { ms_result_free(p->raw); p->raw = nullptr; }
+    p->active = false;
+    std::lock_guard<std::mutex> lk(c->pend_mu);
+    if (c->pend_cache.size() < 8) { c->pend_cache.push_back(p); return; }
+    pending_scan_destroy(p);
+    delete p;
+}
+
+void pending_scan_destroy(PendingScan *p) {
+    for (auto &e : p->ev) if (e) (void) hipEventDestroy(e);
+    if (p->done) (void) hipEventDestroy(p->done);
+    if (p->h_counters) (void) hipHostFree(p->h_counters);
+    if (p->h_offsets) (void) hipHostFree(p->h_offsets);
+    *p = PendingScan();
+}
+
+// stage times, counts and the next scan's prediction, once a scan's kernels are known to be done
+static void finish_scan(ms_result *raw, hipEvent_t *ev, ms_pwmset *pwms, int64_t n_bases, int64_t R, const ScanKey &key,
+                        unsigned long long n_cand, unsigned long long n_hits, bool with_back, unsigned long long n_overflow) {
+    ms_scan_stats &stt = raw->stats;
+    stt.order_overflow_runs = (int32_t) std::min<unsigned long long>(n_overflow, INT32_MAX);
+    stt.n_candidates = (int64_t) n_cand;
+    stt.n_hits = (int64_t) n_hits;
+    raw->n_hits = (int64_t) n_hits;
+    int64_t pwm_bytes = 0;
+    for (int32_t p = 0; p < pwms->P; p++) pwm_bytes += 32LL * pwms->widths[p];
+    // compulsory HBM bytes of one call
+    stt.hbm_bytes_algorithmic = (n_bases + 3) / 4 + (n_bases + 7) / 8 + 8 * (R + 1) + pwm_bytes + 16 * (int64_t) n_hits + 8LL * pwms->P;
+    float ms01 = 0, ms12 = 0, ms34 = 0, ms45 = 0, ms05 = 0;
+    (void) hipEventElapsedTime(&ms01, ev[0], ev[1]);
+    (void) hipEventElapsedTime(&ms12, ev[1], ev[2]);
+    stt.ms_prefilter = ms01; stt.ms_exact = ms12; stt.ms_total = ms01 + ms12;
+    if (with_back) {
+        (void) hipEventElapsedTime(&ms34, ev[3], ev[4]);
+        (void) hipEventElapsedTime(&ms45, ev[4], ev[5]);
+        (void) hipEventElapsedTime(&ms05, ev[0], ev[5]);
+        stt.ms_sort = ms34; stt.ms_finalize = ms45; stt.ms_total = ms05;
+    }
+    if (stt.n_windows > 0) {            // what the next scan of this set of PWMs may expect (scan_locked)
+        pwms->pred_density = (double) n_hits / (double) stt.n_windows;
+        pwms->pred_key = key;
+    }
+}
+
+// The end of a scan whose sizes were predicted: did the scratch buffers and the predicted hit count hold?  A prediction that held
+// narrows the margin of the next scans; one that failed doubles it, and the density is learnt again through the exactly-sized form.
+static bool prediction_held(ms_pwmset *pwms, unsigned long long n_cand, size_t cand_cap, unsigned long long n_hits, size_t hit_cap, size_t n_pred) {
+    if (n_cand <= cand_cap && n_hits <= hit_cap && n_hits <= n_pred) {
+        pwms->pred_margin = std::max(0.04, pwms->pred_margin * 0.9);
+        return true;
+    }
+    pwms->pred_margin = std::min(1.0, pwms->pred_margin * 2.0);
+    pwms->pred_density = -1.0;
+    return false;
+}
+
+int scan_complete(DeviceCtx *c, ms_pwmset *pwms, PendingScan *p, ms_result **out) {
+    *out = nullptr;
+    if (!p || !p->active) { set_error("no pending scan"); return MS_ERR_INVALID; }
+    p->active = false;
+    ms_result *raw = p->raw;
+    p->raw = nullptr;
+    hipError_t he = hipEventSynchronize(p->done);
+    if (he != hipSuccess) { set_error("scan kernels failed: %s", hipGetErrorString(he)); ms_result_free(raw); return MS_ERR_RUNTIME; }
+    const unsigned long long n_cand = p->cand_static + p->h_counters[0], n_hits = p->h_counters[1];
+    (void) c;
+    if (!prediction_held(pwms, n_cand, p->cand_cap, n_hits, p->hit_cap, p->n_pred)) { ms_result_free(raw); return MS_SCAN_RETRY; }
+    const size_t n_off = raw->motif_offsets.size();      // (copied in stream order, in front of `done`: pending_fill)
+    std::memcpy(raw->motif_offsets.data(), p->h_offsets, n_off * sizeof(int64_t));
+    try { raw->h_region_counts.assign(p->h_offsets + n_off, p->h_offsets + n_off + raw->P); } catch (const std::bad_alloc &) { raw->h_region_counts.clear(); }
+    finish_scan(raw, p->ev, pwms, p->n_bases, p->R, ScanKey{p->strand_mask, pwms->cutoff_version, p->exact_only}, n_cand, n_hits, true, p->h_counters[2]);
+    *out = raw;
+    return MS_OK;
+}
+
+// ------------------------------------------------------------------ the scan's stages --
+
+// What the stages of one scan share.  The caller of scan_locked holds c->mu (one scan at a time per device: shared scratch) and
+// pwms->mu (lazily cached device copies / plan).
+struct ScanCtx {
+    DeviceCtx *c = nullptr;
+    ms_pwmset *pwms = nullptr;
+    const ms_seqset *seqs = nullptr;
+    ms_result *raw = nullptr;
+    int strand_mask = 3;
+    uint32_t flags = 0;
+    ScanKey key;
+    ScanGeom g;
+    hipEvent_t *ev = nullptr;            // stage events of this scan: the device's, or a pending scan's own set
+    DevSeq S;
+    DevPwm Pw;
+    bool counts_ok = false;              // a counts-only scan whose set the bitmap form takes (scan_counts_fast)
+};
+
+// The plan of this scan, with its device copies.  Which kernel family it runs (PrefilterPlan::wide) decides the LDS budget it is built
+// with, so a set that may plan wide is planned under the wide budget first.
+static int scan_plan(DeviceCtx *c, ms_pwmset *pwms, const ScanKey &key, const ScanOverrides &ov) {
+    int rc;
+    // only a motif of 32 ... kMaxFastWidth columns can make a wide tile; whether one does (it may fall to the all-fp64 path) the plan says.
+    // The outcome is remembered per (strand, cutoffs, exact-only): a set whose wide motifs all left the pre-filter plans once, not twice per scan
+    bool may_be_wide = false, wide = false;
+    for (int32_t w : pwms->widths) may_be_wide = may_be_wide || (w >= 2 * kF6Cols && w <= kMaxFastWidth);
+    if (may_be_wide && !key.exact_only && !(pwms->narrow_key == key)) {
+        if ((rc = pwmset_plan(pwms, key.strand, scan_lds_budget(c->lds_max, true, ov), key.exact_only, false, c->device))) return rc;
+        wide = pwms->plan.wide;
+        if (!wide) pwms->narrow_key = key;
+    }
+    return pwmset_plan(pwms, key.strand, scan_lds_budget(c->lds_max, wide, ov), key.exact_only, true, c->device);
+}
+
+// the result handle, with the statistics that follow from the sizes alone; *fast_windows: the windows of the motifs on the pre-filter
+static ms_result *scan_result_new(DeviceCtx *c, const ms_pwmset *pwms, const ms_seqset *seqs, int strand_mask, int64_t *fast_windows) {
+    const PrefilterPlan &plan = pwms->plan;
+    std::unique_ptr<ms_result> res(new (std::nothrow) ms_result());
+    if (!res) { set_error("out of host memory"); return nullptr; }
+    res->device = c->device;
+    res->P = pwms->P;
+    res->R = seqs->R;
+    res->motif_offsets.assign((size_t) pwms->P + 1, 0);
+    ms_scan_stats &stt = res->stats;
+    std::memset(&stt, 0, sizeof(stt));
+    stt.n_bases = seqs->n_bases;
+    stt.n_pwms = pwms->P;
+    stt.n_pwms_exact = (int32_t) plan.exact_motifs.size();
+    stt.n_tiles = (int32_t) plan.tiles.size();
+    int64_t cells = 0;                                                          // (window, column) pairs of one strand
+    *fast_windows = 0;
+    for (int32_t p = 0; p < pwms->P; p++) stt.n_windows += windows_for_width(seqs, pwms->widths[p]);
+    for (int32_t p : plan.fast_motifs) {
+        *fast_windows += windows_for_width(seqs, pwms->widths[p]);
+        cells += windows_for_width(seqs, pwms->widths[p]) * pwms->widths[p];
+    }
+    const int64_t padded = ((seqs->n_bases + 63) / 64) * 64;
+    stt.lds_bytes_read = plan.lds_bytes_per_position * padded / (plan.wide ? 1 : 2);      // (the double pass reads a row tile's operand once for 128 window starts)
+    stt.pf_engine = 3;
+    stt.mfma_ops_algorithmic = 2 * (strand_mask == 3 ? 2 : 1) * cells;           // one multiply-add per cell and strand
+    stt.mfma_ops = padded / 32 * plan.kb_total * (2LL * 32 * 32 * 64);           // one 32x32x64 instruction per (32 windows, row tile, k-block)
+    return res.release();
+}
+
+// nothing to scan: [] / [[]...]  (cscore.c:443-445)
+static int scan_empty(ScanCtx &x) {
+    int rc;
+    if ((rc = result_block_alloc(x.c, x.raw, 0))) return rc;
+    hipError_t he = hipMemsetAsync(x.raw->block, 0, 16 * ((size_t) x.pwms->P + 1), x.c->stream);       // counts and offsets: all zero
+    if (he == hipSuccess) he = hipStreamSynchronize(x.c->stream);
+    if (he != hipSuccess) { set_error("memset failed: %s", hipGetErrorString(he)); return MS_ERR_RUNTIME; }
+    return MS_OK;
+}
+
+static HitOut scan_hit_out(const ScanCtx &x) {
+    const Scratch &sc = x.c->sc;
+    HitOut H;
+    H.keys = sc.keys; H.vals = sc.vals; H.n_hits = sc.counters + 1; H.cap = sc.hit_cap; H.gbits = x.g.gbits; H.pbits = x.g.pbits;
+    return H;
+}
+
+// "fetch the eight counters and wait": counters [0] candidate record slots, [1] hits, [2] runs ordered by order_overflow_kernel
+static int fetch_counters(DeviceCtx *c, const char *what) {
+    hipError_t he = hipMemcpyAsync(c->sc.h_counters, c->sc.counters, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+    if (he != hipSuccess) { set_error("%s failed: %s", what, hipGetErrorString(he)); return MS_ERR_RUNTIME; }
+    return MS_OK;
+}
+
+// the pre-filter's launch, in the geometry ScanGeom holds
+static int scan_prefilter(ScanCtx &x) {
+    DeviceCtx *c = x.c;
+    Scratch &sc = c->sc;
+    const ScanGeom &g = x.g;
+    int rc;
+    PfArgs A;
+    A.codes = x.S.codes; A.nmask = x.S.nmask; A.n_bases = x.S.n_bases; A.skip_alln = x.pwms->plan.alln_can_hit ? 0 : 1;
+    A.tables = x.pwms->d_tables; A.tiles = x.pwms->d_tiles;
+    A.lut_off16 = g.lut_off16; A.stage_off16 = g.stage_off16; A.emit_off16 = g.emit_off16; A.onehot_off16 = g.onehot_off16; A.rare_off16 = g.rare_off16;
+    A.rare_cap = g.rare_cap;
+    A.cand = sc.cand; A.n_cand = sc.counters; A.cand_cap = sc.cand_cap; A.cand_block = g.cand_block; A.cand_static = g.cand_static;
+    const size_t counter_words = (size_t) g.n_tiles * kPfCounters * 16;            // kPfCounters words per tile, 64 bytes apart
+    if (counter_words > sc.chunk_counters_cap) {
+        dev_free(sc.chunk_counters);
+        sc.chunk_counters_cap = 0;
+        if ((rc = dev_alloc(&sc.chunk_counters, counter_words + 16))) return rc;
+        sc.chunk_counters_cap = counter_words + 16;
+    }
+    A.chunk_counter = sc.chunk_counters;
+    A.wave_passes = g.wave_passes;
+    A.use_counters = g.counter_used ? 1 : 0;
+    if (g.counter_used) {
+        hipError_t he = hipMemsetAsync(A.chunk_counter, 0, sizeof(unsigned int) * counter_words, c->stream);
+        if (he != hipSuccess) { set_error("memset failed: %s", hipGetErrorString(he)); return MS_ERR_RUNTIME; }
+    }
+    const int li = g.wide ? 2 : g.dense ? 1 : 0;
+    if (g.lds_bytes > c->lds_set[li]) {
+        if ((rc = prefilter_set_lds(g.wide, g.dense, g.lds_bytes))) return rc;
+        c->lds_set[li] = g.lds_bytes;
+    }
+    return launch_prefilter(A, g.wide, g.dense, g.bpt, g.n_tiles, g.lds_bytes, c->stream);
+}
+
+// pre-filter + fp64 stage of one pass, queued on the scan stream (events 0, 1, 2 around the two stages)
+static int scan_front(ScanCtx &x, const HitOut &H) {
+    DeviceCtx *c = x.c;
+    Scratch &sc = c->sc;
+    const PrefilterPlan &plan = x.pwms->plan;
+    int rc;
+    hipError_t he = hipMemsetAsync(sc.counters, 0, 8 * sizeof(unsigned long long), c->stream);
+    if (he != hipSuccess) { set_error("memset failed: %s", hipGetErrorString(he)); return MS_ERR_RUNTIME; }
+    (void) hipEventRecord(x.ev[0], c->stream);
+    if (x.g.n_tiles > 0 && (rc = scan_prefilter(x))) return rc;
+    (void) hipEventRecord(x.ev[1], c->stream);
+    if (!plan.fast_motifs.empty()) {                 // (few blocks for a small scan measured slower: the kernel is a chain of dependent gathers and wants every record in flight at once)
+        if (x.g.rescore_carry) {
+            if (!c->rc_lds_set) { if ((rc = rescore_carry_set_lds())) return rc; c->rc_lds_set = true; }
+            if ((rc = launch_rescore_carry(x.S, x.Pw, sc.cand, sc.counters, x.g.cand_static, sc.cand_cap, x.pwms->d_field_meta, x.strand_mask, H, c->n_cu, c->stream))) return rc;
+        } else if ((rc = launch_rescore(x.S, x.Pw, sc.cand, sc.counters, x.g.cand_static, sc.cand_cap, x.pwms->d_field_meta, x.strand_mask, H, c->n_cu * 8, c->stream))) return rc;
+    }
+    if (!plan.exact_motifs.empty()) {
+        int max_w = 0;
+        for (int32_t m : plan.exact_motifs) max_w = std::max(max_w, (int) x.pwms->widths[m]);
+        if ((rc = launch_exact_all(x.S, x.Pw, x.pwms->d_exact_motifs, (int32_t) plan.exact_motifs.size(), x.strand_mask, H, c->stream, max_w))) return rc;
+    }
+    (void) hipEventRecord(x.ev[2], c->stream);
+    return MS_OK;
+}
+
+// counts only: the flag map costs ~2 x P x R bytes of traffic (clear + count), the ordering it replaces ~200 bytes per hit -- so the map is
+// taken where the set holds at least one hit per ~50 (motif, region) cells (configs[3]: one per 9; a million 50-bp regions: one per 100,
+// where the sort is the cheaper way to the same counts).  Decided before the result block is sized (a second, exactly-sized run after a
+// failed prediction decides again).
+static bool scan_counts_fast(const ScanCtx &x, size_t n_expected) {
+    return x.counts_ok && (double) x.pwms->P * (double) x.seqs->R <= 50.0 * (double) std::max<size_t>(n_expected, 1);
+}
+
+// the complete per-motif offsets are on the device; one copy brings them to the host.  (Not for a scan that is only being
+// QUEUED: the destination is pageable memory, for which the "async" copy makes the host wait for everything queued before
+// it -- scan_complete fetches the offsets once the scan is done.)
+static int fetch_offsets(ScanCtx &x, bool queue_only) {
+    if (queue_only) return MS_OK;
+    ms_result *raw = x.raw;
+    hipError_t he = hipMemcpyAsync(raw->motif_offsets.data(), raw->d_motif_first, raw->motif_offsets.size() * sizeof(int64_t), hipMemcpyDeviceToHost, x.c->stream);
+    if (he != hipSuccess) { set_error("copy failed: %s", hipGetErrorString(he)); return MS_ERR_RUNTIME; }
+    return MS_OK;
+}
+
+// the counts-only form of scan_back: the hits are counted where the fp64 stage left them (events 4, 5 with nothing between them)
+static int back_count_only(ScanCtx &x, size_t n_sort, const unsigned long long *n_dev, bool queue_only) {
+    DeviceCtx *c = x.c;
+    ms_result *raw = x.raw;
+    const int32_t P = x.pwms->P;
+    int rc;
+    // the bitmap + the per-motif site counters in one pooled block the result owns (a queued scan's kernels outlive this call)
+    const size_t words = count_only_bitmap_words(P, x.seqs->R);
+    if ((rc = pool_alloc(c, words * 4 + 256 + 8 * (size_t) P, &raw->coord_blk, &raw->coord_bytes))) return rc;
+    uint32_t *bitmap = static_cast<uint32_t *>(raw->coord_blk);
+    unsigned long long *motif_hits = reinterpret_cast<unsigned long long *>(static_cast<char *>(raw->coord_blk) + ((words * 4 + 255) & ~(size_t) 255));
+    if ((rc = launch_count_only(c->sc.keys, (int64_t) n_sort, n_dev, x.g.gbits, x.g.pbits, x.seqs->R, P, bitmap, raw->d_region_counts, motif_hits, raw->d_motif_first, c->stream))) return rc;
+    raw->counts_only = true;
+    (void) hipEventRecord(x.ev[4], c->stream);
+    (void) hipEventRecord(x.ev[5], c->stream);
+    return fetch_offsets(x, queue_only);
+}
+
+// the radix passes over the key bits [sort_begin, end_bit) of the first n_sort slots, and the fix-up behind them for global-position keys
+static int back_sort(ScanCtx &x, size_t n_sort, const unsigned long long *n_dev, int sort_begin, size_t ovf_bytes) {
+    DeviceCtx *c = x.c;
+    Scratch &sc = c->sc;
+    int rc;
+    size_t need = 0;
+    if ((rc = sort_hit_pairs(nullptr, &need, sc.keys, sc.keys_sorted, sc.vals, x.raw->d_score, n_sort, sort_begin, x.g.end_bit, c->stream))) return rc;
+    need = std::max(need, ovf_bytes);             // (the radix temp storage is free once the passes are done: order_finalize_kernel's overflow list goes there)
+    if (need > sc.sort_tmp_bytes) {
+        if (sc.sort_tmp) (void) hipFree(sc.sort_tmp);
+        sc.sort_tmp = nullptr; sc.sort_tmp_bytes = 0;
+        unsigned char *tmp = nullptr;
+        if ((rc = dev_alloc(&tmp, need))) return rc;
+        sc.sort_tmp = tmp;
+        sc.sort_tmp_bytes = need;
+    }
+    size_t have = sc.sort_tmp_bytes;
+    if ((rc = sort_hit_pairs(sc.sort_tmp, &have, sc.keys, sc.keys_sorted, sc.vals, x.raw->d_score, n_sort, sort_begin, x.g.end_bit, c->stream))) return rc;
+    if (x.g.pbits == 0 && sort_begin) return launch_sort_fixup(sc.keys_sorted, x.raw->d_score, (int64_t) n_sort, n_dev, c->stream);
+    return MS_OK;
+}
+
+// the compact coordinate words of MS_SCAN_PACK_INTERNAL / MS_SCAN_PACK12_INTERNAL, in a pooled block the result owns
+static int back_pack_coords(ScanCtx &x, size_t n_sort, const unsigned long long *n_dev) {
+    DeviceCtx *c = x.c;
+    ms_result *raw = x.raw;
+    int rc;
+    const size_t n_round = (n_sort + 65535) & ~(size_t) 65535;
+    if ((rc = pool_alloc(c, 8 * n_round + 256, &raw->coord_blk, &raw->coord_bytes))) return rc;
+    raw->d_coord = static_cast<uint64_t *>(raw->coord_blk);
+    raw->d_coord_bad = reinterpret_cast<unsigned int *>(raw->d_coord + n_round);
+    hipError_t he = hipMemsetAsync(raw->d_coord_bad, 0, sizeof(unsigned int), c->stream);
+    if (he != hipSuccess) { set_error("memset failed: %s", hipGetErrorString(he)); return MS_ERR_RUNTIME; }
+    // the 4-byte form when asked for and the set's largest region index and position fit 31 bits beside the strand bit
+    raw->coord_shift = (x.flags & MS_SCAN_PACK12_INTERNAL) ? x.g.coord_shift12 : 0;
+    return launch_pack_hits((int64_t) n_sort, n_dev, raw->d_seq_idx, raw->d_pos, raw->d_strand, raw->d_coord, raw->d_coord_bad, c->stream, raw->coord_shift);
+}
+
+// ordering + coordinates of the first n_sort slots of the hit list into the result block (events 3, 4, 5); n_dev != nullptr:
+// only the device knows how many of them are hits (the rest are all-ones keys, which sort behind every hit).  queue_only: this
+// back belongs to a scan that is only queued (scan_complete finishes it).
+static int scan_back(ScanCtx &x, size_t n_sort, const unsigned long long *n_dev, bool counts_fast, bool queue_only) {
+    DeviceCtx *c = x.c;
+    Scratch &sc = c->sc;
+    ms_result *raw = x.raw;
+    const ScanGeom &g = x.g;
+    const int32_t P = x.pwms->P;
+    int rc;
+    hipError_t he = hipMemsetAsync(raw->d_region_counts, 0, 8 * ((size_t) P + 1), c->stream);
+    if (he != hipSuccess) { set_error("memset failed: %s", hipGetErrorString(he)); return MS_ERR_RUNTIME; }
+    (void) hipEventRecord(x.ev[3], c->stream);
+    raw->counts_only = false;
+    if (counts_fast) return back_count_only(x, n_sort, n_dev, queue_only);
+    const int sort_begin = scan_sort_begin(g, P, n_sort);
+    const size_t ovf_bytes = g.pbits > 0 && sort_begin > 0 ? order_overflow_bytes(n_sort, g.order_run_cap) : 0;
+    if (n_sort > 0 && (rc = back_sort(x, n_sort, n_dev, sort_begin, ovf_bytes))) return rc;
+    (void) hipEventRecord(x.ev[4], c->stream);
+    if (g.pbits > 0 && sort_begin > 0) {
+        // counters[2]: the runs order_finalize_kernel leaves to its overflow launch (zeroed with the others in front of the pre-filter).
+        // (A list sorted over every bit -- a short one: launch latencies, not bytes -- keeps the lighter finalize_rp_kernel.)
+        if ((rc = launch_order_finalize(sc.keys_sorted, raw->d_score, (int64_t) n_sort, n_dev, sort_begin, g.rbits, g.pbits, P, raw->d_seq_idx,
+                                        raw->d_pos, raw->d_strand, raw->d_motif_first, raw->d_region_counts, sc.keys, sc.vals, sc.sort_tmp,
+                                        ovf_bytes, sc.counters + 2, g.order_run_cap, c->stream))) return rc;
+    } else if ((rc = launch_finalize(sc.keys_sorted, (int64_t) n_sort, n_dev, g.gbits, g.rbits, g.pbits, P, x.S, raw->d_seq_idx, raw->d_pos,
+                                     raw->d_strand, raw->d_motif_first, raw->d_region_counts, c->stream))) return rc;
+    if ((x.flags & (MS_SCAN_PACK_INTERNAL | MS_SCAN_PACK12_INTERNAL)) && n_sort > 0 && (rc = back_pack_coords(x, n_sort, n_dev))) return rc;
+    (void) hipEventRecord(x.ev[5], c->stream);
+    return fetch_offsets(x, queue_only);
+}
+
+// Every launch of a scan whose sizes are PREDICTED, queued at once: the result block, the sort and the coordinate kernel are sized
+// for n_pred hits (the fp64 stage's real count stays on the device: the unused slots are filled with all-ones keys that sort last,
+// finalize reads the count there).
+static int scan_queue_predicted(ScanCtx &x, size_t n_pred, bool queue_only) {
+    Scratch &sc = x.c->sc;
+    int rc;
+    if ((rc = scratch_reserve(sc, x.g.want_cand, std::max(x.g.want_hits, n_pred)))) return rc;
+    const bool counts_fast = scan_counts_fast(x, n_pred);
+    if ((rc = result_block_alloc(x.c, x.raw, counts_fast ? 1 : n_pred))) return rc;
+    x.raw->stats.n_passes = 1;
+    if ((rc = scan_front(x, scan_hit_out(x)))) return rc;
+    if ((rc = launch_fill_tail(sc.keys, sc.counters + 1, n_pred, x.c->stream))) return rc;
+    return scan_back(x, n_pred, sc.counters + 1, counts_fast, queue_only);
+}
+
+// A predicted scan that is queued, not waited for: the owner queues its next scan behind this one first (everything is in order on one
+// stream: the next scan's kernels only touch the shared scratch after this scan's are done; a scratch buffer that has to grow
+// is freed by hipFree, which waits for the device).  What scan_complete needs goes into the slot.
+static int pending_fill(ScanCtx &x, PendingScan *pend, size_t n_pred) {
+    DeviceCtx *c = x.c;
+    const Scratch &sc = c->sc;
+    ms_result *raw = x.raw;
+    // the per-motif offsets too, in stream order, into the slot's own pinned words: scan_complete used to fetch them with a blocking hipMemcpy
+    // into pageable memory once the scan was done -- one more synchronous driver call per batch on the scan stage's thread (same pass time
+    // either way, profiles/r06z_offsets_ab.log; kept because nothing on that thread should block that need not).  The per-motif region counts
+    // ride along: the stream's copy-out stage brings them to the host with every batch, and its own small copy is one more blit kernel that
+    // has to find a CU beside the running pre-filter
+    const size_t n_off = raw->motif_offsets.size(), n_words = n_off + (size_t) x.pwms->P;
+    hipError_t he;
+    if (pend->h_offsets_cap < n_words) {
+        if (pend->h_offsets) (void) hipHostFree(pend->h_offsets);
+        pend->h_offsets = nullptr; pend->h_offsets_cap = 0;
+        he = hipHostMalloc(&pend->h_offsets, (n_words + 64) * sizeof(int64_t));
+        if (he != hipSuccess) { set_error("out of pinned host memory"); return MS_ERR_NOMEM; }
+        pend->h_offsets_cap = n_words + 64;
+    }
+    he = hipMemcpyAsync(pend->h_offsets, raw->d_motif_first, n_off * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
+    if (he == hipSuccess && x.pwms->P > 0)
+        he = hipMemcpyAsync(pend->h_offsets + n_off, raw->d_region_counts, (size_t) x.pwms->P * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(pend->h_counters, sc.counters, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
+    if (he == hipSuccess) he = hipEventRecord(pend->done, c->stream);
+    if (he != hipSuccess) { set_error("scan kernels failed: %s", hipGetErrorString(he)); return MS_ERR_RUNTIME; }
+    pend->cand_cap = sc.cand_cap;
+    pend->hit_cap = sc.hit_cap;
+    pend->active = true;
+    pend->raw = raw;
+    pend->n_pred = n_pred;
+    pend->cand_static = x.g.cand_static;
+    pend->n_bases = x.seqs->n_bases;
+    pend->R = x.seqs->R;
+    pend->strand_mask = x.strand_mask;
+    pend->exact_only = x.key.exact_only;
+    return MS_OK;
+}
+
+// The exactly-sized form: the front runs (again, with larger buffers, while one overflows), the host reads the counts, and the result
+// block, the sort and the coordinate kernel are sized by them.
+static int scan_exact(ScanCtx &x, size_t want_cand, size_t want_hits) {
+    DeviceCtx *c = x.c;
+    Scratch &sc = c->sc;
+    ms_result *raw = x.raw;
+    int rc;
+    unsigned long long n_cand = 0, n_hits = 0;
+    for (int pass = 1;; pass++) {
+        if ((rc = scratch_reserve(sc, want_cand, want_hits))) return rc;
+        raw->stats.n_passes += 1;
+        if ((rc = scan_front(x, scan_hit_out(x)))) return rc;
+        if ((rc = fetch_counters(c, "scan kernels"))) return rc;
+        n_cand = x.g.cand_static + sc.h_counters[0];
+        n_hits = sc.h_counters[1];
+        if (n_cand <= sc.cand_cap && n_hits <= sc.hit_cap) break;
+        if (pass >= 8) { set_error("scan buffers kept overflowing (%llu candidates, %llu hits)", n_cand, n_hits); return MS_ERR_RUNTIME; }
+        scan_grow(sc.cand_cap, sc.hit_cap, n_cand, n_hits, &want_cand, &want_hits);       // ... and run the pass again
+    }
+    if (x.flags & MS_SCAN_RAW_INTERNAL) {                      // the caller takes the unordered hits from the scratch
+        finish_scan(raw, x.ev, x.pwms, x.seqs->n_bases, x.seqs->R, x.key, n_cand, n_hits, false, 0);
+        raw->raw_gbits = x.g.gbits;
+        raw->raw_pbits = x.g.pbits;
+        return MS_OK;
+    }
+    // one pooled block for everything the result owns
+    const bool counts_fast = scan_counts_fast(x, (size_t) n_hits);
+    if ((rc = result_block_alloc(c, raw, counts_fast ? 1 : (size_t) n_hits))) return rc;
+    if ((rc = scan_back(x, (size_t) n_hits, nullptr, counts_fast, false))) return rc;
+    if ((rc = fetch_counters(c, "finalize"))) return rc;
+    finish_scan(raw, x.ev, x.pwms, x.seqs->n_bases, x.seqs->R, x.key, n_cand, n_hits, true, sc.h_counters[2]);
+    return MS_OK;
+}
+
+// The scan pipeline.  Three forms:
+//   predicted, synchronous -- sizes PREDICTED from the previous scan of these PWMs.  The hit density of a motif set at its cutoffs is a
+//       property of the set (p-value x windows x strands): consecutive scans -- the batches of a stream, the input and control sets of
+//       a run, a benchmark's steps -- repeat it within a fraction of a percent.  Everything is sized for the predicted count plus a
+//       margin, every launch is queued at once (scan_queue_predicted), and ONE synchronisation at the very end validates the
+//       prediction.  A wrong prediction (count above the margin, or a scratch buffer too small) costs a second, exactly-sized run
+//       and doubles the margin of the next scans.
+//   predicted, queued (pend != nullptr) -- the same launches, not waited for: MS_SCAN_PENDING, scan_complete validates.
+//   exactly sized (scan_exact) -- no prediction for this key yet, the caller forbids one, or the prediction just failed.  It always runs
+//       to the end, with or without a PendingScan slot (the first batch of a stream, whose PWM set has no prediction yet, came back
+//       with all-zero offsets when it did not).
+int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand_mask, uint32_t flags, ms_result **out, PendingScan *pend) {
+    int rc;
+    const ScanOverrides ov = read_scan_overrides();
+    ScanCtx x;
+    x.c = c; x.pwms = pwms; x.seqs = seqs; x.strand_mask = strand_mask; x.flags = flags; x.ev = c->ev;
+    if ((rc = seqset_pack_pending(seqs, c->stream))) return rc;       // a batch stream's set: its pack / hint kernels run here, in front of its pre-filter
+    if ((rc = pwmset_upload(pwms, c->device, c->stream))) return rc;
+    x.key = ScanKey{strand_mask, pwms->cutoff_version, (flags & MS_SCAN_EXACT_ONLY) != 0};
+    if ((rc = scan_plan(c, pwms, x.key, ov))) return rc;
+
+    ScanShape sh;
+    std::unique_ptr<ms_result, void (*)(ms_result *)> res(scan_result_new(c, pwms, seqs, strand_mask, &sh.fast_windows), ms_result_free);
+    if (!res) return MS_ERR_NOMEM;
+    x.raw = res.get();
+    if (pwms->P == 0 || seqs->n_bases == 0) {
+        if ((rc = scan_empty(x))) return rc;
+        *out = res.release();
+        return MS_OK;
+    }
+
+    // what the previous scan of this set at these cutoffs and strands found, per (motif, window), if there was one
+    const bool density_known = pwms->pred_density >= 0 && pwms->pred_key == x.key;
+    sh.plan = &pwms->plan; sh.P = pwms->P;
+    sh.n_bases = seqs->n_bases; sh.R = seqs->R; sh.max_len = seqs->len_sorted.empty() ? 0 : seqs->len_sorted.back();
+    sh.n_cu = c->n_cu; sh.lds_max = c->lds_max; sh.cu_reserved = c->n_streams.load() > 0 ? c->n_cu_copy : 0;
+    sh.density_known = density_known; sh.pred_density = pwms->pred_density;
+    x.g = scan_geometry(sh, ov);
+    x.S = dev_seq(seqs);
+    x.Pw = dev_pwm(pwms);
+    x.counts_ok = (flags & MS_SCAN_COUNTS_ONLY_INTERNAL) && !(flags & MS_SCAN_RAW_INTERNAL) && count_only_supported(pwms->P, seqs->R, x.g.pbits);
+    ms_scan_stats &stt = x.raw->stats;
+    if (x.g.n_tiles > 0 && x.g.dense) stt.pf_engine = 4;
+
+    Scratch &sc = c->sc;
+    size_t want_cand = x.g.want_cand, want_hits = x.g.want_hits;
+    if (density_known && !(flags & (MS_SCAN_RAW_INTERNAL | MS_SCAN_NO_PREDICT_INTERNAL)) && !ov.no_predict) {
+        if (pend) x.ev = pend->ev;
+        const double mu = pwms->pred_density * (double) stt.n_windows;
+        const size_t n_pred = (size_t) std::min<double>(mu * (1.0 + pwms->pred_margin) + 6.0 * std::sqrt(mu + 1.0) + 256.0, 3.0e9);
+        if ((rc = scan_queue_predicted(x, n_pred, pend != nullptr))) return rc;
+        if (pend) {
+            if ((rc = pending_fill(x, pend, n_pred))) return rc;
+            res.release();                           // (the slot owns the result now)
+            *out = nullptr;
+            return MS_SCAN_PENDING;
+        }
+        if ((rc = fetch_counters(c, "scan kernels"))) return rc;
+        const unsigned long long n_cand = x.g.cand_static + sc.h_counters[0], n_hits = sc.h_counters[1];
+        if (prediction_held(pwms, n_cand, sc.cand_cap, n_hits, sc.hit_cap, n_pred)) {
+            finish_scan(x.raw, x.ev, pwms, seqs->n_bases, seqs->R, x.key, n_cand, n_hits, true, sc.h_counters[2]);
+            *out = res.release();
+            return MS_OK;
+        }
+        // the prediction failed: give the blocks back and run again with exact sizes
+        pool_free(c, x.raw->block, x.raw->block_bytes);
+        x.raw->block = nullptr;
+        x.raw->block_bytes = 0;
+        if (x.raw->coord_blk) { pool_free(c, x.raw->coord_blk, x.raw->coord_bytes); x.raw->coord_blk = nullptr; x.raw->d_coord = nullptr; x.raw->d_coord_bad = nullptr; }
+        stt.n_passes = 1;
+        scan_grow(sc.cand_cap, sc.hit_cap, n_cand, n_hits, &want_cand, &want_hits);
+    }
+    if ((rc = scan_exact(x, want_cand, want_hits))) return rc;
+    *out = res.release();
+    return MS_OK;
+}
+
+// --------------------------------------------------------------------- window sweep --
+
+// The counts-only form of the hand-out: consumes r1 and raw on failure, r1 on success (ev[0] is recorded by the caller).
+static int sweep_counts_only(DeviceCtx *c, ms_pwmset *pwms, ms_result *r1, ms_result *raw, int64_t span_bases, int32_t window, int32_t stride,
+                             int64_t n_windows, ms_result **out) {
+    int rc;
+    hipError_t he;
+    const size_t n1 = (size_t) r1->n_hits;
+    auto fail = [&](int code) { ms_result_free(raw); ms_result_free(r1); return code; };
+    // what a counts-only sweep reads of a span: per motif the windows with >= 1 site, and the number of sites -- one pass over the
+    // span's hit positions, nothing handed out (sweep_countonly_kernel)
+    if ((size_t) pwms->P > 65536) { set_error("internal: counts-only hand-out with more than 65536 motifs"); return fail(MS_ERR_RUNTIME); }
+    if ((rc = result_block_alloc(c, raw, 1))) return fail(rc);        // (room for >= 65536 words behind the counts)
+    raw->counts_only = true;
+    const size_t P1 = (size_t) pwms->P + 1;
+    unsigned long long *d_sites = reinterpret_cast<unsigned long long *>(raw->d_seq_idx);           // per-motif sites, summed on the host
+    he = hipMemsetAsync(raw->d_region_counts, 0, 8 * P1, c->stream);
+    if (he == hipSuccess) he = hipMemsetAsync(raw->d_motif_first, 0, 8 * P1, c->stream);
+    if (he == hipSuccess) he = hipMemsetAsync(d_sites, 0, 8 * P1, c->stream);
+    if (he != hipSuccess) { set_error("memset failed: %s", hipGetErrorString(he)); return fail(MS_ERR_RUNTIME); }
+    rc = launch_sweep_countonly((int64_t) n1, r1->d_motif_first, r1->P, pwms->d_width, r1->d_pos, window, stride, n_windows,
+                                raw->d_region_counts, d_sites, c->stream);
+    if (rc) return fail(rc);
+    (void) hipEventRecord(c->ev[1], c->stream);
+    std::vector<unsigned long long> per_motif((size_t) pwms->P, 0ULL);
+    if (pwms->P > 0) he = hipMemcpyAsync(per_motif.data(), d_sites, 8 * (size_t) pwms->P, hipMemcpyDeviceToHost, c->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+    if (he != hipSuccess) { set_error("sweep count failed: %s", hipGetErrorString(he)); return fail(MS_ERR_RUNTIME); }
+    unsigned long long n_sites = 0;
+    for (size_t p = 0; p < per_motif.size(); p++) {      // the offsets a caller slices by: consistent with n_hits although no site array exists
+        n_sites += per_motif[p];
+        raw->motif_offsets[p + 1] = (int64_t) n_sites;
+    }
+    raw->n_hits = (int64_t) n_sites;
+    float ms01 = 0;
+    (void) hipEventElapsedTime(&ms01, c->ev[0], c->ev[1]);
+    ms_scan_stats &stt = raw->stats;
+    stt.ms_finalize += ms01;
+    stt.ms_total += ms01;
+    stt.n_hits = (int64_t) n_sites;
+    stt.n_bases = span_bases;
+    stt.n_windows = 0;
+    for (int32_t p = 0; p < pwms->P; p++) stt.n_windows += n_windows * std::max<int64_t>(window - pwms->widths[p] + 1, 0);
+    ms_result_free(r1);
+    *out = raw;
+    return MS_OK;
+}
+
+// r1: the scan of the span as ONE region.  Consumes r1 (also on failure).
+int sweep_handout_locked(DeviceCtx *c, ms_pwmset *pwms, ms_result *r1, int64_t span_bases, int32_t window, int32_t stride,
+                         int64_t n_windows, ms_result **out, bool counts_only) {
+    int rc;
+    auto fail = [&](int code) { ms_result_free(r1); return code; };
+    // the device copies of the widths may have moved since the scan if the set was used on another device in between
+    if ((rc = pwmset_upload(pwms, c->device, c->stream))) return fail(rc);
+    const size_t n1 = (size_t) r1->n_hits;
+
+    std::unique_ptr<ms_result> res(new (std::nothrow) ms_result());
+    if (!res) { set_error("out of host memory"); return fail(MS_ERR_NOMEM); }
+    res->device = r1->device;
+    res->P = pwms->P;
+    res->R = n_windows;
+    res->stats = r1->stats;
+    res->motif_offsets.assign((size_t) pwms->P + 1, 0);
+    ms_result *raw = res.release();
+    auto fail2 = [&](int code) { ms_result_free(raw); return fail(code); };
+
+    // counts, destinations and the prefix sum's work space in ONE pooled block (no hipMalloc / hipFree per span: ADVICE r2)
+    uint32_t *d_cnt = nullptr;
+    uint64_t *d_dst = nullptr;
+    void *wblk = nullptr;
+    size_t wgot = 0;
+    auto cleanup = [&]() { if (wblk) pool_free(c, wblk, wgot); wblk = nullptr; };
+    uint64_t total = 0;
+    hipError_t he = hipSuccess;
+    (void) hipEventRecord(c->ev[0], c->stream);
+    if (counts_only) return sweep_counts_only(c, pwms, r1, raw, span_bases, window, stride, n_windows, out);
+    if (n1 > 0) {
+        size_t tmp_bytes = 0;
+        const size_t n8 = (n1 + 31) & ~(size_t) 31;
+        if ((rc = exclusive_sum_u32(nullptr, &tmp_bytes, nullptr, nullptr, n1, c->stream))) return fail2(rc);
+        if ((rc = pool_alloc(c, 12 * n8 + tmp_bytes + 256, &wblk, &wgot))) return fail2(rc);
+        d_dst = static_cast<uint64_t *>(wblk);
+        d_cnt = reinterpret_cast<uint32_t *>(d_dst + n8);
+        void *d_tmp = d_cnt + n8;
+        rc = launch_sweep_count((int64_t) n1, r1->d_motif_first, r1->P, pwms->d_width, r1->d_pos, window, stride, n_windows,
+                                d_cnt, c->stream);
+        if (!rc) rc = exclusive_sum_u32(d_tmp, &tmp_bytes, d_cnt, d_dst, n1, c->stream);
+        uint32_t last_cnt = 0;
+        uint64_t last_dst = 0;
+        if (!rc) {
+            he = hipMemcpyAsync(&last_cnt, d_cnt + (n1 - 1), 4, hipMemcpyDeviceToHost, c->stream);
+            if (he == hipSuccess) he = hipMemcpyAsync(&last_dst, d_dst + (n1 - 1), 8, hipMemcpyDeviceToHost, c->stream);
+            if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+            if (he != hipSuccess) { set_error("sweep count failed: %s", hipGetErrorString(he)); rc = MS_ERR_RUNTIME; }
+        }
+        if (rc) { cleanup(); return fail2(rc); }
+        total = last_dst + last_cnt;                          // 64-bit prefix sums: > 2^32 sites per call are fine
+    }
+    raw->n_hits = (int64_t) total;
+    {
+        if ((rc = result_block_alloc(c, raw, (size_t) total))) { cleanup(); return fail2(rc); }
+        const size_t P1 = (size_t) pwms->P + 1;
+        he = hipMemsetAsync(raw->d_region_counts, 0, 8 * P1, c->stream);
+        if (he == hipSuccess) he = hipMemsetAsync(raw->d_motif_first, 0xFF, 8 * P1, c->stream);
+        if (he != hipSuccess) { cleanup(); set_error("memset failed: %s", hipGetErrorString(he)); return fail2(MS_ERR_RUNTIME); }
+    }
+    (void) hipEventRecord(c->ev[1], c->stream);
+    rc = launch_sweep_scatter((int64_t) n1, r1->d_motif_first, r1->P, pwms->d_width, r1->d_pos, r1->d_score, r1->d_strand, d_dst,
+                              window, stride, n_windows, (int64_t) total, raw->d_seq_idx, raw->d_pos, raw->d_score, raw->d_strand,
+                              raw->d_motif_first, raw->d_region_counts, c->stream);
+    if (rc) { cleanup(); return fail2(rc); }
+    (void) hipEventRecord(c->ev[2], c->stream);
+    he = hipMemcpyAsync(raw->motif_offsets.data(), raw->d_motif_first, raw->motif_offsets.size() * sizeof(int64_t),
+                        hipMemcpyDeviceToHost, c->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+    cleanup();
+    if (he != hipSuccess) { set_error("sweep hand-out failed: %s", hipGetErrorString(he)); return fail2(MS_ERR_RUNTIME); }
+
+    // statistics: the span scan's stage times plus the hand-out (counts + prefix sum + scatter, booked under ms_finalize)
+    float ms01 = 0, ms12 = 0;
+    (void) hipEventElapsedTime(&ms01, c->ev[0], c->ev[1]);
+    (void) hipEventElapsedTime(&ms12, c->ev[1], c->ev[2]);
+    ms_scan_stats &stt = raw->stats;
+    stt.ms_finalize += ms01 + ms12;
+    stt.ms_total += ms01 + ms12;
+    stt.n_hits = (int64_t) total;
+    stt.n_bases = span_bases;                                   // bases scanned (each once)
+    stt.n_windows = 0;                                          // unit count of the sweep as the reference sees it
+    for (int32_t p = 0; p < pwms->P; p++) stt.n_windows += n_windows * std::max<int64_t>(window - pwms->widths[p] + 1, 0);
+    stt.hbm_bytes_algorithmic += 16 * ((int64_t) total - (int64_t) n1);
+    ms_result_free(r1);
+    *out = raw;
+    return MS_OK;
+}
+
+}  // namespace ms
+
+using namespace ms;
+
+extern "C" {
+
+int ms_scan(const ms_pwmset *pwms_c, const ms_seqset *seqs, int strand_mask, uint32_t flags, ms_result **out) {
+    if (!out) { set_error("out is NULL"); return MS_ERR_INVALID; }
+    *out = nullptr;
+    if (!pwms_c || !seqs) { set_error("NULL handle"); return MS_ERR_INVALID; }
+    if (strand_mask < 1 || strand_mask > 3) { set_error("invalid strand mask %d (1 '+', 2 '-', 3 both)", strand_mask); return MS_ERR_INVALID; }
+    if (flags & ~(uint32_t) (MS_SCAN_EXACT_ONLY | MS_SCAN_COUNTS_ONLY)) { set_error("unknown scan flags 0x%x", flags); return MS_ERR_INVALID; }
+    ms_pwmset *pwms = const_cast<ms_pwmset *>(pwms_c);       // lazily cached device copies / plan
+    DeviceCtx *c;
+    int rc = get_ctx(seqs->device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk_dev(c->mu);
+    std::lock_guard<std::mutex> lk_pwm(pwms->mu);
+    const uint32_t internal = (flags & MS_SCAN_EXACT_ONLY) | ((flags & MS_SCAN_COUNTS_ONLY) ? MS_SCAN_COUNTS_ONLY_INTERNAL : 0u);
+    return scan_locked(c, pwms, seqs, strand_mask, internal, out);
+}
+
+// configs[4]-style sweep (N3): the windows [begin + k*stride, begin + k*stride + window), k = 0..n_windows-1, of one
+// chromosome, with the result the reference gives when every window is a region of its own (scanner.py:71-87 cuts them,
+// cscore.c:336-390 scans each) -- but every base is scored ONCE: the span is scanned as one region and each hit is
+// handed to all windows that contain it whole (window / stride of them), written straight to its place in the
+// reference's order (motif, window, position, strand) -- sweep_scatter_kernel, no second sort.
+
+int ms_scan_sweep(const ms_pwmset *pwms_c, const ms_genome *g, int32_t chrom, int64_t begin, int64_t end, int32_t window,
+                  int32_t stride, int strand_mask, uint32_t flags, ms_result **out) {
+    if (!out) { set_error("out is NULL"); return MS_ERR_INVALID; }
+    *out = nullptr;
+    if (!pwms_c || !g) { set_error("NULL handle"); return MS_ERR_INVALID; }
+    if (strand_mask < 1 || strand_mask > 3) { set_error("invalid strand mask %d (1 '+', 2 '-', 3 both)", strand_mask); return MS_ERR_INVALID; }
+    if (flags & ~(uint32_t) MS_SCAN_EXACT_ONLY) { set_error("unknown scan flags 0x%x", flags); return MS_ERR_INVALID; }
+    if (window < 1 || stride < 1) { set_error("window and stride must be positive"); return MS_ERR_INVALID; }
+    if (begin < 0 || end < begin) { set_error("bad span [%lld, %lld)", (long long) begin, (long long) end); return MS_ERR_INVALID; }
+    const int64_t n_windows = end - begin >= window ? (end - begin - window) / stride + 1 : 0;
+    const int64_t span_end = n_windows > 0 ? begin + (n_windows - 1) * stride + window : begin;
+    ms_pwmset *pwms = const_cast<ms_pwmset *>(pwms_c);
+    ms_seqset *span = nullptr;
+    int rc = ms_seqset_from_genome(g, &chrom, &begin, &span_end, 1, &span);       // validates chrom / coordinates
+    if (rc) return rc;
+    DeviceCtx *c;
+    if ((rc = get_ctx(span->device, &c))) { ms_seqset_free(span); return rc; }
+    // both locks are held across the span scan AND the hand-out: nothing can move the PWM set's device copies in between
+    std::lock_guard<std::mutex> lk_dev(c->mu);
+    std::lock_guard<std::mutex> lk_pwm(pwms->mu);
+    ms_result *r1 = nullptr;
+    rc = scan_locked(c, pwms, span, strand_mask, flags, &r1);
+    const int64_t span_bases = span->n_bases;
+    ms_seqset_free(span);
+    if (rc) return rc;
+    return sweep_handout_locked(c, pwms, r1, span_bases, window, stride, n_windows, out);
+}
+
+}  // extern "C"

@@ -1,6 +1,8 @@
 // tests/sanitize/plan_asan.cpp -- the host side of the pre-filter (motifscan_amd/csrc/ms_plan.cpp: thresholds, the e2m3
 // quantiser, paired rows, the row-tile DP, the operand image) under AddressSanitizer + UndefinedBehaviorSanitizer, compiled
-// by plain g++ from the SAME source file the library is built from.  CPU build container only (`make -C motifscan_amd/csrc
+// by plain g++ from the SAME source file the library is built from -- and, on plans built the way a scan builds them, the scan's
+// geometry (ms_scan_geom.cpp: key layout, LDS layout, launch shape) over a small grid of set shapes and devices, against the
+// invariants the kernels rely on.  CPU build container only (`make -C motifscan_amd/csrc
 // sanitize`; tests/test_sanitizers.py runs it, once with the benchmark motif set dumped to a raw file).
 //
 //     plan_asan [motifs.bin]      motifs.bin: int32 n, int32 widths[n], double cutoffs[n][n_sets], int32 n_sets, double values[...]
@@ -11,7 +13,7 @@
 #include <random>
 #include <vector>
 
-#include "../../motifscan_amd/csrc/ms_internal.h"
+#include "../../motifscan_amd/csrc/ms_scan_geom.h"
 
 namespace ms {
 void set_error(const char *fmt, ...) {
@@ -40,7 +42,57 @@ double c_max_raw(const double *m, int W) {          // cscore.c:36-48: column ma
     return s;
 }
 
-long n_plans = 0;
+long n_plans = 0, n_geoms = 0;
+
+bool pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
+
+// what ms_kernels.hip and ms_order.hip take for granted about a scan's geometry (the comments of ms_kernels.h and ms_scan_geom.cpp)
+void check_geometry(const ms::ScanShape &sh, const ms::ScanOverrides &ov) {
+    const ms::ScanGeom g = ms::scan_geometry(sh, ov);
+    n_geoms++;
+    CHECK(g.lds_bytes <= sh.lds_max / (size_t) ms::kPfBlocksPerCu);
+    CHECK(g.lds_fixed == (g.wide ? ms::kPfLdsFixedWide : ms::kPfLdsFixedNarrow) && (size_t) g.rare_off16 * 16 + ms::kPfRareBytesMin <= g.lds_bytes);
+    CHECK(g.rare_cap >= (uint32_t) ms::kRareCapMin && g.rare_cap <= (uint32_t) ms::kRareCapMax);
+    CHECK(g.bpt >= 1);
+    CHECK(g.wave_passes >= 1 && (!g.counter_used || pow2(g.wave_passes)));
+    CHECK(pow2(g.cand_block) && g.cand_block >= 64 && g.cand_block <= 2048);
+    CHECK(g.end_bit <= 64 && g.end_bit == g.gbits + 1 + g.mbits);
+    int gbits_global = 1;
+    while ((1LL << gbits_global) <= sh.n_bases) gbits_global++;
+    CHECK(g.pbits == 0 ? g.gbits == gbits_global : (g.gbits == g.rbits + g.pbits && g.rbits + g.pbits <= gbits_global + 2));
+    CHECK(g.wide == sh.plan->wide && !(g.wide && g.dense));
+}
+
+// the plan as scan_plan (ms_scan.hip) builds it for a device of lds_max bytes of LDS per block, then the geometry over the grid
+void geometry_all(const std::vector<double> &values, const std::vector<int64_t> &off, const std::vector<int32_t> &widths,
+                  const std::vector<double> &cutoffs, const std::vector<double> &max_raw, int strand) {
+    const int32_t n = (int32_t) widths.size();
+    ms::ScanOverrides test_ov;                                  // the switches tests/test_gpu_parity.py drives, at their harshest
+    test_ov.lds_budget = 4096; test_ov.rare_cap_max = ms::kRareCapMin; test_ov.max_blocks = 2; test_ov.pf_dense = 1; test_ov.sort_low_bits = 24;
+    for (const ms::ScanOverrides &ov : {ms::ScanOverrides(), test_ov})
+        for (size_t lds_max : {(size_t) 64 * 1024, (size_t) 160 * 1024}) {
+            ms::PrefilterPlan plan;
+            int rc = ms::build_plan(values.data(), off.data(), widths.data(), cutoffs.data(), max_raw.data(), n, strand,
+                                    ms::scan_lds_budget(lds_max, true, ov), true, &plan);
+            if (rc != MS_OK) continue;
+            const bool wide = plan.wide;
+            rc = ms::build_plan(values.data(), off.data(), widths.data(), cutoffs.data(), max_raw.data(), n, strand,
+                                ms::scan_lds_budget(lds_max, wide, ov), true, &plan);
+            CHECK(rc == MS_OK && plan.wide == wide);             // the kernel family does not depend on the budget
+            const int64_t shapes[4][2] = {{1, 3000000000LL}, {1000000, 50}, {1, 1}, {0, 0}};       // (regions, bases of each)
+            for (const auto &shape : shapes)
+                for (int n_cu : {1, 256})
+                    for (double density : {-1.0, 0.05}) {
+                        ms::ScanShape sh;
+                        sh.plan = &plan; sh.P = n;
+                        sh.R = shape[0]; sh.max_len = shape[1]; sh.n_bases = shape[0] * shape[1];
+                        for (int32_t p : plan.fast_motifs) sh.fast_windows += shape[0] * std::max<int64_t>(shape[1] - widths[(size_t) p] + 1, 0);
+                        sh.n_cu = n_cu; sh.lds_max = lds_max; sh.cu_reserved = n_cu / 32;
+                        sh.density_known = density >= 0; sh.pred_density = density;
+                        check_geometry(sh, ov);
+                    }
+        }
+}
 
 void plan_all(const std::vector<double> &values, const std::vector<int32_t> &widths, const std::vector<double> &cutoffs) {
     const int32_t n = (int32_t) widths.size();
@@ -49,7 +101,8 @@ void plan_all(const std::vector<double> &values, const std::vector<int32_t> &wid
     CHECK((size_t) off[(size_t) n] == values.size());
     std::vector<double> max_raw((size_t) n);
     for (int32_t p = 0; p < n; p++) max_raw[(size_t) p] = c_max_raw(values.data() + off[(size_t) p], widths[(size_t) p]);
-    for (int strand = 1; strand <= 3; strand++)
+    for (int strand = 1; strand <= 3; strand++) {
+        geometry_all(values, off, widths, cutoffs, max_raw, strand);
         for (int pair = 0; pair < 2; pair++)
             for (size_t lds : {(size_t) 8 * 1024, (size_t) 24 * 1024, (size_t) 70 * 1024, (size_t) 139 * 1024}) {
                 ms::PrefilterPlan plan;
@@ -64,6 +117,7 @@ void plan_all(const std::vector<double> &values, const std::vector<int32_t> &wid
                 for (const auto &t : plan.tiles)                          // every tile's operand image lies inside the table buffer
                     CHECK(((size_t) t.table_off16 + t.table_len16) * 16 <= plan.tables.size() * sizeof(uint32_t) && t.n_classes <= ms::kMaxClasses);
             }
+    }
 }
 
 }  // namespace
@@ -118,6 +172,6 @@ int main(int argc, char **argv) {
             plan_all(values, widths, c);
         }
     }
-    std::printf("plan_asan: ok (%ld plans)\n", n_plans);
+    std::printf("plan_asan: ok (%ld plans, %ld scan geometries)\n", n_plans, n_geoms);
     return 0;
 }
