@@ -1,5 +1,12 @@
-// ms_device.h -- device-side helpers shared by the kernel translation units (ms_kernels.hip, ms_tail.hip): reading
-// the packed sequence, position -> region, and the fp64 window scorer in the reference's order of operations.
+// ms_device.h -- device-side helpers shared by the translation units that hold kernels: reading the packed sequence,
+// position -> region, the fp64 window scorer in the reference's order of operations, hit -> motif.
+//
+// The packed sequence in HBM (owned by ms_seqset, see ms_handles.h):
+//   codes   uint32 words, 16 bases per word, base i at bits [2*(i%16), 2*(i%16)+1]; A0 C1 G2 T3,
+//           non-ACGT stored as 0.  Regions are concatenated with no padding in between
+//           (region r = bases [offsets[r], offsets[r+1])).  kPadWords zero words follow.
+//   nmask   uint32 words, 32 bases per word, bit set = non-ACGT base (cscore.c:109-110 "-1")
+//   offsets int64[R+1]
 #pragma once
 #include "ms_kernels.h"
 
@@ -118,6 +125,16 @@ __device__ __forceinline__ void score_window32(const double2 *__restrict__ tab2,
         score_columns<8>(base, tab_bytes + (uint32_t) c1 * 64u, zero_bytes, (uint32_t) (cw >> (2 * c1)), skip >> c1, fwd, rev);
     if (W - c1 > 0)                                            // ... then four (loads are what the stage pays for)
         score_columns<4>(base, tab_bytes + (uint32_t) c1 * 64u, zero_bytes, (uint32_t) (cw >> (2 * c1)), skip >> c1, fwd, rev);
+}
+
+// the motif of hit i of a result's arrays: motif_off[m] <= i < motif_off[m + 1] (the de-dup / site tables and the window sweep)
+__device__ __forceinline__ int32_t motif_of_hit(const int64_t *__restrict__ motif_off, int32_t P, int64_t i) {
+    int32_t lo = 0, hi = P;                       // motif_off[lo] <= i < motif_off[hi]
+    while (hi - lo > 1) {
+        const int32_t mid = (lo + hi) >> 1;
+        if (motif_off[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
 }
 
 }  // namespace ms

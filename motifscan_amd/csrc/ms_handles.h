@@ -1,6 +1,7 @@
 // ms_handles.h -- private to libmotifscan_amd: per-device state and the structs behind the opaque handles of
 // include/motifscan_amd.h, shared by the library's translation units: ms_context.hip (device contexts, pools), ms_pwmset.hip, ms_seqset.hip,
-// ms_result.hip (one per handle), ms_scan.hip (scan pipeline), ms_regions.hip and ms_stream.hip (batch streams, host-streamed sweeps).
+// ms_result.hip (one per handle), ms_scan.hip (scan pipeline), ms_sweep.hip (window sweep), ms_regions.hip and ms_stream.hip (batch streams,
+// host-streamed sweeps).
 #pragma once
 #include <sched.h>
 #include <atomic>
@@ -296,7 +297,7 @@ int scan_complete(DeviceCtx *c, ms_pwmset *pwms, PendingScan *p, ms_result **out
 // The scan pipeline proper (ms_scan.hip); the caller holds c->mu and pwms->mu.  pend != nullptr: if the sizes can be predicted the
 // scan is only QUEUED (returns MS_SCAN_PENDING, finish with scan_complete); otherwise it runs to the end as usual.
 int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand_mask, uint32_t flags, ms_result **out, PendingScan *pend = nullptr);
-// Hand the hits of a span scan (one region) to the windows of a fixed-stride sweep, in place of *span_res (ms_scan.hip);
+// Hand the hits of a span scan (one region) to the windows of a fixed-stride sweep, in place of *span_res (ms_sweep.hip);
 // the caller holds c->mu and pwms->mu.
 // counts_only: only the per-motif window counts and the number of sites are made (ms_result::counts_only: the hit accessors refuse it)
 int sweep_handout_locked(DeviceCtx *c, ms_pwmset *pwms, ms_result *span_res, int64_t span_bases, int32_t window, int32_t stride,

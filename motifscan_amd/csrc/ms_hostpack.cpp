@@ -6,7 +6,7 @@
 // stage the scan waits for.  Packed on the host the stage has NO kernel: 0.375 B/base of codes + mask and 0.31 B/base of hints cross the
 // link instead of 1 B/base of ASCII, on the copy engines, whatever the CUs do.
 //
-// Layout = the device kernels' (ms_kernels.hip: pack_kernel, blk2reg_kernel), word for word: a unit of 32 bases -> codes[2u], codes[2u+1]
+// Layout = the device kernels' (ms_seqset.hip: pack_kernel, blk2reg_kernel), word for word: a unit of 32 bases -> codes[2u], codes[2u+1]
 // (2 bits per base, base i at bits [2i, 2i+2): a/A 0, c/C 1, g/G 2, t/T 3, anything else 0) and nmask[u] (bit i: base i is none of those);
 // positions past the end are code 0 / not N.  blk2reg[b] = the region of position 64 b (the last region r with offsets[r] <= 64 b);
 // blkinfo[b] = {r, offsets[r] - 64 b, offsets[r+1] - 64 b, offsets[r+2] - 64 b} (clamped to offsets[R]), or {-1, 0, 0, 0} when a value

@@ -1,4 +1,5 @@
-// ms_kernels.h -- kernel argument structs and launchers (ms_kernels.hip).
+// ms_kernels.h -- the pre-filter's constants, the kernels' argument structs, and the launchers that cross a translation unit (a kernel
+// whose only caller is one handle's file sits in that file, its launcher file-local).
 #pragma once
 #include "ms_internal.h"
 
@@ -34,7 +35,7 @@ struct DevSeq {
 };
 
 struct DevPwm {
-    const double2 *tab2;      // see ms_kernels.hip header
+    const double2 *tab2;      // see ms_fp64.hip header
     const int64_t *tab_off;   // [P] offset of motif p in tab2 (double2 units)
     const int32_t *width;     // [P]
     const double *max_raw;    // [P]
@@ -87,25 +88,26 @@ struct PfArgs {
     int wave_passes;               // per-wave hand-out: passes of 64 window starts a wave takes per atomic (sized on the host: ms_scan_geom.cpp)
 };
 
-
-int launch_pack(const uint8_t *ascii, int64_t n_bases, uint32_t *codes, uint32_t *nmask, hipStream_t st);
+// ms_kernels.hip: the pre-filter
 int prefilter_set_lds(bool wide, bool dense, size_t bytes);
 int launch_prefilter(const PfArgs &A, bool wide, bool dense, int blocks_per_tile, int n_tiles, size_t lds_bytes, hipStream_t st);
+// ms_fp64.hip: every window of the motifs the pre-filter cannot take; the pre-filter's candidates, short lists and long ones
+// (rescore_carry_kernel: chunks of the list in motif order, the window carried along; one 1024-thread block per CU)
 int launch_exact_all(const DevSeq &S, const DevPwm &Pw, const int32_t *motifs, int32_t n_motifs, int strand_mask,
                      const HitOut &H, hipStream_t st, int max_width);
-// the same for long lists: chunks of the list in motif order, the window carried along (rescore_carry_kernel); one 1024-thread block per CU
+int launch_rescore(const DevSeq &S, const DevPwm &Pw, const uint64_t *cand, const unsigned long long *n_cand, uint64_t n_static,
+                   uint64_t cand_cap, const FieldMeta *field_meta, int strand_mask, const HitOut &H, int n_blocks, hipStream_t st);
 int rescore_carry_set_lds();
 int launch_rescore_carry(const DevSeq &S, const DevPwm &Pw, const uint64_t *cand, const unsigned long long *n_cand, uint64_t n_static,
                          uint64_t cand_cap, const FieldMeta *field_meta, int strand_mask, const HitOut &H, int n_blocks, hipStream_t st);
-int launch_rescore(const DevSeq &S, const DevPwm &Pw, const uint64_t *cand, const unsigned long long *n_cand, uint64_t n_static,
-                   uint64_t cand_cap, const FieldMeta *field_meta, int strand_mask, const HitOut &H, int n_blocks,
-                   hipStream_t st);
-// after a sort over the key bits above kSortLowBits: runs of hits equal in those bits into full key order (in place)
+// ms_order.hip (its header says which key layout takes which of these).  launch_sort_fixup: after a sort over the key bits above
+// kSortLowBits, runs of hits equal in those bits into full key order (in place)
+int launch_fill_tail(uint64_t *keys, const unsigned long long *n_dev, uint64_t cap, hipStream_t st);
 int launch_sort_fixup(uint64_t *keys, double *vals, int64_t n, const unsigned long long *n_dev, hipStream_t st);
 int launch_finalize(const uint64_t *keys, int64_t n, const unsigned long long *n_dev, int gbits, int rbits, int pbits, int32_t P, const DevSeq &S,
                     int64_t *seq_idx, int64_t *pos, int8_t *strand, int64_t *motif_first, unsigned long long *region_counts,
                     hipStream_t st);
-// ms_order.hip: keys sorted over the bits [L, end_bit) -> every run of equal key >> L into full key order, decoded like launch_finalize's
+// keys sorted over the bits [L, end_bit) -> every run of equal key >> L into full key order, decoded like launch_finalize's
 // region form (pbits > 0), scores moved within d_score.  Runs the kernel cannot sort in LDS are listed in ovf_buf (order_overflow_bytes(n,
 // run_cap) bytes; *ovf_n zero on entry, the number listed on exit) and sorted by a second launch, through tmp_keys / tmp_vals ([n] each).
 size_t order_overflow_bytes(size_t n, int run_cap);
@@ -113,34 +115,13 @@ int launch_order_finalize(uint64_t *keys, double *score, int64_t n, const unsign
                           int64_t *seq_idx, int64_t *pos, int8_t *strand, int64_t *motif_first, unsigned long long *region_counts,
                           uint64_t *tmp_keys, double *tmp_vals, void *ovf_buf, size_t ovf_bytes, unsigned long long *ovf_n, int run_cap,
                           hipStream_t st);
-int launch_fill_tail(uint64_t *keys, const unsigned long long *n_dev, uint64_t cap, hipStream_t st);
-int launch_extract(const uint32_t *gcodes, const uint32_t *gnmask, const int64_t *src_start, const int64_t *dst_off,
-                   int64_t R, int64_t n_out, uint32_t *codes, uint32_t *nmask, hipStream_t st);
-int launch_blk2reg(const int64_t *offsets, int64_t R, int64_t n_bases, int32_t *blk2reg, int4 *blkinfo, hipStream_t st);
-int launch_score(const DevSeq &S, const DevPwm &Pw, int strand_mask, double *out, hipStream_t st);
-int launch_sweep_count(int64_t n, const int64_t *motif_off, int32_t P, const int32_t *width, const int64_t *pos,
-                       int32_t window, int32_t stride, int64_t n_windows, uint32_t *cnt, hipStream_t st);
-// counts only, from the unordered hit keys (ms_regions.hip)
+// ms_regions.hip: counts only, from the unordered hit keys
 bool count_only_supported(int32_t P, int64_t R, int pbits);
 size_t count_only_bitmap_words(int32_t P, int64_t R);
 int launch_count_only(const uint64_t *keys, int64_t n, const unsigned long long *n_dev, int gbits, int pbits, int64_t R, int32_t P, uint32_t *bitmap,
                       unsigned long long *region_counts, unsigned long long *motif_hits, int64_t *motif_first, hipStream_t st);
-int launch_sweep_countonly(int64_t n, const int64_t *motif_off, int32_t P, const int32_t *width, const int64_t *pos,
-                           int32_t window, int32_t stride, int64_t n_windows, unsigned long long *region_counts, unsigned long long *n_sites, hipStream_t st);
-int launch_sweep_scatter(int64_t n, const int64_t *motif_off, int32_t P, const int32_t *width, const int64_t *pos,
-                         const double *score, const int8_t *strand, const uint64_t *dst, int32_t window, int32_t stride,
-                         int64_t n_windows, int64_t total, int64_t *seq_idx_out, int64_t *pos_out, double *score_out,
-                         int8_t *strand_out, int64_t *motif_off_out, unsigned long long *region_counts, hipStream_t st);
-int launch_dedup(int64_t n, const int64_t *motif_off, int32_t P, const int32_t *width, const int64_t *seq_idx,
-                 const int64_t *pos, const double *score, const int8_t *strand, uint32_t *keep, hipStream_t st);
-int launch_compact_hits(int64_t n, const uint32_t *keep, const uint64_t *dst, const int64_t *seq_in, const int64_t *pos_in,
-                        const double *score_in, const int8_t *strand_in, int64_t *seq_out, int64_t *pos_out,
-                        double *score_out, int8_t *strand_out, const int64_t *off_in, int32_t P, int64_t *off_out,
-                        hipStream_t st);
-int launch_site_tables(int64_t n, const int64_t *motif_off, int32_t P, int64_t R, const int64_t *seq_idx,
-                       const double *score, int32_t *n_sites, double *max_score, hipStream_t st);
+// ms_result.hip: the compact copy-out of a result, which a scan that was asked for it queues itself (ms_scan.hip)
 int launch_pack_hits(int64_t n, const unsigned long long *n_dev, const int64_t *seq_idx, const int64_t *pos, const int8_t *strand, uint64_t *coord,
                      unsigned int *bad, hipStream_t st, int shift = 0);
-int launch_gather_ranks(const double *sorted, int64_t n, const int64_t *ranks, int32_t n_ranks, double *out, hipStream_t st);
 
 }  // namespace ms

@@ -1,176 +1,14 @@
-// ms_kernels.hip -- the gfx950 kernels of the PWM scan path and their launchers.
+// ms_kernels.hip -- the pre-filter and nothing else: this object is read back after every compile (check_isa.py: registers and
+// spills), and the file's hash decides whether a recorded traffic figure (profiles/pmc_traffic.json) still belongs to the kernel.
 //
-// Data in HBM (all owned by ms_seqset / ms_pwmset, see ms_handles.h):
-//   codes   uint32 words, 16 bases per word, base i at bits [2*(i%16), 2*(i%16)+1]; A0 C1 G2 T3,
-//           non-ACGT stored as 0.  Regions are concatenated with no padding in between
-//           (region r = bases [offsets[r], offsets[r+1])).  kPadWords zero words follow.
-//   nmask   uint32 words, 32 bases per word, bit set = non-ACGT base (cscore.c:109-110 "-1")
-//   offsets int64[R+1]
-//   tab2    per motif W*4 double2: tab2[c*4+b] = { M[b][c], M[3-b][W-1-c] }  (forward entry and
-//           the reverse-strand entry the reference adds at the same column step, cscore.c:348-352)
-//
-// Kernels:
-//   pack_kernel       ASCII -> codes + nmask                     (cscore.c:81-114)
 //   prefilter_f6_kernel  rigorous upper bound of both strand scores for EVERY window (with or without non-ACGT bases) as an
-//                     fp6 x fp4 one-hot product on the matrix cores (v_mfma_scale_f32_32x32x64_f8f6f4); emits candidates
-//   exact_tiled_kernel / exact_all_kernel  fp64 scoring of every window for motifs the pre-filter cannot take (the motif's table in LDS / in HBM)
-//   rescore_kernel    fp64 scoring of the candidates, in the reference's order of operations,
-//                     and the reference's hit test (cscore.c:356-358, 373-375); short candidate lists
-//   rescore_carry_kernel   the same for long lists: chunks of the list in motif order, the windows read in list order and
-//                     carried through an in-LDS counting sort (few cache lines per read either way)
-//   sort_fixup_kernel the radix sort covers the key bits above the low eight; this orders the short runs that agree in them
-//   finalize_kernel   sorted keys -> (seq_idx, pos, strand), per-motif offsets, region counts
-//   score_kernel      c_score: first W bases of every sequence    (cscore.c:191-224)
-//   gather_ranks_kernel   the rank pick of the cutoff builder    (motif/__init__.py:393-399)
-//   dedup / compact / site_tables kernels   scanner.py:156-193 and io/__init__.py:23-33 on the sorted hits
-//   extract_kernel    regions cut out of a genome that is resident as 2-bit codes (scanner.py:71-87)
-//   blk2reg_kernel    region of every 64th position, so later position -> region lookups are O(1)
-#include <algorithm>
-#include <cstdlib>
-
+//                     fp6 x fp4 one-hot product on the matrix cores (v_mfma_scale_f32_32x32x64_f8f6f4); emits candidates for the
+//                     fp64 stage (ms_fp64.hip).  <2, parked> / <2, dense>: plans of row tiles of 1 or 2 k-blocks; <4, parked>: wide tiles
+//
+// The packed sequence: ms_device.h; operand tables, quantisation and the proof that no hit is lost: ms_internal.h, ms_plan.cpp.
 #include "ms_device.h"
 
 namespace ms {
-
-// The middle field of a hit key: (region << pbits) | position inside the region when the set's regions are short
-// enough for that to fit (H.pbits > 0: finalize then only unpacks bits), else the global base position.
-__device__ __forceinline__ int64_t hit_coord(const HitOut &H, const DevSeq &S, int64_t r, int64_t g) {
-    return H.pbits ? (int64_t) (((uint64_t) r << H.pbits) | (uint64_t) (g - S.offsets[r])) : g;
-}
-
-__device__ __forceinline__ void emit_hit(const HitOut &H, uint32_t motif, int64_t g, uint32_t sbit, double score) {
-    const unsigned long long i = atomicAdd(H.n_hits, 1ULL);
-    if (i < H.cap) {
-        H.keys[i] = ((uint64_t) motif << (H.gbits + 1)) | ((uint64_t) g << 1) | sbit;
-        H.vals[i] = score;
-    }
-}
-
-// the reference's normalisation and threshold test, verbatim (cscore.c:356-358 / 373-375)
-__device__ __forceinline__ void test_and_emit(const HitOut &H, const DevPwm &Pw, uint32_t motif, int64_t g,
-                                              double fwd, double rev, int strand_mask) {
-    // raw_floor: (cutoff - 1e-10) * max_raw minus 2000x the worst fp64 rounding of the sum, the divide and
-    // the subtract (ms_pwmset.hip, pwmset_upload): below it the reference's test is false whatever the roundings do, so the
-    // two IEEE divides are only paid by windows that can actually be hits
-    const double floor_ = Pw.raw_floor[motif];
-    const bool try_f = (strand_mask & 1) && !(fwd < floor_);
-    const bool try_r = (strand_mask & 2) && !(rev < floor_);
-    if (!try_f && !try_r) return;
-    const double max_raw = Pw.max_raw[motif];
-    const double cutoff = Pw.cutoff[motif];
-    const double s_f = try_f ? fwd / max_raw : 0.0, s_r = try_r ? rev / max_raw : 0.0;
-    const bool hit_f = try_f && s_f - cutoff >= -1e-10, hit_r = try_r && s_r - cutoff >= -1e-10;
-    if (hit_f) emit_hit(H, motif, g, 0u, s_f);
-    if (hit_r) emit_hit(H, motif, g, 1u, s_r);
-}
-
-// Block-level staging of hits in LDS: one global atomicAdd per ~2000 hits instead of one per wave
-// (all hit writers of the chip share ONE counter word; it sustains only ~90 M atomics/s).
-constexpr int kHitStage = 2048;
-template <int N>
-struct HitStageN {
-    static constexpr int kCap = N;
-    uint64_t keys[N];
-    double vals[N];
-    unsigned int n;
-    unsigned long long base;
-};
-typedef HitStageN<kHitStage> HitStage;
-
-template <class ST>
-__device__ __forceinline__ void stage_hit(ST &st, const HitOut &H, uint32_t motif, int64_t g, uint32_t sbit, double score) {
-    const unsigned int i = atomicAdd(&st.n, 1u);
-    if (i < (unsigned int) ST::kCap) {
-        st.keys[i] = ((uint64_t) motif << (H.gbits + 1)) | ((uint64_t) g << 1) | sbit;
-        st.vals[i] = score;
-    } else {
-        emit_hit(H, motif, g, sbit, score);            // stage full: straight to HBM
-    }
-}
-
-// all threads of the block, at a block-uniform point
-template <class ST>
-__device__ __forceinline__ void stage_flush(ST &st, const HitOut &H) {
-    __syncthreads();
-    const unsigned int n = st.n < (unsigned int) ST::kCap ? st.n : (unsigned int) ST::kCap;
-    if (threadIdx.x == 0 && n > 0) st.base = atomicAdd(H.n_hits, (unsigned long long) n);
-    __syncthreads();
-    const unsigned long long base = st.base;
-    for (unsigned int i = threadIdx.x; i < n; i += blockDim.x)
-        if (base + i < H.cap) { H.keys[base + i] = st.keys[i]; H.vals[base + i] = st.vals[i]; }
-    __syncthreads();
-    if (threadIdx.x == 0) st.n = 0;
-    __syncthreads();
-}
-
-// floor32: FieldMeta::floor32, the raw-sum floor of test_and_emit rounded DOWN to a float (it came with the field's record: windows
-// that cannot be hits read nothing more); the rest of the test reads {max_raw, cutoff} side by side
-template <class ST>
-__device__ __forceinline__ void test_and_stage(ST &st, const HitOut &H, const DevPwm &Pw, uint32_t motif, int64_t g,
-                                               double fwd, double rev, int strand_mask, float floor32) {
-    const double floor_ = (double) floor32;
-    const bool try_f = (strand_mask & 1) && !(fwd < floor_);
-    const bool try_r = (strand_mask & 2) && !(rev < floor_);
-    if (!try_f && !try_r) return;
-    const double2 mc = *reinterpret_cast<const double2 *>(Pw.thresh + 4 * (size_t) motif);      // {max_raw, cutoff}: one read
-    const double max_raw = mc.x, cutoff = mc.y;
-    if (try_f) {
-        const double s = fwd / max_raw;
-        if (s - cutoff >= -1e-10) stage_hit(st, H, motif, g, 0u, s);
-    }
-    if (try_r) {
-        const double s = rev / max_raw;
-        if (s - cutoff >= -1e-10) stage_hit(st, H, motif, g, 1u, s);
-    }
-}
-
-// --------------------------------------------------------------------------- pack --
-
-// One thread per 32 bases: two 16-byte loads, one 8-byte + one 4-byte store.
-__global__ void __launch_bounds__(256) pack_kernel(const uint8_t *__restrict__ ascii, int64_t n_bases,
-                                                   uint32_t *__restrict__ codes, uint32_t *__restrict__ nmask,
-                                                   int64_t n_units, int aligned16) {
-    const int64_t u = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= n_units) return;
-    const int64_t base = u * 32;
-    uint32_t raw[8];
-    if (aligned16 && base + 32 <= n_bases) {
-        const uint4 a = *reinterpret_cast<const uint4 *>(ascii + base);
-        const uint4 b = *reinterpret_cast<const uint4 *>(ascii + base + 16);
-        raw[0] = a.x; raw[1] = a.y; raw[2] = a.z; raw[3] = a.w;
-        raw[4] = b.x; raw[5] = b.y; raw[6] = b.z; raw[7] = b.w;
-    } else {
-        for (int k = 0; k < 8; k++) {
-            uint32_t w = 0;
-            for (int j = 0; j < 4; j++) {
-                const int64_t i = base + k * 4 + j;
-                w |= (uint32_t) (i < n_bases ? ascii[i] : (uint8_t) 'A') << (8 * j);
-            }
-            raw[k] = w;
-        }
-    }
-    uint64_t cw = 0;
-    uint32_t nw = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const uint32_t ch = ((raw[k] >> (8 * j)) & 0xFFu) | 0x20u;      // fold case (cscore.c:93-108)
-            const uint32_t code = ((ch >> 1) ^ (ch >> 2)) & 3u;             // a,c,g,t -> 0,1,2,3
-            const bool acgt = ch == 0x61u || ch == 0x63u || ch == 0x67u || ch == 0x74u;
-            const int i = k * 4 + j;
-            cw |= (uint64_t) (acgt ? code : 0u) << (2 * i);
-            nw |= (acgt ? 0u : 1u) << i;
-        }
-    }
-    if (base + 32 > n_bases) {          // bases past the end are neither N nor scanned
-        const int valid = (int) (n_bases - base);
-        nw &= low_mask(valid);
-    }
-    codes[2 * u] = (uint32_t) cw;
-    codes[2 * u + 1] = (uint32_t) (cw >> 32);
-    nmask[u] = nw;
-}
 
 // ---------------------------------------------------------------------- pre-filter --
 //
@@ -186,7 +24,7 @@ __global__ void __launch_bounds__(256) pack_kernel(const uint8_t *__restrict__ a
 // (measured in round 1: the whole kernel then runs at the ~90 M atomics/s a single word sustains).  Each wave therefore reserves
 // BLOCKS of A.cand_block record slots of the global list (one atomicAdd per block) and stores its records straight into its block
 // with ballot/mbcnt ranks; slots it leaves unused (fewer than 64 when a block is abandoned, the rest of the last block at the end)
-// are written as empty records (flags 0), which rescore_kernel skips.  (Rounds 1-2 staged 64 records per wave in LDS and spilled
+// are written as empty records (flags 0), which rescore_kernel (ms_fp64.hip) skips.  (Rounds 1-2 staged 64 records per wave in LDS and spilled
 // them through a called function: at p = 1e-3, ten times the records, that flush was most of the kernel's time.)
 // A record is per LANE and per table group: position, group, and one flag bit per field -- rescore_kernel expands the flags.
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -1136,672 +974,6 @@ __global__ void __launch_bounds__(kPfThreads, 4) prefilter_f6_kernel(const PfArg
     }
 }
 
-// -------------------------------------------------------------------- fp64 kernels --
-
-// grid = (ceil(n_bases/256), n_exact motifs).  Fallback for motifs the pre-filter cannot take
-// (W > 63, max_raw <= 0, non-finite values, a cutoff so low that (almost) every window passes).
-__global__ void __launch_bounds__(256) exact_all_kernel(const DevSeq S, const DevPwm Pw, const int32_t *__restrict__ motifs,
-                                                        int strand_mask, const HitOut H) {
-    const int64_t g = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= S.n_bases) return;
-    const int32_t p = motifs[blockIdx.y];
-    const int W = Pw.width[p];
-    const int64_t r = find_region(S, g);
-    if (g + W > S.offsets[r + 1]) return;
-    double fwd, rev;
-    score_window(S, Pw.tab2 + Pw.tab_off[p], W, g, fwd, rev);
-    test_and_emit(H, Pw, (uint32_t) p, hit_coord(H, S, r, g), fwd, rev, strand_mask);
-}
-
-// The same with the motif's table in LDS (round 6): exact_all_kernel reads a table entry per (window, column) through the
-// texture addressers -- the unit the fp64 stage is bound by (profiles/r03t_rescore_ta.log) -- although a wave's 64 lanes want at most four
-// different entries of a column.  Here a block stages its motif's W x 4 entries (+ an all-zero entry for the columns that add nothing) once,
-// scans kExactIter strips of 256 window starts against them, and a column is one 16-byte LDS read (a broadcast: <= 5 distinct addresses per
-// wave) + the two fp64 adds, in the reference's column order; a column that adds nothing ADDS the zero entry (score_window32's argument: a
-// running sum that started at +0.0 is never -0.0, so x + (+0.0) = x bit for bit).  Motifs wider than kExactTileMaxW keep exact_all_kernel.
-constexpr int kExactTileMaxW = 1024;       // 64 KB of LDS for the table
-constexpr int kExactIter = 8;
-
-__global__ void __launch_bounds__(256) exact_tiled_kernel(const DevSeq S, const DevPwm Pw, const int32_t *__restrict__ motifs, int strand_mask, const HitOut H) {
-    extern __shared__ double2 tab_lds[];                       // [W * 4 + 1]
-    const int32_t p = motifs[blockIdx.y];
-    const int W = Pw.width[p];
-    {
-        const double2 *__restrict__ tab = Pw.tab2 + Pw.tab_off[p];
-        for (int i = threadIdx.x; i < W * 4; i += 256) tab_lds[i] = tab[i];
-        if (threadIdx.x == 0) tab_lds[W * 4] = make_double2(0.0, 0.0);
-    }
-    __syncthreads();
-    const uint32_t zero = (uint32_t) W * 4u;
-    for (int it = 0; it < kExactIter; it++) {
-        const int64_t g = ((int64_t) blockIdx.x * kExactIter + it) * 256 + threadIdx.x;
-        if (g >= S.n_bases) break;
-        const int64_t r = find_region(S, g);
-        if (g + W > S.offsets[r + 1]) continue;
-        double fwd = 0.0, rev = 0.0;
-        for (int c0 = 0; c0 < W; c0 += 32) {
-            const uint64_t cw = code_window(S.codes, g + c0);
-            const int n = (W - c0) < 32 ? (W - c0) : 32;
-            const uint32_t skip = n_window(S.nmask, g + c0) | ~low_mask(n);           // bit c: column c0 + c adds nothing
-            for (int c1 = 0; c1 < n; c1 += 8) {
-                double2 t[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const int c = c1 + k;
-                    const uint32_t idx = (uint32_t) (c0 + c) * 4u + ((uint32_t) (cw >> (2 * c)) & 3u);
-                    t[k] = tab_lds[((skip >> c) & 1u) ? zero : idx];
-                }
-#pragma unroll
-                for (int k = 0; k < 8; k++) { fwd += t[k].x; rev += t[k].y; }
-            }
-        }
-        test_and_emit(H, Pw, (uint32_t) p, hit_coord(H, S, r, g), fwd, rev, strand_mask);
-    }
-}
-
-// U candidate records per thread and round, their loads issued side by side: the kernel is a chain of dependent gathers
-// (record -> region hint / sequence words / motif id -> offsets / width / table offset -> table entries), so the records in
-// flight per thread -- not the arithmetic -- set its speed; one barrier pair per round of U records instead of per record.
-constexpr int kRescoreU = 4;
-
-__global__ void __launch_bounds__(256) rescore_kernel(const DevSeq S, const DevPwm Pw, const uint64_t *__restrict__ cand,
-                                                      const unsigned long long *__restrict__ n_cand, uint64_t n_static, uint64_t cand_cap,
-                                                      const FieldMeta *__restrict__ field_meta, int strand_mask,
-                                                      const HitOut H) {
-    __shared__ HitStage st;
-    if (threadIdx.x == 0) st.n = 0;
-    __syncthreads();
-    unsigned long long n = n_static + *n_cand;            // the waves' own first blocks, then the blocks they reserved from the counter
-    if (n > cand_cap) n = cand_cap;
-    constexpr int U = kRescoreU;
-    const bool both = strand_mask == 3;                  // both strands: fields 2k, 2k + 1 = motif slot k forward, reverse; one strand: field n = slot n
-    const unsigned long long per_sub = (unsigned long long) gridDim.x * blockDim.x;
-    const unsigned long long per_round = per_sub * U;
-    const unsigned long long rounds = (n + per_round - 1) / per_round;
-    const int4 *__restrict__ meta4 = reinterpret_cast<const int4 *>(field_meta);
-    for (unsigned long long rd = 0; rd < rounds; rd++) {
-        const unsigned long long i0 = rd * per_round + (unsigned long long) blockIdx.x * blockDim.x + threadIdx.x;
-        uint64_t c[U];
-        bool live[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            live[u] = i0 + u * per_sub < n;
-            c[u] = live[u] ? cand[i0 + u * per_sub] : 0;
-        }
-        // independent of each other: the region's place (one read), sequence words, N words, the first flagged field's motif / width / table (one read)
-        int64_t g[U];
-        int4 bi[U];
-        uint64_t cw[U];
-        uint32_t nw[U], flags[U];
-        int32_t group[U];
-        int4 fm[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            g[u] = (int64_t) (c[u] >> 30);
-            group[u] = (int32_t) ((c[u] >> 16) & 0x3FFFu);
-            const uint32_t f = (uint32_t) c[u] & 0xFFFFu;              // bit n = field n
-            flags[u] = both ? (f | (f >> 1)) & 0x5555u : f;             // a motif's two strands are re-scored together anyway
-            bi[u] = S.blkinfo[g[u] >> 6];
-            cw[u] = code_window(S.codes, g[u]);
-            nw[u] = n_window(S.nmask, g[u]);
-            fm[u] = flags[u] ? meta4[group[u] * kGroupFields + (__ffs((int) flags[u]) - 1)] : make_int4(-1, 0, 0, 0);
-        }
-        // the region's bounds: out of the block's record; only tiny regions (a third region start within the block's reach) and
-        // starts beyond 32 bits need the offsets themselves
-        int64_t r[U], beg[U], end[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int64_t base = g[u] & ~(int64_t) 63;
-            int64_t lo = bi[u].x, o0 = base + bi[u].y, o1 = base + bi[u].z, o2 = base + bi[u].w;
-            if (bi[u].x < 0) {
-                lo = S.blk2reg[g[u] >> 6];
-                o0 = S.offsets[lo]; o1 = S.offsets[lo + 1];
-                o2 = lo + 2 <= S.R ? S.offsets[lo + 2] : o1;
-            }
-            if (g[u] < o1) { r[u] = lo; beg[u] = o0; end[u] = o1; }
-            else if (g[u] < o2) { r[u] = lo + 1; beg[u] = o1; end[u] = o2; }
-            else { r[u] = find_region(S, g[u]); beg[u] = S.offsets[r[u]]; end[u] = S.offsets[r[u] + 1]; }      // tiny regions
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            if (!live[u]) continue;
-            const int64_t gk = H.pbits ? (int64_t) (((uint64_t) r[u] << H.pbits) | (uint64_t) (g[u] - beg[u])) : g[u];
-            bool first = true;
-            while (flags[u]) {
-                const int field = __ffs((int) flags[u]) - 1;
-                flags[u] &= flags[u] - 1u;
-                int4 f4 = fm[u];
-                if (!first) f4 = meta4[group[u] * kGroupFields + field];           // further motifs of the group: rare
-                first = false;
-                const int32_t m = f4.x;
-                const int w = f4.y;
-                if (m < 0) continue;
-                if (g[u] + w > end[u]) continue;                         // window runs past its region (cscore.c:340)
-                double fwd, rev;
-                if (w <= 32 && Pw.tab32) score_window32(Pw.tab2, (uint32_t) f4.z, Pw.zero_bytes, w, cw[u], nw[u], fwd, rev);     // non-ACGT bases add nothing (cscore.c:345-353)
-                else score_window(S, Pw.tab2 + Pw.tab_off[m], w, g[u], fwd, rev);
-                test_and_stage(st, H, Pw, (uint32_t) m, gk, fwd, rev, strand_mask, __int_as_float(f4.w));
-            }
-        }
-        __syncthreads();
-        const bool full = st.n > (unsigned int) (kHitStage - 256 * 2 * U);
-        __syncthreads();                     // every thread has read st.n before any wave can append again: the decision is block-uniform
-        if (full) stage_flush(st, H);
-    }
-    stage_flush(st, H);
-}
-
-// ----------------------------------------------------------------------- finalize --
-
-// n_dev != nullptr: the number of hits is only known on the device (a scan whose sizes were predicted, scan_locked): n is then
-// the launch's capacity and the true count min(*n_dev, n) is read here.
-__global__ void __launch_bounds__(256) finalize_kernel(const uint64_t *__restrict__ keys, int64_t n, const unsigned long long *__restrict__ n_dev,
-                                                       int gbits, int32_t P, const DevSeq S,
-                                                       int64_t *__restrict__ seq_idx, int64_t *__restrict__ pos,
-                                                       int8_t *__restrict__ strand, int64_t *__restrict__ motif_first,
-                                                       unsigned long long *__restrict__ region_counts) {
-    if (n_dev) { const unsigned long long nd = *n_dev; if ((unsigned long long) n > nd) n = (int64_t) nd; }
-    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = i < n;
-    uint32_t motif = 0xFFFFFFFFu;
-    bool new_pair = false;
-    if (live) {
-        const uint64_t k = keys[i];
-        const uint64_t gmask = (1ULL << gbits) - 1ULL;
-        const int64_t g = (int64_t) ((k >> 1) & gmask);
-        motif = (uint32_t) (k >> (gbits + 1));
-        const int64_t r = find_region(S, g);
-        seq_idx[i] = r;
-        pos[i] = g - S.offsets[r];
-        strand[i] = (int8_t) ((k & 1ULL) ? 2 : 1);
-        bool first_of_motif = (i == 0);
-        new_pair = true;
-        int64_t q0 = 0;                                  // per-motif offsets: every motif after the previous hit's up to this one starts here
-        if (i > 0) {
-            const uint64_t kp = keys[i - 1];
-            const uint32_t mp = (uint32_t) (kp >> (gbits + 1));
-            first_of_motif = mp != motif;
-            q0 = (int64_t) mp + 1;
-            if (!first_of_motif) {
-                const int64_t gp = (int64_t) ((kp >> 1) & gmask);
-                new_pair = gp < S.offsets[r];            // previous hit of this motif lies in an earlier region
-            }
-        }
-        if (first_of_motif) for (int64_t q = q0; q <= (int64_t) motif; q++) motif_first[q] = i;
-        if (i == n - 1) for (int64_t q = (int64_t) motif + 1; q <= P; q++) motif_first[q] = n;     // motifs after the last hit: empty
-    }
-    // number of regions with >= 1 hit per motif (stats.py:29-31): one atomic per (wave, motif)
-    unsigned long long todo = __ballot(live && new_pair);
-    while (todo) {
-        const int leader = __ffsll((long long) todo) - 1;
-        const uint32_t m = __shfl(motif, leader);
-        const unsigned long long same = __ballot(live && new_pair && motif == m);
-        if ((int) (threadIdx.x & 63) == leader) atomicAdd(&region_counts[m], (unsigned long long) __popcll(same));
-        todo &= ~same;
-    }
-}
-
-// The same when the keys carry (region, position inside the region): nothing to look up, only bits to unpack.
-// Four consecutive hits per thread: 16-byte loads and stores, the four strand bytes as one word.
-__global__ void __launch_bounds__(256) finalize_rp_kernel(const uint64_t *__restrict__ keys, int64_t n, const unsigned long long *__restrict__ n_dev,
-                                                          int rbits, int pbits, int32_t P,
-                                                          int64_t *__restrict__ seq_idx, int64_t *__restrict__ pos,
-                                                          int8_t *__restrict__ strand, int64_t *__restrict__ motif_first,
-                                                          unsigned long long *__restrict__ region_counts) {
-    if (n_dev) { const unsigned long long nd = *n_dev; if ((unsigned long long) n > nd) n = (int64_t) nd; }
-    const int64_t i0 = 4 * ((int64_t) blockIdx.x * blockDim.x + threadIdx.x);
-    const bool live = i0 < n;
-    uint32_t motif0 = 0xFFFFFFFFu;
-    int n_new = 0;                                              // new (motif, region) pairs among this thread's hits of motif0
-    if (live) {
-        uint64_t k[4];
-        const bool full = i0 + 4 <= n;
-        if (full) {
-            const ulonglong2 a = *reinterpret_cast<const ulonglong2 *>(keys + i0), b2 = *reinterpret_cast<const ulonglong2 *>(keys + i0 + 2);
-            k[0] = a.x; k[1] = a.y; k[2] = b2.x; k[3] = b2.y;
-        } else {
-            for (int j = 0; j < 4; j++) k[j] = i0 + j < n ? keys[i0 + j] : 0;
-        }
-        uint64_t prev = i0 > 0 ? keys[i0 - 1] >> (pbits + 1) : ~0ULL;
-        int64_t sq[4], ps[4];
-        uint32_t sd = 0;
-        const uint64_t rmask = (1ULL << rbits) - 1ULL, pmask = (1ULL << pbits) - 1ULL;
-        motif0 = (uint32_t) (k[0] >> (pbits + 1 + rbits));
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (i0 + j < n) {
-                const uint64_t pair = k[j] >> (pbits + 1);      // (motif, region)
-                const uint32_t motif = (uint32_t) (pair >> rbits);
-                sq[j] = (int64_t) (pair & rmask);
-                ps[j] = (int64_t) ((k[j] >> 1) & pmask);
-                sd |= ((k[j] & 1ULL) ? 2u : 1u) << (8 * j);
-                if (prev == ~0ULL || (uint32_t) (prev >> rbits) != motif)        // every motif after the previous hit's up to this one starts here
-                    for (int64_t q = prev == ~0ULL ? 0 : (int64_t) (uint32_t) (prev >> rbits) + 1; q <= (int64_t) motif; q++) motif_first[q] = i0 + j;
-                if (i0 + j == n - 1) for (int64_t q = (int64_t) motif + 1; q <= P; q++) motif_first[q] = n;   // motifs after the last hit: empty
-                if (prev != pair) {
-                    if (motif == motif0) n_new++;
-                    else atomicAdd(&region_counts[motif], 1ULL);    // a thread's hits rarely span two motifs
-                }
-                prev = pair;
-            }
-        }
-        if (full) {
-            *reinterpret_cast<longlong2 *>(seq_idx + i0) = make_longlong2(sq[0], sq[1]);
-            *reinterpret_cast<longlong2 *>(seq_idx + i0 + 2) = make_longlong2(sq[2], sq[3]);
-            *reinterpret_cast<longlong2 *>(pos + i0) = make_longlong2(ps[0], ps[1]);
-            *reinterpret_cast<longlong2 *>(pos + i0 + 2) = make_longlong2(ps[2], ps[3]);
-            *reinterpret_cast<uint32_t *>(strand + i0) = sd;
-        } else {
-            for (int j = 0; j < 4 && i0 + j < n; j++) { seq_idx[i0 + j] = sq[j]; pos[i0 + j] = ps[j]; strand[i0 + j] = (int8_t) ((sd >> (8 * j)) & 0xFFu); }
-        }
-    }
-    // regions with >= 1 hit per motif (stats.py:29-31): one atomic per (wave, motif)
-    unsigned long long todo = __ballot(live && n_new > 0);
-    while (todo) {
-        const int leader = __ffsll((long long) todo) - 1;
-        const uint32_t m = __shfl(motif0, leader);
-        const unsigned long long same = __ballot(live && n_new > 0 && motif0 == m);
-        int v = (live && motif0 == m) ? n_new : 0;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-        if ((int) (threadIdx.x & 63) == leader) atomicAdd(&region_counts[m], (unsigned long long) v);
-        todo &= ~same;
-    }
-}
-
-// -------------------------------------------------------------- de-dup / site tables --
-
-__device__ __forceinline__ int32_t motif_of_hit(const int64_t *__restrict__ motif_off, int32_t P, int64_t i) {
-    int32_t lo = 0, hi = P;                       // motif_off[lo] <= i < motif_off[hi]
-    while (hi - lo > 1) {
-        const int32_t mid = (lo + hi) >> 1;
-        if (motif_off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// scanner.py:156-193 on the sorted hit arrays.  The thread of the FIRST hit of a (motif, region)
-// segment walks the segment once with one "current site" per strand: a later same-strand site
-// closer than the motif width either loses (score <=: tie keeps the earlier one) or replaces it.
-// The kept hits are already in the order the reference returns (start ascending, '+' first).
-__global__ void __launch_bounds__(256) dedup_kernel(int64_t n, const int64_t *__restrict__ motif_off, int32_t P,
-                                                    const int32_t *__restrict__ width, const int64_t *__restrict__ seq_idx,
-                                                    const int64_t *__restrict__ pos, const double *__restrict__ score,
-                                                    const int8_t *__restrict__ strand, uint32_t *__restrict__ keep) {
-    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int32_t p = motif_of_hit(motif_off, P, i);
-    const int64_t r = seq_idx[i];
-    if (i > motif_off[p] && seq_idx[i - 1] == r) return;            // not the head of its segment
-    const int64_t end = motif_off[p + 1];
-    const int64_t W = width[p];
-    int64_t cur[2] = {-1, -1};
-    for (int64_t j = i; j < end && seq_idx[j] == r; j++) {
-        const int s = strand[j] == 1 ? 0 : 1;
-        uint32_t kj = 1;
-        if (cur[s] >= 0 && pos[j] - pos[cur[s]] < W) {
-            if (score[cur[s]] >= score[j]) kj = 0;                   // scanner.py:163-164
-            else { keep[cur[s]] = 0; cur[s] = j; }                   // scanner.py:165-166
-        } else {
-            cur[s] = j;
-        }
-        keep[j] = kj;
-    }
-}
-
-__global__ void __launch_bounds__(256) compact_hits_kernel(int64_t n, const uint32_t *__restrict__ keep,
-                                                           const uint64_t *__restrict__ dst,
-                                                           const int64_t *__restrict__ seq_in, const int64_t *__restrict__ pos_in,
-                                                           const double *__restrict__ score_in, const int8_t *__restrict__ strand_in,
-                                                           int64_t *__restrict__ seq_out, int64_t *__restrict__ pos_out,
-                                                           double *__restrict__ score_out, int8_t *__restrict__ strand_out) {
-    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || !keep[i]) return;
-    const uint64_t d = dst[i];
-    seq_out[d] = seq_in[i]; pos_out[d] = pos_in[i]; score_out[d] = score_in[i]; strand_out[d] = strand_in[i];
-}
-
-// new per-motif offsets after compaction: off_out[p] = dst[off_in[p]] (or the kept total at the end)
-__global__ void remap_offsets_kernel(const int64_t *__restrict__ off_in, int32_t P, int64_t n, const uint64_t *__restrict__ dst,
-                                     const uint32_t *__restrict__ keep, int64_t *__restrict__ off_out) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p > P) return;
-    const int64_t o = off_in[p];
-    off_out[p] = o < n ? (int64_t) dst[o] : (n > 0 ? (int64_t) dst[n - 1] + keep[n - 1] : 0);
-}
-
-// io/__init__.py:23-33: per (motif, region) the number of sites and the maximum score
-__global__ void __launch_bounds__(256) site_tables_kernel(int64_t n, const int64_t *__restrict__ motif_off, int32_t P, int64_t R,
-                                                          const int64_t *__restrict__ seq_idx, const double *__restrict__ score,
-                                                          int32_t *__restrict__ n_sites, double *__restrict__ max_score) {
-    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int32_t p = motif_of_hit(motif_off, P, i);
-    const int64_t r = seq_idx[i];
-    if (i > motif_off[p] && seq_idx[i - 1] == r) return;
-    const int64_t end = motif_off[p + 1];
-    int32_t cnt = 0;
-    double best = score[i];
-    for (int64_t j = i; j < end && seq_idx[j] == r; j++) {
-        cnt++;
-        if (score[j] > best) best = score[j];
-    }
-    n_sites[(int64_t) p * R + r] = cnt;
-    max_score[(int64_t) p * R + r] = best;
-}
-
-// ---------------------------------------------------------------- window sweep (N3) --
-// A sweep scans one chromosome span as ONE region and hands every hit to each window that holds it whole:
-// window k = [k * stride, k * stride + window) of the span; a hit of a width-W motif at span position g lies in
-// windows ceil((g + W - window) / stride) .. floor(g / stride)  (cscore.c:340: the window must contain all W bases).
-__device__ __forceinline__ void sweep_window_range(int64_t g, int W, int32_t window, int32_t stride, int64_t n_windows,
-                                                   int64_t &lo, int64_t &hi) {
-    hi = g / stride;
-    if (hi > n_windows - 1) hi = n_windows - 1;
-    const int64_t need = g + W - window;                       // smallest window start that still holds the site
-    lo = need <= 0 ? 0 : (need + stride - 1) / stride;
-}
-
-__global__ void __launch_bounds__(256) sweep_count_kernel(int64_t n, const int64_t *__restrict__ motif_off, int32_t P,
-                                                          const int32_t *__restrict__ width, const int64_t *__restrict__ pos,
-                                                          int32_t window, int32_t stride, int64_t n_windows,
-                                                          uint32_t *__restrict__ cnt) {
-    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int32_t m = motif_of_hit(motif_off, P, i);
-    int64_t lo, hi;
-    sweep_window_range(pos[i], width[m], window, stride, n_windows, lo, hi);
-    cnt[i] = hi >= lo ? (uint32_t) (hi - lo + 1) : 0u;
-}
-
-// Hand-out without a sort.  Within a motif the hits are ordered by span position g (then strand), and both ends of
-// a hit's window range are non-decreasing in g, so the number of sites that precede site (hit i, window w) in the
-// reference's order (motif, window, position, strand) is
-//     dst[i]                                   all windows of all earlier hits (exclusive prefix sum of the counts)
-//   + (w - lo_i)                               the hit's own earlier windows
-//   - sum_{i' < i} max(0, hi_i' - w)           earlier hits' windows that come AFTER w
-//   + sum_{i' > i} max(0, min(w, hi_i' + 1) - lo_i')   later hits' windows that come BEFORE w
-// where only hits of the same motif within one window length of g contribute to the two sums (a few at most, except
-// in low-complexity floods where the walk is bounded by window * 2 strands).  A site is the first of its
-// (motif, window) iff the previous hit of the motif does not reach window w.
-__global__ void __launch_bounds__(256) sweep_scatter_kernel(int64_t n, const int64_t *__restrict__ motif_off, int32_t P,
-                                                            const int32_t *__restrict__ width, const int64_t *__restrict__ pos,
-                                                            const double *__restrict__ score, const int8_t *__restrict__ strand,
-                                                            const uint64_t *__restrict__ dst, int32_t window, int32_t stride,
-                                                            int64_t n_windows, int64_t *__restrict__ seq_idx_out,
-                                                            int64_t *__restrict__ pos_out, double *__restrict__ score_out,
-                                                            int8_t *__restrict__ strand_out,
-                                                            unsigned long long *__restrict__ region_counts) {
-    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = i < n;
-    int32_t m = -1;
-    int n_first = 0;
-    if (live) {
-        m = motif_of_hit(motif_off, P, i);
-        const int W = width[m];
-        const int64_t first = motif_off[m], last = motif_off[m + 1];
-        const int64_t g = pos[i];
-        int64_t lo, hi;
-        sweep_window_range(g, W, window, stride, n_windows, lo, hi);
-        if (hi >= lo) {
-            const double sc = score[i];
-            const int8_t sd = strand[i];
-            const int64_t base = (int64_t) dst[i];
-            int64_t prev_hi = -1;                                    // window range end of the previous hit of this motif
-            if (i > first) { int64_t l2; sweep_window_range(pos[i - 1], W, window, stride, n_windows, l2, prev_hi); if (prev_hi < l2) prev_hi = -1; }
-            for (int64_t w = lo; w <= hi; w++) {
-                int64_t idx = base + (w - lo);
-                for (int64_t j = i - 1; j >= first; j--) {           // earlier hits still reaching past w
-                    int64_t l2, h2;
-                    sweep_window_range(pos[j], W, window, stride, n_windows, l2, h2);
-                    if (h2 <= lo) break;                             // monotone: nothing further back reaches past lo <= w
-                    if (h2 >= l2 && h2 > w) idx -= h2 - w;
-                }
-                for (int64_t j = i + 1; j < last; j++) {             // later hits that already started before w
-                    int64_t l2, h2;
-                    sweep_window_range(pos[j], W, window, stride, n_windows, l2, h2);
-                    if (l2 >= hi) break;                             // monotone: nothing further on starts before hi >= w
-                    if (h2 >= l2 && l2 < w) idx += (w < h2 + 1 ? w : h2 + 1) - l2;
-                }
-                seq_idx_out[idx] = w;
-                pos_out[idx] = g - w * stride;
-                score_out[idx] = sc;
-                strand_out[idx] = sd;
-                if (prev_hi < w) n_first++;
-            }
-        }
-    }
-    // windows with >= 1 site per motif (stats.py:29-31): one atomic per (wave, motif)
-    unsigned long long todo = __ballot(live && n_first > 0);
-    while (todo) {
-        const int leader = __ffsll((long long) todo) - 1;
-        const int32_t mm = __shfl(m, leader);
-        const unsigned long long same = __ballot(live && n_first > 0 && m == mm);
-        int v = (live && m == mm) ? n_first : 0;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-        if ((int) (threadIdx.x & 63) == leader) atomicAdd(&region_counts[mm], (unsigned long long) v);
-        todo &= ~same;
-    }
-}
-
-// The hand-out of a COUNTS-ONLY sweep (MS_STREAM_NO_HITS; round 5): what the enrichment statistics read of a sweep is, per motif, the number
-// of windows that hold >= 1 site (stats.py:29-31) -- plus, here, the number of sites.  Within a motif the hits are ordered by span
-// position and both ends of a hit's window range are non-decreasing, so hit i is the FIRST site of exactly the windows of its range that
-// the previous hit of the motif does not reach: max(0, hi_i - max(lo_i, prev_hi + 1) + 1).  One read per hit, no site is written
-// (the full hand-out writes 25 bytes per (site, window): 36 GB per pass of a 3 Gbp genome).
-__global__ void __launch_bounds__(256) sweep_countonly_kernel(int64_t n, const int64_t *__restrict__ motif_off, int32_t P,
-                                                              const int32_t *__restrict__ width, const int64_t *__restrict__ pos,
-                                                              int32_t window, int32_t stride, int64_t n_windows,
-                                                              unsigned long long *__restrict__ region_counts, unsigned long long *__restrict__ n_sites /* [P] */) {
-    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = i < n;
-    int32_t m = -1;
-    int n_first = 0;
-    unsigned long long mine = 0;
-    if (live) {
-        m = motif_of_hit(motif_off, P, i);
-        const int W = width[m];
-        int64_t lo, hi;
-        sweep_window_range(pos[i], W, window, stride, n_windows, lo, hi);
-        if (hi >= lo) {
-            mine = (unsigned long long) (hi - lo + 1);
-            int64_t prev_hi = -1;
-            if (i > motif_off[m]) { int64_t l2; sweep_window_range(pos[i - 1], W, window, stride, n_windows, l2, prev_hi); if (prev_hi < l2) prev_hi = -1; }
-            const int64_t from = lo > prev_hi + 1 ? lo : prev_hi + 1;
-            n_first = hi >= from ? (int) (hi - from + 1) : 0;
-        }
-    }
-    // per motif: windows with >= 1 site and sites -- one pair of atomics per (wave, motif), spread over the motifs' words (ONE counter for
-    // the sites was tried first: 234 k atomics per span on one address, 2.6 ms per span at the ~90 M/s a single word sustains)
-    unsigned long long todo = __ballot(live && mine > 0);
-    while (todo) {
-        const int leader = __ffsll((long long) todo) - 1;
-        const int32_t mm = __shfl(m, leader);
-        const unsigned long long same = __ballot(live && mine > 0 && m == mm);
-        int v = (live && m == mm) ? n_first : 0;
-        unsigned long long s64 = (live && m == mm) ? mine : 0ULL;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) { v += __shfl_xor(v, o); s64 += __shfl_xor(s64, o); }
-        if ((int) (threadIdx.x & 63) == leader) {
-            if (v) atomicAdd(&region_counts[mm], (unsigned long long) v);
-            atomicAdd(&n_sites[mm], s64);
-        }
-        todo &= ~same;
-    }
-}
-
-// per-motif offsets of the handed-out sites: where the motif's first hit went
-__global__ void sweep_offsets_kernel(const int64_t *__restrict__ motif_off, int32_t P, int64_t n, const uint64_t *__restrict__ dst,
-                                     int64_t total, int64_t *__restrict__ out) {
-    const int32_t m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m > P) return;
-    const int64_t f = m < P ? motif_off[m] : n;
-    out[m] = f < n ? (int64_t) dst[f] : total;
-}
-
-__global__ void fill_nan_kernel(double *__restrict__ a, int64_t n) {
-    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) a[i] = __longlong_as_double(0x7FF8000000000000LL);
-}
-
-// -------------------------------------------------------------------------- score --
-
-// c_score (cscore.c:191-224): one thread per (sequence, motif); first W bases only.
-__global__ void __launch_bounds__(256) score_kernel(const DevSeq S, const DevPwm Pw, int strand_mask,
-                                                    double *__restrict__ out) {
-    const int64_t r = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const int32_t p = blockIdx.y;
-    if (r >= S.R) return;
-    const int W = Pw.width[p];
-    const int64_t start = S.offsets[r];
-    const int64_t len = S.offsets[r + 1] - start;
-    const double2 *__restrict__ tab = Pw.tab2 + Pw.tab_off[p];
-    double fwd = 0.0, rev = 0.0;
-    const int n = (int) (len < W ? len : W);          // bases past the sequence end add nothing
-    for (int c0 = 0; c0 < n; c0 += 32) {
-        const uint64_t cw = code_window(S.codes, start + c0);
-        const uint32_t nw = n_window(S.nmask, start + c0);
-        const int m = (n - c0) < 32 ? (n - c0) : 32;
-        for (int c = 0; c < m; c++) {
-            if ((nw >> c) & 1u) continue;
-            const uint32_t b = (uint32_t) (cw >> (2 * c)) & 3u;
-            const double2 t = tab[(c0 + c) * 4 + b];
-            fwd += t.x;
-            rev += t.y;
-        }
-    }
-    double s = 0.0;
-    switch (strand_mask) {                               // cscore.c:208-222
-        case 1: s = fwd; break;
-        case 2: s = rev; break;
-        case 3: s = fwd > rev ? fwd : rev; break;
-    }
-    out[(int64_t) p * S.R + r] = s / Pw.max_raw[p];
-}
-
-// out[k] = sorted[ranks[k]]  (ranks beyond the row give NaN)
-__global__ void gather_ranks_kernel(const double *__restrict__ sorted, int64_t n, const int64_t *__restrict__ ranks,
-                                    int32_t n_ranks, double *__restrict__ out) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n_ranks) return;
-    const int64_t r = ranks[k];
-    out[k] = (r >= 0 && r < n) ? sorted[r] : __longlong_as_double(0x7FF8000000000000LL);
-}
-
-// --------------------------------------------------------------- on-device extraction --
-
-// Regions cut out of a resident packed genome (replaces Scanner._extract_seq -> Genome.fetch_sequence
-// -> pysam fetch, scanner.py:71-87 / genome/__init__.py:117-135): one thread per 32 output bases,
-// which may straddle several regions.  src_start[r] is the region's first base in the genome's
-// packed coordinates; dst_off[r] its first base in the output.
-__global__ void __launch_bounds__(256) extract_kernel(const uint32_t *__restrict__ gcodes, const uint32_t *__restrict__ gnmask,
-                                                      const int64_t *__restrict__ src_start, const int64_t *__restrict__ dst_off,
-                                                      int64_t R, int64_t n_out, uint32_t *__restrict__ codes,
-                                                      uint32_t *__restrict__ nmask) {
-    const int64_t u = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t pos = u * 32;
-    if (pos >= n_out) return;
-    int64_t r = find_region_bsearch(dst_off, R, pos);
-    uint64_t cw = 0;
-    uint32_t nw = 0;
-    int filled = 0;
-    while (filled < 32 && pos + filled < n_out) {
-        const int64_t d = pos + filled;
-        while (dst_off[r + 1] <= d) r++;                              // skip empty regions
-        const int64_t left = dst_off[r + 1] - d;
-        const int seg = left < (int64_t) (32 - filled) ? (int) left : 32 - filled;
-        const int64_t sp = src_start[r] + (d - dst_off[r]);
-        const uint64_t scw = code_window(gcodes, sp);
-        const uint32_t snw = n_window(gnmask, sp);
-        const uint64_t m = seg >= 32 ? ~0ULL : ((1ULL << (2 * seg)) - 1ULL);
-        cw |= (scw & m) << (2 * filled);
-        nw |= (snw & low_mask(seg)) << filled;
-        filled += seg;
-    }
-    codes[2 * u] = (uint32_t) cw;
-    codes[2 * u + 1] = (uint32_t) (cw >> 32);
-    nmask[u] = nw;
-}
-
-// ------------------------------------------------------------------- region hints --
-
-// blk2reg[b] = region that holds position 64*b (part of the extraction stage, next to pack_kernel); blkinfo[b] = the same region with
-// its own and the next two regions' starts RELATIVE to 64*b as 32-bit numbers -- everything rescore_kernel needs to place a position,
-// in one 16-byte read (the fp64 stage pays per vector-memory instruction); region -1: a start lies more than 2^31 bases away, look it up
-__global__ void __launch_bounds__(256) blk2reg_kernel(const int64_t *__restrict__ offsets, int64_t R, int64_t n_blocks,
-                                                      int32_t *__restrict__ blk2reg, int4 *__restrict__ blkinfo, int all_far) {
-    const int64_t b = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= n_blocks) return;
-    const int64_t r = find_region_bsearch(offsets, R, b * 64);
-    blk2reg[b] = (int32_t) r;
-    const int64_t base = b * 64;
-    const int64_t o0 = offsets[r] - base, o1 = offsets[r + 1 <= R ? r + 1 : R] - base, o2 = offsets[r + 2 <= R ? r + 2 : (r + 1 <= R ? r + 1 : R)] - base;
-    const bool fits = o0 > -(1LL << 31) && o1 < (1LL << 31) && o2 < (1LL << 31) && o1 > -(1LL << 31) && o2 > -(1LL << 31) && r < (1LL << 31);
-    blkinfo[b] = fits && !all_far ? make_int4((int) r, (int) o0, (int) o1, (int) o2) : make_int4(-1, 0, 0, 0);     // (all_far: a test aid, MS_BLKINFO_FAR)
-}
-
-// ---------------------------------------------------------------- compact copy-out --
-
-// coord = seq_idx << 32 | pos << 1 | (strand - 1): 8 bytes per hit on the host link instead of 17 (ms_result_hits_packed_host).
-// shift > 0: the 4-byte form, coord32 = seq_idx << shift | pos << 1 | (strand - 1) (ms_result_hits_packed12_host: the caller has
-// checked that every region index and position of the set fits).  bad[0] is set if a hit does not fit the format.
-__global__ void __launch_bounds__(256) pack_hits_kernel(int64_t n, const unsigned long long *__restrict__ n_dev, const int64_t *__restrict__ seq_idx,
-                                                        const int64_t *__restrict__ pos, const int8_t *__restrict__ strand,
-                                                        uint64_t *__restrict__ coord, unsigned int *__restrict__ bad, int shift) {
-    if (n_dev) { const unsigned long long nd = *n_dev; if ((unsigned long long) n > nd) n = (int64_t) nd; }     // (finalize_kernel: a predicted-size scan)
-    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t sq = (uint64_t) seq_idx[i], ps = (uint64_t) pos[i];
-    if (shift > 0) {
-        if ((ps >> (shift - 1)) != 0 || (sq >> (32 - shift)) != 0) *bad = 1u;
-        reinterpret_cast<uint32_t *>(coord)[i] = (uint32_t) ((sq << shift) | (ps << 1) | (uint64_t) (strand[i] == 2 ? 1 : 0));
-        return;
-    }
-    if ((sq >> 32) != 0 || (ps >> 31) != 0) *bad = 1u;
-    coord[i] = (sq << 32) | ((ps & 0x7FFFFFFFull) << 1) | (uint64_t) (strand[i] == 2 ? 1 : 0);
-}
-
-int launch_pack_hits(int64_t n, const unsigned long long *n_dev, const int64_t *seq_idx, const int64_t *pos, const int8_t *strand, uint64_t *coord,
-                     unsigned int *bad, hipStream_t st, int shift) {
-    if (n == 0) return MS_OK;
-    hipLaunchKernelGGL(pack_hits_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, n, n_dev, seq_idx, pos, strand, coord, bad, shift);
-    MS_HIP(hipGetLastError());
-    return MS_OK;
-}
-
-// ---------------------------------------------------------------------- launchers --
-
-int launch_extract(const uint32_t *gcodes, const uint32_t *gnmask, const int64_t *src_start, const int64_t *dst_off,
-                   int64_t R, int64_t n_out, uint32_t *codes, uint32_t *nmask, hipStream_t st) {
-    const int64_t n_units = (n_out + 31) / 32;
-    if (n_units == 0) return MS_OK;
-    hipLaunchKernelGGL(extract_kernel, dim3((unsigned) ((n_units + 255) / 256)), dim3(256), 0, st, gcodes, gnmask, src_start,
-                       dst_off, R, n_out, codes, nmask);
-    MS_HIP(hipGetLastError());
-    return MS_OK;
-}
-
-int launch_blk2reg(const int64_t *offsets, int64_t R, int64_t n_bases, int32_t *blk2reg, int4 *blkinfo, hipStream_t st) {
-    const int64_t n_blocks = (n_bases + 63) / 64 + 1;
-    const int all_far = measure_env("MS_BLKINFO_FAR") ? 1 : 0;          // test aid: every block record says "look the region up" (starts beyond 32 bits)
-    hipLaunchKernelGGL(blk2reg_kernel, dim3((unsigned) ((n_blocks + 255) / 256)), dim3(256), 0, st, offsets, R, n_blocks,
-                       blk2reg, blkinfo, all_far);
-    MS_HIP(hipGetLastError());
-    return MS_OK;
-}
-
-
-int launch_pack(const uint8_t *ascii, int64_t n_bases, uint32_t *codes, uint32_t *nmask, hipStream_t st) {
-    const int64_t n_units = (n_bases + 31) / 32;
-    if (n_units == 0) return MS_OK;
-    const int aligned16 = (reinterpret_cast<uintptr_t>(ascii) & 15u) == 0;
-    hipLaunchKernelGGL(pack_kernel, dim3((unsigned) ((n_units + 255) / 256)), dim3(256), 0, st, ascii, n_bases,
-                       codes, nmask, n_units, aligned16);
-    MS_HIP(hipGetLastError());
-    return MS_OK;
-}
-
 typedef void (*PfKernel)(const PfArgs);
 static PfKernel pf_kernel(bool wide, bool dense) {                  // (dense: only without wide classes)
     if (wide) return prefilter_f6_kernel<4, false>;
@@ -1819,368 +991,6 @@ int launch_prefilter(const PfArgs &A, bool wide, bool dense, int blocks_per_tile
     if (blocks_per_tile > n_chunks) blocks_per_tile = (int) n_chunks;
     hipLaunchKernelGGL(pf_kernel(wide, dense), dim3((unsigned) blocks_per_tile, (unsigned) n_tiles), dim3(kPfThreads), lds_bytes, st, A);
     MS_HIP(hipGetLastError());
-    return MS_OK;
-}
-
-int launch_exact_all(const DevSeq &S, const DevPwm &Pw, const int32_t *motifs, int32_t n_motifs, int strand_mask,
-                     const HitOut &H, hipStream_t st, int max_width) {
-    if (S.n_bases == 0 || n_motifs == 0) return MS_OK;
-    const bool tiled = max_width >= 1 && max_width <= kExactTileMaxW && !measure_env("MS_EXACT_UNTILED");      // (A/B and test aid: the round-1 kernel)
-    const size_t lds = tiled ? ((size_t) max_width * 4 + 1) * sizeof(double2) : 0;
-    if (tiled && lds > 48 * 1024)                                    // (motifs of more than 767 columns: rare enough to ask the driver every time, on whatever device is current)
-        MS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(exact_tiled_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    for (int32_t m0 = 0; m0 < n_motifs; m0 += 32768) {               // grid.y limit
-        const int32_t n = n_motifs - m0 < 32768 ? n_motifs - m0 : 32768;
-        if (tiled) {
-            dim3 grid((unsigned) ((S.n_bases + 256 * kExactIter - 1) / (256 * kExactIter)), (unsigned) n);
-            hipLaunchKernelGGL(exact_tiled_kernel, grid, dim3(256), lds, st, S, Pw, motifs + m0, strand_mask, H);
-        } else {
-            dim3 grid((unsigned) ((S.n_bases + 255) / 256), (unsigned) n);
-            hipLaunchKernelGGL(exact_all_kernel, grid, dim3(256), 0, st, S, Pw, motifs + m0, strand_mask, H);
-        }
-        MS_HIP(hipGetLastError());
-    }
-    return MS_OK;
-}
-
-// ---- the fp64 stage for LONG candidate lists: chunks of the list in motif order, the window carried through the sort.
-// A scattered read costs the texture addressers ~1.9 cycles per distinct 64-byte line its 64 lanes touch, whatever its width
-// (tools/ubench/gather_rate.hip: 122 cycles for 64 lines, 22 for 8), and ~16 of the ~21 reads per candidate are table entries -- one
-// line per (motif, column).  In list order a wave's lanes hold ~16 different motifs; in motif order far fewer -- but then the three
-// position-bound reads (block record, code words, mask words), whose lanes sit in one or two pre-filter units in list order, would
-// touch 64 lines each.  So a block takes 4096 candidates, reads the position-bound data in LIST order, packs what the scoring needs
-// into 24 bytes per candidate -- the window's 32 codes, its mask bits, (group, flags), the hit coordinate and how much room the region
-// leaves -- brings THAT into (table group, first flagged field) order with a counting sort in LDS on a hash of the record (no memory
-// read), and the scoring pass reads only per-motif data.  profiles/r03z_rescore_sorted.log: 2.01 ms per 500 Mbase against 2.73 in list
-// order (rescore_kernel, which short lists keep: a chunk per block leaves most of the device idle below ~2e6 candidates).
-constexpr int kRwThreads = 1024;
-constexpr int kRwPerThread = 4;
-constexpr int kRwChunk = kRwThreads * kRwPerThread;       // 4096 candidates: 96 KB of LDS
-constexpr int kRwBins = 4096;
-typedef HitStageN<2048> RwStage;
-
-__global__ void __launch_bounds__(kRwThreads) rescore_carry_kernel(const DevSeq S, const DevPwm Pw, const uint64_t *__restrict__ cand,
-                                                                   const unsigned long long *__restrict__ n_cand, uint64_t n_static, uint64_t cand_cap,
-                                                                   const FieldMeta *__restrict__ field_meta, int strand_mask, const HitOut H) {
-    extern __shared__ uint4 rw_lds4[];
-    uint64_t *s_cw = reinterpret_cast<uint64_t *>(rw_lds4);                                 // [kRwChunk] the window's codes
-    uint64_t *s_gk = s_cw + kRwChunk;                                                       // [kRwChunk] hit coordinate << 8 | room (bases to the region's end, <= 255)
-    uint32_t *s_nw = reinterpret_cast<uint32_t *>(s_gk + kRwChunk);                         // [kRwChunk] the window's non-ACGT bits
-    uint32_t *s_gf = s_nw + kRwChunk;                                                       // [kRwChunk] group << 16 | flags (0: nothing)
-    uint32_t *bins = s_gf + kRwChunk;                                                       // [kRwBins]
-    uint32_t *wave_tot = bins + kRwBins;                                                    // [16]
-    RwStage &st = *reinterpret_cast<RwStage *>(wave_tot + 32);
-    if (threadIdx.x == 0) st.n = 0;
-    unsigned long long n = n_static + *n_cand;
-    if (n > cand_cap) n = cand_cap;
-    const bool both = strand_mask == 3;
-    const int4 *__restrict__ meta4 = reinterpret_cast<const int4 *>(field_meta);
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t pmask = H.pbits ? ((1ULL << H.pbits) - 1ULL) : 0ULL;
-    const unsigned long long n_chunks = (n + kRwChunk - 1) / kRwChunk;
-    for (unsigned long long ch = blockIdx.x; ch < n_chunks; ch += gridDim.x) {
-        for (uint32_t i = threadIdx.x; i < (uint32_t) kRwBins; i += kRwThreads) bins[i] = 0;
-        __syncthreads();
-        {
-            // ---- list order: everything that depends on the POSITION
-            uint64_t cw[kRwPerThread], gk[kRwPerThread];
-            uint32_t nw[kRwPerThread], gf[kRwPerThread], key[kRwPerThread], rank[kRwPerThread];
-            int64_t g[kRwPerThread];
-            int4 bi[kRwPerThread];
-#pragma unroll
-            for (int k = 0; k < kRwPerThread; k++) {
-                const unsigned long long i = ch * kRwChunk + (unsigned long long) k * kRwThreads + threadIdx.x;
-                const uint64_t rec = i < n ? cand[i] : 0ULL;
-                g[k] = (int64_t) (rec >> 30);
-                gf[k] = (uint32_t) rec & 0x3FFFFFFFu;                                       // group << 16 | flags
-                if (!(gf[k] & 0xFFFFu)) { gf[k] = 0; g[k] = 0; }
-                bi[k] = S.blkinfo[g[k] >> 6];
-                cw[k] = code_window(S.codes, g[k]);
-                nw[k] = n_window(S.nmask, g[k]);
-            }
-#pragma unroll
-            for (int k = 0; k < kRwPerThread; k++) {
-                const int64_t base = g[k] & ~(int64_t) 63;
-                int64_t lo = bi[k].x, o0 = base + bi[k].y, o1 = base + bi[k].z, o2 = base + bi[k].w, r, beg, end;
-                if (bi[k].x < 0) {
-                    lo = S.blk2reg[g[k] >> 6];
-                    o0 = S.offsets[lo]; o1 = S.offsets[lo + 1];
-                    o2 = lo + 2 <= S.R ? S.offsets[lo + 2] : o1;
-                }
-                if (g[k] < o1) { r = lo; beg = o0; end = o1; }
-                else if (g[k] < o2) { r = lo + 1; beg = o1; end = o2; }
-                else { r = find_region(S, g[k]); beg = S.offsets[r]; end = S.offsets[r + 1]; }      // tiny regions
-                const uint64_t coord = H.pbits ? (((uint64_t) r << H.pbits) | (uint64_t) (g[k] - beg)) : (uint64_t) g[k];
-                const int64_t room = end - g[k];
-                gk[k] = (coord << 8) | (uint64_t) (room > 255 ? 255 : (room < 0 ? 0 : room));
-                const uint32_t f = gf[k] & 0xFFFFu;
-                const uint32_t fl = both ? (f | (f >> 1)) & 0x5555u : f;
-                key[k] = fl ? (((gf[k] >> 16) << 4) | (uint32_t) (__ffs((int) fl) - 1)) & (uint32_t) (kRwBins - 1) : (uint32_t) (kRwBins - 1);
-            }
-#pragma unroll
-            for (int k = 0; k < kRwPerThread; k++) rank[k] = atomicAdd(&bins[key[k]], 1u);
-            __syncthreads();
-            {   // exclusive prefix over the bins: four per thread, wave scans, wave totals
-                const uint32_t b0 = bins[4 * threadIdx.x], b1 = bins[4 * threadIdx.x + 1], b2 = bins[4 * threadIdx.x + 2], b3 = bins[4 * threadIdx.x + 3];
-                const uint32_t tot = b0 + b1 + b2 + b3;
-                uint32_t v = tot;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const uint32_t o = __shfl_up(v, d);
-                    if ((int) lane >= d) v += o;
-                }
-                if (lane == 63u) wave_tot[wave] = v;
-                __syncthreads();
-                uint32_t base = 0;
-                for (uint32_t w = 0; w < wave; w++) base += wave_tot[w];
-                const uint32_t excl = base + v - tot;
-                bins[4 * threadIdx.x] = excl;
-                bins[4 * threadIdx.x + 1] = excl + b0;
-                bins[4 * threadIdx.x + 2] = excl + b0 + b1;
-                bins[4 * threadIdx.x + 3] = excl + b0 + b1 + b2;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < kRwPerThread; k++) {
-                const uint32_t at = bins[key[k]] + rank[k];
-                s_cw[at] = cw[k]; s_gk[at] = gk[k]; s_nw[at] = nw[k]; s_gf[at] = gf[k];
-            }
-        }
-        __syncthreads();
-        // ---- motif order: two rounds of two candidates per thread, per-motif reads only
-        for (int round = 0; round < 2; round++) {
-#pragma unroll
-            for (int u = 0; u < 2; u++) {
-                const uint32_t at = (uint32_t) (round * 2 + u) * kRwThreads + threadIdx.x;
-                const uint32_t gfu = s_gf[at];
-                const uint32_t f = gfu & 0xFFFFu;
-                uint32_t flags = both ? (f | (f >> 1)) & 0x5555u : f;
-                if (!flags) continue;
-                const uint64_t cwu = s_cw[at], gku = s_gk[at];
-                const uint32_t nwu = s_nw[at];
-                const int32_t group = (int32_t) (gfu >> 16);
-                const int room = (int) (gku & 0xFFu);
-                const int64_t coord = (int64_t) (gku >> 8);
-                while (flags) {
-                    const int field = __ffs((int) flags) - 1;
-                    flags &= flags - 1u;
-                    const int4 f4 = meta4[group * kGroupFields + field];
-                    const int32_t m = f4.x;
-                    const int w = f4.y;
-                    if (m < 0) continue;
-                    if (w > room) continue;                                  // window runs past its region (cscore.c:340)
-                    double fwd, rev;
-                    if (w <= 32 && Pw.tab32) score_window32(Pw.tab2, (uint32_t) f4.z, Pw.zero_bytes, w, cwu, nwu, fwd, rev);
-                    else {
-                        const int64_t gpos = H.pbits ? S.offsets[coord >> H.pbits] + (int64_t) ((uint64_t) coord & pmask) : coord;
-                        score_window(S, Pw.tab2 + Pw.tab_off[m], w, gpos, fwd, rev);
-                    }
-                    test_and_stage(st, H, Pw, (uint32_t) m, coord, fwd, rev, strand_mask, __int_as_float(f4.w));
-                }
-            }
-            stage_flush(st, H);
-        }
-    }
-}
-
-size_t rescore_carry_lds_bytes() { return (size_t) kRwChunk * 24 + (size_t) kRwBins * 4 + 32 * 4 + sizeof(RwStage) + 64; }
-int rescore_carry_set_lds() {
-    MS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(rescore_carry_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) rescore_carry_lds_bytes()));
-    return MS_OK;
-}
-int launch_rescore_carry(const DevSeq &S, const DevPwm &Pw, const uint64_t *cand, const unsigned long long *n_cand, uint64_t n_static,
-                         uint64_t cand_cap, const FieldMeta *field_meta, int strand_mask, const HitOut &H, int n_blocks, hipStream_t st) {
-    hipLaunchKernelGGL(rescore_carry_kernel, dim3((unsigned) n_blocks), dim3(kRwThreads), rescore_carry_lds_bytes(), st, S, Pw, cand, n_cand, n_static,
-                       cand_cap, field_meta, strand_mask, H);
-    MS_HIP(hipGetLastError());
-    return MS_OK;
-}
-
-int launch_rescore(const DevSeq &S, const DevPwm &Pw, const uint64_t *cand, const unsigned long long *n_cand, uint64_t n_static,
-                   uint64_t cand_cap, const FieldMeta *field_meta, int strand_mask, const HitOut &H, int n_blocks,
-                   hipStream_t st) {
-    hipLaunchKernelGGL(rescore_kernel, dim3((unsigned) n_blocks), dim3(256), 0, st, S, Pw, cand, n_cand, n_static, cand_cap,
-                       field_meta, strand_mask, H);
-    MS_HIP(hipGetLastError());
-    return MS_OK;
-}
-
-int launch_finalize(const uint64_t *keys, int64_t n, const unsigned long long *n_dev, int gbits, int rbits, int pbits, int32_t P, const DevSeq &S,
-                    int64_t *seq_idx, int64_t *pos, int8_t *strand, int64_t *motif_first, unsigned long long *region_counts,
-                    hipStream_t st) {
-    if (n == 0 || n_dev) {                           // no hits: every per-motif offset is 0 (with n_dev the kernel overwrites them unless the count is 0)
-        MS_HIP(hipMemsetAsync(motif_first, 0, ((size_t) P + 1) * sizeof(int64_t), st));
-        if (n == 0) return MS_OK;
-    }
-    if (pbits > 0) {
-        hipLaunchKernelGGL(finalize_rp_kernel, dim3((unsigned) ((n + 1023) / 1024)), dim3(256), 0, st, keys, n, n_dev, rbits, pbits, P,
-                           seq_idx, pos, strand, motif_first, region_counts);
-        MS_HIP(hipGetLastError());
-        return MS_OK;
-    }
-    hipLaunchKernelGGL(finalize_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, keys, n, n_dev, gbits, P, S,
-                       seq_idx, pos, strand, motif_first, region_counts);
-    MS_HIP(hipGetLastError());
-    return MS_OK;
-}
-
-// keys[i] = all ones for i in [min(*n_dev, cap), cap): the unused rest of a predicted-size hit list sorts behind every hit
-__global__ void __launch_bounds__(256) fill_tail_kernel(uint64_t *__restrict__ keys, const unsigned long long *__restrict__ n_dev, uint64_t cap) {
-    const unsigned long long n = *n_dev < cap ? *n_dev : cap;
-    for (unsigned long long i = n + (unsigned long long) blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += (unsigned long long) gridDim.x * blockDim.x)
-        keys[i] = ~0ULL;
-}
-
-// The radix sort orders a scan's hits over the key bits ABOVE kSortLowBits only (one eight-bit pass fewer over 62 M pairs of 16 bytes);
-// hits that agree in those bits -- the same motif, region and 128-base stretch: a motif's two strands at one position, mostly -- are
-// neighbours afterwards, in the order the list held them.  This kernel finishes the order: the first hit of every such run sorts its
-// run in place by the whole key (runs hold <= 2^kSortLowBits hits: the keys of a scan are distinct; all-ones padding keys are left alone).
-__global__ void __launch_bounds__(256) sort_fixup_kernel(uint64_t *__restrict__ keys, double *__restrict__ vals, int64_t n, const unsigned long long *__restrict__ n_dev) {
-    if (n_dev) { const unsigned long long nd = *n_dev; if ((unsigned long long) n > nd) n = (int64_t) nd; }
-    const int64_t i0 = ((int64_t) blockIdx.x * blockDim.x + threadIdx.x) * 4;     // four consecutive hits per thread: two 16-byte reads
-    if (i0 >= n) return;
-    uint64_t k[4] = {0, 0, 0, 0};
-    uint64_t hi[6];                                                               // the high bits of hits i0 - 1 ... i0 + 4 (all-ones: none)
-    hi[0] = i0 > 0 ? keys[i0 - 1] >> kSortLowBits : ~0ULL;
-    if (i0 + 4 <= n) {
-        const ulonglong2 a = *reinterpret_cast<const ulonglong2 *>(keys + i0), b = *reinterpret_cast<const ulonglong2 *>(keys + i0 + 2);
-        k[0] = a.x; k[1] = a.y; k[2] = b.x; k[3] = b.y;
-    } else {
-        for (int q = 0; q < 4; q++) k[q] = i0 + q < n ? keys[i0 + q] : ~0ULL;
-    }
-#pragma unroll
-    for (int q = 0; q < 4; q++) hi[1 + q] = i0 + q < n ? k[q] >> kSortLowBits : ~0ULL;
-    hi[5] = i0 + 4 < n ? keys[i0 + 4] >> kSortLowBits : ~0ULL;
-    // (the high bits of a run's members do not change while another thread sorts the run: what is compared here is stable)
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int64_t i = i0 + q;
-        if (i + 1 >= n || hi[1 + q] == hi[q] || hi[1 + q] != hi[2 + q]) continue;   // not the first of a run of two or more
-        if (q < 3 && hi[3 + q] != hi[1 + q]) {
-            // a run of exactly two, both in this thread's registers (a motif's two strands at one position: nearly every run):
-            // half of them are in order already and touch nothing more
-            if (k[q] > k[q + 1]) {
-                keys[i] = k[q + 1];
-                keys[i + 1] = k[q];
-                const double v0 = vals[i], v1 = vals[i + 1];
-                vals[i] = v1;
-                vals[i + 1] = v0;
-            }
-            continue;
-        }
-        const uint64_t h = hi[1 + q];
-        int64_t len = 2;
-        while (i + len < n && len < ((int64_t) 1 << kSortLowBits) && (keys[i + len] >> kSortLowBits) == h) len++;
-        for (int64_t a = 1; a < len; a++) {                                      // insertion sort: short runs
-            const uint64_t ka = keys[i + a];
-            const double va = vals[i + a];
-            int64_t b = a;
-            while (b > 0 && keys[i + b - 1] > ka) { keys[i + b] = keys[i + b - 1]; vals[i + b] = vals[i + b - 1]; b--; }
-            keys[i + b] = ka;
-            vals[i + b] = va;
-        }
-    }
-}
-
-int launch_sort_fixup(uint64_t *keys, double *vals, int64_t n, const unsigned long long *n_dev, hipStream_t st) {
-    if (n == 0) return MS_OK;
-    hipLaunchKernelGGL(sort_fixup_kernel, dim3((unsigned) ((n + 1023) / 1024)), dim3(256), 0, st, keys, vals, n, n_dev);
-    MS_HIP(hipGetLastError());
-    return MS_OK;
-}
-
-int launch_fill_tail(uint64_t *keys, const unsigned long long *n_dev, uint64_t cap, hipStream_t st) {
-    if (cap == 0) return MS_OK;
-    hipLaunchKernelGGL(fill_tail_kernel, dim3(256), dim3(256), 0, st, keys, n_dev, cap);
-    MS_HIP(hipGetLastError());
-    return MS_OK;
-}
-
-int launch_sweep_count(int64_t n, const int64_t *motif_off, int32_t P, const int32_t *width, const int64_t *pos,
-                       int32_t window, int32_t stride, int64_t n_windows, uint32_t *cnt, hipStream_t st) {
-    if (n == 0) return MS_OK;
-    hipLaunchKernelGGL(sweep_count_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, n, motif_off, P, width, pos,
-                       window, stride, n_windows, cnt);
-    MS_HIP(hipGetLastError());
-    return MS_OK;
-}
-
-int launch_sweep_countonly(int64_t n, const int64_t *motif_off, int32_t P, const int32_t *width, const int64_t *pos,
-                           int32_t window, int32_t stride, int64_t n_windows, unsigned long long *region_counts, unsigned long long *n_sites, hipStream_t st) {
-    if (n == 0) return MS_OK;
-    hipLaunchKernelGGL(sweep_countonly_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, n, motif_off, P, width, pos,
-                       window, stride, n_windows, region_counts, n_sites);
-    MS_HIP(hipGetLastError());
-    return MS_OK;
-}
-
-int launch_sweep_scatter(int64_t n, const int64_t *motif_off, int32_t P, const int32_t *width, const int64_t *pos,
-                         const double *score, const int8_t *strand, const uint64_t *dst, int32_t window, int32_t stride,
-                         int64_t n_windows, int64_t total, int64_t *seq_idx_out, int64_t *pos_out, double *score_out,
-                         int8_t *strand_out, int64_t *motif_off_out, unsigned long long *region_counts, hipStream_t st) {
-    hipLaunchKernelGGL(sweep_offsets_kernel, dim3((unsigned) ((P + 1 + 255) / 256)), dim3(256), 0, st, motif_off, P, n, dst, total,
-                       motif_off_out);
-    MS_HIP(hipGetLastError());
-    if (n == 0) return MS_OK;
-    hipLaunchKernelGGL(sweep_scatter_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, n, motif_off, P, width, pos,
-                       score, strand, dst, window, stride, n_windows, seq_idx_out, pos_out, score_out, strand_out, region_counts);
-    MS_HIP(hipGetLastError());
-    return MS_OK;
-}
-
-int launch_dedup(int64_t n, const int64_t *motif_off, int32_t P, const int32_t *width, const int64_t *seq_idx,
-                 const int64_t *pos, const double *score, const int8_t *strand, uint32_t *keep, hipStream_t st) {
-    if (n == 0) return MS_OK;
-    hipLaunchKernelGGL(dedup_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, n, motif_off, P, width, seq_idx,
-                       pos, score, strand, keep);
-    MS_HIP(hipGetLastError());
-    return MS_OK;
-}
-
-int launch_compact_hits(int64_t n, const uint32_t *keep, const uint64_t *dst, const int64_t *seq_in, const int64_t *pos_in,
-                        const double *score_in, const int8_t *strand_in, int64_t *seq_out, int64_t *pos_out,
-                        double *score_out, int8_t *strand_out, const int64_t *off_in, int32_t P, int64_t *off_out,
-                        hipStream_t st) {
-    hipLaunchKernelGGL(remap_offsets_kernel, dim3((unsigned) ((P + 1 + 255) / 256)), dim3(256), 0, st, off_in, P, n, dst, keep, off_out);
-    MS_HIP(hipGetLastError());
-    if (n == 0) return MS_OK;
-    hipLaunchKernelGGL(compact_hits_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, n, keep, dst, seq_in, pos_in,
-                       score_in, strand_in, seq_out, pos_out, score_out, strand_out);
-    MS_HIP(hipGetLastError());
-    return MS_OK;
-}
-
-int launch_site_tables(int64_t n, const int64_t *motif_off, int32_t P, int64_t R, const int64_t *seq_idx,
-                       const double *score, int32_t *n_sites, double *max_score, hipStream_t st) {
-    const int64_t cells = (int64_t) P * R;
-    if (cells == 0) return MS_OK;
-    MS_HIP(hipMemsetAsync(n_sites, 0, (size_t) cells * sizeof(int32_t), st));
-    hipLaunchKernelGGL(fill_nan_kernel, dim3((unsigned) ((cells + 255) / 256)), dim3(256), 0, st, max_score, cells);
-    MS_HIP(hipGetLastError());
-    if (n == 0) return MS_OK;
-    hipLaunchKernelGGL(site_tables_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, n, motif_off, P, R, seq_idx,
-                       score, n_sites, max_score);
-    MS_HIP(hipGetLastError());
-    return MS_OK;
-}
-
-int launch_gather_ranks(const double *sorted, int64_t n, const int64_t *ranks, int32_t n_ranks, double *out, hipStream_t st) {
-    if (n_ranks <= 0) return MS_OK;
-    hipLaunchKernelGGL(gather_ranks_kernel, dim3((unsigned) ((n_ranks + 63) / 64)), dim3(64), 0, st, sorted, n, ranks, n_ranks, out);
-    MS_HIP(hipGetLastError());
-    return MS_OK;
-}
-
-int launch_score(const DevSeq &S, const DevPwm &Pw, int strand_mask, double *out, hipStream_t st) {
-    if (S.R == 0 || Pw.P == 0) return MS_OK;
-    for (int32_t p0 = 0; p0 < Pw.P; p0 += 32768) {
-        const int32_t n = Pw.P - p0 < 32768 ? Pw.P - p0 : 32768;
-        DevPwm sub = Pw;
-        sub.tab_off += p0; sub.width += p0; sub.max_raw += p0; sub.cutoff += p0; sub.raw_floor += p0; sub.P = n;
-        dim3 grid((unsigned) ((S.R + 255) / 256), (unsigned) n);
-        hipLaunchKernelGGL(score_kernel, grid, dim3(256), 0, st, S, sub, strand_mask, out + (int64_t) p0 * S.R);
-        MS_HIP(hipGetLastError());
-    }
     return MS_OK;
 }
 

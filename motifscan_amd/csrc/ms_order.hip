@@ -1,9 +1,15 @@
-// ms_order.hip -- the last step of a scan's ordering when the hit keys carry (region, position inside the region) (pbits > 0).
+// ms_order.hip -- the last step of a scan's ordering: sorted hit keys -> seq_idx, pos, strand, per-motif offsets and region counts.
+// Which kernels run depends on the key layout (HitOut, ms_kernels.h) and on the key bits the radix passes covered (scan_back):
+//   pbits > 0 (region, position in it), sorted over [L, end_bit), L > 0   order_finalize_kernel, order_overflow_kernel: a region set's usual path
+//   pbits > 0, sorted over every bit (short lists, ms_scan_regions_once)  finalize_rp_kernel: only bits to unpack
+//   pbits == 0 (global base position: regions too long for the field)     sort_fixup_kernel if the sort left out the low kSortLowBits, then
+//                                                                         finalize_kernel, which looks every hit's region up
+//   either layout, a scan with predicted sizes                            fill_tail_kernel first: all-ones keys behind the hits sort last
 //
 // The radix passes (ms_sort.hip) order the keys over the bits [L, end_bit) only.  Hits that agree in those bits -- a RUN -- are then
 // neighbours, in no particular order among themselves.  order_finalize_kernel finishes the order of every run in LDS and writes the
 // result arrays in the same pass: seq_idx, pos and strand, the score moved to its final slot of d_score, the per-motif offsets and
-// the per-motif region counts (the semantics of finalize_rp_kernel, ms_kernels.hip).  This replaces a fix-up kernel plus a finalize
+// the per-motif region counts (the semantics of finalize_rp_kernel, below).  This replaces a fix-up kernel plus a finalize
 // kernel (one read of keys and scores fewer), and L up to 24 lets the radix sort drop up to two of its eight-bit passes.
 //
 //   order_finalize_kernel  block b owns the runs that START in slots [b * kOrderTile, (b + 1) * kOrderTile); it stages those slots and
@@ -21,7 +27,7 @@
 // two runs, so the pair changes.  The radix-order predecessor is therefore enough, and no block depends on another block's output.
 #include <algorithm>
 
-#include "ms_kernels.h"
+#include "ms_device.h"
 
 namespace ms {
 
@@ -285,6 +291,215 @@ int launch_order_finalize(uint64_t *keys, double *score, int64_t n, const unsign
                            ovf, ovf_n, ovf_cap);
         MS_HIP(hipGetLastError());
     }
+    return MS_OK;
+}
+
+// --------------------------------------- fill_tail, and the tail of the other two paths --
+
+// keys[i] = all ones for i in [min(*n_dev, cap), cap): the unused rest of a predicted-size hit list sorts behind every hit
+__global__ void __launch_bounds__(256) fill_tail_kernel(uint64_t *__restrict__ keys, const unsigned long long *__restrict__ n_dev, uint64_t cap) {
+    const unsigned long long n = *n_dev < cap ? *n_dev : cap;
+    for (unsigned long long i = n + (unsigned long long) blockIdx.x * blockDim.x + threadIdx.x; i < cap; i += (unsigned long long) gridDim.x * blockDim.x)
+        keys[i] = ~0ULL;
+}
+
+// The radix sort orders a scan's hits over the key bits ABOVE kSortLowBits only (one eight-bit pass fewer over 62 M pairs of 16 bytes);
+// hits that agree in those bits -- the same motif, region and 128-base stretch: a motif's two strands at one position, mostly -- are
+// neighbours afterwards, in the order the list held them.  This kernel finishes the order: the first hit of every such run sorts its
+// run in place by the whole key (runs hold <= 2^kSortLowBits hits: the keys of a scan are distinct; all-ones padding keys are left alone).
+__global__ void __launch_bounds__(256) sort_fixup_kernel(uint64_t *__restrict__ keys, double *__restrict__ vals, int64_t n, const unsigned long long *__restrict__ n_dev) {
+    if (n_dev) { const unsigned long long nd = *n_dev; if ((unsigned long long) n > nd) n = (int64_t) nd; }
+    const int64_t i0 = ((int64_t) blockIdx.x * blockDim.x + threadIdx.x) * 4;     // four consecutive hits per thread: two 16-byte reads
+    if (i0 >= n) return;
+    uint64_t k[4] = {0, 0, 0, 0};
+    uint64_t hi[6];                                                               // the high bits of hits i0 - 1 ... i0 + 4 (all-ones: none)
+    hi[0] = i0 > 0 ? keys[i0 - 1] >> kSortLowBits : ~0ULL;
+    if (i0 + 4 <= n) {
+        const ulonglong2 a = *reinterpret_cast<const ulonglong2 *>(keys + i0), b = *reinterpret_cast<const ulonglong2 *>(keys + i0 + 2);
+        k[0] = a.x; k[1] = a.y; k[2] = b.x; k[3] = b.y;
+    } else {
+        for (int q = 0; q < 4; q++) k[q] = i0 + q < n ? keys[i0 + q] : ~0ULL;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; q++) hi[1 + q] = i0 + q < n ? k[q] >> kSortLowBits : ~0ULL;
+    hi[5] = i0 + 4 < n ? keys[i0 + 4] >> kSortLowBits : ~0ULL;
+    // (the high bits of a run's members do not change while another thread sorts the run: what is compared here is stable)
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int64_t i = i0 + q;
+        if (i + 1 >= n || hi[1 + q] == hi[q] || hi[1 + q] != hi[2 + q]) continue;   // not the first of a run of two or more
+        if (q < 3 && hi[3 + q] != hi[1 + q]) {
+            // a run of exactly two, both in this thread's registers (a motif's two strands at one position: nearly every run):
+            // half of them are in order already and touch nothing more
+            if (k[q] > k[q + 1]) {
+                keys[i] = k[q + 1];
+                keys[i + 1] = k[q];
+                const double v0 = vals[i], v1 = vals[i + 1];
+                vals[i] = v1;
+                vals[i + 1] = v0;
+            }
+            continue;
+        }
+        const uint64_t h = hi[1 + q];
+        int64_t len = 2;
+        while (i + len < n && len < ((int64_t) 1 << kSortLowBits) && (keys[i + len] >> kSortLowBits) == h) len++;
+        for (int64_t a = 1; a < len; a++) {                                      // insertion sort: short runs
+            const uint64_t ka = keys[i + a];
+            const double va = vals[i + a];
+            int64_t b = a;
+            while (b > 0 && keys[i + b - 1] > ka) { keys[i + b] = keys[i + b - 1]; vals[i + b] = vals[i + b - 1]; b--; }
+            keys[i + b] = ka;
+            vals[i + b] = va;
+        }
+    }
+}
+
+int launch_sort_fixup(uint64_t *keys, double *vals, int64_t n, const unsigned long long *n_dev, hipStream_t st) {
+    if (n == 0) return MS_OK;
+    hipLaunchKernelGGL(sort_fixup_kernel, dim3((unsigned) ((n + 1023) / 1024)), dim3(256), 0, st, keys, vals, n, n_dev);
+    MS_HIP(hipGetLastError());
+    return MS_OK;
+}
+
+int launch_fill_tail(uint64_t *keys, const unsigned long long *n_dev, uint64_t cap, hipStream_t st) {
+    if (cap == 0) return MS_OK;
+    hipLaunchKernelGGL(fill_tail_kernel, dim3(256), dim3(256), 0, st, keys, n_dev, cap);
+    MS_HIP(hipGetLastError());
+    return MS_OK;
+}
+
+// n_dev != nullptr: the number of hits is only known on the device (a scan whose sizes were predicted, scan_locked): n is then
+// the launch's capacity and the true count min(*n_dev, n) is read here.
+__global__ void __launch_bounds__(256) finalize_kernel(const uint64_t *__restrict__ keys, int64_t n, const unsigned long long *__restrict__ n_dev,
+                                                       int gbits, int32_t P, const DevSeq S,
+                                                       int64_t *__restrict__ seq_idx, int64_t *__restrict__ pos,
+                                                       int8_t *__restrict__ strand, int64_t *__restrict__ motif_first,
+                                                       unsigned long long *__restrict__ region_counts) {
+    if (n_dev) { const unsigned long long nd = *n_dev; if ((unsigned long long) n > nd) n = (int64_t) nd; }
+    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = i < n;
+    uint32_t motif = 0xFFFFFFFFu;
+    bool new_pair = false;
+    if (live) {
+        const uint64_t k = keys[i];
+        const uint64_t gmask = (1ULL << gbits) - 1ULL;
+        const int64_t g = (int64_t) ((k >> 1) & gmask);
+        motif = (uint32_t) (k >> (gbits + 1));
+        const int64_t r = find_region(S, g);
+        seq_idx[i] = r;
+        pos[i] = g - S.offsets[r];
+        strand[i] = (int8_t) ((k & 1ULL) ? 2 : 1);
+        bool first_of_motif = (i == 0);
+        new_pair = true;
+        int64_t q0 = 0;                                  // per-motif offsets: every motif after the previous hit's up to this one starts here
+        if (i > 0) {
+            const uint64_t kp = keys[i - 1];
+            const uint32_t mp = (uint32_t) (kp >> (gbits + 1));
+            first_of_motif = mp != motif;
+            q0 = (int64_t) mp + 1;
+            if (!first_of_motif) {
+                const int64_t gp = (int64_t) ((kp >> 1) & gmask);
+                new_pair = gp < S.offsets[r];            // previous hit of this motif lies in an earlier region
+            }
+        }
+        if (first_of_motif) for (int64_t q = q0; q <= (int64_t) motif; q++) motif_first[q] = i;
+        if (i == n - 1) for (int64_t q = (int64_t) motif + 1; q <= P; q++) motif_first[q] = n;     // motifs after the last hit: empty
+    }
+    // number of regions with >= 1 hit per motif (stats.py:29-31): one atomic per (wave, motif)
+    unsigned long long todo = __ballot(live && new_pair);
+    while (todo) {
+        const int leader = __ffsll((long long) todo) - 1;
+        const uint32_t m = __shfl(motif, leader);
+        const unsigned long long same = __ballot(live && new_pair && motif == m);
+        if ((int) (threadIdx.x & 63) == leader) atomicAdd(&region_counts[m], (unsigned long long) __popcll(same));
+        todo &= ~same;
+    }
+}
+
+// The same when the keys carry (region, position inside the region): nothing to look up, only bits to unpack.
+// Four consecutive hits per thread: 16-byte loads and stores, the four strand bytes as one word.
+__global__ void __launch_bounds__(256) finalize_rp_kernel(const uint64_t *__restrict__ keys, int64_t n, const unsigned long long *__restrict__ n_dev,
+                                                          int rbits, int pbits, int32_t P,
+                                                          int64_t *__restrict__ seq_idx, int64_t *__restrict__ pos,
+                                                          int8_t *__restrict__ strand, int64_t *__restrict__ motif_first,
+                                                          unsigned long long *__restrict__ region_counts) {
+    if (n_dev) { const unsigned long long nd = *n_dev; if ((unsigned long long) n > nd) n = (int64_t) nd; }
+    const int64_t i0 = 4 * ((int64_t) blockIdx.x * blockDim.x + threadIdx.x);
+    const bool live = i0 < n;
+    uint32_t motif0 = 0xFFFFFFFFu;
+    int n_new = 0;                                              // new (motif, region) pairs among this thread's hits of motif0
+    if (live) {
+        uint64_t k[4];
+        const bool full = i0 + 4 <= n;
+        if (full) {
+            const ulonglong2 a = *reinterpret_cast<const ulonglong2 *>(keys + i0), b2 = *reinterpret_cast<const ulonglong2 *>(keys + i0 + 2);
+            k[0] = a.x; k[1] = a.y; k[2] = b2.x; k[3] = b2.y;
+        } else {
+            for (int j = 0; j < 4; j++) k[j] = i0 + j < n ? keys[i0 + j] : 0;
+        }
+        uint64_t prev = i0 > 0 ? keys[i0 - 1] >> (pbits + 1) : ~0ULL;
+        int64_t sq[4], ps[4];
+        uint32_t sd = 0;
+        const uint64_t rmask = (1ULL << rbits) - 1ULL, pmask = (1ULL << pbits) - 1ULL;
+        motif0 = (uint32_t) (k[0] >> (pbits + 1 + rbits));
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (i0 + j < n) {
+                const uint64_t pair = k[j] >> (pbits + 1);      // (motif, region)
+                const uint32_t motif = (uint32_t) (pair >> rbits);
+                sq[j] = (int64_t) (pair & rmask);
+                ps[j] = (int64_t) ((k[j] >> 1) & pmask);
+                sd |= ((k[j] & 1ULL) ? 2u : 1u) << (8 * j);
+                if (prev == ~0ULL || (uint32_t) (prev >> rbits) != motif)        // every motif after the previous hit's up to this one starts here
+                    for (int64_t q = prev == ~0ULL ? 0 : (int64_t) (uint32_t) (prev >> rbits) + 1; q <= (int64_t) motif; q++) motif_first[q] = i0 + j;
+                if (i0 + j == n - 1) for (int64_t q = (int64_t) motif + 1; q <= P; q++) motif_first[q] = n;   // motifs after the last hit: empty
+                if (prev != pair) {
+                    if (motif == motif0) n_new++;
+                    else atomicAdd(&region_counts[motif], 1ULL);    // a thread's hits rarely span two motifs
+                }
+                prev = pair;
+            }
+        }
+        if (full) {
+            *reinterpret_cast<longlong2 *>(seq_idx + i0) = make_longlong2(sq[0], sq[1]);
+            *reinterpret_cast<longlong2 *>(seq_idx + i0 + 2) = make_longlong2(sq[2], sq[3]);
+            *reinterpret_cast<longlong2 *>(pos + i0) = make_longlong2(ps[0], ps[1]);
+            *reinterpret_cast<longlong2 *>(pos + i0 + 2) = make_longlong2(ps[2], ps[3]);
+            *reinterpret_cast<uint32_t *>(strand + i0) = sd;
+        } else {
+            for (int j = 0; j < 4 && i0 + j < n; j++) { seq_idx[i0 + j] = sq[j]; pos[i0 + j] = ps[j]; strand[i0 + j] = (int8_t) ((sd >> (8 * j)) & 0xFFu); }
+        }
+    }
+    // regions with >= 1 hit per motif (stats.py:29-31): one atomic per (wave, motif)
+    unsigned long long todo = __ballot(live && n_new > 0);
+    while (todo) {
+        const int leader = __ffsll((long long) todo) - 1;
+        const uint32_t m = __shfl(motif0, leader);
+        const unsigned long long same = __ballot(live && n_new > 0 && motif0 == m);
+        int v = (live && motif0 == m) ? n_new : 0;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+        if ((int) (threadIdx.x & 63) == leader) atomicAdd(&region_counts[m], (unsigned long long) v);
+        todo &= ~same;
+    }
+}
+
+int launch_finalize(const uint64_t *keys, int64_t n, const unsigned long long *n_dev, int gbits, int rbits, int pbits, int32_t P, const DevSeq &S,
+                    int64_t *seq_idx, int64_t *pos, int8_t *strand, int64_t *motif_first, unsigned long long *region_counts,
+                    hipStream_t st) {
+    if (n == 0 || n_dev) {                           // no hits: every per-motif offset is 0 (with n_dev the kernel overwrites them unless the count is 0)
+        MS_HIP(hipMemsetAsync(motif_first, 0, ((size_t) P + 1) * sizeof(int64_t), st));
+        if (n == 0) return MS_OK;
+    }
+    if (pbits > 0) {
+        hipLaunchKernelGGL(finalize_rp_kernel, dim3((unsigned) ((n + 1023) / 1024)), dim3(256), 0, st, keys, n, n_dev, rbits, pbits, P,
+                           seq_idx, pos, strand, motif_first, region_counts);
+        MS_HIP(hipGetLastError());
+        return MS_OK;
+    }
+    hipLaunchKernelGGL(finalize_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, keys, n, n_dev, gbits, P, S,
+                       seq_idx, pos, strand, motif_first, region_counts);
+    MS_HIP(hipGetLastError());
     return MS_OK;
 }
 

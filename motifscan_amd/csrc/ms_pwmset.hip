@@ -8,9 +8,74 @@
 #include <mutex>
 #include <thread>
 
+#include "ms_device.h"
 #include "ms_handles.h"
 
 namespace ms {
+
+// -------------------------------------------------------------------------- score --
+
+// c_score (cscore.c:191-224): one thread per (sequence, motif); first W bases only.
+__global__ void __launch_bounds__(256) score_kernel(const DevSeq S, const DevPwm Pw, int strand_mask,
+                                                    double *__restrict__ out) {
+    const int64_t r = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    const int32_t p = blockIdx.y;
+    if (r >= S.R) return;
+    const int W = Pw.width[p];
+    const int64_t start = S.offsets[r];
+    const int64_t len = S.offsets[r + 1] - start;
+    const double2 *__restrict__ tab = Pw.tab2 + Pw.tab_off[p];
+    double fwd = 0.0, rev = 0.0;
+    const int n = (int) (len < W ? len : W);          // bases past the sequence end add nothing
+    for (int c0 = 0; c0 < n; c0 += 32) {
+        const uint64_t cw = code_window(S.codes, start + c0);
+        const uint32_t nw = n_window(S.nmask, start + c0);
+        const int m = (n - c0) < 32 ? (n - c0) : 32;
+        for (int c = 0; c < m; c++) {
+            if ((nw >> c) & 1u) continue;
+            const uint32_t b = (uint32_t) (cw >> (2 * c)) & 3u;
+            const double2 t = tab[(c0 + c) * 4 + b];
+            fwd += t.x;
+            rev += t.y;
+        }
+    }
+    double s = 0.0;
+    switch (strand_mask) {                               // cscore.c:208-222
+        case 1: s = fwd; break;
+        case 2: s = rev; break;
+        case 3: s = fwd > rev ? fwd : rev; break;
+    }
+    out[(int64_t) p * S.R + r] = s / Pw.max_raw[p];
+}
+
+// out[k] = sorted[ranks[k]]  (ranks beyond the row give NaN)
+__global__ void gather_ranks_kernel(const double *__restrict__ sorted, int64_t n, const int64_t *__restrict__ ranks,
+                                    int32_t n_ranks, double *__restrict__ out) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_ranks) return;
+    const int64_t r = ranks[k];
+    out[k] = (r >= 0 && r < n) ? sorted[r] : __longlong_as_double(0x7FF8000000000000LL);
+}
+
+static int launch_gather_ranks(const double *sorted, int64_t n, const int64_t *ranks, int32_t n_ranks, double *out, hipStream_t st) {
+    if (n_ranks <= 0) return MS_OK;
+    hipLaunchKernelGGL(gather_ranks_kernel, dim3((unsigned) ((n_ranks + 63) / 64)), dim3(64), 0, st, sorted, n, ranks, n_ranks, out);
+    MS_HIP(hipGetLastError());
+    return MS_OK;
+}
+
+static int launch_score(const DevSeq &S, const DevPwm &Pw, int strand_mask, double *out, hipStream_t st) {
+    if (S.R == 0 || Pw.P == 0) return MS_OK;
+    for (int32_t p0 = 0; p0 < Pw.P; p0 += 32768) {
+        const int32_t n = Pw.P - p0 < 32768 ? Pw.P - p0 : 32768;
+        DevPwm sub = Pw;
+        sub.tab_off += p0; sub.width += p0; sub.max_raw += p0; sub.cutoff += p0; sub.raw_floor += p0; sub.P = n;
+        dim3 grid((unsigned) ((S.R + 255) / 256), (unsigned) n);
+        hipLaunchKernelGGL(score_kernel, grid, dim3(256), 0, st, S, sub, strand_mask, out + (int64_t) p0 * S.R);
+        MS_HIP(hipGetLastError());
+    }
+    return MS_OK;
+}
 
 // C-style max_raw: column maxima start at 0 (cscore.c:36-48)
 static double c_max_raw(const double *m, int W) {

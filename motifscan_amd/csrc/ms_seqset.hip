@@ -8,9 +8,139 @@
 #include <mutex>
 #include <thread>
 
+#include "ms_device.h"
 #include "ms_handles.h"
 
 namespace ms {
+
+// --------------------------------------------------------------------------- pack --
+
+// One thread per 32 bases: two 16-byte loads, one 8-byte + one 4-byte store.
+__global__ void __launch_bounds__(256) pack_kernel(const uint8_t *__restrict__ ascii, int64_t n_bases,
+                                                   uint32_t *__restrict__ codes, uint32_t *__restrict__ nmask,
+                                                   int64_t n_units, int aligned16) {
+    const int64_t u = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= n_units) return;
+    const int64_t base = u * 32;
+    uint32_t raw[8];
+    if (aligned16 && base + 32 <= n_bases) {
+        const uint4 a = *reinterpret_cast<const uint4 *>(ascii + base);
+        const uint4 b = *reinterpret_cast<const uint4 *>(ascii + base + 16);
+        raw[0] = a.x; raw[1] = a.y; raw[2] = a.z; raw[3] = a.w;
+        raw[4] = b.x; raw[5] = b.y; raw[6] = b.z; raw[7] = b.w;
+    } else {
+        for (int k = 0; k < 8; k++) {
+            uint32_t w = 0;
+            for (int j = 0; j < 4; j++) {
+                const int64_t i = base + k * 4 + j;
+                w |= (uint32_t) (i < n_bases ? ascii[i] : (uint8_t) 'A') << (8 * j);
+            }
+            raw[k] = w;
+        }
+    }
+    uint64_t cw = 0;
+    uint32_t nw = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint32_t ch = ((raw[k] >> (8 * j)) & 0xFFu) | 0x20u;      // fold case (cscore.c:93-108)
+            const uint32_t code = ((ch >> 1) ^ (ch >> 2)) & 3u;             // a,c,g,t -> 0,1,2,3
+            const bool acgt = ch == 0x61u || ch == 0x63u || ch == 0x67u || ch == 0x74u;
+            const int i = k * 4 + j;
+            cw |= (uint64_t) (acgt ? code : 0u) << (2 * i);
+            nw |= (acgt ? 0u : 1u) << i;
+        }
+    }
+    if (base + 32 > n_bases) {          // bases past the end are neither N nor scanned
+        const int valid = (int) (n_bases - base);
+        nw &= low_mask(valid);
+    }
+    codes[2 * u] = (uint32_t) cw;
+    codes[2 * u + 1] = (uint32_t) (cw >> 32);
+    nmask[u] = nw;
+}
+
+// --------------------------------------------------------------- on-device extraction --
+
+// Regions cut out of a resident packed genome (replaces Scanner._extract_seq -> Genome.fetch_sequence
+// -> pysam fetch, scanner.py:71-87 / genome/__init__.py:117-135): one thread per 32 output bases,
+// which may straddle several regions.  src_start[r] is the region's first base in the genome's
+// packed coordinates; dst_off[r] its first base in the output.
+__global__ void __launch_bounds__(256) extract_kernel(const uint32_t *__restrict__ gcodes, const uint32_t *__restrict__ gnmask,
+                                                      const int64_t *__restrict__ src_start, const int64_t *__restrict__ dst_off,
+                                                      int64_t R, int64_t n_out, uint32_t *__restrict__ codes,
+                                                      uint32_t *__restrict__ nmask) {
+    const int64_t u = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t pos = u * 32;
+    if (pos >= n_out) return;
+    int64_t r = find_region_bsearch(dst_off, R, pos);
+    uint64_t cw = 0;
+    uint32_t nw = 0;
+    int filled = 0;
+    while (filled < 32 && pos + filled < n_out) {
+        const int64_t d = pos + filled;
+        while (dst_off[r + 1] <= d) r++;                              // skip empty regions
+        const int64_t left = dst_off[r + 1] - d;
+        const int seg = left < (int64_t) (32 - filled) ? (int) left : 32 - filled;
+        const int64_t sp = src_start[r] + (d - dst_off[r]);
+        const uint64_t scw = code_window(gcodes, sp);
+        const uint32_t snw = n_window(gnmask, sp);
+        const uint64_t m = seg >= 32 ? ~0ULL : ((1ULL << (2 * seg)) - 1ULL);
+        cw |= (scw & m) << (2 * filled);
+        nw |= (snw & low_mask(seg)) << filled;
+        filled += seg;
+    }
+    codes[2 * u] = (uint32_t) cw;
+    codes[2 * u + 1] = (uint32_t) (cw >> 32);
+    nmask[u] = nw;
+}
+
+// ------------------------------------------------------------------- region hints --
+
+// blk2reg[b] = region that holds position 64*b (part of the extraction stage, next to pack_kernel); blkinfo[b] = the same region with
+// its own and the next two regions' starts RELATIVE to 64*b as 32-bit numbers -- everything rescore_kernel needs to place a position,
+// in one 16-byte read (the fp64 stage pays per vector-memory instruction); region -1: a start lies more than 2^31 bases away, look it up
+__global__ void __launch_bounds__(256) blk2reg_kernel(const int64_t *__restrict__ offsets, int64_t R, int64_t n_blocks,
+                                                      int32_t *__restrict__ blk2reg, int4 *__restrict__ blkinfo, int all_far) {
+    const int64_t b = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n_blocks) return;
+    const int64_t r = find_region_bsearch(offsets, R, b * 64);
+    blk2reg[b] = (int32_t) r;
+    const int64_t base = b * 64;
+    const int64_t o0 = offsets[r] - base, o1 = offsets[r + 1 <= R ? r + 1 : R] - base, o2 = offsets[r + 2 <= R ? r + 2 : (r + 1 <= R ? r + 1 : R)] - base;
+    const bool fits = o0 > -(1LL << 31) && o1 < (1LL << 31) && o2 < (1LL << 31) && o1 > -(1LL << 31) && o2 > -(1LL << 31) && r < (1LL << 31);
+    blkinfo[b] = fits && !all_far ? make_int4((int) r, (int) o0, (int) o1, (int) o2) : make_int4(-1, 0, 0, 0);     // (all_far: a test aid, MS_BLKINFO_FAR)
+}
+
+static int launch_extract(const uint32_t *gcodes, const uint32_t *gnmask, const int64_t *src_start, const int64_t *dst_off,
+                          int64_t R, int64_t n_out, uint32_t *codes, uint32_t *nmask, hipStream_t st) {
+    const int64_t n_units = (n_out + 31) / 32;
+    if (n_units == 0) return MS_OK;
+    hipLaunchKernelGGL(extract_kernel, dim3((unsigned) ((n_units + 255) / 256)), dim3(256), 0, st, gcodes, gnmask, src_start,
+                       dst_off, R, n_out, codes, nmask);
+    MS_HIP(hipGetLastError());
+    return MS_OK;
+}
+
+static int launch_blk2reg(const int64_t *offsets, int64_t R, int64_t n_bases, int32_t *blk2reg, int4 *blkinfo, hipStream_t st) {
+    const int64_t n_blocks = (n_bases + 63) / 64 + 1;
+    const int all_far = measure_env("MS_BLKINFO_FAR") ? 1 : 0;          // test aid: every block record says "look the region up" (starts beyond 32 bits)
+    hipLaunchKernelGGL(blk2reg_kernel, dim3((unsigned) ((n_blocks + 255) / 256)), dim3(256), 0, st, offsets, R, n_blocks,
+                       blk2reg, blkinfo, all_far);
+    MS_HIP(hipGetLastError());
+    return MS_OK;
+}
+
+static int launch_pack(const uint8_t *ascii, int64_t n_bases, uint32_t *codes, uint32_t *nmask, hipStream_t st) {
+    const int64_t n_units = (n_bases + 31) / 32;
+    if (n_units == 0) return MS_OK;
+    const int aligned16 = (reinterpret_cast<uintptr_t>(ascii) & 15u) == 0;
+    hipLaunchKernelGGL(pack_kernel, dim3((unsigned) ((n_units + 255) / 256)), dim3(256), 0, st, ascii, n_bases,
+                       codes, nmask, n_units, aligned16);
+    MS_HIP(hipGetLastError());
+    return MS_OK;
+}
 
 // Host loops over tens of millions of regions (whole-genome window sweeps) are split over a few threads.
 template <typename F>

@@ -4,7 +4,7 @@
 // needs: "per-GPU host threads doing pack + H2D concurrently, pinned memory, and overlap (double-buffered chunks)".  A
 // stream is exactly that for one device: three host threads, one per stage, connected by bounded queues --
 //     uploader     host ASCII -> HBM (upload stream) + pack kernel              ms_seqset_create
-//     scanner      pre-filter -> fp64 -> order (-> sweep hand-out) (-> de-dup)   scan_locked, sweep_handout_locked (ms_scan.hip)
+//     scanner      pre-filter -> fp64 -> order (-> sweep hand-out) (-> de-dup)   scan_locked (ms_scan.hip), sweep_handout_locked (ms_sweep.hip)
 //     downloader   hit arrays -> pinned host memory (copy-out stream)           ms_result_hits_host / _packed_host
 // so that batch i's copy-out, batch i+1's scan and batch i+2's upload run together.  Results leave in submission order.
 // The reference has no counterpart (its Scanner holds every sequence as a Python str and makes one c_scan_motif call,

@@ -46,7 +46,7 @@ long n_plans = 0, n_geoms = 0;
 
 bool pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
 
-// what ms_kernels.hip and ms_order.hip take for granted about a scan's geometry (the comments of ms_kernels.h and ms_scan_geom.cpp)
+// what the pre-filter (ms_kernels.hip) and ms_order.hip take for granted about a scan's geometry (the comments of ms_kernels.h and ms_scan_geom.cpp)
 void check_geometry(const ms::ScanShape &sh, const ms::ScanOverrides &ov) {
     const ms::ScanGeom g = ms::scan_geometry(sh, ov);
     n_geoms++;
