@@ -66,6 +66,9 @@
  *   ms_result_rank_profile    the ranked fold-change profile of plot_motif_sites_enrich   plot.py:95-153 (the loop at :133-141)
  *                         and its smoothing, smooth() plot.py:34-40
  *   ms_result_from_hits   a result made of hit arrays that are on the host (the sites of a view that no longer owns its result)
+ *   ms_scan_variants / ms_varscan_*
+ *                         no reference counterpart: the windows of a resident genome that cover a single-base substitution, scored for
+ *                         both alleles with the scan's own lines (cscore.c:336-390) -- the motif sites a variant creates or destroys
  */
 #ifndef MOTIFSCAN_AMD_H
 #define MOTIFSCAN_AMD_H
@@ -297,6 +300,36 @@ int ms_result_dedup(ms_result *res, const ms_pwmset *pwms);
  * aggregates the reference's site tables are made of (io/__init__.py:23-33).  Host buffers [P][R]. */
 int ms_result_site_tables(const ms_result *res, int32_t *n_sites, double *max_score);
 void ms_result_free(ms_result *res);
+
+/* ---- single-base substitutions on a resident genome: motif sites gained and lost (ms_variants.hip) ---------- */
+/* Variant v = (chromosome index chrom[v], 0-based position pos[v] on it, alt byte alt[v]); duplicates and any order are allowed, an alt
+ * equal to the reference base is scored like any other.  For motif m of width W the windows that matter start at
+ * s in [max(0, x - W + 1), min(x, L_c - W)] (none when L_c < W; a window never crosses a chromosome boundary).  For each of them and each
+ * strand of strand_mask two normalised scores are computed exactly as ms_scan computes them (cscore.c:336-390: columns in order, forward
+ * M[b][c], reverse M[3 - b][W - 1 - c], a non-ACGT base adds nothing, raw / max_raw, hit iff score - cutoff >= -1e-10): score_ref on the
+ * genome as it is, score_alt with base x replaced by the alt byte converted as convert_seq converts it (AaCcGgTt, anything else "no
+ * contribution": cscore.c:81-114).  A RECORD exists for every (motif, variant, s, strand) of which at least one allele passes: variant =
+ * index in the caller's arrays, start = s, strand 1 / 2, both scores whatever their value, state bit 0 = ref passes, bit 1 = alt passes
+ * (1 lost, 2 gained, 3 kept).  Order: motif, variant index, start ascending, '+' before '-'; the same bytes on every run.  No record is
+ * ever dropped, however many there are.  The handle is device-bound (the genome's device).
+ * MS_ERR_INVALID: a chromosome index outside the genome, pos outside [0, L_c), a strand mask outside 1..3, flags != 0.  n_variants = 0 is
+ * valid and gives an empty result. */
+typedef struct ms_varscan ms_varscan;
+int  ms_scan_variants(const ms_pwmset *pwms, const ms_genome *genome, const int32_t *chrom, const int64_t *pos, const char *alt,
+                      int64_t n_variants, int strand_mask, uint32_t flags /* 0 */, ms_varscan **out);
+int  ms_varscan_num_sites(const ms_varscan *vs, int64_t *n);
+int  ms_varscan_motif_offsets(const ms_varscan *vs, int64_t *out /* [P+1] */);
+/* Copy the record arrays to host buffers of length n (any pointer may be NULL). */
+int  ms_varscan_sites(const ms_varscan *vs, int64_t *variant, int64_t *start, int8_t *strand, double *score_ref, double *score_alt,
+                      uint8_t *state);
+/* The base the genome holds at every variant: 0..3 = A C G T, -1 = non-ACGT (to check a VCF's REF column against). */
+int  ms_varscan_ref_codes(const ms_varscan *vs, int8_t *out /* [V] */);
+/* gained[m] / lost[m] = input variants (duplicates count apiece) with at least one record of motif m whose state is 2 / 1; counted on
+ * the device, like ms_result_region_counts.  Either pointer may be NULL. */
+int  ms_varscan_motif_counts(const ms_varscan *vs, int64_t *gained /* [P] */, int64_t *lost /* [P] */);
+/* Device time of the call that made the result: upload of the variants -> last kernel done (HIP events on the library's stream). */
+int  ms_varscan_device_ms(const ms_varscan *vs, double *ms);
+void ms_varscan_free(ms_varscan *vs);
 
 /* The hit arrays in COMPACT form in library-owned pinned host memory: coord[i] = seq_idx << 32 | pos << 1 | (strand - 1),
  * score[i] -- 16 bytes per hit on the host link instead of 25.  Needs seq_idx < 2^32 and pos < 2^31 (MS_ERR_INVALID

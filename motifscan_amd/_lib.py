@@ -163,6 +163,15 @@ def lib():
         "ms_debug_plan_rows": (c_int, [vp, pi32, ctypes.POINTER(ctypes.c_int16), pi32, pi32, pi32, pi32, pi32, pi32]),
         "ms_debug_release_scratch": (c_int, []),
         "ms_debug_numa_probe": (c_int, [ctypes.c_char_p, ctypes.c_char_p, pi32, pi32, pi32]),
+        "ms_scan_variants": (c_int, [vp, vp, pi32, pi64, ctypes.c_char_p, c_i64, c_int, c_u32, pvp]),
+        "ms_varscan_num_sites": (c_int, [vp, pi64]),
+        "ms_varscan_motif_offsets": (c_int, [vp, pi64]),
+        "ms_varscan_sites": (c_int, [vp, pi64, pi64, pi8, pd, pd, pu8]),
+        "ms_varscan_ref_codes": (c_int, [vp, pi8]),
+        "ms_varscan_motif_counts": (c_int, [vp, pi64, pi64]),
+        "ms_varscan_device_ms": (c_int, [vp, pd]),
+        "ms_varscan_free": (None, [vp]),
+        "ms_debug_varscan_chunk": (c_int, [c_i64, pi64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -853,6 +862,86 @@ def scan_sweep(pwms, genome, chrom, begin, end, window, stride, strand_mask=3, f
     check(lib().ms_scan_sweep(pwms.h, genome.h, ci, int(begin), int(end), int(window), int(stride), int(strand_mask),
                               int(flags), ctypes.byref(h)))
     return _fence_exact_only(ScanResult(h, pwms.n), pwms, int(flags))
+
+
+class VariantScan:
+    """Records of one ms_scan_variants call: per motif, variant index, window start, '+' before '-' (include/motifscan_amd.h)."""
+
+    def __init__(self, handle, n_pwms, n_variants):
+        self.h = handle
+        self.n_pwms = n_pwms
+        self.n_variants = n_variants
+        n = ctypes.c_int64()
+        check(lib().ms_varscan_num_sites(self.h, ctypes.byref(n)))
+        self.n_sites = n.value
+        self.motif_offsets = np.zeros(n_pwms + 1, dtype=np.int64)
+        check(lib().ms_varscan_motif_offsets(self.h, ptr(self.motif_offsets, ctypes.c_int64)))
+
+    def sites(self):
+        """dict of fresh numpy arrays: variant, start, strand (1 '+', 2 '-'), score_ref, score_alt, state (1 lost, 2 gained, 3 kept),
+        motif (motif_offsets expanded) and motif_offsets."""
+        n = self.n_sites
+        variant, start = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        strand, state = np.zeros(n, dtype=np.int8), np.zeros(n, dtype=np.uint8)
+        score_ref, score_alt = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64)
+        check(lib().ms_varscan_sites(self.h, ptr(variant, ctypes.c_int64), ptr(start, ctypes.c_int64), ptr(strand, ctypes.c_int8),
+                                     ptr(score_ref, ctypes.c_double), ptr(score_alt, ctypes.c_double), ptr(state, ctypes.c_uint8)))
+        motif = np.repeat(np.arange(self.n_pwms, dtype=np.int32), np.diff(self.motif_offsets))
+        return {"variant": variant, "start": start, "strand": strand, "score_ref": score_ref, "score_alt": score_alt, "state": state,
+                "motif": motif, "motif_offsets": self.motif_offsets}
+
+    def ref_codes(self):
+        """int8 per input variant: the genome's base there, 0..3 = A C G T, -1 = non-ACGT."""
+        out = np.zeros(self.n_variants, dtype=np.int8)
+        check(lib().ms_varscan_ref_codes(self.h, ptr(out, ctypes.c_int8)))
+        return out
+
+    def motif_counts(self):
+        """(gained, lost) int64 [P]: variants with at least one gained / lost site of the motif, counted on the device."""
+        gained, lost = np.zeros(self.n_pwms, dtype=np.int64), np.zeros(self.n_pwms, dtype=np.int64)
+        check(lib().ms_varscan_motif_counts(self.h, ptr(gained, ctypes.c_int64), ptr(lost, ctypes.c_int64)))
+        return gained, lost
+
+    def device_ms(self):
+        ms = ctypes.c_double()
+        check(lib().ms_varscan_device_ms(self.h, ctypes.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ms_varscan_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+
+def scan_variants(pwms, genome, chrom_idx, pos, alt, strand_mask=3, flags=0):
+    """ms_scan_variants: chrom_idx / pos (0-based) / alt (bytes, a str, or a uint8 / S1 array: one byte per variant) against a
+    ResidentGenome.  Returns a VariantScan."""
+    ci = np.ascontiguousarray(chrom_idx, dtype=np.int32)
+    ps = np.ascontiguousarray(pos, dtype=np.int64)
+    if isinstance(alt, str):
+        alt = alt.encode("latin-1")
+    if isinstance(alt, (bytes, bytearray)):
+        ab = np.frombuffer(bytes(alt), dtype=np.uint8)
+    else:
+        ab = np.asarray(alt)
+        ab = ab.astype("S1").view(np.uint8) if ab.dtype.kind in "SU" else ab.astype(np.uint8)
+    ab = np.ascontiguousarray(ab).reshape(-1)
+    if ci.ndim != 1 or not (ci.size == ps.size == ab.size):
+        raise ValueError("chrom_idx, pos and alt must have one entry per variant")
+    h = ctypes.c_void_p()
+    check(lib().ms_scan_variants(pwms.h, genome.h, ptr(ci, ctypes.c_int32), ptr(ps, ctypes.c_int64), ab.ctypes.data_as(ctypes.c_char_p),
+                                 ci.size, int(strand_mask), int(flags), ctypes.byref(h)))
+    return VariantScan(h, pwms.n, ci.size)
+
+
+def varscan_chunk(n_variants):
+    """ms_debug_varscan_chunk: variants per chunk of scan_variants for the calls that follow (0 = the library's own); returns the
+    value before.  Tests only."""
+    prev = ctypes.c_int64()
+    check(lib().ms_debug_varscan_chunk(int(n_variants), ctypes.byref(prev)))
+    return prev.value
 
 
 class PinnedBuffer:

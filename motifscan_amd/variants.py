@@ -1,0 +1,166 @@
+"""
+motifscan_amd.variants -- motif sites gained and lost by single-base substitutions.
+
+The reference has no counterpart: it scans regions, not alleles.  Here the genome is resident in HBM (a `_lib.ResidentGenome`), and
+for every variant only the windows that cover it are scored, for both alleles, with the scan's own fp64 arithmetic and hit test
+(cscore.c:336-390; ms_variants.hip).  `read_vcf` reads the variants, `scan_variants` runs them, `VariantSites` holds the flat result
+arrays -- they are the interface; no writer is part of this module.
+"""
+import gzip
+from collections import namedtuple
+
+import numpy as np
+
+from . import _lib
+
+_STRAND_FLAG = {"both": 3, "+": 1, "-": 2}
+_BASES = "ACGT"
+
+VcfVariants = namedtuple("VcfVariants", ["chrom", "pos", "ref", "alt", "id", "skipped"])
+
+
+def read_vcf(path):
+    """The single-base substitutions of a VCF (plain text or .gz): tab-separated CHROM, POS (1-based in the file, 0-based here), ID, REF,
+    ALT; '#' lines are skipped, a comma-separated ALT gives one variant per allele.  Only single-letter REF and ALT become variants; the
+    rest is skipped and counted per reason in `.skipped`: 'indel' (alleles of different lengths), 'multi_base' (equal lengths > 1),
+    'symbolic' (<...>), 'star' (*), 'missing' (.).  Returns VcfVariants(chrom names, pos int64, ref, alt, id, skipped)."""
+    chrom, pos, ref, alt, ids = [], [], [], [], []
+    skipped = {"indel": 0, "multi_base": 0, "symbolic": 0, "star": 0, "missing": 0}
+    opener = gzip.open if str(path).endswith(".gz") else open
+    with opener(path, "rt") as fh:
+        for line in fh:
+            if not line.strip() or line.startswith("#"):
+                continue
+            f = line.rstrip("\r\n").split("\t")
+            if len(f) < 5:
+                raise ValueError(f"VCF line with fewer than 5 tab-separated columns: {line!r}")
+            r = f[3]
+            for a in f[4].split(","):
+                if a == "." or r == ".":
+                    skipped["missing"] += 1
+                elif a == "*":
+                    skipped["star"] += 1
+                elif a.startswith("<") or "[" in a or "]" in a:
+                    skipped["symbolic"] += 1
+                elif len(r) != len(a):
+                    skipped["indel"] += 1
+                elif len(r) > 1:
+                    skipped["multi_base"] += 1
+                else:
+                    chrom.append(f[0])
+                    pos.append(int(f[1]) - 1)
+                    ref.append(r)
+                    alt.append(a)
+                    ids.append(f[2])
+    return VcfVariants(np.array(chrom, dtype=object), np.array(pos, dtype=np.int64), np.array(ref, dtype="U1"), np.array(alt, dtype="U1"),
+                       np.array(ids, dtype=object), skipped)
+
+
+class VariantSites:
+    """Flat records of a variant scan in the library's order (motif, variant index, start, '+' before '-'): motif, variant (index into
+    the caller's arrays), start (0-based on the chromosome), strand (1 '+', 2 '-'), score_ref, score_alt, state (bit 0 ref passes,
+    bit 1 alt passes), motif_offsets [P + 1]; `skipped` = indices of the variants dropped for a REF mismatch (on_mismatch='skip')."""
+
+    def __init__(self, motif, variant, start, strand, score_ref, score_alt, state, motif_offsets, ref_codes=None, counts=None, skipped=None):
+        self.motif = np.asarray(motif)
+        self.variant = np.asarray(variant)
+        self.start = np.asarray(start)
+        self.strand = np.asarray(strand)
+        self.score_ref = np.asarray(score_ref, dtype=np.float64)
+        self.score_alt = np.asarray(score_alt, dtype=np.float64)
+        self.state = np.asarray(state, dtype=np.uint8)
+        self.motif_offsets = np.asarray(motif_offsets, dtype=np.int64)
+        self.ref_codes = ref_codes
+        self._counts = counts
+        self.skipped = np.zeros(0, dtype=np.int64) if skipped is None else np.asarray(skipped, dtype=np.int64)
+
+    def __len__(self):
+        return len(self.state)
+
+    @property
+    def gained(self):
+        return self.state == 2
+
+    @property
+    def lost(self):
+        return self.state == 1
+
+    @property
+    def kept(self):
+        return self.state == 3
+
+    @property
+    def delta(self):
+        return self.score_alt - self.score_ref
+
+    def motif_counts(self):
+        """(gained, lost) int64 [P]: per motif the variants with at least one gained / lost site, as the device counted them (variants
+        dropped by on_mismatch='skip' taken out again)."""
+        if self._counts is None:
+            raise ValueError("these sites do not come from a device scan")
+        return self._counts
+
+
+def _marshal(pwms, p_value):
+    """Scanner._marshal: matrices and the cutoffs of `p_value`, the same ValueError for a PWM without that cutoff."""
+    pwms = list(pwms)
+    cutoffs = []
+    for pwm in pwms:
+        try:
+            cutoffs.append(pwm.cutoffs[p_value])
+        except (TypeError, KeyError):
+            raise ValueError(f"PWM has no motif score cutoff set for P-value {p_value!r}")
+    return [np.asarray(pwm.matrix, dtype=np.float64) for pwm in pwms], np.asarray(cutoffs, dtype=np.float64)
+
+
+def scan_variants(genome, pwms, chrom, pos, alt, ref=None, strand="both", p_value="1e-4", on_mismatch="raise"):
+    """Score the windows that cover each variant for both alleles (ms_scan_variants) and return the VariantSites.
+
+    genome: a _lib.ResidentGenome; pwms: objects with .matrix (4 x W) and .cutoffs[p_value]; chrom: chromosome names (KeyError for one the
+    genome does not have); pos: 0-based; alt (and ref): one letter per variant.  With `ref`, the genome's base at every variant is
+    compared with it, case-insensitively (a non-ACGT genome base matches any letter that is not A, C, G or T): on_mismatch='raise' raises
+    ValueError naming the first few, 'skip' drops those variants' records and lists them in `.skipped`."""
+    if on_mismatch not in ("raise", "skip"):
+        raise ValueError("on_mismatch must be 'raise' or 'skip'")
+    if strand not in _STRAND_FLAG:
+        raise ValueError("strand must be one of 'both', '+', '-'")
+    matrices, cutoffs = _marshal(pwms, p_value)
+    chrom_idx = np.array([genome.index[c] for c in chrom], dtype=np.int32)
+    pos = np.ascontiguousarray(pos, dtype=np.int64)
+    alt = np.asarray(alt, dtype="U1") if not isinstance(alt, (bytes, str)) else alt
+    pw = _lib.PwmSet.from_matrices(matrices, cutoffs)
+    try:
+        res = _lib.scan_variants(pw, genome, chrom_idx, pos, alt, _STRAND_FLAG[strand])
+    finally:
+        pw.close()
+    try:
+        ref_codes = res.ref_codes()
+        bad = np.zeros(0, dtype=np.int64)
+        if ref is not None:
+            letters = np.char.upper(np.asarray(ref, dtype="U1"))
+            if letters.shape != ref_codes.shape:
+                raise ValueError("ref must have one letter per variant")
+            want = np.full(letters.shape, -1, dtype=np.int8)
+            for code, base in enumerate(_BASES):
+                want[letters == base] = code
+            bad = np.flatnonzero(want != ref_codes)
+            if bad.size and on_mismatch == "raise":
+                shown = ", ".join(f"{chrom[i]}:{int(pos[i]) + 1} REF {letters[i]} but the genome has {_BASES[ref_codes[i]] if ref_codes[i] >= 0 else 'N'}"
+                                  for i in bad[:5].tolist())
+                raise ValueError(f"{bad.size} variant(s) whose REF is not the genome's base: {shown}" + (" ..." if bad.size > 5 else ""))
+        s = res.sites()
+        gained, lost = res.motif_counts()
+    finally:
+        res.close()
+    if bad.size:
+        drop = np.isin(s["variant"], bad)
+        for name, col in (("gained", gained), ("lost", lost)):            # the dropped variants leave the counts too
+            sel = drop & (s["state"] == (2 if name == "gained" else 1))
+            pairs = np.unique(np.stack([s["motif"][sel].astype(np.int64), s["variant"][sel]]), axis=1)
+            np.subtract.at(col, pairs[0], 1)
+        keep = ~drop
+        offsets = np.zeros(len(matrices) + 1, dtype=np.int64)
+        np.cumsum(np.bincount(s["motif"][keep], minlength=len(matrices)), out=offsets[1:])
+        s = {k: (v[keep] if k != "motif_offsets" else offsets) for k, v in s.items()}
+    return VariantSites(s["motif"], s["variant"], s["start"], s["strand"], s["score_ref"], s["score_alt"], s["state"], s["motif_offsets"],
+                        ref_codes=ref_codes, counts=(gained, lost), skipped=bad)
