@@ -69,6 +69,9 @@
  *   ms_scan_variants / ms_varscan_*
  *                         no reference counterpart: the windows of a resident genome that cover a single-base substitution, scored for
  *                         both alleles with the scan's own lines (cscore.c:336-390) -- the motif sites a variant creates or destroys
+ *   ms_scan_alleles / ms_allelescan_*
+ *                         the same for alleles of any length (multi-base, insertions, deletions): the windows of the ref and of the
+ *                         spliced alt haplotype that the allele touches, each scored on its own haplotype
  */
 #ifndef MOTIFSCAN_AMD_H
 #define MOTIFSCAN_AMD_H
@@ -330,6 +333,45 @@ int  ms_varscan_motif_counts(const ms_varscan *vs, int64_t *gained /* [P] */, in
 /* Device time of the call that made the result: upload of the variants -> last kernel done (HIP events on the library's stream). */
 int  ms_varscan_device_ms(const ms_varscan *vs, double *ms);
 void ms_varscan_free(ms_varscan *vs);
+
+/* ---- alleles of any length on a resident genome: substitutions, multi-base alleles, insertions, deletions (ms_alleles.hip) ---------- */
+/* Variant v = (chromosome index chrom[v], 0-based x = pos[v], r = ref_len[v], alt = alt_bases[alt_offsets[v] .. alt_offsets[v + 1]) of
+ * a bytes): the r >= 0 reference bases [x, x + r) of the chromosome (length L) are replaced by the a >= 0 alt bytes.  The REF haplotype is
+ * the chromosome as it is; the ALT haplotype is chrom[0:x] + alt + chrom[x + r:], of length L' = L - r + a.  Alt bytes are converted as
+ * convert_seq converts them (AaCcGgTt, anything else "no contribution": cscore.c:81-114), as in ms_scan_variants.
+ * Affected windows of a motif of width W: on the ref haplotype the starts s in [max(0, x - W + 1), min(x + r - 1, L - W)]; on the alt
+ * haplotype, in ALT-HAPLOTYPE coordinates, the starts t in [max(0, x - W + 1), min(x + a - 1, L' - W)].  ONE formula covers an empty
+ * allele: with r = 0 (a = 0) the range is exactly the windows that straddle the junction between x - 1 and x, and it is empty for W = 1.
+ * A haplotype shorter than W has no windows.  Every affected window is scored as ms_scan scores it (cscore.c:336-390: columns in order,
+ * forward M[b][c], reverse M[3 - b][W - 1 - c] at the same step, +0.0 for a base that adds nothing, raw / max_raw, hit iff
+ * score - cutoff >= -1e-10).  A RECORD (variant, allele, start, strand, score) exists for every affected window and strand of strand_mask
+ * that passes: variant = index in the caller's arrays, allele 0 = ref / 1 = alt, start in THAT haplotype's coordinates (for allele 1 and
+ * start >= x + a the reference coordinate is start - a + r), strand 1 / 2.  Order: motif, variant index, allele (ref first), start
+ * ascending, '+' before '-'; the same bytes on every run; no record is ever dropped; duplicates and any input order are allowed.
+ * gained[m] / lost[m] (counted on the device in the count pass) = input variants with at least one alt record and no ref record /
+ * at least one ref record and no alt record of motif m.  This classifies VARIANTS, not positions: windows of two haplotypes of different
+ * lengths have no canonical pairing, so -- unlike ms_varscan_motif_counts, which counts variants with a gained / lost WINDOW -- a variant
+ * that destroys one site of a motif and creates another of the same motif counts as neither here.
+ * With ref_bases (the REF strings concatenated, sum of ref_len bytes) every REF is compared with the genome at [x, x + r), ignoring case;
+ * a non-ACGT genome base matches any letter that is not A, C, G or T.  ms_allelescan_ref_mismatch gives 1 per variant that differs, and
+ * 0 for every variant when ref_bases was NULL.
+ * MS_ERR_INVALID: a chromosome index outside the genome; x outside [0, L], r < 0 or x + r > L; r + a = 0; alt_offsets that do not start at
+ * 0 or decrease; an allele (r or a) longer than MS_ALLELE_MAX_LEN; a strand mask outside 1..3; flags != 0; NULL handles.  n_variants = 0
+ * is valid and gives an empty result.  Without a device: MS_ERR_RUNTIME ("no CPU fallback") before anything else. */
+#define MS_ALLELE_MAX_LEN 65536
+typedef struct ms_allelescan ms_allelescan;
+int  ms_scan_alleles(const ms_pwmset *pwms, const ms_genome *genome, const int32_t *chrom, const int64_t *pos, const int32_t *ref_len,
+                     const char *alt_bases, const int64_t *alt_offsets /* [V+1] */, const char *ref_bases /* or NULL */,
+                     int64_t n_variants, int strand_mask, uint32_t flags /* 0 */, ms_allelescan **out);
+int  ms_allelescan_num_sites(const ms_allelescan *as, int64_t *n);
+int  ms_allelescan_motif_offsets(const ms_allelescan *as, int64_t *out /* [P+1] */);
+/* Copy the record arrays to host buffers of length n (any pointer may be NULL). */
+int  ms_allelescan_sites(const ms_allelescan *as, int64_t *variant, uint8_t *allele, int64_t *start, int8_t *strand, double *score);
+int  ms_allelescan_motif_counts(const ms_allelescan *as, int64_t *gained /* [P] */, int64_t *lost /* [P] */);
+int  ms_allelescan_ref_mismatch(const ms_allelescan *as, uint8_t *out /* [V] */);
+/* Device time of the call that made the result: upload of the variants -> last kernel done. */
+int  ms_allelescan_device_ms(const ms_allelescan *as, double *ms);
+void ms_allelescan_free(ms_allelescan *as);
 
 /* The hit arrays in COMPACT form in library-owned pinned host memory: coord[i] = seq_idx << 32 | pos << 1 | (strand - 1),
  * score[i] -- 16 bytes per hit on the host link instead of 25.  Needs seq_idx < 2^32 and pos < 2^31 (MS_ERR_INVALID

@@ -42,7 +42,7 @@ int ms_debug_numa_probe(const char *root, const char *bdf, int32_t *node, int32_
  * test can force the "buffer too small -> grow -> run the pass again" path.  Needs a GPU. */
 int ms_debug_release_scratch(void);
 
-/* ms_scan_variants takes its variants in chunks (the per-(motif, tile) record counts of one chunk are bounded); n_variants > 0 sets the
+/* ms_scan_variants (and ms_scan_alleles: the same knob) takes its variants in chunks (the per-(motif, tile) record counts of one chunk are bounded); n_variants > 0 sets the
  * chunk size for the calls that follow in this process, 0 gives it back to the library.  *previous (may be NULL) = the value before.
  * The result of a scan does not depend on it: a test proves that with a chunk of a few variants.  Needs no GPU. */
 int ms_debug_varscan_chunk(int64_t n_variants, int64_t *previous);

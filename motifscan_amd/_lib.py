@@ -172,6 +172,14 @@ def lib():
         "ms_varscan_device_ms": (c_int, [vp, pd]),
         "ms_varscan_free": (None, [vp]),
         "ms_debug_varscan_chunk": (c_int, [c_i64, pi64]),
+        "ms_scan_alleles": (c_int, [vp, vp, pi32, pi64, pi32, ctypes.c_char_p, pi64, ctypes.c_char_p, c_i64, c_int, c_u32, pvp]),
+        "ms_allelescan_num_sites": (c_int, [vp, pi64]),
+        "ms_allelescan_motif_offsets": (c_int, [vp, pi64]),
+        "ms_allelescan_sites": (c_int, [vp, pi64, pu8, pi64, pi8, pd]),
+        "ms_allelescan_motif_counts": (c_int, [vp, pi64, pi64]),
+        "ms_allelescan_ref_mismatch": (c_int, [vp, pu8]),
+        "ms_allelescan_device_ms": (c_int, [vp, pd]),
+        "ms_allelescan_free": (None, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -937,11 +945,93 @@ def scan_variants(pwms, genome, chrom_idx, pos, alt, strand_mask=3, flags=0):
 
 
 def varscan_chunk(n_variants):
-    """ms_debug_varscan_chunk: variants per chunk of scan_variants for the calls that follow (0 = the library's own); returns the
+    """ms_debug_varscan_chunk: variants per chunk of scan_variants and scan_alleles for the calls that follow (0 = the library's own); returns the
     value before.  Tests only."""
     prev = ctypes.c_int64()
     check(lib().ms_debug_varscan_chunk(int(n_variants), ctypes.byref(prev)))
     return prev.value
+
+
+class AlleleScan:
+    """Records of one ms_scan_alleles call: per motif, variant index, allele (ref first), start, '+' before '-' (include/motifscan_amd.h)."""
+
+    def __init__(self, handle, n_pwms, n_variants):
+        self.h = handle
+        self.n_pwms = n_pwms
+        self.n_variants = n_variants
+        n = ctypes.c_int64()
+        check(lib().ms_allelescan_num_sites(self.h, ctypes.byref(n)))
+        self.n_sites = n.value
+        self.motif_offsets = np.zeros(n_pwms + 1, dtype=np.int64)
+        check(lib().ms_allelescan_motif_offsets(self.h, ptr(self.motif_offsets, ctypes.c_int64)))
+
+    def sites(self):
+        """dict of fresh numpy arrays: variant, allele (0 ref, 1 alt), start (in that haplotype's coordinates), strand (1 '+', 2 '-'),
+        score, motif (motif_offsets expanded) and motif_offsets."""
+        n = self.n_sites
+        variant, start = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        strand, allele = np.zeros(n, dtype=np.int8), np.zeros(n, dtype=np.uint8)
+        score_ = np.zeros(n, dtype=np.float64)
+        check(lib().ms_allelescan_sites(self.h, ptr(variant, ctypes.c_int64), ptr(allele, ctypes.c_uint8), ptr(start, ctypes.c_int64),
+                                        ptr(strand, ctypes.c_int8), ptr(score_, ctypes.c_double)))
+        motif = np.repeat(np.arange(self.n_pwms, dtype=np.int32), np.diff(self.motif_offsets))
+        return {"variant": variant, "allele": allele, "start": start, "strand": strand, "score": score_, "motif": motif,
+                "motif_offsets": self.motif_offsets}
+
+    def motif_counts(self):
+        """(gained, lost) int64 [P]: variants with records of the motif on the alt haplotype only / on the ref haplotype only."""
+        gained, lost = np.zeros(self.n_pwms, dtype=np.int64), np.zeros(self.n_pwms, dtype=np.int64)
+        check(lib().ms_allelescan_motif_counts(self.h, ptr(gained, ctypes.c_int64), ptr(lost, ctypes.c_int64)))
+        return gained, lost
+
+    def ref_mismatch(self):
+        """bool per input variant: its REF string is not what the genome holds (all False when no REF strings were given)."""
+        out = np.zeros(self.n_variants, dtype=np.uint8)
+        check(lib().ms_allelescan_ref_mismatch(self.h, ptr(out, ctypes.c_uint8)))
+        return out.astype(bool)
+
+    def device_ms(self):
+        ms = ctypes.c_double()
+        check(lib().ms_allelescan_device_ms(self.h, ctypes.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ms_allelescan_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+
+def _flatten_alleles(seqs):
+    """Sequences of str / bytes -> (their bytes concatenated as a uint8 array, int64 offsets [n + 1])."""
+    parts = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in seqs]
+    offsets = np.zeros(len(parts) + 1, dtype=np.int64)
+    if parts:
+        np.cumsum([len(p) for p in parts], out=offsets[1:])
+    return np.frombuffer(b"".join(parts), dtype=np.uint8), offsets
+
+
+def scan_alleles(pwms, genome, chrom_idx, pos, ref_len, alts, refs=None, strand_mask=3, flags=0):
+    """ms_scan_alleles: chrom_idx / pos (0-based) / ref_len (reference bases replaced) / alts (a str or bytes per variant, '' for a
+    deletion) against a ResidentGenome; refs (a str or bytes per variant, of ref_len bytes) has the library compare them with the genome.
+    Returns an AlleleScan."""
+    ci = np.ascontiguousarray(chrom_idx, dtype=np.int32)
+    ps = np.ascontiguousarray(pos, dtype=np.int64)
+    rl = np.ascontiguousarray(ref_len, dtype=np.int32)
+    ab, ao = _flatten_alleles(alts)
+    if ci.ndim != 1 or not (ci.size == ps.size == rl.size == ao.size - 1):
+        raise ValueError("chrom_idx, pos, ref_len and alts must have one entry per variant")
+    rb = None
+    if refs is not None:
+        rb, ro = _flatten_alleles(refs)
+        if ro.size - 1 != ci.size or not np.array_equal(np.diff(ro), rl):
+            raise ValueError("refs must hold one string of ref_len bytes per variant")
+    h = ctypes.c_void_p()
+    check(lib().ms_scan_alleles(pwms.h, genome.h, ptr(ci, ctypes.c_int32), ptr(ps, ctypes.c_int64), ptr(rl, ctypes.c_int32),
+                                ab.ctypes.data_as(ctypes.c_char_p), ptr(ao, ctypes.c_int64),
+                                None if rb is None else rb.ctypes.data_as(ctypes.c_char_p), ci.size, int(strand_mask), int(flags), ctypes.byref(h)))
+    return AlleleScan(h, pwms.n, ci.size)
 
 
 class PinnedBuffer:

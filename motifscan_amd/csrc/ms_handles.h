@@ -316,5 +316,7 @@ MS_HIDDEN DevPwm dev_pwm(const ms_pwmset *p);
 MS_HIDDEN DevSeq dev_seq(const ms_seqset *s);
 // sum_r max(L_r - W + 1, 0) from the set's sorted lengths (ms_seqset.hip)
 MS_HIDDEN int64_t windows_for_width(const ms_seqset *s, int W);
+// what ms_debug_varscan_chunk set: variants per chunk of the variant scans, 0 = their own size (ms_variants.hip; read by ms_alleles.hip)
+MS_HIDDEN int64_t varscan_chunk_setting();
 
 }  // namespace ms

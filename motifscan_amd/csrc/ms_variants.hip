@@ -281,6 +281,8 @@ size_t up256(size_t x) { return (x + 255) & ~(size_t) 255; }
 
 }  // namespace
 
+int64_t varscan_chunk_setting() { return g_var_chunk.load(); }
+
 }  // namespace ms
 
 using namespace ms;

@@ -1,10 +1,14 @@
 """
-motifscan_amd.variants -- motif sites gained and lost by single-base substitutions.
+motifscan_amd.variants -- motif sites gained and lost by single-base substitutions, and by alleles of any length.
 
 The reference has no counterpart: it scans regions, not alleles.  Here the genome is resident in HBM (a `_lib.ResidentGenome`), and
 for every variant only the windows that cover it are scored, for both alleles, with the scan's own fp64 arithmetic and hit test
 (cscore.c:336-390; ms_variants.hip).  `read_vcf` reads the variants, `scan_variants` runs them, `VariantSites` holds the flat result
 arrays -- they are the interface; no writer is part of this module.
+
+Alleles whose REF and ALT differ in length, or are longer than one base, take the second route: `read_vcf_alleles`, `scan_alleles` and
+`AlleleSites` (ms_alleles.hip).  There the two haplotypes are scanned apiece -- the chromosome as it is, and the chromosome with the
+allele spliced in -- and a record belongs to ONE haplotype, with a start in that haplotype's coordinates.
 """
 import gzip
 from collections import namedtuple
@@ -164,3 +168,172 @@ def scan_variants(genome, pwms, chrom, pos, alt, ref=None, strand="both", p_valu
         s = {k: (v[keep] if k != "motif_offsets" else offsets) for k, v in s.items()}
     return VariantSites(s["motif"], s["variant"], s["start"], s["strand"], s["score_ref"], s["score_alt"], s["state"], s["motif_offsets"],
                         ref_codes=ref_codes, counts=(gained, lost), skipped=bad)
+
+
+# ---------------------------------------------------------------------------------------------- alleles of any length
+
+VcfAlleles = namedtuple("VcfAlleles", ["chrom", "pos", "ref", "alt", "id", "skipped"])
+
+
+def trim_allele(pos, ref, alt):
+    """The shared suffix, then the shared prefix, of REF and ALT removed (compared without case) and pos moved past the prefix: VCF's
+    anchored AT -> A at p becomes T -> '' at p + 1.  Identical alleles are left as they are; nothing is left-aligned."""
+    if ref.upper() == alt.upper():
+        return pos, ref, alt
+    ru, au = ref.upper(), alt.upper()
+    n = min(len(ref), len(alt))
+    k = 0
+    while k < n and ru[len(ru) - 1 - k] == au[len(au) - 1 - k]:
+        k += 1
+    if k:
+        ref, alt, ru, au = ref[:-k], alt[:-k], ru[:-k], au[:-k]
+    n = min(len(ref), len(alt))
+    k = 0
+    while k < n and ru[k] == au[k]:
+        k += 1
+    return pos + k, ref[k:], alt[k:]
+
+
+def read_vcf_alleles(path, max_len=1000, trim=True):
+    """Every sequence-resolved allele of a VCF (plain text or .gz) -- substitutions, multi-base alleles, insertions, deletions -- read as
+    `read_vcf` reads it: POS 0-based here, a comma-separated ALT gives one variant per allele.  trim=True applies `trim_allele`, so an
+    insertion has ref '' and a deletion alt ''.  Skipped and counted per reason in `.skipped`: 'symbolic' (<...>, breakends), 'star' (*),
+    'missing' (.), 'too_long' (REF or ALT of more than max_len bases, after trimming).
+    Returns VcfAlleles(chrom names, pos int64, ref, alt, id, skipped); ref and alt are object arrays of str."""
+    chrom, pos, ref, alt, ids = [], [], [], [], []
+    skipped = {"symbolic": 0, "star": 0, "missing": 0, "too_long": 0}
+    opener = gzip.open if str(path).endswith(".gz") else open
+    with opener(path, "rt") as fh:
+        for line in fh:
+            if not line.strip() or line.startswith("#"):
+                continue
+            f = line.rstrip("\r\n").split("\t")
+            if len(f) < 5:
+                raise ValueError(f"VCF line with fewer than 5 tab-separated columns: {line!r}")
+            r = f[3]
+            for a in f[4].split(","):
+                if a == "." or r == ".":
+                    skipped["missing"] += 1
+                elif a == "*":
+                    skipped["star"] += 1
+                elif a.startswith("<") or "[" in a or "]" in a:
+                    skipped["symbolic"] += 1
+                else:
+                    x, rr, aa = trim_allele(int(f[1]) - 1, r, a) if trim else (int(f[1]) - 1, r, a)
+                    if len(rr) > max_len or len(aa) > max_len:
+                        skipped["too_long"] += 1
+                        continue
+                    chrom.append(f[0])
+                    pos.append(x)
+                    ref.append(rr)
+                    alt.append(aa)
+                    ids.append(f[2])
+    obj = lambda items: np.array(items + [None], dtype=object)[:-1]         # (an object array whatever the strings' lengths)
+    return VcfAlleles(obj(chrom), np.array(pos, dtype=np.int64), obj(ref), obj(alt), obj(ids), skipped)
+
+
+class AlleleSites:
+    """Flat records of an allele scan in the library's order (motif, variant index, allele, start, '+' before '-'): motif, variant (index
+    into the caller's arrays), allele (0 ref haplotype, 1 alt haplotype), start (0-based, in THAT haplotype's coordinates), strand
+    (1 '+', 2 '-'), score, motif_offsets [P + 1]; pos / ref_len / alt_len are the caller's variants (what `ref_start` needs); `skipped` =
+    indices of the variants dropped for a REF mismatch (on_mismatch='skip')."""
+
+    def __init__(self, motif, variant, allele, start, strand, score, motif_offsets, pos=None, ref_len=None, alt_len=None, counts=None, skipped=None):
+        self.motif = np.asarray(motif)
+        self.variant = np.asarray(variant, dtype=np.int64)
+        self.allele = np.asarray(allele, dtype=np.uint8)
+        self.start = np.asarray(start, dtype=np.int64)
+        self.strand = np.asarray(strand)
+        self.score = np.asarray(score, dtype=np.float64)
+        self.motif_offsets = np.asarray(motif_offsets, dtype=np.int64)
+        self.pos = None if pos is None else np.asarray(pos, dtype=np.int64)
+        self.ref_len = None if ref_len is None else np.asarray(ref_len, dtype=np.int64)
+        self.alt_len = None if alt_len is None else np.asarray(alt_len, dtype=np.int64)
+        self._counts = counts
+        self.skipped = np.zeros(0, dtype=np.int64) if skipped is None else np.asarray(skipped, dtype=np.int64)
+
+    def __len__(self):
+        return len(self.score)
+
+    def ref_start(self):
+        """The records' starts in reference coordinates: a ref-haplotype start, and an alt-haplotype start in front of the allele, is one
+        already; an alt-haplotype start at or behind the allele's end x + a maps to start - a + r; one INSIDE the alt bases has no
+        reference base of its own and maps to the allele's, x + min(start - x, r)."""
+        if self.pos is None or self.ref_len is None or self.alt_len is None:
+            raise ValueError("these sites carry no variants (pos, ref_len, alt_len)")
+        x, r, a = self.pos[self.variant], self.ref_len[self.variant], self.alt_len[self.variant]
+        behind = self.start - a + r
+        inside = x + np.minimum(self.start - x, r)
+        out = np.where(self.start >= x + a, behind, np.where(self.start > x, inside, self.start))
+        return np.where(self.allele == 1, out, self.start)
+
+    def per_variant(self):
+        """One row per (motif, variant) that has records, in record order: dict of motif, variant, n_ref, n_alt (records on either
+        haplotype, both strands), best_ref, best_alt (their highest score, NaN where there is none)."""
+        n = len(self)
+        if n == 0:
+            z = np.zeros(0, dtype=np.int64)
+            return {"motif": z.astype(np.int32), "variant": z, "n_ref": z, "n_alt": z, "best_ref": np.zeros(0), "best_alt": np.zeros(0)}
+        motif = self.motif.astype(np.int64)
+        first = np.flatnonzero(np.concatenate([[True], (motif[1:] != motif[:-1]) | (self.variant[1:] != self.variant[:-1])]))
+        is_alt = self.allele == 1
+        n_all = np.diff(np.concatenate([first, [n]]))
+        n_alt = np.add.reduceat(is_alt.astype(np.int64), first)
+        best = []
+        for sel in (~is_alt, is_alt):
+            b = np.maximum.reduceat(np.where(sel, self.score, -np.inf), first)
+            best.append(np.where(np.isneginf(b), np.nan, b))
+        return {"motif": self.motif[first], "variant": self.variant[first], "n_ref": n_all - n_alt, "n_alt": n_alt, "best_ref": best[0], "best_alt": best[1]}
+
+    def motif_counts(self):
+        """(gained, lost) int64 [P]: per motif the variants with records on the alt haplotype only / the ref haplotype only, as the
+        device counted them (variants dropped by on_mismatch='skip' taken out again)."""
+        if self._counts is None:
+            raise ValueError("these sites do not come from a device scan")
+        return self._counts
+
+
+def scan_alleles(genome, pwms, chrom, pos, ref, alt, strand="both", p_value="1e-4", on_mismatch="raise"):
+    """Score the windows each allele touches on the ref and on the alt haplotype (ms_scan_alleles) and return the AlleleSites.
+
+    genome: a _lib.ResidentGenome; pwms: objects with .matrix (4 x W) and .cutoffs[p_value]; chrom: chromosome names (KeyError for one the
+    genome does not have); pos: 0-based; ref / alt: one string per variant, '' for an insertion's ref / a deletion's alt (what
+    `read_vcf_alleles` returns).  Every ref is compared with the genome, case-insensitively (a non-ACGT genome base matches any letter that
+    is not A, C, G or T): on_mismatch='raise' raises ValueError naming the first few, 'skip' drops those variants' records and lists them
+    in `.skipped`."""
+    if on_mismatch not in ("raise", "skip"):
+        raise ValueError("on_mismatch must be 'raise' or 'skip'")
+    if strand not in _STRAND_FLAG:
+        raise ValueError("strand must be one of 'both', '+', '-'")
+    matrices, cutoffs = _marshal(pwms, p_value)
+    ref, alt = [str(r) for r in ref], [str(a) for a in alt]
+    chrom_idx = np.array([genome.index[c] for c in chrom], dtype=np.int32)
+    pos = np.ascontiguousarray(pos, dtype=np.int64)
+    ref_len = np.array([len(r) for r in ref], dtype=np.int32)
+    alt_len = np.array([len(a) for a in alt], dtype=np.int64)
+    pw = _lib.PwmSet.from_matrices(matrices, cutoffs)
+    try:
+        res = _lib.scan_alleles(pw, genome, chrom_idx, pos, ref_len, alt, refs=ref, strand_mask=_STRAND_FLAG[strand])
+    finally:
+        pw.close()
+    try:
+        bad = np.flatnonzero(res.ref_mismatch())
+        if bad.size and on_mismatch == "raise":
+            shown = ", ".join(f"{chrom[i]}:{int(pos[i]) + 1} REF {ref[i]}" for i in bad[:5].tolist())
+            raise ValueError(f"{bad.size} variant(s) whose REF is not the genome's sequence: {shown}" + (" ..." if bad.size > 5 else ""))
+        s = res.sites()
+        gained, lost = res.motif_counts()
+    finally:
+        res.close()
+    if bad.size:
+        drop = np.isin(s["variant"], bad)
+        gone = AlleleSites(s["motif"][drop], s["variant"][drop], s["allele"][drop], s["start"][drop], s["strand"][drop], s["score"][drop],
+                           s["motif_offsets"]).per_variant()                 # the dropped variants leave the counts too
+        np.subtract.at(gained, gone["motif"][gone["n_ref"] == 0], 1)
+        np.subtract.at(lost, gone["motif"][gone["n_alt"] == 0], 1)
+        keep = ~drop
+        offsets = np.zeros(len(matrices) + 1, dtype=np.int64)
+        np.cumsum(np.bincount(s["motif"][keep], minlength=len(matrices)), out=offsets[1:])
+        s = {k: (v[keep] if k != "motif_offsets" else offsets) for k, v in s.items()}
+    return AlleleSites(s["motif"], s["variant"], s["allele"], s["start"], s["strand"], s["score"], s["motif_offsets"], pos=pos, ref_len=ref_len,
+                       alt_len=alt_len, counts=(gained, lost), skipped=bad)
