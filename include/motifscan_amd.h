@@ -125,6 +125,8 @@ typedef struct ms_scan_stats {
     int64_t mfma_ops_algorithmic; /* 2 x windows x strands x W: the adds the reference performs */
     int32_t pf_engine;          /* 3: the fp6 x fp4 one-hot product on the matrix cores, candidates parked and decoded later; 4: the same with the flags decoded in place (chosen when the previous scan of the PWM set found many hits per row tile: p >= ~5e-4) */
     int32_t order_overflow_runs; /* runs of hits too long for the ordering's LDS sort, ordered by its global-memory form instead (0 on i.i.d. sequence) */
+    int32_t order_bucketed;     /* 1: the fp64 stage wrote the hits in buckets of the lowest sorted radix digit and the hit sort ran one pass fewer (long hit lists of a PWM set's second and later scans); 0: the plain list */
+    int32_t reserved0;          /* always 0 */
 } ms_scan_stats;
 
 const char *ms_last_error(void);

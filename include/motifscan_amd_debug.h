@@ -38,6 +38,20 @@ int ms_debug_host_pack(const char *bases, const int64_t *offsets, int64_t n_seqs
  * PCI device `bdf` (-1 unknown), the number of CPUs of that node (0 unknown), the number of online nodes. */
 int ms_debug_numa_probe(const char *root, const char *bdf, int32_t *node, int32_t *n_cpus, int32_t *n_nodes);
 
+/* The host arithmetic behind a scan's bucketed hit list (the fp64 stage writes the hits of a long, predicted-size list in 256 buckets of the
+ * radix digit at key bit low_bits, and the hit sort runs one pass fewer); no device.
+ *   weights [256]: offsets != NULL -- computed from the set (offsets [n_seqs + 1], widths [n_pwms]) for the key layout (gbits coordinate bits,
+ *       pbits of them the position in a region) and returned: the (motif, window start) pairs whose key falls into each bucket;
+ *       offsets == NULL -- taken as given (n_pwms and n_regions then say how many motifs and regions the set has: the gate looks at the largest key).
+ *   mu: expected hits; n_pred: slots of the list; cap_max: no bucket larger than this (UINT64_MAX: no limit).
+ *   form: bit 0 predicted-size scan, bit 1 counts-only form, bit 2 the fp64 stage is rescore_carry_kernel alone, bit 3 the PWM set's sticky
+ *       "a bucket overflowed once" flag; force: -1 the product's gate, 0 / 1 as MS_ORDER_BUCKETS; end_bit: key bits in all.
+ *   *need: the sum over the buckets of (expected count + 6 sigma of a Poisson count + 1, rounded up); *gate: 1 if such a scan is bucketed;
+ *   base, cap [256]: the buckets' places in the list (sum of cap <= n_pred). */
+int ms_debug_bucket_plan(const int64_t *offsets, int64_t n_seqs, const int32_t *widths, int32_t n_pwms, int32_t gbits, int32_t pbits, int32_t end_bit,
+                         int32_t low_bits, int64_t n_regions, uint64_t *weights, double mu, uint64_t n_pred, uint64_t cap_max, uint32_t form, int32_t force,
+                         uint64_t *need, int32_t *gate, uint64_t *base, uint64_t *cap);
+
 /* Free the current device's grow-only work buffers (candidate list, hit list, sort space), so a
  * test can force the "buffer too small -> grow -> run the pass again" path.  Needs a GPU. */
 int ms_debug_release_scratch(void);

@@ -31,7 +31,7 @@ class ScanStats(ctypes.Structure):
                 ("ms_total", ctypes.c_double), ("lds_bytes_read", ctypes.c_int64),
                 ("hbm_bytes_algorithmic", ctypes.c_int64), ("pf_clock_mhz", ctypes.c_double),
                 ("mfma_ops", ctypes.c_int64), ("mfma_ops_algorithmic", ctypes.c_int64), ("pf_engine", ctypes.c_int32),
-                ("order_overflow_runs", ctypes.c_int32)]
+                ("order_overflow_runs", ctypes.c_int32), ("order_bucketed", ctypes.c_int32), ("reserved0", ctypes.c_int32)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -172,6 +172,9 @@ def lib():
         "ms_varscan_device_ms": (c_int, [vp, pd]),
         "ms_varscan_free": (None, [vp]),
         "ms_debug_varscan_chunk": (c_int, [c_i64, pi64]),
+        "ms_debug_bucket_plan": (c_int, [pi64, c_i64, pi32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_i64,
+                                 ctypes.POINTER(ctypes.c_uint64), ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int32,
+                                 ctypes.POINTER(ctypes.c_uint64), pi32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
         "ms_scan_alleles": (c_int, [vp, vp, pi32, pi64, pi32, ctypes.c_char_p, pi64, ctypes.c_char_p, c_i64, c_int, c_u32, pvp]),
         "ms_allelescan_num_sites": (c_int, [vp, pi64]),
         "ms_allelescan_motif_offsets": (c_int, [vp, pi64]),
@@ -805,6 +808,28 @@ def result_from_hits(n_pwms, n_regions, motif_offsets, seq_idx, pos, score_, str
     check(lib().ms_result_from_hits(int(n_pwms), int(n_regions), ptr(motif_offsets, ctypes.c_int64), ptr(seq_idx, ctypes.c_int64),
                                     ptr(pos, ctypes.c_int64), ptr(score_, ctypes.c_double), ptr(strand, ctypes.c_int8), ctypes.byref(h)))
     return ScanResult(h, int(n_pwms))
+
+
+def bucket_plan(mu, n_pred, *, gbits, pbits, end_bit, low_bits, offsets=None, widths=None, weights=None, n_pwms=0, n_regions=0, cap_max=None,
+                predicted=True, counts_only=False, carry_only=True, sticky_off=False, force=-1):
+    """ms_debug_bucket_plan (no device): the host arithmetic of a scan's bucketed hit list.  Either a set (offsets, widths) or the 256 bucket
+    weights; returns dict(weights, need, gate, base, cap)."""
+    w = np.zeros(256, dtype=np.uint64)
+    po = pw = None
+    n_seqs = 0
+    if offsets is not None:
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        widths = np.ascontiguousarray(widths, dtype=np.int32)
+        po, pw, n_seqs, n_pwms = ptr(offsets, ctypes.c_int64), ptr(widths, ctypes.c_int32), offsets.size - 1, widths.size
+    else:
+        w[:] = np.asarray(weights, dtype=np.uint64)
+    need, gate = ctypes.c_uint64(), ctypes.c_int32()
+    base, cap = np.zeros(256, dtype=np.uint64), np.zeros(256, dtype=np.uint64)
+    form = (1 if predicted else 0) | (2 if counts_only else 0) | (4 if carry_only else 0) | (8 if sticky_off else 0)
+    check(lib().ms_debug_bucket_plan(po, n_seqs, pw, n_pwms, int(gbits), int(pbits), int(end_bit), int(low_bits), int(n_regions), ptr(w, ctypes.c_uint64), float(mu),
+                                     int(n_pred), (1 << 64) - 1 if cap_max is None else int(cap_max), form, int(force), ctypes.byref(need),
+                                     ctypes.byref(gate), ptr(base, ctypes.c_uint64), ptr(cap, ctypes.c_uint64)))
+    return {"weights": w, "need": need.value, "gate": bool(gate.value), "base": base, "cap": cap}
 
 
 def host_pack(bases, offsets):

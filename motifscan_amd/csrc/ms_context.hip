@@ -86,6 +86,7 @@ int get_ctx(int device, DeviceCtx **out) {
     MS_HIP(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
     for (auto &ev : c->ev) MS_HIP(hipEventCreate(&ev));
     MS_HIP(hipMalloc(&c->sc.counters, 8 * sizeof(unsigned long long)));
+    MS_HIP(hipMalloc(&c->sc.bucket_tab, kBucketTabWords * sizeof(unsigned long long)));
     MS_HIP(hipHostMalloc(&c->sc.h_counters, 8 * sizeof(unsigned long long)));
     {
         size_t mem_free = 0, mem_total = 0;

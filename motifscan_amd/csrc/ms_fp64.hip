@@ -8,6 +8,14 @@
 //   rescore_kernel         the pre-filter's candidates (ms_kernels.hip); short candidate lists
 //   rescore_carry_kernel   the same for long lists: chunks of the list in motif order, the windows read in list order and
 //                          carried through an in-LDS counting sort (few cache lines per read either way)
+//
+// The hit list comes in two forms.  The plain one (HitOut): one counter word, a block appends its staged hits behind whatever the list holds.
+// The BUCKETED one (BucketHitOut; rescore_carry_kernel's second instantiation, for the predicted-size scans bucket_gate passes, ms_scan_geom.h):
+// 256 buckets of the lowest digit d0 = (key >> L) & 255 the radix passes would sort, each with its own fill word and its own stretch of the
+// list.  A flush counts its staged hits per bucket in LDS, reserves room with one atomicAdd per non-empty bucket, and writes each hit to its
+// bucket: a chunk of the candidate list covers ~26 position spots, so ~26 buckets get ~60 hits apiece -- coarser than a radix pass's own
+// scatter.  The stable LSD sort's pass over d0 is then the identity and is not run (scan_back, ms_scan.hip).  A hit that finds its bucket
+// full is dropped and the overflow word set; nobody waits for anybody.
 #include "ms_device.h"
 
 namespace ms {
@@ -57,8 +65,18 @@ struct HitStageN {
 };
 typedef HitStageN<kHitStage> HitStage;
 
-template <class ST>
-__device__ __forceinline__ void stage_hit(ST &st, const HitOut &H, uint32_t motif, int64_t g, uint32_t sbit, double score) {
+// ... into its bucket: a stage that is full sends its hits here one by one
+__device__ __forceinline__ void emit_hit(const BucketHitOut &H, uint32_t motif, int64_t g, uint32_t sbit, double score) {
+    const uint64_t key = ((uint64_t) motif << (H.gbits + 1)) | ((uint64_t) g << 1) | sbit;
+    const uint32_t b = (uint32_t) (key >> H.B.shift) & 255u;
+    const unsigned long long i = atomicAdd(&H.B.fill[b], 1ULL);
+    const unsigned long long at = H.B.base[b] + i;
+    if (i < H.B.cap[b] && at < H.cap) { H.keys[at] = key; H.vals[at] = score; }
+    else *H.B.overflow = 1ULL;
+}
+
+template <class ST, class HO>
+__device__ __forceinline__ void stage_hit(ST &st, const HO &H, uint32_t motif, int64_t g, uint32_t sbit, double score) {
     const unsigned int i = atomicAdd(&st.n, 1u);
     if (i < (unsigned int) ST::kCap) {
         st.keys[i] = ((uint64_t) motif << (H.gbits + 1)) | ((uint64_t) g << 1) | sbit;
@@ -85,8 +103,8 @@ __device__ __forceinline__ void stage_flush(ST &st, const HitOut &H) {
 
 // floor32: FieldMeta::floor32, the raw-sum floor of test_and_emit rounded DOWN to a float (it came with the field's record: windows
 // that cannot be hits read nothing more); the rest of the test reads {max_raw, cutoff} side by side
-template <class ST>
-__device__ __forceinline__ void test_and_stage(ST &st, const HitOut &H, const DevPwm &Pw, uint32_t motif, int64_t g,
+template <class ST, class HO>
+__device__ __forceinline__ void test_and_stage(ST &st, const HO &H, const DevPwm &Pw, uint32_t motif, int64_t g,
                                                double fwd, double rev, int strand_mask, float floor32) {
     const double floor_ = (double) floor32;
     const bool try_f = (strand_mask & 1) && !(fwd < floor_);
@@ -302,10 +320,54 @@ constexpr int kRwPerThread = 4;
 constexpr int kRwChunk = kRwThreads * kRwPerThread;       // 4096 candidates: 96 KB of LDS
 constexpr int kRwBins = 4096;
 typedef HitStageN<2048> RwStage;
+struct RwStageBk : RwStage {                // the bucketed flush's words per bucket: staged hits, room left in the bucket, first slot of this flush's hits
+    unsigned int cnt[kOrderBuckets], room[kOrderBuckets];
+    unsigned long long lo[kOrderBuckets];
+};
 
+// the bucketed form of stage_flush, for the kRwThreads threads of rescore_carry_kernel: every staged hit goes to bucket (key >> shift) & 255
+__device__ __forceinline__ void stage_flush(RwStageBk &st, const BucketHitOut &H) {
+    constexpr int kPer = RwStageBk::kCap / kRwThreads;
+    static_assert(kPer * kRwThreads == RwStageBk::kCap && kOrderBuckets <= kRwThreads, "stage_flush: one pass of the block over the stage");
+    __syncthreads();
+    const unsigned int n = st.n < (unsigned int) RwStageBk::kCap ? st.n : (unsigned int) RwStageBk::kCap;
+    if (threadIdx.x < (unsigned int) kOrderBuckets) st.cnt[threadIdx.x] = 0;
+    __syncthreads();
+    uint32_t bk[kPer], rank[kPer];
+#pragma unroll
+    for (int k = 0; k < kPer; k++) {
+        const unsigned int i = threadIdx.x + (unsigned int) (k * kRwThreads);
+        bk[k] = i < n ? (uint32_t) (st.keys[i] >> H.B.shift) & 255u : 0u;
+        rank[k] = i < n ? atomicAdd(&st.cnt[bk[k]], 1u) : 0u;
+    }
+    __syncthreads();
+    if (threadIdx.x < (unsigned int) kOrderBuckets && st.cnt[threadIdx.x] > 0) {
+        const unsigned int b = threadIdx.x, c = st.cnt[b];
+        const unsigned long long f = atomicAdd(&H.B.fill[b], (unsigned long long) c), cap = H.B.cap[b];
+        const unsigned long long left = f < cap ? cap - f : 0ULL;
+        st.lo[b] = H.B.base[b] + f;
+        st.room[b] = left < (unsigned long long) c ? (unsigned int) left : c;
+        if (left < (unsigned long long) c) *H.B.overflow = 1ULL;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kPer; k++) {
+        const unsigned int i = threadIdx.x + (unsigned int) (k * kRwThreads);
+        if (i < n && rank[k] < st.room[bk[k]]) {
+            const unsigned long long at = st.lo[bk[k]] + rank[k];
+            if (at < H.cap) { H.keys[at] = st.keys[i]; H.vals[at] = st.vals[i]; }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) st.n = 0;
+    __syncthreads();
+}
+
+// HO / ST: HitOut / RwStage -- the plain hit list; BucketHitOut / RwStageBk -- the bucketed one (the header comment)
+template <class HO, class ST>
 __global__ void __launch_bounds__(kRwThreads) rescore_carry_kernel(const DevSeq S, const DevPwm Pw, const uint64_t *__restrict__ cand,
                                                                    const unsigned long long *__restrict__ n_cand, uint64_t n_static, uint64_t cand_cap,
-                                                                   const FieldMeta *__restrict__ field_meta, int strand_mask, const HitOut H) {
+                                                                   const FieldMeta *__restrict__ field_meta, int strand_mask, const HO H) {
     extern __shared__ uint4 rw_lds4[];
     uint64_t *s_cw = reinterpret_cast<uint64_t *>(rw_lds4);                                 // [kRwChunk] the window's codes
     uint64_t *s_gk = s_cw + kRwChunk;                                                       // [kRwChunk] hit coordinate << 8 | room (bases to the region's end, <= 255)
@@ -313,7 +375,7 @@ __global__ void __launch_bounds__(kRwThreads) rescore_carry_kernel(const DevSeq 
     uint32_t *s_gf = s_nw + kRwChunk;                                                       // [kRwChunk] group << 16 | flags (0: nothing)
     uint32_t *bins = s_gf + kRwChunk;                                                       // [kRwBins]
     uint32_t *wave_tot = bins + kRwBins;                                                    // [16]
-    RwStage &st = *reinterpret_cast<RwStage *>(wave_tot + 32);
+    ST &st = *reinterpret_cast<ST *>(wave_tot + 32);
     if (threadIdx.x == 0) st.n = 0;
     unsigned long long n = n_static + *n_cand;
     if (n > cand_cap) n = cand_cap;
@@ -427,15 +489,30 @@ __global__ void __launch_bounds__(kRwThreads) rescore_carry_kernel(const DevSeq 
     }
 }
 
-size_t rescore_carry_lds_bytes() { return (size_t) kRwChunk * 24 + (size_t) kRwBins * 4 + 32 * 4 + sizeof(RwStage) + 64; }
+template <class ST>
+static size_t rescore_carry_lds_bytes() { return (size_t) kRwChunk * 24 + (size_t) kRwBins * 4 + 32 * 4 + sizeof(ST) + 64; }
 int rescore_carry_set_lds() {
-    MS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(rescore_carry_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) rescore_carry_lds_bytes()));
+    MS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(rescore_carry_kernel<HitOut, RwStage>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int) rescore_carry_lds_bytes<RwStage>()));
+    MS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(rescore_carry_kernel<BucketHitOut, RwStageBk>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int) rescore_carry_lds_bytes<RwStageBk>()));
     return MS_OK;
 }
 int launch_rescore_carry(const DevSeq &S, const DevPwm &Pw, const uint64_t *cand, const unsigned long long *n_cand, uint64_t n_static,
                          uint64_t cand_cap, const FieldMeta *field_meta, int strand_mask, const HitOut &H, int n_blocks, hipStream_t st) {
-    hipLaunchKernelGGL(rescore_carry_kernel, dim3((unsigned) n_blocks), dim3(kRwThreads), rescore_carry_lds_bytes(), st, S, Pw, cand, n_cand, n_static,
-                       cand_cap, field_meta, strand_mask, H);
+    hipLaunchKernelGGL((rescore_carry_kernel<HitOut, RwStage>), dim3((unsigned) n_blocks), dim3(kRwThreads), rescore_carry_lds_bytes<RwStage>(), st, S, Pw,
+                       cand, n_cand, n_static, cand_cap, field_meta, strand_mask, H);
+    MS_HIP(hipGetLastError());
+    return MS_OK;
+}
+int launch_rescore_carry_bucketed(const DevSeq &S, const DevPwm &Pw, const uint64_t *cand, const unsigned long long *n_cand, uint64_t n_static,
+                                  uint64_t cand_cap, const FieldMeta *field_meta, int strand_mask, const HitOut &H, const BucketOut &B, int n_blocks,
+                                  hipStream_t st) {
+    BucketHitOut HB;
+    static_cast<HitOut &>(HB) = H;
+    HB.B = B;
+    hipLaunchKernelGGL((rescore_carry_kernel<BucketHitOut, RwStageBk>), dim3((unsigned) n_blocks), dim3(kRwThreads), rescore_carry_lds_bytes<RwStageBk>(), st,
+                       S, Pw, cand, n_cand, n_static, cand_cap, field_meta, strand_mask, HB);
     MS_HIP(hipGetLastError());
     return MS_OK;
 }

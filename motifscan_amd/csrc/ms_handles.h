@@ -23,7 +23,8 @@ struct Scratch {                 // grow-only work buffers of the scan pipeline
     uint64_t *keys = nullptr;     double *vals = nullptr;   uint64_t *keys_sorted = nullptr;  size_t hit_cap = 0;
     void *sort_tmp = nullptr;     size_t sort_tmp_bytes = 0;
     unsigned int *chunk_counters = nullptr;    size_t chunk_counters_cap = 0;   // per LDS tile: the pre-filter's chunk dispenser
-    unsigned long long *counters = nullptr;      // 8 words: [0] candidate record slots, [1] hits, [2] runs ordered by order_overflow_kernel (ms_scan.hip)
+    unsigned long long *counters = nullptr;      // 8 words: [0] candidate record slots, [1] hits, [2] runs ordered by order_overflow_kernel, [3] != 0: a hit did not fit its bucket (ms_scan.hip)
+    unsigned long long *bucket_tab = nullptr;    // kBucketTabWords: base, capacity and fill of the 256 buckets of a bucketed hit list (BucketOut)
     unsigned long long *h_counters = nullptr;    // pinned
 };
 
@@ -171,6 +172,7 @@ struct ms_pwmset {
     // what the last scan with these PWMs (the one pred_key names) found, for the one-sync form of the next (ms_scan.hip, scan_locked):
     // hits per window, and how far above it the next count may be before the prediction counts as failed
     double pred_density = -1.0, pred_margin = 0.06;
+    bool bucket_off = false;                      // a bucket of a bucketed hit list overflowed once (skewed data): this set's scans emit plain lists from then on
     ms::ScanKey pred_key;
     // pre-filter plan (lazy, keyed by strand mask / cutoffs / LDS budget / exact-only)
     ms::PrefilterPlan plan;
@@ -209,6 +211,11 @@ struct ms_seqset {
     hipStream_t up = nullptr;             // the upload stream this set is being built on (DeviceCtx::stream_up, read once)
     void *h_off_pin = nullptr;            // the offsets' way to the device: a pinned copy (from pageable memory the runtime copies with a KERNEL, which waits for a CU the pre-filter holds)
     size_t h_off_pin_bytes = 0;
+    // the weights of a bucketed hit list's 256 buckets (bucket_weights, ms_scan_geom.h), made by the first scan that wants them and kept: the offsets
+    // of a live set never change.  Keyed by the key layout, L and the motif widths (bk_widths: a hash).  Touched under the device's lock.
+    // Up to four are kept (the last used first): PWM sets of different widths that take turns on one sequence set each find theirs.
+    struct BkWeights { int gbits, pbits, L; uint64_t widths; ms::BucketWeights w; };
+    std::vector<BkWeights> bk_weights;
     bool built = false;                   // construction finished (its work on `up` is done)
     bool pack_pending = false;            // a batch stream's upload-only set: ASCII and offsets are in HBM, pack_kernel / blk2reg_kernel still to run (seqset_pack_pending, on the scan stream)
 };

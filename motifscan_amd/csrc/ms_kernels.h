@@ -65,6 +65,27 @@ struct HitOut {
     int pbits;                // > 0: bits of the position inside a region (see keys)
 };
 
+// A hit list in BUCKETS of the lowest radix digit d0 = (key >> shift) & 255 (a predicted-size scan whose geometry passes bucket_gate,
+// ms_scan_geom.h): bucket b owns the slots [base[b], base[b] + cap[b]) of HitOut::keys / vals, fill[b] counts the hits sent to it (beyond
+// cap[b]: dropped, *overflow set -- the scan is run again with a plain list).  One table of kBucketTabWords words: base, cap, fill (256
+// each), then [768] the end of the last bucket.
+constexpr int kOrderBuckets = 256;
+constexpr size_t kBucketTabWords = 3 * kOrderBuckets + 8;
+struct BucketWeights {                   // per (sequence set, motif widths, key layout, L): the (motif, window start) pairs whose key falls into each bucket (bucket_weights, ms_scan_geom.h)
+    unsigned long long w[kOrderBuckets];
+    unsigned long long total;
+};
+struct BucketOut {
+    const unsigned long long *base;
+    const unsigned long long *cap;
+    unsigned long long *fill;
+    unsigned long long *overflow;
+    int shift;
+};
+struct BucketHitOut : HitOut {
+    BucketOut B;
+};
+
 struct PfArgs {
     const uint32_t *codes;
     const uint32_t *nmask;
@@ -100,9 +121,19 @@ int launch_rescore(const DevSeq &S, const DevPwm &Pw, const uint64_t *cand, cons
 int rescore_carry_set_lds();
 int launch_rescore_carry(const DevSeq &S, const DevPwm &Pw, const uint64_t *cand, const unsigned long long *n_cand, uint64_t n_static,
                          uint64_t cand_cap, const FieldMeta *field_meta, int strand_mask, const HitOut &H, int n_blocks, hipStream_t st);
+// ... the same with the hits flushed into the buckets of B
+int launch_rescore_carry_bucketed(const DevSeq &S, const DevPwm &Pw, const uint64_t *cand, const unsigned long long *n_cand, uint64_t n_static,
+                                  uint64_t cand_cap, const FieldMeta *field_meta, int strand_mask, const HitOut &H, const BucketOut &B, int n_blocks,
+                                  hipStream_t st);
 // ms_order.hip (its header says which key layout takes which of these).  launch_sort_fixup: after a sort over the key bits above
 // kSortLowBits, runs of hits equal in those bits into full key order (in place)
 int launch_fill_tail(uint64_t *keys, const unsigned long long *n_dev, uint64_t cap, hipStream_t st);
+// the bucketed hit list's table for this scan (base, cap from the weights and n_pred; fill zeroed), queued in front of the fp64 stage, and its
+// tail fill behind it: all-ones keys into the unused slots of every bucket and behind the last one, *n_hits = the hits the buckets hold
+int launch_bucket_plan(const BucketWeights &bw, double mu, unsigned long long n_pred, unsigned long long need, unsigned long long cap_max,
+                       unsigned long long *tab, hipStream_t st);
+int launch_fill_tail_buckets(uint64_t *keys, const unsigned long long *tab, uint64_t n_pred, unsigned long long *n_hits, unsigned long long *overflow,
+                             hipStream_t st);
 int launch_sort_fixup(uint64_t *keys, double *vals, int64_t n, const unsigned long long *n_dev, hipStream_t st);
 int launch_finalize(const uint64_t *keys, int64_t n, const unsigned long long *n_dev, int gbits, int rbits, int pbits, int32_t P, const DevSeq &S,
                     int64_t *seq_idx, int64_t *pos, int8_t *strand, int64_t *motif_first, unsigned long long *region_counts,

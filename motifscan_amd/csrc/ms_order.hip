@@ -5,6 +5,13 @@
 //   pbits == 0 (global base position: regions too long for the field)     sort_fixup_kernel if the sort left out the low kSortLowBits, then
 //                                                                         finalize_kernel, which looks every hit's region up
 //   either layout, a scan with predicted sizes                            fill_tail_kernel first: all-ones keys behind the hits sort last
+//   ... whose fp64 stage wrote the hits in buckets of the digit at L       bucket_plan_kernel in front of the fp64 stage (the buckets' places for
+//   (ms_fp64.hip's header; L > 0, pbits > 0)                              this scan), fill_tail_buckets_kernel behind it: all-ones keys into every
+//                                                                         bucket's unused slots, the hit count from the buckets' fills
+//
+// A bucketed list is ordered by the digit (key >> L) & 255 already, but for the all-ones keys strewn through it.  The radix passes then cover
+// [L + 8, end_bit) only: they are stable, so hits that agree in those bits keep the list's order -- ascending in the digit at L -- and the
+// all-ones keys, wherever they stood, end up behind every hit.  order_finalize_kernel sees what three passes used to leave it.
 //
 // The radix passes (ms_sort.hip) order the keys over the bits [L, end_bit) only.  Hits that agree in those bits -- a RUN -- are then
 // neighbours, in no particular order among themselves.  order_finalize_kernel finishes the order of every run in LDS and writes the
@@ -357,6 +364,87 @@ __global__ void __launch_bounds__(256) sort_fixup_kernel(uint64_t *__restrict__ 
 int launch_sort_fixup(uint64_t *keys, double *vals, int64_t n, const unsigned long long *n_dev, hipStream_t st) {
     if (n == 0) return MS_OK;
     hipLaunchKernelGGL(sort_fixup_kernel, dim3((unsigned) ((n + 1023) / 1024)), dim3(256), 0, st, keys, vals, n, n_dev);
+    MS_HIP(hipGetLastError());
+    return MS_OK;
+}
+
+// The places of the 256 buckets in a list of n_pred slots: the expressions of ms_scan_geom.cpp's bucket_caps, in its order of operations (the
+// library is built with -ffp-contract=off, so neither side fuses the multiply-adds; should a capacity still come out a slot apart from the
+// host's `need`, the running-sum cut below keeps every bucket inside the list).  The host only needs the sum of the needs, for its gate.  One block of kOrderBuckets threads.  tab: base, cap, fill, then the end of the last bucket (BucketOut, ms_kernels.h).
+__global__ void __launch_bounds__(kOrderBuckets) bucket_plan_kernel(const BucketWeights bw, double mu, unsigned long long n_pred, unsigned long long need,
+                                                                    unsigned long long cap_max, unsigned long long *__restrict__ tab) {
+    __shared__ unsigned long long sum[kOrderBuckets];
+    const int b = (int) threadIdx.x;
+    const unsigned long long w = bw.w[b];
+    unsigned long long cb = 0;
+    if (w) {
+        const double e = mu * (double) w / (double) bw.total;
+        cb = (unsigned long long) ceil(e + 6.0 * __dsqrt_rn(e + 1.0)) + 1ULL;
+        const unsigned long long extra = n_pred > need ? n_pred - need : 0ULL;
+        cb += (unsigned long long) floor((double) extra * (double) w / (double) bw.total);
+    }
+    if (cb > cap_max) cb = cap_max;
+    sum[b] = cb;
+    __syncthreads();
+    for (int d = 1; d < kOrderBuckets; d <<= 1) {
+        const unsigned long long v = b >= d ? sum[b - d] : 0ULL;
+        __syncthreads();
+        sum[b] += v;
+        __syncthreads();
+    }
+    const unsigned long long at = sum[b] - cb, base = at < n_pred ? at : n_pred;
+    tab[b] = base;
+    tab[kOrderBuckets + b] = cb < n_pred - base ? cb : n_pred - base;
+    tab[2 * kOrderBuckets + b] = 0ULL;
+    if (b == kOrderBuckets - 1) tab[3 * kOrderBuckets] = sum[b] < n_pred ? sum[b] : n_pred;
+}
+
+// grid (x, kOrderBuckets + 1): row b < kOrderBuckets fills the unused slots of bucket b, the last row the slots behind the last bucket; its first block
+// also sums the hits the buckets HOLD into *n_hits (what order_finalize_kernel reads as the list's length -- a dropped hit must not count: the slot
+// it would stand for holds an all-ones key, whose "motif" no decode may touch; the scan is run again anyway, *overflow says so)
+__global__ void __launch_bounds__(256) fill_tail_buckets_kernel(uint64_t *__restrict__ keys, const unsigned long long *__restrict__ tab, uint64_t n_pred,
+                                                                unsigned long long *__restrict__ n_hits, unsigned long long *__restrict__ overflow) {
+    const unsigned int b = blockIdx.y;
+    unsigned long long lo, hi;
+    if (b < (unsigned int) kOrderBuckets) {
+        const unsigned long long base = tab[b], cap = tab[kOrderBuckets + b], fill = tab[2 * kOrderBuckets + b];
+        lo = base + (fill < cap ? fill : cap);
+        hi = base + cap;
+        if (fill > cap && blockIdx.x == 0 && threadIdx.x == 0) *overflow = 1ULL;
+    } else {
+        lo = tab[3 * kOrderBuckets];
+        hi = n_pred;
+        if (blockIdx.x == 0) {
+            __shared__ unsigned long long part[256];
+            unsigned long long v = 0;
+            for (int q = (int) threadIdx.x; q < kOrderBuckets; q += 256) {
+                const unsigned long long cap = tab[kOrderBuckets + q], fill = tab[2 * kOrderBuckets + q];
+                v += fill < cap ? fill : cap;
+            }
+            part[threadIdx.x] = v;
+            __syncthreads();
+            for (int d = 128; d > 0; d >>= 1) {
+                if ((int) threadIdx.x < d) part[threadIdx.x] += part[threadIdx.x + d];
+                __syncthreads();
+            }
+            if (threadIdx.x == 0) *n_hits = part[0];
+        }
+    }
+    if (hi > n_pred) hi = n_pred;
+    for (unsigned long long i = lo + (unsigned long long) blockIdx.x * blockDim.x + threadIdx.x; i < hi; i += (unsigned long long) gridDim.x * blockDim.x)
+        keys[i] = ~0ULL;
+}
+
+int launch_bucket_plan(const BucketWeights &bw, double mu, unsigned long long n_pred, unsigned long long need, unsigned long long cap_max,
+                       unsigned long long *tab, hipStream_t st) {
+    hipLaunchKernelGGL(bucket_plan_kernel, dim3(1), dim3(kOrderBuckets), 0, st, bw, mu, n_pred, need, cap_max, tab);
+    MS_HIP(hipGetLastError());
+    return MS_OK;
+}
+
+int launch_fill_tail_buckets(uint64_t *keys, const unsigned long long *tab, uint64_t n_pred, unsigned long long *n_hits, unsigned long long *overflow,
+                             hipStream_t st) {
+    hipLaunchKernelGGL(fill_tail_buckets_kernel, dim3(16, kOrderBuckets + 1), dim3(256), 0, st, keys, tab, n_pred, n_hits, overflow);
     MS_HIP(hipGetLastError());
     return MS_OK;
 }

@@ -101,8 +101,12 @@ static void finish_scan(ms_result *raw, hipEvent_t *ev, ms_pwmset *pwms, int64_t
 
 // The end of a scan whose sizes were predicted: did the scratch buffers and the predicted hit count hold?  A prediction that held
 // narrows the margin of the next scans; one that failed doubles it, and the density is learnt again through the exactly-sized form.
-static bool prediction_held(ms_pwmset *pwms, unsigned long long n_cand, size_t cand_cap, unsigned long long n_hits, size_t hit_cap, size_t n_pred) {
-    if (n_cand <= cand_cap && n_hits <= hit_cap && n_hits <= n_pred) {
+// bucket_overflow: a hit of a bucketed list did not fit its bucket (counters[3]).  That is a failed prediction too -- of how the hits spread
+// over the regions -- and such data (hits crowded into few regions) would fail again: the set's scans emit plain lists from then on.
+static bool prediction_held(ms_pwmset *pwms, unsigned long long n_cand, size_t cand_cap, unsigned long long n_hits, size_t hit_cap, size_t n_pred,
+                            bool bucket_overflow) {
+    if (bucket_overflow) pwms->bucket_off = true;
+    if (n_cand <= cand_cap && n_hits <= hit_cap && n_hits <= n_pred && !bucket_overflow) {
         pwms->pred_margin = std::max(0.04, pwms->pred_margin * 0.9);
         return true;
     }
@@ -121,7 +125,7 @@ int scan_complete(DeviceCtx *c, ms_pwmset *pwms, PendingScan *p, ms_result **out
     if (he != hipSuccess) { set_error("scan kernels failed: %s", hipGetErrorString(he)); ms_result_free(raw); return MS_ERR_RUNTIME; }
     const unsigned long long n_cand = p->cand_static + p->h_counters[0], n_hits = p->h_counters[1];
     (void) c;
-    if (!prediction_held(pwms, n_cand, p->cand_cap, n_hits, p->hit_cap, p->n_pred)) { ms_result_free(raw); return MS_SCAN_RETRY; }
+    if (!prediction_held(pwms, n_cand, p->cand_cap, n_hits, p->hit_cap, p->n_pred, p->h_counters[3] != 0)) { ms_result_free(raw); return MS_SCAN_RETRY; }
     const size_t n_off = raw->motif_offsets.size();      // (copied in stream order, in front of `done`: pending_fill)
     std::memcpy(raw->motif_offsets.data(), p->h_offsets, n_off * sizeof(int64_t));
     try { raw->h_region_counts.assign(p->h_offsets + n_off, p->h_offsets + n_off + raw->P); } catch (const std::bad_alloc &) { raw->h_region_counts.clear(); }
@@ -147,6 +151,12 @@ struct ScanCtx {
     DevSeq S;
     DevPwm Pw;
     bool counts_ok = false;              // a counts-only scan whose set the bitmap form takes (scan_counts_fast)
+    // the bucketed hit list (scan_bucket_decide): the fp64 stage emits in buckets of the digit at bk_L, the radix passes start at bk_L + 8
+    bool bucketed = false;
+    int bk_L = 0;
+    double bk_mu = 0.0;                  // expected hits, and the sum of the buckets' needs at that expectation (bucket_need)
+    unsigned long long bk_need = 0, bk_cap_max = ~0ULL;
+    BucketWeights bk_w;                  // the sequence set's bucket weights for this key layout, L and these motif widths
 };
 
 // The plan of this scan, with its device copies.  Which kernel family it runs (PrefilterPlan::wide) decides the LDS budget it is built
@@ -212,6 +222,14 @@ static HitOut scan_hit_out(const ScanCtx &x) {
     return H;
 }
 
+static BucketOut scan_bucket_out(const ScanCtx &x) {
+    const Scratch &sc = x.c->sc;
+    BucketOut B;
+    B.base = sc.bucket_tab; B.cap = sc.bucket_tab + kOrderBuckets; B.fill = sc.bucket_tab + 2 * kOrderBuckets; B.overflow = sc.counters + 3;
+    B.shift = x.bk_L;
+    return B;
+}
+
 // "fetch the eight counters and wait": counters [0] candidate record slots, [1] hits, [2] runs ordered by order_overflow_kernel
 static int fetch_counters(DeviceCtx *c, const char *what) {
     hipError_t he = hipMemcpyAsync(c->sc.h_counters, c->sc.counters, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
@@ -255,7 +273,7 @@ static int scan_prefilter(ScanCtx &x) {
 }
 
 // pre-filter + fp64 stage of one pass, queued on the scan stream (events 0, 1, 2 around the two stages)
-static int scan_front(ScanCtx &x, const HitOut &H) {
+static int scan_front(ScanCtx &x, const HitOut &H, const BucketOut *B = nullptr) {
     DeviceCtx *c = x.c;
     Scratch &sc = c->sc;
     const PrefilterPlan &plan = x.pwms->plan;
@@ -268,7 +286,9 @@ static int scan_front(ScanCtx &x, const HitOut &H) {
     if (!plan.fast_motifs.empty()) {                 // (few blocks for a small scan measured slower: the kernel is a chain of dependent gathers and wants every record in flight at once)
         if (x.g.rescore_carry) {
             if (!c->rc_lds_set) { if ((rc = rescore_carry_set_lds())) return rc; c->rc_lds_set = true; }
-            if ((rc = launch_rescore_carry(x.S, x.Pw, sc.cand, sc.counters, x.g.cand_static, sc.cand_cap, x.pwms->d_field_meta, x.strand_mask, H, c->n_cu, c->stream))) return rc;
+            if (B) rc = launch_rescore_carry_bucketed(x.S, x.Pw, sc.cand, sc.counters, x.g.cand_static, sc.cand_cap, x.pwms->d_field_meta, x.strand_mask, H, *B, c->n_cu, c->stream);
+            else rc = launch_rescore_carry(x.S, x.Pw, sc.cand, sc.counters, x.g.cand_static, sc.cand_cap, x.pwms->d_field_meta, x.strand_mask, H, c->n_cu, c->stream);
+            if (rc) return rc;
         } else if ((rc = launch_rescore(x.S, x.Pw, sc.cand, sc.counters, x.g.cand_static, sc.cand_cap, x.pwms->d_field_meta, x.strand_mask, H, c->n_cu * 8, c->stream))) return rc;
     }
     if (!plan.exact_motifs.empty()) {
@@ -318,6 +338,7 @@ static int back_count_only(ScanCtx &x, size_t n_sort, const unsigned long long *
 }
 
 // the radix passes over the key bits [sort_begin, end_bit) of the first n_sort slots, and the fix-up behind them for global-position keys
+// (a bucketed list: sort_begin = L + 8, the digit at L is in order as the list stands)
 static int back_sort(ScanCtx &x, size_t n_sort, const unsigned long long *n_dev, int sort_begin, size_t ovf_bytes) {
     DeviceCtx *c = x.c;
     Scratch &sc = c->sc;
@@ -372,7 +393,7 @@ static int scan_back(ScanCtx &x, size_t n_sort, const unsigned long long *n_dev,
     if (counts_fast) return back_count_only(x, n_sort, n_dev, queue_only);
     const int sort_begin = scan_sort_begin(g, P, n_sort);
     const size_t ovf_bytes = g.pbits > 0 && sort_begin > 0 ? order_overflow_bytes(n_sort, g.order_run_cap) : 0;
-    if (n_sort > 0 && (rc = back_sort(x, n_sort, n_dev, sort_begin, ovf_bytes))) return rc;
+    if (n_sort > 0 && (rc = back_sort(x, n_sort, n_dev, x.bucketed ? sort_begin + 8 : sort_begin, ovf_bytes))) return rc;
     (void) hipEventRecord(x.ev[4], c->stream);
     if (g.pbits > 0 && sort_begin > 0) {
         // counters[2]: the runs order_finalize_kernel leaves to its overflow launch (zeroed with the others in front of the pre-filter).
@@ -387,6 +408,44 @@ static int scan_back(ScanCtx &x, size_t n_sort, const unsigned long long *n_dev,
     return fetch_offsets(x, queue_only);
 }
 
+// Whether this predicted-size scan emits its hits in buckets (bucket_gate, ms_scan_geom.h), with what it takes: the set's bucket weights for this
+// key layout and L (made once per sequence set, on the host, from its offsets), and the sum of the buckets' needs.  Forced on by a test
+// (MS_ORDER_BUCKETS=1), *n_pred grows to that sum: a short list's 6-sigma slacks do not fit a few per cent of it.
+static void scan_bucket_decide(ScanCtx &x, const ScanOverrides &ov, double mu, size_t *n_pred) {
+    const PrefilterPlan &plan = x.pwms->plan;
+    ms_seqset *seqs = const_cast<ms_seqset *>(x.seqs);           // (the cached weights; the caller holds the device's lock)
+    BucketShape bs;
+    bs.predicted = true;
+    bs.counts_only = x.counts_ok;                                // (any counts-only scan: whether it takes the bitmap form is decided on the final n_pred)
+    bs.carry_only = x.g.rescore_carry && x.g.n_tiles > 0 && !plan.fast_motifs.empty() && plan.exact_motifs.empty();
+    bs.sticky_off = x.pwms->bucket_off;
+    bs.pbits = x.g.pbits; bs.gbits = x.g.gbits; bs.end_bit = x.g.end_bit; bs.P = x.pwms->P; bs.R = x.seqs->R;
+    bs.L = scan_sort_begin(x.g, x.pwms->P, *n_pred);
+    if (!bucket_gate(bs, ov, 0, *n_pred) || seqs->offsets.size() != (size_t) seqs->R + 1) return;      // (need 0: everything but the size, before the weights are looked at)
+    uint64_t wh = 1469598103934665603ULL;                         // FNV-1a of the widths
+    for (int32_t w : x.pwms->widths) wh = (wh ^ (uint64_t) (uint32_t) w) * 1099511628211ULL;
+    auto &cache = seqs->bk_weights;
+    size_t at = 0;
+    while (at < cache.size() && !(cache[at].L == bs.L && cache[at].gbits == bs.gbits && cache[at].pbits == bs.pbits && cache[at].widths == wh)) at++;
+    try {
+        if (at == cache.size()) {
+            if (cache.size() >= 4) cache.pop_back();
+            cache.insert(cache.begin(), ms_seqset::BkWeights{bs.gbits, bs.pbits, bs.L, wh, {}});
+            bucket_weights(seqs->offsets.data(), seqs->R, x.pwms->widths.data(), x.pwms->P, bs.gbits, bs.pbits, bs.L, &cache[0].w);
+        } else if (at > 0) std::rotate(cache.begin(), cache.begin() + at, cache.begin() + at + 1);
+    } catch (const std::bad_alloc &) { return; }
+    x.bk_w = cache[0].w;
+    if (x.bk_w.total == 0) return;
+    const unsigned long long need = bucket_need(x.bk_w, mu);
+    if (!bucket_gate(bs, ov, need, *n_pred)) return;
+    if (need > *n_pred) {                                        // forced
+        if (need > 3000000000ULL || scan_sort_begin(x.g, x.pwms->P, (size_t) need) != bs.L) return;
+        *n_pred = (size_t) need;
+    }
+    x.bucketed = true;
+    x.bk_L = bs.L; x.bk_mu = mu; x.bk_need = need; x.bk_cap_max = ov.bucket_cap_max;
+}
+
 // Every launch of a scan whose sizes are PREDICTED, queued at once: the result block, the sort and the coordinate kernel are sized
 // for n_pred hits (the fp64 stage's real count stays on the device: the unused slots are filled with all-ones keys that sort last,
 // finalize reads the count there).
@@ -397,8 +456,17 @@ static int scan_queue_predicted(ScanCtx &x, size_t n_pred, bool queue_only) {
     const bool counts_fast = scan_counts_fast(x, n_pred);
     if ((rc = result_block_alloc(x.c, x.raw, counts_fast ? 1 : n_pred))) return rc;
     x.raw->stats.n_passes = 1;
-    if ((rc = scan_front(x, scan_hit_out(x)))) return rc;
-    if ((rc = launch_fill_tail(sc.keys, sc.counters + 1, n_pred, x.c->stream))) return rc;
+    x.raw->stats.order_bucketed = x.bucketed ? 1 : 0;
+    if (x.bucketed) {
+        // the buckets' places for this scan, then the front with the bucketed fp64 stage; the tail fill also makes counters[1] out of the fills
+        const BucketOut B = scan_bucket_out(x);
+        if ((rc = launch_bucket_plan(x.bk_w, x.bk_mu, n_pred, x.bk_need, x.bk_cap_max, sc.bucket_tab, x.c->stream))) return rc;
+        if ((rc = scan_front(x, scan_hit_out(x), &B))) return rc;
+        if ((rc = launch_fill_tail_buckets(sc.keys, sc.bucket_tab, n_pred, sc.counters + 1, sc.counters + 3, x.c->stream))) return rc;
+    } else {
+        if ((rc = scan_front(x, scan_hit_out(x)))) return rc;
+        if ((rc = launch_fill_tail(sc.keys, sc.counters + 1, n_pred, x.c->stream))) return rc;
+    }
     return scan_back(x, n_pred, sc.counters + 1, counts_fast, queue_only);
 }
 
@@ -525,7 +593,8 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
     if (density_known && !(flags & (MS_SCAN_RAW_INTERNAL | MS_SCAN_NO_PREDICT_INTERNAL)) && !ov.no_predict) {
         if (pend) x.ev = pend->ev;
         const double mu = pwms->pred_density * (double) stt.n_windows;
-        const size_t n_pred = (size_t) std::min<double>(mu * (1.0 + pwms->pred_margin) + 6.0 * std::sqrt(mu + 1.0) + 256.0, 3.0e9);
+        size_t n_pred = (size_t) std::min<double>(mu * (1.0 + pwms->pred_margin) + 6.0 * std::sqrt(mu + 1.0) + 256.0, 3.0e9);
+        scan_bucket_decide(x, ov, mu, &n_pred);
         if ((rc = scan_queue_predicted(x, n_pred, pend != nullptr))) return rc;
         if (pend) {
             if ((rc = pending_fill(x, pend, n_pred))) return rc;
@@ -535,7 +604,7 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
         }
         if ((rc = fetch_counters(c, "scan kernels"))) return rc;
         const unsigned long long n_cand = x.g.cand_static + sc.h_counters[0], n_hits = sc.h_counters[1];
-        if (prediction_held(pwms, n_cand, sc.cand_cap, n_hits, sc.hit_cap, n_pred)) {
+        if (prediction_held(pwms, n_cand, sc.cand_cap, n_hits, sc.hit_cap, n_pred, sc.h_counters[3] != 0)) {
             finish_scan(x.raw, x.ev, pwms, seqs->n_bases, seqs->R, x.key, n_cand, n_hits, true, sc.h_counters[2]);
             *out = res.release();
             return MS_OK;
@@ -546,6 +615,8 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
         x.raw->block_bytes = 0;
         if (x.raw->coord_blk) { pool_free(c, x.raw->coord_blk, x.raw->coord_bytes); x.raw->coord_blk = nullptr; x.raw->d_coord = nullptr; x.raw->d_coord_bad = nullptr; }
         stt.n_passes = 1;
+        stt.order_bucketed = 0;
+        x.bucketed = false;
         scan_grow(sc.cand_cap, sc.hit_cap, n_cand, n_hits, &want_cand, &want_hits);
     }
     if ((rc = scan_exact(x, want_cand, want_hits))) return rc;
@@ -573,6 +644,33 @@ int ms_scan(const ms_pwmset *pwms_c, const ms_seqset *seqs, int strand_mask, uin
     std::lock_guard<std::mutex> lk_pwm(pwms->mu);
     const uint32_t internal = (flags & MS_SCAN_EXACT_ONLY) | ((flags & MS_SCAN_COUNTS_ONLY) ? MS_SCAN_COUNTS_ONLY_INTERNAL : 0u);
     return scan_locked(c, pwms, seqs, strand_mask, internal, out);
+}
+
+// the bucketed hit list's host arithmetic alone, for CPU tests (include/motifscan_amd_debug.h)
+int ms_debug_bucket_plan(const int64_t *offsets, int64_t n_seqs, const int32_t *widths, int32_t n_pwms, int32_t gbits, int32_t pbits, int32_t end_bit,
+                         int32_t low_bits, int64_t n_regions, uint64_t *weights, double mu, uint64_t n_pred, uint64_t cap_max, uint32_t form, int32_t force,
+                         uint64_t *need, int32_t *gate, uint64_t *base, uint64_t *cap) {
+    if (!weights || !need || !gate || !base || !cap) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    BucketWeights bw;
+    if (offsets) {
+        if (!widths || n_seqs < 0 || n_pwms < 0) { set_error("invalid set"); return MS_ERR_INVALID; }
+        bucket_weights(offsets, n_seqs, widths, n_pwms, gbits, pbits, low_bits, &bw);
+        for (int b = 0; b < kOrderBuckets; b++) weights[b] = bw.w[b];
+    } else {
+        bw.total = 0;
+        for (int b = 0; b < kOrderBuckets; b++) { bw.w[b] = weights[b]; bw.total += weights[b]; }
+    }
+    BucketShape bs;
+    bs.predicted = (form & 1u) != 0; bs.counts_only = (form & 2u) != 0; bs.carry_only = (form & 4u) != 0; bs.sticky_off = (form & 8u) != 0;
+    bs.pbits = pbits; bs.gbits = gbits; bs.end_bit = end_bit; bs.L = low_bits; bs.P = n_pwms; bs.R = offsets ? n_seqs : n_regions;
+    ScanOverrides ov;
+    ov.order_buckets = force < 0 ? -1 : (force ? 1 : 0);
+    *need = bucket_need(bw, mu);
+    *gate = bw.total > 0 && bucket_gate(bs, ov, *need, n_pred) ? 1 : 0;
+    unsigned long long b64[kOrderBuckets], c64[kOrderBuckets];
+    bucket_caps(bw, mu, n_pred, cap_max, b64, c64);
+    for (int b = 0; b < kOrderBuckets; b++) { base[b] = b64[b]; cap[b] = c64[b]; }
+    return MS_OK;
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // ms_scan_geom.cpp -- a scan's geometry from its sizes (ms_scan_geom.h).  Pure host code: no HIP call, no handle.
 #include <algorithm>
 #include <cmath>
+#include <vector>
 
 #include "ms_scan_geom.h"
 
@@ -19,6 +20,8 @@ ScanOverrides read_scan_overrides() {
     if (const char *e = measure_env("MS_ORDER_RUN_CAP")) o.order_run_cap = std::max(1, atoi(e));
     if (const char *e = measure_env("MS_SORT_FIXUP_MIN")) o.fixup_min = (size_t) std::max(0, atoi(e));
     o.no_predict = measure_env("MS_NO_PREDICT") != nullptr;
+    if (const char *e = measure_env("MS_ORDER_BUCKETS")) o.order_buckets = atoi(e) != 0 ? 1 : 0;   // test aid / A-B: the bucketed hit list at any size, or never
+    if (const char *e = measure_env("MS_ORDER_BUCKET_CAP")) o.bucket_cap_max = (uint64_t) std::max(0LL, atoll(e));
     return o;
 }
 
@@ -149,6 +152,76 @@ static int order_low_bits(const ScanGeom &g, int32_t P, size_t n) {
 int scan_sort_begin(const ScanGeom &g, int32_t P, size_t n_sort) {
     if (g.pbits > 0) return n_sort >= g.fixup_min || g.sort_low_bits >= 0 ? order_low_bits(g, P, n_sort) : 0;
     return n_sort >= g.fixup_min ? g.sort_begin_large : 0;
+}
+
+// ---- the bucketed hit list
+
+// d0 of key = motif << (gbits + 1) | coord << 1 | strand is (coord >> c) & 255 with c = L - 1, as long as the digit stays inside the coordinate
+// (L + 8 <= gbits + 1: bucket_layout_ok).  A region's positions fall into chunks of 2^c coordinates; a chunk [a, b) of a region of length
+// len holds F(len - a) - F(len - b) window starts, F(x) = sum over the motif widths W of max(x - W + 1, 0).
+void bucket_weights(const int64_t *offsets, int64_t R, const int32_t *widths, int32_t P, int gbits, int pbits, int L, BucketWeights *out) {
+    for (auto &w : out->w) w = 0;
+    out->total = 0;
+    if (L < 1 || L + 8 > gbits + 1 || pbits < 1 || P < 1) return;
+    const int c = L - 1;
+    int max_w = 0;
+    unsigned long long sum_w = 0;
+    for (int32_t p = 0; p < P; p++) { max_w = std::max(max_w, (int) widths[p]); sum_w += (unsigned long long) widths[p]; }
+    std::vector<unsigned long long> tab((size_t) max_w + 1, 0);        // F up to the widest motif; linear beyond it
+    for (int32_t p = 0; p < P; p++)
+        for (int x = std::max((int) widths[p], 1); x <= max_w; x++) tab[(size_t) x] += (unsigned long long) (x - widths[p] + 1);
+    auto F = [&](int64_t x) -> unsigned long long {
+        if (x <= 0) return 0;
+        if (x <= max_w) return tab[(size_t) x];
+        return (unsigned long long) P * (unsigned long long) (x + 1) - sum_w;
+    };
+    for (int64_t r = 0; r < R; r++) {
+        const int64_t len = offsets[r + 1] - offsets[r];
+        if (len <= 0) continue;
+        const uint64_t c0 = (uint64_t) r << pbits;
+        for (uint64_t u = c0 >> c; u <= (c0 + (uint64_t) len - 1) >> c; u++) {
+            const int64_t a = (u << c) > c0 ? (int64_t) ((u << c) - c0) : 0;
+            const int64_t b = std::min<int64_t>(len, (int64_t) (((u + 1) << c) - c0));
+            const unsigned long long n = F(len - a) - F(len - b);
+            out->w[u & 255u] += n;
+            out->total += n;
+        }
+    }
+}
+
+unsigned long long bucket_need(const BucketWeights &bw, double mu) {
+    unsigned long long need = 0;
+    for (int b = 0; b < kOrderBuckets; b++) need += bucket_need_one(mu, bw.w[b], bw.total);
+    return need;
+}
+
+void bucket_caps(const BucketWeights &bw, double mu, unsigned long long n_pred, unsigned long long cap_max, unsigned long long *base, unsigned long long *cap) {
+    const unsigned long long need = bucket_need(bw, mu);
+    const unsigned long long extra = n_pred > need ? n_pred - need : 0;
+    unsigned long long at = 0;                      // the running sum of the uncut capacities
+    for (int b = 0; b < kOrderBuckets; b++) {
+        unsigned long long cb = bucket_need_one(mu, bw.w[b], bw.total);
+        if (bw.w[b]) cb += (unsigned long long) std::floor((double) extra * (double) bw.w[b] / (double) bw.total);
+        cb = std::min(cb, cap_max);
+        base[b] = std::min(at, n_pred);
+        cap[b] = std::min(cb, n_pred - base[b]);
+        at += cb;
+    }
+}
+
+bool bucket_layout_ok(const BucketShape &s) {
+    // (the digit inside the coordinate: with a motif bit in it every bucket would hold one class of motifs, and motifs differ tenfold in how often they hit)
+    if (!(s.pbits > 0 && s.L > 0 && s.L + 8 <= s.gbits + 1 && s.end_bit <= 63 && s.P > 0 && s.R > 0)) return false;
+    // the largest key a hit can have (last motif, last region, any position), in the bits [L + 8, end_bit)
+    const uint64_t top = ((((uint64_t) (s.P - 1) << s.gbits) | ((uint64_t) (s.R - 1) << s.pbits) | ((1ULL << s.pbits) - 1ULL)) << 1) >> (s.L + 8);
+    return top != (1ULL << (s.end_bit - s.L - 8)) - 1ULL;
+}
+
+bool bucket_gate(const BucketShape &s, const ScanOverrides &ov, unsigned long long need, unsigned long long n_pred) {
+    if (!s.predicted || s.counts_only || !s.carry_only || s.sticky_off || ov.order_buckets == 0 || !bucket_layout_ok(s)) return false;
+    if (ov.order_buckets == 1) return true;
+    // a full digit left for the passes above d0, and the needs inside the prediction
+    return s.end_bit - (s.L + 8) >= 8 && need <= n_pred;
 }
 
 void scan_grow(size_t cand_cap, size_t hit_cap, unsigned long long n_cand, unsigned long long n_hits, size_t *want_cand, size_t *want_hits) {

@@ -3,6 +3,7 @@
 // also runs under the sanitizers without a device (tests/sanitize/plan_asan.cpp).  ms_scan.hip is its only user in the library.
 #pragma once
 #include <climits>
+#include <cmath>
 
 #include "ms_kernels.h"
 
@@ -22,6 +23,8 @@ struct ScanOverrides {
     int order_run_cap = 1 << 30;          // MS_ORDER_RUN_CAP: longer runs take order_finalize_kernel's overflow path
     size_t fixup_min = (size_t) 1 << 20;  // MS_SORT_FIXUP_MIN: the fix-up form from this many hits (0: on short lists too)
     bool no_predict = false;              // MS_NO_PREDICT: never the predicted-size form
+    int order_buckets = -1;               // MS_ORDER_BUCKETS: 0 / 1 = the fp64 stage never / at any list size emits its hits in low-digit buckets; -1: by size (bucket_gate)
+    uint64_t bucket_cap_max = ~0ULL;      // MS_ORDER_BUCKET_CAP: no bucket holds more than this many hits (a test's way to the overflow path)
 };
 MS_HIDDEN ScanOverrides read_scan_overrides();
 
@@ -69,6 +72,34 @@ MS_HIDDEN ScanGeom scan_geometry(const ScanShape &s, const ScanOverrides &ov);
 
 // the first key bit the radix passes cover when n_sort slots are ordered (the kernels behind them order the bits below)
 MS_HIDDEN int scan_sort_begin(const ScanGeom &g, int32_t P, size_t n_sort);
+// ---- hits emitted in buckets of the lowest radix digit d0 = (key >> L) & 255 (ms_fp64.hip, "the bucketed flush"): the pass over that digit
+// is the identity on such a list, so the radix passes start at L + 8.  Bucket b owns cap_b slots of the predicted-size list, in digit order.
+// offsets [R + 1], widths [P] as the scan sees them; the hit density of a scan is taken as uniform over these pairs (the prediction's own model)
+MS_HIDDEN void bucket_weights(const int64_t *offsets, int64_t R, const int32_t *widths, int32_t P, int gbits, int pbits, int L, BucketWeights *out);
+// a bucket's share of mu expected hits, and the slots it needs at least: that share + 6 sigma of a Poisson count + 1 (0 for a bucket no key can fall
+// into).  The same expressions, operation for operation, in bucket_plan_kernel (ms_order.hip).
+inline double bucket_expected(double mu, unsigned long long w, unsigned long long total) { return total ? mu * (double) w / (double) total : 0.0; }
+inline unsigned long long bucket_need_one(double mu, unsigned long long w, unsigned long long total) {
+    if (!w) return 0;
+    const double e = bucket_expected(mu, w, total);
+    return (unsigned long long) std::ceil(e + 6.0 * std::sqrt(e + 1.0)) + 1ULL;
+}
+MS_HIDDEN unsigned long long bucket_need(const BucketWeights &bw, double mu);         // the sum over the buckets
+// cap_b = need_b + the bucket's share (rounded down) of what n_pred leaves above the sum of the needs, at most cap_max, and cut off where the
+// running sum would pass n_pred: sum cap_b <= n_pred always; cap_b >= need_b for every b when bucket_need() <= n_pred and cap_max allows it
+MS_HIDDEN void bucket_caps(const BucketWeights &bw, double mu, unsigned long long n_pred, unsigned long long cap_max, unsigned long long *base, unsigned long long *cap);
+struct BucketShape {                     // what the gate looks at besides the sizes
+    bool predicted = false, counts_only = false, carry_only = false, sticky_off = false;   // carry_only: the fp64 stage is rescore_carry_kernel alone
+    int pbits = 0, gbits = 0, end_bit = 0, L = 0;
+    int64_t P = 0, R = 0;                // motifs and regions: the largest key of the scan
+};
+// whether the key layout can be bucketed at all (any forced or unforced scan): d0 must lie inside the coordinate bits, and no hit key may
+// be all ones in the bits they sort -- the padding keys stand IN FRONT of later buckets' hits, and a stable sort would leave them there on a tie
+MS_HIDDEN bool bucket_layout_ok(const BucketShape &s);
+// the product's gate: every condition of the form, then the size -- the per-bucket slack must fit inside the prediction's own margin, that is
+// need <= n_pred.  MS_ORDER_BUCKETS=1 passes any size of a layout bucket_layout_ok() takes (the caller raises n_pred to the need); =0 never.
+MS_HIDDEN bool bucket_gate(const BucketShape &s, const ScanOverrides &ov, unsigned long long need, unsigned long long n_pred);
+
 // a buffer was too small: the counters hold the exact need -- the sizes of the next pass
 MS_HIDDEN void scan_grow(size_t cand_cap, size_t hit_cap, unsigned long long n_cand, unsigned long long n_hits, size_t *want_cand, size_t *want_hits);
 

@@ -490,8 +490,9 @@ int ms_seqset_repack(ms_seqset *s) {
     int rc = get_ctx(s->device, &c);
     if (rc) return rc;
     const hipStream_t up = c->stream_up;
+    // (the region hints stay as they are: a handle's offsets are written when it is created and never again, and blk2reg_kernel's output follows
+    // from them alone -- a set whose hints are still to be made, pack_pending, gets them from its first scan as before)
     if ((rc = launch_pack(s->d_ascii, s->n_bases, s->d_codes, s->d_nmask, up))) return rc;
-    if ((rc = launch_blk2reg(s->d_offsets, s->R, s->n_bases, s->d_blk2reg, s->d_blkinfo, up))) return rc;
     MS_HIP(hipStreamSynchronize(up));
     return MS_OK;
 }
