@@ -72,6 +72,9 @@
  *   ms_scan_alleles / ms_allelescan_*
  *                         the same for alleles of any length (multi-base, insertions, deletions): the windows of the ref and of the
  *                         spliced alt haplotype that the allele touches, each scored on its own haplotype
+ *   ms_scan_best / ms_best_*
+ *                         no reference counterpart: the maximum of cscore.c:336-390 over a region -- the best-scoring window of every
+ *                         (motif, region) cell, the dense score matrix behind "max motif score per peak"
  */
 #ifndef MOTIFSCAN_AMD_H
 #define MOTIFSCAN_AMD_H
@@ -374,6 +377,35 @@ int  ms_allelescan_ref_mismatch(const ms_allelescan *as, uint8_t *out /* [V] */)
 /* Device time of the call that made the result: upload of the variants -> last kernel done. */
 int  ms_allelescan_device_ms(const ms_allelescan *as, double *ms);
 void ms_allelescan_free(ms_allelescan *as);
+
+/* ---- the best-scoring window of every (motif, region) cell: the dense motif x region matrix (ms_best.hip) ---------- */
+/* For motif m of width W and region r of length L, over the window starts pos = 0 .. L - W and the strands of strand_mask: score(pos, strand)
+ * is the normalised score exactly as ms_scan computes it (cscore.c:336-390: columns in order, forward M[b][c], reverse M[3 - b][W - 1 - c]
+ * at the same step, a non-ACGT base adds nothing, raw / max_raw as an IEEE fp64 divide).  The BEST SITE of the cell is found by walking the
+ * windows in the reference's order -- pos ascending, '+' before '-' -- from best = -inf, a window replacing the best iff score > best: NaN
+ * and -inf never win, ties keep the earlier window.  Per cell: score (double), pos (int32, relative to the region start), strand (int8,
+ * 1 or 2).  A cell without a winner -- L < W, an -inf entry in every window -- holds score = NaN, pos = -1, strand = 0, and so does every
+ * cell of an UNSCORABLE motif: max_raw not a finite number > 0, or an entry that is NaN or +inf (the reference never reports a site of such
+ * a motif either).  Entries of -inf are ordinary: the window's raw sum is -inf and it never wins.  This is what ms_scan with a cutoff
+ * of -1e30 gives as the first hit of the greatest score per cell -- without making a hit per window.  The cutoffs of the PWM set are not read.
+ * The bytes of all three arrays are the same on every run.  The handle is bound to the sequence set's device.  There is no "handles on
+ * different devices" error: a PWM set is not bound to a device -- its device copies are made on, or moved to, the sequence set's device by
+ * the call, exactly as in ms_scan -- so no pair of handles can disagree.  Sets cut from a resident genome (ms_seqset_from_genome) are
+ * sequence sets like any other.  Work memory: a region of more than ms_debug_best_segment_windows() bases costs 16 bytes per (motif, segment)
+ * for the duration of the call (a 250 Mbase chromosome handed in as ONE region x 579 motifs: 4.5 GB), regions of one segment nothing.
+ * MS_ERR_INVALID: NULL handles, a strand mask outside 1..3, flags != 0, a region of 2^31 bases or more (pos is 32-bit).  MS_ERR_NOMEM: the
+ * 13 bytes per cell do not fit the device (nothing has been launched then).  n_seqs = 0 is valid and gives an empty result.  Without a
+ * device: MS_ERR_RUNTIME ("no CPU fallback") before anything else. */
+typedef struct ms_best ms_best;
+int  ms_scan_best(const ms_pwmset *pwms, const ms_seqset *seqs, int strand_mask, uint32_t flags /* 0 */, ms_best **out);
+int  ms_best_shape(const ms_best *b, int32_t *n_pwms, int64_t *n_seqs);
+/* Motifs m0 <= m < m1 into host buffers [(m1 - m0)][n_seqs] row-major; any pointer may be NULL.  MS_ERR_INVALID for m0 < 0, m1 > n_pwms, m0 > m1. */
+int  ms_best_sites(const ms_best *b, int32_t m0, int32_t m1, double *score, int32_t *pos, int8_t *strand);
+/* Device pointers of the full [n_pwms][n_seqs] arrays, valid until free (for a consumer that stays on the device); any pointer may be NULL. */
+int  ms_best_sites_device(const ms_best *b, void **d_score, void **d_pos, void **d_strand);
+/* Device time of the call that made the result: first launch -> last kernel done (HIP events on the library's stream). */
+int  ms_best_device_ms(const ms_best *b, double *ms);
+void ms_best_free(ms_best *b);
 
 /* The hit arrays in COMPACT form in library-owned pinned host memory: coord[i] = seq_idx << 32 | pos << 1 | (strand - 1),
  * score[i] -- 16 bytes per hit on the host link instead of 25.  Needs seq_idx < 2^32 and pos < 2^31 (MS_ERR_INVALID

@@ -61,6 +61,10 @@ int ms_debug_release_scratch(void);
  * The result of a scan does not depend on it: a test proves that with a chunk of a few variants.  Needs no GPU. */
 int ms_debug_varscan_chunk(int64_t n_variants, int64_t *previous);
 
+/* ms_scan_best cuts a region into segments of this many window starts (one wave each); a region of more than one segment goes through the
+ * per-segment partials and their reduction.  A constant of the build: a test sizes a region of more than two segments with it.  Needs no GPU. */
+int ms_debug_best_segment_windows(void);
+
 #ifdef __cplusplus
 }
 #endif

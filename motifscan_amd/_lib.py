@@ -183,6 +183,13 @@ def lib():
         "ms_allelescan_ref_mismatch": (c_int, [vp, pu8]),
         "ms_allelescan_device_ms": (c_int, [vp, pd]),
         "ms_allelescan_free": (None, [vp]),
+        "ms_scan_best": (c_int, [vp, vp, c_int, c_u32, pvp]),
+        "ms_best_shape": (c_int, [vp, pi32, pi64]),
+        "ms_best_sites": (c_int, [vp, c_i32, c_i32, pd, pi32, pi8]),
+        "ms_best_sites_device": (c_int, [vp, pvp, pvp, pvp]),
+        "ms_best_device_ms": (c_int, [vp, pd]),
+        "ms_best_free": (None, [vp]),
+        "ms_debug_best_segment_windows": (c_int, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1026,6 +1033,81 @@ class AlleleScan:
             self.h = None
 
     __del__ = close
+
+
+class BestSites:
+    """The result of one ms_scan_best call: the best-scoring window of every (motif, region) cell (include/motifscan_amd.h).
+    .score (float64), .pos (int32, relative to the region start) and .strand (int8: 1 '+', 2 '-') are (P, R) numpy arrays, copied from the
+    device the first time they are read; a cell without a winner holds NaN / -1 / 0.  The object owns the device arrays until close():
+    keep it alive while device_pointers() are in use."""
+
+    def __init__(self, handle):
+        self.h = handle
+        p, r = ctypes.c_int32(), ctypes.c_int64()
+        check(lib().ms_best_shape(self.h, ctypes.byref(p), ctypes.byref(r)))
+        self.n_pwms, self.n_seqs = p.value, r.value
+        self._full = None
+
+    @property
+    def shape(self):
+        return (self.n_pwms, self.n_seqs)
+
+    def sites(self, m0=0, m1=None):
+        """(score, pos, strand) of motifs m0 <= m < m1 as fresh (m1 - m0, R) arrays."""
+        if self.h is None:
+            raise ValueError("the result is closed")
+        m1 = self.n_pwms if m1 is None else int(m1)
+        m0 = int(m0)
+        if m0 < 0 or m1 > self.n_pwms or m0 > m1:
+            raise ValueError(f"motif range [{m0}, {m1}) outside [0, {self.n_pwms})")
+        shape = (m1 - m0, self.n_seqs)
+        score, pos, strand = np.zeros(shape, dtype=np.float64), np.zeros(shape, dtype=np.int32), np.zeros(shape, dtype=np.int8)
+        check(lib().ms_best_sites(self.h, m0, m1, ptr(score, ctypes.c_double), ptr(pos, ctypes.c_int32), ptr(strand, ctypes.c_int8)))
+        return score, pos, strand
+
+    def _arrays(self):
+        if self._full is None:
+            self._full = self.sites()
+        return self._full
+
+    score = property(lambda self: self._arrays()[0])
+    pos = property(lambda self: self._arrays()[1])
+    strand = property(lambda self: self._arrays()[2])
+
+    def device_pointers(self):
+        """(score, pos, strand) device addresses of the full (P, R) arrays, valid until close()."""
+        a, b, c = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        check(lib().ms_best_sites_device(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return a.value, b.value, c.value
+
+    def device_ms(self):
+        ms = ctypes.c_double()
+        check(lib().ms_best_device_ms(self.h, ctypes.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ms_best_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+
+def scan_best(pwms, seqs, strand_mask=3, flags=0):
+    """ms_scan_best: the best window of every (motif, region) cell of a PwmSet x SeqSet (the set's cutoffs are not read).  Returns a BestSites."""
+    strand_mask = int(strand_mask)
+    if strand_mask not in (1, 2, 3):
+        raise ValueError(f"invalid strand mask {strand_mask!r} (1 '+', 2 '-', 3 both)")
+    if int(flags) != 0:
+        raise ValueError(f"unknown best-site scan flags {flags!r}")
+    h = ctypes.c_void_p()
+    check(lib().ms_scan_best(pwms.h, seqs.h, strand_mask, int(flags), ctypes.byref(h)))
+    return BestSites(h)
+
+
+def best_segment_windows():
+    """ms_debug_best_segment_windows: window starts per segment of ms_scan_best (tests size a multi-segment region with it)."""
+    return int(lib().ms_debug_best_segment_windows())
 
 
 def _flatten_alleles(seqs):

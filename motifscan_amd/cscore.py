@@ -5,6 +5,8 @@ meaning and the same result shapes, computed on an MI355X through libmotifscan_a
 
     c_scan_motif(pwms, cutoffs, seqs, strand, n_threads) -> list[P] of list of [seq_idx, pos, score, strand]
     c_score(pwms, seqs, strand, n_threads)               -> list[P] of list[R] of float
+plus one function the reference does not have, in the same calling style:
+    c_best_site(pwms, seqs, strand, n_threads)           -> list[P] of list[R] of [pos, score, strand] or None
 
 `n_threads` is accepted for signature compatibility (cscore.c:404, 236) and ignored: the
 parallel axis on the GPU is windows x motifs, not a pthread queue over PWMs.
@@ -63,6 +65,36 @@ def c_score(pwms, seqs, strand, n_threads=1):
     sq = _lib.SeqSet.from_strings(seqs)
     try:
         return _lib.score(pw, sq, strand).tolist()
+    finally:
+        sq.close()
+        pw.close()
+
+
+def best_site_lists(score, pos, strand):
+    """(P, R) arrays of ms_scan_best -> list[P] of list[R] of [pos, score, strand], None for a cell without a winner (strand 0).
+    Pure host code."""
+    score, pos, strand = np.asarray(score), np.asarray(pos), np.asarray(strand)
+    if score.ndim != 2 or score.shape != pos.shape or score.shape != strand.shape:
+        raise ValueError("score, pos and strand must be (P, R) arrays of one shape")
+    out = []
+    for sc, ps, sd in zip(score.tolist(), pos.tolist(), strand.tolist()):
+        out.append([[p, s, d] if d else None for s, p, d in zip(sc, ps, sd)])
+    return out
+
+
+def c_best_site(pwms, seqs, strand, n_threads=1):
+    """The best-scoring window of every PWM in every sequence: the maximum of c_scan_motif's scores (cscore.c:336-390) over the
+    sequence, the first window in the reference's order (pos ascending, '+' before '-') on a tie.  list[P] of list[R] of
+    [pos, score, strand (1 / 2)], None where no window wins (a sequence shorter than the PWM, -inf in every window, an unscorable PWM)."""
+    strand = _check_strand(strand)
+    pw = _lib.PwmSet.from_matrices(pwms)
+    sq = _lib.SeqSet.from_strings(seqs)
+    try:
+        res = _lib.scan_best(pw, sq, strand)
+        try:
+            return best_site_lists(res.score, res.pos, res.strand)
+        finally:
+            res.close()
     finally:
         sq.close()
         pw.close()

@@ -1,7 +1,7 @@
 // ms_handles.h -- private to libmotifscan_amd: per-device state and the structs behind the opaque handles of
 // include/motifscan_amd.h, shared by the library's translation units: ms_context.hip (device contexts, pools), ms_pwmset.hip, ms_seqset.hip,
 // ms_result.hip (one per handle), ms_scan.hip (scan pipeline), ms_sweep.hip (window sweep), ms_regions.hip and ms_stream.hip (batch streams,
-// host-streamed sweeps).
+// host-streamed sweeps), ms_best.hip (best window per cell).
 #pragma once
 #include <sched.h>
 #include <atomic>
@@ -74,6 +74,7 @@ struct DeviceCtx {
     std::atomic<int> n_streams{0};           // live batch streams on this device
     size_t lds_max = 0;
     bool rc_lds_set = false;                // rescore_carry_kernel's dynamic-LDS attribute raised
+    bool best_lds_set = false;              // best_kernel's (ms_best.hip)
     size_t lds_set[3] = {};                 // dynamic-LDS attribute already raised to this, per pre-filter kernel (parked, dense, wide)
     Scratch sc;
     std::mutex mu;               // one scan at a time per device (shared scratch)
@@ -249,6 +250,18 @@ struct ms_result {
     int64_t h_pinned_hits = -1;
     std::vector<int64_t> h_region_counts;             // a batch stream's copy-out stage brings the per-motif region counts along (ms_result_region_counts then copies host to host)
     ms_scan_stats stats;
+};
+
+struct ms_best {                                      // ms_scan_best: the best window of every (motif, region) cell
+    int device = 0;
+    int32_t P = 0;
+    int64_t R = 0;
+    void *block = nullptr;                            // one pooled device block holding the three [P][R] arrays
+    size_t block_bytes = 0;
+    double *d_score = nullptr;                        // NaN: no winner
+    int32_t *d_pos = nullptr;                         // relative to the region start, -1: no winner
+    int8_t *d_strand = nullptr;                       // 1 '+', 2 '-', 0: no winner
+    double device_ms = 0.0;                           // first launch -> last kernel done
 };
 
 namespace ms {

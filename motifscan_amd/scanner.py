@@ -13,6 +13,8 @@ Same public surface and behaviour:
     deduplicate_motif_sites(motif_sites, lengths)        scanner.py:171-193
 plus, for inputs where n_pwms x n_regions Python lists are not an option:
     Scanner.scan_motifs_arrays(pwms) -> flat numpy arrays in the same order.
+and one question the reference cannot answer from its site lists:
+    Scanner.best_sites(pwms) -> BestSiteArrays: the best-scoring window of every (motif, region), cutoff or not.
 
 `genome` is any object with `chrom_sizes[chrom]` and `fetch_sequence(chrom, start, end)`;
 `regions` any objects with `.chrom .start .end .summit` -- i.e. the reference's own
@@ -43,6 +45,25 @@ class _Frozen(list):
         raise TypeError("a Scanner's regions are frozen after construction (its packed device copy is cached): build a new Scanner")
 
     __setitem__ = __delitem__ = __iadd__ = __imul__ = append = extend = insert = pop = remove = clear = sort = reverse = _refuse
+
+
+class BestSiteArrays:
+    """Scanner.best_sites: (n_pwms, n_regions) arrays -- score (float64, NaN where no window wins), start (int64, the window's start
+    in genome coordinates, -1 where none) and strand (int8: 1 '+', 2 '-', 0 where none: the library's strand flags, as
+    scan_motifs_arrays gives them)."""
+    __slots__ = ("score", "start", "strand")
+
+    def __init__(self, score, start, strand):
+        self.score, self.start, self.strand = score, start, strand
+
+
+def best_site_starts(pos, seq_starts):
+    """Positions relative to the region start (P, R; -1 = none) -> genome coordinates, -1 kept.  Pure host code."""
+    pos = np.asarray(pos)
+    starts = np.asarray(seq_starts, dtype=np.int64).reshape(1, -1)
+    if pos.ndim != 2 or pos.shape[1] != starts.shape[1]:
+        raise ValueError("pos must be (P, R) with one column per region")
+    return np.where(pos >= 0, pos.astype(np.int64) + starts, np.int64(-1))
 
 
 class Scanner:
@@ -302,6 +323,23 @@ class Scanner:
                 res.close()
         finally:
             pw.close()
+
+    def best_sites(self, pwms):
+        """The best-scoring window of every (motif, region) cell -- the dense matrix behind "max motif score per region", and how far
+        below its cutoff a region without a site stays -- as a BestSiteArrays.  Every window is scored as scan_motifs scores it; the
+        first window in the reference's order (start ascending, '+' before '-') keeps a tie.  Honours the scanner's `strand`;
+        `p_value` and `remove_dup` have no meaning here (no cutoff is read, one window per cell is reported)."""
+        matrices = [np.asarray(pwm.matrix, dtype=np.float64) for pwm in pwms]
+        pw = _lib.PwmSet.from_matrices(matrices)
+        try:
+            res = _lib.scan_best(pw, self._seqset(), _STRAND_FLAG[self.strand])
+            try:
+                score, pos, strand = res.sites()
+            finally:
+                res.close()
+        finally:
+            pw.close()
+        return BestSiteArrays(score, best_site_starts(pos, self.seq_starts), strand)
 
     def scan_motifs(self, pwms):
         """motif_sites[n_pwms][n_regions] -> list[MotifSite] (scanner.py:89-132), as a read-only nested view over the
