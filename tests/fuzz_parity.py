@@ -10,9 +10,23 @@ to sit ON the decision boundary of cscore.c:360-389 (`score / max_raw - cutoff >
   * sequences with N runs, lower case, other IUPAC letters, empty and shorter-than-W regions;
   * (round 6) every case also through MS_SCAN_COUNTS_ONLY and through a two-batch stream with the 12-byte copy-out.
 
+The same matrices, sequences and cutoffs feed four more families, one per entry point that judges windows with a decision of its own:
+
+  * --sweep     ms_scan_sweep: one chromosome, random window / stride, against the oracle over the windows as separate regions;
+  * --variants  ms_scan_variants: single-base substitutions (duplicates, any order, alt letters that add nothing) on a resident genome,
+                against the oracle over the ref and alt flank of every variant -- all-pass for the scores, the real cutoff for the states;
+  * --alleles   ms_scan_alleles: alleles of 0..40 bases incl. insertions behind the last base, REF strings on even seeds;
+  * --best      ms_scan_best: the first window of the greatest score per (motif, region), regions of up to three segments, run twice.
+
+Each of the last three is make_<x>_case(seed) (inputs), expected_<x>(oracle, case) (expected arrays and a tally; neither needs a GPU) and
+run_<x>_case(seed, oracle, _lib) (the device call, compared exactly: integers by value, scores by their bits).  Odd seeds of the variant
+and allele families run in chunks of 7 variants.  CONDITIONS holds what the seeds of a family must put on the boundary.
+
 It lives under tests/ because it uses the oracle (test infrastructure).  Run on the GPU box:
     python tests/fuzz_parity.py --cases 200 --seed 0
-`tests/test_gpu_parity.py::test_fuzz_decision_boundary` runs a few cases of it in the GPU suite.
+    python tests/fuzz_parity.py --variants --cases 30        (likewise --alleles, --best, --sweep; each prints its tallies)
+`tests/test_gpu_parity.py::test_fuzz_decision_boundary` runs a few cases of ms_scan's family in the GPU suite,
+tests/test_gpu_fuzz_entry_points.py the other four; tests/test_fuzz_cases_host.py checks the cases themselves without a GPU.
 """
 import argparse
 import os
@@ -223,9 +237,9 @@ def run_case(seed, oracle, _lib):
     return True, len(want["pos"]), st
 
 
-def run_sweep_case(seed, oracle, _lib):
-    """ms_scan_sweep (every base scored once, hits handed to the windows that hold them) vs the oracle over the same
-    windows as separate regions; random window / stride incl. stride > window and windows narrower than motifs."""
+def make_sweep_case(seed):
+    """The sweep family's inputs (no GPU): motifs, cutoffs on attainable scores, one chromosome, a span of it and window / stride
+    incl. stride > window and windows narrower than motifs; `seqs` are the windows as separate regions."""
     rng = np.random.default_rng(1_000_003 * 7 + seed)
     n_motifs = int(rng.choice([1, 3, 20, 60]))
     mats = [random_matrix(rng, int(rng.integers(1, 34))) for _ in range(n_motifs)]
@@ -247,11 +261,33 @@ def run_sweep_case(seed, oracle, _lib):
     seqs = [chrom[begin + k * stride: begin + k * stride + window] for k in range(n_win)]
     cutoffs = np.array([attainable_cutoff(rng, m, seqs[:50] + [chrom]) for m in mats], dtype=np.float64)
     strand = int(rng.integers(1, 4))
-    vals = np.concatenate([m.ravel() for m in mats])
-    widths = np.array([m.shape[1] for m in mats], dtype=np.int32)
-    raw = "".join(seqs).encode()
-    offsets = np.arange(n_win + 1, dtype=np.int64) * window
-    want = oracle.scan_arrays(vals, widths, cutoffs, raw, offsets, strand, 4)
+    return {"mats": mats, "cutoffs": cutoffs, "chrom": chrom, "begin": begin, "end": end, "window": window, "stride": stride,
+            "n_win": n_win, "seqs": seqs, "strand": strand}
+
+
+def expected_sweep(oracle, case):
+    """(flat matrix values, widths, the oracle's hits over the windows as separate regions); no GPU."""
+    vals = np.concatenate([m.ravel() for m in case["mats"]])
+    widths = np.array([m.shape[1] for m in case["mats"]], dtype=np.int32)
+    raw = "".join(case["seqs"]).encode()
+    offsets = np.arange(case["n_win"] + 1, dtype=np.int64) * case["window"]
+    return vals, widths, oracle.scan_arrays(vals, widths, case["cutoffs"], raw, offsets, case["strand"], 4)
+
+
+def sweep_tally(seed, oracle):
+    """What a sweep case holds, from the oracle alone: its number of windows, the sites to compare and its kinds of motif."""
+    case = make_sweep_case(seed)
+    want = expected_sweep(oracle, case)[2]
+    return {"n_win": case["n_win"], "sites": len(want["pos"]), "cases_without_windows": int(case["n_win"] == 0), **motif_kinds(case["mats"])}
+
+
+def run_sweep_case(seed, oracle, _lib):
+    """ms_scan_sweep (every base scored once, hits handed to the windows that hold them) vs the oracle over the same
+    windows as separate regions."""
+    case = make_sweep_case(seed)
+    mats, cutoffs, chrom, strand = case["mats"], case["cutoffs"], case["chrom"], case["strand"]
+    begin, end, window, stride, n_motifs = case["begin"], case["end"], case["window"], case["stride"], len(mats)
+    vals, widths, want = expected_sweep(oracle, case)
     genome = _lib.ResidentGenome({"x": "ACGT" * 3, "chr": chrom})
     pw = _lib.PwmSet(vals, widths, cutoffs)
     res = _lib.scan_sweep(pw, genome, "chr", begin, end, window, stride, strand)
@@ -273,18 +309,418 @@ def run_sweep_case(seed, oracle, _lib):
     return True, len(want["pos"])
 
 
+# ------------------------------------------------------------------------------------------------ variants, alleles, best sites
+#
+# Each family: make_<x>_case(seed) builds the inputs, expected_<x>(oracle, case) the expected arrays and a tally dict (neither uses a
+# GPU), run_<x>_case(seed, oracle, _lib) makes the device call.  Every comparison is exact: integers by value, scores by their bits.
+
+ALL_PASS = -1e30
+NEAR = 2e-10                                            # a scored window is "near" when its score is within this of the motif's cutoff
+ALT_LETTERS = "ACGTACGTNacgtR"
+VARIANT_STREAM, ALLELE_STREAM, BEST_STREAM = 2_000_003 * 11, 3_000_017 * 13, 5_000_011 * 17
+
+
+def motif_kinds(mats):
+    """How many of the motifs are of the kinds every family has to meet: max_raw == 0, 64 columns or more, one column."""
+    return {"max_raw_zero": sum(max_raw_of(m) == 0 for m in mats), "wide": sum(m.shape[1] >= 64 for m in mats),
+            "width_one": sum(m.shape[1] == 1 for m in mats)}
+
+
+def add_tally(total, tally):
+    """Sum a case's tally into a running one (numbers only)."""
+    for k, v in tally.items():
+        total[k] = total.get(k, 0) + int(v)
+    return total
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
+
+
+def random_motifs(rng, counts):
+    n_motifs = int(rng.choice(counts))
+    wmax = int(rng.choice([8, 16, 32, 40, 66]))
+    return [random_matrix(rng, int(rng.integers(1, wmax + 1))) for _ in range(n_motifs)]
+
+
+def random_chromosomes(rng):
+    chroms = [s for s in random_sequences(rng, int(rng.choice([2, 4, 8])), int(rng.choice([40, 150, 300]))) if s]
+    return chroms or ["ACGTTGCANacgtACGGT"]
+
+
+def score_tables(oracle, mat, cutoff, seqs, strand):
+    """The oracle twice over `seqs` for one motif: its scan at the all-pass cutoff gives score[N, 2] of every window x strand it reports
+    (NaN elsewhere), its scan at the real cutoff gives hit[N, 2] -- the reference's own line decides.  Windows are numbered sequence
+    after sequence, start ascending: woff[i] is the first window of sequence i."""
+    W = mat.shape[1]
+    nwin = np.maximum(np.array([len(s) for s in seqs], dtype=np.int64) - W + 1, 0)
+    woff = np.concatenate([[0], np.cumsum(nwin)])
+    vals, widths = oracle.flatten_pwms([mat])
+    bases, off = oracle.flatten_seqs(seqs)
+    score, hit = np.full((int(woff[-1]), 2), np.nan), np.zeros((int(woff[-1]), 2), dtype=bool)
+    r = oracle.scan_arrays(vals, widths, [ALL_PASS], bases, off, strand)
+    score[woff[r["seq_idx"]] + r["pos"], r["strand"] - 1] = r["score"]
+    r = oracle.scan_arrays(vals, widths, [cutoff], bases, off, strand)
+    hit[woff[r["seq_idx"]] + r["pos"], r["strand"] - 1] = True
+    assert not np.any(hit & np.isnan(score))
+    return nwin, woff, score, hit
+
+
+def near_tally(score, hit, cutoff):
+    near = np.abs(score - cutoff) <= NEAR                # (NaN compares false: a window the oracle does not score is not counted)
+    return {"near_pass": int((near & hit).sum()), "near_fail": int((near & ~hit).sum()), "pairs": int((~np.isnan(score)).sum())}
+
+
+# ---- ms_scan_variants
+
+def make_variants_case(seed):
+    rng = np.random.default_rng(VARIANT_STREAM + seed)
+    mats = random_motifs(rng, [1, 2, 5, 13, 40])
+    chroms = random_chromosomes(rng)
+    V = int(rng.choice([1, 30, 200, 400]))
+    chrom_idx = rng.integers(0, len(chroms), V).astype(np.int32)
+    lens = np.array([len(c) for c in chroms], dtype=np.int64)
+    pos = (rng.random(V) * lens[chrom_idx]).astype(np.int64)            # uniform on the chromosome: duplicates and any order occur
+    alt = "".join(rng.choice(list(ALT_LETTERS), size=V)).encode()
+    cutoffs = np.array([attainable_cutoff(rng, m, chroms) for m in mats], dtype=np.float64)
+    return {"mats": mats, "cutoffs": cutoffs, "chroms": chroms, "chrom_idx": chrom_idx, "pos": pos, "alt": alt,
+            "strand": int(rng.integers(1, 4))}
+
+
+def expected_variants(oracle, case):
+    """The records include/motifscan_amd.h describes for ms_scan_variants, from the oracle over Python-built flank strings
+    [max(0, x - W + 1), min(L, x + W)) of the ref and the alt allele."""
+    chroms, chrom_idx, pos, alt = case["chroms"], case["chrom_idx"], case["pos"], case["alt"].decode()
+    V = len(pos)
+    out = {k: [] for k in ("variant", "start", "strand", "score_ref", "score_alt", "state")}
+    offsets, gained, lost = [0], [], []
+    tally = {"records": 0, "near_pass": 0, "near_fail": 0, "pairs": 0, **motif_kinds(case["mats"])}
+    by_width = {}
+    for mat, cutoff in zip(case["mats"], case["cutoffs"]):
+        W = mat.shape[1]
+        if W not in by_width:
+            ref_seqs, alt_seqs, los = [], [], []
+            for v in range(V):
+                seq, x = chroms[chrom_idx[v]], int(pos[v])
+                lo, hi = max(0, x - W + 1), min(len(seq), x + W)
+                ref_seqs.append(seq[lo:hi])
+                alt_seqs.append(seq[lo:x] + alt[v] + seq[x + 1:hi])
+                los.append(lo)
+            by_width[W] = (ref_seqs + alt_seqs, np.array(los, dtype=np.int64))
+        seqs, los = by_width[W]
+        nwin, woff, score, hit = score_tables(oracle, mat, cutoff, seqs, case["strand"])
+        n = int(woff[V])
+        assert int(woff[-1]) == 2 * n
+        add_tally(tally, near_tally(score, hit, cutoff))
+        state = hit[:n].astype(np.uint8) | (hit[n:].astype(np.uint8) << 1)
+        keep = state.ravel() != 0                                        # window-major, '+' before '-'
+        variant = np.repeat(np.arange(V, dtype=np.int64), nwin[:V])
+        start = np.repeat(los, nwin[:V]) + (np.arange(n) - np.repeat(woff[:V], nwin[:V]))
+        out["variant"].append(np.repeat(variant, 2)[keep])
+        out["start"].append(np.repeat(start, 2)[keep])
+        out["strand"].append(np.tile(np.array([1, 2], dtype=np.int8), n)[keep])
+        out["score_ref"].append(score[:n].ravel()[keep])
+        out["score_alt"].append(score[n:].ravel()[keep])
+        out["state"].append(state.ravel()[keep])
+        offsets.append(offsets[-1] + int(keep.sum()))
+        gained.append(np.unique(out["variant"][-1][out["state"][-1] == 2]).size)
+        lost.append(np.unique(out["variant"][-1][out["state"][-1] == 1]).size)
+    want = {k: np.concatenate(v) for k, v in out.items()}
+    want["motif_offsets"] = np.array(offsets, dtype=np.int64)
+    want["gained"], want["lost"] = np.array(gained, dtype=np.int64), np.array(lost, dtype=np.int64)
+    want["ref_codes"] = np.array([oracle.convert_seq(chroms[c][int(x)].encode())[0] for c, x in zip(chrom_idx, pos)], dtype=np.int8)
+    tally["records"] = offsets[-1]
+    for s in (1, 2, 3):
+        tally[f"state_{s}"] = int((want["state"] == s).sum())
+    return want, tally
+
+
+def chunked(seed, _lib, call):
+    """Odd seeds run with 7 variants per chunk (ms_debug_varscan_chunk): the result must not depend on the chunk size."""
+    if seed % 2 == 0:
+        return call()
+    prev = _lib.varscan_chunk(7)
+    try:
+        return call()
+    finally:
+        _lib.varscan_chunk(prev)
+
+
+def run_variants_case(seed, oracle, _lib):
+    case = make_variants_case(seed)
+    want, tally = expected_variants(oracle, case)
+    genome = _lib.ResidentGenome({f"c{i}": c for i, c in enumerate(case["chroms"])})
+    pw = _lib.PwmSet.from_matrices(case["mats"], case["cutoffs"])
+    try:
+        res = chunked(seed, _lib, lambda: _lib.scan_variants(pw, genome, case["chrom_idx"], case["pos"], case["alt"], case["strand"]))
+        try:
+            got = res.sites()
+            got["gained"], got["lost"] = res.motif_counts()
+            got["ref_codes"] = res.ref_codes()
+        finally:
+            res.close()
+    finally:
+        pw.close()
+        genome.close()
+    for k in ("motif_offsets", "variant", "start", "strand", "state", "gained", "lost", "ref_codes"):
+        if not np.array_equal(got[k], want[k]):
+            return False, f"variants seed {seed}: {k} differs ({len(got['state'])} vs {len(want['state'])} records)"
+    for k in ("score_ref", "score_alt"):
+        if not same_bits(got[k], want[k]):
+            return False, f"variants seed {seed}: the bits of {k} differ"
+    return True, tally
+
+
+# ---- ms_scan_alleles
+
+def allele_flanks(seq, x, r, alt, W):
+    """(lo, ref flank, alt flank): the pieces of the two haplotypes whose windows of width W are exactly the affected ones."""
+    lo, hi = max(0, x - W + 1), min(len(seq), x + r + W - 1)
+    return lo, seq[lo:hi], seq[lo:x] + alt + seq[x + r:hi]
+
+
+def make_alleles_case(seed):
+    rng = np.random.default_rng(ALLELE_STREAM + seed)
+    mats = random_motifs(rng, [1, 2, 5, 13, 40])
+    chroms = random_chromosomes(rng)
+    V = int(rng.choice([1, 30, 200]))
+    chrom_idx = rng.integers(0, len(chroms), V).astype(np.int32)
+    pos, ref_len, alts = np.zeros(V, dtype=np.int64), np.zeros(V, dtype=np.int32), []
+    for v in range(V):
+        L = len(chroms[chrom_idx[v]])
+        hi = 41 if rng.random() < 0.1 else 4
+        r, a = int(rng.integers(0, hi)), int(rng.integers(0, hi))
+        r = min(r, L)
+        if r + a == 0:
+            a = 1
+        pos[v], ref_len[v] = int(rng.integers(0, L - r + 1)), r            # x = L occurs for pure insertions
+        alts.append("".join(rng.choice(list(ALT_LETTERS), size=a)))
+    cutoffs = np.array([attainable_cutoff(rng, m, chroms) for m in mats], dtype=np.float64)
+    strand = int(rng.integers(1, 4))
+    refs = None
+    if seed % 2 == 0:                                   # REF strings: half as the genome has them, half with one letter changed
+        refs = []
+        for v in range(V):
+            x, r = int(pos[v]), int(ref_len[v])
+            ref = chroms[chrom_idx[v]][x:x + r]
+            if r and rng.random() < 0.5:
+                k = int(rng.integers(0, r))
+                other = [c for c in "ACGTN" if "ACGT".find(c) != "ACGT".find(ref[k].upper())]
+                ref = ref[:k] + other[int(rng.integers(0, len(other)))] + ref[k + 1:]
+            refs.append(ref)
+    return {"mats": mats, "cutoffs": cutoffs, "chroms": chroms, "chrom_idx": chrom_idx, "pos": pos, "ref_len": ref_len, "alts": alts,
+            "refs": refs, "strand": strand}
+
+
+def expected_alleles(oracle, case):
+    """The records include/motifscan_amd.h describes for ms_scan_alleles, from the oracle over the Python-built flanks of the two
+    haplotypes; gained / lost classify variants (records on one haplotype only)."""
+    chroms, chrom_idx, pos, ref_len, alts = case["chroms"], case["chrom_idx"], case["pos"], case["ref_len"], case["alts"]
+    V = len(pos)
+    out = {k: [] for k in ("variant", "allele", "start", "strand", "score")}
+    offsets, gained, lost = [0], [], []
+    tally = {"records": 0, "near_pass": 0, "near_fail": 0, "pairs": 0, **motif_kinds(case["mats"])}
+    by_width = {}
+    for mat, cutoff in zip(case["mats"], case["cutoffs"]):
+        W = mat.shape[1]
+        if W not in by_width:
+            seqs, los = [], []
+            for v in range(V):
+                lo, fr, fa = allele_flanks(chroms[chrom_idx[v]], int(pos[v]), int(ref_len[v]), alts[v], W)
+                seqs += [fr, fa]                                             # variant, then allele (ref first): the order of the records
+                los += [lo, lo]
+            by_width[W] = (seqs, np.array(los, dtype=np.int64))
+        seqs, los = by_width[W]
+        nwin, woff, score, hit = score_tables(oracle, mat, cutoff, seqs, case["strand"])
+        add_tally(tally, near_tally(score, hit, cutoff))
+        n = int(woff[-1])
+        keep = hit.ravel()                                                   # window-major, '+' before '-'
+        seq_of = np.repeat(np.arange(2 * V, dtype=np.int64), nwin)
+        start = np.repeat(los, nwin) + (np.arange(n) - np.repeat(woff[:-1], nwin))
+        out["variant"].append(np.repeat(seq_of // 2, 2)[keep])
+        out["allele"].append(np.repeat(seq_of % 2, 2)[keep].astype(np.uint8))
+        out["start"].append(np.repeat(start, 2)[keep])
+        out["strand"].append(np.tile(np.array([1, 2], dtype=np.int8), n)[keep])
+        out["score"].append(score.ravel()[keep])
+        offsets.append(offsets[-1] + int(keep.sum()))
+        has = np.zeros((V, 2), dtype=bool)
+        has[out["variant"][-1], out["allele"][-1]] = True
+        gained.append(int((has[:, 1] & ~has[:, 0]).sum()))
+        lost.append(int((has[:, 0] & ~has[:, 1]).sum()))
+    want = {k: np.concatenate(v) for k, v in out.items()}
+    want["motif_offsets"] = np.array(offsets, dtype=np.int64)
+    want["gained"], want["lost"] = np.array(gained, dtype=np.int64), np.array(lost, dtype=np.int64)
+    mismatch = np.zeros(V, dtype=bool)
+    if case["refs"] is not None:                        # case is ignored; a non-ACGT genome base matches any letter that is not ACGT
+        for v in range(V):
+            x, r = int(pos[v]), int(ref_len[v])
+            mismatch[v] = not np.array_equal(oracle.convert_seq(chroms[chrom_idx[v]][x:x + r].encode()), oracle.convert_seq(case["refs"][v].encode()))
+    want["ref_mismatch"] = mismatch
+    tally.update(records=offsets[-1], gained=int(sum(gained)), lost=int(sum(lost)), ref_mismatches=int(mismatch.sum()),
+                 at_chrom_end=int(sum(int(pos[v]) == len(chroms[chrom_idx[v]]) for v in range(V))))
+    return want, tally
+
+
+def run_alleles_case(seed, oracle, _lib):
+    case = make_alleles_case(seed)
+    want, tally = expected_alleles(oracle, case)
+    genome = _lib.ResidentGenome({f"c{i}": c for i, c in enumerate(case["chroms"])})
+    pw = _lib.PwmSet.from_matrices(case["mats"], case["cutoffs"])
+    try:
+        res = chunked(seed, _lib, lambda: _lib.scan_alleles(pw, genome, case["chrom_idx"], case["pos"], case["ref_len"], case["alts"],
+                                                            refs=case["refs"], strand_mask=case["strand"]))
+        try:
+            got = res.sites()
+            got["gained"], got["lost"] = res.motif_counts()
+            got["ref_mismatch"] = res.ref_mismatch()
+        finally:
+            res.close()
+    finally:
+        pw.close()
+        genome.close()
+    for k in ("motif_offsets", "variant", "allele", "start", "strand", "gained", "lost", "ref_mismatch"):
+        if not np.array_equal(got[k], want[k]):
+            return False, f"alleles seed {seed}: {k} differs ({len(got['score'])} vs {len(want['score'])} records)"
+    if not same_bits(got["score"], want["score"]):
+        return False, f"alleles seed {seed}: the bits of score differ"
+    return True, tally
+
+
+# ---- ms_scan_best
+
+def oracle_best(oracle, mats, seqs, strand_mask, segment_windows=None, tally=None):
+    """Per cell the greatest score of the oracle's all-pass scan and the FIRST hit that reaches it (the oracle lists a cell's hits pos
+    ascending, '+' before '-'); NaN / -1 / 0 where the oracle reports nothing.  With a dict as `tally`, the cells whose greatest score
+    more than one (window, strand) reaches are counted into it, and those whose tied windows start in different segments of
+    `segment_windows` window starts."""
+    vals, widths = oracle.flatten_pwms(mats)
+    bases, off = oracle.flatten_seqs(seqs)
+    P, R = len(mats), len(seqs)
+    r = oracle.scan_arrays(vals, widths, np.full(P, ALL_PASS), bases, off, strand_mask)
+    score = np.full((P, R), np.nan)
+    pos = np.full((P, R), -1, dtype=np.int32)
+    strand = np.zeros((P, R), dtype=np.int8)
+    for m in range(P):
+        a, b = int(r["motif_offsets"][m]), int(r["motif_offsets"][m + 1])
+        if a == b:
+            continue
+        seq, sc = r["seq_idx"][a:b], r["score"][a:b]
+        assert np.all(np.diff(seq) >= 0)
+        first = np.concatenate([[0], np.flatnonzero(np.diff(seq)) + 1])
+        counts = np.diff(np.concatenate([first, [b - a]]))
+        best = np.maximum.reduceat(sc, first)
+        at_best = sc == np.repeat(best, counts)
+        at = np.minimum.reduceat(np.where(at_best, np.arange(b - a), b - a), first)
+        cells = seq[first]
+        score[m, cells], pos[m, cells], strand[m, cells] = sc[at], r["pos"][a:b][at], r["strand"][a:b][at]
+        if tally is not None:
+            tied = np.add.reduceat(at_best.astype(np.int64), first) > 1
+            tally["tied_cells"] = tally.get("tied_cells", 0) + int(tied.sum())
+            if segment_windows:
+                last = np.maximum.reduceat(np.where(at_best, r["pos"][a:b], -1), first)
+                across = tied & (last // segment_windows != r["pos"][a:b][at] // segment_windows)
+                tally["tied_across_segments"] = tally.get("tied_across_segments", 0) + int(across.sum())
+    return score, pos, strand
+
+
+def make_best_case(seed):
+    rng = np.random.default_rng(BEST_STREAM + seed)
+    mats = random_motifs(rng, [1, 2, 5, 13, 40, 97])
+    seqs = random_sequences(rng, int(rng.choice([1, 7, 60])), int(rng.choice([20, 150, 700, 1300])))     # 1300: regions of three segments
+    return {"mats": mats, "seqs": seqs, "strand": int(rng.integers(1, 4))}
+
+
+def expected_best(oracle, case, segment_windows):
+    tally = {"cells": len(case["mats"]) * len(case["seqs"]), "tied_cells": 0, "tied_across_segments": 0, **motif_kinds(case["mats"])}
+    want = oracle_best(oracle, case["mats"], case["seqs"], case["strand"], segment_windows, tally)
+    tally["winners"] = int((want[1] >= 0).sum())
+    tally["pairs"] = sum(max(len(s) - m.shape[1] + 1, 0) for m in case["mats"] for s in case["seqs"]) * bin(case["strand"]).count("1")
+    return want, tally
+
+
+def same_best(got, want):
+    """None, or what differs: positions and strands by value, scores by their bits with the NaN cells compared apart."""
+    (gs, gp, gd), (ws, wp, wd) = got, want
+    if gs.dtype != np.float64 or gp.dtype != np.int32 or gd.dtype != np.int8 or gs.shape != ws.shape:
+        return "dtypes or shapes"
+    if not np.array_equal(gp, wp):
+        return "pos"
+    if not np.array_equal(gd, wd):
+        return "strand"
+    if not np.array_equal(np.isnan(gs), np.isnan(ws)):
+        return "the cells without a winner"
+    if not np.array_equal(gs.view(np.int64)[~np.isnan(ws)], ws.view(np.int64)[~np.isnan(ws)]):
+        return "the bits of score"
+    if not (np.all(gp[np.isnan(gs)] == -1) and np.all(gd[np.isnan(gs)] == 0)):
+        return "pos / strand of the cells without a winner"
+    return None
+
+
+def run_best_case(seed, oracle, _lib):
+    case = make_best_case(seed)
+    want, tally = expected_best(oracle, case, _lib.best_segment_windows())
+    pw, sq = _lib.PwmSet.from_matrices(case["mats"]), _lib.SeqSet.from_strings(case["seqs"])
+    try:
+        runs = []
+        for _ in range(2):                              # twice: the bytes are the same on every run
+            res = _lib.scan_best(pw, sq, case["strand"])
+            try:
+                runs.append(res.sites())
+            finally:
+                res.close()
+    finally:
+        sq.close()
+        pw.close()
+    if runs[0][0].shape != (len(case["mats"]), len(case["seqs"])):
+        return False, f"best seed {seed}: shape {runs[0][0].shape}"
+    bad = same_best(runs[0], want)
+    if bad:
+        return False, f"best seed {seed}: {bad} differ"
+    if any(a.tobytes() != b.tobytes() for a, b in zip(*runs)):
+        return False, f"best seed {seed}: two runs give different bytes"
+    return True, tally
+
+
+FAMILIES = {"variants": run_variants_case, "alleles": run_alleles_case, "best": run_best_case}
+
+# What the seeds of a family must put on the boundary, summed over SEEDS[family] from the oracle's output alone: conditions, not
+# measurements.  If a change to a generator misses one, the seed range changes -- not the threshold, not the mix of matrix kinds.
+SEEDS = {"variants": range(30), "alleles": range(30), "best": range(30), "sweep": range(40)}
+CONDITIONS = {"variants": {"near_fail": 10_000, "near_pass": 10_000, "records": 100_000},
+              "alleles": {"near_fail": 5_000, "near_pass": 5_000, "gained": 500, "lost": 500},
+              "best": {"tied_cells": 1_000, "tied_across_segments": 300},
+              "sweep": {"sites": 100_000}}
+SWEEP_MAX_EMPTY = 10                                    # at most this many of the sweep cases may have no window at all
+
+
+def unmet_conditions(family, total):
+    """The conditions a family's summed tally misses, as text (empty: all met).  Every family must also meet a motif with max_raw == 0
+    and one of a single column, and -- but for the sweep, whose generator draws 1 .. 33 columns -- one of 64 columns or more."""
+    need = dict(CONDITIONS[family], max_raw_zero=1, width_one=1)
+    if family != "sweep":
+        need["wide"] = 1
+    bad = [f"{k}: {total.get(k, 0)} < {n}" for k, n in need.items() if total.get(k, 0) < n]
+    if family == "sweep" and total.get("cases_without_windows", 0) > SWEEP_MAX_EMPTY:
+        bad.append(f"cases_without_windows: {total['cases_without_windows']} > {SWEEP_MAX_EMPTY}")
+    return bad
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--sweep", action="store_true", help="fuzz ms_scan_sweep instead of ms_scan")
+    ap.add_argument("--variants", action="store_true", help="fuzz ms_scan_variants instead of ms_scan")
+    ap.add_argument("--alleles", action="store_true", help="fuzz ms_scan_alleles instead of ms_scan")
+    ap.add_argument("--best", action="store_true", help="fuzz ms_scan_best instead of ms_scan")
     a = ap.parse_args()
     from oracle import oracle
     oracle.build()
     from motifscan_amd import _lib
     _lib.set_device(0)
     if a.sweep:
-        bad, total = 0, 0
+        bad, total, tally = 0, 0, {}
         for k in range(a.cases):
             ok, info = run_sweep_case(a.seed + k, oracle, _lib)
             if not ok:
@@ -292,8 +728,21 @@ def main():
                 print("MISMATCH", info, flush=True)
             else:
                 total += info
-        print(f"sweep fuzz: {a.cases} cases from seed {a.seed}: {bad} mismatches, {total} sites compared")
+            add_tally(tally, sweep_tally(a.seed + k, oracle))
+        print(f"sweep fuzz: {a.cases} cases from seed {a.seed}: {bad} mismatches, {total} sites compared; tallies {tally}")
         return 1 if bad else 0
+    for name, run in FAMILIES.items():
+        if getattr(a, name):
+            bad, tally = 0, {}
+            for k in range(a.cases):
+                ok, info = run(a.seed + k, oracle, _lib)
+                if not ok:
+                    bad += 1
+                    print("MISMATCH", info, flush=True)
+                else:
+                    add_tally(tally, info)
+            print(f"{name} fuzz: {a.cases} cases from seed {a.seed}: {bad} mismatches; tallies {tally}")
+            return 1 if bad else 0
     bad, total_hits, fast, exact = 0, 0, 0, 0
     for k in range(a.cases):
         ok, info, st = run_case(a.seed + k, oracle, _lib)

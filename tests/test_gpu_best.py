@@ -16,11 +16,11 @@ import ctypes
 import numpy as np
 import pytest
 
+from fuzz_parity import oracle_best
 from motifscan_amd import _lib, cscore, scanner
 
 pytestmark = pytest.mark.gpu
 
-ALL_PASS = -1e30
 WIDTHS = (1, 4, 6, 19, 32, 33, 64, 65, 70)
 
 
@@ -41,31 +41,6 @@ def seeded_matrix(width, seed):
 
 def random_dna(rng, n):
     return np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, n)].tobytes().decode()
-
-
-def oracle_best(oracle, mats, seqs, strand_mask):
-    """Per cell the greatest score of the oracle's all-pass scan and the FIRST hit that reaches it (the oracle lists a cell's hits pos
-    ascending, '+' before '-'); NaN / -1 / 0 where the oracle reports nothing."""
-    vals, widths = oracle.flatten_pwms(mats)
-    bases, off = oracle.flatten_seqs(seqs)
-    P, R = len(mats), len(seqs)
-    r = oracle.scan_arrays(vals, widths, np.full(P, ALL_PASS), bases, off, strand_mask)
-    score = np.full((P, R), np.nan)
-    pos = np.full((P, R), -1, dtype=np.int32)
-    strand = np.zeros((P, R), dtype=np.int8)
-    for m in range(P):
-        a, b = int(r["motif_offsets"][m]), int(r["motif_offsets"][m + 1])
-        if a == b:
-            continue
-        seq, sc = r["seq_idx"][a:b], r["score"][a:b]
-        assert np.all(np.diff(seq) >= 0)
-        first = np.concatenate([[0], np.flatnonzero(np.diff(seq)) + 1])
-        counts = np.diff(np.concatenate([first, [b - a]]))
-        best = np.maximum.reduceat(sc, first)
-        at = np.minimum.reduceat(np.where(sc == np.repeat(best, counts), np.arange(b - a), b - a), first)
-        cells = seq[first]
-        score[m, cells], pos[m, cells], strand[m, cells] = sc[at], r["pos"][a:b][at], r["strand"][a:b][at]
-    return score, pos, strand
 
 
 def python_best(mat, seq, strand_mask):
@@ -188,6 +163,19 @@ def test_ties_keep_the_first_window_and_plus(oracle):
         assert np.all(got[1][:, 1] < len(unit)) and np.all(got[1][:, 4] < len(unit))       # a repeat: the winner lies in the first unit
         if strand_mask == 3:
             assert np.all(got[2][2] == 1)                                                  # the palindrome: '+' wins the strand tie
+
+
+def test_ties_across_more_than_a_wave_of_segments(oracle):
+    """Regions of more than 64 segments: a lane of best_reduce_kernel folds several partials, in segment order, before the wave is
+    reduced.  Poly-A and a short repeat tie in every segment; the first window keeps the cell, as the oracle has it."""
+    seg = _lib.best_segment_windows()
+    mats = [seeded_matrix(5, 11), seeded_matrix(9, 12)]
+    unit = "ACGGTCA"
+    seqs = ["A" * (65 * seg + 40), (unit * (130 * seg // len(unit) + 1))[:129 * seg + 3], unit * 3]
+    for strand_mask in (1, 3):
+        got = run_best(mats, seqs, strand_mask)
+        assert_same(got, oracle_best(oracle, mats, seqs, strand_mask))
+        assert np.all(got[1][:, 0] == 0) and np.all(got[1][:, 1] < len(unit))
 
 
 # ------------------------------------------------------------------------------------------------ 3. against the scan, moderate size

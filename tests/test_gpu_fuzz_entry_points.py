@@ -1,0 +1,43 @@
+"""
+The boundary fuzz of tests/fuzz_parity.py on the four entry points beside ms_scan that judge windows -- ms_scan_variants (ms_variants.hip),
+ms_scan_alleles (ms_alleles.hip), ms_scan_best (ms_best.hip) and ms_scan_sweep (ms_sweep.hip) -- against the pinned oracle: tie-rich
+matrices, cutoffs on attainable scores and one ulp / 1e-10 either side, huge and tiny magnitudes, max_raw == 0, N runs and lower case.
+Every comparison is exact (integers by value, scores by their bits).  After its seeds each test asserts, on the tallies of what was
+compared, that the seeds did sit on the boundary (fuzz_parity.CONDITIONS); tests/test_fuzz_cases_host.py asserts the same without a GPU.
+"""
+import pytest
+
+import fuzz_parity
+from motifscan_amd import _lib
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _device():
+    if _lib.device_count() < 1:
+        pytest.fail("no HIP device visible")
+    _lib.set_device(0)
+
+
+@pytest.mark.parametrize("family", ["variants", "alleles", "best"])
+def test_fuzz_entry_point(oracle, family):
+    total = {}
+    for seed in fuzz_parity.SEEDS[family]:
+        ok, info = fuzz_parity.FAMILIES[family](seed, oracle, _lib)
+        assert ok, info
+        fuzz_parity.add_tally(total, info)
+    print(f"{family}: seeds {fuzz_parity.SEEDS[family]}: {total}")
+    assert not fuzz_parity.unmet_conditions(family, total)
+
+
+def test_fuzz_sweep(oracle):
+    total = {}
+    for seed in fuzz_parity.SEEDS["sweep"]:
+        ok, info = fuzz_parity.run_sweep_case(seed, oracle, _lib)
+        assert ok, info
+        tally = fuzz_parity.sweep_tally(seed, oracle)
+        assert tally["sites"] == info
+        fuzz_parity.add_tally(total, tally)
+    print(f"sweep: seeds {fuzz_parity.SEEDS['sweep']}: {total}")
+    assert not fuzz_parity.unmet_conditions("sweep", total)
