@@ -75,6 +75,10 @@
  *   ms_scan_best / ms_best_*
  *                         no reference counterpart: the maximum of cscore.c:336-390 over a region -- the best-scoring window of every
  *                         (motif, region) cell, the dense score matrix behind "max motif score per peak"
+ *   ms_result_cooccurrence    no reference counterpart: the motif x motif matrix of "regions that hold a site of both", reduced on the
+ *                         device from the hit arrays a result holds (has-site bit rows, a tiled popcount product)
+ *   ms_result_pair_spacing    no reference counterpart: for one anchor motif against every partner motif, the histogram of the
+ *                         centre-to-centre distances of their sites in the same region by relative orientation (SpaMo-style spacing)
  */
 #ifndef MOTIFSCAN_AMD_H
 #define MOTIFSCAN_AMD_H
@@ -526,6 +530,36 @@ int ms_result_site_histogram(const ms_result *res, const ms_pwmset *pwms, const 
  * there) and on a counts-only result. */
 int ms_result_rank_profile(const ms_result *res, const int64_t *rank_order, const double *ratio_control, const double *kernel, int32_t m0,
                            int32_t m1, int flags, double *out);
+
+/* ---- motif pairs: co-occurrence and anchor spacing over a result's hit arrays (ms_pairs.hip) -------------- */
+/* Both read the result's sites as they are (de-duplicated or not, like ms_result_site_histogram), are synchronous, exact integer
+ * reductions -- the same bytes on every run -- and additive over shards of the regions (one all-reduce(sum) across ranks).  Both do
+ * nothing and return MS_OK for an empty motif range (m0 == m1), and fail with MS_ERR_INVALID on a counts-only result, as the other hit
+ * accessors.
+ *
+ * out[a][j], a = 0 .. m1 - m0 - 1, j = 0 .. P - 1: the number of regions of the result that hold at least one site of motif m0 + a AND at
+ * least one site of motif j.  out[a][m0 + a] is motif m0 + a's ms_result_region_counts value; the full matrix (m0 = 0, m1 = P) is
+ * symmetric; a motif without sites has a zero row and a zero column.  out: [(m1 - m0) x P] int64, host memory or device memory of the
+ * result's device (then a consumer can all-reduce it where it is).  The library writes a device `out` on its own stream: work the caller
+ * has queued on that memory on another stream (a fill, a collective) must have finished before the call; the call returns after its own
+ * writes are done.
+ * MS_ERR_INVALID: NULL handle or output, a motif range outside [0, P], R >= 2^31, output on another device. */
+int ms_result_cooccurrence(const ms_result *res, int32_t m0, int32_t m1, int64_t *out /* [(m1 - m0)][P] */);
+/* Anchor motif a = `anchor` (width Wa) against the partner motifs j = m0 + row (width Wj), row = 0 .. m1 - m0 - 1.  An ordered PAIR is a
+ * site s of a and a site t of j in the same region.  For j == a a site is not paired with itself, but with every other site of a -- its
+ * other-strand twin at the same position included -- so both (s, t) and (t, s) are pairs.  Per pair, in half base pairs,
+ * t2 = 2 * (pos_t - pos_s) + Wj - Wa is the distance from the anchor site's centre to the partner site's (its parity is that of Wj - Wa);
+ * the pair is counted iff |t2| <= 2 * max_dist, in bin (t2 + 2 * max_dist) >> 1 of 2 * max_dist + 1 (for an odd Wj - Wa the last bin stays
+ * 0) and orientation o = 2 * (strand_s - 1) + (strand_t - 1): 0 '+/+', 1 '+/-', 2 '-/+', 3 '-/-' (anchor first).  Nothing is
+ * reflected for an anchor on the '-' strand: the caller folds (t2 -> -t2, both strands flipped; motifscan_amd/pairs.py).
+ * counts[row][o][bin] = the number of such pairs; n_pairs[row] = ALL ordered pairs of the row in the same region, whatever their
+ * distance: sum over the regions of n_a(region) * n_j(region), minus n_a for j == a.  Both host memory.
+ * The sites of the anchor and of the partner motifs must be in scan order -- per motif by region, then position -- which every scan
+ * result is; a result made by ms_result_from_hits of arrays that are not is refused (checked on the device, outputs zeroed).
+ * MS_ERR_INVALID: NULL handles or outputs, pwms->P != the result's P, anchor outside [0, P), a motif range outside [0, P], max_dist < 0 or
+ * > 2^20, (m1 - m0) * 4 * (2 * max_dist + 1) > 2^31, sites out of order. */
+int ms_result_pair_spacing(const ms_result *res, const ms_pwmset *pwms, int32_t anchor, int32_t m0, int32_t m1, int32_t max_dist,
+                           int64_t *counts /* [(m1 - m0)][4][2 * max_dist + 1] */, int64_t *n_pairs /* [m1 - m0] */);
 
 #ifdef __cplusplus
 }

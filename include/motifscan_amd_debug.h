@@ -65,6 +65,18 @@ int ms_debug_varscan_chunk(int64_t n_variants, int64_t *previous);
  * per-segment partials and their reduction.  A constant of the build: a test sizes a region of more than two segments with it.  Needs no GPU. */
 int ms_debug_best_segment_windows(void);
 
+/* ms_result_pair_spacing bins into an LDS histogram while 2 * max_dist + 1 is at most this, and adds to global memory directly above it.
+ * A constant of the build: a test sits on both sides of it.  Needs no GPU. */
+int ms_debug_pair_lds_bins(void);
+/* ms_result_cooccurrence walks the regions in steps of this many (one LDS stage of bit words); a result of more regions than one step
+ * may have its word range cut across blocks, whose partial sums are added atomically.  A constant of the build.  Needs no GPU. */
+int ms_debug_cooc_chunk_regions(void);
+/* A block of ms_result_pair_spacing uses its LDS histogram only while (partner hits) x (anchor hits of the block) <= this limit, so that
+ * no 32-bit counter can overflow; above it the block adds to global memory.  The library's own limit is 2^32 - 1 (more than 4M partner
+ * hits); limit > 0 sets it for the calls that follow in this process, so that a small case reaches the fallback, 0 gives it back to the
+ * library.  *previous (may be NULL) = the value before.  The result does not depend on it.  Needs no GPU. */
+int ms_debug_pair_lds_pair_limit(int64_t limit, int64_t *previous);
+
 #ifdef __cplusplus
 }
 #endif

@@ -156,6 +156,11 @@ def lib():
         "ms_result_from_hits": (c_int, [c_i32, c_i64, pi64, pi64, pi64, pd, pi8, pvp]),
         "ms_result_site_histogram": (c_int, [vp, vp, pi64, c_i64, c_i32, c_i32, pi64, pi64]),
         "ms_result_rank_profile": (c_int, [vp, pi64, pd, pd, c_i32, c_i32, c_int, vp]),
+        "ms_result_cooccurrence": (c_int, [vp, c_i32, c_i32, vp]),
+        "ms_result_pair_spacing": (c_int, [vp, vp, c_i32, c_i32, c_i32, c_i32, pi64, pi64]),
+        "ms_debug_pair_lds_bins": (c_int, []),
+        "ms_debug_cooc_chunk_regions": (c_int, []),
+        "ms_debug_pair_lds_pair_limit": (c_int, [c_i64, pi64]),
         "ms_score": (c_int, [vp, vp, c_int, pd]),
         "ms_score_ranks": (c_int, [vp, vp, c_int, pi64, c_i32, pd]),
         "ms_dedup_hits": (c_int, [pi64, c_i32, pi32, pi64, pi64, pd, pi8, pu8]),
@@ -793,6 +798,37 @@ class ScanResult:
                                            0 if smoothed else MS_PROFILE_UNSMOOTHED, ctypes.c_void_p(dst)))
         return out
 
+    def cooccurrence(self, m0=0, m1=None, out=None):
+        """ms_result_cooccurrence: int64 [m1 - m0][P], the regions that hold a site of motif m0 + a and a site of motif j.  out: an int64
+        numpy array of that shape, or None (a new one); the device pointer of a torch tensor may be passed as an int instead (then it is
+        returned)."""
+        m1 = self.n_pwms if m1 is None else int(m1)
+        m0 = int(m0)
+        shape = (max(m1 - m0, 0), self.n_pwms)
+        if isinstance(out, int):
+            dst = out
+        else:
+            if out is None:
+                out = np.zeros(shape, dtype=np.int64)
+            if out.dtype != np.int64 or out.shape != shape or not out.flags.c_contiguous:
+                raise ValueError("out must be a C-contiguous int64 array of shape (m1 - m0, P)")
+            dst = out.ctypes.data
+        check(lib().ms_result_cooccurrence(self.h, m0, m1, ctypes.c_void_p(dst)))
+        return out
+
+    def pair_spacing(self, pwms, anchor, max_dist, m0=0, m1=None):
+        """ms_result_pair_spacing: (counts int64 [m1 - m0][4][2 * max_dist + 1], n_pairs int64 [m1 - m0]) of the anchor motif's sites against
+        those of motifs m0 .. m1 - 1 in the same region: bin = centre-to-centre distance in half base pairs shifted to 0 and halved,
+        orientation 2 * (anchor strand - 1) + (partner strand - 1).  The library checks every argument."""
+        m1 = self.n_pwms if m1 is None else int(m1)
+        m0, anchor, max_dist = int(m0), int(anchor), int(max_dist)
+        rows, n_bins = max(m1 - m0, 0), 2 * max_dist + 1
+        fits = 0 <= max_dist <= 1 << 20 and rows * 4 * n_bins <= 1 << 31        # what it refuses is refused before it writes
+        counts = np.zeros((rows, 4, n_bins) if fits else (1, 4, 1), dtype=np.int64)
+        n_pairs = np.zeros(max(rows, 1), dtype=np.int64)
+        check(lib().ms_result_pair_spacing(self.h, pwms.h, anchor, m0, m1, max_dist, ptr(counts, ctypes.c_int64), ptr(n_pairs, ctypes.c_int64)))
+        return counts, n_pairs[:rows]
+
     def close(self):
         if getattr(self, "h", None):
             lib().ms_result_free(self.h)
@@ -1108,6 +1144,24 @@ def scan_best(pwms, seqs, strand_mask=3, flags=0):
 def best_segment_windows():
     """ms_debug_best_segment_windows: window starts per segment of ms_scan_best (tests size a multi-segment region with it)."""
     return int(lib().ms_debug_best_segment_windows())
+
+
+def pair_lds_bins():
+    """ms_debug_pair_lds_bins: the widest 2 * max_dist + 1 that ms_result_pair_spacing bins in LDS."""
+    return int(lib().ms_debug_pair_lds_bins())
+
+
+def cooc_chunk_regions():
+    """ms_debug_cooc_chunk_regions: regions per LDS stage of ms_result_cooccurrence."""
+    return int(lib().ms_debug_cooc_chunk_regions())
+
+
+def pair_lds_pair_limit(limit):
+    """ms_debug_pair_lds_pair_limit: partner hits x anchor hits up to which a block of pair_spacing bins in LDS, for the calls that follow
+    (0 = the library's own); returns the value before.  Tests only."""
+    prev = ctypes.c_int64()
+    check(lib().ms_debug_pair_lds_pair_limit(int(limit), ctypes.byref(prev)))
+    return prev.value
 
 
 def _flatten_alleles(seqs):
