@@ -52,6 +52,13 @@ int ms_debug_bucket_plan(const int64_t *offsets, int64_t n_seqs, const int32_t *
                          int32_t low_bits, int64_t n_regions, uint64_t *weights, double mu, uint64_t n_pred, uint64_t cap_max, uint32_t form, int32_t force,
                          uint64_t *need, int32_t *gate, uint64_t *base, uint64_t *cap);
 
+/* The layout of a scan's hit keys (motif << (gbits + 1) | coordinate << 1 | strand bit) for a sequence set of n_bases bases in n_seqs
+ * regions, the longest of max_len bases, and n_pwms motifs -- the same arithmetic a scan runs before its first launch; no device.
+ * coord_global != 0: as under MS_MEASURE=1 MS_HIT_COORD=global.  *gbits: coordinate bits.  *pbits > 0: the coordinate is
+ * region << pbits | position in the region; *pbits == 0: it is the global base position (ms_scan_regions_once then looks the span up
+ * by binary search).  A test learns from it which of the two forms a set takes by itself. */
+int ms_debug_key_layout(int64_t n_bases, int64_t n_seqs, int64_t max_len, int32_t n_pwms, int32_t coord_global, int32_t *gbits, int32_t *pbits);
+
 /* Free the current device's grow-only work buffers (candidate list, hit list, sort space), so a
  * test can force the "buffer too small -> grow -> run the pass again" path.  Needs a GPU. */
 int ms_debug_release_scratch(void);

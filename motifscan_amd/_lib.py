@@ -195,6 +195,7 @@ def lib():
         "ms_best_device_ms": (c_int, [vp, pd]),
         "ms_best_free": (None, [vp]),
         "ms_debug_best_segment_windows": (c_int, []),
+        "ms_debug_key_layout": (c_int, [c_i64, c_i64, c_i64, c_i32, c_i32, pi32, pi32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -873,6 +874,15 @@ def bucket_plan(mu, n_pred, *, gbits, pbits, end_bit, low_bits, offsets=None, wi
                                      int(n_pred), (1 << 64) - 1 if cap_max is None else int(cap_max), form, int(force), ctypes.byref(need),
                                      ctypes.byref(gate), ptr(base, ctypes.c_uint64), ptr(cap, ctypes.c_uint64)))
     return {"weights": w, "need": need.value, "gate": bool(gate.value), "base": base, "cap": cap}
+
+
+def key_layout(n_bases, n_seqs, max_len, n_pwms, coord_global=False):
+    """ms_debug_key_layout (no device): (gbits, pbits) of the hit keys of a scan over a set of these sizes; pbits > 0 = (region, position)
+    coordinates, 0 = global base positions."""
+    gbits, pbits = ctypes.c_int32(), ctypes.c_int32()
+    check(lib().ms_debug_key_layout(int(n_bases), int(n_seqs), int(max_len), int(n_pwms), 1 if coord_global else 0, ctypes.byref(gbits),
+                                    ctypes.byref(pbits)))
+    return gbits.value, pbits.value
 
 
 def host_pack(bases, offsets):

@@ -673,4 +673,14 @@ int ms_debug_bucket_plan(const int64_t *offsets, int64_t n_seqs, const int32_t *
     return MS_OK;
 }
 
+// the hit keys' layout for a set of these sizes, as scan_locked would choose it (include/motifscan_amd_debug.h)
+int ms_debug_key_layout(int64_t n_bases, int64_t n_seqs, int64_t max_len, int32_t n_pwms, int32_t coord_global, int32_t *gbits, int32_t *pbits) {
+    if (!gbits || !pbits) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    if (n_bases < 0 || n_seqs < 0 || max_len < 0 || max_len > n_bases || n_pwms < 0) { set_error("invalid sizes"); return MS_ERR_INVALID; }
+    const ScanGeom g = scan_key_layout(n_bases, n_seqs, max_len, n_pwms, coord_global != 0);
+    *gbits = g.gbits;
+    *pbits = g.pbits;
+    return MS_OK;
+}
+
 }  // extern "C"

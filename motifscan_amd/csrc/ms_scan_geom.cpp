@@ -48,6 +48,16 @@ static void key_layout(const ScanShape &s, const ScanOverrides &ov, ScanGeom &g)
     g.coord_shift12 = g.rbits + pb + 1 <= 32 ? pb + 1 : 0;
 }
 
+ScanGeom scan_key_layout(int64_t n_bases, int64_t R, int64_t max_len, int32_t P, bool coord_global) {
+    ScanShape s;
+    s.n_bases = n_bases; s.R = R; s.max_len = max_len; s.P = P;
+    ScanOverrides ov;
+    ov.coord_global = coord_global;
+    ScanGeom g;
+    key_layout(s, ov, g);
+    return g;
+}
+
 static void lds_layout(const ScanShape &s, const ScanOverrides &ov, ScanGeom &g) {
     g.lds_fixed = g.wide ? kPfLdsFixedWide : kPfLdsFixedNarrow;
     size_t tables = 0;

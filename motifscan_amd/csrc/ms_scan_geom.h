@@ -69,6 +69,8 @@ struct ScanGeom {
     size_t fixup_min = (size_t) 1 << 20;
 };
 MS_HIDDEN ScanGeom scan_geometry(const ScanShape &s, const ScanOverrides &ov);
+// the key fields alone (gbits, rbits, pbits, mbits, end_bit, coord_shift12) of a set of these sizes: what scan_geometry() puts there
+MS_HIDDEN ScanGeom scan_key_layout(int64_t n_bases, int64_t R, int64_t max_len, int32_t P, bool coord_global);
 
 // the first key bit the radix passes cover when n_sort slots are ordered (the kernels behind them order the bits below)
 MS_HIDDEN int scan_sort_begin(const ScanGeom &g, int32_t P, size_t n_sort);

@@ -10,25 +10,33 @@ to sit ON the decision boundary of cscore.c:360-389 (`score / max_raw - cutoff >
   * sequences with N runs, lower case, other IUPAC letters, empty and shorter-than-W regions;
   * (round 6) every case also through MS_SCAN_COUNTS_ONLY and through a two-batch stream with the 12-byte copy-out.
 
-The same matrices, sequences and cutoffs feed four more families, one per entry point that judges windows with a decision of its own:
+The same matrices, sequences and cutoffs feed five more families, one per entry point that judges windows with a decision of its own
+or hands them out by one:
 
   * --sweep     ms_scan_sweep: one chromosome, random window / stride, against the oracle over the windows as separate regions;
   * --variants  ms_scan_variants: single-base substitutions (duplicates, any order, alt letters that add nothing) on a resident genome,
                 against the oracle over the ref and alt flank of every variant -- all-pass for the scores, the real cutoff for the states;
   * --alleles   ms_scan_alleles: alleles of 0..40 bases incl. insertions behind the last base, REF strings on even seeds;
-  * --best      ms_scan_best: the first window of the greatest score per (motif, region), regions of up to three segments, run twice.
+  * --best      ms_scan_best: the first window of the greatest score per (motif, region), regions of up to three segments, run twice;
+  * --once      ms_scan_regions_once: overlapping, nested, touching, duplicate and empty regions of a resident genome in five layouts
+                (summit windows, tiny regions beside chromosome-long ones, jittered tilings, shared starts, uniform), against the oracle
+                over the regions cut as strings: as is, run twice, with the span hits keyed by global positions, every third seed under
+                MS_SCAN_EXACT_ONLY, odd seeds de-duplicated; the tally counts the windows that end flush with a region, stick out of one
+                by a base or start a base in front of one, and which form of hit key the spans take by themselves.
 
-Each of the last three is make_<x>_case(seed) (inputs), expected_<x>(oracle, case) (expected arrays and a tally; neither needs a GPU) and
+Each of the last four is make_<x>_case(seed) (inputs), expected_<x>(oracle, case) (expected arrays and a tally; neither needs a GPU) and
 run_<x>_case(seed, oracle, _lib) (the device call, compared exactly: integers by value, scores by their bits).  Odd seeds of the variant
 and allele families run in chunks of 7 variants.  CONDITIONS holds what the seeds of a family must put on the boundary.
 
 It lives under tests/ because it uses the oracle (test infrastructure).  Run on the GPU box:
     python tests/fuzz_parity.py --cases 200 --seed 0
-    python tests/fuzz_parity.py --variants --cases 30        (likewise --alleles, --best, --sweep; each prints its tallies)
+    python tests/fuzz_parity.py --variants --cases 30        (likewise --alleles, --best, --sweep, --once; each prints its tallies)
 `tests/test_gpu_parity.py::test_fuzz_decision_boundary` runs a few cases of ms_scan's family in the GPU suite,
-tests/test_gpu_fuzz_entry_points.py the other four; tests/test_fuzz_cases_host.py checks the cases themselves without a GPU.
+tests/test_gpu_fuzz_entry_points.py the next four, tests/test_gpu_scan_once.py the last; tests/test_fuzz_cases_host.py checks the cases
+themselves without a GPU.
 """
 import argparse
+import contextlib
 import os
 import sys
 
@@ -317,7 +325,7 @@ def run_sweep_case(seed, oracle, _lib):
 ALL_PASS = -1e30
 NEAR = 2e-10                                            # a scored window is "near" when its score is within this of the motif's cutoff
 ALT_LETTERS = "ACGTACGTNacgtR"
-VARIANT_STREAM, ALLELE_STREAM, BEST_STREAM = 2_000_003 * 11, 3_000_017 * 13, 5_000_011 * 17
+VARIANT_STREAM, ALLELE_STREAM, BEST_STREAM, ONCE_STREAM = 2_000_003 * 11, 3_000_017 * 13, 5_000_011 * 17, 7_000_003 * 23
 
 
 def motif_kinds(mats):
@@ -327,10 +335,18 @@ def motif_kinds(mats):
 
 
 def add_tally(total, tally):
-    """Sum a case's tally into a running one (numbers only)."""
+    """Sum a case's tally into a running one: numbers are added, sets (what was seen) united."""
     for k, v in tally.items():
-        total[k] = total.get(k, 0) + int(v)
+        if isinstance(v, (set, frozenset)):
+            total[k] = total.get(k, set()) | v
+        else:
+            total[k] = total.get(k, 0) + int(v)
     return total
+
+
+def shown(total):
+    """A tally for printing: a set as its size."""
+    return {k: len(v) if isinstance(v, (set, frozenset)) else v for k, v in total.items()}
 
 
 def same_bits(a, b):
@@ -682,16 +698,305 @@ def run_best_case(seed, oracle, _lib):
     return True, tally
 
 
-FAMILIES = {"variants": run_variants_case, "alleles": run_alleles_case, "best": run_best_case}
+# ---- ms_scan_regions_once
+
+ONCE_LAYOUTS = ("summits", "mixed", "tilings", "shared_starts", "uniform")
+
+
+def once_regions(rng, kind, lens, n):
+    """n regions (chromosome, start, end) of one layout kind on chromosomes of these lengths, all inside their chromosome."""
+    out = []
+
+    def clipped(c, a, b):
+        a = min(max(int(a), 0), lens[c])
+        out.append((c, a, min(max(int(b), a), lens[c])))
+
+    if kind == "summits":                               # summit +- w / 2, summits uniform: spacing much smaller than w
+        w = int(rng.choice([20, 100, 500]))
+        for _ in range(n):
+            c = int(rng.integers(0, len(lens)))
+            s = int(rng.integers(0, lens[c] + 1))
+            clipped(c, s - w // 2, s + w // 2)
+    elif kind == "mixed":                               # tiny regions beside one or two that cover a chromosome: the span_maxlen bound
+        for _ in range(min(n, int(rng.integers(1, 3)))):
+            c = int(rng.integers(0, len(lens)))
+            clipped(c, rng.integers(0, 3), lens[c] - int(rng.integers(0, 3)))
+        while len(out) < n:
+            c = int(rng.integers(0, len(lens)))
+            a = int(rng.integers(0, lens[c] + 1))
+            clipped(c, a, a + int(rng.choice([0, 1, 3, 17, 120])))
+    elif kind == "tilings":                             # touching tiles, one-base overlaps and one-base gaps
+        w = int(rng.choice([8, 33, 64]))
+        at = [int(rng.integers(0, w)) for _ in lens]
+        for _ in range(n):
+            room = [c for c in range(len(lens)) if at[c] + w <= lens[c]]
+            c = room[int(rng.integers(0, len(room)))] if room else int(rng.integers(0, len(lens)))
+            if not room:
+                at[c] = int(rng.integers(0, w))          # every chromosome is tiled: the next row over one of them, at another phase
+            clipped(c, at[c] + int(rng.integers(-1, 2)), at[c] + w + int(rng.integers(-1, 2)))
+            at[c] += w
+    elif kind == "shared_starts":                       # equal starts, nesting, duplicates
+        starts = []
+        for _ in range(int(rng.integers(1, 5))):
+            c = int(rng.integers(0, len(lens)))
+            starts.append((c, int(rng.integers(0, lens[c] + 1))))
+        for _ in range(n):
+            c, a = starts[int(rng.integers(0, len(starts)))]
+            clipped(c, a, a + int(rng.choice([0, 5, 40, 41, 300])))
+    else:
+        for _ in range(n):
+            c = int(rng.integers(0, len(lens)))
+            a = int(rng.integers(0, lens[c] + 1))
+            clipped(c, a, a + int(rng.integers(0, 400)))
+    return out
+
+
+def make_once_case(seed):
+    """The scan-once family's inputs (no GPU): motifs, 1 / 2 / 5 chromosomes, a region list of one of ONCE_LAYOUTS with an eighth of it
+    repeated as exact duplicates, shuffled; cutoffs on attainable scores of the cut regions."""
+    rng = np.random.default_rng(ONCE_STREAM + seed)
+    mats = random_motifs(rng, [1, 2, 5, 13, 40])
+    chroms = [random_sequences(rng, 1, int(rng.choice([60, 400, 1500, 6000])))[0] or "ACGTTGCANacgtACGGT" for _ in range(int(rng.choice([1, 2, 5])))]
+    n = int(rng.choice([1, 8, 60, 300]))
+    kind = ONCE_LAYOUTS[int(rng.integers(0, len(ONCE_LAYOUTS)))]
+    regions = once_regions(rng, kind, [len(c) for c in chroms], n - n // 8)
+    regions += [regions[int(k)] for k in rng.integers(0, len(regions), n // 8)]
+    regions = [regions[int(k)] for k in rng.permutation(len(regions))]
+    seqs = [chroms[c][a:b] for c, a, b in regions]
+    cutoffs = np.array([attainable_cutoff(rng, m, seqs) for m in mats], dtype=np.float64)
+    chrom_idx, start, end = (np.array([r[k] for r in regions], dtype=t) for k, t in enumerate((np.int32, np.int64, np.int64)))
+    return {"mats": mats, "cutoffs": cutoffs, "chroms": chroms, "chrom_idx": chrom_idx, "start": start, "end": end, "seqs": seqs,
+            "strand": int(rng.integers(1, 4)), "layout": kind}
+
+
+def merge_spans(chrom_idx, start, end):
+    """The regions ordered by (chromosome, start, index) and merged into spans the way ms_scan_regions_once does: a region joins the
+    span in front of it iff it starts before that span's end (touching regions do not join; an empty region can be a span of its own).
+    Returns (order [R], span of every ORDERED region [R], span chromosome / start / end [S])."""
+    ci, st, en = np.asarray(chrom_idx, dtype=np.int64), np.asarray(start, dtype=np.int64), np.asarray(end, dtype=np.int64)
+    order = np.lexsort((np.arange(len(ci)), st, ci))
+    span_of, sp = [], []
+    for r in order.tolist():
+        if sp and sp[-1][0] == ci[r] and st[r] < sp[-1][2]:
+            sp[-1][2] = max(sp[-1][2], int(en[r]))
+        else:
+            sp.append([int(ci[r]), int(st[r]), int(en[r])])
+        span_of.append(len(sp) - 1)
+    sp = np.array(sp, dtype=np.int64).reshape(-1, 3)
+    return order, np.array(span_of, dtype=np.int64), sp[:, 0], sp[:, 1], sp[:, 2]
+
+
+def bits_for(n):
+    b = 1
+    while (1 << b) < max(int(n), 1):
+        b += 1
+    return b
+
+
+def default_key_form(n_bases, n_seqs, max_len):
+    """"local" / "global": the form of the hit coordinate a scan of a set of these sizes chooses by itself (ms_scan_geom.cpp, key_layout:
+    (region, position) when that costs at most two bits more than the global base position).  tests/test_fuzz_cases_host.py holds this
+    against the library's own answer (ms_debug_key_layout)."""
+    gbits = 1
+    while (1 << gbits) <= n_bases:
+        gbits += 1
+    return "local" if bits_for(n_seqs) + bits_for(max_len) <= gbits + 2 else "global"
+
+
+def once_span_shape(case):
+    """(bases, spans, longest span) of the case's merged regions: the sequence set ms_scan_regions_once scans."""
+    _, _, _, sp_start, sp_end = merge_spans(case["chrom_idx"], case["start"], case["end"])
+    lens = sp_end - sp_start
+    return int(lens.sum()), len(lens), int(lens.max()) if len(lens) else 0
+
+
+def once_tally(case, want):
+    """What a scan-once case puts on the hand-out's boundaries, from the regions and the oracle's hits alone."""
+    ci, st, en = case["chrom_idx"].astype(np.int64), case["start"], case["end"]
+    widths = np.array([m.shape[1] for m in case["mats"]], dtype=np.int64)
+    R, n = len(ci), len(want["pos"])
+    order, span_sorted, sp_chrom, sp_start, sp_end = merge_spans(ci, st, en)
+    span = np.zeros(R, dtype=np.int64)
+    span[order] = span_sorted
+    lens = en - st
+    tally = {"sites": n, "cases_without_sites": int(n == 0), "empty_regions": int((lens == 0).sum()), **motif_kinds(case["mats"]),
+             "strand_masks": {case["strand"]}, "layouts": {case["layout"]}}
+    tally["pairs"] = int(sum(np.maximum(lens - w + 1, 0).sum() for w in widths.tolist())) * bin(case["strand"]).count("1")
+    # the merge: touching non-empty neighbours that stay apart, equal starts with different ends, spans of very different regions
+    so_c, so_s, so_e = ci[order], st[order], en[order]
+    new_span = np.concatenate([[True], np.diff(span_sorted) > 0]) if R else np.zeros(0, dtype=bool)
+    prev_end = np.concatenate([[0], sp_end[span_sorted[:-1]]]) if R else np.zeros(0, dtype=np.int64)
+    prev_len = np.concatenate([[0], (sp_end - sp_start)[span_sorted[:-1]]]) if R else np.zeros(0, dtype=np.int64)
+    same_chrom = np.concatenate([[False], so_c[1:] == so_c[:-1]]) if R else np.zeros(0, dtype=bool)
+    tally["touching"] = int((new_span & same_chrom & (so_s == prev_end) & (prev_len > 0) & (so_e > so_s)).sum())
+    tally["equal_starts"] = int((same_chrom & (so_s == np.concatenate([[-1], so_s[:-1]])) & (so_e != np.concatenate([[-1], so_e[:-1]]))).sum()) if R else 0
+    mixed = 0
+    for s in range(len(sp_chrom)):
+        ls = lens[order][span_sorted == s]
+        mixed += int(ls[ls > 0].size > 0 and ls.max() >= 50 * ls[ls > 0].min())
+    tally["mixed_spans"] = mixed
+    goff = np.concatenate([[0], np.cumsum([len(c) for c in case["chroms"]])])
+    tally["span_start_residues"] = {int(x) for x in ((goff[sp_chrom] + sp_start)[sp_end > sp_start] % 32).tolist()}
+    form = default_key_form(*once_span_shape(case))
+    tally["cases_local"], tally["cases_global"] = int(n > 0 and form == "local"), int(n > 0 and form == "global")
+    for k in ("shared_sites", "shared_by_8", "flush_end", "flush_start", "one_base_out", "one_base_before"):
+        tally[k] = 0
+    if n == 0:
+        return tally
+    # the sites: shared between regions, flush with a region's ends
+    m = np.repeat(np.arange(len(widths)), np.diff(want["motif_offsets"]))
+    r, p, W = want["seq_idx"], want["pos"], widths[m]
+    g = st[r] + p
+    big = int(max(len(c) for c in case["chroms"])) + 2
+    site = ((m * len(case["chroms"]) + ci[r]) * big + g) * 2 + (want["strand"].astype(np.int64) - 1)
+    uniq, first, inverse, count = np.unique(site, return_index=True, return_inverse=True, return_counts=True)
+    tally["shared_sites"], tally["shared_by_8"] = int((count[inverse] >= 2).sum()), int((count[inverse] >= 8).sum())
+    tally["flush_end"], tally["flush_start"] = int((p + W == lens[r]).sum()), int((p == 0).sum())
+    # per distinct span site, the regions of its span the inclusion test has to turn down by one base
+    ug, uW, usp = g[first], W[first], span[r[first]]
+    by_end = np.sort((span * big + en) * big + st)                          # (span, end, start)
+    lo = np.searchsorted(by_end, (usp * big + ug + uW - 1) * big, side="left")
+    hi = np.searchsorted(by_end, (usp * big + ug + uW - 1) * big + ug, side="right")
+    tally["one_base_out"] = int((hi - lo).sum())                            # start <= g and g + W == end + 1
+    by_start = np.sort((span * big + st) * big + en)                        # (span, start, end)
+    lo = np.searchsorted(by_start, (usp * big + ug + 1) * big + ug + uW, side="left")
+    hi = np.searchsorted(by_start, (usp * big + ug + 1) * big + big - 1, side="right")
+    tally["one_base_before"] = int((hi - lo).sum())                         # g == start - 1 and g + W <= end
+    return tally
+
+
+def expected_once(oracle, case):
+    """(the oracle's hits over the regions cut as Python strings, in the caller's order; the tally); no GPU."""
+    vals, widths = oracle.flatten_pwms(case["mats"])
+    bases, off = oracle.flatten_seqs(case["seqs"])
+    want = oracle.scan_arrays(vals, widths, case["cutoffs"], bases, off, case["strand"], 4)
+    return want, once_tally(case, want)
+
+
+def once_differs(got, want):
+    """None, or what differs between two hit lists: integers by value, scores by their bits."""
+    for k in ("motif_offsets", "seq_idx", "pos"):
+        if not np.array_equal(got[k], want[k]):
+            return f"{k} differs ({len(got['pos'])} vs {len(want['pos'])} sites)"
+    if not np.array_equal(got["strand"].astype(np.int32), want["strand"].astype(np.int32)):
+        return "strand differs"
+    if not same_bits(got["score"], want["score"]):
+        return "the bits of score differ"
+    return None
+
+
+@contextlib.contextmanager
+def forced_global_keys():
+    """Scans inside the block key their hits by the global base position (MS_MEASURE=1 MS_HIT_COORD=global; a scan reads the switches
+    when it starts).  The environment is as before afterwards."""
+    before = {k: os.environ.get(k) for k in ("MS_MEASURE", "MS_HIT_COORD")}
+    os.environ.update(MS_MEASURE="1", MS_HIT_COORD="global")
+    try:
+        yield
+    finally:
+        for k, v in before.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def check_once(case, want, _lib, dedup=False, exact_only=False):
+    """ms_scan_regions_once over a ResidentGenome of the case's chromosomes against `want` (expected_once): as is (hits, region counts,
+    site tables), again on the same PwmSet (the same bytes), with the span hits keyed by global positions, optionally under
+    MS_SCAN_EXACT_ONLY, and optionally de-duplicated against ms_dedup_hits over the expected arrays.  None, or what differs."""
+    P, R = len(case["mats"]), len(case["chrom_idx"])
+    widths = np.array([m.shape[1] for m in case["mats"]], dtype=np.int32)
+    motif = np.repeat(np.arange(P, dtype=np.int64), np.diff(want["motif_offsets"]))
+    want_regions = np.bincount(np.unique(motif << 32 | want["seq_idx"]) >> 32, minlength=P)
+    genome = _lib.ResidentGenome({f"c{i}": c for i, c in enumerate(case["chroms"])})
+    pw = _lib.PwmSet.from_matrices(case["mats"], case["cutoffs"])
+
+    def scan(flags=0):
+        return _lib.scan_regions_once(pw, genome, case["chrom_idx"], case["start"], case["end"], case["strand"], flags)
+
+    def differs(res, what):
+        bad = once_differs(res.hits(), want)
+        if bad is None and not np.array_equal(res.region_counts(), want_regions):
+            bad = "region counts differ"
+        return f"{what}: {bad}" if bad else None
+
+    res = scan()
+    try:
+        bad = differs(res, "as is")
+        if bad:
+            return bad
+        first = {k: v.tobytes() for k, v in res.hits().items()}
+        n_sites, max_score = res.site_tables(R)
+        want_n, want_max = np.zeros((P, R), dtype=np.int32), np.full((P, R), -np.inf)
+        np.add.at(want_n, (motif, want["seq_idx"]), 1)
+        np.maximum.at(want_max, (motif, want["seq_idx"]), want["score"])
+        want_max[want_n == 0] = np.nan
+        if not np.array_equal(n_sites, want_n) or not np.array_equal(np.isnan(max_score), np.isnan(want_max)) or \
+                not same_bits(max_score[want_n > 0], want_max[want_n > 0]):
+            return "site tables differ"
+        again = scan()
+        try:
+            if {k: v.tobytes() for k, v in again.hits().items()} != first:
+                return "a second run on the same PWM set gives different bytes"
+        finally:
+            again.close()
+        with forced_global_keys():
+            glob = scan()
+        try:
+            bad = differs(glob, "global positions")
+        finally:
+            glob.close()
+        if bad:
+            return bad
+        if exact_only:
+            ex = scan(_lib.MS_SCAN_EXACT_ONLY)
+            try:
+                bad = differs(ex, "exact only")
+            finally:
+                ex.close()
+            if bad:
+                return bad
+        if dedup:
+            keep = _lib.dedup_keep(want["motif_offsets"], widths, want["seq_idx"], want["pos"], want["score"], want["strand"])
+            kept = {k: want[k][keep] for k in ("seq_idx", "pos", "score", "strand")}
+            kept["motif_offsets"] = np.concatenate([[0], np.cumsum(np.bincount(motif[keep], minlength=P))]).astype(np.int64)
+            res.dedup(pw)
+            bad = once_differs(res.hits(), kept)
+            if bad is None and not np.array_equal(res.region_counts(), want_regions):
+                bad = "region counts differ"                                  # (de-duplication never empties a region)
+            if bad:
+                return f"de-duplicated: {bad}"
+    finally:
+        res.close()
+        pw.close()
+        genome.close()
+    return None
+
+
+def run_once_case(seed, oracle, _lib):
+    """Odd seeds are also de-duplicated, every third seed also runs under MS_SCAN_EXACT_ONLY."""
+    case = make_once_case(seed)
+    want, tally = expected_once(oracle, case)
+    bad = check_once(case, want, _lib, dedup=seed % 2 == 1, exact_only=seed % 3 == 0)
+    return (False, f"once seed {seed}: {bad}") if bad else (True, tally)
+
+
+FAMILIES = {"variants": run_variants_case, "alleles": run_alleles_case, "best": run_best_case, "once": run_once_case}
 
 # What the seeds of a family must put on the boundary, summed over SEEDS[family] from the oracle's output alone: conditions, not
 # measurements.  If a change to a generator misses one, the seed range changes -- not the threshold, not the mix of matrix kinds.
-SEEDS = {"variants": range(30), "alleles": range(30), "best": range(30), "sweep": range(40)}
+SEEDS = {"variants": range(30), "alleles": range(30), "best": range(30), "sweep": range(40), "once": range(40)}
 CONDITIONS = {"variants": {"near_fail": 10_000, "near_pass": 10_000, "records": 100_000},
               "alleles": {"near_fail": 5_000, "near_pass": 5_000, "gained": 500, "lost": 500},
               "best": {"tied_cells": 1_000, "tied_across_segments": 300},
-              "sweep": {"sites": 100_000}}
+              "sweep": {"sites": 100_000},
+              "once": {"sites": 500_000, "shared_sites": 500_000, "shared_by_8": 100_000, "flush_end": 5_000, "flush_start": 5_000,
+                       "one_base_out": 2_000, "one_base_before": 2_000, "touching": 20, "equal_starts": 200, "empty_regions": 100,
+                       "mixed_spans": 10, "cases_local": 10, "cases_global": 3}}
 SWEEP_MAX_EMPTY = 10                                    # at most this many of the sweep cases may have no window at all
+ONCE_MAX_EMPTY = 12                                     # at most this many of the scan-once cases may have no site at all
+ONCE_SEEN = {"span_start_residues": 32, "strand_masks": 3, "layouts": len(ONCE_LAYOUTS)}      # every one of them must occur
 
 
 def unmet_conditions(family, total):
@@ -703,6 +1008,10 @@ def unmet_conditions(family, total):
     bad = [f"{k}: {total.get(k, 0)} < {n}" for k, n in need.items() if total.get(k, 0) < n]
     if family == "sweep" and total.get("cases_without_windows", 0) > SWEEP_MAX_EMPTY:
         bad.append(f"cases_without_windows: {total['cases_without_windows']} > {SWEEP_MAX_EMPTY}")
+    if family == "once":
+        bad += [f"{k}: {len(total.get(k, ()))} of {n} seen" for k, n in ONCE_SEEN.items() if len(total.get(k, ())) != n]
+        if total.get("cases_without_sites", 0) > ONCE_MAX_EMPTY:
+            bad.append(f"cases_without_sites: {total['cases_without_sites']} > {ONCE_MAX_EMPTY}")
     return bad
 
 
@@ -714,6 +1023,7 @@ def main():
     ap.add_argument("--variants", action="store_true", help="fuzz ms_scan_variants instead of ms_scan")
     ap.add_argument("--alleles", action="store_true", help="fuzz ms_scan_alleles instead of ms_scan")
     ap.add_argument("--best", action="store_true", help="fuzz ms_scan_best instead of ms_scan")
+    ap.add_argument("--once", action="store_true", help="fuzz ms_scan_regions_once instead of ms_scan")
     a = ap.parse_args()
     from oracle import oracle
     oracle.build()
@@ -741,7 +1051,7 @@ def main():
                     print("MISMATCH", info, flush=True)
                 else:
                     add_tally(tally, info)
-            print(f"{name} fuzz: {a.cases} cases from seed {a.seed}: {bad} mismatches; tallies {tally}")
+            print(f"{name} fuzz: {a.cases} cases from seed {a.seed}: {bad} mismatches; tallies {shown(tally)}")
             return 1 if bad else 0
     bad, total_hits, fast, exact = 0, 0, 0, 0
     for k in range(a.cases):

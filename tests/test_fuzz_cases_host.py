@@ -1,8 +1,9 @@
 """
-The cases of tests/fuzz_parity.py's variant, allele, best-site and sweep families without a GPU: that their seeds put what they should
+The cases of tests/fuzz_parity.py's variant, allele, best-site, sweep and scan-once families without a GPU: that their seeds put what they should
 on the decision boundary (fuzz_parity.CONDITIONS, tallied from the oracle's output alone -- the same conditions the GPU tests assert on
 what they compared), and that the builders of the expected records are right, against the same scoring in plain Python floats (columns
-in order, raw / max_raw, score - cutoff >= -1e-10) on every seed small enough for it.
+in order, raw / max_raw, score - cutoff >= -1e-10) on every seed small enough for it.  For the scan-once family also that its tally's
+view of the merged spans and of the hit keys' form is the library's own (_lib.union_bases, ms_debug_key_layout).
 """
 import numpy as np
 import pytest
@@ -19,7 +20,7 @@ CODE.update({c.lower(): i for c, i in list(CODE.items())})
 def expected(oracle):
     """family -> [(seed, case, expected arrays, tally)] over the family's seeds, computed once."""
     seg = _lib.best_segment_windows()
-    out = {"variants": [], "alleles": [], "best": []}
+    out = {"variants": [], "alleles": [], "best": [], "once": []}
     for seed in fp.SEEDS["variants"]:
         case = fp.make_variants_case(seed)
         out["variants"].append((seed, case, *fp.expected_variants(oracle, case)))
@@ -29,17 +30,20 @@ def expected(oracle):
     for seed in fp.SEEDS["best"]:
         case = fp.make_best_case(seed)
         out["best"].append((seed, case, *fp.expected_best(oracle, case, seg)))
+    for seed in fp.SEEDS["once"]:
+        case = fp.make_once_case(seed)
+        out["once"].append((seed, case, *fp.expected_once(oracle, case)))
     return out
 
 
 # ------------------------------------------------------------------------------------------------ the conditions
 
-@pytest.mark.parametrize("family", ["variants", "alleles", "best"])
+@pytest.mark.parametrize("family", ["variants", "alleles", "best", "once"])
 def test_seeds_meet_the_conditions(expected, family):
     total = {}
     for _, _, _, tally in expected[family]:
         fp.add_tally(total, tally)
-    print(f"{family}: seeds {fp.SEEDS[family]}: {total}")
+    print(f"{family}: seeds {fp.SEEDS[family]}: {fp.shown(total)}")
     assert not fp.unmet_conditions(family, total)
 
 
@@ -188,3 +192,46 @@ def test_expected_best_equals_python_floats(expected):
                     assert fp.same_bits(score[m, r], best), (seed, m, r)
                 else:
                     assert np.isnan(score[m, r]), (seed, m, r)
+
+
+def test_expected_once_equals_python_floats(expected):
+    for seed, case, want in small_cases(expected, "once"):
+        recs, offsets = [], [0]
+        for mat, cutoff in zip(case["mats"], case["cutoffs"]):
+            for r, (c, a, b) in enumerate(zip(case["chrom_idx"].tolist(), case["start"].tolist(), case["end"].tolist())):
+                recs += [(r, p, s, q) for p, s, q in python_windows(mat, case["chroms"][c][a:b], case["strand"]) if passes(q, cutoff)]
+            offsets.append(len(recs))
+        region, pos, strand, q = columns(recs, (np.int64, np.int64, np.int8, np.float64))
+        for k, a in (("seq_idx", region), ("pos", pos), ("strand", strand), ("motif_offsets", offsets)):
+            assert np.array_equal(want[k], a), (seed, k)
+        assert fp.same_bits(want["score"], q), seed
+
+
+# ------------------------------------------------------------------------------------------------ the scan-once tally's view of the spans
+
+def test_once_span_merge_agrees_with_union_bases(expected):
+    for seed, case, _, _ in expected["once"]:
+        order, span_of, sp_chrom, sp_start, sp_end = fp.merge_spans(case["chrom_idx"], case["start"], case["end"])
+        assert int((sp_end - sp_start).sum()) == _lib.union_bases(case["chrom_idx"], case["start"], case["end"]), seed
+        # spans are ordered, apart (they may touch) and every region lies inside its own
+        same = sp_chrom[1:] == sp_chrom[:-1]
+        assert np.all(np.diff(sp_chrom) >= 0) and np.all(sp_start[1:][same] >= sp_end[:-1][same]), seed
+        assert np.all(case["start"][order] >= sp_start[span_of]) and np.all(case["end"][order] <= sp_end[span_of]), seed
+        assert np.array_equal(case["chrom_idx"][order], sp_chrom[span_of]), seed
+
+
+def test_once_key_form_is_the_librarys(expected):
+    """cases_local / cases_global of the tally say which form of hit key ms_scan_regions_once's span scan takes by itself: held against
+    key_layout (ms_scan_geom.cpp) through ms_debug_key_layout on every seed's span set, so that the restatement cannot drift."""
+    for seed, case, want, tally in expected["once"]:
+        n_bases, n_spans, longest = fp.once_span_shape(case)
+        gbits, pbits = _lib.key_layout(n_bases, n_spans, longest, len(case["mats"]))
+        assert (1 << gbits) > n_bases or pbits > 0, seed
+        assert fp.default_key_form(n_bases, n_spans, longest) == ("local" if pbits > 0 else "global"), seed
+        has = int(len(want["pos"]) > 0)
+        assert (tally["cases_local"], tally["cases_global"]) == ((has, 0) if pbits > 0 else (0, has)), seed
+        assert _lib.key_layout(n_bases, n_spans, longest, len(case["mats"]), coord_global=True)[1] == 0, seed
+    assert _lib.key_layout(64 * 256, 64, 256, 5)[1] > 0                       # 64 spans of 256 bases: (span, position)
+    assert _lib.key_layout(63 * 40 + 5000, 64, 5000, 5)[1] == 0               # 63 spans of 40 bases and one of 5000: global positions
+    with pytest.raises(ValueError):
+        _lib.key_layout(10, 1, 11, 1)
