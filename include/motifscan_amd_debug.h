@@ -84,6 +84,14 @@ int ms_debug_cooc_chunk_regions(void);
  * library.  *previous (may be NULL) = the value before.  The result does not depend on it.  Needs no GPU. */
 int ms_debug_pair_lds_pair_limit(int64_t limit, int64_t *previous);
 
+/* The sizes at which the plot-data kernels (ms_result_site_histogram, ms_result_rank_profile) change path, as constants of the build:
+ * out[0] the widest histogram (bins) counted in LDS -- wider ones add to global memory directly; out[1] the hits of the fullest motif
+ * per block of the histogram and rank-mark grids (several trips of a block's grid-stride loop); out[2] the most such blocks per motif, beyond
+ * which the grid stays as it is and the loops run longer; out[3] the threads of the one block that prefix-counts a motif's rank words (more than 64 * out[3] regions: several words per
+ * thread); out[4] the ranks per block of the profile; out[5] the smoothing halo either side (window 2 * out[5] + 1).  Tests take every
+ * boundary size from here.  Needs no GPU. */
+int ms_debug_plot_dims(int32_t out[6]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -160,6 +160,7 @@ def lib():
         "ms_result_pair_spacing": (c_int, [vp, vp, c_i32, c_i32, c_i32, c_i32, pi64, pi64]),
         "ms_debug_pair_lds_bins": (c_int, []),
         "ms_debug_cooc_chunk_regions": (c_int, []),
+        "ms_debug_plot_dims": (c_int, [pi32]),
         "ms_debug_pair_lds_pair_limit": (c_int, [c_i64, pi64]),
         "ms_score": (c_int, [vp, vp, c_int, pd]),
         "ms_score_ranks": (c_int, [vp, vp, c_int, pi64, c_i32, pd]),
@@ -1164,6 +1165,14 @@ def pair_lds_bins():
 def cooc_chunk_regions():
     """ms_debug_cooc_chunk_regions: regions per LDS stage of ms_result_cooccurrence."""
     return int(lib().ms_debug_cooc_chunk_regions())
+
+
+def plot_dims():
+    """ms_debug_plot_dims: the sizes at which the plot-data kernels change path -- dict(hist_lds_bins, hist_hits_per_block,
+    hist_max_blocks, scan_threads, prof_tile, half).  Constants of the build; no device."""
+    out = np.zeros(6, dtype=np.int32)
+    check(lib().ms_debug_plot_dims(ptr(out, ctypes.c_int32)))
+    return dict(zip(("hist_lds_bins", "hist_hits_per_block", "hist_max_blocks", "scan_threads", "prof_tile", "half"), out.tolist()))
 
 
 def pair_lds_pair_limit(limit):

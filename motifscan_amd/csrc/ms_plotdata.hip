@@ -31,6 +31,8 @@ constexpr int kProfThreads = 256;
 constexpr int kProfPerThread = 4;
 constexpr int kProfTile = kProfThreads * kProfPerThread;
 constexpr int kHalf = 5;                           // smoothing window 11 = 2 * kHalf + 1
+constexpr int kHistHitsPerBlock = 8 * kHistThreads;  // hist_blocks_per_motif: one block per this many hits of the fullest motif (8 trips of its loop) ...
+constexpr int kHistMaxBlocks = 64;                 // ... up to this many; beyond them the grid stays and the grid-stride loops run longer
 
 // grid: x = blocks over one motif's hit slice, y = motif row (motif m0 + y).  counts [rows][n_bins], zeroed by the caller.
 __global__ __launch_bounds__(kHistThreads) void site_hist_kernel(const int64_t *__restrict__ motif_first, int32_t m0,
@@ -157,7 +159,7 @@ __global__ __launch_bounds__(kProfThreads) void rank_profile_kernel(const unsign
 int hist_blocks_per_motif(const std::vector<int64_t> &off, int32_t m0, int32_t m1) {
     int64_t most = 0;
     for (int32_t m = m0; m < m1; ++m) most = std::max<int64_t>(most, off[m + 1] - off[m]);
-    return (int) std::max<int64_t>(1, std::min<int64_t>(64, (most + 8 * kHistThreads - 1) / (8 * kHistThreads)));
+    return (int) std::max<int64_t>(1, std::min<int64_t>(kHistMaxBlocks, (most + kHistHitsPerBlock - 1) / kHistHitsPerBlock));
 }
 
 const char *kCountsOnly = "a counts-only result (MS_SCAN_COUNTS_ONLY, a counts-only batch or sweep span of a stream) holds the per-motif region counts and site numbers, no site arrays";
@@ -168,6 +170,13 @@ const char *kCountsOnly = "a counts-only result (MS_SCAN_COUNTS_ONLY, a counts-o
 using namespace ms;
 
 extern "C" {
+
+int ms_debug_plot_dims(int32_t out[6]) {
+    if (!out) { set_error("NULL output"); return MS_ERR_INVALID; }
+    const int32_t dims[6] = {kHistLdsBins, kHistHitsPerBlock, kHistMaxBlocks, kScanThreads, kProfTile, kHalf};
+    std::memcpy(out, dims, sizeof(dims));
+    return MS_OK;
+}
 
 int ms_result_from_hits(int32_t n_pwms, int64_t n_regions, const int64_t *motif_offsets, const int64_t *seq_idx, const int64_t *pos,
                         const double *score, const int8_t *strand, ms_result **out) {

@@ -11,7 +11,7 @@ to sit ON the decision boundary of cscore.c:360-389 (`score / max_raw - cutoff >
   * (round 6) every case also through MS_SCAN_COUNTS_ONLY and through a two-batch stream with the 12-byte copy-out.
 
 The same matrices, sequences and cutoffs feed five more families, one per entry point that judges windows with a decision of its own
-or hands them out by one:
+or hands them out by one; a seventh family has no scan in it:
 
   * --sweep     ms_scan_sweep: one chromosome, random window / stride, against the oracle over the windows as separate regions;
   * --variants  ms_scan_variants: single-base substitutions (duplicates, any order, alt letters that add nothing) on a resident genome,
@@ -24,15 +24,22 @@ or hands them out by one:
                 MS_SCAN_EXACT_ONLY, odd seeds de-duplicated; the tally counts the windows that end flush with a region, stick out of one
                 by a base or start a base in front of one, and which form of hit key the spans take by themselves.
 
-Each of the last four is make_<x>_case(seed) (inputs), expected_<x>(oracle, case) (expected arrays and a tally; neither needs a GPU) and
+  * --plot      ms_result_site_histogram and ms_result_rank_profile over synthetic hit arrays (ms_result_from_hits; no oracle): centres on a
+                bin edge and half a base pair or one either side, on and around the first and the closed last edge and far outside the
+                window; region counts on the rank words' and the profile tile's edges, windows both sides of the LDS histogram's limit;
+                rows without a site and with one in every region, ranks with tied scores; counts and unsmoothed profiles exact, smoothed
+                profiles within 16 * 2^-53 of the exact sum.
+
+Each of --variants, --alleles, --best and --once is make_<x>_case(seed) (inputs), expected_<x>(oracle, case) (expected arrays and a tally; neither needs a GPU) and
 run_<x>_case(seed, oracle, _lib) (the device call, compared exactly: integers by value, scores by their bits).  Odd seeds of the variant
-and allele families run in chunks of 7 variants.  CONDITIONS holds what the seeds of a family must put on the boundary.
+and allele families run in chunks of 7 variants.  The plot family is split the same way, but its expected_plot(case) needs no oracle.
+CONDITIONS holds what the seeds of a family must put on the boundary.
 
 It lives under tests/ because it uses the oracle (test infrastructure).  Run on the GPU box:
     python tests/fuzz_parity.py --cases 200 --seed 0
-    python tests/fuzz_parity.py --variants --cases 30        (likewise --alleles, --best, --sweep, --once; each prints its tallies)
+    python tests/fuzz_parity.py --variants --cases 30        (likewise --alleles, --best, --sweep, --once, --plot; each prints its tallies)
 `tests/test_gpu_parity.py::test_fuzz_decision_boundary` runs a few cases of ms_scan's family in the GPU suite,
-tests/test_gpu_fuzz_entry_points.py the next four, tests/test_gpu_scan_once.py the last; tests/test_fuzz_cases_host.py checks the cases
+tests/test_gpu_fuzz_entry_points.py the next four and the plot family, tests/test_gpu_scan_once.py the scan-once family; tests/test_fuzz_cases_host.py checks the cases
 themselves without a GPU.
 """
 import argparse
@@ -325,7 +332,7 @@ def run_sweep_case(seed, oracle, _lib):
 ALL_PASS = -1e30
 NEAR = 2e-10                                            # a scored window is "near" when its score is within this of the motif's cutoff
 ALT_LETTERS = "ACGTACGTNacgtR"
-VARIANT_STREAM, ALLELE_STREAM, BEST_STREAM, ONCE_STREAM = 2_000_003 * 11, 3_000_017 * 13, 5_000_011 * 17, 7_000_003 * 23
+VARIANT_STREAM, ALLELE_STREAM, BEST_STREAM, ONCE_STREAM, PLOT_STREAM = 2_000_003 * 11, 3_000_017 * 13, 5_000_011 * 17, 7_000_003 * 23, 11_000_027 * 29
 
 
 def motif_kinds(mats):
@@ -982,32 +989,211 @@ def run_once_case(seed, oracle, _lib):
     return (False, f"once seed {seed}: {bad}") if bad else (True, tally)
 
 
-FAMILIES = {"variants": run_variants_case, "alleles": run_alleles_case, "best": run_best_case, "once": run_once_case}
+# ---- ms_result_site_histogram / ms_result_rank_profile (the plot data; no scan and no oracle: synthetic hit arrays)
+
+def plot_n_bins(extend):
+    return len(np.arange(-extend - 5, extend + 6, 10)) - 1
+
+
+def plot_boundary_sizes(dims):
+    """(region counts, extends) on the plot kernels' boundaries, from the library's own constants (_lib.plot_dims): the word and window
+    edges, the profile tile and its halo; the usual windows, and the widest histogram counted in LDS with the first one that is not."""
+    tile, half, lds = dims["prof_tile"], dims["half"], dims["hist_lds_bins"]
+    ext_lds = max(e for e in range(5 * lds - 10, 5 * lds + 10) if plot_n_bins(e) <= lds)
+    return ([100, 101, 127, 128, 129, 199, 200, tile - 1, tile, tile + 1, tile + half, tile + half + 1, 2 * tile],
+            [0, 4, 5, 17, 250, ext_lds, ext_lds + 1])
+
+
+def make_plot_case(seed, dims=None):
+    """The plot family's inputs (no GPU): 1 .. 9 motifs of 1 .. 64 columns (some without a hit), R regions from the boundary list or
+    uniform in [100, 3000] with summits of their own (some outside any region), a window from the ladder or uniform in [0, 600]; hits
+    whose centres sit on a bin edge or within a base pair of one, on and around the first and the last edge, far outside, or anywhere
+    in the window, several per region; region scores with ties, ranked by plot.rank_order; ratio_control of every magnitude."""
+    from motifscan_amd import plot
+    if dims is None:
+        from motifscan_amd import _lib
+        dims = _lib.plot_dims()
+    rng = np.random.default_rng(PLOT_STREAM + seed)
+    sizes, ladder = plot_boundary_sizes(dims)
+    P = int(rng.integers(1, 10))
+    widths = rng.integers(1, 65, size=P).astype(np.int32)
+    R = int(rng.choice(sizes)) if rng.random() < 0.6 else int(rng.integers(100, 3001))
+    extend = int(rng.choice(ladder)) if rng.random() < 0.5 else int(rng.integers(0, 601))
+    summit_rel = rng.integers(-50, 2 * extend + 50, size=R).astype(np.int64)
+    edges = np.arange(-extend - 5, extend + 6, 10)
+    no_hits = rng.random() < 0.05
+    off, region, pos = [0], [], []
+    for m in range(P):
+        W = int(widths[m])
+        kind = 0 if no_hits else int(rng.integers(0, 7))     # 0: empty; 1: every region; 2: one rank end; 3: edges; 4 - 6: mixed
+        if kind == 0:
+            n = 0
+        elif kind == 1:
+            n = R + int(rng.integers(0, R))
+        elif kind == 2:
+            n = int(rng.integers(1, 4))
+        else:
+            n = int(rng.integers(1, 3 * R))
+        r = rng.integers(0, R, size=n)
+        if kind == 1:
+            r[:R] = np.arange(R)                                # a site in every region, some regions several times
+        # twice the distance centre - summit: on an edge, half a base pair and one base pair either side of one (as W's parity allows),
+        # anywhere in the window, or far outside it
+        e = edges[rng.integers(0, len(edges), size=n)]
+        end = rng.random(n) < 0.3
+        e[end] = np.where(rng.random(int(end.sum())) < 0.5, edges[0], edges[-1])
+        near = 2 * e + rng.integers(-2, 3, size=n)
+        spread = rng.integers(2 * edges[0] - 30, 2 * edges[-1] + 31, size=n)
+        far = rng.choice([-1, 1], size=n) * ((1 << 41) + rng.integers(0, 1000, size=n))
+        how = rng.random(n)
+        d2 = np.where(how < (0.9 if kind == 3 else 0.45), near, np.where(how < 0.97, spread, far))
+        d2 += (d2 - W) % 2                                      # 2 * pos = d2 - W + 2 * summit must be even
+        region.append(r)
+        pos.append((d2 - W) // 2 + summit_rel[r])
+        off.append(off[-1] + n)
+    off = np.array(off, dtype=np.int64)
+    region = np.concatenate(region).astype(np.int64) if region else np.zeros(0, dtype=np.int64)
+    pos = np.concatenate(pos).astype(np.int64) if pos else np.zeros(0, dtype=np.int64)
+    scores = np.round(rng.normal(0, 3, size=R), 0)              # integral: many ties, both zeros
+    scores[rng.random(R) < 0.05] = -0.0
+    order = plot.rank_order(scores)
+    for m in range(P):                                          # the hits of a "one rank end" motif go to rank 0 or rank R - 1
+        if 0 < off[m + 1] - off[m] < 4:
+            region[off[m]:off[m + 1]] = order[0 if rng.random() < 0.5 else R - 1]
+    for m in range(P):                                          # ms_result order: by region, then position
+        sl = slice(off[m], off[m + 1])
+        o = np.lexsort((pos[sl], region[sl]))
+        region[sl], pos[sl] = region[sl][o], pos[sl][o]
+    ratio = np.array([(1.0, 1 / 3, 7 / 13, 1e-300)[(m + seed) % 4] for m in range(P)])
+    return {"P": P, "R": R, "widths": widths, "extend": extend, "summit_rel": summit_rel, "motif_offsets": off, "region": region, "pos": pos,
+            "scores": scores, "order": order, "ratio": ratio, "dims": dims}
+
+
+def plot_smoothed_reference(y, k):
+    """sum_j k[j] * y[i - 5 + j] over y reflected at both ends, summed wider than double: np.longdouble where that is wider (x86), else
+    math.fsum on a strided sample of the ranks (both ends and every 37th).  Returns (the ranks, their reference values)."""
+    import math
+    half = len(k) // 2
+    R = len(y)
+    if np.finfo(np.longdouble).nmant > np.finfo(np.float64).nmant:
+        s = np.pad(y, half, mode="reflect").astype(np.longdouble)
+        ref = np.zeros(R, dtype=np.longdouble)
+        for j in range(len(k)):
+            ref += np.longdouble(k[j]) * s[j:j + R]
+        return np.arange(R), ref
+    s = np.pad(y, half, mode="reflect")
+    idx = np.unique(np.concatenate([np.arange(min(R, 2 * half + 2)), np.arange(0, R, 37), np.arange(max(0, R - 2 * half - 2), R)]))
+    return idx, np.array([math.fsum(float(k[j]) * float(s[i + j]) for j in range(len(k))) for i in idx])
+
+
+def plot_smoothed_differs(got, raw, k):
+    """None, or where a smoothed profile row leaves the exact sum of its 11 non-negative products k[j] * raw[..] by more than
+    16 * 2^-53 of it: gamma_11 of any summation order, fused or not, with room for the reference's own rounding."""
+    idx, ref = plot_smoothed_reference(raw, k)
+    err = np.abs(got[idx].astype(ref.dtype) - ref)
+    bad = np.flatnonzero(~(err <= 16 * 2.0 ** -53 * ref))
+    if len(bad):
+        i = int(bad[0])
+        return f"rank {int(idx[i])}: got {got[idx[i]]!r}, exact {ref[i]!r}"
+    return None
+
+
+def expected_plot(case):
+    """(dict(counts, n_sites, raw, smooth_k), tally) of a plot case: numpy alone -- np.histogram over the centres, the window ratio from
+    prefix counts over the ranked has-site flags; no GPU.  The tally counts what the case puts on the kernels' edges."""
+    from motifscan_amd import plot
+    from test_plot_host import flat_histogram, flat_profiles
+    P, R, ext, off, dims = case["P"], case["R"], case["extend"], case["motif_offsets"], case["dims"]
+    counts, n_sites = flat_histogram(off, case["region"], case["pos"], case["widths"], case["summit_rel"], ext)
+    raw = flat_profiles(off, case["region"], case["order"], case["ratio"], np.arange(P), False)
+    n = int(off[-1])
+    m = np.repeat(np.arange(P), np.diff(off))
+    d2 = 2 * (case["pos"] - case["summit_rel"][case["region"]]) + case["widths"][m].astype(np.int64)      # twice centre - summit
+    first, last = 2 * (-ext - 5), 2 * (-ext - 5) + 20 * counts.shape[1]
+    with_site = np.array([len(np.unique(case["region"][off[i]:off[i + 1]])) for i in range(P)], dtype=np.int64)
+    f, tile, half = R // 100, dims["prof_tile"], dims["half"]
+    tally = {"sites": n, "cases_without_sites": int(n == 0), "in_range": int(counts.sum()),
+             "on_edge": int(((d2 - first) % 20 == 0)[(d2 >= first) & (d2 <= last)].sum()), "on_last_edge": int((d2 == last).sum()),
+             "below_first": int((d2 < first).sum()), "beyond_last": int((d2 > last).sum()), "half_bp": int((d2 % 2 != 0).sum()),
+             "empty_rows": int((with_site == 0).sum()), "full_rows": int((with_site == R).sum()),
+             "cases_r_mult_64": int(R % 64 == 0), "cases_multi_tile": int(R > tile), "cases_short_last_tile": int(0 < R % tile < half),
+             "cases_global_bins": int(counts.shape[1] > dims["hist_lds_bins"]),
+             "clipped_head": P * f, "clipped_tail": P * (f - 1), "width_one": int((case["widths"] == 1).sum()),
+             "wide": int((case["widths"] >= 64).sum())}
+    return {"counts": counts, "n_sites": n_sites, "raw": raw, "smooth_k": plot.smoothing_weights()}, tally
+
+
+def run_plot_case(seed, oracle, _lib):
+    """The device's histogram and profiles of a case against expected_plot: counts and unsmoothed profiles exactly, the smoothed
+    profiles within the derived bound, a range of motifs against the rows of the whole call.  `oracle` is not used."""
+    case = make_plot_case(seed, _lib.plot_dims())
+    want, tally = expected_plot(case)
+    P, R = case["P"], case["R"]
+    n = int(case["motif_offsets"][-1])
+    res = _lib.result_from_hits(P, R, case["motif_offsets"], case["region"], case["pos"], np.zeros(n), np.ones(n, dtype=np.int8))
+    pw = _lib.PwmSet.from_matrices([np.full((4, int(w)), 0.25) for w in case["widths"]])
+    try:
+        counts, n_sites = res.site_histogram(pw, case["summit_rel"], case["extend"])
+        if not np.array_equal(counts, want["counts"]) or not np.array_equal(n_sites, want["n_sites"]):
+            bad = np.argwhere(counts != want["counts"])
+            return False, f"plot seed {seed}: histogram differs ({len(bad)} bins, first (motif, bin) {bad[:1].tolist()})"
+        m0 = seed % P
+        m1 = min(P, m0 + 1 + seed % 3)
+        part, part_n = res.site_histogram(pw, case["summit_rel"], case["extend"], m0, m1)
+        if not np.array_equal(part, counts[m0:m1]) or not np.array_equal(part_n, n_sites[m0:m1]):
+            return False, f"plot seed {seed}: histogram of motifs [{m0}, {m1}) differs from those rows of the whole call"
+        raw = res.rank_profile(case["order"], case["ratio"], smoothed=False)
+        if not same_bits(raw, want["raw"]):
+            return False, f"plot seed {seed}: the bits of the unsmoothed profile differ"
+        sm = res.rank_profile(case["order"], case["ratio"], want["smooth_k"])
+        for m in range(P):
+            bad = plot_smoothed_differs(sm[m], want["raw"][m], want["smooth_k"])
+            if bad:
+                return False, f"plot seed {seed}: smoothed profile of motif {m}, {bad}"
+        part = res.rank_profile(case["order"], case["ratio"][m0:m1], want["smooth_k"], m0, m1)
+        if not same_bits(part, sm[m0:m1]):
+            return False, f"plot seed {seed}: profile of motifs [{m0}, {m1}) differs from those rows of the whole call"
+    finally:
+        res.close()
+        pw.close()
+    return True, tally
+
+
+FAMILIES = {"variants": run_variants_case, "alleles": run_alleles_case, "best": run_best_case, "once": run_once_case, "plot": run_plot_case}
 
 # What the seeds of a family must put on the boundary, summed over SEEDS[family] from the oracle's output alone: conditions, not
 # measurements.  If a change to a generator misses one, the seed range changes -- not the threshold, not the mix of matrix kinds.
-SEEDS = {"variants": range(30), "alleles": range(30), "best": range(30), "sweep": range(40), "once": range(40)}
+SEEDS = {"variants": range(30), "alleles": range(30), "best": range(30), "sweep": range(40), "once": range(40), "plot": range(40)}
 CONDITIONS = {"variants": {"near_fail": 10_000, "near_pass": 10_000, "records": 100_000},
               "alleles": {"near_fail": 5_000, "near_pass": 5_000, "gained": 500, "lost": 500},
               "best": {"tied_cells": 1_000, "tied_across_segments": 300},
               "sweep": {"sites": 100_000},
               "once": {"sites": 500_000, "shared_sites": 500_000, "shared_by_8": 100_000, "flush_end": 5_000, "flush_start": 5_000,
                        "one_base_out": 2_000, "one_base_before": 2_000, "touching": 20, "equal_starts": 200, "empty_regions": 100,
-                       "mixed_spans": 10, "cases_local": 10, "cases_global": 3}}
+                       "mixed_spans": 10, "cases_local": 10, "cases_global": 3},
+              "plot": {"sites": 200_000, "in_range": 150_000, "on_edge": 20_000, "on_last_edge": 3_000, "below_first": 10_000, "beyond_last": 10_000,
+                       "half_bp": 100_000, "empty_rows": 20, "full_rows": 20, "cases_r_mult_64": 5, "cases_multi_tile": 15,
+                       "cases_short_last_tile": 3, "cases_global_bins": 2, "clipped_head": 1_000, "clipped_tail": 1_000}}
 SWEEP_MAX_EMPTY = 10                                    # at most this many of the sweep cases may have no window at all
+PLOT_MAX_EMPTY = 4                                      # at most this many of the plot cases may have no hit at all
 ONCE_MAX_EMPTY = 12                                     # at most this many of the scan-once cases may have no site at all
 ONCE_SEEN = {"span_start_residues": 32, "strand_masks": 3, "layouts": len(ONCE_LAYOUTS)}      # every one of them must occur
 
 
 def unmet_conditions(family, total):
     """The conditions a family's summed tally misses, as text (empty: all met).  Every family must also meet a motif with max_raw == 0
-    and one of a single column, and -- but for the sweep, whose generator draws 1 .. 33 columns -- one of 64 columns or more."""
-    need = dict(CONDITIONS[family], max_raw_zero=1, width_one=1)
+    (but for the plot family, which has widths and no matrices) and one of a single column, and -- but for the sweep, whose generator
+    draws 1 .. 33 columns -- one of 64 columns or more."""
+    need = dict(CONDITIONS[family], width_one=1)
+    if family != "plot":
+        need["max_raw_zero"] = 1
     if family != "sweep":
         need["wide"] = 1
     bad = [f"{k}: {total.get(k, 0)} < {n}" for k, n in need.items() if total.get(k, 0) < n]
     if family == "sweep" and total.get("cases_without_windows", 0) > SWEEP_MAX_EMPTY:
         bad.append(f"cases_without_windows: {total['cases_without_windows']} > {SWEEP_MAX_EMPTY}")
+    if family == "plot" and total.get("cases_without_sites", 0) > PLOT_MAX_EMPTY:
+        bad.append(f"cases_without_sites: {total['cases_without_sites']} > {PLOT_MAX_EMPTY}")
     if family == "once":
         bad += [f"{k}: {len(total.get(k, ()))} of {n} seen" for k, n in ONCE_SEEN.items() if len(total.get(k, ())) != n]
         if total.get("cases_without_sites", 0) > ONCE_MAX_EMPTY:
@@ -1024,6 +1210,7 @@ def main():
     ap.add_argument("--alleles", action="store_true", help="fuzz ms_scan_alleles instead of ms_scan")
     ap.add_argument("--best", action="store_true", help="fuzz ms_scan_best instead of ms_scan")
     ap.add_argument("--once", action="store_true", help="fuzz ms_scan_regions_once instead of ms_scan")
+    ap.add_argument("--plot", action="store_true", help="fuzz ms_result_site_histogram and ms_result_rank_profile instead of ms_scan")
     a = ap.parse_args()
     from oracle import oracle
     oracle.build()

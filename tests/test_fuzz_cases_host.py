@@ -1,5 +1,5 @@
 """
-The cases of tests/fuzz_parity.py's variant, allele, best-site, sweep and scan-once families without a GPU: that their seeds put what they should
+The cases of tests/fuzz_parity.py's variant, allele, best-site, sweep, scan-once and plot families without a GPU: that their seeds put what they should
 on the decision boundary (fuzz_parity.CONDITIONS, tallied from the oracle's output alone -- the same conditions the GPU tests assert on
 what they compared), and that the builders of the expected records are right, against the same scoring in plain Python floats (columns
 in order, raw / max_raw, score - cutoff >= -1e-10) on every seed small enough for it.  For the scan-once family also that its tally's
@@ -77,6 +77,37 @@ def test_generators_reach_the_edges(expected):
     assert {c["strand"] for c in b} == {1, 2, 3}
     assert any(len(s) > 2 * seg for c in b for s in c["seqs"]) and any(s == "" for c in b for s in c["seqs"])
     assert any(np.isnan(w[0]).any() for _, _, w, _ in expected["best"]) and any((w[1] >= 0).any() for _, _, w, _ in expected["best"])
+
+
+def test_plot_seeds_meet_the_conditions_and_the_integer_bin_rule():
+    """The plot family needs no oracle: its tallies come from numpy's own histogram and prefix counts.  Every case is also binned by the
+    rule the kernel uses -- t = 2 * (pos - summit) + W + 2 * (extend + 5) in integers, bin t / 20, the last bin closed -- which must
+    agree with np.histogram everywhere, and a sample of ranks is redone as the reference's slice sum."""
+    total, dims = {}, _lib.plot_dims()
+    for seed in fp.SEEDS["plot"]:
+        case = fp.make_plot_case(seed, dims)
+        want, tally = fp.expected_plot(case)
+        fp.add_tally(total, tally)
+        off, n_bins = case["motif_offsets"], want["counts"].shape[1]
+        assert n_bins == fp.plot_n_bins(case["extend"]) and sorted(case["order"].tolist()) == list(range(case["R"])), seed
+        m = np.repeat(np.arange(case["P"]), np.diff(off))
+        t = 2 * (case["pos"] - case["summit_rel"][case["region"]]) + case["widths"][m].astype(np.int64) + 2 * (case["extend"] + 5)
+        b = np.where(t == 20 * n_bins, n_bins - 1, t // 20)
+        ok = (t >= 0) & (b < n_bins)
+        rule = np.zeros_like(want["counts"])
+        np.add.at(rule, (m[ok], b[ok]), 1)
+        assert np.array_equal(rule, want["counts"]) and tally["in_range"] == int(ok.sum()), seed
+        R, f = case["R"], case["R"] // 100
+        for row in range(case["P"]):
+            has = np.zeros(R, dtype=bool)
+            has[case["region"][off[row]:off[row + 1]]] = True
+            flags = has[case["order"]].tolist()
+            for i in {0, 1, f - 1, f, f + 1, R // 2, R - f - 1, R - f, R - 2, R - 1}:
+                head, tail = max(0, i - f), min(i + f, R)
+                assert want["raw"][row, i] == sum(flags[head:tail]) / (tail - head) / float(case["ratio"][row]), (seed, row, i)
+    print(f"plot: seeds {fp.SEEDS['plot']}: {fp.shown(total)}")
+    assert not fp.unmet_conditions("plot", total)
+    assert 0 < total["cases_without_sites"] <= fp.PLOT_MAX_EMPTY
 
 
 # ------------------------------------------------------------------------------------------------ the builders, against Python floats

@@ -2,7 +2,9 @@
 The boundary fuzz of tests/fuzz_parity.py on the four entry points beside ms_scan that judge windows -- ms_scan_variants (ms_variants.hip),
 ms_scan_alleles (ms_alleles.hip), ms_scan_best (ms_best.hip) and ms_scan_sweep (ms_sweep.hip) -- against the pinned oracle: tie-rich
 matrices, cutoffs on attainable scores and one ulp / 1e-10 either side, huge and tiny magnitudes, max_raw == 0, N runs and lower case.
-Every comparison is exact (integers by value, scores by their bits).  After its seeds each test asserts, on the tallies of what was
+The plot family (ms_result_site_histogram, ms_result_rank_profile; ms_plotdata.hip) runs beside them over synthetic hit arrays: centres
+on and around the bin edges, region counts on the rank words' and profile tiles' edges, against numpy alone.
+Every comparison is exact (integers by value, scores by their bits; the smoothed profiles within their derived bound).  After its seeds each test asserts, on the tallies of what was
 compared, that the seeds did sit on the boundary (fuzz_parity.CONDITIONS); tests/test_fuzz_cases_host.py asserts the same without a GPU.
 """
 import pytest
@@ -20,7 +22,7 @@ def _device():
     _lib.set_device(0)
 
 
-@pytest.mark.parametrize("family", ["variants", "alleles", "best"])
+@pytest.mark.parametrize("family", ["variants", "alleles", "best", "plot"])
 def test_fuzz_entry_point(oracle, family):
     total = {}
     for seed in fuzz_parity.SEEDS[family]:

@@ -4,14 +4,16 @@ smooth() of the histogram rows), argument validation and the drop-ins' early ret
 (tests/golden/ref_plot.npz, made by tests/golden/make_golden_plot.py).  The two device calls are replaced by numpy restatements of
 the contract (`np_histogram`, `np_profiles` below; the GPU tests compare the device against the same restatements).
 """
+import ctypes
 import logging
 import os
+import re
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
-from motifscan_amd import plot
+from motifscan_amd import _lib, plot
 from motifscan_amd.sites import MotifSite, MotifSites
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_plot.npz")
@@ -42,22 +44,22 @@ def flat_sites(motif_sites):
     return np.array(off, dtype=np.int64), np.array(region, dtype=np.int64), np.array(start, dtype=np.int64)
 
 
-def np_histogram(motif_sites, pwms, summits, extend):
-    """plot.py:65-68: np.histogram of site.start + W / 2 - summit per motif -> (counts, n_sites)."""
-    off, region, start = flat_sites(motif_sites)
+def flat_histogram(off, region, start, widths, summits, extend):
+    """plot.py:65-68 over flat hit arrays: np.histogram of start + W / 2 - summit[region] per motif -> (counts, n_sites)."""
+    off, region, start = np.asarray(off, dtype=np.int64), np.asarray(region, dtype=np.int64), np.asarray(start, dtype=np.int64)
     summits = np.asarray(summits, dtype=np.int64)
     edges = np.arange(-extend - 5, extend + 6, 10)
-    counts = np.zeros((len(pwms), len(edges) - 1), dtype=np.int64)
-    for m, pwm in enumerate(pwms):
+    counts = np.zeros((len(widths), len(edges) - 1), dtype=np.int64)
+    for m, w in enumerate(widths):
         sl = slice(off[m], off[m + 1])
-        d = start[sl] + pwm.length / 2 - summits[region[sl]]
+        d = start[sl] + int(w) / 2 - summits[region[sl]]
         counts[m] = np.histogram(d, bins=edges)[0]
     return counts, np.diff(off)
 
 
-def np_profiles(motif_sites, order, ratio, rows, smoothed):
-    """plot.py:133-142 per motif: prefix counts over the ranked has-site flags, the window ratio (two divisions), smooth()."""
-    off, region, _ = flat_sites(motif_sites)
+def flat_profiles(off, region, order, ratio, rows, smoothed):
+    """plot.py:133-142 per motif of `rows` over flat hit arrays: prefix counts over the ranked has-site flags, the window ratio (two
+    divisions), smooth().  ratio is indexed by motif."""
     R = len(order)
     f = R // 100
     idx = np.arange(R)
@@ -70,6 +72,18 @@ def np_profiles(motif_sites, order, ratio, rows, smoothed):
         y = ((pre[tail] - pre[head]) / (tail - head)) / ratio[m]
         out[i] = plot.smooth(y) if smoothed else y
     return out
+
+
+def np_histogram(motif_sites, pwms, summits, extend):
+    """plot.py:65-68: np.histogram of site.start + W / 2 - summit per motif -> (counts, n_sites)."""
+    off, region, start = flat_sites(motif_sites)
+    return flat_histogram(off, region, start, [pwm.length for pwm in pwms], summits, extend)
+
+
+def np_profiles(motif_sites, order, ratio, rows, smoothed):
+    """plot.py:133-142 per motif: prefix counts over the ranked has-site flags, the window ratio (two divisions), smooth()."""
+    off, region, _ = flat_sites(motif_sites)
+    return flat_profiles(off, region, order, ratio, rows, smoothed)
 
 
 @pytest.fixture
@@ -275,3 +289,71 @@ def test_drop_ins_draw_the_reference_bars(gold, host_device, tmp_path, monkeypat
     assert np.array_equal(np.stack([h for _, h in bars]), gold["enr_101_profile"])
     assert all(np.array_equal(x, np.arange(1, 102)) for x, _ in bars)
     assert len([n for n in os.listdir(tmp_path / "plots") if n.endswith("_sites_enrichment.pdf")]) == 4
+
+
+# --------------------------------------------------------------- the restatement at sizes without a golden; the kernels' constants --
+
+def literal_profile(flags, ratio_control):
+    """plot.py:135-140 as ms_plotdata.hip's header describes it: per rank the slice sum of the ranked has-site flags over the
+    2 * (R / 100) neighbouring ranks, over the slice's length, over ratio_control -- plain Python, one rank at a time."""
+    R = len(flags)
+    f = R // 100
+    out = []
+    for idx in range(R):
+        head = max(0, idx - f)
+        tail = min(idx + f, R)
+        ratio_input = sum(flags[head:tail]) / (tail - head)
+        out.append(ratio_input / ratio_control)
+    return out
+
+
+@pytest.mark.parametrize("size", ["128", "200", "tile-1", "tile+1", "tile+half"])
+def test_profile_restatement_equals_the_literal_slice_sum(size):
+    d = _lib.plot_dims()
+    R = {"tile-1": d["prof_tile"] - 1, "tile+1": d["prof_tile"] + 1, "tile+half": d["prof_tile"] + d["half"]}.get(size) or int(size)
+    rng = np.random.default_rng(R)
+    k = np.arange(R)
+    rows = [np.zeros(0, dtype=np.int64), np.concatenate([k, k[::9]]), np.array([0]), np.array([R - 1]), k[(k % 64 == 63) | (k % 64 == 0)],
+            np.flatnonzero(rng.random(R) < 0.3)]
+    ratio = np.array([1.0, 1 / 3, 7 / 13, 1e-300, 1.0, 1 / 3])
+    for order in (np.arange(R), np.arange(R)[::-1].copy(), rng.permutation(R)):
+        off = np.concatenate([[0], np.cumsum([len(r) for r in rows])])
+        region = np.concatenate([order[r] for r in rows])                       # row m has its sites at the ranks rows[m]
+        raw = flat_profiles(off, region, order, ratio, np.arange(len(rows)), False)
+        sm = flat_profiles(off, region, order, ratio, np.arange(len(rows)), True)
+        for m, ranks in enumerate(rows):
+            flags = np.zeros(R, dtype=bool)
+            flags[ranks] = True
+            want = literal_profile(flags.tolist(), float(ratio[m]))
+            assert raw[m].tolist() == want, (size, m)
+            assert np.array_equal(sm[m], plot.smooth(np.array(want))), (size, m)
+        # a sub-set of rows indexes ratio by motif
+        assert np.array_equal(flat_profiles(off, region, order, ratio, [5, 2], False), raw[[5, 2]])
+
+
+def test_plot_dims_are_constants_of_the_build():
+    L = _lib.lib()
+    out = (ctypes.c_int32 * 6)()
+    assert L.ms_debug_plot_dims(out) == _lib.MS_OK
+    d = _lib.plot_dims()
+    assert list(out) == [d[k] for k in ("hist_lds_bins", "hist_hits_per_block", "hist_max_blocks", "scan_threads", "prof_tile", "half")]
+    assert all(v > 0 for v in out)
+    assert 4 * d["hist_lds_bins"] <= 64 * 1024                                   # 32-bit counters in one block's static LDS
+    assert d["scan_threads"] % 64 == 0 and d["scan_threads"] <= 1024              # whole waves, one block
+    assert 2 * d["half"] + 1 == plot.SMOOTH_WINDOW == len(plot.smoothing_weights())
+    assert d["prof_tile"] > 2 * d["half"]
+    assert L.ms_debug_plot_dims(None) == _lib.MS_ERR_INVALID
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "motifscan_amd_debug.h")) as fh:
+        assert re.search(r"\bint\s+ms_debug_plot_dims\s*\(\s*int32_t\s+out\s*\[\s*6\s*\]\s*\)", fh.read())
+
+
+def test_bin_count_crosses_the_lds_limit_where_the_device_tests_assume():
+    """include/motifscan_amd.h: n_bins = (2 * extend + 11 + 9) / 10 - 1.  It equals numpy's count around the limit, reaches
+    hist_lds_bins at 5 extends, and is one more at the next: the two windows tests/test_gpu_plot_boundaries.py runs."""
+    lds = _lib.plot_dims()["hist_lds_bins"]
+    n_bins = {e: (2 * e + 11 + 9) // 10 - 1 for e in range(5 * lds - 12, 5 * lds + 12)}
+    assert all(n == len(plot.bin_edges(e)) - 1 for e, n in n_bins.items())
+    at_limit = [e for e, n in n_bins.items() if n == lds]
+    assert at_limit == list(range(5 * lds - 5, 5 * lds)) and n_bins[5 * lds] == lds + 1
+    for e in (0, 4, 5, 17, 250):
+        assert (2 * e + 11 + 9) // 10 - 1 == len(plot.bin_edges(e)) - 1 <= lds
