@@ -92,6 +92,24 @@ int ms_debug_pair_lds_pair_limit(int64_t limit, int64_t *previous);
  * boundary size from here.  Needs no GPU. */
 int ms_debug_plot_dims(int32_t out[6]);
 
+/* The sizes at which the kernels either side of the scan change path (ms_seqset.hip, ms_background.hip, ms_pwmset.hip,
+ * ms_annotation.hip), as constants of the build: out[0] the bases of one block's tile of the base count; out[1] the chromosomes of a
+ * tile counted in LDS (later ones add to global memory); out[2] the candidates per block of the window filter; out[3] the bases per
+ * block of the pack and extract kernels; out[4] the regions per block of ms_genes_nearest_tss; out[5] the genes per LDS tile of it;
+ * out[6] the regions per block of ms_genes_promoter_overlap; out[7] the scores ms_score_ranks holds at once (its motifs go in batches
+ * of out[7] / n_seqs, at least one).  Tests take every boundary size from here.  Needs no GPU. */
+int ms_debug_genome_dims(int32_t out[8]);
+
+/* The four device arrays of a built sequence set on the host, in the layout of ms_debug_host_pack (codes [2 x ceil(n / 32)], nmask
+ * [ceil(n / 32)], blk2reg [(n + 63) / 64 + 1], blkinfo [4 x that]); any pointer may be NULL.  MS_ERR_INVALID for a set whose planes are
+ * not on the device yet (a batch stream's upload-only set before its scan).  Needs a GPU. */
+int ms_debug_seqset_planes(const ms_seqset *seqs, uint32_t *codes, uint32_t *nmask, int32_t *blk2reg, int32_t *blkinfo);
+
+/* ms_score_ranks scores its motifs in batches of (budget / n_seqs, at least one): elems > 0 sets the budget for the calls that follow
+ * in this process, so that a small case runs several batches, 0 gives it back to the library.  *previous (may be NULL) = the value
+ * before.  The result does not depend on it: a test proves that with batches of one and of three motifs.  Needs no GPU. */
+int ms_debug_score_rank_budget(int64_t elems, int64_t *previous);
+
 #ifdef __cplusplus
 }
 #endif

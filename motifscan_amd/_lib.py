@@ -162,6 +162,9 @@ def lib():
         "ms_debug_cooc_chunk_regions": (c_int, []),
         "ms_debug_plot_dims": (c_int, [pi32]),
         "ms_debug_pair_lds_pair_limit": (c_int, [c_i64, pi64]),
+        "ms_debug_genome_dims": (c_int, [pi32]),
+        "ms_debug_seqset_planes": (c_int, [vp, pu32, pu32, pi32, pi32]),
+        "ms_debug_score_rank_budget": (c_int, [c_i64, pi64]),
         "ms_score": (c_int, [vp, vp, c_int, pd]),
         "ms_score_ranks": (c_int, [vp, vp, c_int, pi64, c_i32, pd]),
         "ms_dedup_hits": (c_int, [pi64, c_i32, pi32, pi64, pi64, pd, pi8, pu8]),
@@ -1173,6 +1176,37 @@ def plot_dims():
     out = np.zeros(6, dtype=np.int32)
     check(lib().ms_debug_plot_dims(ptr(out, ctypes.c_int32)))
     return dict(zip(("hist_lds_bins", "hist_hits_per_block", "hist_max_blocks", "scan_threads", "prof_tile", "half"), out.tolist()))
+
+
+def genome_dims():
+    """ms_debug_genome_dims: the sizes at which the kernels either side of the scan change path -- dict(count_tile_bases, lds_chroms,
+    filter_threads, pack_block_bases, near_threads, gene_tile, overlap_threads, rank_budget); constants of the build, no GPU."""
+    out = np.zeros(8, dtype=np.int32)
+    check(lib().ms_debug_genome_dims(ptr(out, ctypes.c_int32)))
+    return dict(zip(("count_tile_bases", "lds_chroms", "filter_threads", "pack_block_bases", "near_threads", "gene_tile", "overlap_threads",
+                     "rank_budget"), out.tolist()))
+
+
+def seqset_planes(seqs):
+    """ms_debug_seqset_planes: (codes, nmask, blk2reg, blkinfo [n, 4]) of a SeqSet or a ResidentGenome as they are on the device, in
+    host_pack's layout."""
+    n = ctypes.c_int64()
+    check(lib().ms_seqset_size(seqs.h, None, ctypes.byref(n)))
+    n = n.value
+    units, blocks = (n + 31) // 32, (n + 63) // 64 + 1
+    codes, nmask = np.zeros(2 * units, dtype=np.uint32), np.zeros(units, dtype=np.uint32)
+    blk2reg, blkinfo = np.zeros(blocks, dtype=np.int32), np.zeros((blocks, 4), dtype=np.int32)
+    check(lib().ms_debug_seqset_planes(seqs.h, ptr(codes, ctypes.c_uint32), ptr(nmask, ctypes.c_uint32), ptr(blk2reg, ctypes.c_int32),
+                                       ptr(blkinfo, ctypes.c_int32)))
+    return codes, nmask, blk2reg, blkinfo
+
+
+def score_rank_budget(elems):
+    """ms_debug_score_rank_budget: the scores score_ranks holds at once for the calls that follow (0 = the library's own); returns the
+    value before."""
+    prev = ctypes.c_int64()
+    check(lib().ms_debug_score_rank_budget(int(elems), ctypes.byref(prev)))
+    return prev.value
 
 
 def pair_lds_pair_limit(limit):

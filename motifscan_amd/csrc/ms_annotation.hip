@@ -169,6 +169,9 @@ inline bool randbelow(const uint32_t *words, int64_t n_words, int64_t &pos, uint
 }
 
 }  // namespace
+
+void annotation_dims(int32_t out[3]) { out[0] = kNearThreads; out[1] = kGeneTile; out[2] = kOverlapThreads; }
+
 }  // namespace ms
 
 using namespace ms;

@@ -152,6 +152,17 @@ using namespace ms;
 
 extern "C" {
 
+int ms_debug_genome_dims(int32_t out[8]) {
+    if (!out) { set_error("NULL out"); return MS_ERR_INVALID; }
+    out[0] = kCountThreads * kUnitsPerThread * 32;
+    out[1] = kLdsChroms;
+    out[2] = kFilterThreads;
+    out[3] = seqset_block_bases();
+    annotation_dims(out + 4);
+    out[7] = (int32_t) score_rank_budget_default();
+    return MS_OK;
+}
+
 int ms_genome_base_counts(const ms_genome *g, int64_t *counts) {
     if (!g) { set_error("NULL genome"); return MS_ERR_INVALID; }
     const ms_seqset *G = reinterpret_cast<const ms_seqset *>(g);

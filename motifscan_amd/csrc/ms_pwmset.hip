@@ -1,6 +1,7 @@
 // ms_pwmset.hip -- the PWM set handle: creation and cutoffs, its lazily cached device copies and pre-filter plan, the two scoring entry
 // points that need nothing else (ms_score, ms_score_ranks) and the host-only plan views of include/motifscan_amd_debug.h.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <climits>
 #include <cstring>
@@ -14,6 +15,10 @@
 namespace ms {
 
 // -------------------------------------------------------------------------- score --
+
+constexpr int64_t kRankBudget = 1LL << 27;       // scores held at once by ms_score_ranks: its motifs go in batches of kRankBudget / R
+static std::atomic<int64_t> g_rank_budget{0};    // ms_debug_score_rank_budget: 0 = kRankBudget
+int64_t score_rank_budget_default() { return kRankBudget; }
 
 // c_score (cscore.c:191-224): one thread per (sequence, motif); first W bases only.
 __global__ void __launch_bounds__(256) score_kernel(const DevSeq S, const DevPwm Pw, int strand_mask,
@@ -358,7 +363,9 @@ int ms_score_ranks(const ms_pwmset *pwms_c, const ms_seqset *seqs, int strand_ma
     std::lock_guard<std::mutex> lk_pwm(pwms->mu);
     if ((rc = pwmset_upload(pwms, c->device, c->stream))) return rc;
     const size_t R = (size_t) seqs->R;
-    const int32_t batch = (int32_t) std::max<size_t>(1, std::min<size_t>((size_t) pwms->P, ((size_t) 1 << 27) / R));
+    const int64_t set_budget = g_rank_budget.load();
+    const size_t budget = (size_t) (set_budget > 0 ? set_budget : kRankBudget);
+    const int32_t batch = (int32_t) std::max<size_t>(1, std::min<size_t>((size_t) pwms->P, budget / R));
     double *d_scores = nullptr, *d_sorted = nullptr, *d_out = nullptr;
     int64_t *d_ranks = nullptr;
     void *d_tmp = nullptr;
@@ -390,6 +397,13 @@ int ms_score_ranks(const ms_pwmset *pwms_c, const ms_seqset *seqs, int strand_ma
     cleanup();
     if (rc) return rc;
     if (he != hipSuccess) { set_error("score/rank kernels failed: %s", hipGetErrorString(he)); return MS_ERR_RUNTIME; }
+    return MS_OK;
+}
+
+int ms_debug_score_rank_budget(int64_t elems, int64_t *previous) {
+    if (elems < 0) { set_error("budget must be >= 0 (0 = the library's own)"); return MS_ERR_INVALID; }
+    const int64_t old = g_rank_budget.exchange(elems);
+    if (previous) *previous = old;
     return MS_OK;
 }
 

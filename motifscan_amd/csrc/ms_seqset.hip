@@ -15,8 +15,11 @@ namespace ms {
 
 // --------------------------------------------------------------------------- pack --
 
+constexpr int kPackThreads = 256;                // pack_kernel, extract_kernel, blk2reg_kernel: one block
+int32_t seqset_block_bases() { return kPackThreads * 32; }
+
 // One thread per 32 bases: two 16-byte loads, one 8-byte + one 4-byte store.
-__global__ void __launch_bounds__(256) pack_kernel(const uint8_t *__restrict__ ascii, int64_t n_bases,
+__global__ void __launch_bounds__(kPackThreads) pack_kernel(const uint8_t *__restrict__ ascii, int64_t n_bases,
                                                    uint32_t *__restrict__ codes, uint32_t *__restrict__ nmask,
                                                    int64_t n_units, int aligned16) {
     const int64_t u = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
@@ -67,7 +70,7 @@ __global__ void __launch_bounds__(256) pack_kernel(const uint8_t *__restrict__ a
 // -> pysam fetch, scanner.py:71-87 / genome/__init__.py:117-135): one thread per 32 output bases,
 // which may straddle several regions.  src_start[r] is the region's first base in the genome's
 // packed coordinates; dst_off[r] its first base in the output.
-__global__ void __launch_bounds__(256) extract_kernel(const uint32_t *__restrict__ gcodes, const uint32_t *__restrict__ gnmask,
+__global__ void __launch_bounds__(kPackThreads) extract_kernel(const uint32_t *__restrict__ gcodes, const uint32_t *__restrict__ gnmask,
                                                       const int64_t *__restrict__ src_start, const int64_t *__restrict__ dst_off,
                                                       int64_t R, int64_t n_out, uint32_t *__restrict__ codes,
                                                       uint32_t *__restrict__ nmask) {
@@ -101,7 +104,7 @@ __global__ void __launch_bounds__(256) extract_kernel(const uint32_t *__restrict
 // blk2reg[b] = region that holds position 64*b (part of the extraction stage, next to pack_kernel); blkinfo[b] = the same region with
 // its own and the next two regions' starts RELATIVE to 64*b as 32-bit numbers -- everything rescore_kernel needs to place a position,
 // in one 16-byte read (the fp64 stage pays per vector-memory instruction); region -1: a start lies more than 2^31 bases away, look it up
-__global__ void __launch_bounds__(256) blk2reg_kernel(const int64_t *__restrict__ offsets, int64_t R, int64_t n_blocks,
+__global__ void __launch_bounds__(kPackThreads) blk2reg_kernel(const int64_t *__restrict__ offsets, int64_t R, int64_t n_blocks,
                                                       int32_t *__restrict__ blk2reg, int4 *__restrict__ blkinfo, int all_far) {
     const int64_t b = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= n_blocks) return;
@@ -117,7 +120,7 @@ static int launch_extract(const uint32_t *gcodes, const uint32_t *gnmask, const 
                           int64_t R, int64_t n_out, uint32_t *codes, uint32_t *nmask, hipStream_t st) {
     const int64_t n_units = (n_out + 31) / 32;
     if (n_units == 0) return MS_OK;
-    hipLaunchKernelGGL(extract_kernel, dim3((unsigned) ((n_units + 255) / 256)), dim3(256), 0, st, gcodes, gnmask, src_start,
+    hipLaunchKernelGGL(extract_kernel, dim3((unsigned) ((n_units + kPackThreads - 1) / kPackThreads)), dim3(kPackThreads), 0, st, gcodes, gnmask, src_start,
                        dst_off, R, n_out, codes, nmask);
     MS_HIP(hipGetLastError());
     return MS_OK;
@@ -126,7 +129,7 @@ static int launch_extract(const uint32_t *gcodes, const uint32_t *gnmask, const 
 static int launch_blk2reg(const int64_t *offsets, int64_t R, int64_t n_bases, int32_t *blk2reg, int4 *blkinfo, hipStream_t st) {
     const int64_t n_blocks = (n_bases + 63) / 64 + 1;
     const int all_far = measure_env("MS_BLKINFO_FAR") ? 1 : 0;          // test aid: every block record says "look the region up" (starts beyond 32 bits)
-    hipLaunchKernelGGL(blk2reg_kernel, dim3((unsigned) ((n_blocks + 255) / 256)), dim3(256), 0, st, offsets, R, n_blocks,
+    hipLaunchKernelGGL(blk2reg_kernel, dim3((unsigned) ((n_blocks + kPackThreads - 1) / kPackThreads)), dim3(kPackThreads), 0, st, offsets, R, n_blocks,
                        blk2reg, blkinfo, all_far);
     MS_HIP(hipGetLastError());
     return MS_OK;
@@ -136,7 +139,7 @@ static int launch_pack(const uint8_t *ascii, int64_t n_bases, uint32_t *codes, u
     const int64_t n_units = (n_bases + 31) / 32;
     if (n_units == 0) return MS_OK;
     const int aligned16 = (reinterpret_cast<uintptr_t>(ascii) & 15u) == 0;
-    hipLaunchKernelGGL(pack_kernel, dim3((unsigned) ((n_units + 255) / 256)), dim3(256), 0, st, ascii, n_bases,
+    hipLaunchKernelGGL(pack_kernel, dim3((unsigned) ((n_units + kPackThreads - 1) / kPackThreads)), dim3(kPackThreads), 0, st, ascii, n_bases,
                        codes, nmask, n_units, aligned16);
     MS_HIP(hipGetLastError());
     return MS_OK;
@@ -458,6 +461,19 @@ int ms_debug_host_pack(const char *bases, const int64_t *offsets, int64_t n_seqs
     if (n > 0 && !bases) { set_error("bases is NULL"); return MS_ERR_INVALID; }
     host_pack_units(reinterpret_cast<const uint8_t *>(bases), n, 0, (n + 31) / 32, codes, nmask);
     host_region_hints(offsets, n_seqs, 0, (n + 63) / 64 + 1, blk2reg, blkinfo, false);
+    return MS_OK;
+}
+
+// the four device arrays of a built set on the host, in ms_debug_host_pack's layout (any pointer may be NULL)
+int ms_debug_seqset_planes(const ms_seqset *s, uint32_t *codes, uint32_t *nmask, int32_t *blk2reg, int32_t *blkinfo) {
+    if (!s) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    if (!s->built || s->pack_pending || !s->block) { set_error("the set's planes are not on the device yet (packed by its first scan)"); return MS_ERR_INVALID; }
+    const size_t n_units = (size_t) ((s->n_bases + 31) / 32), n_blocks = (size_t) ((s->n_bases + 63) / 64 + 1);
+    MS_HIP(hipSetDevice(s->device));
+    if (codes && n_units) MS_HIP(hipMemcpy(codes, s->d_codes, n_units * 8, hipMemcpyDeviceToHost));
+    if (nmask && n_units) MS_HIP(hipMemcpy(nmask, s->d_nmask, n_units * 4, hipMemcpyDeviceToHost));
+    if (blk2reg) MS_HIP(hipMemcpy(blk2reg, s->d_blk2reg, n_blocks * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (blkinfo) MS_HIP(hipMemcpy(blkinfo, s->d_blkinfo, n_blocks * sizeof(int4), hipMemcpyDeviceToHost));
     return MS_OK;
 }
 

@@ -30,16 +30,31 @@ or hands them out by one; a seventh family has no scan in it:
                 rows without a site and with one in every region, ranks with tied scores; counts and unsmoothed profiles exact, smoothed
                 profiles within 16 * 2^-53 of the exact sum.
 
+  * --genome    the kernels in front of and behind the scan on a resident genome (no scan): pack_kernel / blk2reg_kernel / extract_kernel
+                read back plane for plane (ms_debug_seqset_planes) against the host packer -- set sizes on the unit and block edges, ASCII
+                at unaligned device addresses, every source phase against every output phase, empty and one-base regions, more than 32
+                regions in one unit; ms_genome_base_counts against numpy counts over genomes of a tile - 1 .. 2 tiles + 1 bases whose
+                chromosomes end on every bit of a unit, on and across the tile edges, past the LDS counters by number and by empty
+                neighbours; ms_genome_window_filter against N / n counts of the byte slices with exceptions on both window ends, counts
+                on max_n and one above, n_want either side of the accepted count, candidate counts on the wave and block edges;
+                ResidentGenome.random_windows against the restated sampler, the global RandomState included; ms_score by bits against the
+                oracle and ms_score_ranks against the sorted oracle row, in one batch, in batches of one motif and of three.
+  * --annot     ms_genes_nearest_tss against the reference's recurrence restated (chromosomes of 0 .. 2 tiles + 1 genes; one lane, one wave
+                or nothing of a block live behind the first LDS tile; distances equal to the running minimum and one either side; five
+                cutoffs) and ms_genes_promoter_overlap against the literal binary search (regions on and one base off an interval's ends,
+                empty and inverted regions, extents that sum to 0 and below, one table switched between two extent pairs and back).
+
 Each of --variants, --alleles, --best and --once is make_<x>_case(seed) (inputs), expected_<x>(oracle, case) (expected arrays and a tally; neither needs a GPU) and
 run_<x>_case(seed, oracle, _lib) (the device call, compared exactly: integers by value, scores by their bits).  Odd seeds of the variant
-and allele families run in chunks of 7 variants.  The plot family is split the same way, but its expected_plot(case) needs no oracle.
+and allele families run in chunks of 7 variants.  The plot family is split the same way, but its expected_plot(case) needs no oracle; so are the genome and annot families, whose cases take
+every boundary size from the library's own constants (ms_debug_genome_dims).
 CONDITIONS holds what the seeds of a family must put on the boundary.
 
 It lives under tests/ because it uses the oracle (test infrastructure).  Run on the GPU box:
     python tests/fuzz_parity.py --cases 200 --seed 0
-    python tests/fuzz_parity.py --variants --cases 30        (likewise --alleles, --best, --sweep, --once, --plot; each prints its tallies)
+    python tests/fuzz_parity.py --variants --cases 30        (likewise --alleles, --best, --sweep, --once, --plot, --genome, --annot; each prints its tallies)
 `tests/test_gpu_parity.py::test_fuzz_decision_boundary` runs a few cases of ms_scan's family in the GPU suite,
-tests/test_gpu_fuzz_entry_points.py the next four and the plot family, tests/test_gpu_scan_once.py the scan-once family; tests/test_fuzz_cases_host.py checks the cases
+tests/test_gpu_fuzz_entry_points.py the next four and the plot, genome and annot families, tests/test_gpu_scan_once.py the scan-once family; tests/test_fuzz_cases_host.py checks the cases
 themselves without a GPU.
 """
 import argparse
@@ -333,6 +348,7 @@ ALL_PASS = -1e30
 NEAR = 2e-10                                            # a scored window is "near" when its score is within this of the motif's cutoff
 ALT_LETTERS = "ACGTACGTNacgtR"
 VARIANT_STREAM, ALLELE_STREAM, BEST_STREAM, ONCE_STREAM, PLOT_STREAM = 2_000_003 * 11, 3_000_017 * 13, 5_000_011 * 17, 7_000_003 * 23, 11_000_027 * 29
+GENOME_STREAM, ANNOT_STREAM = 13_000_027 * 31, 17_000_023 * 37
 
 
 def motif_kinds(mats):
@@ -346,14 +362,16 @@ def add_tally(total, tally):
     for k, v in tally.items():
         if isinstance(v, (set, frozenset)):
             total[k] = total.get(k, set()) | v
+        elif isinstance(v, np.ndarray):                 # a table of counters
+            total[k] = total.get(k, 0) + v
         else:
             total[k] = total.get(k, 0) + int(v)
     return total
 
 
 def shown(total):
-    """A tally for printing: a set as its size."""
-    return {k: len(v) if isinstance(v, (set, frozenset)) else v for k, v in total.items()}
+    """A tally for printing: a set as its size, a table of counters as its least cell."""
+    return {k: len(v) if isinstance(v, (set, frozenset)) else f"least cell {int(v.min())}" if isinstance(v, np.ndarray) else v for k, v in total.items()}
 
 
 def same_bits(a, b):
@@ -1158,12 +1176,970 @@ def run_plot_case(seed, oracle, _lib):
         pw.close()
     return True, tally
 
+# ---- the genome-build kernels (ms_seqset.hip, ms_background.hip, ms_pwmset.hip's ms_score / ms_score_ranks); no scan
 
-FAMILIES = {"variants": run_variants_case, "alleles": run_alleles_case, "best": run_best_case, "once": run_once_case, "plot": run_plot_case}
+GENOME_LETTERS = np.frombuffer(b"ACGTacgtNn" + b"RYKMSWBDHVrykmswbdhv", dtype=np.uint8)
+GENOME_P = np.array([0.19] * 4 + [0.03] * 4 + [0.05, 0.02] + [0.0025] * 20)
+FILTER_LENGTHS = (1, 31, 32, 33, 64, 100)
+RANK_WIDTHS = (1, 31, 32, 33, 63, 64, 65, 66)
+GENOME_NAN_SEEDS = (3, 11, 19, 27, 35)                  # the seeds that hold ONE motif with max_raw == 0 (its rank row has NaN: not compared)
+EXTRACT_MAX_LEN = 70
+
+
+def ref_random_sequences(chroms, n_times, length, max_n=0, random_seed=None, log=None):
+    """Genome.random_sequences (genome/__init__.py:137-176) restated over a dict of strings, step by step.  With a dict as `log`, the
+    accepted (chromosome name, start) pairs and the number of attempts are left in it."""
+    if random_seed is not None:
+        np.random.seed(random_seed)
+    sizes = {c: len(s) for c, s in chroms.items()}
+    names = sorted(chroms)
+    total = sum(sizes.values())
+    random_chroms = np.random.choice(names, size=n_times, p=[sizes[c] / total for c in names])
+    out, n_loop, windows = [], 0, []
+    while len(out) < n_times:
+        chrom = random_chroms[n_loop % n_times]
+        start = np.random.randint(sizes[chrom] - length)
+        seq = chroms[chrom][start:start + length]
+        if seq.count("N") + seq.count("n") <= max_n:
+            out.append(seq)
+            windows.append((str(chrom), int(start)))
+        n_loop += 1
+    if log is not None:
+        log.update(windows=windows, n_loop=n_loop)
+    return out
+
+
+def same_random_state(a, b):
+    return a[0] == b[0] and np.array_equal(a[1], b[1]) and tuple(a[2:]) == tuple(b[2:])
+
+
+def genome_dims_of(dims):
+    if dims is None:
+        from motifscan_amd import _lib
+        dims = _lib.genome_dims()
+    return dims
+
+
+def genome_bytes(rng, n, all_bytes=False):
+    """n bytes over ACGTacgtNn and the IUPAC letters of both cases, with N / n runs; all_bytes: every byte value 0 .. 255 once."""
+    a = GENOME_LETTERS[rng.choice(GENOME_LETTERS.size, size=n, p=GENOME_P)]
+    for _ in range(min(n // 400, 100)):
+        k = int(rng.integers(0, n))
+        a[k:k + int(rng.integers(1, 60))] = ord("N") if rng.random() < 0.8 else ord("n")
+    if all_bytes and n >= 256:
+        k = int(rng.integers(0, n - 255))
+        a[k:k + 256] = rng.permutation(256).astype(np.uint8)
+    return a
+
+
+def pack_totals(dims):
+    blk = dims["pack_block_bases"]
+    return [0, 1, 31, 32, 33, 63, 64, 65, blk - 1, blk, blk + 1]
+
+
+def random_offsets(rng, total, n_seqs):
+    """offsets [n_seqs + 1] of a set of `total` bases: cuts anywhere, equal cuts (empty sequences) included."""
+    cuts = np.sort(rng.integers(0, total + 1, size=n_seqs - 1))
+    return np.concatenate([[0], cuts, [total]]).astype(np.int64)
+
+
+def count_layout(rng, N, tile, lds, clustered):
+    """Chromosome lengths summing to N for the base count: empty chromosomes in front and behind; `clustered`: lds + 1 or more
+    chromosomes of 33 bases in the first tile (their ends walk through every bit of a unit; those past the lds-th take global atomics),
+    else three short chromosomes each behind lds or more empty ones (pushed past index lds by empties alone); at the tile edges inside
+    the genome in turn a chromosome that ends on the edge and one that straddles it (`clustered` starts with the end, else with the
+    straddler); the rest in chromosomes of 2 000 .. 30 000 bases (a thread's stride of 256 units leaves them)."""
+    lens = [0] * int(rng.integers(1, 3))
+    lens.append(int(rng.integers(40, 400)))
+    if clustered:
+        lens += [33] * (lds + 1 + int(rng.integers(0, 8)))
+    else:
+        for _ in range(3):
+            lens += [0] * (lds + int(rng.integers(0, 4)))
+            lens.append(int(rng.integers(1, 70)))
+
+    def fill(to):
+        used = sum(lens)
+        while used < to:
+            L = min(int(rng.integers(2000, 30000)), to - used)
+            lens.append(L)
+            used += L
+
+    for k, edge in enumerate(range(tile, N, tile)):
+        if (k % 2 == 0) == clustered:
+            fill(edge)                                      # a chromosome ends on the tile edge
+        else:
+            fill(edge - int(rng.integers(1, 30)))
+            lens.append(min(int(rng.integers(31, 90)), N - sum(lens)))      # ... straddles it
+    fill(N)
+    assert sum(lens) == N
+    return lens + [0] * int(rng.integers(1, 3))
+
+
+def count_genome(rng, N, tile, lds, clustered, all_bytes):
+    """(lengths, bytes) of one genome of the base count: count_layout's chromosomes, one of the long ones all N / n, one lower case."""
+    lens = count_layout(rng, N, tile, lds, clustered)
+    off = np.concatenate([[0], np.cumsum(lens)])
+    a = genome_bytes(rng, N, all_bytes)
+    long_ones = [c for c, L in enumerate(lens) if L >= 2000]
+    c = long_ones[int(rng.integers(0, len(long_ones)))]
+    a[off[c]:off[c + 1]] = np.where(rng.random(lens[c]) < 0.7, ord("N"), ord("n"))
+    c = long_ones[int(rng.integers(0, len(long_ones)))]
+    a[off[c]:off[c + 1]] |= 0x20
+    return lens, a
+
+
+def extract_regions(rng, lens, blk, seed):
+    """The extraction's region list [(chromosome, start, end)] over chromosomes of these lengths: regions of 0 .. 70 bases whose source
+    phase (genome position mod 32) is one their output phase has not met yet, until all 32 x 32 pairs occurred; region boundaries on
+    every multiple of blk in the output and a base either side; a region that ends on the last base of every chromosome; twice 40 or more empty
+    regions in a row (at chromosome ends and on an empty chromosome too); 32 one-base regions and 8 empty ones inside one output unit;
+    the output ends on a multiple of blk - 1, + 0 or + 1 by seed."""
+    goff = np.concatenate([[0], np.cumsum(lens)])
+    real = [c for c, L in enumerate(lens) if L >= 200]
+    regs, dst, seen, queue = [], [0], np.zeros((32, 32), dtype=bool), []
+
+    def add(c, a, b):
+        assert 0 <= a <= b <= lens[c]
+        regs.append((c, int(a), int(b)))
+        dst[0] += b - a
+
+    def phased(length):
+        c = real[int(rng.integers(0, len(real)))]
+        d = dst[0] % 32
+        want = np.flatnonzero(~seen[:, d])
+        s = int(want[rng.integers(0, len(want))]) if len(want) else int(rng.integers(0, 32))
+        lo = int((s - goff[c]) % 32)
+        a = lo + 32 * int(rng.integers(0, (lens[c] - length - lo) // 32 + 1))
+        if length:
+            seen[s, d] = True
+        add(c, a, a + length)
+
+    def walk(until):
+        while not until():
+            gap = (dst[0] // blk + 1) * blk - 1 - dst[0]
+            if not queue and 0 < gap <= EXTRACT_MAX_LEN:
+                queue.extend([gap, 1, 1])                   # boundaries on blk - 1, blk and blk + 1
+            phased(queue.pop(0) if queue else int(rng.integers(0, EXTRACT_MAX_LEN + 1)))
+
+    walk(lambda: seen.all() and not queue)
+    for c, L in enumerate(lens):
+        if L:
+            add(c, max(0, L - int(rng.integers(1, EXTRACT_MAX_LEN + 1))), L)
+    last = max(c for c, L in enumerate(lens) if L)
+    add(last, lens[last] - 1, lens[last])                   # the genome's last base alone
+    empties = [(c, L) for c, L in enumerate(lens)] + [(c, 0) for c in real]
+    for k in range(40):
+        c, a = empties[k % len(empties)]
+        add(c, a, a)
+    phased(int(rng.integers(1, EXTRACT_MAX_LEN + 1)))
+    for k in range(40 + int(rng.integers(0, 30))):
+        c, a = empties[int(rng.integers(0, len(empties)))]
+        add(c, a, a)
+    c = real[0]
+    add(c, 5, 5 + (-dst[0]) % 32)
+    for k in range(32):
+        c = real[k % len(real)]
+        a = int(rng.integers(0, lens[c]))
+        add(c, a, a + 1)
+        if k % 4 == 3:
+            add(c, a, a)
+    while (dst[0] + 1) % blk:                               # ... up to one base short of the next multiple of blk
+        gap = (dst[0] // blk + 1) * blk - 1 - dst[0]
+        phased(gap if gap <= EXTRACT_MAX_LEN else int(rng.integers(1, EXTRACT_MAX_LEN + 1)))
+    for _ in range(seed % 3):
+        phased(1)
+    return regs
+
+
+def filter_calls(rng, bases, seed, dims, run0, run_len):
+    """The window filter's calls over the genome `bases`: per call dict(gstart, length, max_n, n_want).  Candidate counts on the wave and
+    block edges; starts anywhere, beside an exception byte (the exception at g0 - 1, g0, g1 - 1 and g1) and on the genome's last window;
+    max_n 0, at least the length, below every window's count inside the N run [run0, run0 + run_len) (all rejected), or a count v that
+    occurs beside v + 1; n_want 1, the accepted count and one either side of it, or more than the candidates."""
+    N, ft = len(bases), dims["filter_threads"]
+    fold = bases | 0x20
+    is_n = fold == ord("n")
+    acgt = (fold == ord("a")) | (fold == ord("c")) | (fold == ord("g")) | (fold == ord("t"))
+    exc = np.flatnonzero(~acgt & ~is_n)
+    cn = np.concatenate([[0], np.cumsum(is_n)])
+    calls = []
+    for j, n_cand in enumerate([1, 63, 64, 65, ft - 1, ft, ft + 1, ft * int(rng.integers(2, 5)) + 1, 2, 129, 3 * ft, ft * int(rng.integers(2, 5)) + 1]):
+        length = FILTER_LENGTHS[(seed + j) % len(FILTER_LENGTHS)]
+        kind = (2 * seed + j) % 6
+        g0 = rng.integers(0, N - length + 1, size=n_cand)
+        if kind == 2:
+            g0 = rng.integers(run0 - length + 1, run0 + run_len, size=n_cand)
+        else:
+            near = rng.random(n_cand) < 0.5
+            e = exc[rng.integers(0, len(exc), size=n_cand)] + rng.choice([1, 0, 1 - length, -length], size=n_cand)
+            g0 = np.where(near, e, g0)
+            g0[int(rng.integers(0, n_cand))] = N - length
+        g0 = np.clip(g0, 0, N - length).astype(np.int64)
+        nn = cn[g0 + length] - cn[g0]
+        if kind in (0, 2):
+            max_n = 0
+        elif kind == 1:
+            max_n = length + int(rng.choice([0, 5]))
+        else:
+            both = np.intersect1d(nn, nn - 1)
+            max_n = int(both[rng.integers(0, len(both))]) if len(both) else int(np.median(nn))
+        acc = int((nn <= max_n).sum())
+        n_want = (1, max(1, acc - 1), max(1, acc), acc + 1, n_cand + 5)[(seed + j) % 5]
+        calls.append({"gstart": g0, "length": length, "max_n": max_n, "n_want": n_want})
+    return calls
+
+
+def make_genome_case(seed, dims=None):
+    """The genome family's inputs (no GPU; every boundary size from _lib.genome_dims): sets to pack of 0 .. 65 bases and of the pack
+    block - 1, + 0 and + 1, a set of empty sequences and one of none; a genome of eleven chromosomes (empty, 1, 31, 33 and 64 bases
+    among them) with extract_regions' list and filter_calls' windows; two samples of random_windows, the first rejecting more than a
+    fifth of its attempts; eight genomes for the base count, of tile - 1, tile, tile + 1 and 2 tiles + 1 bases in both of count_layout's forms; motifs of
+    RANK_WIDTHS' widths and up to three more (P no multiple of 3), tie-rich; odd seeds hold every byte value."""
+    dims = genome_dims_of(dims)
+    rng = np.random.default_rng(GENOME_STREAM + seed)
+    tile, lds, blk = dims["count_tile_bases"], dims["lds_chroms"], dims["pack_block_bases"]
+    all_bytes = seed % 2 == 1
+    packs = [(genome_bytes(rng, T, all_bytes), random_offsets(rng, T, int(rng.integers(1, 6)))) for T in pack_totals(dims)]
+    packs.append((np.zeros(0, dtype=np.uint8), np.zeros(5, dtype=np.int64)))
+    packs.append((np.zeros(0, dtype=np.uint8), np.zeros(1, dtype=np.int64)))
+    big = [int(x) for x in rng.integers(400, 9000, size=4)]
+    lens = [0, big[0], 1, 33, 64, big[1], 0, big[2], 31, big[3], 0]
+    goff = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    bases = genome_bytes(rng, int(goff[-1]), all_bytes)
+    run_len = 300
+    run0 = int(goff[1] + rng.integers(0, big[0] - run_len))
+    bases[run0:run0 + run_len] = np.where(rng.random(run_len) < 0.8, ord("N"), ord("n"))
+    regions = extract_regions(rng, lens, blk, seed)
+    calls = filter_calls(rng, bases, seed, dims, run0, run_len)
+    samples = [{"n_times": 100, "length": 9, "max_n": 0, "seed": 1000 + seed}, {"n_times": 60, "length": 100, "max_n": 5, "seed": None}]
+    counts = [count_genome(rng, N, tile, lds, clustered, all_bytes) for N in (tile - 1, tile, tile + 1, 2 * tile + 1) for clustered in (True, False)]
+    n_extra = (0, 2, 3)[seed % 3]
+    nan_motif = seed in GENOME_NAN_SEEDS
+    if nan_motif and n_extra == 0:
+        n_extra = 2
+    mats = []
+    for w in list(RANK_WIDTHS) + [int(x) for x in rng.integers(1, 67, size=n_extra)]:
+        m = random_matrix(rng, w)
+        while max_raw_of(m) == 0:
+            m = random_matrix(rng, w)
+        mats.append(m)
+    if nan_motif:
+        mats[-1] = -np.abs(rng.integers(1, 4, size=mats[-1].shape)).astype(np.float64)
+    return {"dims": dims, "packs": packs, "lens": lens, "goff": goff, "bases": bases, "regions": regions, "calls": calls, "samples": samples,
+            "counts": counts, "mats": mats, "strand": 1 + seed % 3, "all_bytes": all_bytes}
+
+
+def sampling_chroms(case):
+    """The chromosomes of the case's genome long enough to be sampled, under names whose sorted order is not the file order:
+    (names, uint8 arrays)."""
+    keep = [c for c, L in enumerate(case["lens"]) if L >= 200]
+    return [f"c{(7 * c) % 11}_{c}" for c in keep], [case["bases"][case["goff"][c]:case["goff"][c + 1]] for c in keep]
+
+
+def packed_cut(bases, goff, regions):
+    """(bytes, offsets) of the regions cut out of the genome as byte strings."""
+    parts = [bases[goff[c] + a:goff[c] + b] for c, a, b in regions]
+    offsets = np.concatenate([[0], np.cumsum([len(x) for x in parts])]).astype(np.int64)
+    return (np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)), offsets
+
+
+def count_tally(lens, dims):
+    """What a genome of these chromosome lengths puts on base_count_kernel's paths, from the offsets alone."""
+    tile, lds = dims["count_tile_bases"], dims["lds_chroms"]
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    N, lens = int(off[-1]), np.asarray(lens, dtype=np.int64)
+    nonempty = np.flatnonzero(lens > 0)
+    ends = off[nonempty + 1]
+    t = {"end_bits": np.bincount((ends - 1) % 32, minlength=32), "end_bit0": int(((ends - 1) % 32 == 0).sum()), "end_bit31": int((ends % 32 == 0).sum()),
+         "end_on_tile_edge": int(((ends % tile == 0) & (ends < N)).sum()),
+         "straddles_tile_edge": int(((off[nonempty] // tile != (ends - 1) // tile) & (off[nonempty] % tile != 0)).sum()),
+         "leading_empty": int(nonempty[0]), "trailing_empty": int(len(lens) - 1 - nonempty[-1]),
+         "last_unit_1": int(N % 32 == 1), "last_unit_31": int(N % 32 == 31), "lds_path": 0, "global_by_nonempty": 0, "global_by_empty": 0,
+         "size_tile_minus_1": int(N == tile - 1), "size_tile": int(N == tile), "size_tile_plus_1": int(N == tile + 1), "size_2_tiles_plus_1": int(N == 2 * tile + 1)}
+    for t0 in range(0, N, tile):
+        cb = int(np.searchsorted(off, t0, side="right")) - 1
+        for c in nonempty[(off[nonempty] < min(t0 + tile, N)) & (ends > t0)].tolist():
+            if c - cb < lds:
+                t["lds_path"] += 1
+            elif int((lens[cb:c] > 0).sum()) >= lds:
+                t["global_by_nonempty"] += 1
+            else:
+                t["global_by_empty"] += 1
+    # a thread's next unit (256 units on) starts past the chromosome its last unit ended in: it looks its chromosome up again
+    units = np.arange((N + 31) // 32, dtype=np.int64)
+    units = units[units % (tile // 32) >= 256]
+    last = np.minimum(32 * (units - 256) + 32, N) - 1
+    t["stride_leaves_chrom"] = int((32 * units >= off[np.searchsorted(off, last, side="right")]).sum())
+    return t
+
+
+def expected_genome(oracle, case):
+    """(expected arrays, tally) of a genome case from the library's host packer (held against the oracle's convert_seq by
+    tests/test_genome.py), numpy counts of the bytes, the restated sampler and the oracle's c_score; no GPU."""
+    from motifscan_amd import _lib
+    dims, bases, goff, lens = case["dims"], case["bases"], case["goff"], case["lens"]
+    blk, N = dims["pack_block_bases"], len(bases)
+    want, tally = {}, {"phase_table": np.zeros((32, 32), dtype=np.int64), "end_bits": np.zeros(32, dtype=np.int64)}
+    # 1. pack
+    want["packs"] = [_lib.host_pack(b, o) for b, o in case["packs"]]
+    totals = [len(b) for b, _ in case["packs"]]
+    tally.update(pack_sets=len(totals), pack_block_edge=sum(T in (blk - 1, blk, blk + 1) for T in totals),
+                 pack_unit_edge=sum(T in (31, 32, 33, 63, 64, 65) for T in totals), pack_empty_sets=sum(T == 0 for T in totals),
+                 pack_empty_seqs=int(sum((np.diff(o) == 0).sum() for _, o in case["packs"])), cases_all_bytes=int(case["all_bytes"]))
+    # 2. extract
+    cut, offsets = packed_cut(bases, goff, case["regions"])
+    want["extract"] = _lib.host_pack(cut, offsets)
+    want["extract_offsets"], want["genome"] = offsets, _lib.host_pack(bases, goff)
+    reg = np.array(case["regions"], dtype=np.int64)
+    rl, ds = reg[:, 2] - reg[:, 1], offsets[:-1]
+    ne = rl > 0
+    np.add.at(tally["phase_table"], ((goff[reg[:, 0]] + reg[:, 1])[ne] % 32, ds[ne] % 32), 1)
+    empty_runs = np.diff(np.flatnonzero(np.concatenate([[True], ne, [True]]))) - 1
+    on_edge = (ds >= blk - 1) & (((ds + 1) % blk) <= 2)
+    tally.update(regions=len(reg), empty_regions=int((~ne).sum()), empty_runs_of_40=int((empty_runs >= 40).sum()),
+                 units_of_more_than_32_regions=int((np.bincount(ds // 32) > 32).sum()), one_base_regions=int((rl == 1).sum()),
+                 ends_on_chrom_last_base=int((ne & (reg[:, 2] == np.asarray(lens)[reg[:, 0]])).sum()),
+                 ends_on_genome_last_base=int((ne & (goff[reg[:, 0]] + reg[:, 2] == N)).sum()),
+                 chrom_changes=int((np.diff(reg[ne, 0]) != 0).sum()), starts_on_block_edge=int(on_edge.sum()),
+                 extract_lengths={int(x) for x in rl.tolist()}, out_mod_block={int((offsets[-1] + 1) % blk)})
+    # 3. base counts
+    want["counts"] = []
+    for cl, a in case["counts"]:
+        off = np.concatenate([[0], np.cumsum(cl)])
+        want["counts"].append(np.array([[np.count_nonzero((a[off[c]:off[c + 1]] | 0x20) == ord(b)) for b in "acgt"] for c in range(len(cl))],
+                                       dtype=np.int64).reshape(len(cl), 4))
+        ct = count_tally(cl, dims)
+        tally["end_bits"] += ct.pop("end_bits")
+        add_tally(tally, ct)
+        fold = [a[off[c]:off[c + 1]] | 0x20 for c in range(len(cl)) if cl[c] >= 2000]
+        tally["all_n_chroms"] = tally.get("all_n_chroms", 0) + sum(bool(np.all(f == ord("n"))) for f in fold)
+        tally["lower_case_chroms"] = tally.get("lower_case_chroms", 0) + sum(bool(np.all(a[off[c]:off[c + 1]] & 0x20)) for c in range(len(cl)) if cl[c] >= 2000)
+    # 4. the window filter
+    fold = bases | 0x20
+    is_n = fold == ord("n")
+    other = ~((fold == ord("a")) | (fold == ord("c")) | (fold == ord("g")) | (fold == ord("t")))
+    is_exc = np.concatenate([other & ~is_n, [False]])
+    cn, co = np.concatenate([[0], np.cumsum(is_n)]), np.concatenate([[0], np.cumsum(other)])
+    want["exc_pos"] = np.flatnonzero(is_exc).astype(np.int64)
+    want["taken"] = []
+    ft = dims["filter_threads"]
+    for k in ("n_equal_max", "n_equal_max_plus_1", "exc_at_g0_minus_1", "exc_at_g0", "exc_at_g1_minus_1", "exc_at_g1", "pass_by_exceptions",
+              "window_on_last_base", "n_want_below_accepted", "n_want_equal_accepted", "n_want_above_accepted", "n_want_above_candidates",
+              "n_want_one", "all_rejected", "all_accepted", "max_n_zero", "max_n_at_least_length", "n_cand_wave_edge", "n_cand_block_edge",
+              "n_cand_blocks_plus_1", "filter_lengths_on_unit_edge"):
+        tally[k] = 0
+    tally["filter_phases"] = set()
+    for call in case["calls"]:
+        g0, L, max_n, n_want = call["gstart"], call["length"], call["max_n"], call["n_want"]
+        nn, no = cn[g0 + L] - cn[g0], co[g0 + L] - co[g0]
+        ok = nn <= max_n
+        acc, n_cand = int(ok.sum()), len(g0)
+        want["taken"].append(np.flatnonzero(ok)[:n_want].astype(np.int64))
+        tally["n_equal_max"] += int((nn == max_n).sum())
+        tally["n_equal_max_plus_1"] += int((nn == max_n + 1).sum())
+        tally["exc_at_g0_minus_1"] += int(is_exc[g0 - 1][g0 > 0].sum())
+        tally["exc_at_g0"] += int(is_exc[g0].sum())
+        tally["exc_at_g1_minus_1"] += int(is_exc[g0 + L - 1].sum())
+        tally["exc_at_g1"] += int(is_exc[g0 + L].sum())
+        tally["pass_by_exceptions"] += int((ok & (no > max_n)).sum())
+        tally["window_on_last_base"] += int((g0 + L == N).sum())
+        tally["n_want_below_accepted"] += int(n_want < acc)
+        tally["n_want_equal_accepted"] += int(n_want == acc)
+        tally["n_want_above_accepted"] += int(acc < n_want <= n_cand)
+        tally["n_want_above_candidates"] += int(n_want > n_cand)
+        tally["n_want_one"] += int(n_want == 1)
+        tally["all_rejected"] += int(acc == 0)
+        tally["all_accepted"] += int(acc == n_cand)
+        tally["max_n_zero"] += int(max_n == 0)
+        tally["max_n_at_least_length"] += int(max_n >= L)
+        tally["n_cand_wave_edge"] += int(n_cand in (63, 64, 65))
+        tally["n_cand_block_edge"] += int(n_cand in (ft - 1, ft, ft + 1))
+        tally["n_cand_blocks_plus_1"] += int(n_cand > ft + 1 and n_cand % ft == 1)
+        tally["filter_lengths_on_unit_edge"] += int(L in (31, 32, 33, 64))
+        tally["filter_phases"] |= {int(x) for x in (g0 % 32).tolist()}
+    # ... and its front end: the restated sampler over strings, the global RandomState saved and put back
+    names, arrs = sampling_chroms(case)
+    strings = {n: a.tobytes().decode("latin-1") for n, a in zip(names, arrs)}
+    file_idx = {n: i for i, n in enumerate(names)}
+    before = np.random.get_state()
+    want["samples"], windows = [], []
+    tally["samples_with_second_batch"] = 0
+    try:
+        for sm in case["samples"]:
+            log = {}
+            ref_random_sequences(strings, sm["n_times"], sm["length"], sm["max_n"], sm["seed"], log)
+            ci = np.array([file_idx[n] for n, _ in log["windows"]], dtype=np.int32)
+            st = np.array([s for _, s in log["windows"]], dtype=np.int64)
+            want["samples"].append((ci, st, np.random.get_state()))
+            tally["samples_with_second_batch"] += int(log["n_loop"] > max(sm["n_times"] + sm["n_times"] // 4, 64))
+            windows += [(names[c], s, s + sm["length"]) for c, s in zip(ci.tolist(), st.tolist())]
+    finally:
+        np.random.set_state(before)
+    # 5. scores and ranks over windows of the genome: the samples', the filter's accepted ones that lie inside a chromosome, empty
+    # and one-base ones
+    orig = {n: int(n.split("_")[1]) for n in names}
+    sregs = [(orig[n], a, b) for n, a, b in windows]
+    for call, taken in zip(case["calls"], want["taken"]):
+        if call["length"] >= 64:
+            for g in call["gstart"][taken][:40].tolist():
+                c = int(np.searchsorted(goff, g, side="right")) - 1
+                if g + call["length"] <= goff[c + 1]:
+                    sregs.append((c, g - int(goff[c]), g - int(goff[c]) + call["length"]))
+    sregs += [(1, 7, 7), (0, 0, 0), (2, 0, 1), (3, 0, 33), (8, 0, 31), (1, lens[1] - 66, lens[1])]
+    want["score_regions"] = sregs
+    raw, soff = packed_cut(bases, goff, sregs)
+    vals, widths = oracle.flatten_pwms(case["mats"])
+    R, P = len(sregs), len(case["mats"])
+    want["score"] = {s: oracle.score_arrays(vals, widths, raw.tobytes(), soff, s) for s in (1, 2, 3)}
+    ranks = np.array([0, int(R * 0.1 ** 1) - 1, int(R * 0.1 ** 2) - 1, int(R * 0.1 ** 4) - 1, R - 1, -1, R], dtype=np.int64)
+    row_of = want["score"][case["strand"]]
+    want["ranks"], want["rank_rows"] = ranks, np.full((P, len(ranks)), np.nan)
+    want["rank_compared"] = np.ones(P, dtype=bool)
+    tally.update(score_regions=R, shorter_than_motif=int(sum((np.diff(soff) < w).sum() for w in widths.tolist())), empty_score_regions=int((np.diff(soff) == 0).sum()),
+                 rank_rows_compared=0, rank_rows_with_nan=0, ranks_outside=0, tied_rank_values=0, **motif_kinds(case["mats"]))
+    for p in range(P):
+        row = row_of[p].tolist()
+        if np.isnan(row_of[p]).any():
+            want["rank_compared"][p] = False
+            tally["rank_rows_with_nan"] += 1
+            continue
+        srt = sorted(row, reverse=True)
+        for k, r in enumerate(ranks.tolist()):
+            if 0 <= r < R:
+                want["rank_rows"][p, k] = srt[r]
+                tally["tied_rank_values"] += int(row.count(srt[r]) > 1)
+            else:
+                tally["ranks_outside"] += 1
+        tally["rank_rows_compared"] += 1
+    return want, tally
+
+
+def planes_differ(got, want):
+    """None, or the first of (codes, nmask, blk2reg, blkinfo) that differs between two quadruples of planes."""
+    for name, g, w in zip(("codes", "nmask", "blk2reg", "blkinfo"), got, want):
+        if g.shape != w.shape or g.dtype != w.dtype or not np.array_equal(g, w):
+            return name
+    return None
+
+
+def plane_invariants_broken(codes, nmask, n):
+    """None, or which of the planes' invariants does not hold: code 0 under every mask bit, nothing set past base n."""
+    cw = codes[0::2].astype(np.uint64) | (codes[1::2].astype(np.uint64) << np.uint64(32))
+    m, spread = nmask.astype(np.uint64), np.zeros(len(nmask), dtype=np.uint64)
+    for i in range(32):
+        spread |= ((m >> np.uint64(i)) & np.uint64(1)) * (np.uint64(3) << np.uint64(2 * i))
+    if np.any(cw & spread):
+        return "a code under a mask bit"
+    if len(nmask) != (n + 31) // 32:
+        return "the number of units"
+    if n % 32 and (int(cw[-1]) >> (2 * (n % 32)) or int(nmask[-1]) >> (n % 32)):
+        return "bits past the last base"
+    return None
+
+
+def same_score_bits(got, want):
+    """Scores by their bits; NaN cells (0 / 0 of a motif with max_raw == 0: the sign of the NaN is the divider's own) by their place."""
+    got, want = np.ascontiguousarray(got, dtype=np.float64), np.ascontiguousarray(want, dtype=np.float64)
+    nan = np.isnan(want)
+    return got.shape == want.shape and np.array_equal(np.isnan(got), nan) and np.array_equal(got.view(np.int64)[~nan], want.view(np.int64)[~nan])
+
+
+def check_genome_ranks(case, want, _lib, pw, sq):
+    """ms_score_ranks with the library's budget, with batches of one motif and of three: None, or what differs."""
+    R, P = len(want["score_regions"]), len(case["mats"])
+    assert P % 3 and case["dims"]["rank_budget"] // R >= P
+    runs = []
+    for budget in (0, R, 3 * R + 1):
+        prev = _lib.score_rank_budget(budget)
+        try:
+            runs.append(_lib.score_ranks(pw, sq, want["ranks"], case["strand"]))
+        finally:
+            _lib.score_rank_budget(prev)
+    for name, r in zip(("one motif per batch", "three motifs per batch"), runs[1:]):
+        if r.tobytes() != runs[0].tobytes():
+            return f"score_ranks in batches of {name} differs from one batch (motifs {np.flatnonzero((r.view(np.int64) != runs[0].view(np.int64)).any(axis=1)).tolist()})"
+    keep = want["rank_compared"]
+    if not same_score_bits(runs[0][keep], want["rank_rows"][keep]):
+        bad = np.argwhere(runs[0][keep].view(np.int64) != want["rank_rows"][keep].view(np.int64))
+        return f"score_ranks differs from the sorted oracle row at (compared motif, rank slot) {bad[:3].tolist()}"
+    outside = (want["ranks"] < 0) | (want["ranks"] >= R)
+    if not np.isnan(runs[0][:, outside]).all():
+        return "a rank outside the row does not give NaN"
+    return None
+
+
+def run_genome_case(seed, oracle, _lib):
+    """The device's planes, region hints, base counts, accepted windows, sampled windows, scores and ranks of a case against
+    expected_genome, all exactly."""
+    import torch
+    case = make_genome_case(seed, _lib.genome_dims())
+    want, tally = expected_genome(oracle, case)
+    where = f"genome seed {seed}"
+    # 1. pack: ms_genome_create, and ms_seqset_from_device at a byte offset of 1 .. 15
+    shift = 1 + seed % 15
+    for (b, o), w in zip(case["packs"], want["packs"]):
+        g = _lib.ResidentGenome({f"s{i}": b[o[i]:o[i + 1]] for i in range(len(o) - 1)})
+        try:
+            bad = planes_differ(_lib.seqset_planes(g), w)
+        finally:
+            g.close()
+        if bad:
+            return False, f"{where}: pack of {len(b)} bases in {len(o) - 1} sequences: {bad} differ from the host packer"
+        t = torch.zeros(len(b) + 32, dtype=torch.uint8, device="cuda:0")
+        t[shift:shift + len(b)] = torch.from_numpy(b).to("cuda:0")
+        torch.cuda.synchronize()
+        sq = _lib.SeqSet.from_device(t.data_ptr() + shift, o)
+        try:
+            bad = planes_differ(_lib.seqset_planes(sq), w)
+        finally:
+            sq.close()
+        if bad:
+            return False, f"{where}: pack of {len(b)} device bytes at offset {shift}: {bad} differ from the host packer"
+    names, arrs = sampling_chroms(case)
+    genome = _lib.ResidentGenome({f"c{i}": case["bases"][case["goff"][i]:case["goff"][i + 1]] for i in range(len(case["lens"]))})
+    sampler = _lib.ResidentGenome(dict(zip(names, arrs)), keep_host=True)
+    pw = _lib.PwmSet.from_matrices(case["mats"])
+    try:
+        bad = planes_differ(_lib.seqset_planes(genome), want["genome"])
+        if bad:
+            return False, f"{where}: the genome's {bad} differ from the host packer"
+        # 2. extract
+        reg = np.array(case["regions"], dtype=np.int64)
+        sq = genome.extract(reg[:, 0], reg[:, 1], reg[:, 2])
+        try:
+            got = _lib.seqset_planes(sq)
+        finally:
+            sq.close()
+        bad = planes_differ(got, want["extract"]) or plane_invariants_broken(got[0], got[1], int(want["extract_offsets"][-1]))
+        if bad:
+            return False, f"{where}: extraction of {len(reg)} regions: {bad}"
+        # 3. base counts
+        for (cl, a), w in zip(case["counts"], want["counts"]):
+            off = np.concatenate([[0], np.cumsum(cl)])
+            g = _lib.ResidentGenome({f"c{i}": a[off[i]:off[i + 1]] for i in range(len(cl))})
+            try:
+                got = g.base_counts()
+            finally:
+                g.close()
+            if not np.array_equal(got, w):
+                return False, f"{where}: base counts of {len(a)} bases differ at chromosomes {np.flatnonzero((got != w).any(axis=1))[:5].tolist()}"
+        # 4. the window filter and the sampler
+        for k, (call, w) in enumerate(zip(case["calls"], want["taken"])):
+            got = _lib.window_filter(genome, call["gstart"], call["length"], call["max_n"], want["exc_pos"], call["n_want"])
+            if not np.array_equal(got, w):
+                return False, f"{where}: window filter call {k} ({len(call['gstart'])} candidates of {call['length']}, max_n {call['max_n']}, n_want {call['n_want']}): {len(got)} taken, {len(w)} expected"
+        before = np.random.get_state()
+        try:
+            for sm, (ci, st, state) in zip(case["samples"], want["samples"]):
+                got_c, got_s = sampler.random_windows(sm["n_times"], sm["length"], sm["max_n"], sm["seed"])
+                if not (np.array_equal(got_c, ci) and np.array_equal(got_s, st)):
+                    return False, f"{where}: random_windows({sm}) differs from the restated sampler"
+                if not same_random_state(np.random.get_state(), state):
+                    return False, f"{where}: numpy's global RandomState after random_windows({sm}) is not the reference's"
+        finally:
+            np.random.set_state(before)
+        # 5. scores and ranks over windows extracted on the device
+        sreg = np.array(want["score_regions"], dtype=np.int64)
+        sq = genome.extract(sreg[:, 0], sreg[:, 1], sreg[:, 2])
+        try:
+            for s in (1, 2, 3):
+                if not same_score_bits(_lib.score(pw, sq, s), want["score"][s]):
+                    return False, f"{where}: the bits of ms_score differ for strand mask {s}"
+            bad = check_genome_ranks(case, want, _lib, pw, sq)
+        finally:
+            sq.close()
+        if bad:
+            return False, f"{where}: {bad}"
+    finally:
+        pw.close()
+        sampler.close()
+        genome.close()
+    return True, tally
+
+# ---- the gene-annotation kernels (ms_annotation.hip: ms_genes_nearest_tss, ms_genes_promoter_overlap); no scan and no oracle
+
+ANNOT_CUTOFFS = (10000, 0, 1, -5, 1 << 59)              # the first one is the reference's own: the scenarios are built for it
+ANNOT_EXTENTS = ((2000, 2000), (3000, 1000), (0, 0), (500, -500), (100, -300), (-200, 1000), (1000, 3000))
+OVERLAP_KINDS = ("end_on_lo", "end_on_lo_plus_1", "start_on_hi", "start_on_hi_minus_1", "empty_inside", "empty_on_lo", "empty_on_hi",
+                 "start_behind_end", "overlapping", "far")
+
+
+def annot_gene_counts(dims):
+    """The genes per chromosome of an annot case: 0 .. 3, every power of two up to the LDS tile with one either side, two tiles and
+    two tiles + 1."""
+    tile = dims["gene_tile"]
+    sizes = {0, 1, 2, 3, tile - 1, tile, tile + 1, 2 * tile, 2 * tile + 1}
+    k = 4
+    while k <= tile:
+        sizes |= {k - 1, k, k + 1}
+        k *= 2
+    return sorted(sizes)
+
+
+def interleave(rng, lists):
+    """The lists' items in one list, chosen list by list in a random order that keeps every list's own order."""
+    labels = np.repeat(np.arange(len(lists)), [len(x) for x in lists])
+    at = [0] * len(lists)
+    out = []
+    for c in rng.permutation(labels).tolist():
+        out.append(lists[c][at[c]])
+        at[c] += 1
+    return out
+
+
+def make_annot_case(seed, dims=None):
+    """The annot family's inputs (no GPU): a gene table whose chromosomes hold annot_gene_counts' numbers of genes in a shuffled order,
+    duplicate genes and equal TSS on opposite strands among them, and
+      * regions for nearest_tss, 1, 2 blocks + 1, block + 1, block - 1 and block of them on the chromosomes of 0, 1, 2, 3 and tile - 1
+        genes, a few elsewhere and on chromosomes -1 and n_chroms, their chromosomes interleaved.  On tile + 1 genes a block and two
+        waves: all regions freeze on the first gene (a negative or zero distance, closer genes behind it) but lane `lone` of the block
+        and wave `wave` of the two, which stay live to the last gene of the last tile and accept it alone; on two tiles 70 regions that
+        all freeze in the first tile; on two tiles + 1 the genes approach the
+        regions from one side in steps of -3 .. +1 (accepted in every tile; distances equal to the running minimum and one either
+        side of it); elsewhere regions within 10 001 of a gene, negative coordinates on the chromosome of `tile` genes;
+      * five calls of promoter_overlap with extents A, B, A (two of ANNOT_EXTENTS), a pair that sums to 0 and one that sums to less,
+        over block - 1, block, block + 1, block and 2 blocks + 1 regions of
+        OVERLAP_KINDS relative to a gene's interval under the call's extents, chromosomes out of range among them."""
+    dims = genome_dims_of(dims)
+    rng = np.random.default_rng(ANNOT_STREAM + seed)
+    tile, block, oblock = dims["gene_tile"], dims["near_threads"], dims["overlap_threads"]
+    C = ANNOT_CUTOFFS[0]
+    sizes = [int(x) for x in rng.permutation(annot_gene_counts(dims))]
+    n_chroms = len(sizes)
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    tss = rng.integers(0, 5_000_000, size=int(off[-1])).astype(np.int64)
+    strand = rng.integers(1, 3, size=int(off[-1])).astype(np.int8)
+    chrom_of_size = {g: c for c, g in enumerate(sizes)}
+    near = [[] for _ in range(n_chroms)]                    # per chromosome, the starts of its regions in their order
+
+    def around(c, n):
+        g = rng.integers(off[c], off[c + 1], size=n)
+        return (tss[g] + np.where(rng.random(n) < 0.05, 0, rng.integers(-10001, 10002, size=n))).tolist()
+
+    # tile genes: negative coordinates
+    c = chrom_of_size[tile]
+    tss[off[c]:off[c + 1]] = rng.integers(-60_000, 60_000, size=tile)
+    near[c] = around(c, 100)
+    near[chrom_of_size[0]] = [int(rng.integers(-100, 100000))]
+    near[chrom_of_size[1]] = around(chrom_of_size[1], 2 * block + 1)
+    near[chrom_of_size[2]] = around(chrom_of_size[2], block + 1)
+    near[chrom_of_size[3]] = around(chrom_of_size[3], block - 1)
+    near[chrom_of_size[tile - 1]] = around(chrom_of_size[tile - 1], block)
+    # tile + 1 genes: one live lane, one live wave, one frozen lane
+    c = chrom_of_size[tile + 1]
+    T = int(rng.integers(1_000_000, 2_000_000))
+    far = T + 60_000
+    tss[off[c]:off[c + 1]] = T + rng.integers(-4000, 4001, size=tile + 1)
+    tss[off[c]] = T
+    tss[off[c + 1] - 1] = far - 7 if seed % 2 else far + 7
+    lone, wave = int(rng.integers(0, block)), int(rng.integers(0, 2))
+    starts = (T - rng.integers(0, 3000, size=block + 128)).tolist()
+    starts[lone] = far
+    for k in range(64):
+        starts[block + 64 * wave + k] = far + int(rng.integers(-3, 4))
+    near[c] = starts
+    # two tiles: frozen in the first tile
+    c = chrom_of_size[2 * tile]
+    T = int(rng.integers(1_000_000, 2_000_000))
+    tss[off[c]:off[c + 1]] = T + rng.integers(-4000, 4001, size=2 * tile)
+    tss[off[c]:off[c] + 4] = T + rng.integers(3000, 9000, size=4)      # far enough to be accepted by some and not by others
+    tss[off[c] + 4] = T
+    near[c] = (T - rng.integers(0, 3000, size=70)).tolist()
+    # two tiles + 1: the genes come closer in steps of -3 .. +1
+    c = chrom_of_size[2 * tile + 1]
+    T = int(rng.integers(1_000_000, 2_000_000))
+    D = 9900 + np.cumsum(rng.choice([-3, -2, -1, -1, 0, 0, 1], size=2 * tile + 1))
+    assert D.min() > 500
+    tss[off[c]:off[c + 1]] = T - D
+    twin = np.flatnonzero(np.diff(D) == 0) + 1
+    strand[off[c] + twin] = 3 - strand[off[c] + twin - 1]                 # equal TSS on opposite strands: the first in file order wins
+    near[c] = (T + rng.integers(0, 400, size=70)).tolist()
+    for c in rng.choice([c for c in range(n_chroms) if not near[c] and sizes[c]], size=6, replace=False).tolist():
+        near[c] = around(c, int(rng.integers(1, 5)))
+    # duplicate genes for the sorted promoter lists
+    for c in range(n_chroms):
+        if sizes[c] >= 4 and not near[c]:
+            k = rng.integers(off[c], off[c + 1] - 1, size=max(1, sizes[c] // 16))
+            tss[k + 1], strand[k + 1] = tss[k], strand[k]
+    pairs = interleave(rng, [[(c, x) for x in near[c]] for c in range(n_chroms)] + [[(-1, 5), (n_chroms, 7), (-1, int(tss[0])), (n_chroms, 0)]])
+    near_chrom, near_start = np.array([p[0] for p in pairs], dtype=np.int32), np.array([p[1] for p in pairs], dtype=np.int64)
+    # promoter overlap: extents A, B, A
+    A = ANNOT_EXTENTS[seed % len(ANNOT_EXTENTS)]
+    B = ANNOT_EXTENTS[(seed + 1 + seed // len(ANNOT_EXTENTS) % (len(ANNOT_EXTENTS) - 1)) % len(ANNOT_EXTENTS)]
+    if seed % 2:
+        B = (A[0], A[1] + 700)                              # only `downstream` changes: the cached table's key has two parts
+    calls, n_genes = [], np.asarray(sizes, dtype=np.int64)
+    for (up, down), n in zip((A, B, A, ANNOT_EXTENTS[2 + seed % 2], ANNOT_EXTENTS[4]), (oblock - 1, oblock, oblock + 1, oblock, 2 * oblock + 1)):
+        ci = rng.integers(0, n_chroms, size=n)
+        outside = rng.random(n) < 0.05
+        ci[outside] = rng.choice([-1, n_chroms], size=int(outside.sum()))
+        kind = rng.integers(0, len(OVERLAP_KINDS), size=n)
+        cc = np.where(outside, 0, ci)
+        real = ~outside & (n_genes[cc] > 0)
+        g = np.minimum(off[cc] + (rng.random(n) * n_genes[cc]).astype(np.int64), len(tss) - 1)      # a gene of the chromosome, where it has one
+        lo, hi = np.where(strand[g] == 1, tss[g] - up, tss[g] - down), np.where(strand[g] == 1, tss[g] + down, tss[g] + up)
+        w, mid = rng.integers(1, 500, size=n), (lo + hi) // 2
+        forms = np.array([(lo - w, lo), (lo - w, lo + 1), (hi, hi + w), (hi - 1, hi + w), (mid, mid), (lo, lo), (hi, hi), (mid + w, mid - w),
+                          (mid - w, mid + w), (hi + 10_000_000, hi + 10_000_000 + w)])                  # [kind][start / end][region]
+        st, en = forms[kind, 0, np.arange(n)], forms[kind, 1, np.arange(n)]
+        plain = rng.integers(0, 1000, size=n)
+        st, en = np.where(real, st, plain).astype(np.int64), np.where(real, en, plain + 100).astype(np.int64)
+        calls.append({"upstream": up, "downstream": down, "chrom": ci.astype(np.int32), "start": st, "end": en, "kind": kind})
+    return {"dims": dims, "sizes": sizes, "off": off, "tss": tss, "strand": strand, "near_chrom": near_chrom, "near_start": near_start,
+            "lone": lone, "wave": wave, "calls": calls}
+
+
+def nearest_stepwise(off, tss, strand, chrom, start, cutoff):
+    """dis_to_nearest_gene (region/utils.py:148-180) for every region at once: the reference's recurrence over the genes of the region's
+    chromosome in file order -- m = cutoff; per gene d = start - tss; |d| < m: m = d, target = the gene -- one numpy step per gene
+    index, every chromosome that has such a gene taking it together.  (distance, found)."""
+    n_chroms, n = len(off) - 1, len(chrom)
+    dist, found = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=bool)
+    idx = np.flatnonzero((chrom >= 0) & (chrom < n_chroms))
+    c = chrom[idx].astype(np.int64)
+    s, base, n_g = start[idx].astype(np.int64), off[c], off[c + 1] - off[c]
+    m = np.full(len(idx), cutoff, dtype=np.int64)
+    minus, hit = np.zeros(len(idx), dtype=bool), np.zeros(len(idx), dtype=bool)
+    for i in range(int(n_g.max()) if len(idx) else 0):
+        live = i < n_g
+        g = np.where(live, base + i, 0)
+        d = s - tss[g]
+        acc = live & (np.abs(d) < m)
+        m = np.where(acc, d, m)
+        minus = np.where(acc, strand[g] == 2, minus)
+        hit |= acc
+    dist[idx], found[idx] = np.where(hit, np.where(minus, -m, m), 0), hit
+    return dist, found
+
+
+def nearest_restated(off, tss, strand, chrom, start, cutoff, tile, trace=None, chunk=256):
+    """The same recurrence, a chromosome at a time and `chunk` genes at a time (a tile is cut into whole chunks), for the regions that
+    can still accept (m > 0): while a region has accepted only positive distances its m is the least |d| so far (or the cutoff), so
+    gene k of a chunk is accepted iff |d_k| < min(m, |d| of the chunk's genes before k) and no gene before k was accepted with
+    d <= 0 -- the first such gene freezes the region for good.  (distance, found).  tests/test_fuzz_cases_host.py holds it against
+    nearest_stepwise and against the plain loop nearest_plain.  With a dict as `trace`, what the walk met is left in it, per region
+    that has a chromosome: how often |d| was the running minimum, one less and one more, accepts with d == 0 and of the first of two
+    equal TSS on opposite strands, the tiles with an accept, the last accepted gene, whether the region could still accept after the
+    first tile and at the last gene, and whether a gene behind the one that froze it at a negative distance was closer."""
+    n_chroms, n = len(off) - 1, len(chrom)
+    dist, found = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=bool)
+    keys = ("ties", "min_minus_1", "min_plus_1", "zero_accepts", "twin_wins", "accepts", "tiles_hit", "closer_later")
+    tr = {k: np.zeros(n, dtype=np.int64) for k in keys}
+    tr["last_accept"], tr["live_after_tile_1"], tr["live_at_last_gene"] = np.full(n, -1, dtype=np.int64), np.zeros(n, dtype=bool), np.zeros(n, dtype=bool)
+    for ch in range(n_chroms):
+        rows = np.flatnonzero(chrom == ch)
+        G = int(off[ch + 1] - off[ch])
+        if not len(rows) or not G:
+            continue
+        t, sd = tss[off[ch]:off[ch + 1]], strand[off[ch]:off[ch + 1]]
+        twin = np.concatenate([(t[1:] == t[:-1]) & (sd[1:] != sd[:-1]), [False]])
+        s = start[rows].astype(np.int64)
+        m = np.full(len(rows), cutoff, dtype=np.int64)
+        target = np.full(len(rows), -1, dtype=np.int64)
+        for k0 in [k for t0 in range(0, G, tile) for k in range(t0, min(t0 + tile, G), chunk)]:
+            k1 = min(k0 + chunk, G, (k0 // tile + 1) * tile)
+            if trace is not None and k0 == tile:
+                tr["live_after_tile_1"][rows] = m > 0
+            live = np.flatnonzero(m > 0)
+            if not len(live):
+                break
+            d = s[live, None] - t[None, k0:k1]
+            a = np.abs(d)
+            before_min = np.minimum.accumulate(np.concatenate([m[live, None], a[:, :-1]], axis=1), axis=1)
+            record = a < before_min
+            stop = record & (d <= 0)
+            stops_before = np.cumsum(stop, axis=1) - stop
+            acc = record & (stops_before == 0)
+            any_acc = acc.any(axis=1)
+            last = acc.shape[1] - 1 - np.argmax(acc[:, ::-1], axis=1)
+            hit_rows = live[any_acc]
+            m[hit_rows] = d[any_acc, last[any_acc]]
+            target[hit_rows] = k0 + last[any_acc]
+            if trace is not None:
+                pos = stops_before == 0
+                r = rows[live]
+                tr["ties"][r] += (pos & (a == before_min)).sum(axis=1)
+                tr["min_minus_1"][r] += (pos & (a == before_min - 1)).sum(axis=1)
+                tr["min_plus_1"][r] += (pos & (a == before_min + 1)).sum(axis=1)
+                tr["zero_accepts"][r] += (acc & (d == 0)).sum(axis=1)
+                tr["twin_wins"][r] += (acc & twin[None, k0:k1]).sum(axis=1)
+                tr["accepts"][r] += acc.sum(axis=1)
+                tr["tiles_hit"][r] |= any_acc.astype(np.int64) << (k0 // tile)
+                if k1 == G:
+                    tr["live_at_last_gene"][r] = pos[:, -1]
+        hit = target >= 0
+        dist[rows] = np.where(hit, np.where(sd[np.maximum(target, 0)] == 2, -m, m), 0)
+        found[rows] = hit
+        if trace is not None:
+            tr["last_accept"][rows] = target
+            frozen = np.flatnonzero(hit & (m < 0))
+            if len(frozen):
+                behind = np.arange(G)[None, :] > target[frozen, None]
+                tr["closer_later"][rows[frozen]] = (behind & (np.abs(s[frozen, None] - t[None, :]) < -m[frozen, None])).any(axis=1)
+    if trace is not None:
+        trace.update(tr)
+    return dist, found
+
+
+def nearest_plain(off, tss, strand, chrom, start, cutoff):
+    """The same for ONE region as the reference writes it: a plain Python loop over the chromosome's genes."""
+    if not (0 <= chrom < len(off) - 1):
+        return 0, False
+    m, target = cutoff, None
+    for g in range(int(off[chrom]), int(off[chrom + 1])):
+        d = start - int(tss[g])
+        if abs(d) < m:
+            m, target = d, g
+    if target is None:
+        return 0, False
+    return (-m if strand[target] == 2 else m), True
+
+
+def overlap_literal(intervals, start, end):
+    """overlap_with (region/utils.py:16-48) as subset_by_location calls it: the literal binary search over a sorted list of [lo, hi]."""
+    left, right = 0, len(intervals) - 1
+    while left <= right:
+        mid = (left + right) // 2
+        lo, hi = intervals[mid]
+        if not (end <= lo or start >= hi):
+            return True
+        if start >= hi:
+            left = mid + 1
+        else:
+            right = mid - 1
+    return False
+
+
+def promoter_lists(case, up, down):
+    """Per chromosome the promoter intervals [lo, hi] of (up, down), sorted as Python sorts lists."""
+    off, fwd = case["off"], case["strand"] == 1
+    lo, hi = np.where(fwd, case["tss"] - up, case["tss"] - down).tolist(), np.where(fwd, case["tss"] + down, case["tss"] + up).tolist()
+    return [sorted(zip(lo[off[c]:off[c + 1]], hi[off[c]:off[c + 1]])) for c in range(len(off) - 1)]        # (pairs order as lists of two do)
+
+
+def expected_annot(oracle, case):
+    """(expected arrays, tally) of an annot case from the restated recurrence and the literal binary search; no GPU, and `oracle` is
+    not used (the reference's walks are Python: they are restated here and held against plain loops by tests/test_fuzz_cases_host.py)."""
+    dims, off, tss, strand, sizes = case["dims"], case["off"], case["tss"], case["strand"], np.asarray(case["sizes"])
+    tile, block, oblock = dims["gene_tile"], dims["near_threads"], dims["overlap_threads"]
+    chrom, start = case["near_chrom"], case["near_start"]
+    n_chroms = len(sizes)
+    want, tr = {"nearest": {}, "overlap": []}, {}
+    for cutoff in ANNOT_CUTOFFS:
+        want["nearest"][cutoff] = nearest_restated(off, tss, strand, chrom, start, cutoff, tile, tr if cutoff == ANNOT_CUTOFFS[0] else None)
+    in_range = (chrom >= 0) & (chrom < n_chroms)
+    c = np.where(in_range, chrom, 0).astype(np.int64)
+    n_g = np.where(in_range, sizes[c], 0)
+    tiles = (n_g + tile - 1) // tile
+    multi = tiles >= 2
+    per_chrom = np.bincount(c[n_g > 0], minlength=n_chroms)                # the regions that reach the device, per chromosome
+    tally = {"regions": len(chrom), "chrom_below_range": int((chrom < 0).sum()), "chrom_above_range": int((chrom >= n_chroms).sum()),
+             "regions_without_genes": int((n_g == 0).sum()), "found": int(want["nearest"][ANNOT_CUTOFFS[0]][1].sum()),
+             "strict_tie_rejections": int(tr["ties"].sum()), "min_minus_1_accepts": int(tr["min_minus_1"].sum()),
+             "min_plus_1_rejections": int(tr["min_plus_1"].sum()), "zero_distance_accepts": int(tr["zero_accepts"].sum()),
+             "first_of_equal_tss_wins": int(tr["twin_wins"].sum()), "negative_accept_closer_later": int(tr["closer_later"].sum()),
+             "accepts_in_every_tile": int((multi & (tr["tiles_hit"] == (1 << tiles) - 1)).sum()),
+             "only_last_gene_accepts": int((multi & (tr["accepts"] == 1) & (tr["last_accept"] == n_g - 1)).sum()),
+             "negative_tss": int((tss < 0).sum()), "negative_starts": int((start < 0).sum()),
+             "lone_live_lane_blocks": 0, "lone_live_wave_blocks": 0, "blocks_frozen_in_tile_1": 0, "cutoffs": len(ANNOT_CUTOFFS),
+             "cutoff_zero": int(0 in ANNOT_CUTOFFS), "cutoff_negative": sum(x < 0 for x in ANNOT_CUTOFFS), "cutoff_huge": int(1 << 59 in ANNOT_CUTOFFS)}
+    for name, g in (("no", 0), ("one", 1), ("tile_minus_1", tile - 1), ("tile", tile), ("tile_plus_1", tile + 1), ("two_tiles", 2 * tile),
+                    ("two_tiles_plus_1", 2 * tile + 1)):
+        tally[f"walked_chroms_of_{name}_genes"] = int(((sizes == g) & ((per_chrom > 0) | (g == 0))).sum())
+    for name, r in (("one", 1), ("block_minus_1", block - 1), ("block", block), ("block_plus_1", block + 1), ("two_blocks_plus_1", 2 * block + 1)):
+        tally[f"chroms_of_{name}_regions"] = int((np.bincount(c[in_range], minlength=n_chroms) == r).sum())
+    # the blocks as the entry cuts them: a chromosome's regions in their order, near_threads at a time
+    for ch in np.flatnonzero((per_chrom > 0) & (sizes > tile)).tolist():
+        mine = np.flatnonzero(in_range & (c == ch))
+        live1, to_end = tr["live_after_tile_1"][mine], tr["live_at_last_gene"][mine]
+        for b0 in range(0, len(mine), block):
+            l1, le = live1[b0:b0 + block], to_end[b0:b0 + block]
+            waves = [bool(l1[w:w + 64].any()) for w in range(0, len(l1), 64)]
+            tally["blocks_frozen_in_tile_1"] += int(not l1.any())
+            tally["lone_live_lane_blocks"] += int(l1.sum() == 1 and len(l1) == block and bool(le[l1].all()))
+            tally["lone_live_wave_blocks"] += int(sum(waves) == 1 and len(waves) > 1 and l1.sum() > 1 and bool(le[l1].all()))
+    # promoter overlap
+    for k in OVERLAP_KINDS:
+        tally[k] = 0
+    tally.update(extent_switches=0, extents_sum_zero=0, extents_sum_negative=0, extents_asymmetric=0, downstream_alone_switches=0, overlaps=0, duplicate_intervals=0,
+                 overlap_n_block_minus_1=0, overlap_n_block=0, overlap_n_block_plus_1=0, overlap_chrom_out_of_range=0,
+                 probed_chroms_of_0_to_3_genes=0, probed_chroms_of_pow2_minus_1_genes=0, probed_chroms_of_pow2_genes=0, probed_chroms_of_pow2_plus_1_genes=0)
+    prev, lists = None, {}
+    for call in case["calls"]:
+        ext = (call["upstream"], call["downstream"])
+        if ext not in lists:
+            lists[ext] = promoter_lists(case, *ext)
+        iv = lists[ext]
+        ok = (call["chrom"] >= 0) & (call["chrom"] < n_chroms)
+        want["overlap"].append(np.array([bool(o) and overlap_literal(iv[ch], s_, e_) for o, ch, s_, e_ in
+                                         zip(ok.tolist(), call["chrom"].tolist(), call["start"].tolist(), call["end"].tolist())], dtype=bool))
+        real = ok & (sizes[np.where(ok, call["chrom"], 0)] > 0)
+        for k, name in enumerate(OVERLAP_KINDS):
+            tally[name] += int((real & (call["kind"] == k)).sum())
+        g = sizes[call["chrom"][real]]
+        pow2 = lambda x: (x >= 4) & ((x & (x - 1)) == 0)
+        tally["probed_chroms_of_0_to_3_genes"] += int((sizes[call["chrom"][ok]] <= 3).sum())
+        tally["probed_chroms_of_pow2_minus_1_genes"] += int(pow2(g + 1).sum())
+        tally["probed_chroms_of_pow2_genes"] += int(pow2(g).sum())
+        tally["probed_chroms_of_pow2_plus_1_genes"] += int(pow2(g - 1).sum())
+        tally["extent_switches"] += int(prev is not None and prev != ext)
+        tally["downstream_alone_switches"] += int(prev is not None and prev[0] == ext[0] and prev[1] != ext[1])
+        tally["extents_sum_zero"] += int(sum(ext) == 0)
+        tally["extents_sum_negative"] += int(sum(ext) < 0)
+        tally["extents_asymmetric"] += int(ext[0] != ext[1])
+        tally["overlaps"] += int(want["overlap"][-1].sum())
+        if prev is None:
+            tally["duplicate_intervals"] = sum(sum(a == b for a, b in zip(x, x[1:])) for x in iv)
+        tally["overlap_chrom_out_of_range"] += int((~ok).sum())
+        n = len(call["chrom"])
+        for name, v in (("overlap_n_block_minus_1", oblock - 1), ("overlap_n_block", oblock), ("overlap_n_block_plus_1", oblock + 1)):
+            tally[name] += int(n == v)
+        prev = ext
+    return want, tally
+
+
+def run_annot_case(seed, oracle, _lib):
+    """One GeneTable: nearest_tss at every cutoff of ANNOT_CUTOFFS, then promoter_overlap with extents A, B and A again with nearest_tss
+    between them, against expected_annot; all exactly."""
+    case = make_annot_case(seed, _lib.genome_dims())
+    want, tally = expected_annot(oracle, case)
+    table = _lib.GeneTable(case["off"], case["tss"], case["strand"])
+    try:
+        def nearest(cutoff):
+            dist, found = table.nearest_tss(case["near_chrom"], case["near_start"], cutoff)
+            wd, wf = want["nearest"][cutoff]
+            if not np.array_equal(found, wf):
+                return f"annot seed {seed}: nearest_tss at cutoff {cutoff}: found differs at regions {np.flatnonzero(found != wf)[:5].tolist()}"
+            if not np.array_equal(dist, wd):
+                return f"annot seed {seed}: nearest_tss at cutoff {cutoff}: distance differs at regions {np.flatnonzero(dist != wd)[:5].tolist()}"
+            return None
+
+        for cutoff in ANNOT_CUTOFFS:
+            bad = nearest(cutoff)
+            if bad:
+                return False, bad
+        for k, (call, w) in enumerate(zip(case["calls"], want["overlap"])):
+            got = table.promoter_overlap(call["chrom"], call["start"], call["end"], call["upstream"], call["downstream"])
+            if not np.array_equal(got, w):
+                r = int(np.flatnonzero(got != w)[0])
+                return False, (f"annot seed {seed}: promoter_overlap call {k} (extents {call['upstream']}, {call['downstream']}) differs at region {r} "
+                               f"({OVERLAP_KINDS[call['kind'][r]]}, chromosome {call['chrom'][r]})")
+            bad = nearest(ANNOT_CUTOFFS[0])
+            if bad:
+                return False, bad + " (between promoter_overlap calls)"
+    finally:
+        table.close()
+    return True, tally
+
+
+FAMILIES = {"variants": run_variants_case, "alleles": run_alleles_case, "best": run_best_case, "once": run_once_case, "plot": run_plot_case,
+            "genome": run_genome_case, "annot": run_annot_case}
 
 # What the seeds of a family must put on the boundary, summed over SEEDS[family] from the oracle's output alone: conditions, not
 # measurements.  If a change to a generator misses one, the seed range changes -- not the threshold, not the mix of matrix kinds.
-SEEDS = {"variants": range(30), "alleles": range(30), "best": range(30), "sweep": range(40), "once": range(40), "plot": range(40)}
+SEEDS = {"variants": range(30), "alleles": range(30), "best": range(30), "sweep": range(40), "once": range(40), "plot": range(40),
+         "genome": range(40), "annot": range(40)}
 CONDITIONS = {"variants": {"near_fail": 10_000, "near_pass": 10_000, "records": 100_000},
               "alleles": {"near_fail": 5_000, "near_pass": 5_000, "gained": 500, "lost": 500},
               "best": {"tied_cells": 1_000, "tied_across_segments": 300},
@@ -1173,27 +2149,68 @@ CONDITIONS = {"variants": {"near_fail": 10_000, "near_pass": 10_000, "records": 
                        "mixed_spans": 10, "cases_local": 10, "cases_global": 3},
               "plot": {"sites": 200_000, "in_range": 150_000, "on_edge": 20_000, "on_last_edge": 3_000, "below_first": 10_000, "beyond_last": 10_000,
                        "half_bp": 100_000, "empty_rows": 20, "full_rows": 20, "cases_r_mult_64": 5, "cases_multi_tile": 15,
-                       "cases_short_last_tile": 3, "cases_global_bins": 2, "clipped_head": 1_000, "clipped_tail": 1_000}}
+                       "cases_short_last_tile": 3, "cases_global_bins": 2, "clipped_head": 1_000, "clipped_tail": 1_000},
+              # genome, annot: one counter per boundary; over the 40 seeds each was at least 40 when these floors were set, at half (or less) of what was counted
+              "genome": {"pack_sets": 260, "pack_block_edge": 60, "pack_unit_edge": 120, "pack_empty_sets": 60, "pack_empty_seqs": 198,
+                         "regions": 33_000, "empty_regions": 2300, "empty_runs_of_40": 40, "units_of_more_than_32_regions": 55,
+                         "one_base_regions": 1300, "ends_on_chrom_last_base": 192, "ends_on_genome_last_base": 42, "chrom_changes": 23_000,
+                         "starts_on_block_edge": 359, "end_bit0": 232, "end_bit31": 252, "end_on_tile_edge": 60, "straddles_tile_edge": 60,
+                         "leading_empty": 234, "trailing_empty": 245, "last_unit_1": 80, "last_unit_31": 40, "lds_path": 3100,
+                         "global_by_nonempty": 1100, "global_by_empty": 998, "size_tile_minus_1": 40, "size_tile": 40, "size_tile_plus_1": 40,
+                         "size_2_tiles_plus_1": 40, "stride_leaves_chrom": 350_000, "all_n_chroms": 160, "lower_case_chroms": 160, "n_equal_max": 6300,
+                         "n_equal_max_plus_1": 6400, "exc_at_g0_minus_1": 11_000, "exc_at_g0": 12_000, "exc_at_g1_minus_1": 12_000,
+                         "exc_at_g1": 11_000, "pass_by_exceptions": 6700, "window_on_last_base": 240, "n_want_below_accepted": 67,
+                         "n_want_equal_accepted": 45, "n_want_above_accepted": 69, "n_want_above_candidates": 58, "n_want_one": 88, "all_rejected": 52,
+                         "all_accepted": 52, "max_n_zero": 103, "max_n_at_least_length": 40, "n_cand_wave_edge": 60, "n_cand_block_edge": 60,
+                         "n_cand_blocks_plus_1": 40, "filter_lengths_on_unit_edge": 160, "samples_with_second_batch": 40, "score_regions": 4700,
+                         "shorter_than_motif": 19_000, "empty_score_regions": 40, "rank_rows_compared": 192, "ranks_outside": 576,
+                         "tied_rank_values": 316},
+              "annot": {"regions": 38_000, "chrom_below_range": 40, "chrom_above_range": 40, "regions_without_genes": 100, "found": 38_000,
+                        "strict_tie_rejections": 1_500_000, "min_minus_1_accepts": 1_300_000, "min_plus_1_rejections": 960_000,
+                        "zero_distance_accepts": 1100, "first_of_equal_tss_wins": 780_000, "negative_accept_closer_later": 12_000,
+                        "accepts_in_every_tile": 560, "only_last_gene_accepts": 1300, "negative_tss": 20_000, "negative_starts": 1000,
+                        "lone_live_lane_blocks": 20, "lone_live_wave_blocks": 20, "blocks_frozen_in_tile_1": 20, "cutoffs": 100, "cutoff_zero": 20,
+                        "cutoff_negative": 20, "cutoff_huge": 20, "walked_chroms_of_no_genes": 20, "walked_chroms_of_one_genes": 20,
+                        "walked_chroms_of_tile_minus_1_genes": 20, "walked_chroms_of_tile_genes": 20, "walked_chroms_of_tile_plus_1_genes": 20,
+                        "walked_chroms_of_two_tiles_genes": 20, "walked_chroms_of_two_tiles_plus_1_genes": 20, "chroms_of_one_regions": 52,
+                        "chroms_of_block_minus_1_regions": 20, "chroms_of_block_regions": 20, "chroms_of_block_plus_1_regions": 20,
+                        "chroms_of_two_blocks_plus_1_regions": 20, "end_on_lo": 2800, "end_on_lo_plus_1": 2800, "start_on_hi": 2800,
+                        "start_on_hi_minus_1": 2800, "empty_inside": 2800, "empty_on_lo": 2700, "empty_on_hi": 2700, "start_behind_end": 2800,
+                        "overlapping": 2800, "far": 2800, "extent_switches": 77, "extents_sum_zero": 35, "extents_sum_negative": 26,
+                        "extents_asymmetric": 72, "downstream_alone_switches": 20, "overlaps": 9900, "duplicate_intervals": 56_000, "overlap_n_block_minus_1": 20,
+                        "overlap_n_block": 40, "overlap_n_block_plus_1": 20, "overlap_chrom_out_of_range": 1500,
+                        "probed_chroms_of_0_to_3_genes": 3300, "probed_chroms_of_pow2_minus_1_genes": 8200, "probed_chroms_of_pow2_genes": 9200,
+                        "probed_chroms_of_pow2_plus_1_genes": 9100}}
 SWEEP_MAX_EMPTY = 10                                    # at most this many of the sweep cases may have no window at all
 PLOT_MAX_EMPTY = 4                                      # at most this many of the plot cases may have no hit at all
 ONCE_MAX_EMPTY = 12                                     # at most this many of the scan-once cases may have no site at all
 ONCE_SEEN = {"span_start_residues": 32, "strand_masks": 3, "layouts": len(ONCE_LAYOUTS)}      # every one of them must occur
+GENOME_SEEN = {"extract_lengths": EXTRACT_MAX_LEN + 1, "out_mod_block": 3, "filter_phases": 32}   # ... of the genome family's sets
+GENOME_TABLES = ("phase_table", "end_bits")             # no cell of these may be empty: extraction's source phase x output phase, the bit of a unit a chromosome ends on
+GENOME_MAX_NAN_ROWS = 5                                 # motifs whose oracle row holds NaN (left out of the rank comparison), over all seeds; one per seed at most
 
 
 def unmet_conditions(family, total):
-    """The conditions a family's summed tally misses, as text (empty: all met).  Every family must also meet a motif with max_raw == 0
-    (but for the plot family, which has widths and no matrices) and one of a single column, and -- but for the sweep, whose generator
-    draws 1 .. 33 columns -- one of 64 columns or more."""
-    need = dict(CONDITIONS[family], width_one=1)
-    if family != "plot":
+    """The conditions a family's summed tally misses, as text (empty: all met).  Every family with motifs must also meet one with
+    max_raw == 0 (but for the plot family, which has widths and no matrices) and one of a single column, and -- but for the sweep, whose
+    generator draws 1 .. 33 columns -- one of 64 columns or more."""
+    need = dict(CONDITIONS[family])
+    if family != "annot":                               # (the annot family has no motifs)
+        need["width_one"] = 1
+    if family not in ("plot", "annot"):
         need["max_raw_zero"] = 1
-    if family != "sweep":
+    if family not in ("sweep", "annot"):
         need["wide"] = 1
     bad = [f"{k}: {total.get(k, 0)} < {n}" for k, n in need.items() if total.get(k, 0) < n]
     if family == "sweep" and total.get("cases_without_windows", 0) > SWEEP_MAX_EMPTY:
         bad.append(f"cases_without_windows: {total['cases_without_windows']} > {SWEEP_MAX_EMPTY}")
     if family == "plot" and total.get("cases_without_sites", 0) > PLOT_MAX_EMPTY:
         bad.append(f"cases_without_sites: {total['cases_without_sites']} > {PLOT_MAX_EMPTY}")
+    if family == "genome":
+        bad += [f"{k}: {len(total.get(k, ()))} of {n} seen" for k, n in GENOME_SEEN.items() if len(total.get(k, ())) != n]
+        bad += [f"{k}: {int((np.asarray(total.get(k, 0)) == 0).sum())} empty cells" for k in GENOME_TABLES if not np.all(np.asarray(total.get(k, 0)) > 0)]
+        if total.get("rank_rows_with_nan", 0) > GENOME_MAX_NAN_ROWS:
+            bad.append(f"rank_rows_with_nan: {total['rank_rows_with_nan']} > {GENOME_MAX_NAN_ROWS}")
     if family == "once":
         bad += [f"{k}: {len(total.get(k, ()))} of {n} seen" for k, n in ONCE_SEEN.items() if len(total.get(k, ())) != n]
         if total.get("cases_without_sites", 0) > ONCE_MAX_EMPTY:
@@ -1211,6 +2228,8 @@ def main():
     ap.add_argument("--best", action="store_true", help="fuzz ms_scan_best instead of ms_scan")
     ap.add_argument("--once", action="store_true", help="fuzz ms_scan_regions_once instead of ms_scan")
     ap.add_argument("--plot", action="store_true", help="fuzz ms_result_site_histogram and ms_result_rank_profile instead of ms_scan")
+    ap.add_argument("--genome", action="store_true", help="fuzz the pack / extract / base-count / window-filter / score-rank kernels instead of ms_scan")
+    ap.add_argument("--annot", action="store_true", help="fuzz ms_genes_nearest_tss and ms_genes_promoter_overlap instead of ms_scan")
     a = ap.parse_args()
     from oracle import oracle
     oracle.build()
@@ -1239,6 +2258,10 @@ def main():
                 else:
                     add_tally(tally, info)
             print(f"{name} fuzz: {a.cases} cases from seed {a.seed}: {bad} mismatches; tallies {shown(tally)}")
+            if name in ("genome", "annot") and not bad and a.seed == 0 and a.cases >= len(SEEDS[name]):
+                unmet = unmet_conditions(name, tally)
+                print(f"{name} fuzz: CONDITIONS {'met' if not unmet else 'NOT met: ' + '; '.join(unmet)}")
+                return 1 if unmet else 0
             return 1 if bad else 0
     bad, total_hits, fast, exact = 0, 0, 0, 0
     for k in range(a.cases):

@@ -4,7 +4,14 @@ on the decision boundary (fuzz_parity.CONDITIONS, tallied from the oracle's outp
 what they compared), and that the builders of the expected records are right, against the same scoring in plain Python floats (columns
 in order, raw / max_raw, score - cutoff >= -1e-10) on every seed small enough for it.  For the scan-once family also that its tally's
 view of the merged spans and of the hit keys' form is the library's own (_lib.union_bases, ms_debug_key_layout).
+The genome and annot families need no scoring oracle for most of what they expect: their cases are checked here against plain Python --
+byte counts, the oracle's convert_seq over the cut regions, a per-region loop of the reference's nearest-gene recurrence, any-overlap by
+brute force -- and the three debug entries they are sized and driven by are checked as far as no GPU is needed.
 """
+import ctypes
+import os
+import re
+
 import numpy as np
 import pytest
 
@@ -38,13 +45,21 @@ def expected(oracle):
 
 # ------------------------------------------------------------------------------------------------ the conditions
 
-@pytest.mark.parametrize("family", ["variants", "alleles", "best", "once"])
-def test_seeds_meet_the_conditions(expected, family):
+@pytest.mark.parametrize("family", ["variants", "alleles", "best", "once", "genome", "annot"])
+def test_seeds_meet_the_conditions(request, family):
+    if family == "genome":
+        tallies = list(request.getfixturevalue("genome_tallies").values())
+    elif family == "annot":
+        tallies = [tally for _, _, _, tally in request.getfixturevalue("annot_expected")]
+    else:
+        tallies = [tally for _, _, _, tally in request.getfixturevalue("expected")[family]]
     total = {}
-    for _, _, _, tally in expected[family]:
+    for tally in tallies:
         fp.add_tally(total, tally)
     print(f"{family}: seeds {fp.SEEDS[family]}: {fp.shown(total)}")
     assert not fp.unmet_conditions(family, total)
+    if family in ("genome", "annot"):                   # one counter per boundary: each at least 40 over the seeds, its floor at most half of it
+        assert all(total[k] >= 40 and 2 * n <= total[k] for k, n in fp.CONDITIONS[family].items()), {k: total[k] for k in fp.CONDITIONS[family]}
 
 
 def test_sweep_seeds_meet_the_conditions(oracle):
@@ -108,6 +123,160 @@ def test_plot_seeds_meet_the_conditions_and_the_integer_bin_rule():
     print(f"plot: seeds {fp.SEEDS['plot']}: {fp.shown(total)}")
     assert not fp.unmet_conditions("plot", total)
     assert 0 < total["cases_without_sites"] <= fp.PLOT_MAX_EMPTY
+
+
+# ------------------------------------------------------------------------------------------------ the genome and annot families
+
+@pytest.fixture(scope="module")
+def genome_tallies(oracle):
+    """seed -> tally of the genome family, with every case checked against plain Python while it is at hand (a case holds 1.5 MB)."""
+    dims, out = _lib.genome_dims(), {}
+    for seed in fp.SEEDS["genome"]:
+        case = fp.make_genome_case(seed, dims)
+        want, out[seed] = fp.expected_genome(oracle, case)
+        check_genome_case(oracle, seed, case, want, out[seed])
+    return out
+
+
+def unpacked(codes, nmask, n):
+    """The planes as one int8 code per base, -1 under a mask bit: convert_seq's own output format."""
+    i = np.arange(n)
+    cw = codes[0::2].astype(np.uint64) | (codes[1::2].astype(np.uint64) << np.uint64(32))
+    code = ((cw[i // 32] >> (2 * (i % 32)).astype(np.uint64)) & np.uint64(3)).astype(np.int8)
+    return np.where((nmask[i // 32] >> (i % 32).astype(np.uint32)) & 1, np.int8(-1), code)
+
+
+def check_genome_case(oracle, seed, case, want, tally):
+    bases, goff, dims = case["bases"], case["goff"], case["dims"]
+    # the expected planes are the oracle's convert_seq of the bytes, and keep the invariants the device's are asked for
+    for (b, o), (codes, nmask, blk2reg, blkinfo) in zip(case["packs"], want["packs"]):
+        assert np.array_equal(unpacked(codes, nmask, len(b)), oracle.convert_seq(b.tobytes())), seed
+        assert fp.plane_invariants_broken(codes, nmask, len(b)) is None, seed
+        assert np.all(o[blk2reg] <= 64 * np.arange(len(blk2reg))) and np.array_equal(blkinfo[:, 0], blk2reg), seed
+    cut, offsets = fp.packed_cut(bases, goff, case["regions"])
+    codes, nmask, blk2reg, blkinfo = want["extract"]
+    assert np.array_equal(unpacked(codes, nmask, len(cut)), oracle.convert_seq(cut.tobytes())), seed
+    assert fp.plane_invariants_broken(codes, nmask, len(cut)) is None, seed
+    # blkinfo restated: the region of position 64 b (the last one that starts at or before it), its start and the next two, relative
+    R = len(case["regions"])
+    for b in {0, 1, len(blk2reg) // 2, len(blk2reg) - 2, len(blk2reg) - 1, *range(dims["pack_block_bases"] // 64 - 2, dims["pack_block_bases"] // 64 + 2)}:
+        r = max(k for k in range(R) if offsets[k] <= 64 * b)
+        assert blk2reg[b] == r, (seed, b)
+        assert blkinfo[b].tolist() == [r, offsets[r] - 64 * b, offsets[min(r + 1, R)] - 64 * b, offsets[min(r + 2, R)] - 64 * b], (seed, b)
+    assert tally["phase_table"].min() >= 1 and tally["extract_lengths"] == set(range(fp.EXTRACT_MAX_LEN + 1)), seed
+    # base counts by bytes.count
+    for (cl, a), w in zip(case["counts"], want["counts"]):
+        off = np.concatenate([[0], np.cumsum(cl)])
+        for c in {0, len(cl) - 1, *np.flatnonzero(np.asarray(cl) == 33)[:3].tolist(), int(np.argmax(cl))}:
+            raw = a[off[c]:off[c + 1]].tobytes()
+            assert w[c].tolist() == [raw.count(x) + raw.count(x.lower()) for x in (b"A", b"C", b"G", b"T")], (seed, c)
+        assert int(w.sum()) == sum(a.tobytes().count(x) for x in (b"A", b"C", b"G", b"T", b"a", b"c", b"g", b"t")), seed
+    # the window filter in plain Python: count N and n in the byte slice, keep the first n_want indices
+    raw = bases.tobytes()
+    for call, taken in zip(case["calls"], want["taken"]):
+        L = call["length"]
+        ok = [k for k, g in enumerate(call["gstart"].tolist()) if raw[g:g + L].count(b"N") + raw[g:g + L].count(b"n") <= call["max_n"]]
+        assert taken.tolist() == ok[:call["n_want"]], seed
+        assert call["gstart"].min() >= 0 and call["gstart"].max() + L <= len(raw), seed
+    assert np.array_equal(want["exc_pos"], [i for i, x in enumerate(raw) if chr(x) not in "ACGTacgtNn"]), seed
+    # the sampled windows hold at most max_n N / n
+    names, arrs = fp.sampling_chroms(case)
+    for sm, (ci, st, _) in zip(case["samples"], want["samples"]):
+        assert len(ci) == sm["n_times"], seed
+        for c, a in zip(ci.tolist(), st.tolist()):
+            w = arrs[c][a:a + sm["length"]].tobytes()
+            assert len(w) == sm["length"] and w.count(b"N") + w.count(b"n") <= sm["max_n"], seed
+    # ranks: one motif with a NaN row at most, on the seeds that are meant to hold one; P no multiple of 3
+    assert tally["rank_rows_with_nan"] == int(seed in fp.GENOME_NAN_SEEDS) <= 1, seed
+    assert len(case["mats"]) % 3 and tally["max_raw_zero"] == tally["rank_rows_with_nan"], seed
+    R = len(want["score_regions"])
+    row = want["score"][case["strand"]]
+    for p in np.flatnonzero(want["rank_compared"]).tolist():
+        desc = -np.sort(-row[p], kind="stable")
+        for k, r in enumerate(want["ranks"].tolist()):
+            assert (np.isnan(want["rank_rows"][p, k]) and not 0 <= r < R) or want["rank_rows"][p, k] == desc[r], (seed, p, k)
+
+
+def test_genome_nan_rows_are_capped(genome_tallies):
+    """A motif whose oracle row holds a NaN is left out of the rank comparison: one per seed at most, GENOME_MAX_NAN_ROWS in all."""
+    n = [t["rank_rows_with_nan"] for t in genome_tallies.values()]
+    assert max(n) == 1 and 0 < sum(n) <= fp.GENOME_MAX_NAN_ROWS
+
+
+@pytest.fixture(scope="module")
+def annot_expected():
+    dims, out = _lib.genome_dims(), []
+    for seed in fp.SEEDS["annot"]:
+        case = fp.make_annot_case(seed, dims)
+        out.append((seed, case, *fp.expected_annot(None, case)))
+    return out
+
+
+def test_every_annot_seed_holds_the_three_kinds_of_block(annot_expected):
+    for seed, _, _, tally in annot_expected:
+        assert tally["lone_live_lane_blocks"] >= 1 and tally["lone_live_wave_blocks"] >= 1 and tally["blocks_frozen_in_tile_1"] >= 1, seed
+
+
+def test_annot_restatements_equal_plain_loops(annot_expected):
+    """nearest_restated (chunks of genes) against the reference's loop over one region's genes, on the lanes the scenarios are about and
+    a sample of the others at every cutoff, and against the gene-by-gene numpy recurrence on every region of three seeds; the literal
+    binary search against any-overlap by brute force where the two must agree (a hit is a real overlap; with intervals of one positive
+    width no overlap is missed)."""
+    for seed, case, want, _ in annot_expected:
+        off, tss, strand, chrom, start = case["off"], case["tss"], case["strand"], case["near_chrom"], case["near_start"]
+        rng = np.random.default_rng(seed)
+        c_lone = case["sizes"].index(case["dims"]["gene_tile"] + 1)
+        mine = np.flatnonzero(chrom == c_lone)
+        block = case["dims"]["near_threads"]
+        sample = {int(mine[case["lone"]]), int(mine[block + 64 * case["wave"]]), int(mine[block + 64 * (1 - case["wave"])]), int(mine[0 if case["lone"] else 1]),
+                  *np.flatnonzero(chrom == case["sizes"].index(2 * case["dims"]["gene_tile"] + 1))[:2].tolist(),
+                  *np.flatnonzero((chrom < 0) | (chrom >= len(case["sizes"]))).tolist(), *rng.integers(0, len(chrom), 12).tolist()}
+        for cutoff in fp.ANNOT_CUTOFFS:
+            dist, found = want["nearest"][cutoff]
+            for r in sample:
+                assert (int(dist[r]), bool(found[r])) == fp.nearest_plain(off, tss, strand, int(chrom[r]), int(start[r]), cutoff), (seed, cutoff, r)
+            if seed < 3:
+                d2, f2 = fp.nearest_stepwise(off, tss, strand, chrom, start, cutoff)
+                assert np.array_equal(dist, d2) and np.array_equal(found, f2), (seed, cutoff)
+        # the scenario lanes do what the case says they do, at the reference's own cutoff
+        dist, found = want["nearest"][fp.ANNOT_CUTOFFS[0]]
+        assert found[mine[case["lone"]]] and abs(int(dist[mine[case["lone"]]])) == 7, seed
+        others = np.delete(mine[:block], case["lone"])
+        assert found[others].all() and np.all(np.abs(dist[others]) < 3000), seed
+        for call, got in zip(case["calls"], want["overlap"]):
+            iv = fp.promoter_lists(case, call["upstream"], call["downstream"])
+            for r in rng.integers(0, len(got), 60).tolist():
+                ch, s_, e_ = int(call["chrom"][r]), int(call["start"][r]), int(call["end"][r])
+                brute = 0 <= ch < len(iv) and any(not (e_ <= lo or s_ >= hi) for lo, hi in iv[ch])
+                assert not got[r] or brute, (seed, r)
+                if call["upstream"] + call["downstream"] > 0 and s_ < e_ and call["upstream"] == call["downstream"]:
+                    assert got[r] == brute, (seed, r)
+
+
+def test_genome_debug_entries_without_a_gpu():
+    L = _lib.lib()
+    out = (ctypes.c_int32 * 8)()
+    assert L.ms_debug_genome_dims(out) == _lib.MS_OK
+    d = _lib.genome_dims()
+    assert list(out) == list(d.values()) and all(v > 0 for v in out)
+    assert d["count_tile_bases"] % 32 == 0 and d["pack_block_bases"] % 64 == 0 and d["filter_threads"] % 64 == 0 and d["near_threads"] % 64 == 0
+    assert d["rank_budget"] // 1_000_000 >= 100                    # build_motif's own n_random fits: a batch holds 100 motifs or more
+    assert L.ms_debug_genome_dims(None) == _lib.MS_ERR_INVALID
+    assert L.ms_debug_seqset_planes(None, None, None, None, None) == _lib.MS_ERR_INVALID
+    prev = _lib.score_rank_budget(12345)
+    try:
+        assert prev == 0 and _lib.score_rank_budget(7) == 12345
+        with pytest.raises(ValueError):
+            _lib.score_rank_budget(-1)
+        assert _lib.score_rank_budget(0) == 7
+    finally:
+        _lib.score_rank_budget(0)
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "motifscan_amd_debug.h")) as fh:
+        text = fh.read()
+    assert re.search(r"\bint\s+ms_debug_genome_dims\s*\(\s*int32_t\s+out\s*\[\s*8\s*\]\s*\)", text)
+    assert re.search(r"\bint\s+ms_debug_seqset_planes\s*\(", text) and re.search(r"\bint\s+ms_debug_score_rank_budget\s*\(", text)
+    for name in ("genome_dims", "seqset_planes", "score_rank_budget"):
+        assert callable(getattr(_lib, name))
 
 
 # ------------------------------------------------------------------------------------------------ the builders, against Python floats

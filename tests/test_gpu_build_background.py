@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+from fuzz_parity import ref_random_sequences          # Genome.random_sequences restated step by step (shared with the genome fuzz family)
 from motifscan_amd import _lib, build, genome, matrix
 
 pytestmark = pytest.mark.gpu
@@ -47,25 +48,6 @@ def _state(d, i):
 
 def _same_state(a, b):
     return a[0] == b[0] and np.array_equal(a[1], b[1]) and a[2:] == b[2:]
-
-
-def ref_random_sequences(chroms, n_times, length, max_n=0, random_seed=None):
-    """Genome.random_sequences (genome/__init__.py:137-176) restated over a dict of strings, step by step."""
-    if random_seed is not None:
-        np.random.seed(random_seed)
-    sizes = {c: len(s) for c, s in chroms.items()}
-    names = sorted(chroms)
-    total = sum(sizes.values())
-    random_chroms = np.random.choice(names, size=n_times, p=[sizes[c] / total for c in names])
-    out, n_loop = [], 0
-    while len(out) < n_times:
-        chrom = random_chroms[n_loop % n_times]
-        start = np.random.randint(sizes[chrom] - length)
-        seq = chroms[chrom][start:start + length]
-        if seq.count("N") + seq.count("n") <= max_n:
-            out.append(seq)
-        n_loop += 1
-    return out
 
 
 @pytest.fixture(scope="module")

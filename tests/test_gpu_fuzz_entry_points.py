@@ -3,7 +3,10 @@ The boundary fuzz of tests/fuzz_parity.py on the four entry points beside ms_sca
 ms_scan_alleles (ms_alleles.hip), ms_scan_best (ms_best.hip) and ms_scan_sweep (ms_sweep.hip) -- against the pinned oracle: tie-rich
 matrices, cutoffs on attainable scores and one ulp / 1e-10 either side, huge and tiny magnitudes, max_raw == 0, N runs and lower case.
 The plot family (ms_result_site_histogram, ms_result_rank_profile; ms_plotdata.hip) runs beside them over synthetic hit arrays: centres
-on and around the bin edges, region counts on the rank words' and profile tiles' edges, against numpy alone.
+on and around the bin edges, region counts on the rank words' and profile tiles' edges, against numpy alone.  The genome family holds the
+kernels either side of the scan (pack, extract, region hints, base counts, the window filter, scores and ranks) against the host packer,
+numpy counts, the restated sampler and the oracle's c_score; the annot family holds ms_genes_nearest_tss and ms_genes_promoter_overlap
+against the reference's walks restated.
 Every comparison is exact (integers by value, scores by their bits; the smoothed profiles within their derived bound).  After its seeds each test asserts, on the tallies of what was
 compared, that the seeds did sit on the boundary (fuzz_parity.CONDITIONS); tests/test_fuzz_cases_host.py asserts the same without a GPU.
 """
@@ -22,7 +25,7 @@ def _device():
     _lib.set_device(0)
 
 
-@pytest.mark.parametrize("family", ["variants", "alleles", "best", "plot"])
+@pytest.mark.parametrize("family", ["variants", "alleles", "best", "plot", "genome", "annot"])
 def test_fuzz_entry_point(oracle, family):
     total = {}
     for seed in fuzz_parity.SEEDS[family]:
