@@ -72,6 +72,9 @@
  *   ms_scan_alleles / ms_allelescan_*
  *                         the same for alleles of any length (multi-base, insertions, deletions): the windows of the ref and of the
  *                         spliced alt haplotype that the allele touches, each scored on its own haplotype
+ *   ms_scan_alleles_best / ms_allelebest_*
+ *                         no reference counterpart: the maximum of cscore.c:336-390 over the windows an allele touches, per haplotype --
+ *                         the best-scoring window of every (motif, variant, haplotype) cell, the dense form of ms_scan_alleles
  *   ms_scan_best / ms_best_*
  *                         no reference counterpart: the maximum of cscore.c:336-390 over a region -- the best-scoring window of every
  *                         (motif, region) cell, the dense score matrix behind "max motif score per peak"
@@ -381,6 +384,37 @@ int  ms_allelescan_ref_mismatch(const ms_allelescan *as, uint8_t *out /* [V] */)
 /* Device time of the call that made the result: upload of the variants -> last kernel done. */
 int  ms_allelescan_device_ms(const ms_allelescan *as, double *ms);
 void ms_allelescan_free(ms_allelescan *as);
+
+/* ---- the best-scoring window of every (motif, variant, haplotype) cell: ms_scan_alleles without a cutoff, dense (ms_allelebest.hip) ---------- */
+/* The variant arguments, their validation, the alt-byte conversion, the REF check and the MS_ERR_* cases are ms_scan_alleles's, word for word;
+ * so are the affected windows of motif m (width W): ref-haplotype starts s in [max(0, x - W + 1), min(x + r - 1, L - W)] and alt-haplotype
+ * starts t in [max(0, x - W + 1), min(x + a - 1, L' - W)], the empty-allele and W = 1 cases included.  Every window is scored as ms_scan scores
+ * it (columns in order, forward M[b][c], reverse M[3 - b][W - 1 - c] at the same step, +0.0 for a base that adds nothing, raw / max_raw as one
+ * IEEE fp64 divide).  The cutoffs of the PWM set are not read.
+ * The BEST SITE of (m, v, haplotype) follows ms_scan_best's rule over that haplotype's affected windows: start ascending, '+' before '-',
+ * from best = -inf, a window replacing the best iff score > best -- NaN and -inf never win, ties keep the earlier window.  Per cell and
+ * haplotype: score (double), offset (int32) = winning start - x in that haplotype's own coordinates, in [-(W - 1), max(r, a) - 1], and strand
+ * (int8, 1 or 2).  A cell without a winner -- no affected window, a haplotype shorter than W, -inf in every window -- holds (NaN, 0, 0):
+ * strand == 0 is the marker.  So does every cell of an UNSCORABLE motif (ms_scan_best's definition: max_raw not a finite number > 0, or a
+ * NaN or +inf entry).  The bytes of all six arrays are the same on every run and do not depend on the variant chunking
+ * (ms_debug_varscan_chunk).  MS_ERR_NOMEM, with nothing launched, when the 26 bytes x n_pwms x n_variants do not fit the device.
+ * n_variants = 0 is valid and gives an empty result.  Without a device: MS_ERR_RUNTIME ("no CPU fallback") before anything else. */
+typedef struct ms_allelebest ms_allelebest;
+int  ms_scan_alleles_best(const ms_pwmset *pwms, const ms_genome *genome, const int32_t *chrom, const int64_t *pos, const int32_t *ref_len,
+                          const char *alt_bases, const int64_t *alt_offsets /* [V+1] */, const char *ref_bases /* or NULL */,
+                          int64_t n_variants, int strand_mask, uint32_t flags /* 0 */, ms_allelebest **out);
+int  ms_allelebest_shape(const ms_allelebest *b, int32_t *n_pwms, int64_t *n_variants);
+/* Motifs m0 <= m < m1 into host buffers [(m1 - m0)][V] row-major; any pointer may be NULL.  MS_ERR_INVALID for m0 < 0, m1 > n_pwms, m0 > m1. */
+int  ms_allelebest_sites(const ms_allelebest *b, int32_t m0, int32_t m1, double *score_ref, int32_t *offset_ref, int8_t *strand_ref,
+                         double *score_alt, int32_t *offset_alt, int8_t *strand_alt);
+/* Device pointers of the full [n_pwms][V] arrays, valid until free; any pointer may be NULL. */
+int  ms_allelebest_sites_device(const ms_allelebest *b, void **d_score_ref, void **d_offset_ref, void **d_strand_ref, void **d_score_alt,
+                                void **d_offset_alt, void **d_strand_alt);
+/* 1 per variant whose REF differs from the genome (ms_allelescan_ref_mismatch's rule), 0 for every variant when ref_bases was NULL. */
+int  ms_allelebest_ref_mismatch(const ms_allelebest *b, uint8_t *out /* [V] */);
+/* Device time of the call that made the result: upload of the variants -> last kernel done. */
+int  ms_allelebest_device_ms(const ms_allelebest *b, double *ms);
+void ms_allelebest_free(ms_allelebest *b);
 
 /* ---- the best-scoring window of every (motif, region) cell: the dense motif x region matrix (ms_best.hip) ---------- */
 /* For motif m of width W and region r of length L, over the window starts pos = 0 .. L - W and the strands of strand_mask: score(pos, strand)

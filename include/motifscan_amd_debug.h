@@ -63,10 +63,17 @@ int ms_debug_key_layout(int64_t n_bases, int64_t n_seqs, int64_t max_len, int32_
  * test can force the "buffer too small -> grow -> run the pass again" path.  Needs a GPU. */
 int ms_debug_release_scratch(void);
 
-/* ms_scan_variants (and ms_scan_alleles: the same knob) takes its variants in chunks (the per-(motif, tile) record counts of one chunk are bounded); n_variants > 0 sets the
+/* ms_scan_variants (and ms_scan_alleles and ms_scan_alleles_best: the same knob) takes its variants in chunks (the per-(motif, tile) record counts of one chunk are bounded,
+ * ms_scan_alleles_best's chunks bound its grids); n_variants > 0 sets the
  * chunk size for the calls that follow in this process, 0 gives it back to the library.  *previous (may be NULL) = the value before.
  * The result of a scan does not depend on it: a test proves that with a chunk of a few variants.  Needs no GPU. */
 int ms_debug_varscan_chunk(int64_t n_variants, int64_t *previous);
+
+/* The sizes at which ms_scan_alleles_best changes path, as constants of the build: out[0] the variants of one block's tile (a thread per
+ * variant); out[1] the window count -- both haplotypes of a cell together -- above which a cell that is not a single-base substitution
+ * takes the wave path (a wave per haplotype); out[2] the widest motif whose table is staged in LDS (wider ones read it from HBM).  Tests
+ * size their boundary cases from here.  Needs no GPU. */
+int ms_debug_allelebest_dims(int32_t out[3]);
 
 /* ms_scan_best cuts a region into segments of this many window starts (one wave each); a region of more than one segment goes through the
  * per-segment partials and their reduction.  A constant of the build: a test sizes a region of more than two segments with it.  Needs no GPU. */

@@ -192,6 +192,14 @@ def lib():
         "ms_allelescan_ref_mismatch": (c_int, [vp, pu8]),
         "ms_allelescan_device_ms": (c_int, [vp, pd]),
         "ms_allelescan_free": (None, [vp]),
+        "ms_scan_alleles_best": (c_int, [vp, vp, pi32, pi64, pi32, ctypes.c_char_p, pi64, ctypes.c_char_p, c_i64, c_int, c_u32, pvp]),
+        "ms_allelebest_shape": (c_int, [vp, pi32, pi64]),
+        "ms_allelebest_sites": (c_int, [vp, c_i32, c_i32, pd, pi32, pi8, pd, pi32, pi8]),
+        "ms_allelebest_sites_device": (c_int, [vp, pvp, pvp, pvp, pvp, pvp, pvp]),
+        "ms_allelebest_ref_mismatch": (c_int, [vp, pu8]),
+        "ms_allelebest_device_ms": (c_int, [vp, pd]),
+        "ms_allelebest_free": (None, [vp]),
+        "ms_debug_allelebest_dims": (c_int, [pi32]),
         "ms_scan_best": (c_int, [vp, vp, c_int, c_u32, pvp]),
         "ms_best_shape": (c_int, [vp, pi32, pi64]),
         "ms_best_sites": (c_int, [vp, c_i32, c_i32, pd, pi32, pi8]),
@@ -1027,7 +1035,7 @@ def scan_variants(pwms, genome, chrom_idx, pos, alt, strand_mask=3, flags=0):
 
 
 def varscan_chunk(n_variants):
-    """ms_debug_varscan_chunk: variants per chunk of scan_variants and scan_alleles for the calls that follow (0 = the library's own); returns the
+    """ms_debug_varscan_chunk: variants per chunk of scan_variants, scan_alleles and scan_alleles_best for the calls that follow (0 = the library's own); returns the
     value before.  Tests only."""
     prev = ctypes.c_int64()
     check(lib().ms_debug_varscan_chunk(int(n_variants), ctypes.byref(prev)))
@@ -1246,6 +1254,97 @@ def scan_alleles(pwms, genome, chrom_idx, pos, ref_len, alts, refs=None, strand_
                                 ab.ctypes.data_as(ctypes.c_char_p), ptr(ao, ctypes.c_int64),
                                 None if rb is None else rb.ctypes.data_as(ctypes.c_char_p), ci.size, int(strand_mask), int(flags), ctypes.byref(h)))
     return AlleleScan(h, pwms.n, ci.size)
+
+
+class AlleleBest:
+    """The result of one ms_scan_alleles_best call: the best-scoring window of every (motif, variant, haplotype) cell
+    (include/motifscan_amd.h).  sites(m0, m1) copies out the six (m1 - m0, V) arrays of a motif range: score (float64), offset (int32,
+    winning start - x in that haplotype's coordinates) and strand (int8: 1 '+', 2 '-') for the ref and for the alt haplotype; a cell
+    without a winner holds NaN / 0 / 0.  The object owns the device arrays until close(): keep it alive while device_pointers() are in use."""
+
+    FIELDS = ("score_ref", "offset_ref", "strand_ref", "score_alt", "offset_alt", "strand_alt")
+
+    def __init__(self, handle):
+        self.h = handle
+        p, v = ctypes.c_int32(), ctypes.c_int64()
+        check(lib().ms_allelebest_shape(self.h, ctypes.byref(p), ctypes.byref(v)))
+        self.n_pwms, self.n_variants = p.value, v.value
+
+    @property
+    def shape(self):
+        return (self.n_pwms, self.n_variants)
+
+    def sites(self, m0=0, m1=None):
+        """dict of fresh (m1 - m0, V) arrays: score_ref, offset_ref, strand_ref, score_alt, offset_alt, strand_alt."""
+        if self.h is None:
+            raise ValueError("the result is closed")
+        m1 = self.n_pwms if m1 is None else int(m1)
+        m0 = int(m0)
+        if m0 < 0 or m1 > self.n_pwms or m0 > m1:
+            raise ValueError(f"motif range [{m0}, {m1}) outside [0, {self.n_pwms})")
+        shape = (m1 - m0, self.n_variants)
+        out = {}
+        for hap in ("ref", "alt"):
+            out["score_" + hap] = np.zeros(shape, dtype=np.float64)
+            out["offset_" + hap] = np.zeros(shape, dtype=np.int32)
+            out["strand_" + hap] = np.zeros(shape, dtype=np.int8)
+        check(lib().ms_allelebest_sites(self.h, m0, m1, ptr(out["score_ref"], ctypes.c_double), ptr(out["offset_ref"], ctypes.c_int32),
+                                        ptr(out["strand_ref"], ctypes.c_int8), ptr(out["score_alt"], ctypes.c_double),
+                                        ptr(out["offset_alt"], ctypes.c_int32), ptr(out["strand_alt"], ctypes.c_int8)))
+        return out
+
+    def ref_mismatch(self):
+        """bool per input variant: its REF string is not what the genome holds (all False when no REF strings were given)."""
+        out = np.zeros(self.n_variants, dtype=np.uint8)
+        check(lib().ms_allelebest_ref_mismatch(self.h, ptr(out, ctypes.c_uint8)))
+        return out.astype(bool)
+
+    def device_pointers(self):
+        """dict of the device addresses of the six full (P, V) arrays, valid until close()."""
+        a = [ctypes.c_void_p() for _ in self.FIELDS]
+        check(lib().ms_allelebest_sites_device(self.h, *[ctypes.byref(x) for x in a]))
+        return {k: x.value for k, x in zip(self.FIELDS, a)}
+
+    def device_ms(self):
+        ms = ctypes.c_double()
+        check(lib().ms_allelebest_device_ms(self.h, ctypes.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ms_allelebest_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+
+def scan_alleles_best(pwms, genome, chrom_idx, pos, ref_len, alts, refs=None, strand_mask=3, flags=0):
+    """ms_scan_alleles_best: scan_alleles' arguments (the PwmSet's cutoffs are not read); the best window of every (motif, variant,
+    haplotype) cell.  Returns an AlleleBest."""
+    ci = np.ascontiguousarray(chrom_idx, dtype=np.int32)
+    ps = np.ascontiguousarray(pos, dtype=np.int64)
+    rl = np.ascontiguousarray(ref_len, dtype=np.int32)
+    ab, ao = _flatten_alleles(alts)
+    if ci.ndim != 1 or not (ci.size == ps.size == rl.size == ao.size - 1):
+        raise ValueError("chrom_idx, pos, ref_len and alts must have one entry per variant")
+    rb = None
+    if refs is not None:
+        rb, ro = _flatten_alleles(refs)
+        if ro.size - 1 != ci.size or not np.array_equal(np.diff(ro), rl):
+            raise ValueError("refs must hold one string of ref_len bytes per variant")
+    h = ctypes.c_void_p()
+    check(lib().ms_scan_alleles_best(pwms.h, genome.h, ptr(ci, ctypes.c_int32), ptr(ps, ctypes.c_int64), ptr(rl, ctypes.c_int32),
+                                     ab.ctypes.data_as(ctypes.c_char_p), ptr(ao, ctypes.c_int64),
+                                     None if rb is None else rb.ctypes.data_as(ctypes.c_char_p), ci.size, int(strand_mask), int(flags), ctypes.byref(h)))
+    return AlleleBest(h)
+
+
+def allelebest_dims():
+    """ms_debug_allelebest_dims: dict(tile, long_windows, lds_max_width) -- variants per block tile, the window count above which a cell
+    takes the wave path, the widest motif whose table is staged in LDS.  Constants of the build; no device."""
+    out = np.zeros(3, dtype=np.int32)
+    check(lib().ms_debug_allelebest_dims(ptr(out, ctypes.c_int32)))
+    return dict(zip(("tile", "long_windows", "lds_max_width"), out.tolist()))
 
 
 class PinnedBuffer:

@@ -1,0 +1,122 @@
+// ms_allele_dev.h -- what the kernels over sequence-resolved alleles share (ms_alleles.hip: the records of the windows that pass;
+// ms_allelebest.hip: the best window per haplotype): a variant's prep record, the count of the windows an allele touches, the alt planes
+// and the spliced read of an alt-haplotype step.  ms_alleles.hip's header comment has the geometry.
+#pragma once
+#include "ms_device.h"
+
+namespace ms {
+
+namespace {
+
+constexpr int32_t kAlFar = 1 << 30;
+constexpr int kAlPlanePad = 4;                  // zero words behind either alt plane: code_window reads 3 words, n_window 2
+
+struct AlRec {                                   // what an item needs of its variant
+    int64_t g;                                   // position of x in the packed genome
+    int64_t aoff;                                // first alt base in the alt planes
+    int32_t lo;                                  // bases of the chromosome in front of x (clamped to kAlFar)
+    int32_t hi;                                  // ... and from x + r on
+    int32_t r, a;
+};
+
+// windows of a haplotype whose allele has len bases, lo bases in front of it and hi behind (the header of ms_alleles.hip)
+__host__ __device__ __forceinline__ uint32_t allele_windows(int32_t lo, int32_t hi, int32_t len, int W) {
+    const int64_t n = (int64_t) len + (hi - W + 1 < 0 ? hi - W + 1 : 0) + (lo < W - 1 ? lo : W - 1);
+    return n > 0 ? (uint32_t) n : 0u;
+}
+
+// convert_seq (cscore.c:81-114) for 32 alt bytes a thread: two code words and a mask word in the genome's layout
+__global__ void __launch_bounds__(256) al_pack_kernel(const uint8_t *__restrict__ alt, int64_t A, uint32_t *__restrict__ acodes, uint32_t *__restrict__ amask) {
+    const int64_t w = (int64_t) blockIdx.x * blockDim.x + threadIdx.x, b0 = w * 32;
+    if (b0 >= A) return;
+    uint64_t code = 0;
+    uint32_t mask = 0;
+    const int n = (int) (A - b0 < 32 ? A - b0 : 32);
+    for (int k = 0; k < n; k++) {
+        const uint32_t ch = (uint32_t) alt[b0 + k] | 0x20u;                            // fold case (cscore.c:93-108)
+        const bool acgt = ch == 0x61u || ch == 0x63u || ch == 0x67u || ch == 0x74u;
+        if (acgt) code |= (uint64_t) (((ch >> 1) ^ (ch >> 2)) & 3u) << (2 * k);
+        else mask |= 1u << k;
+    }
+    acodes[2 * w] = (uint32_t) code;
+    acodes[2 * w + 1] = (uint32_t) (code >> 32);
+    amask[w] = mask;
+}
+
+// the variant's place and clip distances, and (ref != nullptr) its REF string against the genome: case-insensitive, a non-ACGT genome
+// base matches any letter that is not A, C, G or T
+__global__ void __launch_bounds__(256) al_prep_kernel(const uint32_t *__restrict__ codes, const uint32_t *__restrict__ nmask,
+                                                      const int64_t *__restrict__ offsets, const int32_t *__restrict__ chrom,
+                                                      const int64_t *__restrict__ pos, const int32_t *__restrict__ ref_len,
+                                                      const int64_t *__restrict__ alt_off, const uint8_t *__restrict__ ref,
+                                                      const int64_t *__restrict__ ref_off, int64_t V, AlRec *__restrict__ rec,
+                                                      uint8_t *__restrict__ mismatch) {
+    const int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= V) return;
+    const int64_t beg = offsets[chrom[v]], end = offsets[chrom[v] + 1], x = pos[v], g = beg + x;
+    const int32_t r = ref_len[v];
+    AlRec q;
+    q.g = g;
+    q.aoff = alt_off[v];
+    q.lo = (int32_t) (x < kAlFar ? x : kAlFar);
+    q.hi = (int32_t) (end - g - r < kAlFar ? end - g - r : kAlFar);
+    q.r = r;
+    q.a = (int32_t) (alt_off[v + 1] - alt_off[v]);
+    rec[v] = q;
+    uint32_t bad = 0u;
+    if (ref) {
+        const uint8_t *__restrict__ s = ref + ref_off[v];
+        for (int32_t i = 0; i < r; i++) {
+            const int64_t p = g + i;
+            const uint32_t code = (codes[p >> 4] >> (2u * ((uint32_t) p & 15u))) & 3u;
+            const uint32_t isn = (nmask[p >> 5] >> ((uint32_t) p & 31u)) & 1u;
+            const uint32_t ch = (uint32_t) s[i] | 0x20u;
+            const bool acgt = ch == 0x61u || ch == 0x63u || ch == 0x67u || ch == 0x74u;
+            const uint32_t want = ((ch >> 1) ^ (ch >> 2)) & 3u;
+            bad |= acgt ? (isn || code != want) : !isn;
+        }
+    }
+    mismatch[v] = (uint8_t) bad;
+}
+
+__device__ __forceinline__ uint64_t low_mask2(int n) { return n >= 32 ? ~0ULL : ((1ULL << (2 * n)) - 1ULL); }
+
+// columns [0, n) of the 32-column step that starts d bases behind x on the alt haplotype of q (d < 0: in front of x): the code word and
+// the non-ACGT mask, whatever lies past column n undefined.  Every read stays inside its array: a genome read starts inside the
+// chromosome (the window does), an alt-plane read at one of the allele's own bases.
+__device__ __forceinline__ void alt_step(const uint32_t *__restrict__ codes, const uint32_t *__restrict__ nmask, const uint32_t *__restrict__ acodes,
+                                         const uint32_t *__restrict__ amask, const AlRec &q, int d, int n, uint64_t &cw, uint32_t &nw) {
+    if (d + n <= 0) {                                          // wholly left of the allele
+        cw = code_window(codes, q.g + d);
+        nw = n_window(nmask, q.g + d);
+        return;
+    }
+    if (d >= q.a) {                                            // wholly right of it
+        const int64_t g = q.g + q.r + (d - q.a);
+        cw = code_window(codes, g);
+        nw = n_window(nmask, g);
+        return;
+    }
+    const int nl = d < 0 ? -d : 0;                             // columns of the genome left of x: < n <= 32
+    const int ja = d < 0 ? 0 : d;                              // first alt base of the step
+    const int na = (q.a - ja) < (32 - nl) ? (q.a - ja) : (32 - nl);
+    const int nr0 = nl + na;                                   // first column of the genome from x + r on
+    cw = 0;
+    nw = 0;
+    if (nl > 0) {
+        cw = code_window(codes, q.g + d) & low_mask2(nl);
+        nw = n_window(nmask, q.g + d) & low_mask(nl);
+    }
+    if (na > 0) {
+        cw |= (code_window(acodes, q.aoff + ja) & low_mask2(na)) << (2 * nl);
+        nw |= (n_window(amask, q.aoff + ja) & low_mask(na)) << nl;
+    }
+    if (nr0 < n) {                                             // (then the allele ends in this step: column nr0 is base x + r)
+        cw |= code_window(codes, q.g + q.r) << (2 * nr0);
+        nw |= n_window(nmask, q.g + q.r) << nr0;
+    }
+}
+
+}  // namespace
+
+}  // namespace ms

@@ -1,0 +1,595 @@
+// ms_allelebest.hip -- the best-scoring window of every (motif, variant, haplotype) cell (ms_scan_alleles_best): the dense, cutoff-free
+// form of ms_scan_alleles, as ms_scan_best is the dense form of ms_scan.
+//
+// For variant v = (chromosome, x, r, alt[0..a)) and motif m of width W the affected windows of either haplotype are ms_alleles.hip's
+// (allele_windows: starts max(0, x - W + 1) .. min(x + len - 1, L_h - W) in that haplotype's coordinates), each scored as ms_scan scores
+// it (columns 0 .. W - 1, forward M[b][c], reverse M[3 - b][W - 1 - c] at the same step, +0.0 for a base that adds nothing, raw / max_raw
+// as one IEEE divide), and per haplotype they are walked in the reference's order -- start ascending, '+' before '-' -- from best = -inf,
+// a window replacing the best iff its score is GREATER (ms_best.hip's rule).  26 bytes leave per cell: (score, offset, strand) twice.
+//
+// Mapping.  A block owns one motif and a tile of kAbTile variants; the motif's tab2 entries sit in LDS behind an all-zero entry
+// (var_scan_kernel's layout), motifs wider than kAbTabMaxW read them from HBM.
+//   Short cells (ab_cell_kernel): ONE THREAD per (variant) cell walks the windows of the ref and then of the alt haplotype one after
+//   the other, in the reference's order, so that order holds by construction: no cross-lane reduction.  A single-base substitution
+//   (r = a = 1) takes var_scan_kernel's walk: one pass over the columns gives the four raw sums of a window, the alt entry of column
+//   k = x - s read once per window and selected.  For W <= 32 the 64 bases that hold all of a substitution's windows are read once and
+//   window j's code / mask words are shifted out of those registers; wider motifs and the spliced walks read per window and step.
+//   Long cells (ab_wave_kernel, a launch of its own so that the short path stays convergent): a cell that is not a substitution and has
+//   more than kAbLongWindows affected windows on its two haplotypes together -- long insertions and deletions -- gets a wave per
+//   (variant, haplotype); lanes stride over the windows and wave_best's total order decides (the greater q, equal q to the smaller
+//   (start, strand) key).  The candidates are listed on the host (an upper bound that does not look at the motif); a wave whose cell is
+//   short for its motif leaves at once, and ab_cell_kernel skips exactly the cells for which the same test says long.
+//
+// The divide is paid only by a window whose raw sum is strictly greater than the lane's best raw sum so far (ms_best.hip: with max_raw > 0
+// a correctly rounded divide is monotone, so raw <= best_raw gives q <= best_q).  It stays exact per lane in the strided form because a
+// lane's windows still ASCEND: a window with raw <= best_raw has q <= best_q and a greater (start, strand) key than the lane's best, so it
+// loses under the total order as well as under the sequential rule; the lane's result is the first maximum of ITS windows, and the first
+// maximum of the cell is, among the lanes' first maxima with the greatest q, the one of the smallest key -- what wave_best returns.
+//
+// No floating-point atomic, no sort, no data-dependent order; each of the six outputs of a cell is written exactly once: a scorable
+// motif's short cells by their thread, its long cells by lane 0 of their two waves, every cell of an unscorable motif (ms_best.hip's
+// definition) by ab_cell_kernel as the "no winner" triple (NaN, 0, 0).  Variants go in chunks (the grid's limits); the bytes do not depend
+// on them (ms_debug_varscan_chunk sets the chunk here too).
+#include <algorithm>
+#include <memory>
+#include <type_traits>
+
+#include "ms_allele_dev.h"
+#include "ms_best_dev.h"
+#include "ms_device.h"
+#include "ms_handles.h"
+
+struct ms_allelebest {
+    int device = 0;
+    int32_t P = 0;
+    int64_t V = 0;
+    void *block = nullptr;                            // one pooled device block holding the six [P][V] arrays
+    size_t block_bytes = 0;
+    double *d_score[2] = {nullptr, nullptr};          // [0] ref haplotype, [1] alt; NaN: no winner
+    int32_t *d_offset[2] = {nullptr, nullptr};        // winning start - x
+    int8_t *d_strand[2] = {nullptr, nullptr};         // 1 '+', 2 '-', 0: no winner
+    std::vector<uint8_t> mismatch;                    // [V]
+    double device_ms = 0.0;                           // first launch -> last kernel done
+};
+
+namespace ms {
+
+namespace {
+
+constexpr int kAbThreads = 256;
+constexpr int kAbTile = kAbThreads;             // variants per block: a thread each
+constexpr int kAbLongWindows = 96;              // a cell (not a substitution) of more windows than this on both haplotypes together takes the wave path
+constexpr int kAbTabMaxW = 896;                 // widest motif whose table (W x 4 entries, 56 KB) is staged in LDS; wider ones read it from HBM
+constexpr int64_t kAbChunk = 1LL << 24;         // variants per launch (65536 tiles)
+constexpr int kAbWaves = kAbThreads / 64;
+
+struct AbOut {
+    double *score[2];
+    int32_t *offset[2];
+    int8_t *strand[2];
+};
+
+struct AbArgs {
+    const uint32_t *codes, *nmask, *acodes, *amask;
+    int64_t n_bases;                             // bases of the packed genome
+    DevPwm Pw;
+    const uint8_t *scorable;                     // [P]
+    const AlRec *rec;                            // [V]
+    int64_t V;
+    int strand_mask;
+    AbOut O;
+};
+
+__device__ __forceinline__ bool ab_is_snv(const AlRec &q) { return q.r == 1 && q.a == 1; }
+
+// the test both kernels make: this cell goes to the wave path
+__device__ __forceinline__ bool ab_is_long(const AlRec &q, int W) {
+    return !ab_is_snv(q) && allele_windows(q.lo, q.hi, q.r, W) + allele_windows(q.lo, q.hi, q.a, W) > (uint32_t) kAbLongWindows;
+}
+
+// N columns from c1 on of the 32-column step at column c0, added in column order (var_scan_kernel's and al_scan_kernel's step: the reads are
+// issued together).  TWO: a second pair of sums takes entry tk in place of the table's at column kk (the alt allele of a substitution).
+template <bool LDS_TAB, bool TWO, int N>
+__device__ __forceinline__ void ab_cols(const double2 *lds, const double2 *__restrict__ tab_g, uint32_t zero, int c0, int n, int c1, uint64_t cw,
+                                        uint32_t skip, int kk, double2 tk, double &rf, double &rr, double &af, double &ar) {
+    double2 t[N];
+#pragma unroll
+    for (int u = 0; u < N; u++) {
+        const int c = c1 + u;
+        const bool nothing = (skip >> c) & 1u;                          // adds +0.0: a sum that started at +0.0 is never -0.0
+        if constexpr (LDS_TAB) {
+            t[u] = lds[nothing ? zero : (uint32_t) (c0 + c) * 4u + ((uint32_t) (cw >> (2 * c)) & 3u)];
+        } else {
+            const int cc = c < n ? c : n - 1;                           // clamped: always an entry of the motif
+            t[u] = tab_g[(uint32_t) (c0 + cc) * 4u + ((uint32_t) (cw >> (2 * cc)) & 3u)];
+            if (nothing) t[u] = make_double2(0.0, 0.0);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < N; u++) {
+        rf += t[u].x;
+        rr += t[u].y;
+        if constexpr (TWO) {
+            const double2 ta = (c1 + u == kk) ? tk : t[u];
+            af += ta.x;
+            ar += ta.y;
+        }
+    }
+}
+
+// the n <= 32 columns of the step at c0: eight columns a time while more than four are left, then four
+template <bool LDS_TAB, bool TWO>
+__device__ __forceinline__ void ab_step(const double2 *lds, const double2 *__restrict__ tab_g, uint32_t zero, int c0, int n, uint64_t cw, uint32_t nw,
+                                        int kk, double2 tk, double &rf, double &rr, double &af, double &ar) {
+    const uint32_t skip = nw | ~low_mask(n);                            // bit c: column c0 + c adds nothing
+    int c1 = 0;
+    for (; n - c1 > 4; c1 += 8) ab_cols<LDS_TAB, TWO, 8>(lds, tab_g, zero, c0, n, c1, cw, skip, kk, tk, rf, rr, af, ar);
+    if (n - c1 > 0) ab_cols<LDS_TAB, TWO, 4>(lds, tab_g, zero, c0, n, c1, cw, skip, kk, tk, rf, rr, af, ar);
+}
+
+// window `rel` (its start, from x on) of haplotype hap (0 ref, 1 alt) of q: the two raw sums
+template <bool LDS_TAB>
+__device__ __forceinline__ void ab_window(const AbArgs &A, const double2 *lds, const double2 *__restrict__ tab_g, uint32_t zero, int W, const AlRec &q,
+                                          int hap, int rel, double &fw, double &rv) {
+    fw = 0.0;
+    rv = 0.0;
+    double u0 = 0.0, u1 = 0.0;
+    for (int c0 = 0; c0 < W; c0 += 32) {
+        const int n = (W - c0) < 32 ? (W - c0) : 32;
+        uint64_t cw;
+        uint32_t nw;
+        if (hap) {
+            alt_step(A.codes, A.nmask, A.acodes, A.amask, q, rel + c0, n, cw, nw);
+        } else {
+            cw = code_window(A.codes, q.g + rel + c0);
+            nw = n_window(A.nmask, q.g + rel + c0);
+        }
+        ab_step<LDS_TAB, false>(lds, tab_g, zero, c0, n, cw, nw, -1, make_double2(0.0, 0.0), fw, rv, u0, u1);
+    }
+}
+
+struct AbBest {                                  // a lane's best of one haplotype
+    double raw, q;
+    int32_t at;                                  // what the caller numbers its windows by
+    int32_t strand;                              // 0: none yet
+};
+
+__device__ __forceinline__ AbBest ab_none() {
+    AbBest b;
+    b.raw = -std::numeric_limits<double>::infinity();
+    b.q = b.raw;
+    b.at = 0;
+    b.strand = 0;
+    return b;
+}
+
+// '+' then '-': the divide only where the raw sum improves (the header comment)
+__device__ __forceinline__ void ab_take(AbBest &b, int strand_mask, double fw, double rv, double max_raw, int32_t at) {
+    if ((strand_mask & 1) && fw > b.raw) {
+        b.raw = fw;
+        const double q = fw / max_raw;
+        if (q > b.q) { b.q = q; b.at = at; b.strand = 1; }
+    }
+    if ((strand_mask & 2) && rv > b.raw) {
+        b.raw = rv;
+        const double q = rv / max_raw;
+        if (q > b.q) { b.q = q; b.at = at; b.strand = 2; }
+    }
+}
+
+__device__ __forceinline__ void ab_put(const AbOut &O, int hap, int64_t cell, double q, int32_t offset, int32_t strand) {
+    O.score[hap][cell] = strand ? q : __builtin_nan("");
+    O.offset[hap][cell] = strand ? offset : 0;
+    O.strand[hap][cell] = (int8_t) strand;
+}
+
+// grid = (tiles of the chunk, motifs); a thread per variant of the tile.  LDS_TAB: the motif's table in LDS (W <= kAbTabMaxW) or read
+// from HBM; a block of the other kind leaves at once.
+template <bool LDS_TAB>
+__global__ void __launch_bounds__(kAbThreads) ab_cell_kernel(const AbArgs A, int64_t v0, int64_t nv) {
+    extern __shared__ double2 abtab_lds[];                     // [W * 4 + 1]: the motif's entries, and an all-zero one for the columns that add nothing
+    const int32_t m = (int32_t) blockIdx.y;
+    const int W = A.Pw.width[m];
+    if ((W <= kAbTabMaxW) != LDS_TAB) return;
+    const int64_t vl = (int64_t) blockIdx.x * kAbTile + threadIdx.x;
+    const int64_t v = v0 + vl, cell = (int64_t) m * A.V + v;
+    if (!A.scorable[m]) {                                      // (block-uniform) no cell of this motif has a winner
+        if (vl < nv) {
+            ab_put(A.O, 0, cell, 0.0, 0, 0);
+            ab_put(A.O, 1, cell, 0.0, 0, 0);
+        }
+        return;
+    }
+    const double2 *__restrict__ tab_g = A.Pw.tab2 + A.Pw.tab_off[m];
+    const uint32_t zero = (uint32_t) W * 4u;
+    if (LDS_TAB) {
+        for (int i = threadIdx.x; i < W * 4; i += kAbThreads) abtab_lds[i] = tab_g[i];
+        if (threadIdx.x == 0) abtab_lds[zero] = make_double2(0.0, 0.0);
+        __syncthreads();
+    }
+    if (vl >= nv) return;
+    const AlRec q = A.rec[v];
+    if (ab_is_long(q, W)) return;                              // ab_wave_kernel's
+    const double max_raw = A.Pw.max_raw[m];
+    const int base = q.lo < W - 1 ? q.lo : W - 1;              // bases in front of x that the first window starts at
+    if (ab_is_snv(q)) {
+        // windows s = x - k, k = base down to max(0, W - 1 - hi): the variant sits in column k
+        const int k_last = W - 1 - q.hi > 0 ? W - 1 - q.hi : 0;
+        const uint32_t a_code = (uint32_t) code_window(A.acodes, q.aoff) & 3u;
+        const bool a_n = n_window(A.amask, q.aoff) & 1u;
+        AbBest br = ab_none(), ba = ab_none();
+        const int64_t g0 = q.g - base;
+        // W <= 32 (block-uniform): all windows lie in the 64 bases from g0 on.  The second word pair is read only where the genome goes
+        // on: a window needs it only if it reaches base g0 + 32, which is then inside the chromosome
+        uint64_t c_lo = 0, c_hi = 0;
+        uint32_t n_lo = 0, n_hi = 0;
+        if (W <= 32) {
+            c_lo = code_window(A.codes, g0);
+            n_lo = n_window(A.nmask, g0);
+            if (g0 + 32 < A.n_bases) {
+                c_hi = code_window(A.codes, g0 + 32);
+                n_hi = n_window(A.nmask, g0 + 32);
+            }
+        }
+        for (int k = base; k >= k_last; k--) {
+            const int j = base - k;
+            double2 tk = make_double2(0.0, 0.0);               // what the alt allele adds at column k
+            if (!a_n) {
+                if constexpr (LDS_TAB) tk = abtab_lds[(uint32_t) k * 4u + a_code];
+                else tk = tab_g[(uint32_t) k * 4u + a_code];
+            }
+            double rf = 0.0, rr = 0.0, af = 0.0, ar = 0.0;
+            if (W <= 32) {
+                const uint64_t cw = j ? (c_lo >> (2 * j)) | (c_hi << (64 - 2 * j)) : c_lo;
+                const uint32_t nw = j ? (n_lo >> j) | (n_hi << (32 - j)) : n_lo;
+                ab_step<LDS_TAB, true>(abtab_lds, tab_g, zero, 0, W, cw, nw, k, tk, rf, rr, af, ar);
+            } else {
+                for (int c0 = 0; c0 < W; c0 += 32) {
+                    const int n = (W - c0) < 32 ? (W - c0) : 32;
+                    const uint64_t cw = code_window(A.codes, g0 + j + c0);
+                    const uint32_t nw = n_window(A.nmask, g0 + j + c0);
+                    ab_step<LDS_TAB, true>(abtab_lds, tab_g, zero, c0, n, cw, nw, k - c0, tk, rf, rr, af, ar);
+                }
+            }
+            ab_take(br, A.strand_mask, rf, rr, max_raw, -k);
+            ab_take(ba, A.strand_mask, af, ar, max_raw, -k);
+        }
+        ab_put(A.O, 0, cell, br.q, br.at, br.strand);
+        ab_put(A.O, 1, cell, ba.q, ba.at, ba.strand);
+        return;
+    }
+#pragma unroll 1
+    for (int hap = 0; hap < 2; hap++) {
+        const int n_win = (int) allele_windows(q.lo, q.hi, hap ? q.a : q.r, W);
+        AbBest b = ab_none();
+#pragma unroll 1
+        for (int i = 0; i < n_win; i++) {
+            double fw, rv;
+            ab_window<LDS_TAB>(A, abtab_lds, tab_g, zero, W, q, hap, i - base, fw, rv);
+            ab_take(b, A.strand_mask, fw, rv, max_raw, i - base);
+        }
+        ab_put(A.O, hap, cell, b.q, b.at, b.strand);
+    }
+}
+
+// grid = (ceil(2 x candidates of the chunk / kAbWaves), motifs): wave (2 c + hap) of the launch owns haplotype hap of candidate c
+template <bool LDS_TAB>
+__global__ void __launch_bounds__(kAbThreads) ab_wave_kernel(const AbArgs A, const int64_t *__restrict__ cand, int64_t n_cand) {
+    extern __shared__ double2 abtab_lds[];
+    const int32_t m = (int32_t) blockIdx.y;
+    const int W = A.Pw.width[m];
+    if ((W <= kAbTabMaxW) != LDS_TAB) return;
+    if (!A.scorable[m]) return;                                // (ab_cell_kernel has filled the motif's row)
+    const int wave = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+    const int lane = (int) (threadIdx.x & 63u);
+    const int64_t item = (int64_t) blockIdx.x * kAbWaves + wave, ci = item >> 1;
+    const int hap = (int) (item & 1);
+    AlRec q = {};
+    int64_t v = 0;
+    bool is_long = false;
+    if (ci < n_cand) {
+        v = cand[ci];
+        q = A.rec[v];
+        is_long = ab_is_long(q, W);
+    }
+    if (!__syncthreads_or(is_long ? 1 : 0)) return;            // no long cell of this motif in the block: nothing to stage
+    const double2 *__restrict__ tab_g = A.Pw.tab2 + A.Pw.tab_off[m];
+    const uint32_t zero = (uint32_t) W * 4u;
+    if (LDS_TAB) {
+        for (int i = threadIdx.x; i < W * 4; i += kAbThreads) abtab_lds[i] = tab_g[i];
+        if (threadIdx.x == 0) abtab_lds[zero] = make_double2(0.0, 0.0);
+        __syncthreads();
+    }
+    if (!is_long) return;
+    const double max_raw = A.Pw.max_raw[m];
+    const int base = q.lo < W - 1 ? q.lo : W - 1;
+    const int n_win = (int) allele_windows(q.lo, q.hi, hap ? q.a : q.r, W);
+    AbBest b = ab_none();
+#pragma unroll 1
+    for (int i = lane; i < n_win; i += 64) {                   // ascending per lane: the divide argument holds lane by lane
+        double fw, rv;
+        ab_window<LDS_TAB>(A, abtab_lds, tab_g, zero, W, q, hap, i - base, fw, rv);
+        ab_take(b, A.strand_mask, fw, rv, max_raw, i);
+    }
+    double bq = b.q;
+    uint64_t key = b.strand ? (((uint64_t) (uint32_t) b.at << 2) | (uint32_t) b.strand) : kNoKey;
+    wave_best(bq, key);
+    if (lane == 0) {
+        const bool won = key != kNoKey;
+        ab_put(A.O, hap, (int64_t) m * A.V + v, bq, won ? (int32_t) (key >> 2) - base : 0, won ? (int32_t) (key & 3u) : 0);
+    }
+}
+
+size_t ab_up256(size_t x) { return (x + 255) & ~(size_t) 255; }
+
+}  // namespace
+
+}  // namespace ms
+
+using namespace ms;
+
+extern "C" {
+
+int ms_debug_allelebest_dims(int32_t out[3]) {
+    if (!out) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    out[0] = kAbTile;
+    out[1] = kAbLongWindows;
+    out[2] = kAbTabMaxW;
+    return MS_OK;
+}
+
+void ms_allelebest_free(ms_allelebest *b) {
+    if (!b) return;
+    if (b->block) {
+        (void) hipSetDevice(b->device);
+        DeviceCtx *c = nullptr;
+        if (get_ctx(b->device, &c) == MS_OK) pool_free(c, b->block, b->block_bytes); else (void) hipFree(b->block);
+    }
+    delete b;
+}
+
+int ms_scan_alleles_best(const ms_pwmset *pwms_c, const ms_genome *genome, const int32_t *chrom, const int64_t *pos, const int32_t *ref_len,
+                         const char *alt_bases, const int64_t *alt_offsets, const char *ref_bases, int64_t n_variants, int strand_mask,
+                         uint32_t flags, ms_allelebest **out) {
+    if (!out) { set_error("out is NULL"); return MS_ERR_INVALID; }
+    *out = nullptr;
+    if (strand_mask < 1 || strand_mask > 3) { set_error("invalid strand mask %d (1 '+', 2 '-', 3 both)", strand_mask); return MS_ERR_INVALID; }
+    if (flags != 0u) { set_error("unknown allele best-site scan flags 0x%x", flags); return MS_ERR_INVALID; }
+    {
+        int n_dev = 0;                                         // (a genome handle cannot exist without a device: say so before asking for one)
+        if (ms_device_count(&n_dev) != MS_OK || n_dev <= 0) { set_error("no usable HIP device; libmotifscan_amd has no CPU fallback"); return MS_ERR_RUNTIME; }
+    }
+    if (!pwms_c || !genome) { set_error("NULL handle"); return MS_ERR_INVALID; }
+    if (n_variants < 0 || (n_variants > 0 && (!chrom || !pos || !ref_len || !alt_offsets))) { set_error("bad variant arrays"); return MS_ERR_INVALID; }
+    ms_pwmset *pwms = const_cast<ms_pwmset *>(pwms_c);
+    const ms_seqset *G = reinterpret_cast<const ms_seqset *>(genome);
+    const int64_t V = n_variants, n_chroms = G->R;
+    const int32_t P = pwms->P;
+    const int64_t *goff = G->offsets.data();
+    if (V > 0 && alt_offsets[0] != 0) { set_error("alt_offsets[0] must be 0"); return MS_ERR_INVALID; }
+    std::vector<int64_t> ref_off, cand;
+    try { ref_off.assign((size_t) V + 1, 0); } catch (const std::bad_alloc &) { set_error("out of host memory"); return MS_ERR_NOMEM; }
+    for (int64_t v = 0; v < V; v++) {
+        if (chrom[v] < 0 || chrom[v] >= n_chroms) { set_error("variant %lld: chromosome index %d out of range", (long long) v, chrom[v]); return MS_ERR_INVALID; }
+        const int64_t len = goff[chrom[v] + 1] - goff[chrom[v]], x = pos[v], r = ref_len[v], a = alt_offsets[v + 1] - alt_offsets[v];
+        if (a < 0) { set_error("variant %lld: alt_offsets must not decrease", (long long) v); return MS_ERR_INVALID; }
+        if (x < 0 || x > len || r < 0 || x + r > len) {
+            set_error("variant %lld: reference bases [%lld, %lld) are outside chromosome %d of length %lld", (long long) v, (long long) x, (long long) (x + r),
+                      chrom[v], (long long) len);
+            return MS_ERR_INVALID;
+        }
+        if (r + a == 0) { set_error("variant %lld: both alleles are empty", (long long) v); return MS_ERR_INVALID; }
+        if (r > MS_ALLELE_MAX_LEN || a > MS_ALLELE_MAX_LEN) {
+            set_error("variant %lld: an allele of %lld bases is longer than MS_ALLELE_MAX_LEN (%d)", (long long) v, (long long) std::max(r, a), MS_ALLELE_MAX_LEN);
+            return MS_ERR_INVALID;
+        }
+        ref_off[(size_t) v + 1] = ref_off[(size_t) v] + r;
+    }
+    const int64_t A = V > 0 ? alt_offsets[V] : 0, Rn = ref_bases ? ref_off[(size_t) V] : 0;
+    if (A > 0 && !alt_bases) { set_error("alt_bases is NULL"); return MS_ERR_INVALID; }
+    // the variants that can be long cells of SOME motif: no substitution, and r + a + 2 (W_max - 1) windows at most
+    std::vector<uint8_t> ok;
+    try {
+        const int64_t slack = 2 * (int64_t) std::max(pwms->max_width - 1, 0);
+        for (int64_t v = 0; v < V; v++) {
+            const int64_t r = ref_len[v], a = alt_offsets[v + 1] - alt_offsets[v];
+            if (!(r == 1 && a == 1) && r + a + slack > kAbLongWindows) cand.push_back(v);
+        }
+        ok.assign((size_t) std::max<int32_t>(P, 1), 0);
+        for (int32_t m = 0; m < P; m++) ok[(size_t) m] = scorable(pwms, m) ? 1 : 0;
+    } catch (const std::bad_alloc &) { set_error("out of host memory"); return MS_ERR_NOMEM; }
+    DeviceCtx *c;
+    int rc = get_ctx(G->device, &c);
+    if (rc) return rc;
+    std::unique_ptr<ms_allelebest> res(new (std::nothrow) ms_allelebest());
+    if (!res) { set_error("out of host memory"); return MS_ERR_NOMEM; }
+    try { res->mismatch.assign((size_t) V, 0); } catch (const std::bad_alloc &) { set_error("out of host memory"); return MS_ERR_NOMEM; }
+    res->device = c->device;
+    res->P = P;
+    res->V = V;
+    // ---- 26 bytes per cell, allocated before anything is launched: a failure there is the MS_ERR_NOMEM of the header (the test here only
+    // keeps the byte counts below inside size_t)
+    if (26.0 * (double) P * (double) V >= 0.5 * (double) std::numeric_limits<size_t>::max()) {
+        set_error("%d x %lld cells do not fit the device", P, (long long) V);
+        return MS_ERR_NOMEM;
+    }
+    const size_t cells = (size_t) P * (size_t) V, cz = std::max<size_t>(cells, 1);
+    std::lock_guard<std::mutex> lk_dev(c->mu);
+    std::lock_guard<std::mutex> lk_pwm(pwms->mu);
+    MS_HIP(hipSetDevice(c->device));
+    {
+        void *blk = nullptr;
+        size_t got = 0;
+        if ((rc = pool_alloc(c, 2 * (ab_up256(8 * cz) + ab_up256(4 * cz) + ab_up256(cz)), &blk, &got))) return rc;
+        res->block = blk;
+        res->block_bytes = got;
+        char *p = static_cast<char *>(blk);
+        for (int h = 0; h < 2; h++) { res->d_score[h] = reinterpret_cast<double *>(p); p += ab_up256(8 * cz); }
+        for (int h = 0; h < 2; h++) { res->d_offset[h] = reinterpret_cast<int32_t *>(p); p += ab_up256(4 * cz); }
+        for (int h = 0; h < 2; h++) { res->d_strand[h] = reinterpret_cast<int8_t *>(p); p += ab_up256(cz); }
+    }
+    ms_allelebest *raw = res.release();
+    if (V == 0) { *out = raw; return MS_OK; }
+    if ((rc = pwmset_upload(pwms, c->device, c->stream))) { ms_allelebest_free(raw); return rc; }
+    const hipStream_t st = c->stream;
+
+    int64_t chunk = varscan_chunk_setting();
+    if (chunk <= 0) chunk = kAbChunk;
+    chunk = std::min<int64_t>(chunk, V);
+    const int64_t n_chunks = (V + chunk - 1) / chunk;
+
+    const size_t Vz = (size_t) V, Pz = (size_t) std::max<int32_t>(P, 1);
+    const size_t a_words = (size_t) ((A + 31) / 32);            // mask words of the alt plane; twice as many code words
+    const size_t b_chrom = ab_up256(4 * Vz), b_pos = ab_up256(8 * Vz), b_rlen = ab_up256(4 * Vz), b_aoff = ab_up256(8 * (Vz + 1)),
+                 b_roff = ab_up256(8 * (Vz + 1)), b_alt = ab_up256((size_t) std::max<int64_t>(A, 1)), b_ref = ab_up256((size_t) std::max<int64_t>(Rn, 1)),
+                 b_acode = ab_up256(4 * (2 * a_words + kAlPlanePad)), b_amask = ab_up256(4 * (a_words + kAlPlanePad)), b_rec = ab_up256(sizeof(AlRec) * Vz),
+                 b_mis = ab_up256(Vz), b_ok = ab_up256(Pz), b_cand = ab_up256(8 * std::max<size_t>(cand.size(), 1));
+    void *wblk = nullptr;
+    size_t wgot = 0;
+    if ((rc = pool_alloc(c, b_chrom + b_pos + b_rlen + b_aoff + b_roff + b_alt + b_ref + b_acode + b_amask + b_rec + b_mis + b_ok + b_cand, &wblk, &wgot))) {
+        ms_allelebest_free(raw);
+        return rc;
+    }
+    char *b = static_cast<char *>(wblk);
+    int32_t *d_chrom = reinterpret_cast<int32_t *>(b); b += b_chrom;
+    int64_t *d_pos = reinterpret_cast<int64_t *>(b); b += b_pos;
+    int32_t *d_rlen = reinterpret_cast<int32_t *>(b); b += b_rlen;
+    int64_t *d_aoff = reinterpret_cast<int64_t *>(b); b += b_aoff;
+    int64_t *d_roff = reinterpret_cast<int64_t *>(b); b += b_roff;
+    uint8_t *d_alt = reinterpret_cast<uint8_t *>(b); b += b_alt;
+    uint8_t *d_ref = reinterpret_cast<uint8_t *>(b); b += b_ref;
+    uint32_t *d_acode = reinterpret_cast<uint32_t *>(b); b += b_acode;
+    uint32_t *d_amask = reinterpret_cast<uint32_t *>(b); b += b_amask;
+    AlRec *d_rec = reinterpret_cast<AlRec *>(b); b += b_rec;
+    uint8_t *d_mis = reinterpret_cast<uint8_t *>(b); b += b_mis;
+    uint8_t *d_ok = reinterpret_cast<uint8_t *>(b); b += b_ok;
+    int64_t *d_cand = reinterpret_cast<int64_t *>(b);
+    auto fail = [&](int code) { pool_free(c, wblk, wgot); ms_allelebest_free(raw); return code; };
+    auto hip_fail = [&](hipError_t e, const char *what) { set_error("%s failed: %s", what, hipGetErrorString(e)); return fail(e == hipErrorOutOfMemory ? MS_ERR_NOMEM : MS_ERR_RUNTIME); };
+
+    AbArgs K;
+    K.codes = G->d_codes; K.nmask = G->d_nmask; K.acodes = d_acode; K.amask = d_amask; K.n_bases = G->n_bases;
+    K.Pw = dev_pwm(pwms); K.scorable = d_ok; K.rec = d_rec; K.V = V; K.strand_mask = strand_mask;
+    for (int h = 0; h < 2; h++) { K.O.score[h] = raw->d_score[h]; K.O.offset[h] = raw->d_offset[h]; K.O.strand[h] = raw->d_strand[h]; }
+    const int max_width = pwms->max_width;
+    const int min_width = P > 0 ? *std::min_element(pwms->widths.begin(), pwms->widths.end()) : 0;
+    int lds_width = 0;
+    for (int32_t p = 0; p < P; p++) if (pwms->widths[p] <= kAbTabMaxW) lds_width = std::max(lds_width, (int) pwms->widths[p]);
+    const size_t lds = ((size_t) lds_width * 4 + 1) * sizeof(double2);
+    hipError_t he = hipSuccess;
+    if (lds > 40 * 1024) {                                     // (wide motifs: rare enough to ask the driver every time; ab_wave_kernel has static LDS too)
+        he = hipFuncSetAttribute(reinterpret_cast<const void *>(ab_cell_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+        if (he == hipSuccess) he = hipFuncSetAttribute(reinterpret_cast<const void *>(ab_wave_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+        if (he != hipSuccess) return hip_fail(he, "raising the LDS limit");
+    }
+
+    (void) hipEventRecord(c->ev[0], st);
+    he = hipMemcpyAsync(d_chrom, chrom, 4 * (size_t) V, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess) he = hipMemcpyAsync(d_pos, pos, 8 * (size_t) V, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess) he = hipMemcpyAsync(d_rlen, ref_len, 4 * (size_t) V, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess) he = hipMemcpyAsync(d_aoff, alt_offsets, 8 * ((size_t) V + 1), hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && ref_bases) he = hipMemcpyAsync(d_roff, ref_off.data(), 8 * ((size_t) V + 1), hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && A > 0) he = hipMemcpyAsync(d_alt, alt_bases, (size_t) A, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && Rn > 0) he = hipMemcpyAsync(d_ref, ref_bases, (size_t) Rn, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && P > 0) he = hipMemcpyAsync(d_ok, ok.data(), (size_t) P, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && !cand.empty()) he = hipMemcpyAsync(d_cand, cand.data(), 8 * cand.size(), hipMemcpyHostToDevice, st);
+    if (he == hipSuccess) he = hipMemsetAsync(d_acode, 0, b_acode + b_amask, st);       // (the two planes lie side by side: their padding too)
+    if (he == hipSuccess && A > 0) {
+        hipLaunchKernelGGL(al_pack_kernel, dim3((unsigned) ((a_words + 255) / 256)), dim3(256), 0, st, d_alt, A, d_acode, d_amask);
+        he = hipGetLastError();
+    }
+    if (he == hipSuccess) {
+        hipLaunchKernelGGL(al_prep_kernel, dim3((unsigned) ((V + 255) / 256)), dim3(256), 0, st, G->d_codes, G->d_nmask, G->d_offsets, d_chrom, d_pos,
+                           d_rlen, d_aoff, ref_bases ? d_ref : (const uint8_t *) nullptr, d_roff, V, d_rec, d_mis);
+        he = hipGetLastError();
+    }
+    if (he == hipSuccess) he = hipMemcpyAsync(raw->mismatch.data(), d_mis, (size_t) V, hipMemcpyDeviceToHost, st);
+    if (he != hipSuccess) return hip_fail(he, "variant upload");
+
+    for (int64_t k = 0; P > 0 && k < n_chunks; k++) {
+        const int64_t v0 = k * chunk, nv = std::min(chunk, V - v0);
+        const dim3 grid((unsigned) ((nv + kAbTile - 1) / kAbTile), (unsigned) P);
+        if (min_width <= kAbTabMaxW) {
+            hipLaunchKernelGGL(ab_cell_kernel<true>, grid, dim3(kAbThreads), lds, st, K, v0, nv);
+            if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "allele best-site kernel");
+        }
+        if (max_width > kAbTabMaxW) {
+            hipLaunchKernelGGL(ab_cell_kernel<false>, grid, dim3(kAbThreads), 0, st, K, v0, nv);
+            if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "allele best-site kernel (tables in HBM)");
+        }
+        // the chunk's candidates for the wave path: cand is ascending
+        const int64_t c0 = std::lower_bound(cand.begin(), cand.end(), v0) - cand.begin();
+        const int64_t c1 = std::lower_bound(cand.begin(), cand.end(), v0 + nv) - cand.begin();
+        if (c1 > c0) {
+            const dim3 wgrid((unsigned) ((2 * (c1 - c0) + kAbWaves - 1) / kAbWaves), (unsigned) P);
+            if (min_width <= kAbTabMaxW) {
+                hipLaunchKernelGGL(ab_wave_kernel<true>, wgrid, dim3(kAbThreads), lds, st, K, d_cand + c0, c1 - c0);
+                if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "allele best-site wave kernel");
+            }
+            if (max_width > kAbTabMaxW) {
+                hipLaunchKernelGGL(ab_wave_kernel<false>, wgrid, dim3(kAbThreads), 0, st, K, d_cand + c0, c1 - c0);
+                if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "allele best-site wave kernel (tables in HBM)");
+            }
+        }
+    }
+    (void) hipEventRecord(c->ev[1], st);
+    he = hipStreamSynchronize(st);
+    if (he != hipSuccess) return hip_fail(he, "allele best-site scan");
+    float ms01 = 0;
+    (void) hipEventElapsedTime(&ms01, c->ev[0], c->ev[1]);
+    raw->device_ms = ms01;
+    pool_free(c, wblk, wgot);
+    *out = raw;
+    return MS_OK;
+}
+
+int ms_allelebest_shape(const ms_allelebest *b, int32_t *n_pwms, int64_t *n_variants) {
+    if (!b) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    if (n_pwms) *n_pwms = b->P;
+    if (n_variants) *n_variants = b->V;
+    return MS_OK;
+}
+
+int ms_allelebest_sites(const ms_allelebest *b, int32_t m0, int32_t m1, double *score_ref, int32_t *offset_ref, int8_t *strand_ref,
+                        double *score_alt, int32_t *offset_alt, int8_t *strand_alt) {
+    if (!b) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    if (m0 < 0 || m1 > b->P || m0 > m1) { set_error("motif range [%d, %d) outside [0, %d)", m0, m1, b->P); return MS_ERR_INVALID; }
+    const size_t at = (size_t) m0 * (size_t) b->V, n = (size_t) (m1 - m0) * (size_t) b->V;
+    if (n == 0) return MS_OK;
+    MS_HIP(hipSetDevice(b->device));
+    double *score[2] = {score_ref, score_alt};
+    int32_t *offset[2] = {offset_ref, offset_alt};
+    int8_t *strand[2] = {strand_ref, strand_alt};
+    for (int h = 0; h < 2; h++) {
+        if (score[h]) MS_HIP(hipMemcpy(score[h], b->d_score[h] + at, 8 * n, hipMemcpyDeviceToHost));
+        if (offset[h]) MS_HIP(hipMemcpy(offset[h], b->d_offset[h] + at, 4 * n, hipMemcpyDeviceToHost));
+        if (strand[h]) MS_HIP(hipMemcpy(strand[h], b->d_strand[h] + at, n, hipMemcpyDeviceToHost));
+    }
+    return MS_OK;
+}
+
+int ms_allelebest_sites_device(const ms_allelebest *b, void **d_score_ref, void **d_offset_ref, void **d_strand_ref, void **d_score_alt,
+                               void **d_offset_alt, void **d_strand_alt) {
+    if (!b) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    if (d_score_ref) *d_score_ref = b->d_score[0];
+    if (d_offset_ref) *d_offset_ref = b->d_offset[0];
+    if (d_strand_ref) *d_strand_ref = b->d_strand[0];
+    if (d_score_alt) *d_score_alt = b->d_score[1];
+    if (d_offset_alt) *d_offset_alt = b->d_offset[1];
+    if (d_strand_alt) *d_strand_alt = b->d_strand[1];
+    return MS_OK;
+}
+
+int ms_allelebest_ref_mismatch(const ms_allelebest *b, uint8_t *out) {
+    if (!b || (!out && b->V > 0)) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    std::copy(b->mismatch.begin(), b->mismatch.end(), out);
+    return MS_OK;
+}
+
+int ms_allelebest_device_ms(const ms_allelebest *b, double *ms) {
+    if (!b || !ms) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    *ms = b->device_ms;
+    return MS_OK;
+}
+
+}  // extern "C"

@@ -27,6 +27,7 @@
 #include <limits>
 #include <memory>
 
+#include "ms_best_dev.h"
 #include "ms_device.h"
 #include "ms_handles.h"
 
@@ -64,18 +65,6 @@ struct BestArgs {
     int8_t *strand;
     BestPart *part;                                      // [P][n_part]
 };
-
-constexpr uint64_t kNoKey = ~0ULL;
-
-// (q, key) of the wave's lanes -> the winner in every lane: the greater q, equal q to the smaller key = pos << 2 | strand
-__device__ __forceinline__ void wave_best(double &q, uint64_t &key) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const double oq = __shfl_xor(q, d);
-        const unsigned long long ok = __shfl_xor((unsigned long long) key, d);
-        if (oq > q || (oq == q && ok < key)) { q = oq; key = ok; }
-    }
-}
 
 __device__ __forceinline__ void put_best(double *__restrict__ score, int32_t *__restrict__ pos, int8_t *__restrict__ strand, int64_t cell, double q, uint64_t key) {
     const bool won = key != kNoKey;
@@ -224,17 +213,6 @@ __global__ void __launch_bounds__(256) best_fill_kernel(const int32_t *__restric
 }
 
 size_t up256(size_t x) { return (x + 255) & ~(size_t) 255; }
-
-// the reference never reports a site of such a motif: max_raw is not a finite number > 0, or an entry is NaN or +inf
-bool scorable(const ms_pwmset *p, int32_t m) {
-    const double mr = p->max_raw[(size_t) m];
-    if (!(std::isfinite(mr) && mr > 0.0)) return false;
-    const double *v = p->values.data() + p->val_off[(size_t) m];
-    const int64_t n = 4 * (int64_t) p->widths[(size_t) m];
-    for (int64_t i = 0; i < n; i++)
-        if (std::isnan(v[i]) || v[i] == std::numeric_limits<double>::infinity()) return false;
-    return true;
-}
 
 }  // namespace
 

@@ -1,7 +1,7 @@
 // ms_handles.h -- private to libmotifscan_amd: per-device state and the structs behind the opaque handles of
 // include/motifscan_amd.h, shared by the library's translation units: ms_context.hip (device contexts, pools), ms_pwmset.hip, ms_seqset.hip,
 // ms_result.hip (one per handle), ms_scan.hip (scan pipeline), ms_sweep.hip (window sweep), ms_regions.hip and ms_stream.hip (batch streams,
-// host-streamed sweeps), ms_best.hip (best window per cell), ms_pairs.hip (motif pairs over a result's hits).
+// host-streamed sweeps), ms_best.hip (best window per cell), ms_allelebest.hip (best window per variant haplotype), ms_pairs.hip (motif pairs over a result's hits).
 #pragma once
 #include <sched.h>
 #include <atomic>
@@ -336,7 +336,7 @@ MS_HIDDEN DevPwm dev_pwm(const ms_pwmset *p);
 MS_HIDDEN DevSeq dev_seq(const ms_seqset *s);
 // sum_r max(L_r - W + 1, 0) from the set's sorted lengths (ms_seqset.hip)
 MS_HIDDEN int64_t windows_for_width(const ms_seqset *s, int W);
-// what ms_debug_varscan_chunk set: variants per chunk of the variant scans, 0 = their own size (ms_variants.hip; read by ms_alleles.hip)
+// what ms_debug_varscan_chunk set: variants per chunk of the variant scans, 0 = their own size (ms_variants.hip; read by ms_alleles.hip and ms_allelebest.hip)
 MS_HIDDEN int64_t varscan_chunk_setting();
 // the path constants of the kernels around the scan, for ms_debug_genome_dims (ms_background.hip): the pack / extract block in bases
 // (ms_seqset.hip), kNearThreads / kGeneTile / kOverlapThreads (ms_annotation.hip), the element budget of a score-rank batch (ms_pwmset.hip)

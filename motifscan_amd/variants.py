@@ -9,6 +9,9 @@ arrays -- they are the interface; no writer is part of this module.
 Alleles whose REF and ALT differ in length, or are longer than one base, take the second route: `read_vcf_alleles`, `scan_alleles` and
 `AlleleSites` (ms_alleles.hip).  There the two haplotypes are scanned apiece -- the chromosome as it is, and the chromosome with the
 allele spliced in -- and a record belongs to ONE haplotype, with a start in that haplotype's coordinates.
+
+`best_alleles` and `AlleleEffects` are the dense form (ms_allelebest.hip): no cutoff, one best window per (motif, variant, haplotype) --
+what ranking variants by motif disruption needs for every pair, also where neither allele passes a cutoff.
 """
 import gzip
 from collections import namedtuple
@@ -337,3 +340,98 @@ def scan_alleles(genome, pwms, chrom, pos, ref, alt, strand="both", p_value="1e-
         s = {k: (v[keep] if k != "motif_offsets" else offsets) for k, v in s.items()}
     return AlleleSites(s["motif"], s["variant"], s["allele"], s["start"], s["strand"], s["score"], s["motif_offsets"], pos=pos, ref_len=ref_len,
                        alt_len=alt_len, counts=(gained, lost), skipped=bad)
+
+
+# ---------------------------------------------------------------------------------------------- the best site per (motif, variant, haplotype)
+
+class AlleleEffects:
+    """The dense result of `best_alleles`: per (motif, variant) the best-scoring affected window of the ref and of the alt haplotype.
+    score_ref / score_alt (float64), offset_ref / offset_alt (int32: winning start - pos, in that haplotype's coordinates) and
+    strand_ref / strand_alt (int8: 1 '+', 2 '-') are (P, V) arrays; a cell without a winner holds NaN / 0 / 0 (strand == 0 marks it).
+    pos / ref_len / alt_len are the caller's variants; `skipped` = indices of the variants blanked for a REF mismatch
+    (on_mismatch='skip')."""
+
+    def __init__(self, score_ref, score_alt, offset_ref, offset_alt, strand_ref, strand_alt, pos, ref_len, alt_len, skipped=None):
+        self.score_ref = np.asarray(score_ref, dtype=np.float64)
+        self.score_alt = np.asarray(score_alt, dtype=np.float64)
+        self.offset_ref = np.asarray(offset_ref, dtype=np.int32)
+        self.offset_alt = np.asarray(offset_alt, dtype=np.int32)
+        self.strand_ref = np.asarray(strand_ref, dtype=np.int8)
+        self.strand_alt = np.asarray(strand_alt, dtype=np.int8)
+        self.pos = np.asarray(pos, dtype=np.int64)
+        self.ref_len = np.asarray(ref_len, dtype=np.int64)
+        self.alt_len = np.asarray(alt_len, dtype=np.int64)
+        self.skipped = np.zeros(0, dtype=np.int64) if skipped is None else np.asarray(skipped, dtype=np.int64)
+
+    @property
+    def shape(self):
+        return self.score_ref.shape
+
+    @property
+    def delta(self):
+        """score_alt - score_ref, NaN where either haplotype has no winner."""
+        return self.score_alt - self.score_ref
+
+    def start_ref(self):
+        """The winning start on the ref haplotype (reference coordinates), -1 where there is no winner."""
+        return np.where(self.strand_ref != 0, self.pos[None, :] + self.offset_ref, -1)
+
+    def start_alt(self):
+        """The winning start on the alt haplotype, in ALT-haplotype coordinates, -1 where there is no winner."""
+        return np.where(self.strand_alt != 0, self.pos[None, :] + self.offset_alt, -1)
+
+    def start_alt_in_ref(self):
+        """start_alt() in reference coordinates, by `AlleleSites.ref_start`'s rule: a start in front of the allele is one already; one at
+        or behind the allele's end x + a maps to start - a + r; one INSIDE the alt bases maps to x + min(start - x, r); -1: no winner."""
+        x, r, a = self.pos[None, :], self.ref_len[None, :], self.alt_len[None, :]
+        start = x + self.offset_alt
+        out = np.where(start >= x + a, start - a + r, np.where(start > x, x + np.minimum(start - x, r), start))
+        return np.where(self.strand_alt != 0, out, -1)
+
+
+def best_alleles(genome, pwms, chrom, pos, ref, alt, strand="both", on_mismatch="raise", motif_batch=None):
+    """The best-scoring affected window of every (motif, variant) on the ref and on the alt haplotype (ms_scan_alleles_best): the
+    cutoff-free, dense counterpart of `scan_alleles`.  Returns an AlleleEffects.
+
+    genome, chrom, pos, ref, alt and on_mismatch as in `scan_alleles` ('skip' sets the variant's columns to the no-winner triple and
+    lists it in `.skipped`); pwms: objects with .matrix (4 x W) -- no cutoffs are needed.  motif_batch: motifs copied from the device
+    per step (None: all at once)."""
+    if on_mismatch not in ("raise", "skip"):
+        raise ValueError("on_mismatch must be 'raise' or 'skip'")
+    if strand not in _STRAND_FLAG:
+        raise ValueError("strand must be one of 'both', '+', '-'")
+    if motif_batch is not None and int(motif_batch) < 1:
+        raise ValueError("motif_batch must be at least 1")
+    matrices = [np.asarray(pwm.matrix, dtype=np.float64) for pwm in pwms]
+    ref, alt = [str(r) for r in ref], [str(a) for a in alt]
+    pos = np.ascontiguousarray(pos, dtype=np.int64)
+    if not (len(chrom) == len(pos) == len(ref) == len(alt)):
+        raise ValueError("chrom, pos, ref and alt must have one entry per variant")
+    chrom_idx = np.array([genome.index[c] for c in chrom], dtype=np.int32)
+    ref_len = np.array([len(r) for r in ref], dtype=np.int32)
+    alt_len = np.array([len(a) for a in alt], dtype=np.int64)
+    P, V = len(matrices), len(pos)
+    pw = _lib.PwmSet.from_matrices(matrices)
+    try:
+        res = _lib.scan_alleles_best(pw, genome, chrom_idx, pos, ref_len, alt, refs=ref, strand_mask=_STRAND_FLAG[strand])
+    finally:
+        pw.close()
+    try:
+        bad = np.flatnonzero(res.ref_mismatch())
+        if bad.size and on_mismatch == "raise":
+            shown = ", ".join(f"{chrom[i]}:{int(pos[i]) + 1} REF {ref[i]}" for i in bad[:5].tolist())
+            raise ValueError(f"{bad.size} variant(s) whose REF is not the genome's sequence: {shown}" + (" ..." if bad.size > 5 else ""))
+        out = {k: np.zeros((P, V), dtype=t) for k, t in (("score_ref", np.float64), ("score_alt", np.float64), ("offset_ref", np.int32),
+                                                          ("offset_alt", np.int32), ("strand_ref", np.int8), ("strand_alt", np.int8))}
+        step = P if motif_batch is None else int(motif_batch)
+        for m0 in range(0, P, max(step, 1)):
+            part = res.sites(m0, min(P, m0 + step))
+            for k in out:
+                out[k][m0:m0 + step] = part[k]
+    finally:
+        res.close()
+    if bad.size:
+        for k in out:
+            out[k][:, bad] = np.nan if k.startswith("score") else 0
+    return AlleleEffects(out["score_ref"], out["score_alt"], out["offset_ref"], out["offset_alt"], out["strand_ref"], out["strand_alt"],
+                         pos, ref_len, alt_len, skipped=bad)
