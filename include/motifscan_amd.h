@@ -82,6 +82,9 @@
  *                         device from the hit arrays a result holds (has-site bit rows, a tiled popcount product)
  *   ms_result_pair_spacing    no reference counterpart: for one anchor motif against every partner motif, the histogram of the
  *                         centre-to-centre distances of their sites in the same region by relative orientation (SpaMo-style spacing)
+ *   ms_scan_score_histogram   c_score at EVERY window of a sequence set, counted per score bin: the exhaustive form of what
+ *                         get_score_cutoffs samples (motif_score_thread, cscore.c:174-229; the sort and the rank reads of
+ *                         motif/__init__.py:378-401) -- the score distribution behind exact cutoffs and empirical P-values
  */
 #ifndef MOTIFSCAN_AMD_H
 #define MOTIFSCAN_AMD_H
@@ -594,6 +597,37 @@ int ms_result_cooccurrence(const ms_result *res, int32_t m0, int32_t m1, int64_t
  * > 2^20, (m1 - m0) * 4 * (2 * max_dist + 1) > 2^31, sites out of order. */
 int ms_result_pair_spacing(const ms_result *res, const ms_pwmset *pwms, int32_t anchor, int32_t m0, int32_t m1, int32_t max_dist,
                            int64_t *counts /* [(m1 - m0)][4][2 * max_dist + 1] */, int64_t *n_pairs /* [m1 - m0] */);
+
+/* ---- the score distribution of every window (ms_scorehist.hip) ------------------------------------------------ */
+#define MS_SCOREHIST_MAX_BINS   4096
+#define MS_HIST_PER_POSITION    1u   /* one count per window start: (fwd > rev ? fwd : rev) / max_raw, i.e. c_score (cscore.c:207-223) at every
+                                        position; with a one-strand mask it is that strand's score.  Without the flag: one count per
+                                        (window, strand of strand_mask), the scores ms_scan compares with the cutoff. */
+/* Counts, per motif, the scores of ALL windows of the sequence set in n_bins equal bins: what get_score_cutoffs (motif/__init__.py:378-401)
+ * estimates from 10^6 sampled windows scored by c_score (cscore.c:174-229), done exhaustively.  The windows are ms_scan_best's: motif m of
+ * width W, region of length L, starts 0 .. L - W, each scored exactly as ms_scan scores it (columns in order, forward M[b][c], reverse
+ * M[3 - b][W - 1 - c] at the same step, a non-ACGT base adds +0.0, raw / max_raw as one IEEE fp64 divide).  The set's cutoffs are not read.
+ *
+ * The bin rule, with d = score - lo[m] as one rounded subtraction and t = d * inv_width[m] as one rounded multiply: t < 0 goes to
+ * out[m][0] ("below"; a score of -inf too), t >= n_bins to out[m][n_bins + 1] ("above"), anything else to out[m][1 + (int) floor(t)].
+ * A motif that is unscorable -- max_raw is not a finite number > 0, or an entry is NaN or +inf: the reference never reports a site of it --
+ * gets an all-zero row; for every other motif no score is NaN and every counted window lands in exactly one slot, so a row sums to the
+ * number of counted windows (x the strands of the mask without MS_HIST_PER_POSITION).
+ *
+ * max_n >= 0: a window with more than max_n non-ACGT bases among its own W bases is not counted at all; max_n < 0: every window counts.
+ * This counts bits of the packed "non-ACGT" plane, so IUPAC letters count as well as N / n.  It is NOT the reference's filter
+ * (motif/__init__.py:378-401 draws windows of the widest motif's width and rejects on N / n only, for all motifs alike).
+ *
+ * out: [P x (n_bins + 2)] int64, host memory or device memory of the sequence set's device (then a consumer can all-reduce it where it
+ * is).  The library writes a device `out` on its own stream: work the caller has queued on that memory on another stream (a fill, a
+ * collective) must have finished before the call; the call returns after its own writes are done.  An exact integer reduction: the same
+ * bytes on every run, additive over shards of the regions.  device_ms (may be NULL): first launch -> last kernel done.
+ * n_seqs = 0 or P = 0 is valid and gives zeros.  Without a device: MS_ERR_RUNTIME (no CPU fallback), before anything else is looked at.
+ * MS_ERR_INVALID: NULL handles or arrays, a strand mask outside 1..3, unknown flags, n_bins outside [1, MS_SCOREHIST_MAX_BINS], a lo that
+ * is not finite, an inv_width that is not finite and > 0, an output on another device. */
+int ms_scan_score_histogram(const ms_pwmset *pwms, const ms_seqset *seqs, int strand_mask, uint32_t flags,
+                            const double *lo /* [P] */, const double *inv_width /* [P] */, int32_t n_bins, int32_t max_n,
+                            int64_t *out /* [P][n_bins + 2] */, double *device_ms /* or NULL */);
 
 #ifdef __cplusplus
 }

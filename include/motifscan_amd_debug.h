@@ -117,6 +117,12 @@ int ms_debug_seqset_planes(const ms_seqset *seqs, uint32_t *codes, uint32_t *nma
  * before.  The result does not depend on it: a test proves that with batches of one and of three motifs.  Needs no GPU. */
 int ms_debug_score_rank_budget(int64_t elems, int64_t *previous);
 
+/* The sizes at which ms_scan_score_histogram changes path, as constants of the build: out[0] the window starts per segment (a region of
+ * more takes several); out[1] the widest motif whose table is staged in an LDS tile (wider ones read it from HBM); out[2] the LDS counter
+ * slots per block (MS_SCOREHIST_MAX_BINS + 2); out[3] the window starts a block counts between two flushes of its LDS counters (a region
+ * of more is counted by several blocks, or in several flushes).  Tests size their boundary cases from here.  Needs no GPU. */
+int ms_debug_scorehist_dims(int32_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ MS_OK, MS_ERR_INVALID, MS_ERR_NOMEM, MS_ERR_RUNTIME = 0, 1, 2, 3
 MS_SCAN_DEFAULT, MS_SCAN_EXACT_ONLY, MS_SCAN_COUNTS_ONLY = 0, 1, 2
 MS_STREAM_DEDUP, MS_STREAM_NO_HITS, MS_STREAM_EXACT_ONLY, MS_STREAM_PACKED, MS_STREAM_HOST_PACK, MS_STREAM_PACKED12 = 1, 2, 4, 8, 16, 32
 MS_PROFILE_UNSMOOTHED = 1
+MS_SCOREHIST_MAX_BINS, MS_HIST_PER_POSITION = 4096, 1
 MS_REPLAY_DONE, MS_REPLAY_WORDS, MS_REPLAY_ATTEMPTS, MS_REPLAY_NO_SIZE, MS_REPLAY_EMPTY_RANGE, MS_REPLAY_WIDE = 0, 1, 2, 3, 4, 5
 MS_REPLAY_SIZE_MISSING = -(1 << 63)
 
@@ -208,6 +209,8 @@ def lib():
         "ms_best_free": (None, [vp]),
         "ms_debug_best_segment_windows": (c_int, []),
         "ms_debug_key_layout": (c_int, [c_i64, c_i64, c_i64, c_i32, c_i32, pi32, pi32]),
+        "ms_scan_score_histogram": (c_int, [vp, vp, c_int, c_u32, pd, pd, c_i32, c_i32, vp, pd]),
+        "ms_debug_scorehist_dims": (c_int, [pi32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1161,6 +1164,50 @@ def scan_best(pwms, seqs, strand_mask=3, flags=0):
     h = ctypes.c_void_p()
     check(lib().ms_scan_best(pwms.h, seqs.h, strand_mask, int(flags), ctypes.byref(h)))
     return BestSites(h)
+
+
+def histogram_binning(n_pwms, lo, hi, n_bins):
+    """(lo [P], inv_width [P]) of a score histogram: scalars broadcast, inv_width = n_bins / (hi - lo) as one float64 division each.
+    Pure numpy."""
+    lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=np.float64), (n_pwms,)))
+    hi = np.broadcast_to(np.asarray(hi, dtype=np.float64), (n_pwms,))
+    with np.errstate(all="ignore"):
+        inv_width = np.ascontiguousarray(np.float64(n_bins) / (hi - lo))
+    return lo, inv_width
+
+
+def score_histogram(pwms, seqs, strand_mask, lo, hi, n_bins, per_position=False, max_n=-1, out=None, timing=None):
+    """ms_scan_score_histogram: int64 [P][n_bins + 2], per motif the number of windows of the sequence set per score bin -- slot 0
+    "below lo", slots 1 .. n_bins the bins of [lo, hi), slot n_bins + 1 "at or above hi" (the exact rule: include/motifscan_amd.h;
+    motifscan_amd.scoredist restates it).  lo, hi: per motif, scalars broadcast.  per_position: one count per window start (c_score's
+    max over the strands) instead of one per (window, strand).  max_n >= 0: windows with more non-ACGT bases are not counted.  out: an
+    int64 numpy array of that shape, or None (a new one); the device pointer of a torch tensor may be passed as an int instead (then it
+    is returned).  timing: a dict that receives 'device_ms'.  The library checks every argument."""
+    n_bins = int(n_bins)
+    lo, inv_width = histogram_binning(pwms.n, lo, hi, n_bins)
+    shape = (pwms.n, n_bins + 2)
+    if isinstance(out, int):
+        dst = out
+    else:
+        if out is None:
+            out = np.zeros(shape, dtype=np.int64)
+        if out.dtype != np.int64 or out.shape != shape or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous int64 array of shape (P, n_bins + 2)")
+        dst = out.ctypes.data
+    ms = ctypes.c_double()
+    check(lib().ms_scan_score_histogram(pwms.h, seqs.h, int(strand_mask), MS_HIST_PER_POSITION if per_position else 0, ptr(lo, ctypes.c_double),
+                                        ptr(inv_width, ctypes.c_double), n_bins, int(max_n), ctypes.c_void_p(dst), ctypes.byref(ms)))
+    if timing is not None:
+        timing["device_ms"] = ms.value
+    return out
+
+
+def scorehist_dims():
+    """ms_debug_scorehist_dims: dict(segment_windows, tile_max_width, lds_slots, flush_windows) -- the sizes at which
+    ms_scan_score_histogram changes path.  Constants of the build; no device."""
+    out = np.zeros(4, dtype=np.int32)
+    check(lib().ms_debug_scorehist_dims(ptr(out, ctypes.c_int32)))
+    return dict(zip(("segment_windows", "tile_max_width", "lds_slots", "flush_windows"), out.tolist()))
 
 
 def best_segment_windows():

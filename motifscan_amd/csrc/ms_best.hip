@@ -73,21 +73,6 @@ __device__ __forceinline__ void put_best(double *__restrict__ score, int32_t *__
     strand[cell] = won ? (int8_t) (key & 3u) : (int8_t) 0;
 }
 
-// up to 32 columns out of the registers: table entries tb + 4 c of the LDS tile, in column order; bit c of skip: the column adds entry 0
-__device__ __forceinline__ void best_cols32(const double2 *__restrict__ lds, uint32_t tb, int n, uint64_t cw, uint32_t skip, double &fwd, double &rev) {
-    for (int c1 = 0; c1 < n; c1 += 8) {
-        const uint32_t bits = (uint32_t) (cw >> (2 * c1)), sk = skip >> c1;
-        double2 t[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const uint32_t idx = tb + (uint32_t) (c1 + k) * 4u + ((bits >> (2 * k)) & 3u);
-            t[k] = lds[((sk >> k) & 1u) ? 0u : idx];
-        }
-#pragma unroll
-        for (int k = 0; k < 8; k++) { fwd += t[k].x; rev += t[k].y; }
-    }
-}
-
 // grid = (ceil(segments / kBestWaves), tiles).  LDS: the tile's tables in LDS; !LDS: one motif per tile, its table in HBM.
 template <bool LDS>
 __global__ void __launch_bounds__(kBestThreads, 4) best_kernel(const BestArgs A, int32_t tile0) {

@@ -1,5 +1,6 @@
 // ms_best_dev.h -- what the "best window of a cell" kernels share (ms_best.hip: per region; ms_allelebest.hip: per variant haplotype):
-// the total-order wave reduction and the test for a motif the reference never reports a site of.
+// the total-order wave reduction and the test for a motif the reference never reports a site of; and, with ms_scorehist.hip (the score
+// histogram walks the windows as ms_best.hip does), the column loop over an LDS tile of tables.
 #pragma once
 #include <cmath>
 #include <limits>
@@ -20,6 +21,21 @@ __device__ __forceinline__ void wave_best(double &q, uint64_t &key) {
         const double oq = __shfl_xor(q, d);
         const unsigned long long ok = __shfl_xor((unsigned long long) key, d);
         if (oq > q || (oq == q && ok < key)) { q = oq; key = ok; }
+    }
+}
+
+// (the dense walks over an LDS tile of tables: best_kernel, scorehist_kernel) up to 32 columns out of the registers: table entries tb + 4 c of the LDS tile, in column order; bit c of skip: the column adds entry 0
+__device__ __forceinline__ void best_cols32(const double2 *__restrict__ lds, uint32_t tb, int n, uint64_t cw, uint32_t skip, double &fwd, double &rev) {
+    for (int c1 = 0; c1 < n; c1 += 8) {
+        const uint32_t bits = (uint32_t) (cw >> (2 * c1)), sk = skip >> c1;
+        double2 t[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const uint32_t idx = tb + (uint32_t) (c1 + k) * 4u + ((bits >> (2 * k)) & 3u);
+            t[k] = lds[((sk >> k) & 1u) ? 0u : idx];
+        }
+#pragma unroll
+        for (int k = 0; k < 8; k++) { fwd += t[k].x; rev += t[k].y; }
     }
 }
 

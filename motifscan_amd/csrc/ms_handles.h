@@ -1,7 +1,7 @@
 // ms_handles.h -- private to libmotifscan_amd: per-device state and the structs behind the opaque handles of
 // include/motifscan_amd.h, shared by the library's translation units: ms_context.hip (device contexts, pools), ms_pwmset.hip, ms_seqset.hip,
 // ms_result.hip (one per handle), ms_scan.hip (scan pipeline), ms_sweep.hip (window sweep), ms_regions.hip and ms_stream.hip (batch streams,
-// host-streamed sweeps), ms_best.hip (best window per cell), ms_allelebest.hip (best window per variant haplotype), ms_pairs.hip (motif pairs over a result's hits).
+// host-streamed sweeps), ms_best.hip (best window per cell), ms_allelebest.hip (best window per variant haplotype), ms_pairs.hip (motif pairs over a result's hits), ms_scorehist.hip (score histogram of every window).
 #pragma once
 #include <sched.h>
 #include <atomic>

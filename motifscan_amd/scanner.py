@@ -13,8 +13,9 @@ Same public surface and behaviour:
     deduplicate_motif_sites(motif_sites, lengths)        scanner.py:171-193
 plus, for inputs where n_pwms x n_regions Python lists are not an option:
     Scanner.scan_motifs_arrays(pwms) -> flat numpy arrays in the same order.
-and one question the reference cannot answer from its site lists:
+and two questions the reference cannot answer from its site lists:
     Scanner.best_sites(pwms) -> BestSiteArrays: the best-scoring window of every (motif, region), cutoff or not.
+    Scanner.score_histogram(pwms, ...) -> scoredist.ScoreHistogram: the score distribution of all windows, per motif.
 
 `genome` is any object with `chrom_sizes[chrom]` and `fetch_sequence(chrom, start, end)`;
 `regions` any objects with `.chrom .start .end .summit` -- i.e. the reference's own
@@ -340,6 +341,24 @@ class Scanner:
         finally:
             pw.close()
         return BestSiteArrays(score, best_site_starts(pos, self.seq_starts), strand)
+
+    def score_histogram(self, pwms, lo=0.0, hi=None, n_bins=1024, per_position=False):
+        """The score distribution of ALL windows of the scanner's regions, per motif, as a scoredist.ScoreHistogram: n_bins equal bins over
+        [lo, hi) plus a "below" and an "above" slot, every window scored as scan_motifs scores it and counted on the device
+        (ms_scan_score_histogram).  One count per (window, strand of the scanner's `strand`), or with per_position one per window start
+        (the greater strand: c_score's score of a position).  hi=None: the least double above 1.0, scaled so that a score of exactly
+        1.0 falls in the last bin (scoredist.default_hi).  `p_value` and `remove_dup` have no meaning here; no window is dropped for its
+        N bases.  From the histogram: ScoreHistogram.tail (sites at any cutoff), .p_value (empirical P-value of a site), .cutoffs."""
+        from . import scoredist
+        if hi is None:
+            hi = scoredist.default_hi(lo, n_bins)
+        matrices = [np.asarray(pwm.matrix, dtype=np.float64) for pwm in pwms]
+        pw = _lib.PwmSet.from_matrices(matrices)
+        try:
+            counts = _lib.score_histogram(pw, self._seqset(), _STRAND_FLAG[self.strand], lo, hi, n_bins, per_position)
+        finally:
+            pw.close()
+        return scoredist.ScoreHistogram.from_range(counts, lo, hi, n_bins)
 
     def scan_motifs(self, pwms):
         """motif_sites[n_pwms][n_regions] -> list[MotifSite] (scanner.py:89-132), as a read-only nested view over the
