@@ -75,6 +75,9 @@
  *   ms_scan_alleles_best / ms_allelebest_*
  *                         no reference counterpart: the maximum of cscore.c:336-390 over the windows an allele touches, per haplotype --
  *                         the best-scoring window of every (motif, variant, haplotype) cell, the dense form of ms_scan_alleles
+ *   ms_genome_apply_alleles / ms_liftmap_*
+ *                         no reference counterpart: a whole variant set spliced into a NEW resident genome (a personal haplotype) that
+ *                         every region-based entry point takes as it is, and the coordinate map between the two genomes
  *   ms_scan_best / ms_best_*
  *                         no reference counterpart: the maximum of cscore.c:336-390 over a region -- the best-scoring window of every
  *                         (motif, region) cell, the dense score matrix behind "max motif score per peak"
@@ -418,6 +421,49 @@ int  ms_allelebest_ref_mismatch(const ms_allelebest *b, uint8_t *out /* [V] */);
 /* Device time of the call that made the result: upload of the variants -> last kernel done. */
 int  ms_allelebest_device_ms(const ms_allelebest *b, double *ms);
 void ms_allelebest_free(ms_allelebest *b);
+
+/* ---- a personal haplotype: a variant set applied to a resident genome, and the map between the two (ms_personal.hip) ---------- */
+/* The variant arguments, their validation, the alt-byte conversion, the REF check and the MS_ERR_INVALID cases are ms_scan_alleles's, word
+ * for word (x in [0, L], r + a > 0, MS_ALLELE_MAX_LEN, the REF rule); flags other than MS_APPLY_SKIP_MISMATCH are MS_ERR_INVALID.  Without
+ * a device: MS_ERR_RUNTIME ("no CPU fallback") before anything else.  MS_ERR_NOMEM when the new planes do not fit the device (the splice is
+ * not launched then).
+ * WHICH VARIANTS ARE APPLIED.  With MS_APPLY_SKIP_MISMATCH and ref_bases a variant whose REF differs from the genome gets status 2 and
+ * takes no further part (without the flag it is applied like any other; ms_liftmap_ref_mismatch names it either way).  The rest are ordered by
+ * (chromosome, x, index in the caller's arrays).  Variant v is skipped for overlap (status 0) iff some variant u of its chromosome EARLIER
+ * in that order has x_u + r_u > x_v -- whether u is itself applied or not: the running maximum of the ends in front of v exceeds x_v.  Every
+ * other variant is applied (status 1).  So: a duplicate of a substitution is skipped; an insertion (r = 0) at x does not block a later
+ * variant at x; several insertions at one point are all applied, in input-index order; and, the rule being a max-scan (parallel) and NOT
+ * the sequential greedy rule of consensus tools, a variant that overlaps a skipped one is skipped too.  The input order does not matter
+ * beyond the index tie-break.
+ * THE OUTPUT GENOME has the same number of chromosomes; chromosome c is the reference chromosome with [x, x + r) of every applied variant
+ * replaced by its alt bases, of length L'_c = L_c + sum(a - r) (0 is allowed).  It is a complete ms_genome, independent of the input genome
+ * and of the map: its planes are exactly what ms_pack_bases_host makes of the spliced ASCII (a non-ACGT alt byte is a mask bit with code
+ * 0, bits past the last base are zero), with the region hints and host tables of any other genome, the same bytes on every run.
+ * n_variants = 0 gives a copy.  Positions and length sums are 64-bit throughout.
+ * THE LIFT MAP.  Per chromosome, with its applied variants in order (x_i, r_i, a_i) and x'_i = x_i + sum_{j < i} (a_j - r_j):
+ *   MS_LIFT_REF_TO_ALT, p in [0, L_c]:  x_i <= p < x_i + r_i for some i -> x'_i + min(p - x_i, a_i), inside = 1; otherwise
+ *       p + sum(a_j - r_j) over the applied j with x_j + r_j <= p, inside = 0 (a reference base at an insertion point lies BEHIND the
+ *       inserted bases);
+ *   MS_LIFT_ALT_TO_REF, q in [0, L'_c]: x'_i <= q < x'_i + a_i -> x_i + min(q - x'_i, r_i), inside = 1 (AlleleSites.ref_start's convention);
+ *       otherwise q - sum(a_j - r_j) over the applied j with x'_j + a_j <= q.
+ * Both are non-decreasing and map the chromosome's end to the chromosome's end.  A chromosome index or a position outside those ranges is
+ * MS_ERR_INVALID.  Host arrays in and out; the queries run on the device.  The map owns its device arrays and outlives both genomes. */
+#define MS_APPLY_SKIP_MISMATCH 1u
+#define MS_LIFT_REF_TO_ALT 0
+#define MS_LIFT_ALT_TO_REF 1
+typedef struct ms_liftmap ms_liftmap;
+int  ms_genome_apply_alleles(const ms_genome *genome, const int32_t *chrom, const int64_t *pos, const int32_t *ref_len,
+                             const char *alt_bases, const int64_t *alt_offsets /* [V+1] */, const char *ref_bases /* or NULL */,
+                             int64_t n_variants, uint32_t flags, ms_genome **out, ms_liftmap **map /* may be NULL */);
+int  ms_liftmap_shape(const ms_liftmap *m, int32_t *n_chroms, int64_t *n_variants, int64_t *n_applied);
+int  ms_liftmap_status(const ms_liftmap *m, uint8_t *status /* [V] */);          /* 1 applied, 0 skipped: overlap, 2 skipped: REF mismatch */
+int  ms_liftmap_ref_mismatch(const ms_liftmap *m, uint8_t *out /* [V] */);
+int  ms_liftmap_chrom_sizes(const ms_liftmap *m, int64_t *ref_len /* [C] */, int64_t *alt_len /* [C] */);
+int  ms_liftmap_lift(const ms_liftmap *m, int direction, const int32_t *chrom, const int64_t *pos, int64_t n,
+                     int64_t *out_pos, uint8_t *inside /* may be NULL */);
+/* Device time of the call that made the map: first launch -> last kernel done (the host's sizing of the output in between included). */
+int  ms_liftmap_device_ms(const ms_liftmap *m, double *ms);
+void ms_liftmap_free(ms_liftmap *m);
 
 /* ---- the best-scoring window of every (motif, region) cell: the dense motif x region matrix (ms_best.hip) ---------- */
 /* For motif m of width W and region r of length L, over the window starts pos = 0 .. L - W and the strands of strand_mask: score(pos, strand)

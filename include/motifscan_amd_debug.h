@@ -123,6 +123,15 @@ int ms_debug_score_rank_budget(int64_t elems, int64_t *previous);
  * of more is counted by several blocks, or in several flushes).  Tests size their boundary cases from here.  Needs no GPU. */
 int ms_debug_scorehist_dims(int32_t out[4]);
 
+/* The path constants of ms_genome_apply_alleles and ms_liftmap_lift, as constants of the build: out[0] the output bases of one block of the
+ * splice kernel; out[1] the applied variants (= alt pieces, each followed by a genome piece) a block stages in LDS -- a block whose bases
+ * touch more searches them in global memory; out[2] the queries per block of the lift kernel; out[3] reserved, 0.  Tests size their boundary
+ * cases from here.  Needs no GPU. */
+int ms_debug_personal_dims(int32_t out[4]);
+/* The stage times of the ms_genome_apply_alleles call that made the map, in ms: out[0] upload, alt packing and prep; out[1] order, status and
+ * layout up to the copy of the new offsets; out[2] the host's part (the output genome's tables and block); out[3] the splice and the region hints. */
+int ms_debug_liftmap_stage_ms(const ms_liftmap *m, double out[4]);
+
 #ifdef __cplusplus
 }
 #endif

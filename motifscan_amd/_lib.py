@@ -211,6 +211,16 @@ def lib():
         "ms_debug_key_layout": (c_int, [c_i64, c_i64, c_i64, c_i32, c_i32, pi32, pi32]),
         "ms_scan_score_histogram": (c_int, [vp, vp, c_int, c_u32, pd, pd, c_i32, c_i32, vp, pd]),
         "ms_debug_scorehist_dims": (c_int, [pi32]),
+        "ms_genome_apply_alleles": (c_int, [vp, pi32, pi64, pi32, ctypes.c_char_p, pi64, ctypes.c_char_p, c_i64, c_u32, pvp, pvp]),
+        "ms_liftmap_shape": (c_int, [vp, pi32, pi64, pi64]),
+        "ms_liftmap_status": (c_int, [vp, pu8]),
+        "ms_liftmap_ref_mismatch": (c_int, [vp, pu8]),
+        "ms_liftmap_chrom_sizes": (c_int, [vp, pi64, pi64]),
+        "ms_liftmap_lift": (c_int, [vp, c_int, pi32, pi64, c_i64, pi64, pu8]),
+        "ms_liftmap_device_ms": (c_int, [vp, pd]),
+        "ms_liftmap_free": (None, [vp]),
+        "ms_debug_personal_dims": (c_int, [pi32]),
+        "ms_debug_liftmap_stage_ms": (c_int, [vp, pd]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -490,6 +500,9 @@ class ResidentGenome:
         if self._host is not None:
             return self._host[chrom][start:end].decode()
         if getattr(self, "_packed", None) is not None:
+            return self._packed.fetch_sequence(chrom, start, end)
+        if getattr(self, "_device_made", False):         # made on the device (apply_alleles): the planes are copied back once, ms_genome_packed_host
+            self._packed = self.packed()
             return self._packed.fetch_sequence(chrom, start, end)
         raise RuntimeError("ResidentGenome was created without keep_host: sequences live on the device only")
 
@@ -1392,6 +1405,106 @@ def allelebest_dims():
     out = np.zeros(3, dtype=np.int32)
     check(lib().ms_debug_allelebest_dims(ptr(out, ctypes.c_int32)))
     return dict(zip(("tile", "long_windows", "lds_max_width"), out.tolist()))
+
+
+MS_APPLY_SKIP_MISMATCH, MS_LIFT_REF_TO_ALT, MS_LIFT_ALT_TO_REF = 1, 0, 1
+
+
+class LiftMap:
+    """The coordinate map of one ms_genome_apply_alleles call (include/motifscan_amd.h): `status` (uint8 per input variant: 1 applied,
+    0 skipped for overlap, 2 skipped for a REF mismatch), `ref_mismatch`, the chromosome lengths of both genomes, and the two lifts --
+    to_alt(chrom_idx, pos) / to_ref(chrom_idx, pos) return (positions int64, inside uint8).  It outlives both genomes."""
+
+    def __init__(self, handle):
+        self.h = handle
+        c, v, n = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int64()
+        check(lib().ms_liftmap_shape(self.h, ctypes.byref(c), ctypes.byref(v), ctypes.byref(n)))
+        self.n_chroms, self.n_variants, self.n_applied = c.value, v.value, n.value
+        self.status, self.ref_mismatch = np.zeros(v.value, dtype=np.uint8), np.zeros(v.value, dtype=np.uint8)
+        check(lib().ms_liftmap_status(self.h, ptr(self.status, ctypes.c_uint8)))
+        check(lib().ms_liftmap_ref_mismatch(self.h, ptr(self.ref_mismatch, ctypes.c_uint8)))
+        self.ref_sizes, self.alt_sizes = np.zeros(c.value, dtype=np.int64), np.zeros(c.value, dtype=np.int64)
+        check(lib().ms_liftmap_chrom_sizes(self.h, ptr(self.ref_sizes, ctypes.c_int64), ptr(self.alt_sizes, ctypes.c_int64)))
+
+    def _lift(self, direction, chrom_idx, pos):
+        if not getattr(self, "h", None):
+            raise ValueError("the lift map is closed")
+        ps = np.ascontiguousarray(pos, dtype=np.int64)
+        ci = np.ascontiguousarray(np.broadcast_to(np.asarray(chrom_idx, dtype=np.int32), ps.shape))
+        if ps.ndim != 1:
+            raise ValueError("chrom_idx and pos must be one-dimensional, one entry per query")
+        out, inside = np.zeros(ps.size, dtype=np.int64), np.zeros(ps.size, dtype=np.uint8)
+        check(lib().ms_liftmap_lift(self.h, direction, ptr(ci, ctypes.c_int32), ptr(ps, ctypes.c_int64), ps.size, ptr(out, ctypes.c_int64),
+                                    ptr(inside, ctypes.c_uint8)))
+        return out, inside
+
+    def to_alt(self, chrom_idx, pos):
+        return self._lift(MS_LIFT_REF_TO_ALT, chrom_idx, pos)
+
+    def to_ref(self, chrom_idx, pos):
+        return self._lift(MS_LIFT_ALT_TO_REF, chrom_idx, pos)
+
+    def device_ms(self):
+        ms = ctypes.c_double()
+        check(lib().ms_liftmap_device_ms(self.h, ctypes.byref(ms)))
+        return ms.value
+
+    def stage_ms(self):
+        """ms_debug_liftmap_stage_ms: dict(prep, order, host, splice) of the call that made the map."""
+        out = np.zeros(4)
+        check(lib().ms_debug_liftmap_stage_ms(self.h, ptr(out, ctypes.c_double)))
+        return dict(zip(("prep", "order", "host", "splice"), out.tolist()))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ms_liftmap_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+
+def apply_alleles(genome, chrom_idx, pos, ref_len, alts, refs=None, skip_mismatch=False):
+    """ms_genome_apply_alleles: scan_alleles' variant arguments applied to a ResidentGenome TOGETHER.  Returns (ResidentGenome, LiftMap):
+    the personal haplotype as a new resident genome with the same chromosome names -- Scanner and every region-based entry point take it
+    as it is; its packed() and fetch_sequence are served by the planes copied back (N for every non-ACGT base) -- and the map between
+    the two coordinate systems.  The header has the overlap rule."""
+    ci = np.ascontiguousarray(chrom_idx, dtype=np.int32)
+    ps = np.ascontiguousarray(pos, dtype=np.int64)
+    rl = np.ascontiguousarray(ref_len, dtype=np.int32)
+    ab, ao = _flatten_alleles(alts)
+    if ci.ndim != 1 or not (ci.size == ps.size == rl.size == ao.size - 1):
+        raise ValueError("chrom_idx, pos, ref_len and alts must have one entry per variant")
+    rb = None
+    if refs is not None:
+        rb, ro = _flatten_alleles(refs)
+        if ro.size - 1 != ci.size or not np.array_equal(np.diff(ro), rl):
+            raise ValueError("refs must hold one string of ref_len bytes per variant")
+    h, hm = ctypes.c_void_p(), ctypes.c_void_p()
+    check(lib().ms_genome_apply_alleles(genome.h, ptr(ci, ctypes.c_int32), ptr(ps, ctypes.c_int64), ptr(rl, ctypes.c_int32),
+                                        ab.ctypes.data_as(ctypes.c_char_p), ptr(ao, ctypes.c_int64),
+                                        None if rb is None else rb.ctypes.data_as(ctypes.c_char_p), ci.size,
+                                        MS_APPLY_SKIP_MISMATCH if skip_mismatch else 0, ctypes.byref(h), ctypes.byref(hm)))
+    g = ResidentGenome.__new__(ResidentGenome)
+    g.h = h
+    g.names = list(genome.names)
+    g.index = dict(genome.index)
+    g._host = None
+    g._packed = None
+    g._device_made = True
+    lm = LiftMap(hm)
+    sizes = lm.alt_sizes
+    g.offsets = np.zeros(len(g.names) + 1, dtype=np.int64)
+    np.cumsum(sizes, out=g.offsets[1:])
+    g.chrom_sizes = {n: int(s) for n, s in zip(g.names, sizes)}
+    return g, lm
+
+
+def personal_dims():
+    """ms_debug_personal_dims: dict(block_bases, stage_variants, lift_block) -- the output bases of one splice block, the applied variants
+    a block stages in LDS, the queries per block of the lift kernel.  Constants of the build; no device."""
+    out = np.zeros(4, dtype=np.int32)
+    check(lib().ms_debug_personal_dims(ptr(out, ctypes.c_int32)))
+    return dict(zip(("block_bases", "stage_variants", "lift_block"), out.tolist()[:3]))
 
 
 class PinnedBuffer:

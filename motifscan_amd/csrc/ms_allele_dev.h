@@ -1,12 +1,48 @@
 // ms_allele_dev.h -- what the kernels over sequence-resolved alleles share (ms_alleles.hip: the records of the windows that pass;
-// ms_allelebest.hip: the best window per haplotype): a variant's prep record, the count of the windows an allele touches, the alt planes
-// and the spliced read of an alt-haplotype step.  ms_alleles.hip's header comment has the geometry.
+// ms_allelebest.hip: the best window per haplotype; ms_personal.hip: the whole variant set spliced into a new genome): the validation of
+// the variant arguments, a variant's prep record, the count of the windows an allele touches, the alt planes and the spliced read of an
+// alt-haplotype step.  ms_alleles.hip's header comment has the geometry.
 #pragma once
+#include <algorithm>
+
 #include "ms_device.h"
+#include "ms_handles.h"
 
 namespace ms {
 
 namespace {
+
+// The variant arguments of ms_scan_alleles, ms_scan_alleles_best and ms_genome_apply_alleles, validated in one place (the header's
+// MS_ERR_INVALID cases, in this order); on MS_OK ref_off [V + 1] holds the prefix of ref_len, *A the alt bytes and *Rn the REF bytes
+// (0 when ref_bases is NULL).
+inline int validate_alleles(const ms_seqset *G, const int32_t *chrom, const int64_t *pos, const int32_t *ref_len, const char *alt_bases,
+                            const int64_t *alt_offsets, const char *ref_bases, int64_t V, std::vector<int64_t> &ref_off, int64_t *A, int64_t *Rn) {
+    if (V < 0 || (V > 0 && (!chrom || !pos || !ref_len || !alt_offsets))) { set_error("bad variant arrays"); return MS_ERR_INVALID; }
+    const int64_t n_chroms = G->R;
+    const int64_t *goff = G->offsets.data();
+    if (V > 0 && alt_offsets[0] != 0) { set_error("alt_offsets[0] must be 0"); return MS_ERR_INVALID; }
+    try { ref_off.assign((size_t) V + 1, 0); } catch (const std::bad_alloc &) { set_error("out of host memory"); return MS_ERR_NOMEM; }
+    for (int64_t v = 0; v < V; v++) {
+        if (chrom[v] < 0 || chrom[v] >= n_chroms) { set_error("variant %lld: chromosome index %d out of range", (long long) v, chrom[v]); return MS_ERR_INVALID; }
+        const int64_t len = goff[chrom[v] + 1] - goff[chrom[v]], x = pos[v], r = ref_len[v], a = alt_offsets[v + 1] - alt_offsets[v];
+        if (a < 0) { set_error("variant %lld: alt_offsets must not decrease", (long long) v); return MS_ERR_INVALID; }
+        if (x < 0 || x > len || r < 0 || x + r > len) {
+            set_error("variant %lld: reference bases [%lld, %lld) are outside chromosome %d of length %lld", (long long) v, (long long) x, (long long) (x + r),
+                      chrom[v], (long long) len);
+            return MS_ERR_INVALID;
+        }
+        if (r + a == 0) { set_error("variant %lld: both alleles are empty", (long long) v); return MS_ERR_INVALID; }
+        if (r > MS_ALLELE_MAX_LEN || a > MS_ALLELE_MAX_LEN) {
+            set_error("variant %lld: an allele of %lld bases is longer than MS_ALLELE_MAX_LEN (%d)", (long long) v, (long long) std::max(r, a), MS_ALLELE_MAX_LEN);
+            return MS_ERR_INVALID;
+        }
+        ref_off[(size_t) v + 1] = ref_off[(size_t) v] + r;
+    }
+    *A = V > 0 ? alt_offsets[V] : 0;
+    *Rn = ref_bases ? ref_off[(size_t) V] : 0;
+    if (*A > 0 && !alt_bases) { set_error("alt_bases is NULL"); return MS_ERR_INVALID; }
+    return MS_OK;
+}
 
 constexpr int32_t kAlFar = 1 << 30;
 constexpr int kAlPlanePad = 4;                  // zero words behind either alt plane: code_window reads 3 words, n_window 2

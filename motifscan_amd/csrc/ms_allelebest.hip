@@ -360,33 +360,13 @@ int ms_scan_alleles_best(const ms_pwmset *pwms_c, const ms_genome *genome, const
         if (ms_device_count(&n_dev) != MS_OK || n_dev <= 0) { set_error("no usable HIP device; libmotifscan_amd has no CPU fallback"); return MS_ERR_RUNTIME; }
     }
     if (!pwms_c || !genome) { set_error("NULL handle"); return MS_ERR_INVALID; }
-    if (n_variants < 0 || (n_variants > 0 && (!chrom || !pos || !ref_len || !alt_offsets))) { set_error("bad variant arrays"); return MS_ERR_INVALID; }
     ms_pwmset *pwms = const_cast<ms_pwmset *>(pwms_c);
     const ms_seqset *G = reinterpret_cast<const ms_seqset *>(genome);
-    const int64_t V = n_variants, n_chroms = G->R;
+    const int64_t V = n_variants;
     const int32_t P = pwms->P;
-    const int64_t *goff = G->offsets.data();
-    if (V > 0 && alt_offsets[0] != 0) { set_error("alt_offsets[0] must be 0"); return MS_ERR_INVALID; }
     std::vector<int64_t> ref_off, cand;
-    try { ref_off.assign((size_t) V + 1, 0); } catch (const std::bad_alloc &) { set_error("out of host memory"); return MS_ERR_NOMEM; }
-    for (int64_t v = 0; v < V; v++) {
-        if (chrom[v] < 0 || chrom[v] >= n_chroms) { set_error("variant %lld: chromosome index %d out of range", (long long) v, chrom[v]); return MS_ERR_INVALID; }
-        const int64_t len = goff[chrom[v] + 1] - goff[chrom[v]], x = pos[v], r = ref_len[v], a = alt_offsets[v + 1] - alt_offsets[v];
-        if (a < 0) { set_error("variant %lld: alt_offsets must not decrease", (long long) v); return MS_ERR_INVALID; }
-        if (x < 0 || x > len || r < 0 || x + r > len) {
-            set_error("variant %lld: reference bases [%lld, %lld) are outside chromosome %d of length %lld", (long long) v, (long long) x, (long long) (x + r),
-                      chrom[v], (long long) len);
-            return MS_ERR_INVALID;
-        }
-        if (r + a == 0) { set_error("variant %lld: both alleles are empty", (long long) v); return MS_ERR_INVALID; }
-        if (r > MS_ALLELE_MAX_LEN || a > MS_ALLELE_MAX_LEN) {
-            set_error("variant %lld: an allele of %lld bases is longer than MS_ALLELE_MAX_LEN (%d)", (long long) v, (long long) std::max(r, a), MS_ALLELE_MAX_LEN);
-            return MS_ERR_INVALID;
-        }
-        ref_off[(size_t) v + 1] = ref_off[(size_t) v] + r;
-    }
-    const int64_t A = V > 0 ? alt_offsets[V] : 0, Rn = ref_bases ? ref_off[(size_t) V] : 0;
-    if (A > 0 && !alt_bases) { set_error("alt_bases is NULL"); return MS_ERR_INVALID; }
+    int64_t A = 0, Rn = 0;
+    if (int vrc = validate_alleles(G, chrom, pos, ref_len, alt_bases, alt_offsets, ref_bases, V, ref_off, &A, &Rn)) return vrc;
     // the variants that can be long cells of SOME motif: no substitution, and r + a + 2 (W_max - 1) windows at most
     std::vector<uint8_t> ok;
     try {

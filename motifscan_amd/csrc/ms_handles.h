@@ -1,7 +1,8 @@
 // ms_handles.h -- private to libmotifscan_amd: per-device state and the structs behind the opaque handles of
 // include/motifscan_amd.h, shared by the library's translation units: ms_context.hip (device contexts, pools), ms_pwmset.hip, ms_seqset.hip,
 // ms_result.hip (one per handle), ms_scan.hip (scan pipeline), ms_sweep.hip (window sweep), ms_regions.hip and ms_stream.hip (batch streams,
-// host-streamed sweeps), ms_best.hip (best window per cell), ms_allelebest.hip (best window per variant haplotype), ms_pairs.hip (motif pairs over a result's hits), ms_scorehist.hip (score histogram of every window).
+// host-streamed sweeps), ms_best.hip (best window per cell), ms_allelebest.hip (best window per variant haplotype), ms_pairs.hip (motif pairs over a result's hits), ms_scorehist.hip (score histogram of every window),
+// ms_personal.hip (a variant set spliced into a new resident genome, and the lift map between the two).
 #pragma once
 #include <sched.h>
 #include <atomic>
@@ -341,7 +342,9 @@ MS_HIDDEN int64_t varscan_chunk_setting();
 // the path constants of the kernels around the scan, for ms_debug_genome_dims (ms_background.hip): the pack / extract block in bases
 // (ms_seqset.hip), kNearThreads / kGeneTile / kOverlapThreads (ms_annotation.hip), the element budget of a score-rank batch (ms_pwmset.hip)
 MS_HIDDEN int32_t seqset_block_bases();
-MS_HIDDEN void annotation_dims(int32_t out[3]);
+// a set of these offsets on `device` with its planes and hints unwritten, and blk2reg_kernel for it on `st` (ms_seqset.hip; ms_personal.hip writes the planes)
+MS_HIDDEN int seqset_create_unpacked(const int64_t *offsets, int64_t n_seqs, int device, ms_seqset **out);
+MS_HIDDEN int seqset_launch_hints(const ms_seqset *s, hipStream_t st);MS_HIDDEN void annotation_dims(int32_t out[3]);
 MS_HIDDEN int64_t score_rank_budget_default();
 
 }  // namespace ms

@@ -244,4 +244,9 @@ int sort_doubles_desc(void *temp, size_t *temp_bytes, const double *in, double *
 // sites a sweep hands out: more than 2^32 of them per call are legal).
 int exclusive_sum_u32(void *temp, size_t *temp_bytes, const uint32_t *in, uint64_t *out, size_t n, hipStream_t stream);
 
+// The two scans of ms_genome_apply_alleles's layout (ms_personal.hip): the running maximum of the variants' ends in (chromosome, x) order
+// -- the overlap rule -- and the exclusive sum of the applied variants' length changes a - r.  Integer operators: the same in any order.
+int inclusive_max_u64(void *temp, size_t *temp_bytes, const uint64_t *in, uint64_t *out, size_t n, hipStream_t stream);
+int exclusive_sum_i64(void *temp, size_t *temp_bytes, const int64_t *in, int64_t *out, size_t n, hipStream_t stream);
+
 }  // namespace ms

@@ -408,6 +408,28 @@ int seqset_pack_pending(const ms_seqset *s_c, hipStream_t st) {
     return MS_OK;
 }
 
+// A set of the given offsets on `device` whose planes and region hints are still to be written by the caller's kernels (ms_personal.hip:
+// the splice writes the planes, seqset_launch_hints the hints): host tables, the device block, the offsets and the zero pad words, waited for.
+int seqset_create_unpacked(const int64_t *offsets, int64_t n_seqs, int device, ms_seqset **out) {
+    *out = nullptr;
+    const int prev_dev = current_device();
+    set_current_device(device);
+    std::unique_ptr<ms_seqset> s;
+    int rc = seqset_common(offsets, n_seqs, s);
+    set_current_device(prev_dev);
+    if (rc) return rc;
+    ms_seqset *raw = s.release();
+    auto fail = [&](int code) { ms_seqset_free(raw); return code; };
+    if ((rc = seqset_alloc_packed(raw))) return fail(rc);
+    const hipError_t e = hipStreamSynchronize(raw->up);
+    if (e != hipSuccess) { set_error("upload of the offsets failed: %s", hipGetErrorString(e)); return fail(MS_ERR_RUNTIME); }
+    raw->built = true;
+    *out = raw;
+    return MS_OK;
+}
+
+int seqset_launch_hints(const ms_seqset *s, hipStream_t st) { return launch_blk2reg(s->d_offsets, s->R, s->n_bases, s->d_blk2reg, s->d_blkinfo, st); }
+
 }  // namespace ms
 
 using namespace ms;

@@ -40,4 +40,14 @@ int exclusive_sum_u32(void *temp, size_t *temp_bytes, const uint32_t *in, uint64
     return MS_OK;
 }
 
+int inclusive_max_u64(void *temp, size_t *temp_bytes, const uint64_t *in, uint64_t *out, size_t n, hipStream_t stream) {
+    MS_HIP(rocprim::inclusive_scan(temp, *temp_bytes, in, out, n, rocprim::maximum<uint64_t>(), stream));
+    return MS_OK;
+}
+
+int exclusive_sum_i64(void *temp, size_t *temp_bytes, const int64_t *in, int64_t *out, size_t n, hipStream_t stream) {
+    MS_HIP(rocprim::exclusive_scan(temp, *temp_bytes, in, out, (int64_t) 0, n, rocprim::plus<int64_t>(), stream));
+    return MS_OK;
+}
+
 }  // namespace ms
