@@ -88,6 +88,9 @@
  *   ms_scan_score_histogram   c_score at EVERY window of a sequence set, counted per score bin: the exhaustive form of what
  *                         get_score_cutoffs samples (motif_score_thread, cscore.c:174-229; the sort and the rank reads of
  *                         motif/__init__.py:378-401) -- the score distribution behind exact cutoffs and empirical P-values
+ *   ms_result_site_base_counts   no reference counterpart: how often A, C, G and T stand under each motif column (and the flanks) over a
+ *                         result's sites, in the motif's orientation, with the adjacent-column dinucleotide counts -- the observed
+ *                         count matrix of the sites found, reduced on the device from the hit arrays and the packed sequence
  */
 #ifndef MOTIFSCAN_AMD_H
 #define MOTIFSCAN_AMD_H
@@ -643,6 +646,32 @@ int ms_result_cooccurrence(const ms_result *res, int32_t m0, int32_t m1, int64_t
  * > 2^20, (m1 - m0) * 4 * (2 * max_dist + 1) > 2^31, sites out of order. */
 int ms_result_pair_spacing(const ms_result *res, const ms_pwmset *pwms, int32_t anchor, int32_t m0, int32_t m1, int32_t max_dist,
                            int64_t *counts /* [(m1 - m0)][4][2 * max_dist + 1] */, int64_t *n_pairs /* [m1 - m0] */);
+
+/* ---- site stacks: base counts per motif column over a result's sites (ms_sitestack.hip) ------------------------- */
+#define MS_SITESTACK_MAX_FLANK 64
+/* For motifs m0 <= m < m1 (row = m - m0) of a result and the sequence set it was made over: what the motif's sites look like, column
+ * by column, in the MOTIF's orientation.  C = pwms->max_width + 2 * flank is the column pitch of every row.  Motif m of width W uses
+ * columns j = 0 .. W + 2 * flank - 1 (column flank + c is motif column c); the columns behind them stay zero.  For a site (region r of
+ * length L, pos, strand), column j reads region base q = pos - flank + j as it is on '+', and q = pos + W - 1 + flank - j complemented
+ * (code 3 - b) on '-': the columns follow the motif, exactly as the scan's reverse strand reads M[3 - b][W - 1 - c].
+ *   counts[row][j][s]: s = 0 .. 3 the sites with A, C, G, T there after orientation (either case); s = 4 a non-ACGT base (a bit of the
+ *       packed "non-ACGT" plane: IUPAC letters count as well as N); s = 5 q < 0 or q >= L, outside the region -- decided by the
+ *       region's bounds, never by what lies beside it in the packed planes.
+ *   dinuc[row][j][4 * a + b], j = 0 .. W + 2 * flank - 2 (may be NULL): the sites whose oriented base is a at column j and b at column
+ *       j + 1, counted only when both columns fall in slots 0 .. 3.
+ *   n_sites[row] (may be NULL): the motif's sites in the result; every used column of counts sums to it.
+ * The sites are read as they are (de-duplicated or not).  Synchronous; an exact integer reduction -- the same bytes on every run --
+ * and additive over shards of the regions.  An empty motif range (m0 == m1) does nothing and returns MS_OK.  Every output is host
+ * memory or device memory of the result's device (then a consumer can all-reduce it where it is).  The library writes a device output
+ * on its own stream: work the caller has queued on that memory on another stream (a fill, a collective) must have finished before the
+ * call; the call returns after its own writes are done.  *device_ms (may be NULL): first launch -> last kernel done.
+ * MS_ERR_RUNTIME without a usable device, before anything else.  MS_ERR_INVALID: NULL handles or a NULL counts, flags != 0, flank
+ * outside [0, MS_SITESTACK_MAX_FLANK], a motif range outside [0, P], pwms->P != the result's P, seqs->R != the result's R or seqs on
+ * another device, a counts-only result, an output on another device, and a site with a region index outside [0, R), pos < 0 or
+ * pos + W > L (a result of ms_result_from_hits, or the wrong sequence set: checked on the device while counting, outputs zeroed). */
+int ms_result_site_base_counts(const ms_result *res, const ms_pwmset *pwms, const ms_seqset *seqs, int32_t flank, int32_t m0, int32_t m1,
+                               uint32_t flags /* 0 */, int64_t *counts /* [(m1 - m0)][C][6] */, int64_t *dinuc /* [(m1 - m0)][C][16], or NULL */,
+                               int64_t *n_sites /* [m1 - m0], or NULL */, double *device_ms /* or NULL */);
 
 /* ---- the score distribution of every window (ms_scorehist.hip) ------------------------------------------------ */
 #define MS_SCOREHIST_MAX_BINS   4096

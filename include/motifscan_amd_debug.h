@@ -132,6 +132,12 @@ int ms_debug_personal_dims(int32_t out[4]);
  * layout up to the copy of the new offsets; out[2] the host's part (the output genome's tables and block); out[3] the splice and the region hints. */
 int ms_debug_liftmap_stage_ms(const ms_liftmap *m, double out[4]);
 
+/* The path constants of ms_result_site_base_counts, as constants of the build: out[0] the threads of a block; out[1] the hits of one
+ * block chunk (a motif of more hits takes several chunks, and beyond a fixed number of blocks several chunks per block); out[2] the
+ * largest column pitch C = max_width + 2 * flank counted in LDS -- above it the counts go to global memory directly; out[3] the same
+ * when dinuc is not asked for (equal to out[2]: one limit).  Tests size their boundary cases from here.  Needs no GPU. */
+int ms_debug_sitestack_dims(int32_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

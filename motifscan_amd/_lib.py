@@ -159,6 +159,8 @@ def lib():
         "ms_result_rank_profile": (c_int, [vp, pi64, pd, pd, c_i32, c_i32, c_int, vp]),
         "ms_result_cooccurrence": (c_int, [vp, c_i32, c_i32, vp]),
         "ms_result_pair_spacing": (c_int, [vp, vp, c_i32, c_i32, c_i32, c_i32, pi64, pi64]),
+        "ms_result_site_base_counts": (c_int, [vp, vp, vp, c_i32, c_i32, c_i32, c_u32, vp, vp, vp, pd]),
+        "ms_debug_sitestack_dims": (c_int, [pi32]),
         "ms_debug_pair_lds_bins": (c_int, []),
         "ms_debug_cooc_chunk_regions": (c_int, []),
         "ms_debug_plot_dims": (c_int, [pi32]),
@@ -858,6 +860,42 @@ class ScanResult:
         check(lib().ms_result_pair_spacing(self.h, pwms.h, anchor, m0, m1, max_dist, ptr(counts, ctypes.c_int64), ptr(n_pairs, ctypes.c_int64)))
         return counts, n_pairs[:rows]
 
+    def site_base_counts(self, pwmset, seqset, flank=0, m0=0, m1=None, dinuc=False, out=None, flags=0):
+        """ms_result_site_base_counts: (counts int64 [m1 - m0][C][6], dinuc int64 [m1 - m0][C][16] or None, n_sites int64 [m1 - m0]) of
+        the sites of motifs m0 .. m1 - 1 over the sequence set the result was made of, C = the set's widest motif + 2 * flank: per
+        column of the motif (column flank + c is motif column c) the sites with A, C, G, T there in the motif's orientation, with a
+        non-ACGT base (slot 4) and outside the region (slot 5); dinuc[.][j][4 * a + b] the sites with a at column j and b at j + 1.
+        out: None, or (counts, dinuc, n_sites), each an int64 numpy array of that shape or None (a new one; dinuc must be None unless
+        asked for); the device pointer of a torch tensor may be passed as an int instead (then it is returned).  The call's
+        device_ms is left in self.site_base_counts_ms.  The library checks every argument."""
+        m1 = self.n_pwms if m1 is None else int(m1)
+        m0, flank = int(m0), int(flank)
+        rows = max(m1 - m0, 0)
+        fits = 0 <= flank <= 64                                  # what the library refuses is refused before it writes
+        C = (int(pwmset.widths.max()) if pwmset.n else 0) + 2 * flank if fits else 1
+        shapes = ((rows, C, 6), (rows, C, 16), (rows,))
+        given = (None, None, None) if out is None else tuple(out)
+        if len(given) != 3 or (given[1] is not None and not dinuc):
+            raise ValueError("out must be (counts, dinuc, n_sites), dinuc None unless asked for")
+        arrs, dst = [], []
+        for a, shape, want in zip(given, shapes, (True, bool(dinuc), True)):
+            if not want:
+                a, p = None, None
+            elif isinstance(a, int):
+                p = a
+            else:
+                if a is None:
+                    a = np.zeros(shape, dtype=np.int64)
+                if a.dtype != np.int64 or a.shape != shape or not a.flags.c_contiguous:
+                    raise ValueError("out arrays must be C-contiguous int64 of shapes (m1 - m0, C, 6), (m1 - m0, C, 16) and (m1 - m0,)")
+                p = a.ctypes.data
+            arrs.append(a)
+            dst.append(ctypes.c_void_p(p))
+        ms = ctypes.c_double(0.0)
+        check(lib().ms_result_site_base_counts(self.h, pwmset.h, seqset.h, flank, m0, m1, int(flags), dst[0], dst[1], dst[2], ctypes.byref(ms)))
+        self.site_base_counts_ms = ms.value
+        return tuple(arrs)
+
     def close(self):
         if getattr(self, "h", None):
             lib().ms_result_free(self.h)
@@ -1231,6 +1269,14 @@ def best_segment_windows():
 def pair_lds_bins():
     """ms_debug_pair_lds_bins: the widest 2 * max_dist + 1 that ms_result_pair_spacing bins in LDS."""
     return int(lib().ms_debug_pair_lds_bins())
+
+
+def sitestack_dims():
+    """ms_debug_sitestack_dims: the path constants of ms_result_site_base_counts -- dict(threads, chunk_hits, lds_columns,
+    lds_columns_no_dinuc).  Constants of the build; no device."""
+    out = np.zeros(4, dtype=np.int32)
+    check(lib().ms_debug_sitestack_dims(ptr(out, ctypes.c_int32)))
+    return dict(zip(("threads", "chunk_hits", "lds_columns", "lds_columns_no_dinuc"), out.tolist()))
 
 
 def cooc_chunk_regions():

@@ -2,7 +2,8 @@
 // include/motifscan_amd.h, shared by the library's translation units: ms_context.hip (device contexts, pools), ms_pwmset.hip, ms_seqset.hip,
 // ms_result.hip (one per handle), ms_scan.hip (scan pipeline), ms_sweep.hip (window sweep), ms_regions.hip and ms_stream.hip (batch streams,
 // host-streamed sweeps), ms_best.hip (best window per cell), ms_allelebest.hip (best window per variant haplotype), ms_pairs.hip (motif pairs over a result's hits), ms_scorehist.hip (score histogram of every window),
-// ms_personal.hip (a variant set spliced into a new resident genome, and the lift map between the two).
+// ms_personal.hip (a variant set spliced into a new resident genome, and the lift map between the two), ms_sitestack.hip (base counts per
+// motif column over a result's sites).
 #pragma once
 #include <sched.h>
 #include <atomic>

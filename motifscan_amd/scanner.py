@@ -13,9 +13,10 @@ Same public surface and behaviour:
     deduplicate_motif_sites(motif_sites, lengths)        scanner.py:171-193
 plus, for inputs where n_pwms x n_regions Python lists are not an option:
     Scanner.scan_motifs_arrays(pwms) -> flat numpy arrays in the same order.
-and two questions the reference cannot answer from its site lists:
+and three questions the reference cannot answer from its site lists:
     Scanner.best_sites(pwms) -> BestSiteArrays: the best-scoring window of every (motif, region), cutoff or not.
     Scanner.score_histogram(pwms, ...) -> scoredist.ScoreHistogram: the score distribution of all windows, per motif.
+    Scanner.site_base_counts(pwms, ...) -> sitestack.SiteStack: the base counts per motif column over the sites found.
 
 `genome` is any object with `chrom_sizes[chrom]` and `fetch_sequence(chrom, start, end)`;
 `regions` any objects with `.chrom .start .end .summit` -- i.e. the reference's own
@@ -359,6 +360,28 @@ class Scanner:
         finally:
             pw.close()
         return scoredist.ScoreHistogram.from_range(counts, lo, hi, n_bins)
+
+    def site_base_counts(self, pwms, flank=0, dinuc=False):
+        """What the sites of a scan look like, as a sitestack.SiteStack: per motif and per column of the motif, with `flank` columns
+        either side, how many sites have A, C, G, T there in the motif's orientation, a non-ACGT base, or lie outside the region there
+        (ms_result_site_base_counts); dinuc adds the counts of the 16 base pairs of adjacent columns.  One scan of the scanner's own
+        sequence set with its `strand` and `p_value`, de-duplicated if `remove_dup`, counted where it lies: no hit leaves the device.
+        SiteStack.pfm(i) is the observed count matrix of motif i's sites."""
+        from . import sitestack
+        matrices, cutoffs, lengths = self._marshal(pwms)
+        pw = _lib.PwmSet.from_matrices(matrices, cutoffs)
+        try:
+            sq = self._seqset()
+            res = _lib.scan(pw, sq, _STRAND_FLAG[self.strand])
+            try:
+                if self.remove_dup:
+                    res.dedup(pw)
+                counts, di, n_sites = res.site_base_counts(pw, sq, int(flank), dinuc=dinuc)
+            finally:
+                res.close()
+        finally:
+            pw.close()
+        return sitestack.SiteStack(counts, di, n_sites, np.asarray(lengths, dtype=np.int64), int(flank))
 
     def scan_motifs(self, pwms):
         """motif_sites[n_pwms][n_regions] -> list[MotifSite] (scanner.py:89-132), as a read-only nested view over the
