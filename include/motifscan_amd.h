@@ -91,6 +91,11 @@
  *   ms_result_site_base_counts   no reference counterpart: how often A, C, G and T stand under each motif column (and the flanks) over a
  *                         result's sites, in the motif's orientation, with the adjacent-column dinucleotide counts -- the observed
  *                         count matrix of the sites found, reduced on the device from the hit arrays and the packed sequence
+ *   ms_best_rank_sum      no reference counterpart: the rank-sum (Mann-Whitney / AUROC) comparison of two groups of regions by their best
+ *                         score per motif, without a cutoff -- the exact integers 2U and the tie sum, from the matrices ms_scan_best left
+ *                         on the device
+ *   ms_best_count_passing no reference counterpart: the number of regions whose best score passes each of several cutoffs per motif --
+ *                         what ms_result_region_counts gives for one ms_scan per cutoff, from ONE best-site scan
  */
 #ifndef MOTIFSCAN_AMD_H
 #define MOTIFSCAN_AMD_H
@@ -496,6 +501,40 @@ int  ms_best_sites_device(const ms_best *b, void **d_score, void **d_pos, void *
 /* Device time of the call that made the result: first launch -> last kernel done (HIP events on the library's stream). */
 int  ms_best_device_ms(const ms_best *b, double *ms);
 void ms_best_free(ms_best *b);
+
+/* ---- cutoff-free enrichment over best-site matrices that stay on the device (ms_ranksum.hip) ------------------------- */
+/* ORDER OF CELL VALUES, for both calls: a cell without a winner (score NaN, strand 0) ranks below every number; all cells without a winner
+ * tie with one another; numbers compare as IEEE doubles, so -0.0 equals +0.0.  Nothing is special-cased for unscorable motifs: their rows
+ * are all NaN and follow the rule (u2 = na * nb, ties = N^3 - N).
+ *
+ * ms_best_rank_sum.  Group A = the cells a.score[m][i] with sel_a == NULL or sel_a[i] != 0 (na of them); group B likewise from b (nb).  a and b
+ * may be the same handle; the selections may overlap.  Per motif row m0 <= m < m1, with x over group A, y over group B and N = na + nb:
+ *     u2[m - m0]   = 2 #{(x, y): x > y} + #{(x, y): x == y}      twice the Mann-Whitney U of group A, an integer; AUROC = u2 / (2 na nb); it
+ *                                                                 fits int64 because a group holds fewer than 2^31 regions
+ *     ties[m - m0] = sum over the tie groups of the pooled sample of (t^3 - t), an unsigned 128-bit integer as {low word, high word}
+ *                    (it passes 2^63 at N = 2 097 152)
+ * n (may be NULL) receives {na, nb}.  na = 0 or nb = 0 is valid and gives u2 = 0.  m0 == m1 does nothing and returns MS_OK.  The outputs are
+ * HOST memory.  Rank sums are NOT additive over region shards: a multi-GPU caller shards the motifs, not the regions.  The call is
+ * synchronous.  It is an exact integer reduction: the same bytes on every run and for every internal batching (motif rows are ranked in
+ * batches of max(1, budget / N) rows, budget = 2^27 elements; work memory 16 bytes per element of a batch plus the sort's own).
+ * z and P-values are host arithmetic on these integers (motifscan_amd/enrich.py).
+ *
+ * ms_best_count_passing.  counts[row][k] = the number of selected regions whose best score s satisfies s - cutoffs[row][k] >= -1e-10: ms_scan's
+ * hit rule, one rounded subtraction; a NaN cell never passes.  The rounded subtraction is monotone in s, so this is exactly the number of
+ * regions that hold at least one site at that cutoff: it equals what ms_result_region_counts gives for an ms_scan of the same sequence set
+ * and strand mask at that cutoff.  The counts are additive over region shards.  The outputs are HOST memory.  n_cut = 0 is valid.
+ *
+ * Errors, both calls: MS_ERR_RUNTIME ("no CPU fallback") without a usable device, before the handles are looked at.  MS_ERR_INVALID: NULL
+ * handles or NULL required outputs, flags != 0, a motif range outside [0, n_pwms], a->P != b->P, handles on different devices, n_cut < 0 or
+ * n_cut > 0 with NULL arrays, a cutoff that is not finite.  MS_ERR_NOMEM: the work memory does not fit (nothing has been launched). */
+int ms_best_rank_sum(const ms_best *a, const uint8_t *sel_a /* [Ra] or NULL */,
+                     const ms_best *b, const uint8_t *sel_b /* [Rb] or NULL */,
+                     int32_t m0, int32_t m1, uint32_t flags /* 0 */,
+                     int64_t *u2 /* [m1 - m0] */, uint64_t *ties /* [m1 - m0][2]: low word, high word */,
+                     int64_t *n /* [2]: na, nb; may be NULL */, double *device_ms /* or NULL */);
+int ms_best_count_passing(const ms_best *b, const uint8_t *sel /* [R] or NULL */,
+                          const double *cutoffs /* [m1 - m0][n_cut] */, int32_t n_cut, int32_t m0, int32_t m1,
+                          int64_t *counts /* [m1 - m0][n_cut] */, double *device_ms /* or NULL */);
 
 /* The hit arrays in COMPACT form in library-owned pinned host memory: coord[i] = seq_idx << 32 | pos << 1 | (strand - 1),
  * score[i] -- 16 bytes per hit on the host link instead of 25.  Needs seq_idx < 2^32 and pos < 2^31 (MS_ERR_INVALID

@@ -138,6 +138,17 @@ int ms_debug_liftmap_stage_ms(const ms_liftmap *m, double out[4]);
  * when dinuc is not asked for (equal to out[2]: one limit).  Tests size their boundary cases from here.  Needs no GPU. */
 int ms_debug_sitestack_dims(int32_t out[4]);
 
+/* The path constants of ms_best_rank_sum and ms_best_count_passing, as constants of the build: out[0] the threads of a block; out[1] the
+ * cells per block of the gather kernel; out[2] the sorted elements per block of the rank kernel (a group of more takes several blocks, each
+ * with its own partial slot); out[3] the cells per block of the count kernel; out[4] the default element budget of a batch of motif rows;
+ * out[5] the cutoffs a block counts between two flushes of its LDS counters; out[6] the largest group (cells per motif row) whose rows are
+ * sorted by one segmented radix sort per batch -- a larger group takes one device radix sort per row; out[7] reserved, 0.  Tests size their
+ * boundary cases from here.  Needs no GPU. */
+int ms_debug_ranksum_dims(int32_t out[8]);
+/* ms_best_rank_sum ranks its motif rows in batches of (budget / (na + nb), at least one): elems > 0 sets the budget for the calls that follow
+ * in this process, 0 gives it back to the library.  *previous (may be NULL) = the value before.  The result does not depend on it.  Needs no GPU. */
+int ms_debug_ranksum_budget(int64_t elems, int64_t *previous);
+
 #ifdef __cplusplus
 }
 #endif

@@ -210,6 +210,10 @@ def lib():
         "ms_best_device_ms": (c_int, [vp, pd]),
         "ms_best_free": (None, [vp]),
         "ms_debug_best_segment_windows": (c_int, []),
+        "ms_best_rank_sum": (c_int, [vp, pu8, vp, pu8, c_i32, c_i32, c_u32, pi64, ctypes.POINTER(ctypes.c_uint64), pi64, pd]),
+        "ms_best_count_passing": (c_int, [vp, pu8, pd, c_i32, c_i32, c_i32, pi64, pd]),
+        "ms_debug_ranksum_dims": (c_int, [pi32]),
+        "ms_debug_ranksum_budget": (c_int, [c_i64, pi64]),
         "ms_debug_key_layout": (c_int, [c_i64, c_i64, c_i64, c_i32, c_i32, pi32, pi32]),
         "ms_scan_score_histogram": (c_int, [vp, vp, c_int, c_u32, pd, pd, c_i32, c_i32, vp, pd]),
         "ms_debug_scorehist_dims": (c_int, [pi32]),
@@ -1197,6 +1201,57 @@ class BestSites:
         check(lib().ms_best_device_ms(self.h, ctypes.byref(ms)))
         return ms.value
 
+    def _motif_range(self, m0, m1):
+        m1 = self.n_pwms if m1 is None else int(m1)
+        return int(m0), m1
+
+    @staticmethod
+    def _selection(sel, n_seqs):
+        """A region selection as the uint8 [R] array the library reads (None stays None: every region)."""
+        if sel is None:
+            return None, None
+        sel = np.ascontiguousarray(np.asarray(sel) != 0, dtype=np.uint8)
+        if sel.shape != (n_seqs,):
+            raise ValueError(f"a selection must hold one flag per region ({n_seqs}), got shape {sel.shape}")
+        return sel, ptr(sel, ctypes.c_uint8)
+
+    def rank_sum(self, other, sel=None, sel_other=None, m0=0, m1=None, timing=None):
+        """ms_best_rank_sum of this matrix's selected regions (group A) against `other`'s (group B; may be self): (u2 int64 [m1 - m0],
+        ties as a list of Python ints, na, nb).  The matrices stay on the device.  timing: a dict that receives 'device_ms'."""
+        if self.h is None or other.h is None:
+            raise ValueError("the result is closed")
+        m0, m1 = self._motif_range(m0, m1)
+        rows = max(m1 - m0, 0)
+        sa, pa = self._selection(sel, self.n_seqs)
+        sb, pb = self._selection(sel_other, other.n_seqs)
+        u2, ties, n, ms = np.zeros(rows, dtype=np.int64), np.zeros((rows, 2), dtype=np.uint64), np.zeros(2, dtype=np.int64), ctypes.c_double()
+        check(lib().ms_best_rank_sum(self.h, pa, other.h, pb, m0, m1, 0, ptr(u2, ctypes.c_int64), ptr(ties, ctypes.c_uint64), ptr(n, ctypes.c_int64),
+                                     ctypes.byref(ms)))
+        if rows == 0:                                      # (the library leaves its outputs alone for an empty range)
+            n[:] = (self.n_seqs if sa is None else int(sa.sum()), other.n_seqs if sb is None else int(sb.sum()))
+        if timing is not None:
+            timing["device_ms"] = ms.value
+        return u2, [int(lo) | (int(hi) << 64) for lo, hi in ties.tolist()], int(n[0]), int(n[1])
+
+    def count_passing(self, cutoffs, sel=None, m0=0, m1=None, timing=None):
+        """ms_best_count_passing: int64 [m1 - m0][K], the selected regions whose best score passes cutoffs[row][k] by ms_scan's hit rule.
+        cutoffs: [m1 - m0][K] (a 1-D array is one cutoff per motif)."""
+        if self.h is None:
+            raise ValueError("the result is closed")
+        m0, m1 = self._motif_range(m0, m1)
+        rows = max(m1 - m0, 0)
+        cutoffs = np.ascontiguousarray(cutoffs, dtype=np.float64)
+        if cutoffs.ndim == 1:
+            cutoffs = cutoffs.reshape(-1, 1)
+        if cutoffs.ndim != 2 or cutoffs.shape[0] != rows:
+            raise ValueError(f"cutoffs must be [{rows}][K], got shape {cutoffs.shape}")
+        _, ps = self._selection(sel, self.n_seqs)
+        counts, ms = np.zeros(cutoffs.shape, dtype=np.int64), ctypes.c_double()
+        check(lib().ms_best_count_passing(self.h, ps, ptr(cutoffs, ctypes.c_double), cutoffs.shape[1], m0, m1, ptr(counts, ctypes.c_int64), ctypes.byref(ms)))
+        if timing is not None:
+            timing["device_ms"] = ms.value
+        return counts
+
     def close(self):
         if getattr(self, "h", None):
             lib().ms_best_free(self.h)
@@ -1264,6 +1319,22 @@ def scorehist_dims():
 def best_segment_windows():
     """ms_debug_best_segment_windows: window starts per segment of ms_scan_best (tests size a multi-segment region with it)."""
     return int(lib().ms_debug_best_segment_windows())
+
+
+def ranksum_dims():
+    """ms_debug_ranksum_dims: the path constants of ms_best_rank_sum and ms_best_count_passing -- dict(threads, gather_elems, rank_elems,
+    count_elems, budget, cut_chunk, segmented_max).  Constants of the build; no device."""
+    out = np.zeros(8, dtype=np.int32)
+    check(lib().ms_debug_ranksum_dims(ptr(out, ctypes.c_int32)))
+    return dict(zip(("threads", "gather_elems", "rank_elems", "count_elems", "budget", "cut_chunk", "segmented_max"), out.tolist()))
+
+
+def ranksum_budget(elems):
+    """ms_debug_ranksum_budget: the elements ms_best_rank_sum holds at once for the calls that follow (0 = the library's own); returns the
+    value before."""
+    prev = ctypes.c_int64()
+    check(lib().ms_debug_ranksum_budget(int(elems), ctypes.byref(prev)))
+    return prev.value
 
 
 def pair_lds_bins():

@@ -3,7 +3,7 @@
 // ms_result.hip (one per handle), ms_scan.hip (scan pipeline), ms_sweep.hip (window sweep), ms_regions.hip and ms_stream.hip (batch streams,
 // host-streamed sweeps), ms_best.hip (best window per cell), ms_allelebest.hip (best window per variant haplotype), ms_pairs.hip (motif pairs over a result's hits), ms_scorehist.hip (score histogram of every window),
 // ms_personal.hip (a variant set spliced into a new resident genome, and the lift map between the two), ms_sitestack.hip (base counts per
-// motif column over a result's sites).
+// motif column over a result's sites), ms_ranksum.hip (rank sums and passing-region counts over best-site matrices).
 #pragma once
 #include <sched.h>
 #include <atomic>

@@ -240,6 +240,10 @@ int sort_hit_pairs(void *temp, size_t *temp_bytes, const uint64_t *keys_in, uint
 // Descending sort of one row of fp64 scores (cutoff builder).  Query temp size with temp == nullptr.
 int sort_doubles_desc(void *temp, size_t *temp_bytes, const double *in, double *out, size_t n, hipStream_t stream);
 
+// Every row of a [rows][n] array of 64-bit keys ascending, row by row (ms_ranksum.hip): one device radix sort per row, or (segmented; rows * n < 2^32)
+// one segmented radix sort.  Query temp size with temp == nullptr (for rows of n keys: it does not grow with rows unless segmented).
+int sort_key_rows(void *temp, size_t *temp_bytes, const uint64_t *in, uint64_t *out, size_t rows, size_t n, bool segmented, hipStream_t stream);
+
 // Exclusive prefix sum of 32-bit counts into 64-bit slots (destinations of the hits that survive de-duplication, of the
 // sites a sweep hands out: more than 2^32 of them per call are legal).
 int exclusive_sum_u32(void *temp, size_t *temp_bytes, const uint32_t *in, uint64_t *out, size_t n, hipStream_t stream);

@@ -1,11 +1,15 @@
 // ms_sort.hip -- ordering of the sparse hit list (keys = motif | position | strand bit,
 // values = fp64 scores).  The hit list is ~1e-4 of the scanned units, so this is not the hot
 // kernel; rocPRIM's device radix sort (AMD's own header-only primitives) is used as is.
-// Kept in its own translation unit because the rocPRIM headers dominate compile time.
+// Kept in its own translation unit because the rocPRIM headers dominate compile time.  Also here, for the same reason: the scans of
+// ms_personal.hip and the row sorts of ms_ranksum.hip.
 #include <cstring>
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_segmented_radix_sort.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
 
 #include "ms_internal.h"
 
@@ -27,6 +31,30 @@ int sort_keys(void *temp, size_t *temp_bytes, const uint64_t *keys_in, uint64_t 
     if (end_bit < 1) end_bit = 1;
     if (end_bit > 64) end_bit = 64;
     MS_HIP(rocprim::radix_sort_keys(temp, *temp_bytes, keys_in, keys_out, n, 0u, (unsigned int) end_bit, stream));
+    return MS_OK;
+}
+
+namespace {
+struct RowOffset {                                  // segment i of a [rows][n] array starts at i * n
+    unsigned int n;
+    __host__ __device__ unsigned int operator()(unsigned int i) const { return i * n; }
+};
+}  // namespace
+
+int sort_key_rows(void *temp, size_t *temp_bytes, const uint64_t *in, uint64_t *out, size_t rows, size_t n, bool segmented, hipStream_t stream) {
+    if (segmented) {
+        const auto begin = rocprim::make_transform_iterator(rocprim::make_counting_iterator<unsigned int>(0u), RowOffset{(unsigned int) n});
+        MS_HIP(rocprim::segmented_radix_sort_keys(temp, *temp_bytes, in, out, (unsigned int) (rows * n), (unsigned int) rows, begin, begin + 1, 0u, 64u, stream));
+        return MS_OK;
+    }
+    if (!temp) {
+        MS_HIP(rocprim::radix_sort_keys(temp, *temp_bytes, in, out, n, 0u, 64u, stream));
+        return MS_OK;
+    }
+    for (size_t i = 0; i < rows; i++) {
+        size_t tb = *temp_bytes;
+        MS_HIP(rocprim::radix_sort_keys(temp, tb, in + i * n, out + i * n, n, 0u, 64u, stream));
+    }
     return MS_OK;
 }
 

@@ -13,8 +13,10 @@ Same public surface and behaviour:
     deduplicate_motif_sites(motif_sites, lengths)        scanner.py:171-193
 plus, for inputs where n_pwms x n_regions Python lists are not an option:
     Scanner.scan_motifs_arrays(pwms) -> flat numpy arrays in the same order.
-and three questions the reference cannot answer from its site lists:
+and the questions the reference cannot answer from its site lists:
     Scanner.best_sites(pwms) -> BestSiteArrays: the best-scoring window of every (motif, region), cutoff or not.
+    Scanner.rank_sum(pwms, control) -> enrich.RankSum: cutoff-free enrichment of the best scores against a control scanner's.
+    Scanner.count_regions_passing(pwms, cutoffs) -> the regions with >= 1 site at several cutoffs per motif, from one scan.
     Scanner.score_histogram(pwms, ...) -> scoredist.ScoreHistogram: the score distribution of all windows, per motif.
     Scanner.site_base_counts(pwms, ...) -> sitestack.SiteStack: the base counts per motif column over the sites found.
 
@@ -342,6 +344,45 @@ class Scanner:
         finally:
             pw.close()
         return BestSiteArrays(score, best_site_starts(pos, self.seq_starts), strand)
+
+    def _scan_best(self, pw):
+        return _lib.scan_best(pw, self._seqset(), _STRAND_FLAG[self.strand])
+
+    def rank_sum(self, pwms, control, sel=None, sel_control=None):
+        """Is each motif enriched in this scanner's regions against `control`'s (another Scanner), without choosing a cutoff?  The
+        rank-sum comparison of the best score per region, as an enrich.RankSum (.auroc(), .z(), .p_value()).  Both region lists are
+        scanned with ms_scan_best, each with its scanner's `strand`; both matrices stay on the device and are reduced there
+        (ms_best_rank_sum) -- no matrix is copied.  sel / sel_control: one flag per region of either scanner (None: all of them)."""
+        from . import enrich
+        matrices = [np.asarray(pwm.matrix, dtype=np.float64) for pwm in pwms]
+        pw = _lib.PwmSet.from_matrices(matrices)
+        try:
+            mine = self._scan_best(pw)
+            try:
+                theirs = control._scan_best(pw)
+                try:
+                    return enrich.rank_sum(mine, theirs, sel, sel_control)
+                finally:
+                    theirs.close()
+            finally:
+                mine.close()
+        finally:
+            pw.close()
+
+    def count_regions_passing(self, pwms, cutoffs):
+        """int64 [n_pwms][K]: the number of this scanner's regions that hold >= 1 site of each motif at each of its K cutoffs
+        (cutoffs [n_pwms][K]) -- count_regions_with_sites at K cutoffs from ONE best-site scan (ms_best_count_passing) instead of K
+        scans.  Honours `strand`; the PWMs' own cutoffs and `p_value` are not read."""
+        matrices = [np.asarray(pwm.matrix, dtype=np.float64) for pwm in pwms]
+        pw = _lib.PwmSet.from_matrices(matrices)
+        try:
+            res = self._scan_best(pw)
+            try:
+                return res.count_passing(cutoffs)
+            finally:
+                res.close()
+        finally:
+            pw.close()
 
     def score_histogram(self, pwms, lo=0.0, hi=None, n_bins=1024, per_position=False):
         """The score distribution of ALL windows of the scanner's regions, per motif, as a scoredist.ScoreHistogram: n_bins equal bins over
