@@ -66,13 +66,22 @@ struct HitStageN {
 typedef HitStageN<kHitStage> HitStage;
 
 // ... into its bucket: a stage that is full sends its hits here one by one
-__device__ __forceinline__ void emit_hit(const BucketHitOut &H, uint32_t motif, int64_t g, uint32_t sbit, double score) {
+// (*key_out: the hit's key; returns whether the bucket holds it, which is what fill_tail_buckets_kernel counts as a hit of the list)
+__device__ __forceinline__ bool emit_hit(const BucketHitOut &H, uint32_t motif, int64_t g, uint32_t sbit, double score, uint64_t *key_out) {
     const uint64_t key = ((uint64_t) motif << (H.gbits + 1)) | ((uint64_t) g << 1) | sbit;
     const uint32_t b = (uint32_t) (key >> H.B.shift) & 255u;
     const unsigned long long i = atomicAdd(&H.B.fill[b], 1ULL);
     const unsigned long long at = H.B.base[b] + i;
     if (i < H.B.cap[b] && at < H.cap) { H.keys[at] = key; H.vals[at] = score; }
     else *H.B.overflow = 1ULL;
+    *key_out = key;
+    return i < H.B.cap[b];
+}
+
+// a full stage's hit, straight to HBM (the bucketed stage also counts it: emit_direct(RwStageBk &, ...) below)
+template <class ST>
+__device__ __forceinline__ void emit_direct(ST &, const HitOut &H, uint32_t motif, int64_t g, uint32_t sbit, double score) {
+    emit_hit(H, motif, g, sbit, score);
 }
 
 template <class ST, class HO>
@@ -82,7 +91,7 @@ __device__ __forceinline__ void stage_hit(ST &st, const HO &H, uint32_t motif, i
         st.keys[i] = ((uint64_t) motif << (H.gbits + 1)) | ((uint64_t) g << 1) | sbit;
         st.vals[i] = score;
     } else {
-        emit_hit(H, motif, g, sbit, score);            // stage full: straight to HBM
+        emit_direct(st, H, motif, g, sbit, score);     // stage full: straight to HBM
     }
 }
 
@@ -323,7 +332,32 @@ typedef HitStageN<2048> RwStage;
 struct RwStageBk : RwStage {                // the bucketed flush's words per bucket: staged hits, room left in the bucket, first slot of this flush's hits
     unsigned int cnt[kOrderBuckets], room[kOrderBuckets];
     unsigned long long lo[kOrderBuckets];
+    unsigned int hist[kBucketHistPlaces * 256];      // the block's hits by the digits of the radix passes that are left (BucketOut::hist), all chunks together
 };
+
+// one hit the buckets hold, into the block's digit counts: the places [shift + 8 + 8 p, + 8), p < hist_places (a hit key has no bit at or
+// above the scan's end bit, so a last place of fewer than eight bits needs no mask of its own)
+__device__ __forceinline__ void count_places(RwStageBk &st, const BucketOut &B, uint64_t key) {
+    for (int p = 0; p < B.hist_places; p++) atomicAdd(&st.hist[p * 256 + ((uint32_t) (key >> (B.shift + 8 + 8 * p)) & 255u)], 1u);
+}
+// (one LDS add per hit and place.  One add per wave and distinct digit, by ballots, was measured and is far slower -- the fp64 stage
+// 3.30 ms against 2.18: the stage holds its hits in the order its sixteen waves appended them, so a wave's 64 keys share few digits.)
+
+__device__ __forceinline__ void emit_direct(RwStageBk &st, const BucketHitOut &H, uint32_t motif, int64_t g, uint32_t sbit, double score) {
+    uint64_t key;
+    if (emit_hit(H, motif, g, sbit, score, &key)) count_places(st, H.B, key);
+}
+
+// start and end of a block of rescore_carry_kernel: the plain stage keeps no counts
+__device__ __forceinline__ void stage_hist_clear(RwStage &) {}
+__device__ __forceinline__ void stage_hist_clear(RwStageBk &st) {
+    for (unsigned int i = threadIdx.x; i < (unsigned int) (kBucketHistPlaces * 256); i += kRwThreads) st.hist[i] = 0;
+}
+__device__ __forceinline__ void stage_hist_add(RwStage &, const HitOut &) {}
+__device__ __forceinline__ void stage_hist_add(RwStageBk &st, const BucketHitOut &H) {       // behind the last stage_flush's barrier
+    for (unsigned int i = threadIdx.x; i < (unsigned int) (H.B.hist_places * 256); i += kRwThreads)
+        if (st.hist[i]) atomicAdd(&H.B.hist[i], (unsigned long long) st.hist[i]);
+}
 
 // the bucketed form of stage_flush, for the kRwThreads threads of rescore_carry_kernel: every staged hit goes to bucket (key >> shift) & 255
 __device__ __forceinline__ void stage_flush(RwStageBk &st, const BucketHitOut &H) {
@@ -355,7 +389,9 @@ __device__ __forceinline__ void stage_flush(RwStageBk &st, const BucketHitOut &H
         const unsigned int i = threadIdx.x + (unsigned int) (k * kRwThreads);
         if (i < n && rank[k] < st.room[bk[k]]) {
             const unsigned long long at = st.lo[bk[k]] + rank[k];
-            if (at < H.cap) { H.keys[at] = st.keys[i]; H.vals[at] = st.vals[i]; }
+            const uint64_t key = st.keys[i];
+            if (at < H.cap) { H.keys[at] = key; H.vals[at] = st.vals[i]; }
+            count_places(st, H.B, key);
         }
     }
     __syncthreads();
@@ -377,6 +413,7 @@ __global__ void __launch_bounds__(kRwThreads) rescore_carry_kernel(const DevSeq 
     uint32_t *wave_tot = bins + kRwBins;                                                    // [16]
     ST &st = *reinterpret_cast<ST *>(wave_tot + 32);
     if (threadIdx.x == 0) st.n = 0;
+    stage_hist_clear(st);                      // (the chunk loop's first barrier stands between this and the first count)
     unsigned long long n = n_static + *n_cand;
     if (n > cand_cap) n = cand_cap;
     const bool both = strand_mask == 3;
@@ -487,6 +524,7 @@ __global__ void __launch_bounds__(kRwThreads) rescore_carry_kernel(const DevSeq 
             stage_flush(st, H);
         }
     }
+    stage_hist_add(st, H);
 }
 
 template <class ST>

@@ -68,9 +68,14 @@ struct HitOut {
 // A hit list in BUCKETS of the lowest radix digit d0 = (key >> shift) & 255 (a predicted-size scan whose geometry passes bucket_gate,
 // ms_scan_geom.h): bucket b owns the slots [base[b], base[b] + cap[b]) of HitOut::keys / vals, fill[b] counts the hits sent to it (beyond
 // cap[b]: dropped, *overflow set -- the scan is run again with a plain list).  One table of kBucketTabWords words: base, cap, fill (256
-// each), then [768] the end of the last bucket.
+// each), then [768] the end of the last bucket, then from kBucketHistAt on the digit counts of the radix passes that are left: place p counts
+// the list's keys -- the hits the buckets hold and the all-ones keys that pad them -- by (key >> (shift + 8 + 8 p)) & 255 (BucketOut::hist;
+// bucket_plan_kernel zeroes them, the bucketed fp64 stage adds the hits, fill_tail_buckets_kernel the padding keys, sort_hit_pairs_counted
+// reads them in place of a histogram pass over the list).
 constexpr int kOrderBuckets = 256;
-constexpr size_t kBucketTabWords = 3 * kOrderBuckets + 8;
+constexpr int kBucketHistPlaces = 3;             // places counted at most: a scan whose passes cover more takes the histogram pass
+constexpr size_t kBucketHistAt = 3 * kOrderBuckets + 8;
+constexpr size_t kBucketTabWords = kBucketHistAt + (size_t) kBucketHistPlaces * 256;
 struct BucketWeights {                   // per (sequence set, motif widths, key layout, L): the (motif, window start) pairs whose key falls into each bucket (bucket_weights, ms_scan_geom.h)
     unsigned long long w[kOrderBuckets];
     unsigned long long total;
@@ -81,6 +86,8 @@ struct BucketOut {
     unsigned long long *fill;
     unsigned long long *overflow;
     int shift;
+    unsigned long long *hist;            // [hist_places][256], or nullptr: not counted
+    int hist_places;
 };
 struct BucketHitOut : HitOut {
     BucketOut B;
@@ -132,8 +139,16 @@ int launch_fill_tail(uint64_t *keys, const unsigned long long *n_dev, uint64_t c
 // tail fill behind it: all-ones keys into the unused slots of every bucket and behind the last one, *n_hits = the hits the buckets hold
 int launch_bucket_plan(const BucketWeights &bw, double mu, unsigned long long n_pred, unsigned long long need, unsigned long long cap_max,
                        unsigned long long *tab, hipStream_t st);
+// (hist != nullptr: the all-ones keys are added to the digit counts of hist_places places, the last of them hist_last_bits wide)
 int launch_fill_tail_buckets(uint64_t *keys, const unsigned long long *tab, uint64_t n_pred, unsigned long long *n_hits, unsigned long long *overflow,
-                             hipStream_t st);
+                             unsigned long long *hist, int hist_places, int hist_last_bits, hipStream_t st);
+// sort_hit_pairs (ms_internal.h) for a list whose digit counts are known: counts[p * 256 + d] keys have the digit d at the bits
+// [begin_bit + 8 p, + 8) (cut at end_bit), for every place of [begin_bit, end_bit).  The radix passes run without the histogram pass over the
+// list; *done = false and nothing queued where that cannot be had (another rocPRIM than the one this was written against, a configuration
+// that does not sort eight bits a pass, too little temporary storage): the caller then takes sort_hit_pairs.  temp == nullptr: the bytes
+// of temporary storage it takes into *temp_bytes (*done: whether it can run at all).
+int sort_hit_pairs_counted(void *temp, size_t *temp_bytes, const uint64_t *keys_in, uint64_t *keys_out, const double *vals_in, double *vals_out,
+                           size_t n, int begin_bit, int end_bit, const unsigned long long *counts, bool *done, hipStream_t stream);
 int launch_sort_fixup(uint64_t *keys, double *vals, int64_t n, const unsigned long long *n_dev, hipStream_t st);
 int launch_finalize(const uint64_t *keys, int64_t n, const unsigned long long *n_dev, int gbits, int rbits, int pbits, int32_t P, const DevSeq &S,
                     int64_t *seq_idx, int64_t *pos, int8_t *strand, int64_t *motif_first, unsigned long long *region_counts,

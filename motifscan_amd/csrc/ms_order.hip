@@ -19,8 +19,8 @@
 // the per-motif region counts (the semantics of finalize_rp_kernel, below).  This replaces a fix-up kernel plus a finalize
 // kernel (one read of keys and scores fewer), and L up to 24 lets the radix sort drop up to two of its eight-bit passes.
 //
-//   order_finalize_kernel  block b owns the runs that START in slots [b * kOrderTile, (b + 1) * kOrderTile); it stages those slots and
-//                          the kOrderExt after them in LDS, ranks each element inside its run (a scan's keys are distinct: no ties),
+//   order_finalize_kernel  block b owns the runs that START in slots [b * kTile, (b + 1) * kTile); it stages the keys of those slots and of
+//                          the kExt after them in LDS, ranks each element inside its run (a scan's keys are distinct: no ties),
 //                          and decodes.  A run that does not close inside the staged window, or that is longer than run_cap, goes to
 //                          the overflow list instead (an atomic append of its first slot).
 //   order_overflow_kernel  one block per listed run (grid-stride over the list): finds the run's end, sorts it by an LSD radix sort
@@ -33,6 +33,7 @@
 // same for the whole run; the pair bits are either above L too (L <= pbits + 1), or they include bits above L, which differ between
 // two runs, so the pair changes.  The radix-order predecessor is therefore enough, and no block depends on another block's output.
 #include <algorithm>
+#include <cmath>
 
 #include "ms_device.h"
 
@@ -41,9 +42,16 @@ namespace ms {
 namespace {
 
 constexpr int kOrderThreads = 256;
-constexpr int kOrderTile = 1024;                 // slots a block owns the run starts of
-constexpr int kOrderExt = 256;                   // slots staged past the tile to close its last run: every run of <= kOrderExt hits is
-constexpr int kOrderWin = kOrderTile + kOrderExt;    // sorted in LDS (31.5 KB per block: five blocks per CU)
+// order_finalize_kernel<kTile, kExt>: kTile slots a block owns the run starts of, kExt slots staged past them to close the tile's last run.
+// Every run of <= kExt hits is sorted in LDS, whatever kExt is; a longer one that does not close inside the window goes to the overflow kernel.
+// The slots past the tile are read twice (by this block and by the one that owns them), so the host takes the short extension where the
+// expected run n / (P x 2^(gbits + 1 - L)) is at most kOrderShortMeanRun hits.  That is the mean over the motifs, and a motif set's hit
+// rates are far from equal: the benchmark's busiest motif hits 21 times as often as the average one.  At its L = 16 (mean run 6.8, the
+// busiest motif's 142) 26 % of the hits stand in runs of more than 64, and a 960 + 64 window would leave 0.8 % of them (7 000 runs a scan)
+// to the overflow kernel; 1024 + 256 leaves 3e-22.  A mean of at most one hit keeps the busiest motif's runs near 20.
+constexpr int kOrderTileShort = 960, kOrderExtShort = 64;      // 1024 staged slots, 6.7 % of them read twice; 12.2 KB of LDS per block
+constexpr int kOrderTileLong = 1024, kOrderExtLong = 256;      // 1280 staged slots, 25 % read twice; 15.2 KB (the form before: 31.5)
+constexpr double kOrderShortMeanRun = 1.0;
 constexpr int kOverflowBlocks = 256;
 
 struct OrderRun {
@@ -99,23 +107,26 @@ __device__ __forceinline__ void count_pairs(unsigned long long *region_counts, b
 }
 
 // Slot i = tid + kOrderThreads * k of the staged window is thread tid's k-th: its key and score stay in registers from the load to the
-// scatter, and its wave's ballot of run starts (one 64-slot segment) gives the run's bounds without walking the keys.
+// stores, and its wave's ballot of run starts (one 64-slot segment) gives the run's bounds without walking the keys, unless a bound lies in
+// another segment (seg_first / seg_last).  The keys are all LDS holds: the rank loop over a hit's run gives its final slot and, as the
+// largest smaller key, its predecessor there, so every hit is decoded and stored from its own thread's registers -- the stores of a wave
+// fall into the cache lines of its 64 slots (and of a run that straddles them), in another order.
+template <int kTile, int kExt>
 __global__ void __launch_bounds__(kOrderThreads) order_finalize_kernel(const uint64_t *__restrict__ keys, int64_t n, const unsigned long long *__restrict__ n_dev,
                                                                       int L, int run_cap, OrderOut O, OrderRun *__restrict__ ovf,
                                                                       unsigned long long *__restrict__ ovf_n, uint64_t ovf_cap) {
-    constexpr int kPer = kOrderWin / kOrderThreads, kSegs = kOrderWin / 64;
-    __shared__ uint64_t K[kOrderWin];          // radix order
-    __shared__ uint64_t S[kOrderWin];          // final order
-    __shared__ double V[kOrderWin];
-    __shared__ uint8_t D[kOrderWin];           // slot sorted here
-    __shared__ int seg_first[kSegs], seg_last[kSegs];                // first / last run start of each 64-slot segment (none: kOrderWin / -1)
+    constexpr int kWin = kTile + kExt, kPer = kWin / kOrderThreads, kSegs = kWin / 64;
+    static_assert(kWin % kOrderThreads == 0 && kTile % 64 == 0 && kExt % 64 == 0, "whole waves per round, whole segments per tile");
+    __shared__ uint64_t K[kWin];               // radix order
+    __shared__ uint32_t K32[kWin];             // its low words, for the rank loop
+    __shared__ int seg_first[kSegs], seg_last[kSegs];                // first / last run start of each 64-slot segment (none: kWin / -1)
     __shared__ unsigned int rc[kOrderMotifSlots];                    // the block's region counts of its first motifs (a block of a long list spans one or two)
     if (n_dev) { const unsigned long long nd = *n_dev; if ((unsigned long long) n > nd) n = (int64_t) nd; }
-    const int64_t s0 = (int64_t) blockIdx.x * kOrderTile;
+    const int64_t s0 = (int64_t) blockIdx.x * kTile;
     if (s0 >= n) return;
     const int tid = (int) threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wn = (int) std::min<int64_t>(kOrderWin, n - s0);      // staged slots
-    const int tn = std::min(kOrderTile, wn);                          // owned run starts lie in [0, tn)
+    const int wn = (int) std::min<int64_t>(kWin, n - s0);           // staged slots
+    const int tn = std::min(kTile, wn);                               // owned run starts lie in [0, tn)
     uint64_t kr[kPer];
     double vr[kPer];                           // (scores of slots another block owns are read too, and never used)
 #pragma unroll
@@ -124,7 +135,7 @@ __global__ void __launch_bounds__(kOrderThreads) order_finalize_kernel(const uin
         kr[k] = i < wn ? keys[s0 + i] : ~0ULL;
         vr[k] = i < wn ? O.score[s0 + i] : 0.0;
         K[i] = kr[k];
-        D[i] = 0;
+        K32[i] = (uint32_t) kr[k];
     }
     if (tid < kOrderMotifSlots) rc[tid] = 0;
     const uint64_t prevk = s0 > 0 ? keys[s0 - 1] : 0ULL;
@@ -137,52 +148,69 @@ __global__ void __launch_bounds__(kOrderThreads) order_finalize_kernel(const uin
         msk[k] = __ballot(start);
         if (lane == 0) {
             const int seg = w + (kOrderThreads / 64) * k;
-            seg_first[seg] = msk[k] ? seg * 64 + __ffsll((long long) msk[k]) - 1 : kOrderWin;
+            seg_first[seg] = msk[k] ? seg * 64 + __ffsll((long long) msk[k]) - 1 : kWin;
             seg_last[seg] = msk[k] ? seg * 64 + 63 - __clzll((long long) msk[k]) : -1;
         }
     }
     __syncthreads();
-    int lo = kOrderWin, hi = wn;               // owned slots: [lo, hi) -- from the first run start in the tile to the first one past it
+    int lo = kWin, hi = wn;                    // owned slots: [lo, hi) -- from the first run start in the tile to the first one past it
     for (int q = 0; q < kSegs; q++) lo = std::min(lo, seg_first[q]);
-    if (tn == kOrderTile)
-        for (int q = kOrderTile / 64; q < kSegs; q++) hi = std::min(hi, seg_first[q]);
+    if (tn == kTile)
+        for (int q = kTile / 64; q < kSegs; q++) hi = std::min(hi, seg_first[q]);
     if (lo >= tn) return;                      // no run starts in this tile
     const bool closed = hi < wn || s0 + wn == n;                      // else the last owned run runs on past the window
     const int ms = O.rbits + O.pbits + 1;
     const uint32_t m_base = (uint32_t) (K[lo] >> ms);
     const unsigned long long le = lane == 63 ? ~0ULL : (2ULL << lane) - 1ULL;
 #pragma unroll
-    for (int k = 0; k < kPer; k++) {
-        const int i = tid + kOrderThreads * k, seg = w + (kOrderThreads / 64) * k;
-        if (i < lo || i >= hi) continue;
-        int a = -1, b = wn;
-        if (msk[k] & le) a = seg * 64 + 63 - __clzll((long long) (msk[k] & le));
-        else for (int q = seg - 1; q >= 0 && a < 0; q--) a = seg_last[q];
-        if (msk[k] & ~le) b = seg * 64 + __ffsll((long long) (msk[k] & ~le)) - 1;
-        else for (int q = seg + 1; q < kSegs && b == wn; q++) b = std::min(wn, seg_first[q]);
-        if ((b == hi && !closed) || b - a > run_cap) {
-            if (i == a) {
-                const unsigned long long e = atomicAdd(ovf_n, 1ULL);
-                if (e < ovf_cap) ovf[e] = OrderRun{s0 + a, a > 0 ? K[a - 1] : prevk};
-            }
-            continue;
-        }
-        int rank = 0;
-        for (int j = a; j < b; j++) rank += K[j] < kr[k] ? 1 : 0;
-        S[a + rank] = kr[k];
-        V[a + rank] = vr[k];
-        D[a + rank] = 1;
-    }
-    __syncthreads();
-#pragma unroll
     for (int k = 0; k < kPer; k++) {           // whole waves: count_pairs
-        const int j = tid + kOrderThreads * k;
+        const int i = tid + kOrderThreads * k, seg = w + (kOrderThreads / 64) * k;
         bool new_pair = false;
         uint32_t motif = 0;
-        if (j >= lo && j < hi && D[j]) {
-            const bool run_start = (msk[k] >> lane) & 1ULL;
-            const uint64_t pk = run_start ? (j == 0 ? prevk : K[j - 1]) : S[j - 1];
-            new_pair = decode_hit(O, s0 + j, n, S[j], V[j], s0 + j > 0, pk, &motif);
+        if (i >= lo && i < hi) {
+            int a = -1, b = wn;
+            if (msk[k] & le) a = seg * 64 + 63 - __clzll((long long) (msk[k] & le));
+            else for (int q = seg - 1; q >= 0 && a < 0; q--) a = seg_last[q];
+            if (msk[k] & ~le) b = seg * 64 + __ffsll((long long) (msk[k] & ~le)) - 1;
+            else for (int q = seg + 1; q < kSegs && b == wn; q++) b = std::min(wn, seg_first[q]);
+            if ((b == hi && !closed) || b - a > run_cap) {
+                if (i == a) {
+                    const unsigned long long e = atomicAdd(ovf_n, 1ULL);
+                    if (e < ovf_cap) ovf[e] = OrderRun{s0 + a, a > 0 ? K[a - 1] : prevk};
+                }
+            } else {
+                // rank in the run, and the largest key of the run under this one (a scan's keys are distinct).  This loop is where the
+                // kernel's instructions go once runs are long (a wave takes as many turns as its longest run has hits), so with
+                // L <= 32 it compares the keys' low words only -- the run agrees in every bit from L up -- four to a turn.
+                int rank = 0;
+                uint64_t below = 0ULL;
+                if (L <= 32) {
+                    const uint32_t me = (uint32_t) kr[k];
+                    uint32_t under = 0u;
+                    int j = a;
+                    for (; j + 4 <= b; j += 4) {
+                        const uint32_t k0 = K32[j], k1 = K32[j + 1], k2 = K32[j + 2], k3 = K32[j + 3];
+                        rank += (k0 < me ? 1 : 0) + (k1 < me ? 1 : 0) + (k2 < me ? 1 : 0) + (k3 < me ? 1 : 0);
+                        under = std::max(std::max(under, k0 < me ? k0 : 0u), k1 < me ? k1 : 0u);
+                        under = std::max(std::max(under, k2 < me ? k2 : 0u), k3 < me ? k3 : 0u);
+                    }
+                    for (; j < b; j++) {
+                        const uint32_t kj = K32[j];
+                        rank += kj < me ? 1 : 0;
+                        under = std::max(under, kj < me ? kj : 0u);
+                    }
+                    below = (kr[k] & ~0xFFFFFFFFULL) | under;
+                } else {
+                    for (int j = a; j < b; j++) {
+                        const uint64_t kj = K[j];
+                        if (kj < kr[k]) { rank++; below = std::max(below, kj); }
+                    }
+                }
+                // the run's first hit in the final order: its predecessor is any hit of the run in front (the header's last paragraph)
+                const uint64_t pk = rank > 0 ? below : (a > 0 ? K[a - 1] : prevk);
+                const int64_t g = s0 + a + rank;
+                new_pair = decode_hit(O, g, n, kr[k], vr[k], g > 0, pk, &motif);
+            }
         }
         count_pairs(O.region_counts, new_pair, motif, rc, m_base);
     }
@@ -271,7 +299,7 @@ __global__ void __launch_bounds__(kOrderThreads) order_overflow_kernel(uint64_t 
 }  // namespace
 
 size_t order_overflow_bytes(size_t n, int run_cap) {
-    const size_t min_len = (size_t) std::min(std::max(run_cap, 1), kOrderExt) + 1;     // every listed run is longer than this minus one
+    const size_t min_len = (size_t) std::min(std::max(run_cap, 1), kOrderExtShort) + 1;     // every listed run is longer than this minus one, with either extension
     return (n / min_len + 1) * sizeof(OrderRun);
 }
 
@@ -289,11 +317,18 @@ int launch_order_finalize(uint64_t *keys, double *score, int64_t n, const unsign
     O.rbits = rbits; O.pbits = pbits; O.P = P;
     OrderRun *ovf = static_cast<OrderRun *>(ovf_buf);
     const uint64_t ovf_cap = ovf_bytes / sizeof(OrderRun);
-    hipLaunchKernelGGL(order_finalize_kernel, dim3((unsigned) ((n + kOrderTile - 1) / kOrderTile)), dim3(kOrderThreads), 0, st, keys, n, n_dev,
-                       L, run_cap, O, ovf, ovf_n, ovf_cap);
+    // the expected run: n hits over P x 2^(gbits + 1 - L) values of the key bits above L, gbits = rbits + pbits (scan_geom's order_low_bits)
+    const bool short_ext = std::ldexp((double) n / (double) std::max(P, 1), L - rbits - pbits - 1) <= kOrderShortMeanRun;
+    const int ext = short_ext ? kOrderExtShort : kOrderExtLong;
+    if (short_ext)
+        hipLaunchKernelGGL((order_finalize_kernel<kOrderTileShort, kOrderExtShort>), dim3((unsigned) ((n + kOrderTileShort - 1) / kOrderTileShort)),
+                           dim3(kOrderThreads), 0, st, keys, n, n_dev, L, run_cap, O, ovf, ovf_n, ovf_cap);
+    else
+        hipLaunchKernelGGL((order_finalize_kernel<kOrderTileLong, kOrderExtLong>), dim3((unsigned) ((n + kOrderTileLong - 1) / kOrderTileLong)),
+                           dim3(kOrderThreads), 0, st, keys, n, n_dev, L, run_cap, O, ovf, ovf_n, ovf_cap);
     MS_HIP(hipGetLastError());
-    // a run is only listed when it is longer than run_cap or than kOrderExt: with at most 2^L hits per run, not at L = 8 by default
-    if (L < 63 && (1ULL << L) > (unsigned long long) std::min(run_cap, kOrderExt)) {
+    // a run is only listed when it is longer than run_cap or than the extension: with at most 2^L hits per run, not at L = 8 with the long one by default
+    if (L < 63 && (1ULL << L) > (unsigned long long) std::min(run_cap, ext)) {
         hipLaunchKernelGGL(order_overflow_kernel, dim3(kOverflowBlocks), dim3(kOrderThreads), 0, st, keys, tmp_keys, tmp_vals, n, n_dev, L, O,
                            ovf, ovf_n, ovf_cap);
         MS_HIP(hipGetLastError());
@@ -396,14 +431,18 @@ __global__ void __launch_bounds__(kOrderBuckets) bucket_plan_kernel(const Bucket
     tab[b] = base;
     tab[kOrderBuckets + b] = cb < n_pred - base ? cb : n_pred - base;
     tab[2 * kOrderBuckets + b] = 0ULL;
+    for (int p = 0; p < kBucketHistPlaces; p++) tab[kBucketHistAt + (size_t) p * 256 + b] = 0ULL;      // the digit counts (BucketOut::hist)
     if (b == kOrderBuckets - 1) tab[3 * kOrderBuckets] = sum[b] < n_pred ? sum[b] : n_pred;
 }
 
 // grid (x, kOrderBuckets + 1): row b < kOrderBuckets fills the unused slots of bucket b, the last row the slots behind the last bucket; its first block
 // also sums the hits the buckets HOLD into *n_hits (what order_finalize_kernel reads as the list's length -- a dropped hit must not count: the slot
-// it would stand for holds an all-ones key, whose "motif" no decode may touch; the scan is run again anyway, *overflow says so)
+// it would stand for holds an all-ones key, whose "motif" no decode may touch; the scan is run again anyway, *overflow says so).  hist != nullptr:
+// that block also adds the all-ones keys of the whole list -- every slot of the n_pred that holds no hit -- to the digit counts, place by
+// place: bin 255, or the last place's 2^last_bits - 1 where the passes end inside it (a radix pass reads no bit at or above its end bit).
 __global__ void __launch_bounds__(256) fill_tail_buckets_kernel(uint64_t *__restrict__ keys, const unsigned long long *__restrict__ tab, uint64_t n_pred,
-                                                                unsigned long long *__restrict__ n_hits, unsigned long long *__restrict__ overflow) {
+                                                                unsigned long long *__restrict__ n_hits, unsigned long long *__restrict__ overflow,
+                                                                unsigned long long *__restrict__ hist, int places, int last_bits) {
     const unsigned int b = blockIdx.y;
     unsigned long long lo, hi;
     if (b < (unsigned int) kOrderBuckets) {
@@ -428,6 +467,8 @@ __global__ void __launch_bounds__(256) fill_tail_buckets_kernel(uint64_t *__rest
                 __syncthreads();
             }
             if (threadIdx.x == 0) *n_hits = part[0];
+            if (hist && (int) threadIdx.x < places && part[0] < n_pred)
+                hist[threadIdx.x * 256 + ((int) threadIdx.x == places - 1 ? (1u << last_bits) - 1u : 255u)] += n_pred - part[0];
         }
     }
     if (hi > n_pred) hi = n_pred;
@@ -443,8 +484,9 @@ int launch_bucket_plan(const BucketWeights &bw, double mu, unsigned long long n_
 }
 
 int launch_fill_tail_buckets(uint64_t *keys, const unsigned long long *tab, uint64_t n_pred, unsigned long long *n_hits, unsigned long long *overflow,
-                             hipStream_t st) {
-    hipLaunchKernelGGL(fill_tail_buckets_kernel, dim3(16, kOrderBuckets + 1), dim3(256), 0, st, keys, tab, n_pred, n_hits, overflow);
+                             unsigned long long *hist, int hist_places, int hist_last_bits, hipStream_t st) {
+    hipLaunchKernelGGL(fill_tail_buckets_kernel, dim3(16, kOrderBuckets + 1), dim3(256), 0, st, keys, tab, n_pred, n_hits, overflow, hist,
+                       hist_places, hist_last_bits);
     MS_HIP(hipGetLastError());
     return MS_OK;
 }

@@ -227,6 +227,11 @@ static BucketOut scan_bucket_out(const ScanCtx &x) {
     BucketOut B;
     B.base = sc.bucket_tab; B.cap = sc.bucket_tab + kOrderBuckets; B.fill = sc.bucket_tab + 2 * kOrderBuckets; B.overflow = sc.counters + 3;
     B.shift = x.bk_L;
+    // the digit counts of the radix passes that are left, [bk_L + 8, end_bit): taken in the fp64 stage where they fit its LDS words
+    const int places = (x.g.end_bit - (x.bk_L + 8) + 7) / 8;
+    const bool counted = places >= 1 && places <= kBucketHistPlaces;
+    B.hist = counted ? sc.bucket_tab + kBucketHistAt : nullptr;
+    B.hist_places = counted ? places : 0;
     return B;
 }
 
@@ -345,6 +350,16 @@ static int back_sort(ScanCtx &x, size_t n_sort, const unsigned long long *n_dev,
     int rc;
     size_t need = 0;
     if ((rc = sort_hit_pairs(nullptr, &need, sc.keys, sc.keys_sorted, sc.vals, x.raw->d_score, n_sort, sort_begin, x.g.end_bit, c->stream))) return rc;
+    // a bucketed list comes with its digit counts (BucketOut::hist): the passes then run without rocPRIM's histogram pass over the list
+    const unsigned long long *counts = x.bucketed && sort_begin == x.bk_L + 8 ? scan_bucket_out(x).hist : nullptr;
+    if (counts) {
+        size_t need_counted = 0;
+        bool can = false;
+        if ((rc = sort_hit_pairs_counted(nullptr, &need_counted, sc.keys, sc.keys_sorted, sc.vals, x.raw->d_score, n_sort, sort_begin, x.g.end_bit, nullptr,
+                                         &can, c->stream))) return rc;
+        if (can) need = std::max(need, need_counted);
+        else counts = nullptr;
+    }
     need = std::max(need, ovf_bytes);             // (the radix temp storage is free once the passes are done: order_finalize_kernel's overflow list goes there)
     if (need > sc.sort_tmp_bytes) {
         if (sc.sort_tmp) (void) hipFree(sc.sort_tmp);
@@ -355,7 +370,10 @@ static int back_sort(ScanCtx &x, size_t n_sort, const unsigned long long *n_dev,
         sc.sort_tmp_bytes = need;
     }
     size_t have = sc.sort_tmp_bytes;
-    if ((rc = sort_hit_pairs(sc.sort_tmp, &have, sc.keys, sc.keys_sorted, sc.vals, x.raw->d_score, n_sort, sort_begin, x.g.end_bit, c->stream))) return rc;
+    bool done = false;
+    if (counts && (rc = sort_hit_pairs_counted(sc.sort_tmp, &have, sc.keys, sc.keys_sorted, sc.vals, x.raw->d_score, n_sort, sort_begin, x.g.end_bit, counts,
+                                               &done, c->stream))) return rc;
+    if (!done && (rc = sort_hit_pairs(sc.sort_tmp, &have, sc.keys, sc.keys_sorted, sc.vals, x.raw->d_score, n_sort, sort_begin, x.g.end_bit, c->stream))) return rc;
     if (x.g.pbits == 0 && sort_begin) return launch_sort_fixup(sc.keys_sorted, x.raw->d_score, (int64_t) n_sort, n_dev, c->stream);
     return MS_OK;
 }
@@ -462,7 +480,8 @@ static int scan_queue_predicted(ScanCtx &x, size_t n_pred, bool queue_only) {
         const BucketOut B = scan_bucket_out(x);
         if ((rc = launch_bucket_plan(x.bk_w, x.bk_mu, n_pred, x.bk_need, x.bk_cap_max, sc.bucket_tab, x.c->stream))) return rc;
         if ((rc = scan_front(x, scan_hit_out(x), &B))) return rc;
-        if ((rc = launch_fill_tail_buckets(sc.keys, sc.bucket_tab, n_pred, sc.counters + 1, sc.counters + 3, x.c->stream))) return rc;
+        if ((rc = launch_fill_tail_buckets(sc.keys, sc.bucket_tab, n_pred, sc.counters + 1, sc.counters + 3, B.hist, B.hist_places,
+                                           x.g.end_bit - (x.bk_L + 8) - 8 * (B.hist_places - 1), x.c->stream))) return rc;
     } else {
         if ((rc = scan_front(x, scan_hit_out(x)))) return rc;
         if ((rc = launch_fill_tail(sc.keys, sc.counters + 1, n_pred, x.c->stream))) return rc;
