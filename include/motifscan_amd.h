@@ -96,6 +96,10 @@
  *                         on the device
  *   ms_best_count_passing no reference counterpart: the number of regions whose best score passes each of several cutoffs per motif --
  *                         what ms_result_region_counts gives for one ms_scan per cutoff, from ONE best-site scan
+ *   ms_scan_affinity / ms_affinity_*
+ *                         no reference counterpart: the sum of exp(raw window score) over ALL windows of a region -- total binding
+ *                         affinity (TRAP, AME's avg / sum scoring) per (motif, region) cell, dense, without a hit per window;
+ *                         ms_affinity_rank_sum ranks it as ms_best_rank_sum ranks the best score
  */
 #ifndef MOTIFSCAN_AMD_H
 #define MOTIFSCAN_AMD_H
@@ -535,6 +539,51 @@ int ms_best_rank_sum(const ms_best *a, const uint8_t *sel_a /* [Ra] or NULL */,
 int ms_best_count_passing(const ms_best *b, const uint8_t *sel /* [R] or NULL */,
                           const double *cutoffs /* [m1 - m0][n_cut] */, int32_t n_cut, int32_t m0, int32_t m1,
                           int64_t *counts /* [m1 - m0][n_cut] */, double *device_ms /* or NULL */);
+
+/* ---- total binding affinity: the summed likelihood ratio of every (motif, region) cell, dense (ms_affinity.hip) ---------- */
+/* The PWMs are natural-log odds, so a window's raw sum is its log likelihood ratio.  For motif m of width W and region r of length L the
+ * TERMS of the cell are the pairs (window start pos = 0 .. L - W, strand of strand_mask).  With max_n >= 0 only the windows that hold at
+ * most max_n non-ACGT bases among their own W bases are terms (the bits of the non-ACGT mask, IUPAC letters included, as in
+ * ms_scan_score_histogram); max_n = -1 takes every window, as the scan does.  raw(term) is the raw sum exactly as ms_scan / ms_scan_best
+ * form it: columns in order, forward M[b][c], reverse M[3 - b][W - 1 - c] at the same step, +0.0 for a base that adds nothing.  max_raw is
+ * NOT read and nothing is divided.  Per cell, four planes [n_pwms][n_seqs]:
+ *     n_terms   int32    the number of terms; a term of raw = -inf counts.  0 for L < W or when max_n removes every window.
+ *     peak      double   the greatest raw over the terms, bit-exact.  NaN if n_terms == 0.  May be -inf.
+ *     sum       double   S = sum over the terms of exp(scale * (raw - peak)); a term of raw = -inf adds 0.  S = 0 if peak is -inf or
+ *                        n_terms == 0; otherwise 1 <= S <= n_terms up to rounding.
+ *     log_mean  double   scale * peak + log(sum / n_terms), each operation rounded once: the log of the region's MEAN likelihood ratio
+ *                        (+ log(n_terms): of its total binding affinity).  -inf if peak == -inf, NaN if n_terms == 0.  The plane
+ *                        ms_affinity_rank_sum ranks.
+ * A motif with an entry that is NaN or +inf has an EMPTY ROW everywhere: n_terms = 0, peak = NaN, sum = 0, log_mean = NaN.  A motif whose
+ * max_raw is <= 0 (an all-negative matrix) IS scored, unlike in ms_scan_best: its likelihood ratios are well defined.  scale must be
+ * finite and > 0: the lambda of TRAP-like models; 1.0 for natural-log odds, ln 2 for a log2 matrix.  The cutoffs of the PWM set are not read.
+ * ACCURACY of sum against the exact sum of the exact exponentials of the float64 raw sums: within 16 (n_terms + 8) 2^-53 of it, relative
+ * (DESIGN.md has the derivation; n_terms and peak are exact).
+ * DETERMINISM: all four planes are the same bytes on every run, and a cell's bytes depend only on its motif, its region's bases,
+ * strand_mask, scale and max_n -- not on which other regions or motifs share the call.  The reduction order is fixed: a lane takes its
+ * windows in order, the wave is folded by a fixed butterfly, the segments of a long region in a fixed order; no floating-point atomics.
+ * Work memory: a region of more than ms_debug_affinity_dims()[0] bases costs 24 bytes per (motif, segment) for the duration of the call.
+ * MS_ERR_RUNTIME ("no CPU fallback") without a device, before anything else.  MS_ERR_INVALID: NULL handles, a strand mask outside 1..3,
+ * flags != 0, scale not finite or <= 0, max_n < -1, a region of 2^31 bases or more.  MS_ERR_NOMEM: the 28 bytes per cell plus the partials
+ * do not fit (nothing has been launched then).  n_seqs = 0 and n_pwms = 0 are valid and give an empty result. */
+typedef struct ms_affinity ms_affinity;
+int  ms_scan_affinity(const ms_pwmset *pwms, const ms_seqset *seqs, int strand_mask, double scale, int32_t max_n, uint32_t flags /* 0 */,
+                      ms_affinity **out);
+int  ms_affinity_shape(const ms_affinity *a, int32_t *n_pwms, int64_t *n_seqs);
+/* Motifs m0 <= m < m1 into host buffers [(m1 - m0)][n_seqs] row-major; any pointer may be NULL.  MS_ERR_INVALID for m0 < 0, m1 > n_pwms, m0 > m1. */
+int  ms_affinity_cells(const ms_affinity *a, int32_t m0, int32_t m1, double *peak, double *sum, int32_t *n_terms, double *log_mean);
+/* Device pointers of the full [n_pwms][n_seqs] planes, valid until free; any pointer may be NULL. */
+int  ms_affinity_cells_device(const ms_affinity *a, void **d_peak, void **d_sum, void **d_n_terms, void **d_log_mean);
+/* Device time of the call that made the result: first launch -> last kernel done. */
+int  ms_affinity_device_ms(const ms_affinity *a, double *ms);
+void ms_affinity_free(ms_affinity *a);
+/* ms_best_rank_sum's semantics, outputs and errors exactly, applied to the log_mean planes of two affinity results (they may be the same
+ * handle): a NaN cell (no term) ranks below every number and ties with every other NaN cell; -inf is an ordinary number. */
+int  ms_affinity_rank_sum(const ms_affinity *a, const uint8_t *sel_a /* [Ra] or NULL */,
+                          const ms_affinity *b, const uint8_t *sel_b /* [Rb] or NULL */,
+                          int32_t m0, int32_t m1, uint32_t flags /* 0 */,
+                          int64_t *u2 /* [m1 - m0] */, uint64_t *ties /* [m1 - m0][2]: low word, high word */,
+                          int64_t *n /* [2]: na, nb; may be NULL */, double *device_ms /* or NULL */);
 
 /* The hit arrays in COMPACT form in library-owned pinned host memory: coord[i] = seq_idx << 32 | pos << 1 | (strand - 1),
  * score[i] -- 16 bytes per hit on the host link instead of 25.  Needs seq_idx < 2^32 and pos < 2^31 (MS_ERR_INVALID

@@ -149,6 +149,13 @@ int ms_debug_ranksum_dims(int32_t out[8]);
  * in this process, 0 gives it back to the library.  *previous (may be NULL) = the value before.  The result does not depend on it.  Needs no GPU. */
 int ms_debug_ranksum_budget(int64_t elems, int64_t *previous);
 
+/* The sizes at which ms_scan_affinity changes path, as constants of the build (it walks as ms_scan_best does): out[0] the window starts per
+ * segment (a region of more takes several, folded from partials); out[1] the widest motif whose table rides an LDS tile (wider ones read it
+ * from HBM); out[2] the table entries (motif columns x 4) of one LDS tile -- a motif set of more starts a second tile; out[3] the waves
+ * (= segments) per block; out[4] the strips of 64 window starts per segment; out[5] the bytes of a segment's partial; out[6], out[7]
+ * reserved, 0.  Tests size their boundary cases from here.  Needs no GPU. */
+int ms_debug_affinity_dims(int32_t out[8]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -214,6 +214,14 @@ def lib():
         "ms_best_count_passing": (c_int, [vp, pu8, pd, c_i32, c_i32, c_i32, pi64, pd]),
         "ms_debug_ranksum_dims": (c_int, [pi32]),
         "ms_debug_ranksum_budget": (c_int, [c_i64, pi64]),
+        "ms_scan_affinity": (c_int, [vp, vp, c_int, ctypes.c_double, c_i32, c_u32, pvp]),
+        "ms_affinity_shape": (c_int, [vp, pi32, pi64]),
+        "ms_affinity_cells": (c_int, [vp, c_i32, c_i32, pd, pd, pi32, pd]),
+        "ms_affinity_cells_device": (c_int, [vp, pvp, pvp, pvp, pvp]),
+        "ms_affinity_device_ms": (c_int, [vp, pd]),
+        "ms_affinity_free": (None, [vp]),
+        "ms_affinity_rank_sum": (c_int, [vp, pu8, vp, pu8, c_i32, c_i32, c_u32, pi64, ctypes.POINTER(ctypes.c_uint64), pi64, pd]),
+        "ms_debug_affinity_dims": (c_int, [pi32]),
         "ms_debug_key_layout": (c_int, [c_i64, c_i64, c_i64, c_i32, c_i32, pi32, pi32]),
         "ms_scan_score_histogram": (c_int, [vp, vp, c_int, c_u32, pd, pd, c_i32, c_i32, vp, pd]),
         "ms_debug_scorehist_dims": (c_int, [pi32]),
@@ -1151,6 +1159,23 @@ class AlleleScan:
     __del__ = close
 
 
+def _rank_sum(fn, a, b, sel_a, sel_b, m0, m1, timing):
+    """One rank-sum call (ms_best_rank_sum / ms_affinity_rank_sum: the same signature) on two result objects of one kind."""
+    if a.h is None or b.h is None:
+        raise ValueError("the result is closed")
+    m0, m1 = int(m0), (a.n_pwms if m1 is None else int(m1))
+    rows = max(m1 - m0, 0)
+    sa, pa = BestSites._selection(sel_a, a.n_seqs)
+    sb, pb = BestSites._selection(sel_b, b.n_seqs)
+    u2, ties, n, ms = np.zeros(rows, dtype=np.int64), np.zeros((rows, 2), dtype=np.uint64), np.zeros(2, dtype=np.int64), ctypes.c_double()
+    check(fn(a.h, pa, b.h, pb, m0, m1, 0, ptr(u2, ctypes.c_int64), ptr(ties, ctypes.c_uint64), ptr(n, ctypes.c_int64), ctypes.byref(ms)))
+    if rows == 0:                                          # (the library leaves its outputs alone for an empty range)
+        n[:] = (a.n_seqs if sa is None else int(sa.sum()), b.n_seqs if sb is None else int(sb.sum()))
+    if timing is not None:
+        timing["device_ms"] = ms.value
+    return u2, [int(lo) | (int(hi) << 64) for lo, hi in ties.tolist()], int(n[0]), int(n[1])
+
+
 class BestSites:
     """The result of one ms_scan_best call: the best-scoring window of every (motif, region) cell (include/motifscan_amd.h).
     .score (float64), .pos (int32, relative to the region start) and .strand (int8: 1 '+', 2 '-') are (P, R) numpy arrays, copied from the
@@ -1218,20 +1243,7 @@ class BestSites:
     def rank_sum(self, other, sel=None, sel_other=None, m0=0, m1=None, timing=None):
         """ms_best_rank_sum of this matrix's selected regions (group A) against `other`'s (group B; may be self): (u2 int64 [m1 - m0],
         ties as a list of Python ints, na, nb).  The matrices stay on the device.  timing: a dict that receives 'device_ms'."""
-        if self.h is None or other.h is None:
-            raise ValueError("the result is closed")
-        m0, m1 = self._motif_range(m0, m1)
-        rows = max(m1 - m0, 0)
-        sa, pa = self._selection(sel, self.n_seqs)
-        sb, pb = self._selection(sel_other, other.n_seqs)
-        u2, ties, n, ms = np.zeros(rows, dtype=np.int64), np.zeros((rows, 2), dtype=np.uint64), np.zeros(2, dtype=np.int64), ctypes.c_double()
-        check(lib().ms_best_rank_sum(self.h, pa, other.h, pb, m0, m1, 0, ptr(u2, ctypes.c_int64), ptr(ties, ctypes.c_uint64), ptr(n, ctypes.c_int64),
-                                     ctypes.byref(ms)))
-        if rows == 0:                                      # (the library leaves its outputs alone for an empty range)
-            n[:] = (self.n_seqs if sa is None else int(sa.sum()), other.n_seqs if sb is None else int(sb.sum()))
-        if timing is not None:
-            timing["device_ms"] = ms.value
-        return u2, [int(lo) | (int(hi) << 64) for lo, hi in ties.tolist()], int(n[0]), int(n[1])
+        return _rank_sum(lib().ms_best_rank_sum, self, other, sel, sel_other, m0, m1, timing)
 
     def count_passing(self, cutoffs, sel=None, m0=0, m1=None, timing=None):
         """ms_best_count_passing: int64 [m1 - m0][K], the selected regions whose best score passes cutoffs[row][k] by ms_scan's hit rule.
@@ -1270,6 +1282,96 @@ def scan_best(pwms, seqs, strand_mask=3, flags=0):
     h = ctypes.c_void_p()
     check(lib().ms_scan_best(pwms.h, seqs.h, strand_mask, int(flags), ctypes.byref(h)))
     return BestSites(h)
+
+
+class Affinity:
+    """The result of one ms_scan_affinity call: the summed likelihood ratio of every (motif, region) cell (include/motifscan_amd.h).
+    .peak, .sum, .log_mean (float64) and .n_terms (int32) are (P, R) numpy arrays, copied from the device the first time they are
+    read; a cell without a term holds NaN / 0 / NaN / 0.  The object owns the device planes until close(): keep it alive while
+    device_pointers() are in use."""
+
+    def __init__(self, handle):
+        self.h = handle
+        p, r = ctypes.c_int32(), ctypes.c_int64()
+        check(lib().ms_affinity_shape(self.h, ctypes.byref(p), ctypes.byref(r)))
+        self.n_pwms, self.n_seqs = p.value, r.value
+        self._full = None
+
+    @property
+    def shape(self):
+        return (self.n_pwms, self.n_seqs)
+
+    def cells(self, m0=0, m1=None):
+        """(peak, sum, n_terms, log_mean) of motifs m0 <= m < m1 as fresh (m1 - m0, R) arrays."""
+        if self.h is None:
+            raise ValueError("the result is closed")
+        m1 = self.n_pwms if m1 is None else int(m1)
+        m0 = int(m0)
+        if m0 < 0 or m1 > self.n_pwms or m0 > m1:
+            raise ValueError(f"motif range [{m0}, {m1}) outside [0, {self.n_pwms})")
+        shape = (m1 - m0, self.n_seqs)
+        peak, total, log_mean = (np.zeros(shape, dtype=np.float64) for _ in range(3))
+        n_terms = np.zeros(shape, dtype=np.int32)
+        check(lib().ms_affinity_cells(self.h, m0, m1, ptr(peak, ctypes.c_double), ptr(total, ctypes.c_double), ptr(n_terms, ctypes.c_int32),
+                                      ptr(log_mean, ctypes.c_double)))
+        return peak, total, n_terms, log_mean
+
+    def _arrays(self):
+        if self._full is None:
+            self._full = self.cells()
+        return self._full
+
+    peak = property(lambda self: self._arrays()[0])
+    sum = property(lambda self: self._arrays()[1])
+    n_terms = property(lambda self: self._arrays()[2])
+    log_mean = property(lambda self: self._arrays()[3])
+
+    def device_pointers(self):
+        """(peak, sum, n_terms, log_mean) device addresses of the full (P, R) planes, valid until close()."""
+        a = [ctypes.c_void_p() for _ in range(4)]
+        check(lib().ms_affinity_cells_device(self.h, *[ctypes.byref(x) for x in a]))
+        return tuple(x.value for x in a)
+
+    def device_ms(self):
+        ms = ctypes.c_double()
+        check(lib().ms_affinity_device_ms(self.h, ctypes.byref(ms)))
+        return ms.value
+
+    def rank_sum(self, other, sel=None, sel_other=None, m0=0, m1=None, timing=None):
+        """ms_affinity_rank_sum of this result's selected regions (group A) against `other`'s (group B; may be self), on the log_mean
+        planes: (u2 int64 [m1 - m0], ties as a list of Python ints, na, nb) -- BestSites.rank_sum's form.  The planes stay on the device."""
+        return _rank_sum(lib().ms_affinity_rank_sum, self, other, sel, sel_other, m0, m1, timing)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ms_affinity_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+
+def scan_affinity(pwms, seqs, strand_mask=3, scale=1.0, max_n=-1, flags=0):
+    """ms_scan_affinity: the summed likelihood ratio of every (motif, region) cell of a PwmSet x SeqSet (the set's cutoffs are not read).
+    scale: finite and > 0 (1.0 for natural-log odds); max_n >= 0: only windows of at most max_n non-ACGT bases are terms.
+    Returns an Affinity."""
+    from .affinity import check_args
+    strand_mask = int(strand_mask)
+    if strand_mask not in (1, 2, 3):
+        raise ValueError(f"invalid strand mask {strand_mask!r} (1 '+', 2 '-', 3 both)")
+    if int(flags) != 0:
+        raise ValueError(f"unknown affinity scan flags {flags!r}")
+    scale, max_n = check_args(scale, max_n)
+    h = ctypes.c_void_p()
+    check(lib().ms_scan_affinity(pwms.h, seqs.h, strand_mask, scale, max_n, int(flags), ctypes.byref(h)))
+    return Affinity(h)
+
+
+def affinity_dims():
+    """ms_debug_affinity_dims: dict(segment_windows, tile_max_width, tile_entries, waves, strips, part_bytes) -- the sizes at which
+    ms_scan_affinity changes path.  Constants of the build; no device."""
+    out = np.zeros(8, dtype=np.int32)
+    check(lib().ms_debug_affinity_dims(ptr(out, ctypes.c_int32)))
+    return dict(zip(("segment_windows", "tile_max_width", "tile_entries", "waves", "strips", "part_bytes"), out.tolist()))
 
 
 def histogram_binning(n_pwms, lo, hi, n_bins):

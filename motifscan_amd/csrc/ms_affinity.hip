@@ -1,0 +1,451 @@
+// ms_affinity.hip -- the summed likelihood ratio of every (motif, region) cell (ms_scan_affinity): total binding affinity, dense.
+//
+// For motif m of width W and region r of length L the TERMS of the cell are the (window start pos = 0 .. L - W, strand of the mask)
+// pairs, with max_n >= 0 only the windows of at most max_n non-ACGT bases.  raw(term) is the raw sum exactly as ms_scan and ms_scan_best
+// form it (columns 0 .. W - 1, forward M[b][c], reverse M[3 - b][W - 1 - c] at the same step, +0.0 for a base that adds nothing); max_raw
+// is not read and nothing is divided: the PWMs are natural-log odds, so raw IS the window's log likelihood ratio.  Per cell
+//     n_terms   the number of terms (a term of raw = -inf counts)
+//     peak      the greatest raw over the terms                                       (bit-exact; NaN without a term; may be -inf)
+//     sum       S = sum over the terms of exp(scale * (raw - peak)); raw = -inf adds 0
+//     log_mean  scale * peak + log(S / n_terms), each operation rounded               (the plane ms_affinity_rank_sum ranks)
+//
+// Mapping: ms_best.hip's walk with another reduction at its end (ms_best_dev.h holds what the two share).  A wave owns a SEGMENT of
+// kBestSegWindows window starts of a region, a block kBestWaves segments and one tile of motif tables in LDS; a lane keeps the words of
+// its kBestStrips window starts in registers and walks the tile's motifs over them.
+//
+// The reducer is an ONLINE rescale: a lane's state is (peak, S, n) and a term x that is a number
+//     x >  peak:   S = S * exp(scale * (peak - x)) + 1;   peak = x        (from peak = -inf: S = 0 * 0 + 1)
+//     x <= peak:   S = S + exp(scale * (x - peak))
+// -- ONE fp64 exp per term either way, its argument <= 0, no second pass over the strips and no 16 raw sums held in registers (the strip
+// loop is not unrolled: ms_best_dev.h).  A term of raw = -inf only counts: it never meets the subtraction, so (-inf) - (-inf) is never
+// formed.  A lane without a window in a strip, a strip past the region's last window and a window that max_n drops add neither a term
+// nor a peak candidate.
+//
+// Order (the bytes are the same on every run, and a cell's bytes depend on nothing but its own motif, bases and arguments): a lane
+// takes its terms in window order, '+' before '-'; then the wave's peak is the maximum over the lanes (exact, a butterfly of maxima),
+// every lane rescales its S to it ONCE -- a lane that holds the wave's peak keeps its S untouched --, and S and n are added across the wave
+// by a fixed xor butterfly (a + b == b + a: both partners of a step hold the same sum).  A region of one segment writes its cell; a
+// longer one writes a partial (peak, S, n) per segment, and affinity_reduce_kernel folds a cell's partials: lane l takes segments
+// l, l + 64, ... in ascending order by the same online rule -- S_a * exp(scale * (peak_a - peak)) + S_b * exp(scale * (peak_b - peak)),
+// the factor of the greater peak being exactly 1 -- and the wave is reduced as above.  A partial of S = 0 (no term, or -inf terms only)
+// adds its count and nothing else.  No atomics anywhere.
+//
+// Motifs wider than kBestTileMaxW read their table from HBM (score_window); a motif with a NaN or +inf entry is never scored and its
+// row is filled with the "no term" cell (n_terms 0, peak NaN, sum 0, log_mean NaN).  A motif whose max_raw is <= 0 IS scored.
+#include <algorithm>
+#include <cmath>
+#include <limits>
+#include <memory>
+
+#include "ms_best_dev.h"
+#include "ms_device.h"
+#include "ms_handles.h"
+
+namespace ms {
+
+namespace {
+
+struct AffPart {                                         // a segment's share of one cell: 24 bytes
+    double peak;                                         // -inf: no term that is a number
+    double sum;
+    int32_t n;
+    int32_t reserved;
+};
+
+struct AffArgs {
+    const uint32_t *codes, *nmask;
+    const int64_t *offsets;                              // [R + 1]
+    int64_t R;
+    const int64_t *seg_first;                            // [R + 1] first segment of the region; nullptr: one segment per region
+    const int64_t *part_first;                           // [R + 1] first partial of the region; nullptr: no partials
+    int64_t n_seg, n_part;
+    const int32_t *tile_first;                           // [tiles + 1] into mot
+    const int32_t *mot;                                  // the scored motifs, tile after tile
+    DevPwm Pw;
+    int strand_mask;
+    int32_t max_n;
+    double scale;
+    double *peak, *sum, *log_mean;                       // [P][R]
+    int32_t *n_terms;
+    AffPart *part;                                       // [P][n_part]
+};
+
+// one term of raw sum x into a lane's (peak, S, n); counted: the window is a term at all.  Wave-uniform control flow: exp is one call.
+__device__ __forceinline__ void aff_term(bool counted, double x, double scale, double &peak, double &S, int32_t &n) {
+    n += counted ? 1 : 0;
+    const bool live = counted && x > -std::numeric_limits<double>::infinity();      // (x is never NaN or +inf: no such entry is scored)
+    const bool up = live && x > peak;
+    const double d = live ? (up ? peak - x : x - peak) : 0.0;                       // <= 0; -inf on a lane's first number
+    const double e = exp(scale * d);
+    S = live ? (up ? S * e + 1.0 : S + e) : S;
+    peak = up ? x : peak;
+}
+
+// (pp, ps, pn) of an earlier reduction into (peak, S, n), by the same rule; ps > 0 implies a finite pp
+__device__ __forceinline__ void aff_fold(double pp, double ps, int32_t pn, double scale, double &peak, double &S, int32_t &n) {
+    n += pn;
+    const bool live = ps > 0.0;
+    const bool up = live && pp > peak;
+    const double d = live ? (up ? peak - pp : pp - peak) : 0.0;
+    const double e = d == 0.0 ? 1.0 : exp(scale * d);
+    S = live ? (up ? S * e + ps : S + ps * e) : S;
+    peak = up ? pp : peak;
+}
+
+// the lanes' (peak, S, n) -> the wave's, in every lane
+__device__ __forceinline__ void aff_wave(double scale, double &peak, double &S, int32_t &n) {
+    double wp = peak;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const double o = __shfl_xor(wp, d);
+        wp = o > wp ? o : wp;
+    }
+    const bool shift = S > 0.0 && peak != wp;            // (S > 0: peak is a number, and so is wp)
+    const double e = exp(scale * (shift ? peak - wp : 0.0));
+    S = shift ? S * e : S;
+    peak = wp;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        S += __shfl_xor(S, d);
+        n += __shfl_xor(n, d);
+    }
+}
+
+__device__ __forceinline__ void put_cell(const AffArgs &A, int64_t cell, double peak, double S, int32_t n) {
+    const double ninf = -std::numeric_limits<double>::infinity(), nan = __builtin_nan("");
+    const bool none = n == 0, dead = peak == ninf;
+    A.n_terms[cell] = n;
+    A.peak[cell] = none ? nan : peak;
+    A.sum[cell] = (none || dead) ? 0.0 : S;
+    const double ratio = S / (double) (none ? 1 : n);
+    const double a = A.scale * peak, b = log(ratio);
+    A.log_mean[cell] = none ? nan : (dead ? ninf : a + b);
+}
+
+// grid = (ceil(segments / kBestWaves), tiles).  LDS: the tile's tables in LDS; !LDS: one motif per tile, its table in HBM.
+template <bool LDS>
+__global__ void __launch_bounds__(kBestThreads, 4) affinity_kernel(const AffArgs A, int32_t tile0) {
+    extern __shared__ double2 aff_lds[];                 // [1 + the tile's entries]
+    const int32_t tile = tile0 + (int32_t) blockIdx.y;
+    const int32_t k0 = A.tile_first[tile], k1 = A.tile_first[tile + 1];
+    const int64_t tab0 = A.Pw.tab_off[A.mot[k0]];
+    if (LDS) {
+        const int32_t ml = A.mot[k1 - 1];
+        const int32_t n = (int32_t) (A.Pw.tab_off[ml] - tab0) + A.Pw.width[ml] * 4;
+        dense_stage_tile(aff_lds, A.Pw.tab2 + tab0, n);
+    }
+    const int wave = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+    const int lane = (int) (threadIdx.x & 63u);
+    const int64_t seg = (int64_t) blockIdx.x * kBestWaves + wave;
+    if (seg >= A.n_seg) return;
+    const int64_t r = A.seg_first ? find_region_bsearch(A.seg_first, A.R, seg) : seg;
+    const int64_t s_in = A.seg_first ? seg - A.seg_first[r] : 0;
+    const bool whole = A.seg_first ? A.seg_first[r + 1] - A.seg_first[r] == 1 : true;
+    const int64_t beg = A.offsets[r], L = A.offsets[r + 1] - beg;
+    const int64_t p0 = s_in * kBestSegWindows;           // the segment's first window start
+
+    uint64_t cw[kBestStrips];
+    uint32_t nw[kBestStrips];
+    dense_segment_words(A.codes, A.nmask, beg, L, p0, lane, cw, nw);
+
+    for (int32_t k = k0; k < k1; k++) {
+        const int32_t m = A.mot[k];
+        const int W = A.Pw.width[m];
+        const int64_t tab_m = A.Pw.tab_off[m];
+        const uint32_t tb = 1u + (uint32_t) (tab_m - tab0);
+        const int64_t last = L - W;                       // the region's last window start
+        double peak = -std::numeric_limits<double>::infinity(), S = 0.0;
+        int32_t n = 0;
+#pragma unroll 1
+        for (int s = 0; s < kBestStrips; s++) {
+            if (p0 + s * 64 > last) break;                // (wave-uniform) no window of this strip, or of a later one, fits the region
+            const int64_t pos = p0 + s * 64 + lane;
+            const bool valid = pos <= last;
+            double fwd = 0.0, rev = 0.0;
+            int n_non = 0;
+            dense_strip_sums<LDS, true>(aff_lds, tb, A.Pw.tab2 + tab_m, A.codes, A.nmask, W, beg + pos, valid, s, cw, nw, fwd, rev, n_non);
+            const bool counted = valid && (A.max_n < 0 || n_non <= A.max_n);
+            if (A.strand_mask & 1) aff_term(counted, fwd, A.scale, peak, S, n);      // '+' then '-'
+            if (A.strand_mask & 2) aff_term(counted, rev, A.scale, peak, S, n);
+        }
+        aff_wave(A.scale, peak, S, n);
+        if (lane == 0) {
+            if (whole) put_cell(A, (int64_t) m * A.R + r, peak, S, n);
+            else {
+                AffPart p;
+                p.peak = peak; p.sum = S; p.n = n; p.reserved = 0;
+                A.part[(int64_t) m * A.n_part + A.part_first[r] + s_in] = p;
+            }
+        }
+    }
+}
+
+// grid = (regions of more than one segment, ceil(scored motifs / 4)): a wave folds the partials of one (motif, region), lane l the
+// segments l, l + 64, ... in ascending order
+__global__ void __launch_bounds__(256) affinity_reduce_kernel(const AffArgs A, const int64_t *__restrict__ long_regions, int32_t k_first, int32_t n_mot) {
+    const int32_t k = k_first + (int32_t) blockIdx.y * 4 + (int32_t) (threadIdx.x >> 6);
+    if (k >= n_mot) return;
+    const int lane = (int) (threadIdx.x & 63u);
+    const int32_t m = A.mot[k];
+    const int64_t r = long_regions[blockIdx.x];
+    const int64_t n_seg = A.seg_first[r + 1] - A.seg_first[r];
+    const AffPart *__restrict__ part = A.part + (int64_t) m * A.n_part + A.part_first[r];
+    double peak = -std::numeric_limits<double>::infinity(), S = 0.0;
+    int32_t n = 0;
+    const int64_t trips = (n_seg + 63) / 64;              // (wave-uniform: exp is one call for the wave)
+    for (int64_t t = 0; t < trips; t++) {
+        const int64_t s = t * 64 + lane;
+        const bool in = s < n_seg;
+        AffPart p;
+        p.peak = peak; p.sum = 0.0; p.n = 0; p.reserved = 0;
+        if (in) p = part[s];
+        aff_fold(p.peak, p.sum, p.n, A.scale, peak, S, n);
+    }
+    aff_wave(A.scale, peak, S, n);
+    if (lane == 0) put_cell(A, (int64_t) m * A.R + r, peak, S, n);
+}
+
+// grid = (ceil(R / 256), motifs that are not scored): their rows hold no term
+__global__ void __launch_bounds__(256) affinity_fill_kernel(const AffArgs A, const int32_t *__restrict__ motifs) {
+    const int64_t r = (int64_t) blockIdx.x * 256 + threadIdx.x;
+    if (r >= A.R) return;
+    put_cell(A, (int64_t) motifs[blockIdx.y] * A.R + r, 0.0, 0.0, 0);
+}
+
+size_t up256(size_t x) { return (x + 255) & ~(size_t) 255; }
+
+// a motif with a NaN or +inf entry has an empty row; every other one is scored, max_raw <= 0 included
+bool affinity_scored(const ms_pwmset *p, int32_t m) {
+    const double *v = p->values.data() + p->val_off[(size_t) m];
+    const int64_t n = 4 * (int64_t) p->widths[(size_t) m];
+    for (int64_t i = 0; i < n; i++)
+        if (std::isnan(v[i]) || v[i] == std::numeric_limits<double>::infinity()) return false;
+    return true;
+}
+
+bool have_device() {
+    int n_dev = 0;
+    if (ms_device_count(&n_dev) != MS_OK || n_dev <= 0) { set_error("no usable HIP device; libmotifscan_amd has no CPU fallback"); return false; }
+    return true;
+}
+
+}  // namespace
+
+}  // namespace ms
+
+using namespace ms;
+
+extern "C" {
+
+int ms_debug_affinity_dims(int32_t out[8]) {
+    if (!out) { set_error("NULL output"); return MS_ERR_INVALID; }
+    out[0] = kBestSegWindows;
+    out[1] = kBestTileMaxW;
+    out[2] = kBestTileEntries;
+    out[3] = kBestWaves;
+    out[4] = kBestStrips;
+    out[5] = (int32_t) sizeof(AffPart);
+    out[6] = 0;
+    out[7] = 0;
+    return MS_OK;
+}
+
+void ms_affinity_free(ms_affinity *a) {
+    if (!a) return;
+    if (a->block) {
+        (void) hipSetDevice(a->device);
+        DeviceCtx *c = nullptr;
+        if (get_ctx(a->device, &c) == MS_OK) pool_free(c, a->block, a->block_bytes); else (void) hipFree(a->block);
+    }
+    delete a;
+}
+
+int ms_scan_affinity(const ms_pwmset *pwms_c, const ms_seqset *seqs, int strand_mask, double scale, int32_t max_n, uint32_t flags, ms_affinity **out) {
+    if (!out) { set_error("out is NULL"); return MS_ERR_INVALID; }
+    *out = nullptr;
+    if (!have_device()) return MS_ERR_RUNTIME;
+    if (!pwms_c || !seqs) { set_error("NULL handle"); return MS_ERR_INVALID; }
+    if (strand_mask < 1 || strand_mask > 3) { set_error("invalid strand mask %d (1 '+', 2 '-', 3 both)", strand_mask); return MS_ERR_INVALID; }
+    if (flags != 0u) { set_error("unknown affinity scan flags 0x%x", flags); return MS_ERR_INVALID; }
+    if (!(std::isfinite(scale) && scale > 0.0)) { set_error("scale must be a finite number > 0"); return MS_ERR_INVALID; }
+    if (max_n < -1) { set_error("max_n must be >= -1 (-1: every window is a term)"); return MS_ERR_INVALID; }
+    ms_pwmset *pwms = const_cast<ms_pwmset *>(pwms_c);
+    const int32_t P = pwms->P;
+    const int64_t R = seqs->R;
+    const int64_t *off = seqs->offsets.data();
+    for (int64_t r = 0; r < R; r++)
+        if (off[r + 1] - off[r] >= (1LL << 31)) {
+            set_error("region %lld has %lld bases: n_terms is 32-bit, cut it into regions of fewer than 2^31", (long long) r, (long long) (off[r + 1] - off[r]));
+            return MS_ERR_INVALID;
+        }
+    DeviceCtx *c;
+    int rc = get_ctx(seqs->device, &c);
+    if (rc) return rc;
+    std::unique_ptr<ms_affinity> res(new (std::nothrow) ms_affinity());
+    if (!res) { set_error("out of host memory"); return MS_ERR_NOMEM; }
+    res->device = c->device;
+    res->P = P;
+    res->R = R;
+
+    // ---- the plan, on the host: segments of the regions, tiles of the motifs (dense_plan, ms_best_dev.h)
+    DensePlan plan;
+    try {
+        dense_plan(pwms, off, R, [&](int32_t m) { return affinity_scored(pwms, m); }, &plan);
+    } catch (const std::bad_alloc &) { set_error("out of host memory"); return MS_ERR_NOMEM; }
+    const int32_t n_lds_tiles = (int32_t) plan.tile_first.size() - 1, n_wide = (int32_t) plan.wide_first.size() - 1, n_mot = (int32_t) plan.mot.size();
+    const int64_t n_long = (int64_t) plan.long_regions.size(), n_seg = plan.n_seg, n_part = plan.n_part;
+    if (n_long > 0x7FFFFFFFLL || (n_seg + kBestWaves - 1) / kBestWaves > 0x7FFFFFFFLL) { set_error("too many segments for one launch"); return MS_ERR_INVALID; }
+
+    // ---- 28 bytes per cell, 24 per partial: both blocks are allocated before anything is launched, and a failure there is the MS_ERR_NOMEM
+    // of the header (the test here only keeps the byte counts below inside size_t)
+    if (28.0 * (double) P * (double) R + (double) sizeof(AffPart) * (double) P * (double) n_part >= 0.5 * (double) std::numeric_limits<size_t>::max()) {
+        set_error("%d x %lld cells do not fit the device", P, (long long) R);
+        return MS_ERR_NOMEM;
+    }
+    const size_t cells = (size_t) P * (size_t) R, cz = std::max<size_t>(cells, 1);
+    std::lock_guard<std::mutex> lk_dev(c->mu);
+    std::lock_guard<std::mutex> lk_pwm(pwms->mu);
+    MS_HIP(hipSetDevice(c->device));
+    {
+        void *blk = nullptr;
+        size_t got = 0;
+        if ((rc = pool_alloc(c, 3 * up256(8 * cz) + up256(4 * cz), &blk, &got))) return rc;
+        res->block = blk;
+        res->block_bytes = got;
+        char *p = static_cast<char *>(blk);
+        res->d_peak = reinterpret_cast<double *>(p); p += up256(8 * cz);
+        res->d_sum = reinterpret_cast<double *>(p); p += up256(8 * cz);
+        res->d_log_mean = reinterpret_cast<double *>(p); p += up256(8 * cz);
+        res->d_n_terms = reinterpret_cast<int32_t *>(p);
+    }
+    ms_affinity *raw = res.release();
+    if (cells == 0) { *out = raw; return MS_OK; }
+
+    const size_t b_seg = plan.seg_first.empty() ? 0 : up256(8 * plan.seg_first.size()), b_long = up256(8 * std::max<size_t>(plan.long_regions.size(), 1)),
+                 b_mot = up256(4 * std::max<size_t>(plan.mot.size(), 1)), b_tile = up256(4 * plan.tile_first.size()), b_wide = up256(4 * plan.wide_first.size()),
+                 b_skip = up256(4 * std::max<size_t>(plan.skipped.size(), 1)), b_part = up256(sizeof(AffPart) * std::max<size_t>((size_t) P * (size_t) n_part, 1));
+    void *wblk = nullptr;
+    size_t wgot = 0;
+    if ((rc = pool_alloc(c, 2 * b_seg + b_long + b_mot + b_tile + b_wide + b_skip + b_part, &wblk, &wgot))) { ms_affinity_free(raw); return rc; }
+    auto fail = [&](int code) { pool_free(c, wblk, wgot); ms_affinity_free(raw); return code; };
+    auto hip_fail = [&](hipError_t e, const char *what) { set_error("%s failed: %s", what, hipGetErrorString(e)); return fail(e == hipErrorOutOfMemory ? MS_ERR_NOMEM : MS_ERR_RUNTIME); };
+    char *b = static_cast<char *>(wblk);
+    int64_t *d_seg = reinterpret_cast<int64_t *>(b); b += b_seg;
+    int64_t *d_pfirst = reinterpret_cast<int64_t *>(b); b += b_seg;
+    int64_t *d_long = reinterpret_cast<int64_t *>(b); b += b_long;
+    int32_t *d_mot = reinterpret_cast<int32_t *>(b); b += b_mot;
+    int32_t *d_tile = reinterpret_cast<int32_t *>(b); b += b_tile;
+    int32_t *d_wide = reinterpret_cast<int32_t *>(b); b += b_wide;
+    int32_t *d_skip = reinterpret_cast<int32_t *>(b); b += b_skip;
+    AffPart *d_part = reinterpret_cast<AffPart *>(b);
+
+    const hipStream_t st = c->stream;
+    if ((rc = pwmset_upload(pwms, c->device, st))) return fail(rc);
+    if ((rc = seqset_pack_pending(seqs, st))) return fail(rc);
+    const size_t lds = (plan.max_tile + 1) * sizeof(double2);
+    hipError_t he = hipSuccess;
+    if (lds > 48 * 1024) {
+        he = hipFuncSetAttribute(reinterpret_cast<const void *>(affinity_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) ((kBestTileEntries + 1) * sizeof(double2)));
+        if (he != hipSuccess) return hip_fail(he, "raising the LDS limit");
+    }
+    if (!plan.seg_first.empty()) {
+        he = hipMemcpyAsync(d_seg, plan.seg_first.data(), 8 * plan.seg_first.size(), hipMemcpyHostToDevice, st);
+        if (he == hipSuccess) he = hipMemcpyAsync(d_pfirst, plan.part_first.data(), 8 * plan.part_first.size(), hipMemcpyHostToDevice, st);
+        if (he == hipSuccess && n_long > 0) he = hipMemcpyAsync(d_long, plan.long_regions.data(), 8 * plan.long_regions.size(), hipMemcpyHostToDevice, st);
+    }
+    if (he == hipSuccess && n_mot > 0) he = hipMemcpyAsync(d_mot, plan.mot.data(), 4 * plan.mot.size(), hipMemcpyHostToDevice, st);
+    if (he == hipSuccess) he = hipMemcpyAsync(d_tile, plan.tile_first.data(), 4 * plan.tile_first.size(), hipMemcpyHostToDevice, st);
+    if (he == hipSuccess) he = hipMemcpyAsync(d_wide, plan.wide_first.data(), 4 * plan.wide_first.size(), hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && !plan.skipped.empty()) he = hipMemcpyAsync(d_skip, plan.skipped.data(), 4 * plan.skipped.size(), hipMemcpyHostToDevice, st);
+    if (he != hipSuccess) return hip_fail(he, "upload of the plan");
+
+    AffArgs A;
+    A.codes = seqs->d_codes; A.nmask = seqs->d_nmask; A.offsets = seqs->d_offsets; A.R = R;
+    A.seg_first = plan.seg_first.empty() ? nullptr : d_seg;
+    A.part_first = plan.seg_first.empty() ? nullptr : d_pfirst;
+    A.n_seg = n_seg; A.n_part = n_part;
+    A.tile_first = d_tile; A.mot = d_mot;
+    A.Pw = dev_pwm(pwms);
+    A.strand_mask = strand_mask;
+    A.max_n = max_n;
+    A.scale = scale;
+    A.peak = raw->d_peak; A.sum = raw->d_sum; A.log_mean = raw->d_log_mean; A.n_terms = raw->d_n_terms;
+    A.part = d_part;
+
+    (void) hipEventRecord(c->ev[0], st);
+    const unsigned gx = (unsigned) ((n_seg + kBestWaves - 1) / kBestWaves);
+    for (int32_t t0 = 0; t0 < n_lds_tiles; t0 += kBestGridY) {
+        hipLaunchKernelGGL(affinity_kernel<true>, dim3(gx, (unsigned) std::min(kBestGridY, n_lds_tiles - t0)), dim3(kBestThreads), lds, st, A, t0);
+        if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "affinity kernel");
+    }
+    if (n_wide > 0) {
+        AffArgs Aw = A;
+        Aw.tile_first = d_wide;
+        for (int32_t t0 = 0; t0 < n_wide; t0 += kBestGridY) {
+            hipLaunchKernelGGL(affinity_kernel<false>, dim3(gx, (unsigned) std::min(kBestGridY, n_wide - t0)), dim3(kBestThreads), 0, st, Aw, t0);
+            if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "affinity kernel (tables in HBM)");
+        }
+    }
+    for (int32_t kf = 0; n_long > 0 && kf < n_mot; kf += 4 * kBestGridY) {
+        hipLaunchKernelGGL(affinity_reduce_kernel, dim3((unsigned) n_long, (unsigned) std::min(kBestGridY, (n_mot - kf + 3) / 4)), dim3(256), 0, st, A, d_long, kf, n_mot);
+        if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "affinity reduction");
+    }
+    for (size_t u0 = 0; u0 < plan.skipped.size(); u0 += kBestGridY) {
+        hipLaunchKernelGGL(affinity_fill_kernel, dim3((unsigned) ((R + 255) / 256), (unsigned) std::min<size_t>(kBestGridY, plan.skipped.size() - u0)), dim3(256), 0, st, A, d_skip + u0);
+        if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "affinity fill");
+    }
+    (void) hipEventRecord(c->ev[1], st);
+    he = hipStreamSynchronize(st);
+    if (he != hipSuccess) return hip_fail(he, "affinity scan");
+    float ms01 = 0;
+    (void) hipEventElapsedTime(&ms01, c->ev[0], c->ev[1]);
+    raw->device_ms = ms01;
+    pool_free(c, wblk, wgot);
+    *out = raw;
+    return MS_OK;
+}
+
+int ms_affinity_shape(const ms_affinity *a, int32_t *n_pwms, int64_t *n_seqs) {
+    if (!a) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    if (n_pwms) *n_pwms = a->P;
+    if (n_seqs) *n_seqs = a->R;
+    return MS_OK;
+}
+
+int ms_affinity_cells(const ms_affinity *a, int32_t m0, int32_t m1, double *peak, double *sum, int32_t *n_terms, double *log_mean) {
+    if (!a) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    if (m0 < 0 || m1 > a->P || m0 > m1) { set_error("motif range [%d, %d) outside [0, %d)", m0, m1, a->P); return MS_ERR_INVALID; }
+    const size_t at = (size_t) m0 * (size_t) a->R, n = (size_t) (m1 - m0) * (size_t) a->R;
+    if (n == 0) return MS_OK;
+    MS_HIP(hipSetDevice(a->device));
+    if (peak) MS_HIP(hipMemcpy(peak, a->d_peak + at, 8 * n, hipMemcpyDeviceToHost));
+    if (sum) MS_HIP(hipMemcpy(sum, a->d_sum + at, 8 * n, hipMemcpyDeviceToHost));
+    if (n_terms) MS_HIP(hipMemcpy(n_terms, a->d_n_terms + at, 4 * n, hipMemcpyDeviceToHost));
+    if (log_mean) MS_HIP(hipMemcpy(log_mean, a->d_log_mean + at, 8 * n, hipMemcpyDeviceToHost));
+    return MS_OK;
+}
+
+int ms_affinity_cells_device(const ms_affinity *a, void **d_peak, void **d_sum, void **d_n_terms, void **d_log_mean) {
+    if (!a) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    if (d_peak) *d_peak = a->d_peak;
+    if (d_sum) *d_sum = a->d_sum;
+    if (d_n_terms) *d_n_terms = a->d_n_terms;
+    if (d_log_mean) *d_log_mean = a->d_log_mean;
+    return MS_OK;
+}
+
+int ms_affinity_device_ms(const ms_affinity *a, double *ms) {
+    if (!a || !ms) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    *ms = a->device_ms;
+    return MS_OK;
+}
+
+int ms_affinity_rank_sum(const ms_affinity *a, const uint8_t *sel_a, const ms_affinity *b, const uint8_t *sel_b, int32_t m0, int32_t m1, uint32_t flags, int64_t *u2,
+                         uint64_t *ties, int64_t *n, double *device_ms) {
+    if (!have_device()) return MS_ERR_RUNTIME;
+    if (!a || !b) { set_error("NULL handle"); return MS_ERR_INVALID; }
+    const RankPlane pa = {a->device, a->P, a->R, a->d_log_mean}, pb = {b->device, b->P, b->R, b->d_log_mean};
+    return rank_sum_planes("affinity", pa, sel_a, pb, sel_b, m0, m1, flags, u2, ties, n, device_ms);
+}
+
+}  // extern "C"

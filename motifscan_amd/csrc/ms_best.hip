@@ -35,14 +35,7 @@ namespace ms {
 
 namespace {
 
-constexpr int kBestThreads = 512;
-constexpr int kBestWaves = kBestThreads / 64;            // segments per block
-constexpr int kBestStrips = 8;                           // strips of 64 window starts whose words a lane keeps in registers
-constexpr int kBestSegWindows = 64 * kBestStrips;
-constexpr int kBestTileMaxW = 1024;                      // (= kExactTileMaxW, ms_fp64.hip) widest motif whose table fits a tile
-constexpr int kBestTileEntries = kBestTileMaxW * 4;      // 64 KB of tab2 entries per tile (+ the zero entry): two blocks share a CU's 160 KB
-constexpr int kBestGridY = 32768;
-
+// (the sizes of the walk -- kBestThreads ... kBestGridY -- are in ms_best_dev.h: ms_affinity.hip walks the same way)
 struct BestPart {                                        // a segment's best of one motif
     double q;
     int32_t pos;                                         // -1: no winner
@@ -247,47 +240,15 @@ int ms_scan_best(const ms_pwmset *pwms_c, const ms_seqset *seqs, int strand_mask
     res->P = P;
     res->R = R;
 
-    // ---- the plan, on the host: segments of the regions, tiles of the motifs
-    std::vector<int64_t> seg_first, part_first, long_regions;
-    std::vector<int32_t> mot, tile_first, wide_first, uns;
-    int64_t n_seg = R, n_part = 0;
-    size_t max_tile = 0;
+    // ---- the plan, on the host: segments of the regions, tiles of the motifs (dense_plan, ms_best_dev.h)
+    DensePlan plan;
     try {
-        bool any_long = false;
-        for (int64_t r = 0; r < R && !any_long; r++) any_long = off[r + 1] - off[r] > kBestSegWindows;
-        if (any_long) {
-            seg_first.resize((size_t) R + 1);
-            part_first.resize((size_t) R + 1);
-            n_seg = 0;
-            for (int64_t r = 0; r < R; r++) {
-                const int64_t n = std::max<int64_t>(1, (off[r + 1] - off[r] + kBestSegWindows - 1) / kBestSegWindows);
-                seg_first[(size_t) r] = n_seg;
-                part_first[(size_t) r] = n_part;
-                n_seg += n;
-                if (n > 1) { n_part += n; long_regions.push_back(r); }
-            }
-            seg_first[(size_t) R] = n_seg;
-            part_first[(size_t) R] = n_part;
-        }
-        // LDS tiles first: runs of consecutive scorable motifs of <= kBestTileMaxW columns whose entries fit a tile; then one tile per wider motif
-        tile_first.push_back(0);
-        size_t in_tile = 0;
-        int32_t prev = -2;
-        for (int32_t m = 0; m < P; m++) {
-            if (!scorable(pwms, m)) { uns.push_back(m); continue; }
-            const size_t e = (size_t) pwms->widths[(size_t) m] * 4;
-            if (pwms->widths[(size_t) m] > kBestTileMaxW) continue;
-            if (in_tile > 0 && (prev != m - 1 || in_tile + e > (size_t) kBestTileEntries)) { tile_first.push_back((int32_t) mot.size()); in_tile = 0; }
-            mot.push_back(m);
-            in_tile += e;
-            max_tile = std::max(max_tile, in_tile);
-            prev = m;
-        }
-        if (in_tile > 0) tile_first.push_back((int32_t) mot.size());
-        wide_first.push_back((int32_t) mot.size());
-        for (int32_t m = 0; m < P; m++)
-            if (pwms->widths[(size_t) m] > kBestTileMaxW && scorable(pwms, m)) { mot.push_back(m); wide_first.push_back((int32_t) mot.size()); }
+        dense_plan(pwms, off, R, [&](int32_t m) { return scorable(pwms, m); }, &plan);
     } catch (const std::bad_alloc &) { set_error("out of host memory"); return MS_ERR_NOMEM; }
+    const std::vector<int64_t> &seg_first = plan.seg_first, &part_first = plan.part_first, &long_regions = plan.long_regions;
+    const std::vector<int32_t> &mot = plan.mot, &tile_first = plan.tile_first, &wide_first = plan.wide_first, &uns = plan.skipped;
+    const int64_t n_seg = plan.n_seg, n_part = plan.n_part;
+    const size_t max_tile = plan.max_tile;
     const int32_t n_lds_tiles = (int32_t) tile_first.size() - 1, n_wide = (int32_t) wide_first.size() - 1, n_mot = (int32_t) mot.size();
     const int64_t n_long = (int64_t) long_regions.size();
     if (n_long > 0x7FFFFFFFLL || (n_seg + kBestWaves - 1) / kBestWaves > 0x7FFFFFFFLL) { set_error("too many segments for one launch"); return MS_ERR_INVALID; }

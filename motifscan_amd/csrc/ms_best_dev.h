@@ -1,9 +1,15 @@
 // ms_best_dev.h -- what the "best window of a cell" kernels share (ms_best.hip: per region; ms_allelebest.hip: per variant haplotype):
-// the total-order wave reduction and the test for a motif the reference never reports a site of; and, with ms_scorehist.hip (the score
-// histogram walks the windows as ms_best.hip does), the column loop over an LDS tile of tables.
+// the total-order wave reduction and the test for a motif the reference never reports a site of; with ms_scorehist.hip (the score
+// histogram walks the windows as ms_best.hip does), the column loop over an LDS tile of tables; and with ms_affinity.hip (the same
+// walk, another reduction at its end) the dense walk of ms_best.hip: its sizes, the host's plan of segments and motif tiles, and the
+// walk's three steps as functions -- the staging of a tile, a segment's words into registers, the raw sums of one strip of window starts.
+// best_kernel keeps these three steps written out in its own body: called through the functions, hipcc schedules its LDS form
+// differently (its disassembly changes), and that kernel's code is to stay as measured.  A change to a step is made in both places.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <limits>
+#include <vector>
 
 #include "ms_device.h"
 #include "ms_handles.h"
@@ -13,6 +19,15 @@ namespace ms {
 namespace {
 
 constexpr uint64_t kNoKey = ~0ULL;
+
+// the dense walk (best_kernel, affinity_kernel): a wave per segment of a region, a block per tile of motifs
+constexpr int kBestThreads = 512;
+constexpr int kBestWaves = kBestThreads / 64;            // segments per block
+constexpr int kBestStrips = 8;                           // strips of 64 window starts whose words a lane keeps in registers
+constexpr int kBestSegWindows = 64 * kBestStrips;
+constexpr int kBestTileMaxW = 1024;                      // (= kExactTileMaxW, ms_fp64.hip) widest motif whose table fits a tile
+constexpr int kBestTileEntries = kBestTileMaxW * 4;      // 64 KB of tab2 entries per tile (+ the zero entry): two blocks share a CU's 160 KB
+constexpr int kBestGridY = 32768;
 
 // (q, key) of the wave's lanes -> the winner in every lane: the greater q, equal q to the smaller key = pos << 2 | strand
 __device__ __forceinline__ void wave_best(double &q, uint64_t &key) {
@@ -39,6 +54,58 @@ __device__ __forceinline__ void best_cols32(const double2 *__restrict__ lds, uin
     }
 }
 
+// the tile's tables into LDS with one contiguous copy behind an all-zero entry 0 (n entries from src), the block's barrier included
+__device__ __forceinline__ void dense_stage_tile(double2 *__restrict__ lds, const double2 *__restrict__ src, int32_t n) {
+    if (threadIdx.x == 0) lds[0] = make_double2(0.0, 0.0);
+    for (int32_t i = threadIdx.x; i < n; i += kBestThreads) lds[1 + i] = src[i];
+    __syncthreads();
+}
+
+// the code / mask words of the lane's kBestStrips window starts p0 + 64 s + lane of the region [beg, beg + L), read once
+__device__ __forceinline__ void dense_segment_words(const uint32_t *__restrict__ codes, const uint32_t *__restrict__ nmask, int64_t beg, int64_t L, int64_t p0, int lane,
+                                                    uint64_t (&cw)[kBestStrips], uint32_t (&nw)[kBestStrips]) {
+#pragma unroll
+    for (int s = 0; s < kBestStrips; s++) {
+        const int64_t pos = p0 + s * 64 + lane;
+        const bool in = pos < L;                          // (a lane past the region reads nothing: the padding behind the planes is short)
+        cw[s] = in ? code_window(codes, beg + pos) : 0ULL;
+        nw[s] = in ? n_window(nmask, beg + pos) : ~0u;
+    }
+}
+
+// The raw sums of the window that starts at base g (= beg + pos; valid: it lies inside its region) for strip s of the segment's words.
+// LDS: the motif's table at entry tb of the tile; !LDS: in HBM at tab.  COUNT_N: n_non = the window's non-ACGT bases (the mask bits of
+// its own W bases: from the register for the first 32 columns, from the further words a wider motif loads anyway).
+template <bool LDS, bool COUNT_N>
+__device__ __forceinline__ void dense_strip_sums(const double2 *__restrict__ lds, uint32_t tb, const double2 *__restrict__ tab, const uint32_t *__restrict__ codes,
+                                                 const uint32_t *__restrict__ nmask, int W, int64_t g, bool valid, int s, const uint64_t (&cw)[kBestStrips],
+                                                 const uint32_t (&nw)[kBestStrips], double &fwd, double &rev, int &n_non) {
+    if (LDS) {
+        // the strip's words out of the register arrays: a chain of selects on the wave-uniform s (the loop is NOT unrolled: eight
+        // copies of the column loops spill; indexing the arrays with s would put them into scratch)
+        uint64_t cws = cw[0];
+        uint32_t nws = nw[0];
+#pragma unroll
+        for (int j = 1; j < kBestStrips; j++) { cws = s == j ? cw[j] : cws; nws = s == j ? nw[j] : nws; }
+        const int n0 = W < 32 ? W : 32;
+        best_cols32(lds, tb, n0, cws, nws | ~low_mask(n0), fwd, rev);
+        if (COUNT_N) n_non = __popc(nws & low_mask(n0));
+        for (int c0 = 32; c0 < W; c0 += 32) {             // wider motifs: the further words are read per motif (a lane without a window reads nothing)
+            const int n = (W - c0) < 32 ? (W - c0) : 32;
+            const uint64_t cwx = valid ? code_window(codes, g + c0) : 0ULL;
+            const uint32_t nwx = valid ? n_window(nmask, g + c0) : ~0u;
+            best_cols32(lds, tb + (uint32_t) c0 * 4u, n, cwx, nwx | ~low_mask(n), fwd, rev);
+            if (COUNT_N) n_non += __popc(nwx & low_mask(n));
+        }
+    } else if (valid) {
+        DevSeq S;
+        S.codes = codes; S.nmask = nmask;
+        score_window(S, tab, W, g, fwd, rev);
+        if (COUNT_N)
+            for (int c0 = 0; c0 < W; c0 += 32) n_non += __popc(n_window(nmask, g + c0) & low_mask((W - c0) < 32 ? (W - c0) : 32));
+    }
+}
+
 // the reference never reports a site of such a motif: max_raw is not a finite number > 0, or an entry is NaN or +inf
 inline bool scorable(const ms_pwmset *p, int32_t m) {
     const double mr = p->max_raw[(size_t) m];
@@ -48,6 +115,61 @@ inline bool scorable(const ms_pwmset *p, int32_t m) {
     for (int64_t i = 0; i < n; i++)
         if (std::isnan(v[i]) || v[i] == std::numeric_limits<double>::infinity()) return false;
     return true;
+}
+
+// The plan of a dense walk, made on the host: segments of the regions, tiles of the motifs.
+struct DensePlan {
+    std::vector<int64_t> seg_first;                      // [R + 1] first segment of the region (every region has at least one); empty: one segment per region
+    std::vector<int64_t> part_first;                     // [R + 1] first partial of the region (regions of one segment have none); empty with seg_first
+    std::vector<int64_t> long_regions;                   // the regions of more than one segment
+    std::vector<int32_t> mot;                            // the motifs that are walked: the LDS tiles' one after the other, then the wide ones
+    std::vector<int32_t> tile_first;                     // [LDS tiles + 1] into mot
+    std::vector<int32_t> wide_first;                     // [wide motifs + 1] into mot: one "tile" per motif of more than kBestTileMaxW columns
+    std::vector<int32_t> skipped;                        // the motifs that are not walked: their rows are filled
+    int64_t n_seg = 0, n_part = 0;
+    size_t max_tile = 0;                                 // entries of the largest LDS tile
+};
+
+// walked(m): motif m is scored.  LDS tiles first: runs of consecutive walked motifs of <= kBestTileMaxW columns whose entries fit a tile
+// (consecutive motifs are consecutive in tab2: one contiguous copy stages a tile); then one tile per wider motif.  May throw std::bad_alloc.
+template <typename Walked>
+inline void dense_plan(const ms_pwmset *pwms, const int64_t *off, int64_t R, Walked walked, DensePlan *pl) {
+    const int32_t P = pwms->P;
+    pl->n_seg = R;
+    pl->n_part = 0;
+    bool any_long = false;
+    for (int64_t r = 0; r < R && !any_long; r++) any_long = off[r + 1] - off[r] > kBestSegWindows;
+    if (any_long) {
+        pl->seg_first.resize((size_t) R + 1);
+        pl->part_first.resize((size_t) R + 1);
+        pl->n_seg = 0;
+        for (int64_t r = 0; r < R; r++) {
+            const int64_t n = std::max<int64_t>(1, (off[r + 1] - off[r] + kBestSegWindows - 1) / kBestSegWindows);
+            pl->seg_first[(size_t) r] = pl->n_seg;
+            pl->part_first[(size_t) r] = pl->n_part;
+            pl->n_seg += n;
+            if (n > 1) { pl->n_part += n; pl->long_regions.push_back(r); }
+        }
+        pl->seg_first[(size_t) R] = pl->n_seg;
+        pl->part_first[(size_t) R] = pl->n_part;
+    }
+    pl->tile_first.push_back(0);
+    size_t in_tile = 0;
+    int32_t prev = -2;
+    for (int32_t m = 0; m < P; m++) {
+        if (!walked(m)) { pl->skipped.push_back(m); continue; }
+        const size_t e = (size_t) pwms->widths[(size_t) m] * 4;
+        if (pwms->widths[(size_t) m] > kBestTileMaxW) continue;
+        if (in_tile > 0 && (prev != m - 1 || in_tile + e > (size_t) kBestTileEntries)) { pl->tile_first.push_back((int32_t) pl->mot.size()); in_tile = 0; }
+        pl->mot.push_back(m);
+        in_tile += e;
+        pl->max_tile = std::max(pl->max_tile, in_tile);
+        prev = m;
+    }
+    if (in_tile > 0) pl->tile_first.push_back((int32_t) pl->mot.size());
+    pl->wide_first.push_back((int32_t) pl->mot.size());
+    for (int32_t m = 0; m < P; m++)
+        if (pwms->widths[(size_t) m] > kBestTileMaxW && walked(m)) { pl->mot.push_back(m); pl->wide_first.push_back((int32_t) pl->mot.size()); }
 }
 
 }  // namespace

@@ -3,7 +3,8 @@
 // ms_result.hip (one per handle), ms_scan.hip (scan pipeline), ms_sweep.hip (window sweep), ms_regions.hip and ms_stream.hip (batch streams,
 // host-streamed sweeps), ms_best.hip (best window per cell), ms_allelebest.hip (best window per variant haplotype), ms_pairs.hip (motif pairs over a result's hits), ms_scorehist.hip (score histogram of every window),
 // ms_personal.hip (a variant set spliced into a new resident genome, and the lift map between the two), ms_sitestack.hip (base counts per
-// motif column over a result's sites), ms_ranksum.hip (rank sums and passing-region counts over best-site matrices).
+// motif column over a result's sites), ms_ranksum.hip (rank sums and passing-region counts over best-site matrices), ms_affinity.hip (the
+// summed likelihood ratio of every cell).
 #pragma once
 #include <sched.h>
 #include <atomic>
@@ -266,7 +267,31 @@ struct ms_best {                                      // ms_scan_best: the best 
     double device_ms = 0.0;                           // first launch -> last kernel done
 };
 
+struct ms_affinity {                                  // ms_scan_affinity: the summed likelihood ratio of every (motif, region) cell
+    int device = 0;
+    int32_t P = 0;
+    int64_t R = 0;
+    void *block = nullptr;                            // one pooled device block holding the four [P][R] planes
+    size_t block_bytes = 0;
+    double *d_peak = nullptr;                         // the greatest raw sum over the terms; NaN: no term
+    double *d_sum = nullptr;                          // sum of exp(scale * (raw - peak))
+    double *d_log_mean = nullptr;                     // scale * peak + log(sum / n_terms): the plane ms_affinity_rank_sum ranks
+    int32_t *d_n_terms = nullptr;
+    double device_ms = 0.0;                           // first launch -> last kernel done
+};
+
 namespace ms {
+
+// One [P][R] plane of doubles per group, ranked per motif row (ms_ranksum.hip): what ms_best_rank_sum (the score plane of two ms_best) and
+// ms_affinity_rank_sum (the log_mean plane of two ms_affinity) both are.  `what` names the handles in the error texts.
+struct RankPlane {
+    int device;
+    int32_t P;
+    int64_t R;
+    const double *plane;
+};
+MS_HIDDEN int rank_sum_planes(const char *what, const RankPlane &a, const uint8_t *sel_a, const RankPlane &b, const uint8_t *sel_b, int32_t m0, int32_t m1, uint32_t flags,
+                              int64_t *u2, uint64_t *ties, int64_t *n, double *device_ms);
 
 // Internal scan flag: stop after the fp64 stage -- the hits stay UNORDERED in the device scratch (c->sc.keys / vals, key =
 // motif << (gbits + 1) | coordinate << 1 | strand bit, coordinate = sequence << pbits | position when pbits > 0, else the

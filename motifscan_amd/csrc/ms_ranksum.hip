@@ -1,5 +1,7 @@
 // ms_ranksum.hip -- cutoff-free enrichment over best-site matrices that stay on the device (ms_best_rank_sum, ms_best_count_passing): the
 // consumer of ms_scan_best's [P][R] score matrix.  Both results are exact integers; z and P-values are host arithmetic on them (enrich.py).
+// The rank sums read nothing of a handle but one [P][R] plane of doubles per group: rank_sum_planes is their body, and ms_affinity_rank_sum
+// (ms_affinity.hip) calls it with the log_mean planes of two affinity results.
 //
 // Order of cell values (both calls): a cell without a winner (score NaN) ranks below every number and ties with every other such cell;
 // numbers compare as IEEE doubles (-0.0 == +0.0).  rs_gather_kernel turns a cell into an order-preserving 64-bit key: 0 for NaN (by
@@ -228,40 +230,15 @@ bool sort_segmented(uint32_t n) {
 
 }  // namespace
 
-}  // namespace ms
-
-using namespace ms;
-
-extern "C" {
-
-int ms_debug_ranksum_dims(int32_t out[8]) {
-    if (!out) { set_error("NULL output"); return MS_ERR_INVALID; }
-    out[0] = kRsThreads;
-    out[1] = kRsGatherElems;
-    out[2] = kRsRankElems;
-    out[3] = kRsCountElems;
-    out[4] = (int32_t) kRsBudget;
-    out[5] = kRsCutChunk;
-    out[6] = (int32_t) kRsSegmentedMax;
-    out[7] = 0;
-    return MS_OK;
-}
-
-int ms_debug_ranksum_budget(int64_t elems, int64_t *previous) {
-    if (elems < 0) { set_error("budget must be >= 0 (0 = the library's own)"); return MS_ERR_INVALID; }
-    const int64_t old = g_rs_budget.exchange(elems);
-    if (previous) *previous = old;
-    return MS_OK;
-}
-
-int ms_best_rank_sum(const ms_best *a, const uint8_t *sel_a, const ms_best *b, const uint8_t *sel_b, int32_t m0, int32_t m1, uint32_t flags, int64_t *u2, uint64_t *ties,
-                     int64_t *n, double *device_ms) {
-    if (!have_device()) return MS_ERR_RUNTIME;
-    if (!a || !b) { set_error("NULL handle"); return MS_ERR_INVALID; }
+// The rank sums of two [P][R] planes of doubles that lie on one device: the body of ms_best_rank_sum, which ms_affinity_rank_sum shares.
+// The caller has checked for a device and for NULL handles; `what` names its handles in the error texts.
+int rank_sum_planes(const char *what, const RankPlane &pa, const uint8_t *sel_a, const RankPlane &pb, const uint8_t *sel_b, int32_t m0, int32_t m1, uint32_t flags,
+                    int64_t *u2, uint64_t *ties, int64_t *n, double *device_ms) {
+    const RankPlane *a = &pa, *b = &pb;
     if (flags != 0u) { set_error("unknown rank-sum flags 0x%x", flags); return MS_ERR_INVALID; }
-    if (a->P != b->P) { set_error("the two best-site results disagree on the number of PWMs (%d and %d)", a->P, b->P); return MS_ERR_INVALID; }
+    if (a->P != b->P) { set_error("the two %s results disagree on the number of PWMs (%d and %d)", what, a->P, b->P); return MS_ERR_INVALID; }
     if (m0 < 0 || m1 < m0 || m1 > a->P) { set_error("motif range [%d, %d) outside [0, %d)", m0, m1, a->P); return MS_ERR_INVALID; }
-    if (a->device != b->device) { set_error("the best-site results live on devices %d and %d", a->device, b->device); return MS_ERR_INVALID; }
+    if (a->device != b->device) { set_error("the %s results live on devices %d and %d", what, a->device, b->device); return MS_ERR_INVALID; }
     if (a->R >= (1LL << 31) || b->R >= (1LL << 31)) { set_error("a group of 2^31 regions or more: u2 would not fit 64 bits"); return MS_ERR_INVALID; }
     const int32_t rows = m1 - m0;
     if (rows == 0) return MS_OK;
@@ -325,8 +302,8 @@ int ms_best_rank_sum(const ms_best *a, const uint8_t *sel_a, const ms_best *b, c
         uint64_t *raw_a = d_raw, *raw_b = d_raw + (size_t) nr * na, *srt_a = d_sorted, *srt_b = d_sorted + (size_t) nr * na;
         for (int32_t y0 = 0; y0 < nr; y0 += kRsGridY) {
             const unsigned gy = (unsigned) std::min(kRsGridY, nr - y0);
-            if (na) hipLaunchKernelGGL(rs_gather_kernel, dim3((na + kRsGatherElems - 1) / kRsGatherElems, gy), dim3(kRsThreads), 0, st, a->d_score, a->R, m0 + r0, d_ia, na, raw_a, y0);
-            if (nb) hipLaunchKernelGGL(rs_gather_kernel, dim3((nb + kRsGatherElems - 1) / kRsGatherElems, gy), dim3(kRsThreads), 0, st, b->d_score, b->R, m0 + r0, d_ib, nb, raw_b, y0);
+            if (na) hipLaunchKernelGGL(rs_gather_kernel, dim3((na + kRsGatherElems - 1) / kRsGatherElems, gy), dim3(kRsThreads), 0, st, a->plane, a->R, m0 + r0, d_ia, na, raw_a, y0);
+            if (nb) hipLaunchKernelGGL(rs_gather_kernel, dim3((nb + kRsGatherElems - 1) / kRsGatherElems, gy), dim3(kRsThreads), 0, st, b->plane, b->R, m0 + r0, d_ib, nb, raw_b, y0);
         }
         if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "rank-sum gather kernel");
         size_t tb = b_tmp;
@@ -360,6 +337,40 @@ int ms_best_rank_sum(const ms_best *a, const uint8_t *sel_a, const ms_best *b, c
         ties[2 * (size_t) i + 1] = (uint64_t) (t >> 64);
     }
     return MS_OK;
+}
+
+}  // namespace ms
+
+using namespace ms;
+
+extern "C" {
+
+int ms_debug_ranksum_dims(int32_t out[8]) {
+    if (!out) { set_error("NULL output"); return MS_ERR_INVALID; }
+    out[0] = kRsThreads;
+    out[1] = kRsGatherElems;
+    out[2] = kRsRankElems;
+    out[3] = kRsCountElems;
+    out[4] = (int32_t) kRsBudget;
+    out[5] = kRsCutChunk;
+    out[6] = (int32_t) kRsSegmentedMax;
+    out[7] = 0;
+    return MS_OK;
+}
+
+int ms_debug_ranksum_budget(int64_t elems, int64_t *previous) {
+    if (elems < 0) { set_error("budget must be >= 0 (0 = the library's own)"); return MS_ERR_INVALID; }
+    const int64_t old = g_rs_budget.exchange(elems);
+    if (previous) *previous = old;
+    return MS_OK;
+}
+
+int ms_best_rank_sum(const ms_best *a, const uint8_t *sel_a, const ms_best *b, const uint8_t *sel_b, int32_t m0, int32_t m1, uint32_t flags, int64_t *u2, uint64_t *ties,
+                     int64_t *n, double *device_ms) {
+    if (!have_device()) return MS_ERR_RUNTIME;
+    if (!a || !b) { set_error("NULL handle"); return MS_ERR_INVALID; }
+    const RankPlane pa = {a->device, a->P, a->R, a->d_score}, pb = {b->device, b->P, b->R, b->d_score};
+    return rank_sum_planes("best-site", pa, sel_a, pb, sel_b, m0, m1, flags, u2, ties, n, device_ms);
 }
 
 int ms_best_count_passing(const ms_best *b, const uint8_t *sel, const double *cutoffs, int32_t n_cut, int32_t m0, int32_t m1, int64_t *counts, double *device_ms) {

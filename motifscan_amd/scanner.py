@@ -17,6 +17,8 @@ and the questions the reference cannot answer from its site lists:
     Scanner.best_sites(pwms) -> BestSiteArrays: the best-scoring window of every (motif, region), cutoff or not.
     Scanner.rank_sum(pwms, control) -> enrich.RankSum: cutoff-free enrichment of the best scores against a control scanner's.
     Scanner.count_regions_passing(pwms, cutoffs) -> the regions with >= 1 site at several cutoffs per motif, from one scan.
+    Scanner.affinity(pwms) -> affinity.AffinityArrays: the likelihood ratio summed over ALL windows of every (motif, region).
+    Scanner.affinity_rank_sum(pwms, control) -> enrich.RankSum: rank_sum with that sum in place of the best score.
     Scanner.score_histogram(pwms, ...) -> scoredist.ScoreHistogram: the score distribution of all windows, per motif.
     Scanner.site_base_counts(pwms, ...) -> sitestack.SiteStack: the base counts per motif column over the sites found.
 
@@ -381,6 +383,54 @@ class Scanner:
                 return res.count_passing(cutoffs)
             finally:
                 res.close()
+        finally:
+            pw.close()
+
+    def _scan_affinity(self, pw, scale, max_n):
+        return _lib.scan_affinity(pw, self._seqset(), _STRAND_FLAG[self.strand], scale, max_n)
+
+    def affinity(self, pwms, scale=1.0, max_n=-1):
+        """The total binding affinity of every (motif, region) cell -- the likelihood ratio exp(scale * raw score) summed over ALL
+        windows of the region, the cutoff-free statistic that still sees a weak site repeated five times -- as an
+        affinity.AffinityArrays (peak, sum, n_terms, log_mean; .log_sum(), .mean_odds()).  Every window is scored as scan_motifs scores
+        it, nothing is normalised (the PWMs are natural-log odds: scale = 1.0; ln 2 for a log2 matrix).  max_n >= 0 leaves out the
+        windows of more than max_n non-ACGT bases.  Honours the scanner's `strand`; `p_value` and `remove_dup` have no meaning here."""
+        from . import affinity
+        scale, max_n = affinity.check_args(scale, max_n)
+        matrices = [np.asarray(pwm.matrix, dtype=np.float64) for pwm in pwms]
+        pw = _lib.PwmSet.from_matrices(matrices)
+        try:
+            res = self._scan_affinity(pw, scale, max_n)
+            try:
+                return affinity.AffinityArrays(*res.cells())
+            finally:
+                res.close()
+        finally:
+            pw.close()
+
+    def affinity_rank_sum(self, pwms, control, sel=None, sel_control=None, scale=1.0, max_n=-1):
+        """rank_sum with the region's mean likelihood ratio over all windows (affinity's log_mean) in place of its best score: an
+        enrich.RankSum.  Both region lists are scanned with ms_scan_affinity, each with its scanner's `strand`; the planes stay on the
+        device and are reduced there (ms_affinity_rank_sum).  A region without a term (shorter than the motif) ranks below every other."""
+        from . import affinity, enrich
+        scale, max_n = affinity.check_args(scale, max_n)
+        if not isinstance(control, Scanner):
+            raise ValueError("control must be a Scanner")
+        for s, n in ((sel, len(self.seq_starts)), (sel_control, len(control.seq_starts))):
+            if s is not None and np.shape(s) != (n,):
+                raise ValueError(f"a selection must hold one flag per region ({n}), got shape {np.shape(s)}")
+        matrices = [np.asarray(pwm.matrix, dtype=np.float64) for pwm in pwms]
+        pw = _lib.PwmSet.from_matrices(matrices)
+        try:
+            mine = self._scan_affinity(pw, scale, max_n)
+            try:
+                theirs = control._scan_affinity(pw, scale, max_n)
+                try:
+                    return enrich.RankSum(*mine.rank_sum(theirs, sel, sel_control))
+                finally:
+                    theirs.close()
+            finally:
+                mine.close()
         finally:
             pw.close()
 
