@@ -63,6 +63,30 @@ int ms_debug_key_layout(int64_t n_bases, int64_t n_seqs, int64_t max_len, int32_
  * test can force the "buffer too small -> grow -> run the pass again" path.  Needs a GPU. */
 int ms_debug_release_scratch(void);
 
+/* The candidate list between the two stages of a scan: one 64-bit record per window start and table group, g << 30 | group << 16 | flags,
+ * bit n of the flags = field n of the group is a candidate at window start g (global base position); 0 = an empty slot.  Groups and fields
+ * are numbered as ms_debug_plan_rows numbers them.  Both entries run ms_scan's exactly-sized form -- the same overrides, geometry, scratch
+ * and its grow-and-run-again loop -- with a stop or a start point, and leave the set's size prediction as it was.  flags: as ms_scan's.
+ * Need a GPU.
+ *
+ * ms_debug_scan_candidates queues the counter clear and the pre-filter of a scan of (pwms, seqs, strand_mask), waits, and copies the
+ * first min(*n_slots, cap) slots to records (NULL: only the count); *n_slots = the slots the launch used: the waves' own first blocks and
+ * the blocks they reserved after them (which wave reserves how many depends on the hand-out: the number may differ between two calls).
+ * No fp64 stage runs and no result is built.  geom: the launch's geometry -- [0] the wide kernel, [1] the dense-candidate form,
+ * [2] the hand-out's counters are used, [3] passes per unit, [4] blocks per LDS tile, [5] LDS tiles, [6] parking entries per wave,
+ * [7] slots per candidate block, [8] slots of the waves' own first blocks, [9] windows of non-ACGT bases only are dropped unseen,
+ * [10] window starts per pass (128 / 64), [11] records per chunk of the carried fp64 stage; [12..15] reserved, 0.
+ *
+ * ms_debug_scan_from_candidates is the same scan with the pre-filter's launch replaced by an upload of records[0 .. n) into the candidate
+ * list (padded with empty slots up to the waves' own first blocks); the fp64 stage -- rescore_kernel or rescore_carry_kernel, as the
+ * geometry has it --, the motifs on the all-fp64 path, ordering and finalize run as in any scan; *result is an ordinary ms_result.  A
+ * flagged record must name a base of the set and a group of the plan (MS_ERR_INVALID otherwise); the same (g, group) twice, or a flag on
+ * an empty field, is outside the contract. */
+int ms_debug_scan_candidates(const ms_pwmset *pwms, const ms_seqset *seqs, int strand_mask, uint32_t flags, uint64_t *records, uint64_t cap,
+                             uint64_t *n_slots, int64_t geom[16]);
+int ms_debug_scan_from_candidates(const ms_pwmset *pwms, const ms_seqset *seqs, int strand_mask, uint32_t flags, const uint64_t *records, uint64_t n,
+                                  ms_result **result);
+
 /* ms_scan_variants (and ms_scan_alleles and ms_scan_alleles_best: the same knob) takes its variants in chunks (the per-(motif, tile) record counts of one chunk are bounded,
  * ms_scan_alleles_best's chunks bound its grids); n_variants > 0 sets the
  * chunk size for the calls that follow in this process, 0 gives it back to the library.  *previous (may be NULL) = the value before.

@@ -174,6 +174,8 @@ def lib():
         "ms_debug_plan_dims": (c_int, [vp, c_int, c_i64, pi32, pi32, pi32, pi32]),
         "ms_debug_plan_rows": (c_int, [vp, pi32, ctypes.POINTER(ctypes.c_int16), pi32, pi32, pi32, pi32, pi32, pi32]),
         "ms_debug_release_scratch": (c_int, []),
+        "ms_debug_scan_candidates": (c_int, [vp, vp, c_int, c_u32, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), pi64]),
+        "ms_debug_scan_from_candidates": (c_int, [vp, vp, c_int, c_u32, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64, pvp]),
         "ms_debug_numa_probe": (c_int, [ctypes.c_char_p, ctypes.c_char_p, pi32, pi32, pi32]),
         "ms_scan_variants": (c_int, [vp, vp, pi32, pi64, ctypes.c_char_p, c_i64, c_int, c_u32, pvp]),
         "ms_varscan_num_sites": (c_int, [vp, pi64]),
@@ -1016,6 +1018,36 @@ def scan(pwms, seqs, strand_mask=3, flags=MS_SCAN_DEFAULT):
     h = ctypes.c_void_p()
     check(lib().ms_scan(pwms.h, seqs.h, int(strand_mask), int(flags), ctypes.byref(h)))
     return _fence_exact_only(ScanResult(h, pwms.n), pwms, int(flags))
+
+
+SCAN_GEOM_FIELDS = ("wide", "dense", "counter_used", "wave_passes", "blocks_per_tile", "n_tiles", "rare_cap", "cand_block", "cand_static",
+                    "skip_alln", "pass_windows", "rescore_chunk")
+
+
+def scan_candidates(pwms, seqs, strand_mask=3, flags=MS_SCAN_DEFAULT):
+    """ms_debug_scan_candidates (tests only): the pre-filter of a scan alone.  Returns (records uint64 [n_slots], geom dict, cap): every slot
+    of the candidate list the launch used (g << 30 | group << 16 | flags, 0 = empty), the launch's geometry (SCAN_GEOM_FIELDS), and the
+    room the records were asked into.  The list is sized by a first call; which wave reserves how many blocks depends on the hand-out, so the
+    call is repeated with more room should the second list be longer."""
+    L = lib()
+    n, geom = ctypes.c_uint64(0), np.zeros(16, dtype=np.int64)
+    check(L.ms_debug_scan_candidates(pwms.h, seqs.h, int(strand_mask), int(flags), None, 0, ctypes.byref(n), ptr(geom, ctypes.c_int64)))
+    while True:
+        cap = int(n.value) + int(n.value) // 4 + 4096
+        rec = np.zeros(cap, dtype=np.uint64)
+        check(L.ms_debug_scan_candidates(pwms.h, seqs.h, int(strand_mask), int(flags), ptr(rec, ctypes.c_uint64), cap, ctypes.byref(n),
+                                         ptr(geom, ctypes.c_int64)))
+        if n.value <= cap:
+            assert not geom[len(SCAN_GEOM_FIELDS):].any()
+            return rec[:n.value], {k: int(v) for k, v in zip(SCAN_GEOM_FIELDS, geom)}, cap
+
+
+def scan_from_candidates(pwms, seqs, records, strand_mask=3, flags=MS_SCAN_DEFAULT):
+    """ms_debug_scan_from_candidates (tests only): the scan with `records` in place of the pre-filter's candidate list."""
+    rec = np.ascontiguousarray(records, dtype=np.uint64)
+    h = ctypes.c_void_p()
+    check(lib().ms_debug_scan_from_candidates(pwms.h, seqs.h, int(strand_mask), int(flags), ptr(rec, ctypes.c_uint64), rec.size, ctypes.byref(h)))
+    return ScanResult(h, pwms.n)
 
 
 def scan_sweep(pwms, genome, chrom, begin, end, window, stride, strand_mask=3, flags=MS_SCAN_DEFAULT):

@@ -341,9 +341,24 @@ void pending_scan_destroy(PendingScan *p);
 // waits for a pending scan; MS_OK: *out is the result; MS_SCAN_RETRY: nothing was produced.  The caller holds pwms->mu.
 int scan_complete(DeviceCtx *c, ms_pwmset *pwms, PendingScan *p, ms_result **out);
 
+// A stop or a start point in the exactly-sized scan, for the two debug entries of include/motifscan_amd_debug.h (tests only; a scan that
+// carries one is never predicted or queued):
+//   stop  -- the front ends behind the pre-filter: the candidate list goes to the host (out / cap / n_slots / geom), no fp64 stage, no result;
+//   start -- the pre-filter's launch is replaced by an upload of `records` into the candidate list; everything behind it runs as usual.
+struct ScanDebug {
+    bool stop = false;
+    uint64_t *out = nullptr;                 // stop: the first min(*n_slots, cap) record slots land here (nullptr: only the count)
+    uint64_t cap = 0;
+    uint64_t *n_slots = nullptr;             // stop: min(cand_static + counters[0], the list's capacity)
+    int64_t *geom = nullptr;                 // stop: [16] the launch's geometry (ms_debug_scan_candidates)
+    const uint64_t *records = nullptr;       // start: n record slots (0 = empty)
+    uint64_t n = 0;
+};
+
 // The scan pipeline proper (ms_scan.hip); the caller holds c->mu and pwms->mu.  pend != nullptr: if the sizes can be predicted the
 // scan is only QUEUED (returns MS_SCAN_PENDING, finish with scan_complete); otherwise it runs to the end as usual.
-int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand_mask, uint32_t flags, ms_result **out, PendingScan *pend = nullptr);
+int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand_mask, uint32_t flags, ms_result **out, PendingScan *pend = nullptr,
+                const ScanDebug *dbg = nullptr);
 // Hand the hits of a span scan (one region) to the windows of a fixed-stride sweep, in place of *span_res (ms_sweep.hip);
 // the caller holds c->mu and pwms->mu.
 // counts_only: only the per-motif window counts and the number of sites are made (ms_result::counts_only: the hit accessors refuse it)

@@ -14,6 +14,9 @@
 
 namespace ms {
 
+constexpr int kScanDebugGeomWords = 16;          // ms_debug_scan_candidates' geom
+constexpr int64_t kRescoreCarryChunk = 4096;     // records per chunk of rescore_carry_kernel (kRwChunk, ms_fp64.hip: a test compares the two)
+
 static int scratch_reserve(Scratch &sc, size_t cand_cap, size_t hit_cap) {
     int rc;
     if (cand_cap > sc.cand_cap) {
@@ -157,6 +160,7 @@ struct ScanCtx {
     double bk_mu = 0.0;                  // expected hits, and the sum of the buckets' needs at that expectation (bucket_need)
     unsigned long long bk_need = 0, bk_cap_max = ~0ULL;
     BucketWeights bk_w;                  // the sequence set's bucket weights for this key layout, L and these motif widths
+    const ScanDebug *dbg = nullptr;      // a debug entry's stop / start point (ms_handles.h)
 };
 
 // The plan of this scan, with its device copies.  Which kernel family it runs (PrefilterPlan::wide) decides the LDS budget it is built
@@ -277,6 +281,23 @@ static int scan_prefilter(ScanCtx &x) {
     return launch_prefilter(A, g.wide, g.dense, g.bpt, g.n_tiles, g.lds_bytes, c->stream);
 }
 
+// ms_debug_scan_from_candidates: the caller's record slots in place of the pre-filter's launch.  Empty records fill the list up to the
+// waves' own first blocks, and counters[0] says that the fp64 stage sees exactly the given slots.  A list longer than the scratch is cut
+// where the pre-filter's own stores would be cut: scan_exact reads the full count, grows the scratch and runs the pass again.
+static int scan_upload_candidates(ScanCtx &x) {
+    DeviceCtx *c = x.c;
+    Scratch &sc = c->sc;
+    const ScanDebug &d = *x.dbg;
+    const uint64_t n_static = std::min<uint64_t>(x.g.cand_static, sc.cand_cap), n_copy = std::min<uint64_t>(d.n, sc.cand_cap);
+    hipError_t he = hipSuccess;
+    if (n_copy) he = hipMemcpyAsync(sc.cand, d.records, n_copy * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream);
+    if (he == hipSuccess && n_copy < n_static) he = hipMemsetAsync(sc.cand + n_copy, 0, (n_static - n_copy) * sizeof(uint64_t), c->stream);
+    sc.h_counters[0] = d.n > x.g.cand_static ? d.n - x.g.cand_static : 0ULL;        // (pinned, and next written by fetch_counters behind this copy)
+    if (he == hipSuccess) he = hipMemcpyAsync(sc.counters, sc.h_counters, sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream);
+    if (he != hipSuccess) { set_error("candidate upload failed: %s", hipGetErrorString(he)); return MS_ERR_RUNTIME; }
+    return MS_OK;
+}
+
 // pre-filter + fp64 stage of one pass, queued on the scan stream (events 0, 1, 2 around the two stages)
 static int scan_front(ScanCtx &x, const HitOut &H, const BucketOut *B = nullptr) {
     DeviceCtx *c = x.c;
@@ -286,8 +307,13 @@ static int scan_front(ScanCtx &x, const HitOut &H, const BucketOut *B = nullptr)
     hipError_t he = hipMemsetAsync(sc.counters, 0, 8 * sizeof(unsigned long long), c->stream);
     if (he != hipSuccess) { set_error("memset failed: %s", hipGetErrorString(he)); return MS_ERR_RUNTIME; }
     (void) hipEventRecord(x.ev[0], c->stream);
-    if (x.g.n_tiles > 0 && (rc = scan_prefilter(x))) return rc;
+    const bool given = x.dbg && !x.dbg->stop;         // the candidate list comes from the caller
+    if (x.g.n_tiles > 0 && (rc = given ? scan_upload_candidates(x) : scan_prefilter(x))) return rc;
     (void) hipEventRecord(x.ev[1], c->stream);
+    if (x.dbg && x.dbg->stop) {                       // ms_debug_scan_candidates: the list is all that is wanted
+        (void) hipEventRecord(x.ev[2], c->stream);
+        return MS_OK;
+    }
     if (!plan.fast_motifs.empty()) {                 // (few blocks for a small scan measured slower: the kernel is a chain of dependent gathers and wants every record in flight at once)
         if (x.g.rescore_carry) {
             if (!c->rc_lds_set) { if ((rc = rescore_carry_set_lds())) return rc; c->rc_lds_set = true; }
@@ -529,6 +555,25 @@ static int pending_fill(ScanCtx &x, PendingScan *pend, size_t n_pred) {
     return MS_OK;
 }
 
+// ms_debug_scan_candidates: the candidate list as the pre-filter left it, and the geometry it was launched in
+static int scan_candidates_out(ScanCtx &x, unsigned long long n_cand) {
+    DeviceCtx *c = x.c;
+    const Scratch &sc = c->sc;
+    const ScanDebug &d = *x.dbg;
+    const ScanGeom &g = x.g;
+    const uint64_t n_slots = x.g.n_tiles > 0 ? std::min<uint64_t>(n_cand, sc.cand_cap) : 0, n_copy = d.out ? std::min<uint64_t>(n_slots, d.cap) : 0;
+    *d.n_slots = n_slots;
+    if (n_copy) {
+        hipError_t he = hipMemcpyAsync(d.out, sc.cand, n_copy * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
+        if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
+        if (he != hipSuccess) { set_error("candidate copy failed: %s", hipGetErrorString(he)); return MS_ERR_RUNTIME; }
+    }
+    const int64_t geom[kScanDebugGeomWords] = {g.wide, g.dense, g.counter_used, g.wave_passes, g.bpt, g.n_tiles, (int64_t) g.rare_cap, (int64_t) g.cand_block,
+                                               (int64_t) g.cand_static, x.pwms->plan.alln_can_hit ? 0 : 1, g.wide ? 64 : 128, kRescoreCarryChunk};
+    std::memcpy(d.geom, geom, sizeof(geom));
+    return MS_OK;
+}
+
 // The exactly-sized form: the front runs (again, with larger buffers, while one overflows), the host reads the counts, and the result
 // block, the sort and the coordinate kernel are sized by them.
 static int scan_exact(ScanCtx &x, size_t want_cand, size_t want_hits) {
@@ -548,6 +593,7 @@ static int scan_exact(ScanCtx &x, size_t want_cand, size_t want_hits) {
         if (pass >= 8) { set_error("scan buffers kept overflowing (%llu candidates, %llu hits)", n_cand, n_hits); return MS_ERR_RUNTIME; }
         scan_grow(sc.cand_cap, sc.hit_cap, n_cand, n_hits, &want_cand, &want_hits);       // ... and run the pass again
     }
+    if (x.dbg && x.dbg->stop) return scan_candidates_out(x, n_cand);
     if (x.flags & MS_SCAN_RAW_INTERNAL) {                      // the caller takes the unordered hits from the scratch
         finish_scan(raw, x.ev, x.pwms, x.seqs->n_bases, x.seqs->R, x.key, n_cand, n_hits, false, 0);
         raw->raw_gbits = x.g.gbits;
@@ -574,11 +620,12 @@ static int scan_exact(ScanCtx &x, size_t want_cand, size_t want_hits) {
 //   exactly sized (scan_exact) -- no prediction for this key yet, the caller forbids one, or the prediction just failed.  It always runs
 //       to the end, with or without a PendingScan slot (the first batch of a stream, whose PWM set has no prediction yet, came back
 //       with all-zero offsets when it did not).
-int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand_mask, uint32_t flags, ms_result **out, PendingScan *pend) {
+int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand_mask, uint32_t flags, ms_result **out, PendingScan *pend,
+                const ScanDebug *dbg) {
     int rc;
     const ScanOverrides ov = read_scan_overrides();
     ScanCtx x;
-    x.c = c; x.pwms = pwms; x.seqs = seqs; x.strand_mask = strand_mask; x.flags = flags; x.ev = c->ev;
+    x.c = c; x.pwms = pwms; x.seqs = seqs; x.strand_mask = strand_mask; x.flags = flags; x.ev = c->ev; x.dbg = dbg;
     if ((rc = seqset_pack_pending(seqs, c->stream))) return rc;       // a batch stream's set: its pack / hint kernels run here, in front of its pre-filter
     if ((rc = pwmset_upload(pwms, c->device, c->stream))) return rc;
     x.key = ScanKey{strand_mask, pwms->cutoff_version, (flags & MS_SCAN_EXACT_ONLY) != 0};
@@ -588,7 +635,21 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
     std::unique_ptr<ms_result, void (*)(ms_result *)> res(scan_result_new(c, pwms, seqs, strand_mask, &sh.fast_windows), ms_result_free);
     if (!res) return MS_ERR_NOMEM;
     x.raw = res.get();
+    if (dbg && dbg->stop) { *dbg->n_slots = 0; std::memset(dbg->geom, 0, kScanDebugGeomWords * sizeof(int64_t)); }
+    if (dbg && !dbg->stop) {
+        // the kernels behind the list trust a record as they trust the pre-filter: a flagged one must name a base and a table group of this scan
+        const uint64_t n_groups = pwms->plan.group_kb.size();
+        for (uint64_t i = 0; i < dbg->n; i++) {
+            const uint64_t rec = dbg->records[i];
+            if ((rec & 0xFFFFu) && ((int64_t) (rec >> 30) >= seqs->n_bases || ((rec >> 16) & 0x3FFFu) >= n_groups)) {
+                set_error("record %llu names base %llu, table group %llu (the set has %lld bases, the plan %llu groups)", (unsigned long long) i,
+                          (unsigned long long) (rec >> 30), (unsigned long long) ((rec >> 16) & 0x3FFFu), (long long) seqs->n_bases, (unsigned long long) n_groups);
+                return MS_ERR_INVALID;
+            }
+        }
+    }
     if (pwms->P == 0 || seqs->n_bases == 0) {
+        if (dbg && dbg->stop) { *out = nullptr; return MS_OK; }
         if ((rc = scan_empty(x))) return rc;
         *out = res.release();
         return MS_OK;
@@ -609,7 +670,7 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
 
     Scratch &sc = c->sc;
     size_t want_cand = x.g.want_cand, want_hits = x.g.want_hits;
-    if (density_known && !(flags & (MS_SCAN_RAW_INTERNAL | MS_SCAN_NO_PREDICT_INTERNAL)) && !ov.no_predict) {
+    if (density_known && !(flags & (MS_SCAN_RAW_INTERNAL | MS_SCAN_NO_PREDICT_INTERNAL)) && !ov.no_predict && !dbg) {
         if (pend) x.ev = pend->ev;
         const double mu = pwms->pred_density * (double) stt.n_windows;
         size_t n_pred = (size_t) std::min<double>(mu * (1.0 + pwms->pred_margin) + 6.0 * std::sqrt(mu + 1.0) + 256.0, 3.0e9);
@@ -639,7 +700,7 @@ int scan_locked(DeviceCtx *c, ms_pwmset *pwms, const ms_seqset *seqs, int strand
         scan_grow(sc.cand_cap, sc.hit_cap, n_cand, n_hits, &want_cand, &want_hits);
     }
     if ((rc = scan_exact(x, want_cand, want_hits))) return rc;
-    *out = res.release();
+    *out = dbg && dbg->stop ? nullptr : res.release();
     return MS_OK;
 }
 
@@ -663,6 +724,46 @@ int ms_scan(const ms_pwmset *pwms_c, const ms_seqset *seqs, int strand_mask, uin
     std::lock_guard<std::mutex> lk_pwm(pwms->mu);
     const uint32_t internal = (flags & MS_SCAN_EXACT_ONLY) | ((flags & MS_SCAN_COUNTS_ONLY) ? MS_SCAN_COUNTS_ONLY_INTERNAL : 0u);
     return scan_locked(c, pwms, seqs, strand_mask, internal, out);
+}
+
+// The two debug entries around the candidate list (include/motifscan_amd_debug.h): ms_scan's own driver with a stop or a start point
+// (ScanDebug).  What the set remembers of its last scan -- the prediction of the next one's sizes -- is put back: a list of the caller's
+// choosing says nothing about the set's hit density.
+static int scan_debug(const ms_pwmset *pwms_c, const ms_seqset *seqs, int strand_mask, uint32_t flags, const ScanDebug &dbg, ms_result **out) {
+    if (!pwms_c || !seqs) { set_error("NULL handle"); return MS_ERR_INVALID; }
+    if (strand_mask < 1 || strand_mask > 3) { set_error("invalid strand mask %d (1 '+', 2 '-', 3 both)", strand_mask); return MS_ERR_INVALID; }
+    if (flags & ~(uint32_t) (MS_SCAN_EXACT_ONLY | MS_SCAN_COUNTS_ONLY)) { set_error("unknown scan flags 0x%x", flags); return MS_ERR_INVALID; }
+    ms_pwmset *pwms = const_cast<ms_pwmset *>(pwms_c);
+    DeviceCtx *c;
+    int rc = get_ctx(seqs->device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk_dev(c->mu);
+    std::lock_guard<std::mutex> lk_pwm(pwms->mu);
+    const double density = pwms->pred_density, margin = pwms->pred_margin;
+    const ScanKey key = pwms->pred_key;
+    const uint32_t internal = (flags & MS_SCAN_EXACT_ONLY) | ((flags & MS_SCAN_COUNTS_ONLY) ? MS_SCAN_COUNTS_ONLY_INTERNAL : 0u) | MS_SCAN_NO_PREDICT_INTERNAL;
+    rc = scan_locked(c, pwms, seqs, strand_mask, internal, out, nullptr, &dbg);
+    pwms->pred_density = density; pwms->pred_margin = margin; pwms->pred_key = key;
+    return rc;
+}
+
+int ms_debug_scan_candidates(const ms_pwmset *pwms, const ms_seqset *seqs, int strand_mask, uint32_t flags, uint64_t *records, uint64_t cap,
+                             uint64_t *n_slots, int64_t geom[16]) {
+    if (!n_slots || !geom) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    ScanDebug dbg;
+    dbg.stop = true; dbg.out = records; dbg.cap = records ? cap : 0; dbg.n_slots = n_slots; dbg.geom = geom;
+    ms_result *none = nullptr;
+    return scan_debug(pwms, seqs, strand_mask, flags, dbg, &none);
+}
+
+int ms_debug_scan_from_candidates(const ms_pwmset *pwms, const ms_seqset *seqs, int strand_mask, uint32_t flags, const uint64_t *records, uint64_t n,
+                                  ms_result **result) {
+    if (!result) { set_error("out is NULL"); return MS_ERR_INVALID; }
+    *result = nullptr;
+    if (n > 0 && !records) { set_error("records is NULL"); return MS_ERR_INVALID; }
+    ScanDebug dbg;
+    dbg.records = records; dbg.n = n;
+    return scan_debug(pwms, seqs, strand_mask, flags, dbg, result);
 }
 
 // the bucketed hit list's host arithmetic alone, for CPU tests (include/motifscan_amd_debug.h)

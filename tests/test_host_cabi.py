@@ -74,15 +74,7 @@ def test_max_raw_is_the_c_definition(oracle, rnd):
 
 # ---------------------------------------------------------------- pre-filter plan --
 
-LUT = {c: i for i, c in enumerate("ACGT")}
-
-
-def encode(seq):
-    """2-bit codes and the non-ACGT mask of a sequence, as convert_seq sees it (cscore.c:92-111: case folded, the rest 'adds nothing')."""
-    up = seq.upper()
-    codes = np.array([LUT.get(c, 0) for c in up], dtype=np.int64)
-    isn = np.array([c not in LUT for c in up], dtype=bool)
-    return codes, isn
+from prefilter_model import encode          # (the model's home: tests/prefilter_model.py)
 
 
 def field_strand(plan, n):
