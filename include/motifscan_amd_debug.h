@@ -93,6 +93,12 @@ int ms_debug_scan_from_candidates(const ms_pwmset *pwms, const ms_seqset *seqs, 
  * The result of a scan does not depend on it: a test proves that with a chunk of a few variants.  Needs no GPU. */
 int ms_debug_varscan_chunk(int64_t n_variants, int64_t *previous);
 
+/* The sizes at which ms_scan_variants and ms_scan_alleles change path, as constants of the build: out[0] the variants of one block's tile
+ * of ms_scan_variants, out[1] the threads of that block (= the items of one round), out[2] the widest motif whose table it stages in LDS
+ * (wider ones read it from HBM, in a second launch over the same grid); out[3], out[4], out[5] the same three of ms_scan_alleles.  Tests
+ * size their boundary cases from here.  Needs no GPU. */
+int ms_debug_varscan_dims(int32_t out[6]);
+
 /* The sizes at which ms_scan_alleles_best changes path, as constants of the build: out[0] the variants of one block's tile (a thread per
  * variant); out[1] the window count -- both haplotypes of a cell together -- above which a cell that is not a single-base substitution
  * takes the wave path (a wave per haplotype); out[2] the widest motif whose table is staged in LDS (wider ones read it from HBM).  Tests

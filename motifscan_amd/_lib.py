@@ -186,6 +186,7 @@ def lib():
         "ms_varscan_device_ms": (c_int, [vp, pd]),
         "ms_varscan_free": (None, [vp]),
         "ms_debug_varscan_chunk": (c_int, [c_i64, pi64]),
+        "ms_debug_varscan_dims": (c_int, [pi32]),
         "ms_debug_bucket_plan": (c_int, [pi64, c_i64, pi32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_i64,
                                  ctypes.POINTER(ctypes.c_uint64), ctypes.c_double, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int32,
                                  ctypes.POINTER(ctypes.c_uint64), pi32, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
@@ -1138,6 +1139,15 @@ def varscan_chunk(n_variants):
     prev = ctypes.c_int64()
     check(lib().ms_debug_varscan_chunk(int(n_variants), ctypes.byref(prev)))
     return prev.value
+
+
+def varscan_dims():
+    """ms_debug_varscan_dims: dict(variants=dict(tile, threads, lds_max_width), alleles=dict(...)) -- per scan the variants of one block's
+    tile, the threads of that block, the widest motif whose table is staged in LDS.  Constants of the build; no device."""
+    out = np.zeros(6, dtype=np.int32)
+    check(lib().ms_debug_varscan_dims(ptr(out, ctypes.c_int32)))
+    keys = ("tile", "threads", "lds_max_width")
+    return {"variants": dict(zip(keys, out[:3].tolist())), "alleles": dict(zip(keys, out[3:].tolist()))}
 
 
 class AlleleScan:

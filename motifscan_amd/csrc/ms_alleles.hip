@@ -263,6 +263,12 @@ size_t al_up256(size_t x) { return (x + 255) & ~(size_t) 255; }
 
 }  // namespace
 
+void allelescan_dims(int32_t out[3]) {
+    out[0] = kAlTile;
+    out[1] = kAlThreads;
+    out[2] = kAlTabMaxW;
+}
+
 }  // namespace ms
 
 using namespace ms;

@@ -380,6 +380,8 @@ MS_HIDDEN DevSeq dev_seq(const ms_seqset *s);
 MS_HIDDEN int64_t windows_for_width(const ms_seqset *s, int W);
 // what ms_debug_varscan_chunk set: variants per chunk of the variant scans, 0 = their own size (ms_variants.hip; read by ms_alleles.hip and ms_allelebest.hip)
 MS_HIDDEN int64_t varscan_chunk_setting();
+// the allele scan's half of ms_debug_varscan_dims (ms_alleles.hip): kAlTile, kAlThreads, kAlTabMaxW
+MS_HIDDEN void allelescan_dims(int32_t out[3]);
 // the path constants of the kernels around the scan, for ms_debug_genome_dims (ms_background.hip): the pack / extract block in bases
 // (ms_seqset.hip), kNearThreads / kGeneTile / kOverlapThreads (ms_annotation.hip), the element budget of a score-rank batch (ms_pwmset.hip)
 MS_HIDDEN int32_t seqset_block_bases();

@@ -53,7 +53,8 @@ namespace {
 
 constexpr int kVarTile = 128;                   // variants per block
 constexpr int kVarThreads = 256;
-constexpr int kVarTabMaxW = 1023;               // widest motif whose table (W x 4 entries) fits 64 KB of LDS; wider ones read it from HBM
+constexpr int kVarTabMaxW = 1023;               // widest motif whose table (W x 4 entries + the zero one: 65 488 B) fits 64 KB; wider ones read it from HBM
+                                                // (with the 544 B of static arrays a block then takes 66 032 B: above 64 KB, far below gfx950's 160 KB -- DESIGN.md)
 constexpr int64_t kVarMaxTiles = 1LL << 24;     // (motif, tile) counts of one chunk: 64 MB of counts + 128 MB of their prefix sums
 constexpr int32_t kVarFar = 1 << 30;
 
@@ -293,6 +294,15 @@ int ms_debug_varscan_chunk(int64_t n_variants, int64_t *previous) {
     if (n_variants < 0) { set_error("chunk size must be >= 0 (0 = the library's own)"); return MS_ERR_INVALID; }
     const int64_t old = g_var_chunk.exchange(n_variants);
     if (previous) *previous = old;
+    return MS_OK;
+}
+
+int ms_debug_varscan_dims(int32_t out[6]) {
+    if (!out) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    out[0] = kVarTile;
+    out[1] = kVarThreads;
+    out[2] = kVarTabMaxW;
+    allelescan_dims(out + 3);
     return MS_OK;
 }
 

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from motifscan_amd import _lib, synth, variants
+from variant_cases import allele_flank_table, expected_allele_records as expected_records, flanks, n_affected, seeded_matrix
 
 pytestmark = pytest.mark.gpu
 
@@ -21,25 +22,10 @@ def _device():
     _lib.set_device(0)
 
 
-def passes(score, cutoff):
-    return score - cutoff >= -1e-10                     # cscore.c:358 / 375
-
-
-def n_affected(x, length, L_hap, W):
-    """The header's formula: starts max(0, x - W + 1) .. min(x + length - 1, L_hap - W) on a haplotype of L_hap bases."""
-    return np.maximum(np.minimum(x + length - 1, L_hap - W) - np.maximum(0, x - W + 1) + 1, 0)
-
-
 def sites_of(res):
     s = res.sites()
     res.close()
     return s
-
-
-def flanks(seq, x, r, alt, W):
-    """(lo, ref flank, alt flank): the pieces of the two haplotypes whose windows of width W are exactly the affected ones."""
-    lo, hi = max(0, x - W + 1), min(len(seq), x + r + W - 1)
-    return lo, seq[lo:hi], seq[lo:x] + alt + seq[x + r:hi]
 
 
 # ------------------------------------------------------------------------------------------------ 1. the oracle, smallest shapes
@@ -47,13 +33,6 @@ def flanks(seq, x, r, alt, W):
 WIDTHS = (1, 4, 6, 19, 33, 64, 70)
 SHAPES = ((1, 1), (0, 1), (1, 0), (0, 3), (3, 0), (2, 2), (2, 5), (5, 2), (0, 40), (35, 0), (1, 33))
 ALT_LETTERS = b"ACGTACGTNacgtn"
-
-
-def seeded_matrix(width, seed):
-    """A log-odds-like matrix: Dirichlet columns against a flat background, five decimals as the reference keeps them."""
-    rng = np.random.default_rng(seed)
-    ppm = rng.dirichlet(np.full(4, 0.4), size=width).T
-    return np.round(np.log2((ppm + 0.01) / 1.04 / 0.25), 5)
 
 
 @pytest.fixture(scope="module")
@@ -93,27 +72,7 @@ def small(oracle, rnd):
     assert np.any((ref_len > 0) & (pos + ref_len == lens[chrom_idx])) and np.any((ref_len == 0) & (pos == lens[chrom_idx]))
 
     # per motif: every affected window of either haplotype, scored by the oracle on Python-built flank strings (ref, alt per variant)
-    table = []
-    for mat in mats:
-        W = mat.shape[1]
-        seqs, los = [], []
-        for v in range(V):
-            lo, fr, fa = flanks(chroms[names[chrom_idx[v]]], int(pos[v]), int(ref_len[v]), alts[v], W)
-            seqs += [fr, fa]
-            los += [lo, lo]
-        nwin = np.maximum(np.array([len(s) for s in seqs]) - W + 1, 0)
-        L = lens[chrom_idx]
-        assert np.array_equal(nwin[0::2], n_affected(pos, ref_len, L, W))
-        assert np.array_equal(nwin[1::2], n_affected(pos, alt_len, L - ref_len + alt_len, W))
-        woff = np.concatenate([[0], np.cumsum(nwin)])
-        vals, widths = oracle.flatten_pwms([mat])
-        bases, off = oracle.flatten_seqs(seqs)
-        r = oracle.scan_arrays(vals, widths, [ALL_PASS], bases, off, 3)
-        sc = np.full((int(woff[-1]), 2), -np.inf)       # a window the all-pass scan does not report holds a -inf entry
-        sc[woff[r["seq_idx"]] + r["pos"], r["strand"] - 1] = r["score"]
-        seq_of = np.repeat(np.arange(2 * V), nwin)
-        start = np.repeat(np.array(los), nwin) + (np.arange(int(woff[-1])) - np.repeat(woff[:-1], nwin))
-        table.append({"variant": seq_of // 2, "allele": (seq_of % 2).astype(np.uint8), "start": start, "score": sc})
+    table = allele_flank_table(oracle, chroms, names, mats, chrom_idx, pos, ref_len, alts)
     assert any(np.any(n_affected(pos, alt_len, lens[chrom_idx] - ref_len + alt_len, m.shape[1]) == 0) for m in mats)
 
     quant = [float(np.quantile(t["score"][np.isfinite(t["score"])], 0.9)) for t in table]
@@ -122,28 +81,6 @@ def small(oracle, rnd):
            "table": table, "lens": lens, "V": V,
            "cutoffs": {"q90": np.array(quant), "all": np.full(len(mats), ALL_PASS), "none": np.full(len(mats), 2.0)}}
     genome.close()
-
-
-def expected_records(table, cutoffs, strand_mask, V):
-    out = {k: [] for k in ("variant", "allele", "start", "strand", "score")}
-    offsets, gained, lost = [0], [], []
-    for t, cut in zip(table, cutoffs):
-        hit = passes(t["score"], cut)
-        for s in (0, 1):
-            if not strand_mask & (1 << s):
-                hit[:, s] = False
-        keep = hit.ravel()                              # window-major, '+' before '-'
-        out["variant"].append(np.repeat(t["variant"], 2)[keep])
-        out["allele"].append(np.repeat(t["allele"], 2)[keep])
-        out["start"].append(np.repeat(t["start"], 2)[keep])
-        out["strand"].append(np.tile(np.array([1, 2], dtype=np.int8), len(t["variant"]))[keep])
-        out["score"].append(t["score"].ravel()[keep])
-        offsets.append(offsets[-1] + int(keep.sum()))
-        has = np.zeros((V, 2), dtype=bool)
-        has[out["variant"][-1], out["allele"][-1]] = True
-        gained.append(int((has[:, 1] & ~has[:, 0]).sum()))
-        lost.append(int((has[:, 0] & ~has[:, 1]).sum()))
-    return {k: np.concatenate(v) for k, v in out.items()}, np.array(offsets, dtype=np.int64), np.array(gained), np.array(lost)
 
 
 @pytest.mark.parametrize("strand_mask", [1, 2, 3])

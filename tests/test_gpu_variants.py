@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from motifscan_amd import _lib, synth, variants
+from variant_cases import expected_snv_records as expected_records, n_windows, seeded_matrix, snv_flank_table
 
 pytestmark = pytest.mark.gpu
 
@@ -20,15 +21,6 @@ def _device():
     _lib.set_device(0)
 
 
-def passes(score, cutoff):
-    return score - cutoff >= -1e-10                     # cscore.c:358 / 375
-
-
-def n_windows(x, L, W):
-    """Windows of width W that cover position x of a chromosome of L bases: starts max(0, x - W + 1) .. min(x, L - W)."""
-    return np.maximum(np.minimum(x, L - W) - np.maximum(0, x - W + 1) + 1, 0)
-
-
 def sites_of(res):
     s = res.sites()
     res.close()
@@ -39,13 +31,6 @@ def sites_of(res):
 
 WIDTHS = (1, 4, 6, 19, 33, 64, 70)
 ALTS = "ACGTNt"
-
-
-def seeded_matrix(width, seed):
-    """A log-odds-like matrix: Dirichlet columns against a flat background, five decimals as the reference keeps them."""
-    rng = np.random.default_rng(seed)
-    ppm = rng.dirichlet(np.full(4, 0.4), size=width).T
-    return np.round(np.log2((ppm + 0.01) / 1.04 / 0.25), 5)
 
 
 @pytest.fixture(scope="module")
@@ -75,33 +60,9 @@ def small(oracle, rnd):
     V0 = len(pos)                                       # 142 positions x 6 alts
     chrom_idx, pos = np.tile(chrom_idx, len(ALTS)), np.tile(pos, len(ALTS))
     alt = np.repeat(np.frombuffer(ALTS.encode(), dtype=np.uint8), V0)
-    V = len(pos)
 
     # every window that covers a variant, scored by the oracle on the ref and on the alt flank [x - W + 1, x + W) clipped to the chromosome
-    table = []
-    for mat in mats:
-        W = mat.shape[1]
-        ref_seqs, alt_seqs, starts = [], [], []
-        for v in range(V):
-            seq, x = chroms[names[chrom_idx[v]]], int(pos[v])
-            lo, hi = max(0, x - W + 1), min(len(seq), x + W)
-            ref_seqs.append(seq[lo:hi])
-            alt_seqs.append(seq[lo:x] + bytes([alt[v]]) + seq[x + 1:hi])
-            starts.append(lo)
-        nwin = np.maximum(np.array([len(s) for s in ref_seqs]) - W + 1, 0)
-        assert np.array_equal(nwin, n_windows(pos, lens[chrom_idx], W))
-        woff = np.concatenate([[0], np.cumsum(nwin)])
-        vals, widths = oracle.flatten_pwms([mat])
-        score = []
-        for seqs in (ref_seqs, alt_seqs):
-            bases, off = oracle.flatten_seqs(seqs)
-            r = oracle.scan_arrays(vals, widths, [ALL_PASS], bases, off, 3)
-            sc = np.full((int(woff[-1]), 2), -np.inf)   # a window the all-pass scan does not report holds a -inf entry
-            sc[woff[r["seq_idx"]] + r["pos"], r["strand"] - 1] = r["score"]
-            score.append(sc)
-        variant = np.repeat(np.arange(V), nwin)
-        start = np.repeat(np.array(starts), nwin) + (np.arange(int(woff[-1])) - np.repeat(woff[:-1], nwin))
-        table.append({"variant": variant, "start": start, "ref": score[0], "alt": score[1]})
+    table = snv_flank_table(oracle, chroms, names, mats, chrom_idx, pos, alt)
 
     quant = []
     for t in table:
@@ -111,25 +72,6 @@ def small(oracle, rnd):
     yield {"genome": genome, "chroms": chroms, "names": names, "mats": mats, "chrom_idx": chrom_idx, "pos": pos, "alt": alt, "table": table,
            "cutoffs": {"q90": np.array(quant), "all": np.full(len(mats), ALL_PASS), "none": np.full(len(mats), 2.0)}, "lens": lens}
     genome.close()
-
-
-def expected_records(table, cutoffs, strand_mask):
-    out = {k: [] for k in ("variant", "start", "strand", "score_ref", "score_alt", "state")}
-    offsets = [0]
-    for t, cut in zip(table, cutoffs):
-        state = (passes(t["ref"], cut).astype(np.uint8) | (passes(t["alt"], cut).astype(np.uint8) << 1))
-        for s in (0, 1):
-            if not strand_mask & (1 << s):
-                state[:, s] = 0
-        keep = state.ravel() != 0                       # window-major, '+' before '-'
-        out["variant"].append(np.repeat(t["variant"], 2)[keep])
-        out["start"].append(np.repeat(t["start"], 2)[keep])
-        out["strand"].append(np.tile(np.array([1, 2], dtype=np.int8), len(t["variant"]))[keep])
-        out["score_ref"].append(t["ref"].ravel()[keep])
-        out["score_alt"].append(t["alt"].ravel()[keep])
-        out["state"].append(state.ravel()[keep])
-        offsets.append(offsets[-1] + int(keep.sum()))
-    return {k: np.concatenate(v) for k, v in out.items()}, np.array(offsets, dtype=np.int64)
 
 
 @pytest.mark.parametrize("strand_mask", [1, 2, 3])
