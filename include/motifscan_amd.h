@@ -100,6 +100,9 @@
  *                         no reference counterpart: the sum of exp(raw window score) over ALL windows of a region -- total binding
  *                         affinity (TRAP, AME's avg / sum scoring) per (motif, region) cell, dense, without a hit per window;
  *                         ms_affinity_rank_sum ranks it as ms_best_rank_sum ranks the best score
+ *   ms_seqset_shuffle / ms_seqset_packed_host
+ *                         no reference counterpart: the input sequences shuffled on the device, keeping base composition or exact
+ *                         dinucleotide counts per run of ACGT -- the composition-matched control set of AME / HOMER, as another sequence set
  */
 #ifndef MOTIFSCAN_AMD_H
 #define MOTIFSCAN_AMD_H
@@ -201,7 +204,49 @@ int ms_seqset_from_device(const void *d_bases, const int64_t *offsets, int64_t n
                           ms_seqset **out);
 int ms_seqset_repack(ms_seqset *seqs);
 int ms_seqset_size(const ms_seqset *seqs, int64_t *n_seqs, int64_t *n_bases);
+/* The two planes of a sequence set copied back to host buffers, in ms_genome_create_packed's layout (codes[2 * ceil(n / 32)],
+ * nmask[ceil(n / 32)]): the counterpart of ms_genome_packed_host for a set -- how the bases of a set that was made on the device
+ * (ms_seqset_shuffle, ms_seqset_from_genome) reach the host.  MS_ERR_INVALID for a set whose planes are not on the device yet (a batch
+ * stream's upload-only set before its scan). */
+int ms_seqset_packed_host(const ms_seqset *seqs, uint32_t *codes, uint32_t *nmask);
 void ms_seqset_free(ms_seqset *seqs);
+
+/* ---- shuffled control sequences -------------------------------------------------------------- */
+/* A new set on the same device with the same offsets whose sequences are the input's, shuffled on the device: the composition-matched
+ * control of AME / HOMER / the TRAP null, for sets that have no genomic control (FASTA input, personal genomes).  Every scan entry point
+ * takes the result as it is.  A sequence is cut into its maximal runs of ACGT bases; a non-ACGT position stays where it is and every run
+ * is shuffled on its own, so the count of valid windows of any width is unchanged.
+ *   MS_SHUFFLE_MONO   the base composition of every run is kept
+ *   MS_SHUFFLE_DINUC  every dinucleotide count and the first and last base of every run are kept
+ * Sequence k of the set is shuffled as sequence r = seq_index_base + k: a shard of a set gets exactly the bytes the whole set would.
+ *
+ * THE RESULT IS SPECIFIED AS A FUNCTION and does not depend on the device mapping (motifscan_amd/shuffle.py restates it sequentially;
+ * the device output equals it bit for bit).  All arithmetic is unsigned 64-bit with wrap-around.
+ *   mix(x): x ^= x >> 30; x *= 0xbf58476d1ce4e5b9; x ^= x >> 27; x *= 0x94d049bb133111eb; x ^= x >> 31
+ *   h(seed, r, x, y) = mix(mix(mix(mix(seed + 0x9e3779b97f4a7c15) + r) + x) + y)
+ * With b the run's start, e its end and p a position, all relative to the sequence's first base, and s[p] the 2-bit code:
+ *   mono   the output run is the run's bases ordered by the key (h(seed, r, b, p), p), ascending.
+ *   dinuc  Altschul-Erickson with the arborescence drawn by Wilson's loop-erased walk (rejection takes ~n tries on poly-A and
+ *          microsatellite runs).  Runs of fewer than 3 bases are copied.  Otherwise
+ *          1. m[u][w] = the number of p in [b, e - 1) with s[p] = u, s[p + 1] = w;  f = s[e - 1].
+ *          2. in_tree = {f}, draw counter d = 0.  For v = 0, 1, 2, 3 in order, unless v is in the tree or row m[v] is all zero: walk u = v;
+ *             while u is not in the tree: tot = sum over w != u of m[u][w]; x = (h(seed, r, b, 2^62 | d) * tot) >> 64 (the high half of the
+ *             128-bit product); d += 1; w = the first w != u in ascending order whose running sum of m[u][w] exceeds x; next[u] = w
+ *             (overwriting); u = w.  Then walk again from v along next, marking vertices in the tree until one already is.
+ *          3. For every u != f with a non-zero row the reserved edge is the largest p with s[p] = u, s[p + 1] = next[u].
+ *          4. Order the edges p in [b, e - 1) by the key (s[p], reserved(p) ? 1 : 0, h(seed, r, b, p), p): the successors s[p + 1] in that
+ *             order, grouped by s[p], are the four lists L_u -- each shuffled, its reserved successor last.
+ *          5. out[b] = s[b]; then repeatedly cur = L_cur[ptr[cur]++], written out.  The walk uses every edge and ends on f.
+ * The draw (h * tot) >> 64 is biased by less than tot / 2^64; that is part of the specification.  The loop-erased walk has no cap (a cap
+ * would change the distribution); its expected length is at most the run's hitting time, a few hundred draws on (AC) x 100 G.
+ *
+ * MS_ERR_RUNTIME ("no CPU fallback") without a device, before anything else.  MS_ERR_INVALID: NULL handle or out, kind outside {1, 2},
+ * flags != 0, seq_index_base < 0, a set whose planes are not on the device yet (a batch stream's upload-only set).  n_seqs = 0 and empty
+ * sequences are valid.  Runs of more than ms_debug_shuffle_dims()[1] bases are sorted by one block each in pooled device scratch
+ * (about 34 bytes per base of such runs for the call's duration; a chromosome-long run is correct but slow). */
+#define MS_SHUFFLE_MONO  1   /* base composition of every ACGT run kept */
+#define MS_SHUFFLE_DINUC 2   /* every dinucleotide count, first and last base of every ACGT run kept */
+int ms_seqset_shuffle(const ms_seqset *seqs, int kind, uint64_t seed, int64_t seq_index_base, uint32_t flags /* 0 */, ms_seqset **out);
 
 /* ---- resident genome + on-device region extraction ------------------------------------------ */
 /* Replaces the per-region Genome.fetch_sequence (pysam) calls of Scanner._extract_seq

@@ -186,6 +186,17 @@ int ms_debug_ranksum_budget(int64_t elems, int64_t *previous);
  * reserved, 0.  Tests size their boundary cases from here.  Needs no GPU. */
 int ms_debug_affinity_dims(int32_t out[8]);
 
+/* The sizes at which ms_seqset_shuffle changes path, as constants of the build: out[0] the longest run handled by one lane and out[1] the
+ * longest run handled by one wave in LDS -- equal, the mapping has no lane tier: every run of up to out[1] bases takes one wave, a longer
+ * one takes one block with its keys in pooled global scratch; out[2] the bases per block of the stage that writes the mask plane, clears
+ * the code words and finds the runs (the runs then set their code bits word by word); out[3] reserved, 0.  Tests size their boundary
+ * cases from here.  Needs no GPU. */
+int ms_debug_shuffle_dims(int32_t out[4]);
+/* The stage times of the last ms_seqset_shuffle call on the calling thread's device, in ms: out[0] the mask plane, the cleared code words
+ * and the run count, up to the host's read of it; out[1] the run list and the long runs' scratch layout; out[2] the shuffle kernels;
+ * out[3] the region hints.  MS_ERR_INVALID before the first call. */
+int ms_debug_shuffle_stage_ms(double out[4]);
+
 #ifdef __cplusplus
 }
 #endif

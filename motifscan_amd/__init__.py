@@ -10,6 +10,7 @@ motifscan_amd -- MI355X-native drop-in for ONE hot path of shao-lab/MotifScan: t
     motifscan_amd.regions   GenomicRegion / RegionArray / subset_by_location / generate_control_regions / dis_to_nearest_gene
     motifscan_amd.dist      region sharding over the GPUs of a node + the one all-reduce
     motifscan_amd.synth     seeded synthetic workloads (bench.py, tests)
+    motifscan_amd.shuffle   the sequential restatement of ms_seqset_shuffle (mono- and dinucleotide shuffled controls), numpy only
 
 There is no CPU fallback anywhere in this package.
 """

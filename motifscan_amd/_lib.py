@@ -238,6 +238,10 @@ def lib():
         "ms_liftmap_free": (None, [vp]),
         "ms_debug_personal_dims": (c_int, [pi32]),
         "ms_debug_liftmap_stage_ms": (c_int, [vp, pd]),
+        "ms_seqset_packed_host": (c_int, [vp, pu32, pu32]),
+        "ms_seqset_shuffle": (c_int, [vp, c_int, ctypes.c_uint64, c_i64, c_u32, pvp]),
+        "ms_debug_shuffle_dims": (c_int, [pi32]),
+        "ms_debug_shuffle_stage_ms": (c_int, [pd]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -431,12 +435,75 @@ class SeqSet:
     def repack(self):
         check(lib().ms_seqset_repack(self.h))
 
+    def _host_offsets(self):
+        """int64 [n_seqs + 1]: the set's offsets on the host (a set cut from a genome keeps only its region lengths)."""
+        if self.offsets is not None:
+            return self.offsets
+        lens = getattr(self, "_region_lengths", None)
+        if lens is None:
+            raise ValueError("the offsets of this set are not known on the host")
+        off = np.zeros(lens.size + 1, dtype=np.int64)
+        np.cumsum(lens, out=off[1:])
+        return off
+
+    def packed_host(self):
+        """(codes uint32 [2 x units], nmask uint32 [units]) copied back from the device (ms_seqset_packed_host), in host_pack's layout."""
+        units = (self.n_bases + 31) // 32
+        codes, nmask = np.zeros(2 * units, dtype=np.uint32), np.zeros(units, dtype=np.uint32)
+        check(lib().ms_seqset_packed_host(self.h, ptr(codes, ctypes.c_uint32), ptr(nmask, ctypes.c_uint32)))
+        return codes, nmask
+
+    def to_strings(self):
+        """The sequences as a list of str, from the planes on the device: codes become ACGT, every non-ACGT base N (case and IUPAC
+        letters do not survive packing)."""
+        codes, nmask = self.packed_host()
+        n = self.n_bases
+        two = ((codes[:, None] >> (2 * np.arange(16, dtype=np.uint32))[None, :]) & 3).astype(np.uint8).reshape(-1)[:n]
+        isn = np.unpackbits(nmask.view(np.uint8), bitorder="little")[:n].astype(bool)
+        text = np.where(isn, np.uint8(ord("N")), np.frombuffer(b"ACGT", dtype=np.uint8)[two]).tobytes().decode("ascii")
+        off = self._host_offsets().tolist()
+        return [text[off[k]:off[k + 1]] for k in range(self.n_seqs)]
+
+    def shuffled(self, kind, seed, seq_index_base=0):
+        """A new SeqSet with the same offsets whose sequences are this set's, shuffled on the device (ms_seqset_shuffle): kind "mono" (1)
+        keeps the base composition, "dinuc" (2) every dinucleotide count and both end bases, of every run of ACGT; non-ACGT positions
+        stay.  Sequence k is shuffled as sequence seq_index_base + k, so a shard gets the bytes the whole set would.  The result equals
+        shuffle.shuffle_host(...) byte for byte."""
+        return seqset_shuffled(self, kind, seed, seq_index_base)
+
     def close(self):
         if getattr(self, "h", None):
             lib().ms_seqset_free(self.h)
             self.h = None
 
     __del__ = close
+
+
+def seqset_shuffled(seqs, kind, seed, seq_index_base=0):
+    """ms_seqset_shuffle of a SeqSet, or of a ResidentGenome (its chromosomes are the sequences): a new SeqSet on the same device."""
+    from .shuffle import KINDS
+    sq = SeqSet.__new__(SeqSet)
+    h = ctypes.c_void_p()
+    check(lib().ms_seqset_shuffle(seqs.h, int(KINDS.get(kind, kind)), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), int(seq_index_base), 0, ctypes.byref(h)))
+    sq.h = h
+    sq.offsets = seqs._host_offsets() if isinstance(seqs, SeqSet) else np.ascontiguousarray(seqs.offsets, dtype=np.int64)
+    sq.n_seqs = sq.offsets.size - 1
+    sq.n_bases = int(sq.offsets[-1])
+    return sq
+
+
+def shuffle_dims():
+    """ms_debug_shuffle_dims: the run lengths at which ms_seqset_shuffle changes path, as a dict."""
+    out = np.zeros(4, dtype=np.int32)
+    check(lib().ms_debug_shuffle_dims(ptr(out, ctypes.c_int32)))
+    return dict(zip(("lane_run", "lds_run", "block_bases", "reserved"), out.tolist()))
+
+
+def shuffle_stage_ms():
+    """ms_debug_shuffle_stage_ms: [run count, run list, shuffle kernels, region hints] of the last shuffle on this device, in ms."""
+    out = np.zeros(4, dtype=np.float64)
+    check(lib().ms_debug_shuffle_stage_ms(ptr(out, ctypes.c_double)))
+    return out
 
 
 class ResidentGenome:
@@ -537,6 +604,7 @@ class ResidentGenome:
         sq.h = h
         sq.n_seqs = len(ci)
         sq.offsets = None                         # lives on the device; not needed on the host
+        sq._region_lengths = en - st              # (what to_strings / shuffled rebuild the offsets from, if ever asked)
         nb = ctypes.c_int64()
         check(lib().ms_seqset_size(sq.h, None, ctypes.byref(nb)))
         sq.n_bases = nb.value

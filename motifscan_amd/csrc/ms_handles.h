@@ -4,7 +4,7 @@
 // host-streamed sweeps), ms_best.hip (best window per cell), ms_allelebest.hip (best window per variant haplotype), ms_pairs.hip (motif pairs over a result's hits), ms_scorehist.hip (score histogram of every window),
 // ms_personal.hip (a variant set spliced into a new resident genome, and the lift map between the two), ms_sitestack.hip (base counts per
 // motif column over a result's sites), ms_ranksum.hip (rank sums and passing-region counts over best-site matrices), ms_affinity.hip (the
-// summed likelihood ratio of every cell).
+// summed likelihood ratio of every cell), ms_shuffle.hip (a sequence set shuffled into a new one: mono- and dinucleotide controls).
 #pragma once
 #include <sched.h>
 #include <atomic>

@@ -499,6 +499,19 @@ int ms_debug_seqset_planes(const ms_seqset *s, uint32_t *codes, uint32_t *nmask,
     return MS_OK;
 }
 
+// the two planes of a built set on the host, in ms_genome_create_packed's layout (the public counterpart of ms_genome_packed_host)
+int ms_seqset_packed_host(const ms_seqset *s, uint32_t *codes, uint32_t *nmask) {
+    if (!s) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    if (!s->built || s->pack_pending || !s->block) { set_error("the set's planes are not on the device yet (packed by its first scan)"); return MS_ERR_INVALID; }
+    const size_t n_units = (size_t) ((s->n_bases + 31) / 32);
+    if (n_units == 0) return MS_OK;
+    if (!codes || !nmask) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    MS_HIP(hipSetDevice(s->device));
+    MS_HIP(hipMemcpy(codes, s->d_codes, n_units * 8, hipMemcpyDeviceToHost));
+    MS_HIP(hipMemcpy(nmask, s->d_nmask, n_units * 4, hipMemcpyDeviceToHost));
+    return MS_OK;
+}
+
 int ms_seqset_from_device(const void *d_bases, const int64_t *offsets, int64_t n_seqs, ms_seqset **out) {
     if (!out) { set_error("out is NULL"); return MS_ERR_INVALID; }
     *out = nullptr;

@@ -110,6 +110,8 @@ class Scanner:
     def sequences(self):
         """Region sequences as strings (scanner.py:68).  With a ResidentGenome they are only
         materialised on demand (and only if the genome kept a host copy)."""
+        if self._sequences is None and self._resident is None:        # a shuffled scanner: the bases were made on the device (to_strings copies the planes back)
+            self._sequences = _Frozen(self._seqset().to_strings())
         if self._sequences is None:
             g, idx = self._resident
             self._sequences = _Frozen(g.fetch_sequence(g.names[c], lo, hi)
@@ -167,9 +169,29 @@ class Scanner:
             if self._resident is not None:
                 g, idx = self._resident
                 self._sq = g.extract(idx, self.seq_starts, self.seq_ends)
+            elif self._sequences is None:
+                raise RuntimeError("this shuffled scanner was closed before its sequences were read: its bases lived on the device only")
             else:
                 self._sq = _lib.SeqSet.from_strings(self._sequences)
         return self._sq
+
+    def shuffled(self, kind="dinuc", seed=0):
+        """A Scanner over the same coordinates whose sequences are this scanner's, shuffled on the device (ms_seqset_shuffle): "mono" keeps
+        the base composition, "dinuc" every dinucleotide count and both end bases of every run of ACGT; non-ACGT positions stay where they
+        are, so every region keeps its count of valid windows.  The composition-matched control for `rank_sum`, `affinity_rank_sum`,
+        `score_histogram`, `best_sites` and `scan_motifs` when there is no genomic one (sequences from a FASTA, a personal genome):
+        `scanner.rank_sum(pwms, control=scanner.shuffled(seed=1))`.  The result does not depend on how the regions are sharded as long
+        as each shard passes its own first index (`SeqSet.shuffled(..., seq_index_base)`); here the scanner is the whole set.  The new
+        scanner owns its device set (it never takes the sweep or scan-once paths: there is no genome behind it); its `sequences` are
+        copied back from the device on first use."""
+        other = Scanner.__new__(Scanner)
+        other.window_size, other.extend = self.window_size, self.extend
+        other.strand, other.p_value, other.remove_dup, other.n_threads = self.strand, self.p_value, self.remove_dup, self.n_threads
+        other._starts, other._ends = self._starts, self._ends
+        other._resident = None
+        other._sequences = None
+        other._sq = self._seqset().shuffled(kind, seed)
+        return other
 
     def close(self):
         """Release the device copy of the regions (also done when the scanner is collected)."""
@@ -285,7 +307,7 @@ class Scanner:
 
         def batches():
             for r0, r1 in bounds:
-                seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in self._sequences[r0:r1]]
+                seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in self.sequences[r0:r1]]
                 offsets = np.zeros(len(seqs) + 1, dtype=np.int64)
                 if seqs:
                     offsets[1:] = np.cumsum([len(b) for b in seqs])
