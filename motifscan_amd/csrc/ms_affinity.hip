@@ -212,7 +212,6 @@ __global__ void __launch_bounds__(256) affinity_fill_kernel(const AffArgs A, con
     put_cell(A, (int64_t) motifs[blockIdx.y] * A.R + r, 0.0, 0.0, 0);
 }
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t) 255; }
 
 // a motif with a NaN or +inf entry has an empty row; every other one is scored, max_raw <= 0 included
 bool affinity_scored(const ms_pwmset *p, int32_t m) {
@@ -220,12 +219,6 @@ bool affinity_scored(const ms_pwmset *p, int32_t m) {
     const int64_t n = 4 * (int64_t) p->widths[(size_t) m];
     for (int64_t i = 0; i < n; i++)
         if (std::isnan(v[i]) || v[i] == std::numeric_limits<double>::infinity()) return false;
-    return true;
-}
-
-bool have_device() {
-    int n_dev = 0;
-    if (ms_device_count(&n_dev) != MS_OK || n_dev <= 0) { set_error("no usable HIP device; libmotifscan_amd has no CPU fallback"); return false; }
     return true;
 }
 
@@ -263,7 +256,7 @@ void ms_affinity_free(ms_affinity *a) {
 int ms_scan_affinity(const ms_pwmset *pwms_c, const ms_seqset *seqs, int strand_mask, double scale, int32_t max_n, uint32_t flags, ms_affinity **out) {
     if (!out) { set_error("out is NULL"); return MS_ERR_INVALID; }
     *out = nullptr;
-    if (!have_device()) return MS_ERR_RUNTIME;
+    if (!require_device()) return MS_ERR_RUNTIME;
     if (!pwms_c || !seqs) { set_error("NULL handle"); return MS_ERR_INVALID; }
     if (strand_mask < 1 || strand_mask > 3) { set_error("invalid strand mask %d (1 '+', 2 '-', 3 both)", strand_mask); return MS_ERR_INVALID; }
     if (flags != 0u) { set_error("unknown affinity scan flags 0x%x", flags); return MS_ERR_INVALID; }
@@ -442,7 +435,7 @@ int ms_affinity_device_ms(const ms_affinity *a, double *ms) {
 
 int ms_affinity_rank_sum(const ms_affinity *a, const uint8_t *sel_a, const ms_affinity *b, const uint8_t *sel_b, int32_t m0, int32_t m1, uint32_t flags, int64_t *u2,
                          uint64_t *ties, int64_t *n, double *device_ms) {
-    if (!have_device()) return MS_ERR_RUNTIME;
+    if (!require_device()) return MS_ERR_RUNTIME;
     if (!a || !b) { set_error("NULL handle"); return MS_ERR_INVALID; }
     const RankPlane pa = {a->device, a->P, a->R, a->d_log_mean}, pb = {b->device, b->P, b->R, b->d_log_mean};
     return rank_sum_planes("affinity", pa, sel_a, pb, sel_b, m0, m1, flags, u2, ties, n, device_ms);

@@ -29,7 +29,8 @@
 // No floating-point atomic, no sort, no data-dependent order; each of the six outputs of a cell is written exactly once: a scorable
 // motif's short cells by their thread, its long cells by lane 0 of their two waves, every cell of an unscorable motif (ms_best.hip's
 // definition) by ab_cell_kernel as the "no winner" triple (NaN, 0, 0).  Variants go in chunks (the grid's limits); the bytes do not depend
-// on them (ms_debug_varscan_chunk sets the chunk here too).
+// on them (ms_debug_varscan_chunk sets the chunk here too).  The upload of the variants (al_upload) and the column step (tab_step) are
+// ms_allele_dev.h's, shared with ms_alleles.hip, ms_personal.hip and ms_variants.hip.
 #include <algorithm>
 #include <memory>
 #include <type_traits>
@@ -87,46 +88,6 @@ __device__ __forceinline__ bool ab_is_long(const AlRec &q, int W) {
     return !ab_is_snv(q) && allele_windows(q.lo, q.hi, q.r, W) + allele_windows(q.lo, q.hi, q.a, W) > (uint32_t) kAbLongWindows;
 }
 
-// N columns from c1 on of the 32-column step at column c0, added in column order (var_scan_kernel's and al_scan_kernel's step: the reads are
-// issued together).  TWO: a second pair of sums takes entry tk in place of the table's at column kk (the alt allele of a substitution).
-template <bool LDS_TAB, bool TWO, int N>
-__device__ __forceinline__ void ab_cols(const double2 *lds, const double2 *__restrict__ tab_g, uint32_t zero, int c0, int n, int c1, uint64_t cw,
-                                        uint32_t skip, int kk, double2 tk, double &rf, double &rr, double &af, double &ar) {
-    double2 t[N];
-#pragma unroll
-    for (int u = 0; u < N; u++) {
-        const int c = c1 + u;
-        const bool nothing = (skip >> c) & 1u;                          // adds +0.0: a sum that started at +0.0 is never -0.0
-        if constexpr (LDS_TAB) {
-            t[u] = lds[nothing ? zero : (uint32_t) (c0 + c) * 4u + ((uint32_t) (cw >> (2 * c)) & 3u)];
-        } else {
-            const int cc = c < n ? c : n - 1;                           // clamped: always an entry of the motif
-            t[u] = tab_g[(uint32_t) (c0 + cc) * 4u + ((uint32_t) (cw >> (2 * cc)) & 3u)];
-            if (nothing) t[u] = make_double2(0.0, 0.0);
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < N; u++) {
-        rf += t[u].x;
-        rr += t[u].y;
-        if constexpr (TWO) {
-            const double2 ta = (c1 + u == kk) ? tk : t[u];
-            af += ta.x;
-            ar += ta.y;
-        }
-    }
-}
-
-// the n <= 32 columns of the step at c0: eight columns a time while more than four are left, then four
-template <bool LDS_TAB, bool TWO>
-__device__ __forceinline__ void ab_step(const double2 *lds, const double2 *__restrict__ tab_g, uint32_t zero, int c0, int n, uint64_t cw, uint32_t nw,
-                                        int kk, double2 tk, double &rf, double &rr, double &af, double &ar) {
-    const uint32_t skip = nw | ~low_mask(n);                            // bit c: column c0 + c adds nothing
-    int c1 = 0;
-    for (; n - c1 > 4; c1 += 8) ab_cols<LDS_TAB, TWO, 8>(lds, tab_g, zero, c0, n, c1, cw, skip, kk, tk, rf, rr, af, ar);
-    if (n - c1 > 0) ab_cols<LDS_TAB, TWO, 4>(lds, tab_g, zero, c0, n, c1, cw, skip, kk, tk, rf, rr, af, ar);
-}
-
 // window `rel` (its start, from x on) of haplotype hap (0 ref, 1 alt) of q: the two raw sums
 template <bool LDS_TAB>
 __device__ __forceinline__ void ab_window(const AbArgs &A, const double2 *lds, const double2 *__restrict__ tab_g, uint32_t zero, int W, const AlRec &q,
@@ -144,7 +105,7 @@ __device__ __forceinline__ void ab_window(const AbArgs &A, const double2 *lds, c
             cw = code_window(A.codes, q.g + rel + c0);
             nw = n_window(A.nmask, q.g + rel + c0);
         }
-        ab_step<LDS_TAB, false>(lds, tab_g, zero, c0, n, cw, nw, -1, make_double2(0.0, 0.0), fw, rv, u0, u1);
+        tab_step<LDS_TAB, false>(lds, tab_g, zero, c0, n, cw, nw, -1, make_double2(0.0, 0.0), fw, rv, u0, u1);
     }
 }
 
@@ -203,8 +164,7 @@ __global__ void __launch_bounds__(kAbThreads) ab_cell_kernel(const AbArgs A, int
     const double2 *__restrict__ tab_g = A.Pw.tab2 + A.Pw.tab_off[m];
     const uint32_t zero = (uint32_t) W * 4u;
     if (LDS_TAB) {
-        for (int i = threadIdx.x; i < W * 4; i += kAbThreads) abtab_lds[i] = tab_g[i];
-        if (threadIdx.x == 0) abtab_lds[zero] = make_double2(0.0, 0.0);
+        tab_stage<kAbThreads>(abtab_lds, tab_g, W);
         __syncthreads();
     }
     if (vl >= nv) return;
@@ -242,13 +202,13 @@ __global__ void __launch_bounds__(kAbThreads) ab_cell_kernel(const AbArgs A, int
             if (W <= 32) {
                 const uint64_t cw = j ? (c_lo >> (2 * j)) | (c_hi << (64 - 2 * j)) : c_lo;
                 const uint32_t nw = j ? (n_lo >> j) | (n_hi << (32 - j)) : n_lo;
-                ab_step<LDS_TAB, true>(abtab_lds, tab_g, zero, 0, W, cw, nw, k, tk, rf, rr, af, ar);
+                tab_step<LDS_TAB, true>(abtab_lds, tab_g, zero, 0, W, cw, nw, k, tk, rf, rr, af, ar);
             } else {
                 for (int c0 = 0; c0 < W; c0 += 32) {
                     const int n = (W - c0) < 32 ? (W - c0) : 32;
                     const uint64_t cw = code_window(A.codes, g0 + j + c0);
                     const uint32_t nw = n_window(A.nmask, g0 + j + c0);
-                    ab_step<LDS_TAB, true>(abtab_lds, tab_g, zero, c0, n, cw, nw, k - c0, tk, rf, rr, af, ar);
+                    tab_step<LDS_TAB, true>(abtab_lds, tab_g, zero, c0, n, cw, nw, k - c0, tk, rf, rr, af, ar);
                 }
             }
             ab_take(br, A.strand_mask, rf, rr, max_raw, -k);
@@ -296,8 +256,7 @@ __global__ void __launch_bounds__(kAbThreads) ab_wave_kernel(const AbArgs A, con
     const double2 *__restrict__ tab_g = A.Pw.tab2 + A.Pw.tab_off[m];
     const uint32_t zero = (uint32_t) W * 4u;
     if (LDS_TAB) {
-        for (int i = threadIdx.x; i < W * 4; i += kAbThreads) abtab_lds[i] = tab_g[i];
-        if (threadIdx.x == 0) abtab_lds[zero] = make_double2(0.0, 0.0);
+        tab_stage<kAbThreads>(abtab_lds, tab_g, W);
         __syncthreads();
     }
     if (!is_long) return;
@@ -319,8 +278,6 @@ __global__ void __launch_bounds__(kAbThreads) ab_wave_kernel(const AbArgs A, con
         ab_put(A.O, hap, (int64_t) m * A.V + v, bq, won ? (int32_t) (key >> 2) - base : 0, won ? (int32_t) (key & 3u) : 0);
     }
 }
-
-size_t ab_up256(size_t x) { return (x + 255) & ~(size_t) 255; }
 
 }  // namespace
 
@@ -355,10 +312,7 @@ int ms_scan_alleles_best(const ms_pwmset *pwms_c, const ms_genome *genome, const
     *out = nullptr;
     if (strand_mask < 1 || strand_mask > 3) { set_error("invalid strand mask %d (1 '+', 2 '-', 3 both)", strand_mask); return MS_ERR_INVALID; }
     if (flags != 0u) { set_error("unknown allele best-site scan flags 0x%x", flags); return MS_ERR_INVALID; }
-    {
-        int n_dev = 0;                                         // (a genome handle cannot exist without a device: say so before asking for one)
-        if (ms_device_count(&n_dev) != MS_OK || n_dev <= 0) { set_error("no usable HIP device; libmotifscan_amd has no CPU fallback"); return MS_ERR_RUNTIME; }
-    }
+    if (!require_device()) return MS_ERR_RUNTIME;
     if (!pwms_c || !genome) { set_error("NULL handle"); return MS_ERR_INVALID; }
     ms_pwmset *pwms = const_cast<ms_pwmset *>(pwms_c);
     const ms_seqset *G = reinterpret_cast<const ms_seqset *>(genome);
@@ -398,15 +352,23 @@ int ms_scan_alleles_best(const ms_pwmset *pwms_c, const ms_genome *genome, const
     std::lock_guard<std::mutex> lk_pwm(pwms->mu);
     MS_HIP(hipSetDevice(c->device));
     {
+        Carve rv;
+        Carve::Slot<double> s_score[2];
+        Carve::Slot<int32_t> s_offset[2];
+        Carve::Slot<int8_t> s_strand[2];
+        for (int h = 0; h < 2; h++) s_score[h] = rv.add<double>(cz);
+        for (int h = 0; h < 2; h++) s_offset[h] = rv.add<int32_t>(cz);
+        for (int h = 0; h < 2; h++) s_strand[h] = rv.add<int8_t>(cz);
         void *blk = nullptr;
         size_t got = 0;
-        if ((rc = pool_alloc(c, 2 * (ab_up256(8 * cz) + ab_up256(4 * cz) + ab_up256(cz)), &blk, &got))) return rc;
+        if ((rc = pool_alloc(c, rv.bytes(), &blk, &got))) return rc;
         res->block = blk;
         res->block_bytes = got;
-        char *p = static_cast<char *>(blk);
-        for (int h = 0; h < 2; h++) { res->d_score[h] = reinterpret_cast<double *>(p); p += ab_up256(8 * cz); }
-        for (int h = 0; h < 2; h++) { res->d_offset[h] = reinterpret_cast<int32_t *>(p); p += ab_up256(4 * cz); }
-        for (int h = 0; h < 2; h++) { res->d_strand[h] = reinterpret_cast<int8_t *>(p); p += ab_up256(cz); }
+        for (int h = 0; h < 2; h++) {
+            res->d_score[h] = Carve::at(blk, s_score[h]);
+            res->d_offset[h] = Carve::at(blk, s_offset[h]);
+            res->d_strand[h] = Carve::at(blk, s_strand[h]);
+        }
     }
     ms_allelebest *raw = res.release();
     if (V == 0) { *out = raw; return MS_OK; }
@@ -418,38 +380,25 @@ int ms_scan_alleles_best(const ms_pwmset *pwms_c, const ms_genome *genome, const
     chunk = std::min<int64_t>(chunk, V);
     const int64_t n_chunks = (V + chunk - 1) / chunk;
 
-    const size_t Vz = (size_t) V, Pz = (size_t) std::max<int32_t>(P, 1);
-    const size_t a_words = (size_t) ((A + 31) / 32);            // mask words of the alt plane; twice as many code words
-    const size_t b_chrom = ab_up256(4 * Vz), b_pos = ab_up256(8 * Vz), b_rlen = ab_up256(4 * Vz), b_aoff = ab_up256(8 * (Vz + 1)),
-                 b_roff = ab_up256(8 * (Vz + 1)), b_alt = ab_up256((size_t) std::max<int64_t>(A, 1)), b_ref = ab_up256((size_t) std::max<int64_t>(Rn, 1)),
-                 b_acode = ab_up256(4 * (2 * a_words + kAlPlanePad)), b_amask = ab_up256(4 * (a_words + kAlPlanePad)), b_rec = ab_up256(sizeof(AlRec) * Vz),
-                 b_mis = ab_up256(Vz), b_ok = ab_up256(Pz), b_cand = ab_up256(8 * std::max<size_t>(cand.size(), 1));
+    Carve cv;
+    const AlSlots us = al_upload_slots(cv, V, A, Rn);
+    const auto s_ok = cv.add<uint8_t>((size_t) std::max<int32_t>(P, 1));
+    const auto s_cand = cv.add<int64_t>(std::max<size_t>(cand.size(), 1));
     void *wblk = nullptr;
     size_t wgot = 0;
-    if ((rc = pool_alloc(c, b_chrom + b_pos + b_rlen + b_aoff + b_roff + b_alt + b_ref + b_acode + b_amask + b_rec + b_mis + b_ok + b_cand, &wblk, &wgot))) {
+    if ((rc = pool_alloc(c, cv.bytes(), &wblk, &wgot))) {
         ms_allelebest_free(raw);
         return rc;
     }
-    char *b = static_cast<char *>(wblk);
-    int32_t *d_chrom = reinterpret_cast<int32_t *>(b); b += b_chrom;
-    int64_t *d_pos = reinterpret_cast<int64_t *>(b); b += b_pos;
-    int32_t *d_rlen = reinterpret_cast<int32_t *>(b); b += b_rlen;
-    int64_t *d_aoff = reinterpret_cast<int64_t *>(b); b += b_aoff;
-    int64_t *d_roff = reinterpret_cast<int64_t *>(b); b += b_roff;
-    uint8_t *d_alt = reinterpret_cast<uint8_t *>(b); b += b_alt;
-    uint8_t *d_ref = reinterpret_cast<uint8_t *>(b); b += b_ref;
-    uint32_t *d_acode = reinterpret_cast<uint32_t *>(b); b += b_acode;
-    uint32_t *d_amask = reinterpret_cast<uint32_t *>(b); b += b_amask;
-    AlRec *d_rec = reinterpret_cast<AlRec *>(b); b += b_rec;
-    uint8_t *d_mis = reinterpret_cast<uint8_t *>(b); b += b_mis;
-    uint8_t *d_ok = reinterpret_cast<uint8_t *>(b); b += b_ok;
-    int64_t *d_cand = reinterpret_cast<int64_t *>(b);
-    auto fail = [&](int code) { pool_free(c, wblk, wgot); ms_allelebest_free(raw); return code; };
+    const AlDev U = al_upload_at(wblk, us);
+    uint8_t *d_ok = Carve::at(wblk, s_ok);
+    int64_t *d_cand = Carve::at(wblk, s_cand);
+    auto fail = [&](int code) { (void) hipStreamSynchronize(st); pool_free(c, wblk, wgot); ms_allelebest_free(raw); return code; };   // (nothing queued may still read the blocks)
     auto hip_fail = [&](hipError_t e, const char *what) { set_error("%s failed: %s", what, hipGetErrorString(e)); return fail(e == hipErrorOutOfMemory ? MS_ERR_NOMEM : MS_ERR_RUNTIME); };
 
     AbArgs K;
-    K.codes = G->d_codes; K.nmask = G->d_nmask; K.acodes = d_acode; K.amask = d_amask; K.n_bases = G->n_bases;
-    K.Pw = dev_pwm(pwms); K.scorable = d_ok; K.rec = d_rec; K.V = V; K.strand_mask = strand_mask;
+    K.codes = G->d_codes; K.nmask = G->d_nmask; K.acodes = U.acode; K.amask = U.amask; K.n_bases = G->n_bases;
+    K.Pw = dev_pwm(pwms); K.scorable = d_ok; K.rec = U.rec; K.V = V; K.strand_mask = strand_mask;
     for (int h = 0; h < 2; h++) { K.O.score[h] = raw->d_score[h]; K.O.offset[h] = raw->d_offset[h]; K.O.strand[h] = raw->d_strand[h]; }
     const int max_width = pwms->max_width;
     const int min_width = P > 0 ? *std::min_element(pwms->widths.begin(), pwms->widths.end()) : 0;
@@ -464,26 +413,9 @@ int ms_scan_alleles_best(const ms_pwmset *pwms_c, const ms_genome *genome, const
     }
 
     (void) hipEventRecord(c->ev[0], st);
-    he = hipMemcpyAsync(d_chrom, chrom, 4 * (size_t) V, hipMemcpyHostToDevice, st);
-    if (he == hipSuccess) he = hipMemcpyAsync(d_pos, pos, 8 * (size_t) V, hipMemcpyHostToDevice, st);
-    if (he == hipSuccess) he = hipMemcpyAsync(d_rlen, ref_len, 4 * (size_t) V, hipMemcpyHostToDevice, st);
-    if (he == hipSuccess) he = hipMemcpyAsync(d_aoff, alt_offsets, 8 * ((size_t) V + 1), hipMemcpyHostToDevice, st);
-    if (he == hipSuccess && ref_bases) he = hipMemcpyAsync(d_roff, ref_off.data(), 8 * ((size_t) V + 1), hipMemcpyHostToDevice, st);
-    if (he == hipSuccess && A > 0) he = hipMemcpyAsync(d_alt, alt_bases, (size_t) A, hipMemcpyHostToDevice, st);
-    if (he == hipSuccess && Rn > 0) he = hipMemcpyAsync(d_ref, ref_bases, (size_t) Rn, hipMemcpyHostToDevice, st);
+    he = al_upload(G, U, chrom, pos, ref_len, alt_bases, alt_offsets, ref_bases, ref_off, V, A, Rn, raw->mismatch.data(), st);
     if (he == hipSuccess && P > 0) he = hipMemcpyAsync(d_ok, ok.data(), (size_t) P, hipMemcpyHostToDevice, st);
     if (he == hipSuccess && !cand.empty()) he = hipMemcpyAsync(d_cand, cand.data(), 8 * cand.size(), hipMemcpyHostToDevice, st);
-    if (he == hipSuccess) he = hipMemsetAsync(d_acode, 0, b_acode + b_amask, st);       // (the two planes lie side by side: their padding too)
-    if (he == hipSuccess && A > 0) {
-        hipLaunchKernelGGL(al_pack_kernel, dim3((unsigned) ((a_words + 255) / 256)), dim3(256), 0, st, d_alt, A, d_acode, d_amask);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess) {
-        hipLaunchKernelGGL(al_prep_kernel, dim3((unsigned) ((V + 255) / 256)), dim3(256), 0, st, G->d_codes, G->d_nmask, G->d_offsets, d_chrom, d_pos,
-                           d_rlen, d_aoff, ref_bases ? d_ref : (const uint8_t *) nullptr, d_roff, V, d_rec, d_mis);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess) he = hipMemcpyAsync(raw->mismatch.data(), d_mis, (size_t) V, hipMemcpyDeviceToHost, st);
     if (he != hipSuccess) return hip_fail(he, "variant upload");
 
     for (int64_t k = 0; P > 0 && k < n_chunks; k++) {

@@ -14,7 +14,8 @@
 // variant-major, ref before alt, start ascending: item order IS the output order.  A block owns one motif and a TILE of kAlTile
 // variants.  A variant's item count depends on r, a and its distance to the chromosome's ends, so the tile keeps the exclusive prefix
 // of its variants' item counts in LDS, and a thread finds the variant of its item of the round by a 7-step binary search in it.
-// Placement is ms_variants.hip's: ballot prefix inside the wave, the waves' totals through LDS, no sort and no atomic on the records.
+// Placement is ms_scan_variants's, the same code (place_round, ms_allele_dev.h): ballot prefix inside the wave, the waves' totals through
+// LDS, no sort and no atomic on the records.
 //
 // Splice.  The alt bytes of all variants are packed by a prep kernel into a 2-bit code plane and a non-ACGT mask plane in the genome's
 // own layout (ms_device.h), so code_window / n_window read them too.  A 32-column step of an alt-haplotype window is put together of
@@ -22,8 +23,10 @@
 // one side of the allele, and every step of a ref-haplotype window, is one read.
 //
 // Order without a sort: pass 1 counts the records of every (motif, tile), an exclusive prefix sum and the per-motif totals place every
-// block, pass 2 recomputes and writes; variants go in chunks that bound the count arrays (ms_variants.hip: the same scheme and the same
-// ms_debug_varscan_chunk).  One long allele makes its tile's block long: no balancing is done for it.
+// block, pass 2 recomputes and writes; variants go in chunks that bound the count arrays.  That driver is place_records (ms_variants.hip,
+// declared in ms_handles.h; the chunk plan is place_chunks of ms_place.h under the same ms_debug_varscan_chunk): this file gives it the
+// two launches and the allocation of the record arrays.  The upload of the variants is al_upload (ms_allele_dev.h), shared with
+// ms_allelebest.hip and ms_personal.hip.  One long allele makes its tile's block long: no balancing is done for it.
 #include <algorithm>
 #include <memory>
 #include <type_traits>
@@ -32,22 +35,13 @@
 #include "ms_device.h"
 #include "ms_handles.h"
 
-struct ms_allelescan {
-    int device = 0;
-    int32_t P = 0;
-    int64_t V = 0;
-    int64_t n = 0;                                    // records
-    void *block = nullptr;                            // one pooled device block holding the record arrays
-    size_t block_bytes = 0;
+struct ms_allelescan : ms::RecHead {
     int64_t *d_variant = nullptr;
     int64_t *d_start = nullptr;
     double *d_score = nullptr;
     int8_t *d_strand = nullptr;
     uint8_t *d_allele = nullptr;
-    std::vector<int64_t> motif_offsets;               // [P+1]
-    std::vector<int64_t> gained, lost;                // [P], counted on the device
     std::vector<uint8_t> mismatch;                    // [V]
-    double device_ms = 0.0;                           // first launch -> last kernel done
 };
 
 namespace ms {
@@ -97,10 +91,7 @@ __global__ void __launch_bounds__(kAlThreads) al_scan_kernel(const uint32_t *__r
     if ((W <= kAlTabMaxW) != LDS_TAB) return;
     const double2 *__restrict__ tab_g = Pw.tab2 + Pw.tab_off[m];
     const uint32_t zero = (uint32_t) W * 4u;
-    if (LDS_TAB) {
-        for (int i = threadIdx.x; i < W * 4; i += kAlThreads) atab_lds[i] = tab_g[i];
-        if (threadIdx.x == 0) atab_lds[zero] = make_double2(0.0, 0.0);
-    }
+    if (LDS_TAB) tab_stage<kAlThreads>(atab_lds, tab_g, W);
     const int64_t tile = (int64_t) blockIdx.x, row = (int64_t) m * gridDim.x;
     const int64_t vl0 = tile * kAlTile;                        // first variant of the tile, in the chunk
     const int n_local = (int) (nv - vl0 < kAlTile ? nv - vl0 : kAlTile);
@@ -126,7 +117,6 @@ __global__ void __launch_bounds__(kAlThreads) al_scan_kernel(const uint32_t *__r
     __syncthreads();
     const uint32_t n_items = s_pre[kAlTile];
     const double max_raw = Pw.max_raw[m], cutoff = Pw.cutoff[m], floor_ = Pw.raw_floor[m];
-    const uint64_t lt = (1ULL << lane) - 1ULL;
     uint64_t run = 0;                                          // records of the tile's earlier rounds (+ the tile's place when filling)
     if (FILL) run = row_base[m] + (tile_excl[row + tile] - tile_excl[row]);
     int round = 0;
@@ -155,6 +145,9 @@ __global__ void __launch_bounds__(kAlThreads) al_scan_kernel(const uint32_t *__r
                     cw = code_window(codes, q.g + rel + c0);
                     nw = n_window(nmask, q.g + rel + c0);
                 }
+                // tab_step<LDS_TAB, false> (ms_allele_dev.h) written out: called through the function, hipcc schedules this kernel's walk
+                // differently (its disassembly changes) and the scan measures 0.9 % slower; the code is to stay as measured.  A change
+                // to the step is made in both places.
                 const uint32_t skip = nw | ~low_mask(n);                               // bit c: column c0 + c adds nothing
                 // eight columns a step while more than four are left, then four: the reads of a step are issued together
                 auto columns = [&](auto width, int c1) {
@@ -185,19 +178,10 @@ __global__ void __launch_bounds__(kAlThreads) al_scan_kernel(const uint32_t *__r
             if (strand_mask & 1) hit_f = judge_one(fw, max_raw, cutoff, floor_, sc_f);
             if (strand_mask & 2) hit_r = judge_one(rv, max_raw, cutoff, floor_, sc_r);
         }
-        const unsigned long long bf = __ballot(hit_f), br = __ballot(hit_r);
-        const int buf = round & 1;                             // (two buffers: a wave may write round r + 1's total while another still reads round r's)
-        if (lane == 0u) s_wtot[buf][wave] = (uint32_t) (__popcll(bf) + __popcll(br));
-        __syncthreads();
-        uint32_t before = 0u, all = 0u;
-#pragma unroll
-        for (uint32_t w = 0; w < (uint32_t) (kAlThreads / 64); w++) {
-            const uint32_t x = s_wtot[buf][w];
-            all += x;
-            if (w < wave) before += x;
-        }
+        uint32_t before, all;
+        place_round<kAlThreads>(s_wtot, round, hit_f, hit_r, before, all);
         if (FILL) {
-            uint64_t d = run + before + (uint64_t) (__popcll(bf & lt) + __popcll(br & lt));
+            uint64_t d = run + before;
             const int64_t v = v0 + vl0 + vl;
             if (hit_f && d < O.cap) {
                 O.variant[d] = v; O.start[d] = pos[v] + rel; O.strand[d] = (int8_t) 1; O.allele[d] = (uint8_t) allele; O.score[d] = sc_f;
@@ -216,19 +200,9 @@ __global__ void __launch_bounds__(kAlThreads) al_scan_kernel(const uint32_t *__r
         if (gained) {
             __syncthreads();
             const uint32_t f = (int) threadIdx.x < n_local ? s_flag[threadIdx.x] : 0u;
-            const unsigned long long bl = __ballot(f == 1u), bg = __ballot(f == 2u);    // records of the ref haplotype only / the alt only
-            if (lane == 0u) {
-                if (bl) atomicAdd(&lost[m], (unsigned long long) __popcll(bl));            // (integer sums: the same in any order)
-                if (bg) atomicAdd(&gained[m], (unsigned long long) __popcll(bg));
-            }
+            tally_motif(f == 1u, f == 2u, &lost[m], &gained[m]);                        // records of the ref haplotype only / the alt only
         }
     }
-}
-
-// tot[m] = records of motif m in the chunk, out of the prefix sums of its tiles (tile_excl has one entry more than there are tiles)
-__global__ void __launch_bounds__(256) al_row_total_kernel(const uint64_t *__restrict__ tile_excl, int64_t ntx, int32_t P, uint64_t *__restrict__ tot) {
-    const int32_t m = (int32_t) (blockIdx.x * blockDim.x + threadIdx.x);
-    if (m < P) tot[m] = tile_excl[(int64_t) (m + 1) * ntx] - tile_excl[(int64_t) m * ntx];
 }
 
 struct AlLaunch {
@@ -259,8 +233,6 @@ int launch_al_scan(const AlLaunch &L, int64_t v0, int64_t nv, uint32_t *tile_cnt
     return MS_OK;
 }
 
-size_t al_up256(size_t x) { return (x + 255) & ~(size_t) 255; }
-
 }  // namespace
 
 void allelescan_dims(int32_t out[3]) {
@@ -276,12 +248,7 @@ using namespace ms;
 extern "C" {
 
 void ms_allelescan_free(ms_allelescan *r) {
-    if (!r) return;
-    if (r->block) {
-        (void) hipSetDevice(r->device);
-        DeviceCtx *c = nullptr;
-        if (get_ctx(r->device, &c) == MS_OK) pool_free(c, r->block, r->block_bytes); else (void) hipFree(r->block);
-    }
+    rec_release(r);
     delete r;
 }
 
@@ -292,10 +259,7 @@ int ms_scan_alleles(const ms_pwmset *pwms_c, const ms_genome *genome, const int3
     *out = nullptr;
     if (strand_mask < 1 || strand_mask > 3) { set_error("invalid strand mask %d (1 '+', 2 '-', 3 both)", strand_mask); return MS_ERR_INVALID; }
     if (flags != 0u) { set_error("unknown allele scan flags 0x%x", flags); return MS_ERR_INVALID; }
-    {
-        int n_dev = 0;                                         // (a genome handle cannot exist without a device: say so before asking for one)
-        if (ms_device_count(&n_dev) != MS_OK || n_dev <= 0) { set_error("no usable HIP device; libmotifscan_amd has no CPU fallback"); return MS_ERR_RUNTIME; }
-    }
+    if (!require_device()) return MS_ERR_RUNTIME;
     if (!pwms_c || !genome) { set_error("NULL handle"); return MS_ERR_INVALID; }
     ms_pwmset *pwms = const_cast<ms_pwmset *>(pwms_c);
     const ms_seqset *G = reinterpret_cast<const ms_seqset *>(genome);
@@ -324,51 +288,21 @@ int ms_scan_alleles(const ms_pwmset *pwms_c, const ms_genome *genome, const int3
     const hipStream_t st = c->stream;
 
     // ---- chunks of variants: at most kAlMaxTiles (motif, tile) counts at a time
-    int64_t chunk = varscan_chunk_setting();
-    if (chunk <= 0) chunk = std::max<int64_t>(1, kAlMaxTiles / std::max<int32_t>(P, 1)) * kAlTile;
-    chunk = std::min<int64_t>(chunk, std::max<int64_t>(V, 1));
-    const int64_t n_chunks = V > 0 ? (V + chunk - 1) / chunk : 0;
-    const int64_t ntx_max = (chunk + kAlTile - 1) / kAlTile;
-    const size_t n_cells = (size_t) ntx_max * (size_t) std::max<int32_t>(P, 1) + 1;
-
-    size_t scan_tmp = 0;
-    if ((rc = exclusive_sum_u32(nullptr, &scan_tmp, nullptr, nullptr, n_cells, st))) return rc;
-    const size_t Vz = (size_t) std::max<int64_t>(V, 1), Pz = (size_t) std::max<int32_t>(P, 1), Kz = (size_t) std::max<int64_t>(n_chunks, 1);
-    const size_t a_words = (size_t) ((A + 31) / 32);            // mask words of the alt plane; twice as many code words
-    const size_t b_chrom = al_up256(4 * Vz), b_pos = al_up256(8 * Vz), b_rlen = al_up256(4 * Vz), b_aoff = al_up256(8 * (Vz + 1)),
-                 b_roff = al_up256(8 * (Vz + 1)), b_alt = al_up256((size_t) std::max<int64_t>(A, 1)), b_ref = al_up256((size_t) std::max<int64_t>(Rn, 1)),
-                 b_acode = al_up256(4 * (2 * a_words + kAlPlanePad)), b_amask = al_up256(4 * (a_words + kAlPlanePad)), b_rec = al_up256(sizeof(AlRec) * Vz),
-                 b_mis = al_up256(Vz), b_cnt = al_up256(4 * n_cells), b_excl = al_up256(8 * n_cells), b_tot = al_up256(8 * Kz * Pz), b_gl = al_up256(16 * Pz),
-                 b_tmp = al_up256(std::max<size_t>(scan_tmp, 1));
+    const PlaceChunks ch = place_chunks(V, P, kAlTile, kAlMaxTiles, varscan_chunk_setting());
+    Carve cv;
+    const AlSlots us = al_upload_slots(cv, V, A, Rn);
+    PlaceSlots ps;
+    if ((rc = place_slots(cv, ch, P, st, &ps))) return rc;
     void *wblk = nullptr;
     size_t wgot = 0;
-    if ((rc = pool_alloc(c, b_chrom + b_pos + b_rlen + b_aoff + b_roff + b_alt + b_ref + b_acode + b_amask + b_rec + b_mis + b_cnt + b_excl + 2 * b_tot + b_gl + b_tmp,
-                         &wblk, &wgot))) return rc;
-    char *b = static_cast<char *>(wblk);
-    int32_t *d_chrom = reinterpret_cast<int32_t *>(b); b += b_chrom;
-    int64_t *d_pos = reinterpret_cast<int64_t *>(b); b += b_pos;
-    int32_t *d_rlen = reinterpret_cast<int32_t *>(b); b += b_rlen;
-    int64_t *d_aoff = reinterpret_cast<int64_t *>(b); b += b_aoff;
-    int64_t *d_roff = reinterpret_cast<int64_t *>(b); b += b_roff;
-    uint8_t *d_alt = reinterpret_cast<uint8_t *>(b); b += b_alt;
-    uint8_t *d_ref = reinterpret_cast<uint8_t *>(b); b += b_ref;
-    uint32_t *d_acode = reinterpret_cast<uint32_t *>(b); b += b_acode;
-    uint32_t *d_amask = reinterpret_cast<uint32_t *>(b); b += b_amask;
-    AlRec *d_rec = reinterpret_cast<AlRec *>(b); b += b_rec;
-    uint8_t *d_mis = reinterpret_cast<uint8_t *>(b); b += b_mis;
-    uint32_t *d_cnt = reinterpret_cast<uint32_t *>(b); b += b_cnt;
-    uint64_t *d_excl = reinterpret_cast<uint64_t *>(b); b += b_excl;
-    uint64_t *d_tot = reinterpret_cast<uint64_t *>(b); b += b_tot;          // [chunks][P] records of the motif in the chunk
-    uint64_t *d_base = reinterpret_cast<uint64_t *>(b); b += b_tot;         // [chunks][P] where they go
-    unsigned long long *d_gained = reinterpret_cast<unsigned long long *>(b);
-    unsigned long long *d_lost = d_gained + Pz; b += b_gl;
-    void *d_tmp = b;
+    if ((rc = pool_alloc(c, cv.bytes(), &wblk, &wgot))) return rc;
+    const AlDev U = al_upload_at(wblk, us);
     ms_allelescan *raw = res.release();
-    auto fail = [&](int code) { pool_free(c, wblk, wgot); ms_allelescan_free(raw); return code; };
+    auto fail = [&](int code) { (void) hipStreamSynchronize(st); pool_free(c, wblk, wgot); ms_allelescan_free(raw); return code; };   // (nothing queued may still read the blocks)
     auto hip_fail = [&](hipError_t e, const char *what) { set_error("%s failed: %s", what, hipGetErrorString(e)); return fail(e == hipErrorOutOfMemory ? MS_ERR_NOMEM : MS_ERR_RUNTIME); };
 
     AlLaunch L;
-    L.G = G; L.acodes = d_acode; L.amask = d_amask; L.Pw = dev_pwm(pwms); L.rec = d_rec; L.pos = d_pos; L.strand_mask = strand_mask;
+    L.G = G; L.acodes = U.acode; L.amask = U.amask; L.Pw = dev_pwm(pwms); L.rec = U.rec; L.pos = U.pos; L.strand_mask = strand_mask;
     L.max_width = pwms->max_width;
     L.min_width = P > 0 ? *std::min_element(pwms->widths.begin(), pwms->widths.end()) : 0;
     int lds_width = 0;
@@ -383,117 +317,48 @@ int ms_scan_alleles(const ms_pwmset *pwms_c, const ms_genome *genome, const int3
 
     (void) hipEventRecord(c->ev[0], st);
     if (V > 0) {
-        he = hipMemcpyAsync(d_chrom, chrom, 4 * (size_t) V, hipMemcpyHostToDevice, st);
-        if (he == hipSuccess) he = hipMemcpyAsync(d_pos, pos, 8 * (size_t) V, hipMemcpyHostToDevice, st);
-        if (he == hipSuccess) he = hipMemcpyAsync(d_rlen, ref_len, 4 * (size_t) V, hipMemcpyHostToDevice, st);
-        if (he == hipSuccess) he = hipMemcpyAsync(d_aoff, alt_offsets, 8 * ((size_t) V + 1), hipMemcpyHostToDevice, st);
-        if (he == hipSuccess && ref_bases) he = hipMemcpyAsync(d_roff, ref_off.data(), 8 * ((size_t) V + 1), hipMemcpyHostToDevice, st);
-        if (he == hipSuccess && A > 0) he = hipMemcpyAsync(d_alt, alt_bases, (size_t) A, hipMemcpyHostToDevice, st);
-        if (he == hipSuccess && Rn > 0) he = hipMemcpyAsync(d_ref, ref_bases, (size_t) Rn, hipMemcpyHostToDevice, st);
-        if (he == hipSuccess) he = hipMemsetAsync(d_acode, 0, b_acode + b_amask, st);       // (the two planes lie side by side: their padding too)
-        if (he == hipSuccess && A > 0) {
-            hipLaunchKernelGGL(al_pack_kernel, dim3((unsigned) ((a_words + 255) / 256)), dim3(256), 0, st, d_alt, A, d_acode, d_amask);
-            he = hipGetLastError();
-        }
-        if (he == hipSuccess) {
-            hipLaunchKernelGGL(al_prep_kernel, dim3((unsigned) ((V + 255) / 256)), dim3(256), 0, st, G->d_codes, G->d_nmask, G->d_offsets, d_chrom, d_pos,
-                               d_rlen, d_aoff, ref_bases ? d_ref : (const uint8_t *) nullptr, d_roff, V, d_rec, d_mis);
-            he = hipGetLastError();
-        }
-        if (he == hipSuccess) he = hipMemcpyAsync(raw->mismatch.data(), d_mis, (size_t) V, hipMemcpyDeviceToHost, st);
+        he = al_upload(G, U, chrom, pos, ref_len, alt_bases, alt_offsets, ref_bases, ref_off, V, A, Rn, raw->mismatch.data(), st);
         if (he != hipSuccess) return hip_fail(he, "variant upload");
     }
-    he = hipMemsetAsync(d_gained, 0, 16 * Pz, st);
-    if (he != hipSuccess) return hip_fail(he, "memset");
-    const AlOut none{};
 
-    // one chunk's counts and their prefix sums (tally: with the gained / lost numbers -- the first time only)
-    auto count_chunk = [&](int64_t k, bool tally) -> int {
-        const int64_t v0 = k * chunk, nv = std::min(chunk, V - v0), ntx = (nv + kAlTile - 1) / kAlTile;
-        const size_t cells = (size_t) ntx * (size_t) P;
-        hipError_t e = hipMemsetAsync(d_cnt, 0, 4 * (cells + 1), st);
-        if (e != hipSuccess) { set_error("memset failed: %s", hipGetErrorString(e)); return MS_ERR_RUNTIME; }
-        int r = launch_al_scan<false>(L, v0, nv, d_cnt, nullptr, nullptr, tally ? d_gained : nullptr, tally ? d_lost : nullptr, none, st);
-        if (r) return r;
-        size_t tmp = scan_tmp;
-        return exclusive_sum_u32(d_tmp, &tmp, d_cnt, d_excl, cells + 1, st);
+    AlOut O{};                                                 // (no arrays while counting)
+    PlaceCalls calls;
+    calls.count = [&](int64_t v0, int64_t nv, uint32_t *tile_cnt, unsigned long long *gained, unsigned long long *lost) {
+        return launch_al_scan<false>(L, v0, nv, tile_cnt, nullptr, nullptr, gained, lost, O, st);
     };
-
-    std::vector<uint64_t> h_tot, h_base;
-    if (V > 0 && P > 0) {
-        // ---- pass 1: every chunk counted
-        for (int64_t k = 0; k < n_chunks; k++) {
-            if ((rc = count_chunk(k, true))) return fail(rc);
-            const int64_t nv = std::min(chunk, V - k * chunk), ntx = (nv + kAlTile - 1) / kAlTile;
-            hipLaunchKernelGGL(al_row_total_kernel, dim3((unsigned) ((P + 255) / 256)), dim3(256), 0, st, d_excl, ntx, P, d_tot + (size_t) k * P);
-            if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "row totals");
-        }
-        try { h_tot.resize((size_t) n_chunks * P); h_base.resize((size_t) n_chunks * P); }
-        catch (const std::bad_alloc &) { set_error("out of host memory"); return fail(MS_ERR_NOMEM); }
-        he = hipMemcpyAsync(h_tot.data(), d_tot, 8 * h_tot.size(), hipMemcpyDeviceToHost, st);
-        if (he == hipSuccess) he = hipStreamSynchronize(st);
-        if (he != hipSuccess) return hip_fail(he, "allele count pass");
-        // ---- the motif offsets, and where every (chunk, motif) run of records starts
-        uint64_t at = 0;
-        for (int32_t m = 0; m < P; m++) {
-            raw->motif_offsets[(size_t) m] = (int64_t) at;
-            for (int64_t k = 0; k < n_chunks; k++) { h_base[(size_t) k * P + m] = at; at += h_tot[(size_t) k * P + m]; }
-        }
-        raw->motif_offsets[(size_t) P] = (int64_t) at;
-        raw->n = (int64_t) at;
-    }
-    {
-        const size_t n = (size_t) raw->n, nz = std::max<size_t>(n, 1);
+    calls.fill = [&](int64_t v0, int64_t nv, const uint64_t *tile_excl, const uint64_t *row_base) {
+        return launch_al_scan<true>(L, v0, nv, nullptr, tile_excl, row_base, nullptr, nullptr, O, st);
+    };
+    calls.alloc = [&](size_t n) {
+        const size_t nz = std::max<size_t>(n, 1);
+        Carve rv;
+        const auto s_variant = rv.add<int64_t>(nz), s_start = rv.add<int64_t>(nz);
+        const auto s_score = rv.add<double>(nz);
+        const auto s_strand = rv.add<int8_t>(nz);
+        const auto s_allele = rv.add<uint8_t>(nz);
         void *blk = nullptr;
         size_t got = 0;
-        if ((rc = pool_alloc(c, 3 * al_up256(8 * nz) + 2 * al_up256(nz), &blk, &got))) return fail(rc);
+        if (int r = pool_alloc(c, rv.bytes(), &blk, &got)) return r;
         raw->block = blk;
         raw->block_bytes = got;
-        char *p = static_cast<char *>(blk);
-        raw->d_variant = reinterpret_cast<int64_t *>(p); p += al_up256(8 * nz);
-        raw->d_start = reinterpret_cast<int64_t *>(p); p += al_up256(8 * nz);
-        raw->d_score = reinterpret_cast<double *>(p); p += al_up256(8 * nz);
-        raw->d_strand = reinterpret_cast<int8_t *>(p); p += al_up256(nz);
-        raw->d_allele = reinterpret_cast<uint8_t *>(p);
-    }
-    if (raw->n > 0) {
-        // ---- pass 2: every chunk filled (its counts made again unless they are still there)
-        AlOut O;
-        O.variant = raw->d_variant; O.start = raw->d_start; O.score = raw->d_score; O.strand = raw->d_strand; O.allele = raw->d_allele;
-        O.cap = (uint64_t) raw->n;
-        he = hipMemcpyAsync(d_base, h_base.data(), 8 * h_base.size(), hipMemcpyHostToDevice, st);
-        if (he != hipSuccess) return hip_fail(he, "upload of the record offsets");
-        for (int64_t k = 0; k < n_chunks; k++) {
-            if (n_chunks > 1 && (rc = count_chunk(k, false))) return fail(rc);
-            const int64_t v0 = k * chunk, nv = std::min(chunk, V - v0);
-            if ((rc = launch_al_scan<true>(L, v0, nv, nullptr, d_excl, d_base + (size_t) k * P, nullptr, nullptr, O, st))) return fail(rc);
-        }
-    }
-    (void) hipEventRecord(c->ev[1], st);
-    he = hipSuccess;
-    if (P > 0) he = hipMemcpyAsync(raw->gained.data(), d_gained, 8 * (size_t) P, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess && P > 0) he = hipMemcpyAsync(raw->lost.data(), d_lost, 8 * (size_t) P, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess) he = hipStreamSynchronize(st);
-    if (he != hipSuccess) return hip_fail(he, "allele scan");
-    float ms01 = 0;
-    (void) hipEventElapsedTime(&ms01, c->ev[0], c->ev[1]);
-    raw->device_ms = ms01;
+        O.variant = raw->d_variant = Carve::at(blk, s_variant);
+        O.start = raw->d_start = Carve::at(blk, s_start);
+        O.score = raw->d_score = Carve::at(blk, s_score);
+        O.strand = raw->d_strand = Carve::at(blk, s_strand);
+        O.allele = raw->d_allele = Carve::at(blk, s_allele);
+        O.cap = (uint64_t) n;
+        return MS_OK;
+    };
+    if ((rc = place_records(c, ch, kAlTile, wblk, ps, "allele", calls, raw))) return fail(rc);
     pool_free(c, wblk, wgot);
     *out = raw;
     return MS_OK;
 }
 
-int ms_allelescan_num_sites(const ms_allelescan *r, int64_t *n) {
-    if (!r || !n) { set_error("NULL argument"); return MS_ERR_INVALID; }
-    *n = r->n;
-    return MS_OK;
-}
-
-int ms_allelescan_motif_offsets(const ms_allelescan *r, int64_t *out) {
-    if (!r || !out) { set_error("NULL argument"); return MS_ERR_INVALID; }
-    std::copy(r->motif_offsets.begin(), r->motif_offsets.end(), out);
-    return MS_OK;
-}
+int ms_allelescan_num_sites(const ms_allelescan *r, int64_t *n) { return rec_num_sites(r, n); }
+int ms_allelescan_motif_offsets(const ms_allelescan *r, int64_t *out) { return rec_motif_offsets(r, out); }
+int ms_allelescan_motif_counts(const ms_allelescan *r, int64_t *gained, int64_t *lost) { return rec_motif_counts(r, gained, lost); }
+int ms_allelescan_device_ms(const ms_allelescan *r, double *ms) { return rec_device_ms(r, ms); }
 
 int ms_allelescan_sites(const ms_allelescan *r, int64_t *variant, uint8_t *allele, int64_t *start, int8_t *strand, double *score) {
     if (!r) { set_error("NULL argument"); return MS_ERR_INVALID; }
@@ -508,22 +373,9 @@ int ms_allelescan_sites(const ms_allelescan *r, int64_t *variant, uint8_t *allel
     return MS_OK;
 }
 
-int ms_allelescan_motif_counts(const ms_allelescan *r, int64_t *gained, int64_t *lost) {
-    if (!r) { set_error("NULL argument"); return MS_ERR_INVALID; }
-    if (gained) std::copy(r->gained.begin(), r->gained.end(), gained);
-    if (lost) std::copy(r->lost.begin(), r->lost.end(), lost);
-    return MS_OK;
-}
-
 int ms_allelescan_ref_mismatch(const ms_allelescan *r, uint8_t *out) {
     if (!r || (!out && r->V > 0)) { set_error("NULL argument"); return MS_ERR_INVALID; }
     std::copy(r->mismatch.begin(), r->mismatch.end(), out);
-    return MS_OK;
-}
-
-int ms_allelescan_device_ms(const ms_allelescan *r, double *ms) {
-    if (!r || !ms) { set_error("NULL argument"); return MS_ERR_INVALID; }
-    *ms = r->device_ms;
     return MS_OK;
 }
 

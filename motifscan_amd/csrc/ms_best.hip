@@ -190,7 +190,6 @@ __global__ void __launch_bounds__(256) best_fill_kernel(const int32_t *__restric
     put_best(score, pos, strand, (int64_t) motifs[blockIdx.y] * R + r, 0.0, kNoKey);
 }
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t) 255; }
 
 }  // namespace
 
@@ -215,10 +214,7 @@ void ms_best_free(ms_best *b) {
 int ms_scan_best(const ms_pwmset *pwms_c, const ms_seqset *seqs, int strand_mask, uint32_t flags, ms_best **out) {
     if (!out) { set_error("out is NULL"); return MS_ERR_INVALID; }
     *out = nullptr;
-    {
-        int n_dev = 0;
-        if (ms_device_count(&n_dev) != MS_OK || n_dev <= 0) { set_error("no usable HIP device; libmotifscan_amd has no CPU fallback"); return MS_ERR_RUNTIME; }
-    }
+    if (!require_device()) return MS_ERR_RUNTIME;
     if (!pwms_c || !seqs) { set_error("NULL handle"); return MS_ERR_INVALID; }
     if (strand_mask < 1 || strand_mask > 3) { set_error("invalid strand mask %d (1 '+', 2 '-', 3 both)", strand_mask); return MS_ERR_INVALID; }
     if (flags != 0u) { set_error("unknown best-site scan flags 0x%x", flags); return MS_ERR_INVALID; }

@@ -4,12 +4,14 @@
 // host-streamed sweeps), ms_best.hip (best window per cell), ms_allelebest.hip (best window per variant haplotype), ms_pairs.hip (motif pairs over a result's hits), ms_scorehist.hip (score histogram of every window),
 // ms_personal.hip (a variant set spliced into a new resident genome, and the lift map between the two), ms_sitestack.hip (base counts per
 // motif column over a result's sites), ms_ranksum.hip (rank sums and passing-region counts over best-site matrices), ms_affinity.hip (the
-// summed likelihood ratio of every cell), ms_shuffle.hip (a sequence set shuffled into a new one: mono- and dinucleotide controls).
+// summed likelihood ratio of every cell), ms_shuffle.hip (a sequence set shuffled into a new one: mono- and dinucleotide controls),
+// ms_variants.hip and ms_alleles.hip (the record scans over variants: one placement driver, place_records, and one handle head, RecHead).
 #pragma once
 #include <sched.h>
 #include <atomic>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -18,8 +20,21 @@
 #include <vector>
 
 #include "ms_kernels.h"
+#include "ms_place.h"
 
 namespace ms {
+
+// sizes of the arrays carved out of one pooled block: 256-byte slots (Carve, ms_place.h)
+inline size_t up256(size_t x) { return Carve::up(x); }
+
+// false, with the error text set, where there is no device: a handle cannot exist without one, and an entry point says so before it
+// asks for a handle
+inline bool require_device() {
+    int n_dev = 0;
+    if (ms_device_count(&n_dev) == MS_OK && n_dev > 0) return true;
+    set_error("no usable HIP device; libmotifscan_amd has no CPU fallback");
+    return false;
+}
 
 struct Scratch {                 // grow-only work buffers of the scan pipeline
     uint64_t *cand = nullptr;     size_t cand_cap = 0;
@@ -281,6 +296,49 @@ struct ms_affinity {                                  // ms_scan_affinity: the s
 };
 
 namespace ms {
+
+// What the handles of the two record scans begin with (ms_varscan, ms_allelescan): the placement's output (place_records) and the one
+// implementation of the accessors that only read it.
+struct RecHead {
+    int device = 0;
+    int32_t P = 0;
+    int64_t V = 0;
+    int64_t n = 0;                                    // records
+    void *block = nullptr;                            // one pooled device block holding the record arrays
+    size_t block_bytes = 0;
+    std::vector<int64_t> motif_offsets;               // [P+1]
+    std::vector<int64_t> gained, lost;                // [P], counted on the device
+    double device_ms = 0.0;                           // first launch -> last kernel done
+};
+MS_HIDDEN void rec_release(RecHead *h);               // the block back to its device's pool
+MS_HIDDEN int rec_num_sites(const RecHead *h, int64_t *n);
+MS_HIDDEN int rec_motif_offsets(const RecHead *h, int64_t *out);
+MS_HIDDEN int rec_motif_counts(const RecHead *h, int64_t *gained, int64_t *lost);
+MS_HIDDEN int rec_device_ms(const RecHead *h, double *ms);
+
+// The scratch of place_records in the caller's work block: place_slots adds it to the block's layout (it asks the prefix sum for its
+// temporary size, hence the stream and the return code).
+struct PlaceSlots {
+    Carve::Slot<uint32_t> cnt;                        // [n_cells] records of every (motif, tile) of a chunk
+    Carve::Slot<uint64_t> excl;                       // [n_cells] their exclusive prefix sums
+    Carve::Slot<uint64_t> tot, base;                  // [chunks][P] records of the motif in the chunk, and where they go
+    Carve::Slot<unsigned long long> gl;               // [2][max(P, 1)] gained, lost
+    Carve::Slot<char> tmp;
+    size_t tmp_bytes = 0;
+};
+MS_HIDDEN int place_slots(Carve &cv, const PlaceChunks &ch, int32_t P, hipStream_t st, PlaceSlots *out);
+
+// The two launches of a chunk [v0, v0 + nv) of variants, and the allocation of the record block once their number is known.
+struct PlaceCalls {
+    std::function<int(int64_t v0, int64_t nv, uint32_t *tile_cnt, unsigned long long *gained, unsigned long long *lost)> count;
+    std::function<int(int64_t v0, int64_t nv, const uint64_t *tile_excl, const uint64_t *row_base)> fill;
+    std::function<int(size_t n)> alloc;
+};
+// Records in output order without a sort or an atomic (ms_variants.hip's header has the scheme): every chunk counted, the counts summed
+// into h->motif_offsets and h->n, the records allocated, every chunk filled; then h->gained / lost / device_ms (from c->ev[0], which the
+// caller has recorded in front of its upload).  `tile`: variants per block of the caller's kernel; `what` names the scan in the error
+// texts.  The caller holds c->mu; on an error it synchronises the stream before it gives `work` back.
+MS_HIDDEN int place_records(DeviceCtx *c, const PlaceChunks &ch, int tile, void *work, const PlaceSlots &s, const char *what, const PlaceCalls &calls, RecHead *h);
 
 // One [P][R] plane of doubles per group, ranked per motif row (ms_ranksum.hip): what ms_best_rank_sum (the score plane of two ms_best) and
 // ms_affinity_rank_sum (the log_mean plane of two ms_affinity) both are.  `what` names the handles in the error texts.

@@ -203,7 +203,6 @@ int mark_blocks_per_motif(const std::vector<int64_t> &off, int32_t m0, int32_t m
 
 const char *kCountsOnly = "a counts-only result (MS_SCAN_COUNTS_ONLY, a counts-only batch or sweep span of a stream) holds the per-motif region counts and site numbers, no site arrays";
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t) 255; }
 
 }  // namespace
 }  // namespace ms

@@ -58,7 +58,6 @@ constexpr int kPgBlockBases = kPgThreads * 32;  // output bases of one splice bl
 constexpr int kPgStage = 512;                   // applied variants a splice block stages in LDS (14 KB); more: it searches global memory
 constexpr int kLiftThreads = 256;               // queries per block
 
-size_t pg_up256(size_t x) { return (x + 255) & ~(size_t) 255; }
 unsigned pg_grid(int64_t n) { return (unsigned) ((std::max<int64_t>(n, 1) + kPgThreads - 1) / kPgThreads); }
 
 __global__ void __launch_bounds__(kPgThreads) pg_key_kernel(const AlRec *__restrict__ rec, const int32_t *__restrict__ chrom, const uint8_t *__restrict__ mis,
@@ -272,10 +271,7 @@ int ms_genome_apply_alleles(const ms_genome *genome, const int32_t *chrom, const
     if (map) *map = nullptr;
     if (!out) { set_error("out is NULL"); return MS_ERR_INVALID; }
     *out = nullptr;
-    {
-        int n_dev = 0;                                         // (a genome handle cannot exist without a device: say so before asking for one)
-        if (ms_device_count(&n_dev) != MS_OK || n_dev <= 0) { set_error("no usable HIP device; libmotifscan_amd has no CPU fallback"); return MS_ERR_RUNTIME; }
-    }
+    if (!require_device()) return MS_ERR_RUNTIME;
     if (flags & ~MS_APPLY_SKIP_MISMATCH) { set_error("unknown apply flags 0x%x", flags); return MS_ERR_INVALID; }
     if (!genome) { set_error("NULL handle"); return MS_ERR_INVALID; }
     const ms_seqset *G = reinterpret_cast<const ms_seqset *>(genome);
@@ -319,103 +315,77 @@ int ms_genome_apply_alleles(const ms_genome *genome, const int32_t *chrom, const
 
     // ---- the map's block: the applied variants (at most V) and the chromosome tables
     {
-        const size_t b8 = pg_up256(8 * Vz), b4 = pg_up256(4 * Vz), bc = pg_up256(8 * Cz);
-        if ((rc = pool_alloc(c, 2 * b8 + 2 * b4 + 3 * bc, &res->block, &res->block_bytes))) return rc;
-        char *b = static_cast<char *>(res->block);
-        res->d_g = reinterpret_cast<int64_t *>(b); b += b8;
-        res->d_os = reinterpret_cast<int64_t *>(b); b += b8;
-        res->d_r = reinterpret_cast<int32_t *>(b); b += b4;
-        res->d_a = reinterpret_cast<int32_t *>(b); b += b4;
-        res->d_goff = reinterpret_cast<int64_t *>(b); b += bc;
-        res->d_noff = reinterpret_cast<int64_t *>(b); b += bc;
-        res->d_cstart = reinterpret_cast<int64_t *>(b);
+        Carve mv;
+        const auto s_g = mv.add<int64_t>(Vz), s_os = mv.add<int64_t>(Vz);
+        const auto s_r = mv.add<int32_t>(Vz), s_a = mv.add<int32_t>(Vz);
+        const auto s_goff = mv.add<int64_t>(Cz), s_noff = mv.add<int64_t>(Cz), s_cstart = mv.add<int64_t>(Cz);
+        if ((rc = pool_alloc(c, mv.bytes(), &res->block, &res->block_bytes))) return rc;
+        res->d_g = Carve::at(res->block, s_g);
+        res->d_os = Carve::at(res->block, s_os);
+        res->d_r = Carve::at(res->block, s_r);
+        res->d_a = Carve::at(res->block, s_a);
+        res->d_goff = Carve::at(res->block, s_goff);
+        res->d_noff = Carve::at(res->block, s_noff);
+        res->d_cstart = Carve::at(res->block, s_cstart);
     }
     ms_liftmap *raw = res.release();
 
     // ---- the call's work block
-    const size_t a_words = (size_t) ((A + 31) / 32);            // mask words of the alt plane; twice as many code words
-    const size_t b_chrom = pg_up256(4 * Vz), b_pos = pg_up256(8 * Vz), b_rlen = pg_up256(4 * Vz), b_aoff = pg_up256(8 * (Vz + 1)), b_roff = pg_up256(8 * (Vz + 1)),
-                 b_alt = pg_up256((size_t) std::max<int64_t>(A, 1)), b_ref = pg_up256((size_t) std::max<int64_t>(Rn, 1)),
-                 b_acode = pg_up256(4 * (2 * a_words + kAlPlanePad)), b_amask = pg_up256(4 * (a_words + kAlPlanePad)), b_rec = pg_up256(sizeof(AlRec) * Vz),
-                 b_mis = pg_up256(Vz), b_v8 = pg_up256(8 * (Vz + 1)), b_v4 = pg_up256(4 * (Vz + 1)), b_hdr = pg_up256(8 * Cz), b_tmp = pg_up256(std::max<size_t>(tmp_bytes, 1)),
-                 b_ub = pg_up256(8 * ((size_t) ((G->n_bases + A) / kPgBlockBases) + 3));      // (the output has at most n_bases + A bases)
+    Carve cv;
+    const AlSlots us = al_upload_slots(cv, V, A, Rn);
+    const auto s_status = cv.add<uint8_t>(Vz);
+    const auto s_keys = cv.add<uint64_t>(Vz + 1), s_skeys = cv.add<uint64_t>(Vz + 1), s_ends = cv.add<uint64_t>(Vz + 1), s_max = cv.add<uint64_t>(Vz + 1);
+    const auto s_vals = cv.add<int64_t>(Vz + 1), s_svals = cv.add<int64_t>(Vz + 1);
+    const auto s_dest = cv.add<uint64_t>(Vz + 1);              // [V + 1]: the last entry is the number applied
+    const auto s_delta = cv.add<int64_t>(Vz + 1);              // [V + 1], zero behind the applied ones
+    const auto s_D = cv.add<int64_t>(Vz + 1);                  // [V + 1]
+    const auto s_flag = cv.add<uint32_t>(Vz + 1);              // [V + 1]
+    const auto s_apchrom = cv.add<int32_t>(Vz + 1);
+    const auto s_hdr = cv.add<int64_t>(Cz);                    // the new offsets [C + 1], then the number applied
+    const auto s_ub = cv.add<int64_t>((size_t) ((G->n_bases + A) / kPgBlockBases) + 3);   // [splice blocks + 1]: pg_blockstart_kernel (the output has at most n_bases + A bases)
+    const auto s_tmp = cv.add<char>(std::max<size_t>(tmp_bytes, 1));
     void *wblk = nullptr;
     size_t wgot = 0;
     auto fail = [&](int code) { (void) hipStreamSynchronize(st); if (wblk) pool_free(c, wblk, wgot); ms_liftmap_free(raw); return code; };   // (nothing queued may still read the blocks)
     auto hip_fail = [&](hipError_t e, const char *what) { set_error("%s failed: %s", what, hipGetErrorString(e)); return fail(e == hipErrorOutOfMemory ? MS_ERR_NOMEM : MS_ERR_RUNTIME); };
-    if ((rc = pool_alloc(c, b_chrom + b_pos + b_rlen + b_aoff + b_roff + b_alt + b_ref + b_acode + b_amask + b_rec + 2 * b_mis + 9 * b_v8 + 2 * b_v4 + b_hdr + b_ub + b_tmp,
-                         &wblk, &wgot))) return fail(rc);
-    char *b = static_cast<char *>(wblk);
-    int32_t *d_chrom = reinterpret_cast<int32_t *>(b); b += b_chrom;
-    int64_t *d_pos = reinterpret_cast<int64_t *>(b); b += b_pos;
-    int32_t *d_rlen = reinterpret_cast<int32_t *>(b); b += b_rlen;
-    int64_t *d_aoff = reinterpret_cast<int64_t *>(b); b += b_aoff;
-    int64_t *d_roff = reinterpret_cast<int64_t *>(b); b += b_roff;
-    uint8_t *d_alt = reinterpret_cast<uint8_t *>(b); b += b_alt;
-    uint8_t *d_ref = reinterpret_cast<uint8_t *>(b); b += b_ref;
-    uint32_t *d_acode = reinterpret_cast<uint32_t *>(b); b += b_acode;
-    uint32_t *d_amask = reinterpret_cast<uint32_t *>(b); b += b_amask;
-    AlRec *d_rec = reinterpret_cast<AlRec *>(b); b += b_rec;
-    uint8_t *d_mis = reinterpret_cast<uint8_t *>(b); b += b_mis;
-    uint8_t *d_status = reinterpret_cast<uint8_t *>(b); b += b_mis;
-    uint64_t *d_keys = reinterpret_cast<uint64_t *>(b); b += b_v8;
-    int64_t *d_vals = reinterpret_cast<int64_t *>(b); b += b_v8;
-    uint64_t *d_skeys = reinterpret_cast<uint64_t *>(b); b += b_v8;
-    int64_t *d_svals = reinterpret_cast<int64_t *>(b); b += b_v8;
-    uint64_t *d_ends = reinterpret_cast<uint64_t *>(b); b += b_v8;
-    uint64_t *d_max = reinterpret_cast<uint64_t *>(b); b += b_v8;
-    uint64_t *d_dest = reinterpret_cast<uint64_t *>(b); b += b_v8;      // [V + 1]: the last entry is the number applied
-    int64_t *d_delta = reinterpret_cast<int64_t *>(b); b += b_v8;       // [V + 1], zero behind the applied ones
-    int64_t *d_D = reinterpret_cast<int64_t *>(b); b += b_v8;           // [V + 1]
-    uint32_t *d_flag = reinterpret_cast<uint32_t *>(b); b += b_v4;      // [V + 1]
-    int32_t *d_apchrom = reinterpret_cast<int32_t *>(b); b += b_v4;
-    int64_t *d_hdr = reinterpret_cast<int64_t *>(b); b += b_hdr;        // the new offsets [C + 1], then the number applied
-    int64_t *d_ub = reinterpret_cast<int64_t *>(b); b += b_ub;          // [splice blocks + 1]: pg_blockstart_kernel
-    void *d_tmp = b;
-    int64_t *d_apaoff = d_pos;                                          // (the positions are not read after the prep kernel: AlRec::g has them)
+    if ((rc = pool_alloc(c, cv.bytes(), &wblk, &wgot))) return fail(rc);
+    const AlDev U = al_upload_at(wblk, us);
+    uint8_t *d_status = Carve::at(wblk, s_status);
+    uint64_t *d_keys = Carve::at(wblk, s_keys), *d_skeys = Carve::at(wblk, s_skeys), *d_ends = Carve::at(wblk, s_ends), *d_max = Carve::at(wblk, s_max);
+    int64_t *d_vals = Carve::at(wblk, s_vals), *d_svals = Carve::at(wblk, s_svals);
+    uint64_t *d_dest = Carve::at(wblk, s_dest);
+    int64_t *d_delta = Carve::at(wblk, s_delta), *d_D = Carve::at(wblk, s_D);
+    uint32_t *d_flag = Carve::at(wblk, s_flag);
+    int32_t *d_apchrom = Carve::at(wblk, s_apchrom);
+    int64_t *d_hdr = Carve::at(wblk, s_hdr), *d_ub = Carve::at(wblk, s_ub);
+    void *d_tmp = Carve::at(wblk, s_tmp);
+    int64_t *d_apaoff = U.pos;                                          // (the positions are not read after the prep kernel: AlRec::g has them)
 
     hipError_t he = hipEventRecord(c->ev[0], st);
     if (he == hipSuccess) he = hipMemcpyAsync(raw->d_goff, G->offsets.data(), 8 * ((size_t) C + 1), hipMemcpyHostToDevice, st);
     if (he != hipSuccess) return hip_fail(he, "offset upload");
     if (V > 0) {
-        he = hipMemcpyAsync(d_chrom, chrom, 4 * (size_t) V, hipMemcpyHostToDevice, st);
-        if (he == hipSuccess) he = hipMemcpyAsync(d_pos, pos, 8 * (size_t) V, hipMemcpyHostToDevice, st);
-        if (he == hipSuccess) he = hipMemcpyAsync(d_rlen, ref_len, 4 * (size_t) V, hipMemcpyHostToDevice, st);
-        if (he == hipSuccess) he = hipMemcpyAsync(d_aoff, alt_offsets, 8 * ((size_t) V + 1), hipMemcpyHostToDevice, st);
-        if (he == hipSuccess && ref_bases) he = hipMemcpyAsync(d_roff, ref_off.data(), 8 * ((size_t) V + 1), hipMemcpyHostToDevice, st);
-        if (he == hipSuccess && A > 0) he = hipMemcpyAsync(d_alt, alt_bases, (size_t) A, hipMemcpyHostToDevice, st);
-        if (he == hipSuccess && Rn > 0) he = hipMemcpyAsync(d_ref, ref_bases, (size_t) Rn, hipMemcpyHostToDevice, st);
-        if (he == hipSuccess) he = hipMemsetAsync(d_acode, 0, b_acode + b_amask, st);       // (the two planes lie side by side: their padding too)
+        he = al_upload(G, U, chrom, pos, ref_len, alt_bases, alt_offsets, ref_bases, ref_off, V, A, Rn, raw->mismatch.data(), st);
         if (he == hipSuccess) he = hipMemsetAsync(d_delta, 0, 8 * ((size_t) V + 1), st);
-        if (he == hipSuccess && A > 0) {
-            hipLaunchKernelGGL(al_pack_kernel, dim3((unsigned) ((a_words + 255) / 256)), dim3(256), 0, st, d_alt, A, d_acode, d_amask);
-            he = hipGetLastError();
-        }
-        if (he == hipSuccess) {
-            hipLaunchKernelGGL(al_prep_kernel, dim3((unsigned) ((V + 255) / 256)), dim3(256), 0, st, G->d_codes, G->d_nmask, G->d_offsets, d_chrom, d_pos,
-                               d_rlen, d_aoff, ref_bases ? d_ref : (const uint8_t *) nullptr, d_roff, V, d_rec, d_mis);
-            he = hipGetLastError();
-        }
-        if (he == hipSuccess) he = hipMemcpyAsync(raw->mismatch.data(), d_mis, (size_t) V, hipMemcpyDeviceToHost, st);
         if (he == hipSuccess) he = hipEventRecord(c->ev[1], st);
         if (he != hipSuccess) return hip_fail(he, "variant upload");
         // ---- order
         const dim3 gv(pg_grid(V)), bt(kPgThreads);
-        hipLaunchKernelGGL(pg_key_kernel, gv, bt, 0, st, d_rec, d_chrom, d_mis, skip, skip_key, V, d_keys, d_vals);
+        hipLaunchKernelGGL(pg_key_kernel, gv, bt, 0, st, U.rec, U.chrom, U.mis, skip, skip_key, V, d_keys, d_vals);
         if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "key kernel");
         size_t tb = tmp_bytes;
         if ((rc = sort_hit_pairs(d_tmp, &tb, d_keys, d_skeys, reinterpret_cast<const double *>(d_vals), reinterpret_cast<double *>(d_svals), (size_t) V, 0, end_bit, st)))
             return fail(rc);                                   // (the values are the indices' bit patterns: the sort only moves them)
         // ---- status and layout
-        hipLaunchKernelGGL(pg_end_kernel, gv, bt, 0, st, d_rec, d_chrom, d_mis, skip, d_svals, V, d_ends);
+        hipLaunchKernelGGL(pg_end_kernel, gv, bt, 0, st, U.rec, U.chrom, U.mis, skip, d_svals, V, d_ends);
         if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "end kernel");
         tb = tmp_bytes;
         if ((rc = inclusive_max_u64(d_tmp, &tb, d_ends, d_max, (size_t) V, st))) return fail(rc);
-        hipLaunchKernelGGL(pg_status_kernel, gv, bt, 0, st, d_skeys, d_svals, d_max, d_mis, skip, V, d_status, d_flag);
+        hipLaunchKernelGGL(pg_status_kernel, gv, bt, 0, st, d_skeys, d_svals, d_max, U.mis, skip, V, d_status, d_flag);
         if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "status kernel");
         tb = tmp_bytes;
         if ((rc = exclusive_sum_u32(d_tmp, &tb, d_flag, d_dest, (size_t) V + 1, st))) return fail(rc);
-        hipLaunchKernelGGL(pg_compact_kernel, gv, bt, 0, st, d_rec, d_chrom, d_svals, d_flag, d_dest, V, raw->d_g, raw->d_r, raw->d_a, d_apaoff, d_apchrom, d_delta);
+        hipLaunchKernelGGL(pg_compact_kernel, gv, bt, 0, st, U.rec, U.chrom, d_svals, d_flag, d_dest, V, raw->d_g, raw->d_r, raw->d_a, d_apaoff, d_apchrom, d_delta);
         if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "compaction");
         tb = tmp_bytes;
         if ((rc = exclusive_sum_i64(d_tmp, &tb, d_delta, d_D, (size_t) V + 1, st))) return fail(rc);
@@ -449,8 +419,8 @@ int ms_genome_apply_alleles(const ms_genome *genome, const int32_t *chrom, const
         hipLaunchKernelGGL(pg_blockstart_kernel, dim3(pg_grid(nb + 1)), dim3(kPgThreads), 0, st, (const int64_t *) raw->d_os, n, nb, d_ub);
         he = hipGetLastError();
         if (he == hipSuccess) {
-            hipLaunchKernelGGL(splice_kernel, dim3((unsigned) nb), dim3(kPgThreads), 0, st, G->d_codes, G->d_nmask, (const uint32_t *) d_acode,
-                               (const uint32_t *) d_amask, raw->d_os, raw->d_g, raw->d_r, raw->d_a, d_apaoff, (const int64_t *) d_ub, S->n_bases, S->d_codes, S->d_nmask);
+            hipLaunchKernelGGL(splice_kernel, dim3((unsigned) nb), dim3(kPgThreads), 0, st, G->d_codes, G->d_nmask, U.acode,
+                               U.amask, raw->d_os, raw->d_g, raw->d_r, raw->d_a, d_apaoff, (const int64_t *) d_ub, S->n_bases, S->d_codes, S->d_nmask);
             he = hipGetLastError();
         }
     }
@@ -517,15 +487,17 @@ int ms_liftmap_lift(const ms_liftmap *m, int direction, const int32_t *chrom, co
     DeviceCtx *c;
     int rc = get_ctx(m->device, &c);
     if (rc) return rc;
-    const size_t nz = (size_t) n, b_c = pg_up256(4 * nz), b_p = pg_up256(8 * nz), b_i = pg_up256(nz);
+    const size_t nz = (size_t) n;
+    Carve cv;
+    const auto s_c = cv.add<int32_t>(nz);
+    const auto s_p = cv.add<int64_t>(nz), s_o = cv.add<int64_t>(nz);
+    const auto s_in = cv.add<uint8_t>(nz);
     void *blk = nullptr;
     size_t got = 0;
-    if ((rc = pool_alloc(c, b_c + 2 * b_p + b_i, &blk, &got))) return rc;
-    char *b = static_cast<char *>(blk);
-    int32_t *d_c = reinterpret_cast<int32_t *>(b); b += b_c;
-    int64_t *d_p = reinterpret_cast<int64_t *>(b); b += b_p;
-    int64_t *d_o = reinterpret_cast<int64_t *>(b); b += b_p;
-    uint8_t *d_in = reinterpret_cast<uint8_t *>(b);
+    if ((rc = pool_alloc(c, cv.bytes(), &blk, &got))) return rc;
+    int32_t *d_c = Carve::at(blk, s_c);
+    int64_t *d_p = Carve::at(blk, s_p), *d_o = Carve::at(blk, s_o);
+    uint8_t *d_in = Carve::at(blk, s_in);
     std::lock_guard<std::mutex> lk_dev(c->mu);
     const hipStream_t st = c->stream;
     hipError_t he = hipMemcpyAsync(d_c, chrom, 4 * nz, hipMemcpyHostToDevice, st);

@@ -194,18 +194,11 @@ __global__ void __launch_bounds__(kRsThreads) rs_count_kernel(const double *__re
     }
 }
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t) 255; }
 
 int ceil_log2_plus1(uint32_t n) {                        // the least s with 2^s >= n + 1
     int s = 0;
     while ((1ull << s) < (unsigned long long) n + 1ull) s++;
     return s;
-}
-
-bool have_device() {
-    int n_dev = 0;
-    if (ms_device_count(&n_dev) != MS_OK || n_dev <= 0) { set_error("no usable HIP device; libmotifscan_amd has no CPU fallback"); return false; }
-    return true;
 }
 
 // the selected regions of a handle as an index list (empty with *all = true for a NULL selection)
@@ -367,14 +360,14 @@ int ms_debug_ranksum_budget(int64_t elems, int64_t *previous) {
 
 int ms_best_rank_sum(const ms_best *a, const uint8_t *sel_a, const ms_best *b, const uint8_t *sel_b, int32_t m0, int32_t m1, uint32_t flags, int64_t *u2, uint64_t *ties,
                      int64_t *n, double *device_ms) {
-    if (!have_device()) return MS_ERR_RUNTIME;
+    if (!require_device()) return MS_ERR_RUNTIME;
     if (!a || !b) { set_error("NULL handle"); return MS_ERR_INVALID; }
     const RankPlane pa = {a->device, a->P, a->R, a->d_score}, pb = {b->device, b->P, b->R, b->d_score};
     return rank_sum_planes("best-site", pa, sel_a, pb, sel_b, m0, m1, flags, u2, ties, n, device_ms);
 }
 
 int ms_best_count_passing(const ms_best *b, const uint8_t *sel, const double *cutoffs, int32_t n_cut, int32_t m0, int32_t m1, int64_t *counts, double *device_ms) {
-    if (!have_device()) return MS_ERR_RUNTIME;
+    if (!require_device()) return MS_ERR_RUNTIME;
     if (!b) { set_error("NULL handle"); return MS_ERR_INVALID; }
     if (m0 < 0 || m1 < m0 || m1 > b->P) { set_error("motif range [%d, %d) outside [0, %d)", m0, m1, b->P); return MS_ERR_INVALID; }
     if (n_cut < 0 || (n_cut > 0 && (!cutoffs || !counts))) { set_error("bad cutoffs / counts"); return MS_ERR_INVALID; }

@@ -208,7 +208,6 @@ __global__ void __launch_bounds__(kHistThreads, 4) scorehist_kernel(const HistAr
     }
 }
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t) 255; }
 
 // the ordered bit pattern of a double: a < b <=> key(a) < key(b) for all non-NaN doubles (-0.0 just below +0.0)
 uint64_t ord_key(double x) {
@@ -259,10 +258,7 @@ int ms_debug_scorehist_dims(int32_t out[4]) {
 
 int ms_scan_score_histogram(const ms_pwmset *pwms_c, const ms_seqset *seqs, int strand_mask, uint32_t flags, const double *lo, const double *inv_width,
                             int32_t n_bins, int32_t max_n, int64_t *out, double *device_ms) {
-    {
-        int n_dev = 0;
-        if (ms_device_count(&n_dev) != MS_OK || n_dev <= 0) { set_error("no usable HIP device; libmotifscan_amd has no CPU fallback"); return MS_ERR_RUNTIME; }
-    }
+    if (!require_device()) return MS_ERR_RUNTIME;
     if (device_ms) *device_ms = 0.0;
     if (!pwms_c || !seqs) { set_error("NULL handle"); return MS_ERR_INVALID; }
     if (strand_mask < 1 || strand_mask > 3) { set_error("invalid strand mask %d (1 '+', 2 '-', 3 both)", strand_mask); return MS_ERR_INVALID; }

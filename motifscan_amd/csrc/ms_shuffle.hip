@@ -397,7 +397,6 @@ __global__ void __launch_bounds__(kShLongThreads) sh_global_kernel(ShArgs A, con
     }
 }
 
-size_t sh_up256(size_t x) { return (x + 255) & ~(size_t) 255; }
 
 }  // namespace
 
@@ -428,10 +427,7 @@ int ms_debug_shuffle_stage_ms(double out[4]) {
 int ms_seqset_shuffle(const ms_seqset *seqs, int kind, uint64_t seed, int64_t seq_index_base, uint32_t flags, ms_seqset **out) {
     if (!out) { set_error("out is NULL"); return MS_ERR_INVALID; }
     *out = nullptr;
-    {
-        int n_dev = 0;
-        if (ms_device_count(&n_dev) != MS_OK || n_dev <= 0) { set_error("no usable HIP device; libmotifscan_amd has no CPU fallback"); return MS_ERR_RUNTIME; }
-    }
+    if (!require_device()) return MS_ERR_RUNTIME;
     if (!seqs) { set_error("NULL handle"); return MS_ERR_INVALID; }
     if (kind != MS_SHUFFLE_MONO && kind != MS_SHUFFLE_DINUC) { set_error("invalid shuffle kind %d (1 mono, 2 dinuc)", kind); return MS_ERR_INVALID; }
     if (flags != 0u) { set_error("unknown shuffle flags 0x%x", flags); return MS_ERR_INVALID; }
@@ -468,7 +464,7 @@ int ms_seqset_shuffle(const ms_seqset *seqs, int kind, uint64_t seed, int64_t se
         // ---- 1. the mask plane, zeroed code words, the runs' ends counted per block
         size_t t_scan = 0;
         if ((rc = exclusive_sum_i64(nullptr, &t_scan, nullptr, nullptr, (size_t) n_blk + 1, st))) return fail(rc);
-        const size_t b_ss = sh_up256(4 * ((size_t) n_units + 2)), b_blk = sh_up256(8 * ((size_t) n_blk + 1)), b_tmp = sh_up256(std::max<size_t>(t_scan, 1));
+        const size_t b_ss = up256(4 * ((size_t) n_units + 2)), b_blk = up256(8 * ((size_t) n_blk + 1)), b_tmp = up256(std::max<size_t>(t_scan, 1));
         if ((rc = pool_alloc(c, b_ss + 4 * b_blk + b_tmp + 256, &wblk, &wgot))) return fail(rc);
         char *p = static_cast<char *>(wblk);
         uint32_t *d_ss = reinterpret_cast<uint32_t *>(p); p += b_ss;
@@ -499,12 +495,12 @@ int ms_seqset_shuffle(const ms_seqset *seqs, int kind, uint64_t seed, int64_t se
 
         // ---- 2. the run list, and the runs beyond the LDS tile
         const size_t nz = (size_t) std::max<int64_t>(n_runs, 0) + 8, n_long_max = (size_t) (n_bases / (kShTile + 1)) + 1;
-        if ((rc = pool_alloc(c, 3 * sh_up256(8 * nz) + 2 * sh_up256(8 * n_long_max), &rblk, &rgot))) return fail(rc);
+        if ((rc = pool_alloc(c, 3 * up256(8 * nz) + 2 * up256(8 * n_long_max), &rblk, &rgot))) return fail(rc);
         p = static_cast<char *>(rblk);
-        int64_t *d_rs = reinterpret_cast<int64_t *>(p); p += sh_up256(8 * nz);
-        int64_t *d_re = reinterpret_cast<int64_t *>(p); p += sh_up256(8 * nz);
-        int64_t *d_rq = reinterpret_cast<int64_t *>(p); p += sh_up256(8 * nz);
-        int64_t *d_lr = reinterpret_cast<int64_t *>(p); p += sh_up256(8 * n_long_max);
+        int64_t *d_rs = reinterpret_cast<int64_t *>(p); p += up256(8 * nz);
+        int64_t *d_re = reinterpret_cast<int64_t *>(p); p += up256(8 * nz);
+        int64_t *d_rq = reinterpret_cast<int64_t *>(p); p += up256(8 * nz);
+        int64_t *d_lr = reinterpret_cast<int64_t *>(p); p += up256(8 * n_long_max);
         unsigned long long *d_lo = reinterpret_cast<unsigned long long *>(p);
         if (n_runs > 0) {
             hipLaunchKernelGGL(sh_list_kernel, dim3((unsigned) n_blk), dim3(kShUnitThreads), 0, st, dev_seq(seqs), (const uint32_t *) d_ss, n_units, (const int64_t *) d_bf,

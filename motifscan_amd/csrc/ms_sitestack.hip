@@ -154,7 +154,6 @@ __global__ __launch_bounds__(kStackThreads) void sitestack_kernel(StackArgs A) {
             if (h[n_cnt + i]) atomicAdd(&out_d[i], (unsigned long long) h[n_cnt + i]);
 }
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t) 255; }
 
 // 1: device memory of `device`; 0: host memory; -1: device memory of another device (*other)
 int pointer_place(const void *p, int device, int *other) {
@@ -185,10 +184,7 @@ int ms_debug_sitestack_dims(int32_t out[4]) {
 
 int ms_result_site_base_counts(const ms_result *r, const ms_pwmset *pwms, const ms_seqset *seqs, int32_t flank, int32_t m0, int32_t m1, uint32_t flags,
                                int64_t *counts, int64_t *dinuc, int64_t *n_sites, double *device_ms) {
-    {
-        int n_dev = 0;
-        if (ms_device_count(&n_dev) != MS_OK || n_dev <= 0) { set_error("no usable HIP device; libmotifscan_amd has no CPU fallback"); return MS_ERR_RUNTIME; }
-    }
+    if (!require_device()) return MS_ERR_RUNTIME;
     if (device_ms) *device_ms = 0.0;
     if (!r || !pwms || !seqs) { set_error("NULL handle"); return MS_ERR_INVALID; }
     if (flags != 0) { set_error("unknown site-stack flags 0x%x", flags); return MS_ERR_INVALID; }

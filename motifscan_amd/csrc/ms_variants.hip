@@ -20,31 +20,27 @@
 // per-(chunk, motif) totals are summed on the host into the motif offsets, then every chunk is filled (counted again when there is
 // more than one chunk, the counts of the first pass being gone by then).
 // The per-motif numbers of variants that gain / lose a site are counted in pass 1: a flag word per variant of the tile in LDS.
+//
+// The two passes over the chunks are place_records below, which ms_scan_alleles (ms_alleles.hip) drives with its own kernel; its host
+// arithmetic -- the chunk plan, the offsets out of the totals, the layout of the work block -- is ms_place.h, and the accessors the two
+// record handles have in common (RecHead, ms_handles.h) are implemented here once.  The kernel's column step, table staging, per-round
+// placement and gained / lost tally are ms_allele_dev.h's (tab_step, tab_stage, place_round, tally_motif).
 #include <algorithm>
 #include <atomic>
 #include <memory>
-#include <type_traits>
 
+#include "ms_allele_dev.h"
 #include "ms_device.h"
 #include "ms_handles.h"
 
-struct ms_varscan {
-    int device = 0;
-    int32_t P = 0;
-    int64_t V = 0;
-    int64_t n = 0;                                    // records
-    void *block = nullptr;                            // one pooled device block holding the record arrays
-    size_t block_bytes = 0;
+struct ms_varscan : ms::RecHead {
     int64_t *d_variant = nullptr;
     int64_t *d_start = nullptr;
     double *d_score_ref = nullptr;
     double *d_score_alt = nullptr;
     int8_t *d_strand = nullptr;
     uint8_t *d_state = nullptr;
-    std::vector<int64_t> motif_offsets;               // [P+1]
-    std::vector<int64_t> gained, lost;                // [P], counted on the device
     std::vector<int8_t> ref_codes;                    // [V]
-    double device_ms = 0.0;                           // first launch -> last kernel done
 };
 
 namespace ms {
@@ -126,10 +122,7 @@ __global__ void __launch_bounds__(kVarThreads) var_scan_kernel(const uint32_t *_
     if ((W <= kVarTabMaxW) != LDS_TAB) return;
     const double2 *__restrict__ tab_g = Pw.tab2 + Pw.tab_off[m];
     const uint32_t zero = (uint32_t) W * 4u;
-    if (LDS_TAB) {
-        for (int i = threadIdx.x; i < W * 4; i += kVarThreads) vtab_lds[i] = tab_g[i];
-        if (threadIdx.x == 0) vtab_lds[zero] = make_double2(0.0, 0.0);
-    }
+    if (LDS_TAB) tab_stage<kVarThreads>(vtab_lds, tab_g, W);
     if (!FILL && threadIdx.x < kVarTile) s_flag[threadIdx.x] = 0u;
     __syncthreads();
     auto entry = [&](uint32_t idx) -> double2 {
@@ -141,8 +134,6 @@ __global__ void __launch_bounds__(kVarThreads) var_scan_kernel(const uint32_t *_
     const int n_local = (int) (nv - vl0 < kVarTile ? nv - vl0 : kVarTile);
     const int64_t n_items = (int64_t) n_local * W;
     const double max_raw = Pw.max_raw[m], cutoff = Pw.cutoff[m], floor_ = Pw.raw_floor[m];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t lt = (1ULL << lane) - 1ULL;
     uint64_t run = 0;                                          // records of the tile's earlier rounds (+ the tile's place when filling)
     if (FILL) run = row_base[m] + (tile_excl[row + tile] - tile_excl[row]);
     // item i = vl * W + j of thread t in round r: i = 256 r + t, kept as (vl, j) without a division per round
@@ -165,52 +156,16 @@ __global__ void __launch_bounds__(kVarThreads) var_scan_kernel(const uint32_t *_
                 for (int c0 = 0; c0 < W; c0 += 32) {
                     const uint64_t cw = code_window(codes, g + c0);
                     const int n = (W - c0) < 32 ? (W - c0) : 32;
-                    const uint32_t skip = n_window(nmask, g + c0) | ~low_mask(n);       // bit c: column c0 + c adds nothing
-                    const int kk = k - c0;
-                    // eight columns a step while more than four are left, then four: the reads of a step are issued together
-                    auto columns = [&](auto width, int c1) {
-                        constexpr int N = decltype(width)::value;
-                        double2 t[N];
-#pragma unroll
-                        for (int u = 0; u < N; u++) {
-                            const int c = c1 + u;
-                            const bool nothing = (skip >> c) & 1u;                          // adds +0.0: a sum that started at +0.0 is never -0.0
-                            if constexpr (LDS_TAB) {
-                                t[u] = vtab_lds[nothing ? zero : (uint32_t) (c0 + c) * 4u + ((uint32_t) (cw >> (2 * c)) & 3u)];
-                            } else {
-                                const int cc = c < n ? c : n - 1;                           // clamped: always an entry of the motif
-                                t[u] = tab_g[(uint32_t) (c0 + cc) * 4u + ((uint32_t) (cw >> (2 * cc)) & 3u)];
-                                if (nothing) t[u] = make_double2(0.0, 0.0);
-                            }
-                        }
-#pragma unroll
-                        for (int u = 0; u < N; u++) {
-                            const double2 ta = (c1 + u == kk) ? tk : t[u];
-                            rf += t[u].x; rr += t[u].y;
-                            af += ta.x; ar += ta.y;
-                        }
-                    };
-                    int c1 = 0;
-                    for (; n - c1 > 4; c1 += 8) columns(std::integral_constant<int, 8>{}, c1);
-                    if (n - c1 > 0) columns(std::integral_constant<int, 4>{}, c1);
+                    tab_step<LDS_TAB, true>(vtab_lds, tab_g, zero, c0, n, cw, n_window(nmask, g + c0), k - c0, tk, rf, rr, af, ar);
                 }
                 if (strand_mask & 1) st_f = judge(rf, af, max_raw, cutoff, floor_, sf_ref, sf_alt);
                 if (strand_mask & 2) st_r = judge(rr, ar, max_raw, cutoff, floor_, sr_ref, sr_alt);
             }
         }
-        const unsigned long long bf = __ballot(st_f != 0u), br = __ballot(st_r != 0u);
-        const int buf = round & 1;                             // (two buffers: a wave may write round r + 1's total while another still reads round r's)
-        if (lane == 0u) s_wtot[buf][wave] = (uint32_t) (__popcll(bf) + __popcll(br));
-        __syncthreads();
-        uint32_t before = 0u, all = 0u;
-#pragma unroll
-        for (uint32_t w = 0; w < (uint32_t) (kVarThreads / 64); w++) {
-            const uint32_t x = s_wtot[buf][w];
-            all += x;
-            if (w < wave) before += x;
-        }
+        uint32_t before, all;
+        place_round<kVarThreads>(s_wtot, round, st_f != 0u, st_r != 0u, before, all);
         if (FILL) {
-            uint64_t d = run + before + (uint64_t) (__popcll(bf & lt) + __popcll(br & lt));
+            uint64_t d = run + before;
             const int64_t v = v0 + vl0 + vl;
             if (st_f && d < O.cap) {
                 O.variant[d] = v; O.start[d] = pos[v] - k; O.strand[d] = (int8_t) 1;
@@ -235,17 +190,13 @@ __global__ void __launch_bounds__(kVarThreads) var_scan_kernel(const uint32_t *_
         if (gained) {
             __syncthreads();
             const uint32_t f = (int) threadIdx.x < n_local ? s_flag[threadIdx.x] : 0u;
-            const unsigned long long bl = __ballot((f & 1u) != 0u), bg = __ballot((f & 2u) != 0u);
-            if (lane == 0u) {
-                if (bl) atomicAdd(&lost[m], (unsigned long long) __popcll(bl));            // (integer sums: the same in any order)
-                if (bg) atomicAdd(&gained[m], (unsigned long long) __popcll(bg));
-            }
+            tally_motif((f & 1u) != 0u, (f & 2u) != 0u, &lost[m], &gained[m]);
         }
     }
 }
 
 // tot[m] = records of motif m in the chunk, out of the prefix sums of its tiles (tile_excl has one entry more than there are tiles)
-__global__ void __launch_bounds__(256) var_row_total_kernel(const uint64_t *__restrict__ tile_excl, int64_t ntx, int32_t P, uint64_t *__restrict__ tot) {
+__global__ void __launch_bounds__(256) row_total_kernel(const uint64_t *__restrict__ tile_excl, int64_t ntx, int32_t P, uint64_t *__restrict__ tot) {
     const int32_t m = (int32_t) (blockIdx.x * blockDim.x + threadIdx.x);
     if (m < P) tot[m] = tile_excl[(int64_t) (m + 1) * ntx] - tile_excl[(int64_t) m * ntx];
 }
@@ -278,11 +229,120 @@ int launch_var_scan(const VarLaunch &L, int64_t v0, int64_t nv, uint32_t *tile_c
     return MS_OK;
 }
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t) 255; }
-
 }  // namespace
 
 int64_t varscan_chunk_setting() { return g_var_chunk.load(); }
+
+int place_slots(Carve &cv, const PlaceChunks &ch, int32_t P, hipStream_t st, PlaceSlots *out) {
+    size_t tmp = 0;
+    if (int rc = exclusive_sum_u32(nullptr, &tmp, nullptr, nullptr, ch.n_cells, st)) return rc;
+    const size_t Pz = (size_t) std::max<int32_t>(P, 1), Kz = (size_t) std::max<int64_t>(ch.n_chunks, 1);
+    out->cnt = cv.add<uint32_t>(ch.n_cells);
+    out->excl = cv.add<uint64_t>(ch.n_cells);
+    out->tot = cv.add<uint64_t>(Kz * Pz);
+    out->base = cv.add<uint64_t>(Kz * Pz);
+    out->gl = cv.add<unsigned long long>(2 * Pz);
+    out->tmp = cv.add<char>(std::max<size_t>(tmp, 1));
+    out->tmp_bytes = tmp;
+    return MS_OK;
+}
+
+int place_records(DeviceCtx *c, const PlaceChunks &ch, int tile, void *work, const PlaceSlots &s, const char *what, const PlaceCalls &calls, RecHead *h) {
+    const hipStream_t st = c->stream;
+    const int32_t P = h->P;
+    const int64_t V = h->V, chunk = ch.chunk, n_chunks = ch.n_chunks;
+    uint32_t *d_cnt = Carve::at(work, s.cnt);
+    uint64_t *d_excl = Carve::at(work, s.excl), *d_tot = Carve::at(work, s.tot), *d_base = Carve::at(work, s.base);
+    unsigned long long *d_gained = Carve::at(work, s.gl), *d_lost = d_gained + std::max<int32_t>(P, 1);
+    void *d_tmp = Carve::at(work, s.tmp);
+    auto hip_err = [&](hipError_t e, const char *op) { set_error("%s failed: %s", op, hipGetErrorString(e)); return e == hipErrorOutOfMemory ? MS_ERR_NOMEM : MS_ERR_RUNTIME; };
+    hipError_t he = hipMemsetAsync(d_gained, 0, 16 * (size_t) std::max<int32_t>(P, 1), st);
+    if (he != hipSuccess) return hip_err(he, "memset");
+
+    // one chunk's counts and their prefix sums (tally: with the gained / lost numbers -- the first time only)
+    auto count_chunk = [&](int64_t k, bool tally) -> int {
+        const int64_t v0 = k * chunk, nv = std::min(chunk, V - v0), ntx = (nv + tile - 1) / tile;
+        const size_t cells = (size_t) ntx * (size_t) P;
+        const hipError_t e = hipMemsetAsync(d_cnt, 0, 4 * (cells + 1), st);
+        if (e != hipSuccess) return hip_err(e, "memset");
+        if (int r = calls.count(v0, nv, d_cnt, tally ? d_gained : nullptr, tally ? d_lost : nullptr)) return r;
+        size_t tmp = s.tmp_bytes;
+        return exclusive_sum_u32(d_tmp, &tmp, d_cnt, d_excl, cells + 1, st);
+    };
+
+    int rc;
+    std::vector<uint64_t> h_tot, h_base;
+    if (V > 0 && P > 0) {
+        // ---- pass 1: every chunk counted
+        for (int64_t k = 0; k < n_chunks; k++) {
+            if ((rc = count_chunk(k, true))) return rc;
+            const int64_t nv = std::min(chunk, V - k * chunk), ntx = (nv + tile - 1) / tile;
+            hipLaunchKernelGGL(row_total_kernel, dim3((unsigned) ((P + 255) / 256)), dim3(256), 0, st, d_excl, ntx, P, d_tot + (size_t) k * P);
+            if ((he = hipGetLastError()) != hipSuccess) return hip_err(he, "row totals");
+        }
+        try { h_tot.resize((size_t) n_chunks * P); h_base.resize((size_t) n_chunks * P); }
+        catch (const std::bad_alloc &) { set_error("out of host memory"); return MS_ERR_NOMEM; }
+        he = hipMemcpyAsync(h_tot.data(), d_tot, 8 * h_tot.size(), hipMemcpyDeviceToHost, st);
+        if (he == hipSuccess) he = hipStreamSynchronize(st);
+        if (he != hipSuccess) { set_error("%s count pass failed: %s", what, hipGetErrorString(he)); return he == hipErrorOutOfMemory ? MS_ERR_NOMEM : MS_ERR_RUNTIME; }
+        // ---- the motif offsets, and where every (chunk, motif) run of records starts
+        h->n = (int64_t) place_offsets(h_tot.data(), n_chunks, P, h->motif_offsets.data(), h_base.data());
+    }
+    if ((rc = calls.alloc((size_t) h->n))) return rc;
+    if (h->n > 0) {
+        // ---- pass 2: every chunk filled (its counts made again unless they are still there)
+        he = hipMemcpyAsync(d_base, h_base.data(), 8 * h_base.size(), hipMemcpyHostToDevice, st);
+        if (he != hipSuccess) return hip_err(he, "upload of the record offsets");
+        for (int64_t k = 0; k < n_chunks; k++) {
+            if (n_chunks > 1 && (rc = count_chunk(k, false))) return rc;
+            const int64_t v0 = k * chunk, nv = std::min(chunk, V - v0);
+            if ((rc = calls.fill(v0, nv, d_excl, d_base + (size_t) k * P))) return rc;
+        }
+    }
+    (void) hipEventRecord(c->ev[1], st);
+    he = hipSuccess;
+    if (P > 0) he = hipMemcpyAsync(h->gained.data(), d_gained, 8 * (size_t) P, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess && P > 0) he = hipMemcpyAsync(h->lost.data(), d_lost, 8 * (size_t) P, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipStreamSynchronize(st);
+    if (he != hipSuccess) { set_error("%s scan failed: %s", what, hipGetErrorString(he)); return he == hipErrorOutOfMemory ? MS_ERR_NOMEM : MS_ERR_RUNTIME; }
+    float ms01 = 0;
+    (void) hipEventElapsedTime(&ms01, c->ev[0], c->ev[1]);
+    h->device_ms = ms01;
+    return MS_OK;
+}
+
+void rec_release(RecHead *h) {
+    if (!h || !h->block) return;
+    (void) hipSetDevice(h->device);
+    DeviceCtx *c = nullptr;
+    if (get_ctx(h->device, &c) == MS_OK) pool_free(c, h->block, h->block_bytes); else (void) hipFree(h->block);
+    h->block = nullptr;
+}
+
+int rec_num_sites(const RecHead *h, int64_t *n) {
+    if (!h || !n) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    *n = h->n;
+    return MS_OK;
+}
+
+int rec_motif_offsets(const RecHead *h, int64_t *out) {
+    if (!h || !out) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    std::copy(h->motif_offsets.begin(), h->motif_offsets.end(), out);
+    return MS_OK;
+}
+
+int rec_motif_counts(const RecHead *h, int64_t *gained, int64_t *lost) {
+    if (!h) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    if (gained) std::copy(h->gained.begin(), h->gained.end(), gained);
+    if (lost) std::copy(h->lost.begin(), h->lost.end(), lost);
+    return MS_OK;
+}
+
+int rec_device_ms(const RecHead *h, double *ms) {
+    if (!h || !ms) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    *ms = h->device_ms;
+    return MS_OK;
+}
 
 }  // namespace ms
 
@@ -307,12 +367,7 @@ int ms_debug_varscan_dims(int32_t out[6]) {
 }
 
 void ms_varscan_free(ms_varscan *r) {
-    if (!r) return;
-    if (r->block) {
-        (void) hipSetDevice(r->device);
-        DeviceCtx *c = nullptr;
-        if (get_ctx(r->device, &c) == MS_OK) pool_free(c, r->block, r->block_bytes); else (void) hipFree(r->block);
-    }
+    rec_release(r);
     delete r;
 }
 
@@ -322,10 +377,7 @@ int ms_scan_variants(const ms_pwmset *pwms_c, const ms_genome *genome, const int
     *out = nullptr;
     if (strand_mask < 1 || strand_mask > 3) { set_error("invalid strand mask %d (1 '+', 2 '-', 3 both)", strand_mask); return MS_ERR_INVALID; }
     if (flags != 0u) { set_error("unknown variant scan flags 0x%x", flags); return MS_ERR_INVALID; }
-    {
-        int n_dev = 0;                                         // (a genome handle cannot exist without a device: say so before asking for one)
-        if (ms_device_count(&n_dev) != MS_OK || n_dev <= 0) { set_error("no usable HIP device; libmotifscan_amd has no CPU fallback"); return MS_ERR_RUNTIME; }
-    }
+    if (!require_device()) return MS_ERR_RUNTIME;
     if (!pwms_c || !genome) { set_error("NULL handle"); return MS_ERR_INVALID; }
     if (n_variants < 0 || (n_variants > 0 && (!chrom || !pos || !alt))) { set_error("bad variant arrays"); return MS_ERR_INVALID; }
     ms_pwmset *pwms = const_cast<ms_pwmset *>(pwms_c);
@@ -361,38 +413,26 @@ int ms_scan_variants(const ms_pwmset *pwms_c, const ms_genome *genome, const int
     const hipStream_t st = c->stream;
 
     // ---- chunks of variants: at most kVarMaxTiles (motif, tile) counts at a time
-    int64_t chunk = g_var_chunk.load();
-    if (chunk <= 0) chunk = std::max<int64_t>(1, kVarMaxTiles / std::max<int32_t>(P, 1)) * kVarTile;
-    chunk = std::min<int64_t>(chunk, std::max<int64_t>(V, 1));
-    const int64_t n_chunks = V > 0 ? (V + chunk - 1) / chunk : 0;
-    const int64_t ntx_max = (chunk + kVarTile - 1) / kVarTile;
-    const size_t n_cells = (size_t) ntx_max * (size_t) std::max<int32_t>(P, 1) + 1;
-
-    size_t scan_tmp = 0;
-    if ((rc = exclusive_sum_u32(nullptr, &scan_tmp, nullptr, nullptr, n_cells, st))) return rc;
-    const size_t Vz = (size_t) std::max<int64_t>(V, 1), Pz = (size_t) std::max<int32_t>(P, 1), Kz = (size_t) std::max<int64_t>(n_chunks, 1);
-    const size_t b_chrom = up256(4 * Vz), b_pos = up256(8 * Vz), b_alt = up256(Vz), b_rec = up256(sizeof(VarRec) * Vz), b_altc = up256(Vz),
-                 b_refc = up256(Vz), b_cnt = up256(4 * n_cells), b_excl = up256(8 * n_cells), b_tot = up256(8 * Kz * Pz), b_gl = up256(16 * Pz),
-                 b_tmp = up256(std::max<size_t>(scan_tmp, 1));
+    const PlaceChunks ch = place_chunks(V, P, kVarTile, kVarMaxTiles, g_var_chunk.load());
+    const size_t Vz = (size_t) std::max<int64_t>(V, 1);
+    Carve cv;
+    const auto s_chrom = cv.add<int32_t>(Vz);
+    const auto s_pos = cv.add<int64_t>(Vz);
+    const auto s_alt = cv.add<uint8_t>(Vz);
+    const auto s_rec = cv.add<VarRec>(Vz);
+    const auto s_altc = cv.add<int8_t>(Vz), s_refc = cv.add<int8_t>(Vz);
+    PlaceSlots ps;
+    if ((rc = place_slots(cv, ch, P, st, &ps))) return rc;
     void *wblk = nullptr;
     size_t wgot = 0;
-    if ((rc = pool_alloc(c, b_chrom + b_pos + b_alt + b_rec + b_altc + b_refc + b_cnt + b_excl + 2 * b_tot + b_gl + b_tmp, &wblk, &wgot))) return rc;
-    char *b = static_cast<char *>(wblk);
-    int32_t *d_chrom = reinterpret_cast<int32_t *>(b); b += b_chrom;
-    int64_t *d_pos = reinterpret_cast<int64_t *>(b); b += b_pos;
-    uint8_t *d_alt = reinterpret_cast<uint8_t *>(b); b += b_alt;
-    VarRec *d_rec = reinterpret_cast<VarRec *>(b); b += b_rec;
-    int8_t *d_altc = reinterpret_cast<int8_t *>(b); b += b_altc;
-    int8_t *d_refc = reinterpret_cast<int8_t *>(b); b += b_refc;
-    uint32_t *d_cnt = reinterpret_cast<uint32_t *>(b); b += b_cnt;
-    uint64_t *d_excl = reinterpret_cast<uint64_t *>(b); b += b_excl;
-    uint64_t *d_tot = reinterpret_cast<uint64_t *>(b); b += b_tot;          // [chunks][P] records of the motif in the chunk
-    uint64_t *d_base = reinterpret_cast<uint64_t *>(b); b += b_tot;         // [chunks][P] where they go
-    unsigned long long *d_gained = reinterpret_cast<unsigned long long *>(b);
-    unsigned long long *d_lost = d_gained + Pz; b += b_gl;
-    void *d_tmp = b;
+    if ((rc = pool_alloc(c, cv.bytes(), &wblk, &wgot))) return rc;
+    int32_t *d_chrom = Carve::at(wblk, s_chrom);
+    int64_t *d_pos = Carve::at(wblk, s_pos);
+    uint8_t *d_alt = Carve::at(wblk, s_alt);
+    VarRec *d_rec = Carve::at(wblk, s_rec);
+    int8_t *d_altc = Carve::at(wblk, s_altc), *d_refc = Carve::at(wblk, s_refc);
     ms_varscan *raw = res.release();
-    auto fail = [&](int code) { pool_free(c, wblk, wgot); ms_varscan_free(raw); return code; };
+    auto fail = [&](int code) { (void) hipStreamSynchronize(st); pool_free(c, wblk, wgot); ms_varscan_free(raw); return code; };   // (nothing queued may still read the blocks)
     auto hip_fail = [&](hipError_t e, const char *what) { set_error("%s failed: %s", what, hipGetErrorString(e)); return fail(e == hipErrorOutOfMemory ? MS_ERR_NOMEM : MS_ERR_RUNTIME); };
 
     VarLaunch L;
@@ -422,98 +462,46 @@ int ms_scan_variants(const ms_pwmset *pwms_c, const ms_genome *genome, const int
         if (he == hipSuccess) he = hipMemcpyAsync(raw->ref_codes.data(), d_refc, (size_t) V, hipMemcpyDeviceToHost, st);
         if (he != hipSuccess) return hip_fail(he, "variant upload");
     }
-    he = hipMemsetAsync(d_gained, 0, 16 * Pz, st);
-    if (he != hipSuccess) return hip_fail(he, "memset");
-    const VarOut none{};
 
-    // one chunk's counts and their prefix sums (tally: with the gained / lost numbers -- the first time only)
-    auto count_chunk = [&](int64_t k, bool tally) -> int {
-        const int64_t v0 = k * chunk, nv = std::min(chunk, V - v0), ntx = (nv + kVarTile - 1) / kVarTile;
-        const size_t cells = (size_t) ntx * (size_t) P;
-        hipError_t e = hipMemsetAsync(d_cnt, 0, 4 * (cells + 1), st);
-        if (e != hipSuccess) { set_error("memset failed: %s", hipGetErrorString(e)); return MS_ERR_RUNTIME; }
-        int r = launch_var_scan<false>(L, v0, nv, d_cnt, nullptr, nullptr, tally ? d_gained : nullptr, tally ? d_lost : nullptr, none, st);
-        if (r) return r;
-        size_t tmp = scan_tmp;
-        return exclusive_sum_u32(d_tmp, &tmp, d_cnt, d_excl, cells + 1, st);
+    VarOut O{};                                                // (no arrays while counting)
+    PlaceCalls calls;
+    calls.count = [&](int64_t v0, int64_t nv, uint32_t *tile_cnt, unsigned long long *gained, unsigned long long *lost) {
+        return launch_var_scan<false>(L, v0, nv, tile_cnt, nullptr, nullptr, gained, lost, O, st);
     };
-
-    std::vector<uint64_t> h_tot, h_base;
-    if (V > 0 && P > 0) {
-        // ---- pass 1: every chunk counted
-        for (int64_t k = 0; k < n_chunks; k++) {
-            if ((rc = count_chunk(k, true))) return fail(rc);
-            const int64_t nv = std::min(chunk, V - k * chunk), ntx = (nv + kVarTile - 1) / kVarTile;
-            hipLaunchKernelGGL(var_row_total_kernel, dim3((unsigned) ((P + 255) / 256)), dim3(256), 0, st, d_excl, ntx, P, d_tot + (size_t) k * P);
-            if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "row totals");
-        }
-        try { h_tot.resize((size_t) n_chunks * P); h_base.resize((size_t) n_chunks * P); }
-        catch (const std::bad_alloc &) { set_error("out of host memory"); return fail(MS_ERR_NOMEM); }
-        he = hipMemcpyAsync(h_tot.data(), d_tot, 8 * h_tot.size(), hipMemcpyDeviceToHost, st);
-        if (he == hipSuccess) he = hipStreamSynchronize(st);
-        if (he != hipSuccess) return hip_fail(he, "variant count pass");
-        // ---- the motif offsets, and where every (chunk, motif) run of records starts
-        uint64_t at = 0;
-        for (int32_t m = 0; m < P; m++) {
-            raw->motif_offsets[(size_t) m] = (int64_t) at;
-            for (int64_t k = 0; k < n_chunks; k++) { h_base[(size_t) k * P + m] = at; at += h_tot[(size_t) k * P + m]; }
-        }
-        raw->motif_offsets[(size_t) P] = (int64_t) at;
-        raw->n = (int64_t) at;
-    }
-    {
-        const size_t n = (size_t) raw->n, nz = std::max<size_t>(n, 1);
+    calls.fill = [&](int64_t v0, int64_t nv, const uint64_t *tile_excl, const uint64_t *row_base) {
+        return launch_var_scan<true>(L, v0, nv, nullptr, tile_excl, row_base, nullptr, nullptr, O, st);
+    };
+    calls.alloc = [&](size_t n) {
+        const size_t nz = std::max<size_t>(n, 1);
+        Carve rv;
+        const auto s_variant = rv.add<int64_t>(nz), s_start = rv.add<int64_t>(nz);
+        const auto s_sref = rv.add<double>(nz), s_salt = rv.add<double>(nz);
+        const auto s_strand = rv.add<int8_t>(nz);
+        const auto s_state = rv.add<uint8_t>(nz);
         void *blk = nullptr;
         size_t got = 0;
-        if ((rc = pool_alloc(c, 4 * up256(8 * nz) + 2 * up256(nz), &blk, &got))) return fail(rc);
+        if (int r = pool_alloc(c, rv.bytes(), &blk, &got)) return r;
         raw->block = blk;
         raw->block_bytes = got;
-        char *p = static_cast<char *>(blk);
-        raw->d_variant = reinterpret_cast<int64_t *>(p); p += up256(8 * nz);
-        raw->d_start = reinterpret_cast<int64_t *>(p); p += up256(8 * nz);
-        raw->d_score_ref = reinterpret_cast<double *>(p); p += up256(8 * nz);
-        raw->d_score_alt = reinterpret_cast<double *>(p); p += up256(8 * nz);
-        raw->d_strand = reinterpret_cast<int8_t *>(p); p += up256(nz);
-        raw->d_state = reinterpret_cast<uint8_t *>(p);
-    }
-    if (raw->n > 0) {
-        // ---- pass 2: every chunk filled (its counts made again unless they are still there)
-        VarOut O;
-        O.variant = raw->d_variant; O.start = raw->d_start; O.score_ref = raw->d_score_ref; O.score_alt = raw->d_score_alt;
-        O.strand = raw->d_strand; O.state = raw->d_state; O.cap = (uint64_t) raw->n;
-        he = hipMemcpyAsync(d_base, h_base.data(), 8 * h_base.size(), hipMemcpyHostToDevice, st);
-        if (he != hipSuccess) return hip_fail(he, "upload of the record offsets");
-        for (int64_t k = 0; k < n_chunks; k++) {
-            if (n_chunks > 1 && (rc = count_chunk(k, false))) return fail(rc);
-            const int64_t v0 = k * chunk, nv = std::min(chunk, V - v0);
-            if ((rc = launch_var_scan<true>(L, v0, nv, nullptr, d_excl, d_base + (size_t) k * P, nullptr, nullptr, O, st))) return fail(rc);
-        }
-    }
-    (void) hipEventRecord(c->ev[1], st);
-    he = hipSuccess;
-    if (P > 0) he = hipMemcpyAsync(raw->gained.data(), d_gained, 8 * (size_t) P, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess && P > 0) he = hipMemcpyAsync(raw->lost.data(), d_lost, 8 * (size_t) P, hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess) he = hipStreamSynchronize(st);
-    if (he != hipSuccess) return hip_fail(he, "variant scan");
-    float ms01 = 0;
-    (void) hipEventElapsedTime(&ms01, c->ev[0], c->ev[1]);
-    raw->device_ms = ms01;
+        O.variant = raw->d_variant = Carve::at(blk, s_variant);
+        O.start = raw->d_start = Carve::at(blk, s_start);
+        O.score_ref = raw->d_score_ref = Carve::at(blk, s_sref);
+        O.score_alt = raw->d_score_alt = Carve::at(blk, s_salt);
+        O.strand = raw->d_strand = Carve::at(blk, s_strand);
+        O.state = raw->d_state = Carve::at(blk, s_state);
+        O.cap = (uint64_t) n;
+        return MS_OK;
+    };
+    if ((rc = place_records(c, ch, kVarTile, wblk, ps, "variant", calls, raw))) return fail(rc);
     pool_free(c, wblk, wgot);
     *out = raw;
     return MS_OK;
 }
 
-int ms_varscan_num_sites(const ms_varscan *r, int64_t *n) {
-    if (!r || !n) { set_error("NULL argument"); return MS_ERR_INVALID; }
-    *n = r->n;
-    return MS_OK;
-}
-
-int ms_varscan_motif_offsets(const ms_varscan *r, int64_t *out) {
-    if (!r || !out) { set_error("NULL argument"); return MS_ERR_INVALID; }
-    std::copy(r->motif_offsets.begin(), r->motif_offsets.end(), out);
-    return MS_OK;
-}
+int ms_varscan_num_sites(const ms_varscan *r, int64_t *n) { return rec_num_sites(r, n); }
+int ms_varscan_motif_offsets(const ms_varscan *r, int64_t *out) { return rec_motif_offsets(r, out); }
+int ms_varscan_motif_counts(const ms_varscan *r, int64_t *gained, int64_t *lost) { return rec_motif_counts(r, gained, lost); }
+int ms_varscan_device_ms(const ms_varscan *r, double *ms) { return rec_device_ms(r, ms); }
 
 int ms_varscan_sites(const ms_varscan *r, int64_t *variant, int64_t *start, int8_t *strand, double *score_ref, double *score_alt, uint8_t *state) {
     if (!r) { set_error("NULL argument"); return MS_ERR_INVALID; }
@@ -532,19 +520,6 @@ int ms_varscan_sites(const ms_varscan *r, int64_t *variant, int64_t *start, int8
 int ms_varscan_ref_codes(const ms_varscan *r, int8_t *out) {
     if (!r || (!out && r->V > 0)) { set_error("NULL argument"); return MS_ERR_INVALID; }
     std::copy(r->ref_codes.begin(), r->ref_codes.end(), out);
-    return MS_OK;
-}
-
-int ms_varscan_motif_counts(const ms_varscan *r, int64_t *gained, int64_t *lost) {
-    if (!r) { set_error("NULL argument"); return MS_ERR_INVALID; }
-    if (gained) std::copy(r->gained.begin(), r->gained.end(), gained);
-    if (lost) std::copy(r->lost.begin(), r->lost.end(), lost);
-    return MS_OK;
-}
-
-int ms_varscan_device_ms(const ms_varscan *r, double *ms) {
-    if (!r || !ms) { set_error("NULL argument"); return MS_ERR_INVALID; }
-    *ms = r->device_ms;
     return MS_OK;
 }
 
