@@ -197,6 +197,21 @@ int ms_debug_shuffle_dims(int32_t out[4]);
  * out[3] the region hints.  MS_ERR_INVALID before the first call. */
 int ms_debug_shuffle_stage_ms(double out[4]);
 
+/* The path constants of ms_seqset_kmer_counts / ms_genome_kmer_counts, as constants of the build: out[0] the threads of a block; out[1] the
+ * bases of one block tile of the count pass; out[2] the largest k counted in a block table of LDS counters (lds_k) -- above it the counts go
+ * to global memory directly; out[3] the most windows of a sequence whose codes are sorted in LDS for nseq (sort_windows) -- a longer
+ * sequence sets bits in a bitmap in device scratch; out[4] the sequences per block of that sort tier (1: one block per sequence); out[5] the
+ * default budget of a batch of bitmaps in MiB; out[6], out[7] reserved, 0.  Tests size their boundary cases from here.  Needs no GPU. */
+int ms_debug_kmer_dims(int32_t out[8]);
+/* The bitmaps of the long sequences of a k-mer count are taken in batches of (budget / bitmap bytes, at least one) sequences: bytes > 0 sets
+ * the budget for the calls that follow in this process, 0 gives it back to the library.  *previous (may be NULL) = the value before.  The
+ * result does not depend on it.  Needs no GPU. */
+int ms_debug_kmer_bitmap_budget(int64_t bytes, int64_t *previous);
+/* A set as a batch stream's upload stage leaves it: ASCII and offsets in HBM, the planes still to be packed by its first scan.  The entry
+ * points that read the planes directly (ms_seqset_kmer_counts, ms_seqset_shuffle, ms_seqset_packed_host) refuse it with MS_ERR_INVALID: this
+ * is how a test gets one.  Every scan entry point takes it and packs it; free it with ms_seqset_free.  Needs a GPU. */
+int ms_debug_seqset_upload_only(const char *bases, const int64_t *offsets, int64_t n_seqs, ms_seqset **out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@ motifscan_amd -- MI355X-native drop-in for ONE hot path of shao-lab/MotifScan: t
     motifscan_amd.dist      region sharding over the GPUs of a node + the one all-reduce
     motifscan_amd.synth     seeded synthetic workloads (bench.py, tests)
     motifscan_amd.shuffle   the sequential restatement of ms_seqset_shuffle (mono- and dinucleotide shuffled controls), numpy only
+    motifscan_amd.kmers     k-mer codes, the restatement of ms_seqset_kmer_counts, Markov backgrounds, k-mer enrichment, seed matrices
 
 There is no CPU fallback anywhere in this package.
 """

@@ -242,6 +242,11 @@ def lib():
         "ms_seqset_shuffle": (c_int, [vp, c_int, ctypes.c_uint64, c_i64, c_u32, pvp]),
         "ms_debug_shuffle_dims": (c_int, [pi32]),
         "ms_debug_shuffle_stage_ms": (c_int, [pd]),
+        "ms_seqset_kmer_counts": (c_int, [vp, c_i32, c_u32, pu8, vp, vp, pi64, pd]),
+        "ms_genome_kmer_counts": (c_int, [vp, c_i32, c_u32, pu8, vp, vp, pi64, pd]),
+        "ms_debug_kmer_dims": (c_int, [pi32]),
+        "ms_debug_kmer_bitmap_budget": (c_int, [c_i64, pi64]),
+        "ms_debug_seqset_upload_only": (c_int, [ctypes.c_char_p, pi64, c_i64, pvp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -471,6 +476,14 @@ class SeqSet:
         shuffle.shuffle_host(...) byte for byte."""
         return seqset_shuffled(self, kind, seed, seq_index_base)
 
+    def kmer_counts(self, k, canonical=False, sel=None, nseq=True, out=None, timing=None):
+        """The k-mer spectrum of the set's sequences (ms_seqset_kmer_counts) as a kmers.KmerCounts: occ[c] the windows of code c, nseq[c]
+        the sequences that hold it at least once (nseq=False: not made), and the four totals.  A window with a non-ACGT base is left
+        out; canonical counts a window under min(code, code of its reverse complement).  sel: one flag per sequence, or None for all.
+        out: (occ, nseq) -- each an int64 numpy array [4^k], the device pointer of a torch tensor as an int (it is returned in the
+        array's place), or None (a new array).  timing: a dict that receives 'device_ms'.  Equals kmers.kmer_counts_host exactly."""
+        return _kmer_counts(lib().ms_seqset_kmer_counts, self.h, self.n_seqs, k, canonical, sel, nseq, out, timing)
+
     def close(self):
         if getattr(self, "h", None):
             lib().ms_seqset_free(self.h)
@@ -489,6 +502,78 @@ def seqset_shuffled(seqs, kind, seed, seq_index_base=0):
     sq.offsets = seqs._host_offsets() if isinstance(seqs, SeqSet) else np.ascontiguousarray(seqs.offsets, dtype=np.int64)
     sq.n_seqs = sq.offsets.size - 1
     sq.n_bases = int(sq.offsets[-1])
+    return sq
+
+
+MS_KMER_MAX_K, MS_KMER_CANONICAL = 12, 1
+
+
+def _kmer_counts(fn, handle, n_seqs, k, canonical, sel, nseq, out, timing):
+    """The call behind SeqSet.kmer_counts and ResidentGenome.kmer_counts.  The library checks k, the flags and the handle."""
+    from .kmers import KmerCounts
+    k = int(k)
+    n_codes = 4 ** k if 1 <= k <= MS_KMER_MAX_K else 1          # (an invalid k: the library refuses it before it writes)
+    if sel is not None:
+        sel = np.ascontiguousarray(sel)
+        if sel.shape != (n_seqs,):
+            raise ValueError(f"sel must hold one flag per sequence ({n_seqs}), got shape {sel.shape}")
+        sel = np.ascontiguousarray(sel != 0, dtype=np.uint8)
+    given = (None, None) if out is None else tuple(out)
+    if len(given) != 2:
+        raise ValueError("out must be (occ, nseq)")
+    dst, kept = [], []
+    for a, want in zip(given, (True, bool(nseq))):
+        if not want:
+            dst.append(None)
+            kept.append(None)
+            continue
+        if isinstance(a, int):
+            dst.append(a)
+            kept.append(a)
+            continue
+        if a is None:
+            a = np.zeros(n_codes, dtype=np.int64)
+        if a.dtype != np.int64 or a.shape != (n_codes,) or not a.flags.c_contiguous:
+            raise ValueError("an output must be a C-contiguous int64 array of 4^k entries")
+        dst.append(a.ctypes.data)
+        kept.append(a)
+    totals = np.zeros(4, dtype=np.int64)
+    ms = ctypes.c_double()
+    check(fn(handle, k, MS_KMER_CANONICAL if canonical else 0, None if sel is None else ptr(sel, ctypes.c_uint8), ctypes.c_void_p(dst[0]),
+             ctypes.c_void_p(dst[1]), ptr(totals, ctypes.c_int64), ctypes.byref(ms)))
+    if timing is not None:
+        timing["device_ms"] = ms.value
+    return KmerCounts(k, bool(canonical), kept[0], kept[1], *totals.tolist())
+
+
+def kmer_dims():
+    """ms_debug_kmer_dims: dict(threads, tile_bases, lds_k, sort_windows, sort_seqs_per_block, bitmap_budget_mib) -- the sizes at which
+    the k-mer counts change path.  Constants of the build; no device."""
+    out = np.zeros(8, dtype=np.int32)
+    check(lib().ms_debug_kmer_dims(ptr(out, ctypes.c_int32)))
+    return dict(zip(("threads", "tile_bases", "lds_k", "sort_windows", "sort_seqs_per_block", "bitmap_budget_mib"), out.tolist()))
+
+
+def kmer_bitmap_budget(nbytes):
+    """ms_debug_kmer_bitmap_budget: the bytes of bitmaps a k-mer count holds at once for the calls that follow (0 = the library's own);
+    returns the value before."""
+    prev = ctypes.c_int64()
+    check(lib().ms_debug_kmer_bitmap_budget(int(nbytes), ctypes.byref(prev)))
+    return prev.value
+
+
+def seqset_upload_only(seqs):
+    """ms_debug_seqset_upload_only: a SeqSet of these strings as a batch stream's upload stage leaves it, its planes not packed yet (tests
+    of the entry points that refuse such a set)."""
+    raw = "".join(seqs).encode("latin-1")
+    sq = SeqSet.__new__(SeqSet)
+    sq.offsets = np.zeros(len(seqs) + 1, dtype=np.int64)
+    if seqs:
+        np.cumsum([len(s) for s in seqs], out=sq.offsets[1:])
+    sq.n_seqs, sq.n_bases = len(seqs), len(raw)
+    h = ctypes.c_void_p()
+    check(lib().ms_debug_seqset_upload_only(raw, ptr(sq.offsets, ctypes.c_int64), sq.n_seqs, ctypes.byref(h)))
+    sq.h = h
     return sq
 
 
@@ -616,6 +701,11 @@ class ResidentGenome:
         out = np.zeros((len(self.names), 4), dtype=np.int64)
         check(lib().ms_genome_base_counts(self.h, ptr(out, ctypes.c_int64)))
         return out
+
+    def kmer_counts(self, k, canonical=False, sel=None, nseq=True, out=None, timing=None):
+        """SeqSet.kmer_counts over the genome, whose sequences are its chromosomes in file order (ms_genome_kmer_counts): k = 1 without
+        canonical is base_counts().sum(0); nseq counts chromosomes; sel: one flag per chromosome."""
+        return _kmer_counts(lib().ms_genome_kmer_counts, self.h, len(self.names), k, canonical, sel, nseq, out, timing)
 
     def _exceptions(self):
         """The ascending genome positions of the non-ACGT bytes that are not N / n: the device planes mark them as N, the reference's

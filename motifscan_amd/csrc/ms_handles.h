@@ -5,6 +5,7 @@
 // ms_personal.hip (a variant set spliced into a new resident genome, and the lift map between the two), ms_sitestack.hip (base counts per
 // motif column over a result's sites), ms_ranksum.hip (rank sums and passing-region counts over best-site matrices), ms_affinity.hip (the
 // summed likelihood ratio of every cell), ms_shuffle.hip (a sequence set shuffled into a new one: mono- and dinucleotide controls),
+// ms_kmers.hip (the k-mer counts of a sequence set or a genome),
 // ms_variants.hip and ms_alleles.hip (the record scans over variants: one placement driver, place_records, and one handle head, RecHead).
 #pragma once
 #include <sched.h>

@@ -496,6 +496,22 @@ class Scanner:
             pw.close()
         return sitestack.SiteStack(counts, di, n_sites, np.asarray(lengths, dtype=np.int64), int(flank))
 
+    def kmer_counts(self, k, canonical=True, sel=None):
+        """The k-mer spectrum of the scanner's regions as a kmers.KmerCounts (ms_seqset_kmer_counts on the scanner's own device set, so a
+        shuffled scanner or one over a personal genome counts its own bases): occ, the windows per k-mer; nseq, the regions that hold it
+        at least once.  canonical folds a k-mer onto its reverse complement (a region set has no strand); pass canonical=False for
+        KmerCounts.markov().  sel: one flag per region.  `strand`, `p_value` and `remove_dup` have no meaning here."""
+        return self._seqset().kmer_counts(k, canonical=canonical, sel=sel)
+
+    def kmer_enrichment(self, control, k, canonical=True):
+        """The k-mers enriched in this scanner's regions against the control scanner's, counted HOMER's way (a region counts a k-mer at
+        most once): a kmers.KmerEnrichment -- .top(n) lists the seeds, kmers.seed_matrix turns one into a PWM for the next scan.
+        `control` is another Scanner: a genomic control, or `self.shuffled(...)`."""
+        from . import kmers
+        if not isinstance(control, Scanner):
+            raise ValueError("control must be a Scanner")
+        return kmers.enrichment(self.kmer_counts(k, canonical), control.kmer_counts(k, canonical))
+
     def scan_motifs(self, pwms):
         """motif_sites[n_pwms][n_regions] -> list[MotifSite] (scanner.py:89-132), as a read-only nested view over the
         device's flat hit arrays: a region's list is built when it is indexed (motifscan_amd/sites.py), so the call costs
