@@ -367,8 +367,10 @@ int ms_result_num_hits(const ms_result *res, int64_t *n_hits);
 int ms_result_motif_offsets(const ms_result *res, int64_t *out /* [P+1] */);
 /* Copy the hit arrays to host buffers of length n_hits (any pointer may be NULL). */
 int ms_result_hits(const ms_result *res, int64_t *seq_idx, int64_t *pos, double *score, int8_t *strand);
-/* The same arrays in library-owned pinned host memory (one device-to-host copy at PCIe rate); the
- * pointers stay valid until the result is freed or de-duplicated. */
+/* The same arrays in library-owned pinned host memory (one device-to-host copy at PCIe rate).  A result has ONE pinned buffer,
+ * which this call shares with ms_result_hits_packed_host and ms_result_hits_packed12_host and which holds one form at a time: the
+ * pointers stay valid until the result is freed, de-duplicated, or asked for a DIFFERENT form -- such a request overwrites the
+ * buffer even when it is refused (MS_ERR_INVALID: a hit does not fit the form).  Call again to get the arrays back. */
 int ms_result_hits_host(ms_result *res, const int64_t **seq_idx, const int64_t **pos, const double **score,
                         const int8_t **strand);
 int ms_result_region_counts(const ms_result *res, int64_t *out /* [P] */);
@@ -637,11 +639,14 @@ int  ms_affinity_rank_sum(const ms_affinity *a, const uint8_t *sel_a /* [Ra] or 
 
 /* The hit arrays in COMPACT form in library-owned pinned host memory: coord[i] = seq_idx << 32 | pos << 1 | (strand - 1),
  * score[i] -- 16 bytes per hit on the host link instead of 25.  Needs seq_idx < 2^32 and pos < 2^31 (MS_ERR_INVALID
- * otherwise).  Valid until the result is freed or de-duplicated. */
+ * otherwise).  Valid until the result is freed or de-duplicated, or a different form is asked for (ms_result_hits_host,
+ * ms_result_hits_packed12_host; a refused request included): the three accessors share one pinned buffer. */
 int ms_result_hits_packed_host(ms_result *res, const uint64_t **coord, const double **score);
 /* ... and in 12 bytes per hit: coord32[i] = seq_idx << *shift | pos << 1 | (strand - 1), score[i] -- for results whose region indices and
  * positions fit 31 bits together (a batch of 250 000 regions of 500 bp: 18 + 9), i.e. every batch of a batch stream; MS_ERR_INVALID (and the
- * 16-byte form stays available) when they do not.  Same list building (cscore.c:443-471), a quarter less on the host link. */
+ * 16-byte form stays available) when they do not.  Same list building (cscore.c:443-471), a quarter less on the host link.  The
+ * pointers are valid until the result is freed or de-duplicated, or a different form is asked for (ms_result_hits_host,
+ * ms_result_hits_packed_host): the three accessors share one pinned buffer.  A refused call leaves no form in the buffer. */
 int ms_result_hits_packed12_host(ms_result *res, const uint32_t **coord, const double **score, int32_t *shift);
 /* Which compact form a result holds after a batch stream's copy-out: *bytes_per_hit = 12, 16, or 0 (the plain arrays). */
 int ms_result_packed_form(const ms_result *res, int32_t *bytes_per_hit);

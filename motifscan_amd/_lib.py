@@ -866,9 +866,11 @@ class ScanResult:
     def hits(self, copy=True, packed=False, motif=True):
         """dict of numpy arrays: seq_idx, pos, score, strand (1 '+', 2 '-'), motif (motif=False leaves the per-hit motif
         index out: it is motif_offsets expanded, 4 bytes per hit that few callers read).
-        copy=False returns views of the library's pinned host buffers; the views keep this result alive (they are only
-        invalidated by an explicit close() or dedup()).  packed=True moves 16 instead of 25 bytes per hit over the host
-        link (ms_result_hits_packed_host) and unpacks on the host -- the arrays are then always fresh copies."""
+        copy=False returns views of the library's pinned host buffer; the views keep this result alive.  The result has ONE such
+        buffer, which holds one form at a time: the views are invalidated by an explicit close() or dedup() and ALSO by a request
+        for another form -- hits(packed=...) or packed_words(), even one that is refused -- which overwrites it; fetch them again
+        after such a call.  Arrays of copy=True are the caller's own and never change.  packed=True moves 16 instead of 25 bytes
+        per hit over the host link (ms_result_hits_packed_host) and unpacks on the host -- the arrays are then always fresh copies."""
         if packed:
             return self._hits_packed(None if packed is True else int(packed))
         if self._hits is None or (copy and not self._hits_owned):
@@ -899,34 +901,46 @@ class ScanResult:
         check(lib().ms_result_packed_form(self.h, ctypes.byref(b)))
         return b.value
 
+    def hits_pageable(self):
+        """The four hit arrays through ms_result_hits: four device copies into buffers of the caller's (here fresh numpy arrays),
+        no pinned buffer involved."""
+        n = self.n_hits
+        seq_idx, pos, score_, strand = (np.zeros(n, dtype=t) for t in (np.int64, np.int64, np.float64, np.int8))
+        check(lib().ms_result_hits(self.h, ptr(seq_idx, ctypes.c_int64), ptr(pos, ctypes.c_int64), ptr(score_, ctypes.c_double), ptr(strand, ctypes.c_int8)))
+        return {"seq_idx": seq_idx, "pos": pos, "score": score_, "strand": strand, "motif_offsets": self.motif_offsets}
+
+    def packed_words(self, form, copy=True):
+        """The compact form as the library hands it over: (coord uint64 [n] for form 16 / uint32 [n] for form 12, score float64 [n],
+        shift -- 0 for form 16).  copy=False: views of the pinned buffer, valid until the next request for any form, close() or
+        dedup().  ValueError if a hit does not fit the form; the result stays usable."""
+        n = self.n_hits
+        sh = ctypes.c_int32(0)
+        pv = ctypes.POINTER(ctypes.c_double)()
+        if int(form) == 12:
+            pc = ctypes.POINTER(ctypes.c_uint32)()
+            check(lib().ms_result_hits_packed12_host(self.h, ctypes.byref(pc), ctypes.byref(pv), ctypes.byref(sh)))
+        elif int(form) == 16:
+            pc = ctypes.POINTER(ctypes.c_uint64)()
+            check(lib().ms_result_hits_packed_host(self.h, ctypes.byref(pc), ctypes.byref(pv)))
+        else:
+            raise ValueError("form must be 12 or 16")
+        if n == 0:
+            return np.zeros(0, dtype=np.uint32 if int(form) == 12 else np.uint64), np.zeros(0, dtype=np.float64), sh.value
+        coord, score_ = np.ctypeslib.as_array(pc, shape=(n,)), np.ctypeslib.as_array(pv, shape=(n,))
+        return (coord.copy(), score_.copy(), sh.value) if copy else (coord, score_, sh.value)
+
     def _hits_packed(self, form=None):
         """form: None = whatever the result holds already (a stream's copy-out), else 12 / 16."""
-        n = self.n_hits
         if form is None:
             form = self.packed_form() or 16
-        if form == 12:
-            pc, pv, sh = ctypes.POINTER(ctypes.c_uint32)(), ctypes.POINTER(ctypes.c_double)(), ctypes.c_int32()
-            check(lib().ms_result_hits_packed12_host(self.h, ctypes.byref(pc), ctypes.byref(pv), ctypes.byref(sh)))
-            if n:
-                coord = np.ctypeslib.as_array(pc, shape=(n,))
-                score_ = np.ctypeslib.as_array(pv, shape=(n,)).copy()
-                seq_idx = (coord >> np.uint32(sh.value)).astype(np.int64)
-                pos = ((coord & np.uint32((1 << sh.value) - 1)) >> np.uint32(1)).astype(np.int64)
-                strand = ((coord & np.uint32(1)) + np.uint32(1)).astype(np.int8)
-            else:
-                seq_idx, pos, score_, strand = (np.zeros(0, dtype=t) for t in (np.int64, np.int64, np.float64, np.int8))
-            motif = np.repeat(np.arange(self.n_pwms, dtype=np.int32), np.diff(self.motif_offsets))
-            return {"seq_idx": seq_idx, "pos": pos, "score": score_, "strand": strand, "motif": motif, "motif_offsets": self.motif_offsets}
-        pc, pv = ctypes.POINTER(ctypes.c_uint64)(), ctypes.POINTER(ctypes.c_double)()
-        check(lib().ms_result_hits_packed_host(self.h, ctypes.byref(pc), ctypes.byref(pv)))
-        if n:
-            coord = np.ctypeslib.as_array(pc, shape=(n,))
-            score_ = np.ctypeslib.as_array(pv, shape=(n,)).copy()
-            seq_idx = (coord >> np.uint64(32)).astype(np.int64)
-            pos = ((coord & np.uint64(0xFFFFFFFF)) >> np.uint64(1)).astype(np.int64)
-            strand = ((coord & np.uint64(1)) + np.uint64(1)).astype(np.int8)
-        else:
-            seq_idx, pos, score_, strand = (np.zeros(0, dtype=t) for t in (np.int64, np.int64, np.float64, np.int8))
+        form = 12 if form == 12 else 16
+        coord, score_, shift = self.packed_words(form, copy=False)
+        score_ = score_.copy()
+        word = coord.dtype.type
+        low = word(shift if form == 12 else 32)
+        seq_idx = (coord >> low).astype(np.int64)
+        pos = ((coord & word((1 << int(low)) - 1)) >> word(1)).astype(np.int64)
+        strand = ((coord & word(1)) + word(1)).astype(np.int8)
         motif = np.repeat(np.arange(self.n_pwms, dtype=np.int32), np.diff(self.motif_offsets))
         return {"seq_idx": seq_idx, "pos": pos, "score": score_, "strand": strand, "motif": motif,
                 "motif_offsets": self.motif_offsets}

@@ -232,7 +232,8 @@ int ms_result_hits(const ms_result *r, int64_t *seq_idx, int64_t *pos, double *s
 }
 
 // Hit arrays in library-owned PINNED host memory (one D2H copy at PCIe rate instead of four copies
-// into pageable buffers).  The pointers stay valid until the result is freed or de-duplicated.
+// into pageable buffers).  The result has ONE pinned buffer, shared with the two compact accessors below and holding one form at a
+// time: the pointers stay valid until the result is freed or de-duplicated or another form is asked for (a refused request included).
 // The copy runs on the device's copy-out stream, beside whatever scan is running.
 int ms_result_hits_host(ms_result *r, const int64_t **seq_idx, const int64_t **pos, const double **score,
                         const int8_t **strand) {
@@ -242,6 +243,7 @@ int ms_result_hits_host(ms_result *r, const int64_t **seq_idx, const int64_t **p
     const size_t n_round = (n + 65535) & ~(size_t) 65535;
     const size_t bytes = 25 * n_round + 64;
     if (r->h_pinned_hits != r->n_hits || !r->h_pinned || r->h_packed) {
+        r->h_pinned_hits = -1;                            // refilled from here on: whatever the buffer held is void, the flags are set on success
         if (r->h_pinned && r->h_pinned_bytes < bytes) { pinned_free(r->h_pinned, r->h_pinned_bytes); r->h_pinned = nullptr; }
         if (!r->h_pinned) {
             r->h_pinned = pinned_alloc(bytes, &r->h_pinned_bytes);
@@ -282,6 +284,7 @@ int ms_result_hits_packed_host(ms_result *r, const uint64_t **coord, const doubl
     const size_t n_round = (n + 65535) & ~(size_t) 65535;
     const size_t bytes = 16 * n_round + 64;
     if (r->h_pinned_hits != r->n_hits || !r->h_pinned || !r->h_packed || r->h_coord_shift) {
+        r->h_pinned_hits = -1;                            // refilled from here on: whatever the buffer held is void, the flags are set on success
         if (r->h_pinned && r->h_pinned_bytes < bytes) { pinned_free(r->h_pinned, r->h_pinned_bytes); r->h_pinned = nullptr; }
         if (!r->h_pinned) {
             r->h_pinned = pinned_alloc(bytes, &r->h_pinned_bytes);
@@ -343,6 +346,7 @@ int ms_result_hits_packed12_host(ms_result *r, const uint32_t **coord, const dou
     const size_t n_round = (n + 65535) & ~(size_t) 65535;
     const size_t bytes = 12 * n_round + 64;
     if (r->h_pinned_hits != r->n_hits || !r->h_pinned || !r->h_packed || !r->h_coord_shift) {
+        r->h_pinned_hits = -1;                            // refilled from here on: whatever the buffer held is void, the flags are set on success
         if (r->h_pinned && r->h_pinned_bytes < bytes) { pinned_free(r->h_pinned, r->h_pinned_bytes); r->h_pinned = nullptr; }
         if (!r->h_pinned) {
             r->h_pinned = pinned_alloc(bytes, &r->h_pinned_bytes);
