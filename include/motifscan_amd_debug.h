@@ -207,6 +207,15 @@ int ms_debug_kmer_dims(int32_t out[8]);
  * the budget for the calls that follow in this process, 0 gives it back to the library.  *previous (may be NULL) = the value before.  The
  * result does not depend on it.  Needs no GPU. */
 int ms_debug_kmer_bitmap_budget(int64_t bytes, int64_t *previous);
+/* The path constants of the counts-only forms (MS_SCAN_COUNTS_ONLY's flag map, ms_regions.hip; a MS_STREAM_NO_HITS sweep span, ms_sweep.hip),
+ * as constants of the build: out[0] the motifs the flag map's LDS histogram holds -- a set of more takes the ordered path; out[1] the threads
+ * of a block of its three kernels (the per-motif prefix cuts the motifs into out[1] ranges of ceil(P / out[1])); out[2] the hit keys per block
+ * while the grid may grow; out[3] the largest grid -- more than out[2] * out[3] keys take further trips of the blocks' loop; out[4] the gate:
+ * the flag map is taken while motifs x regions <= out[4] x the hits expected (the true number on a set's first scan, the predicted one later);
+ * out[5] the threads (= hits) of a block of the sweep's counting kernel; out[6] the most motifs a counts-only span takes; out[7] reserved, 0.
+ * Tests size their boundary cases from here.  Needs no GPU. */
+int ms_debug_counts_dims(int32_t out[8]);
+
 /* A set as a batch stream's upload stage leaves it: ASCII and offsets in HBM, the planes still to be packed by its first scan.  The entry
  * points that read the planes directly (ms_seqset_kmer_counts, ms_seqset_shuffle, ms_seqset_packed_host) refuse it with MS_ERR_INVALID: this
  * is how a test gets one.  Every scan entry point takes it and packs it; free it with ms_seqset_free.  Needs a GPU. */

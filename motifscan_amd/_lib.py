@@ -246,6 +246,7 @@ def lib():
         "ms_genome_kmer_counts": (c_int, [vp, c_i32, c_u32, pu8, vp, vp, pi64, pd]),
         "ms_debug_kmer_dims": (c_int, [pi32]),
         "ms_debug_kmer_bitmap_budget": (c_int, [c_i64, pi64]),
+        "ms_debug_counts_dims": (c_int, [pi32]),
         "ms_debug_seqset_upload_only": (c_int, [ctypes.c_char_p, pi64, c_i64, pvp]),
     }
     for name, (res, args) in sig.items():
@@ -552,6 +553,14 @@ def kmer_dims():
     out = np.zeros(8, dtype=np.int32)
     check(lib().ms_debug_kmer_dims(ptr(out, ctypes.c_int32)))
     return dict(zip(("threads", "tile_bases", "lds_k", "sort_windows", "sort_seqs_per_block", "bitmap_budget_mib"), out.tolist()))
+
+
+def counts_dims():
+    """ms_debug_counts_dims: dict(bins, threads, keys_per_block, max_blocks, gate_ratio, sweep_threads, sweep_max_motifs) -- the sizes at
+    which the counts-only scan and sweep change path.  Constants of the build; no device."""
+    out = np.zeros(8, dtype=np.int32)
+    check(lib().ms_debug_counts_dims(ptr(out, ctypes.c_int32)))
+    return dict(zip(("bins", "threads", "keys_per_block", "max_blocks", "gate_ratio", "sweep_threads", "sweep_max_motifs"), out.tolist()))
 
 
 def kmer_bitmap_budget(nbytes):

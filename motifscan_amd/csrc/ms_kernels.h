@@ -162,6 +162,9 @@ int launch_order_finalize(uint64_t *keys, double *score, int64_t n, const unsign
                           uint64_t *tmp_keys, double *tmp_vals, void *ovf_buf, size_t ovf_bytes, unsigned long long *ovf_n, int run_cap,
                           hipStream_t st);
 // ms_regions.hip: counts only, from the unordered hit keys
+constexpr int kCountsGateRatio = 50;            // the flag map is taken while P x R <= this x the hits expected (scan_counts_fast, ms_scan.hip)
+constexpr int kSweepCountThreads = 256;         // threads (= hits) of a block of sweep_countonly_kernel (ms_sweep.hip)
+constexpr int kSweepCountMaxMotifs = 65536;     // motifs whose site counters fit behind a counts-only sweep result's own counts
 bool count_only_supported(int32_t P, int64_t R, int pbits);
 size_t count_only_bitmap_words(int32_t P, int64_t R);
 int launch_count_only(const uint64_t *keys, int64_t n, const unsigned long long *n_dev, int gbits, int pbits, int64_t R, int32_t P, uint32_t *bitmap,

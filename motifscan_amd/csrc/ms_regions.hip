@@ -105,8 +105,12 @@ __global__ void __launch_bounds__(256) once_expand_kernel(int64_t n, const RawKe
 // save; tools/counts_only_time.py), per-motif site numbers aggregated per wave and block in LDS; a second pass counts every motif's flags.
 // No radix sort, no finalize, no hit arrays.
 constexpr int kCountBins = 4096;                              // motifs the LDS histogram holds (more: the ordered path)
+constexpr int kCountThreads = 256;                            // threads of a block of the three kernels (a power of two: count_rows_kernel folds in halves)
+static_assert((kCountThreads & (kCountThreads - 1)) == 0 && kCountThreads % 64 == 0, "whole waves, folded in halves");
+constexpr int kCountKeysPerBlock = 4096;                      // hit keys per block of count_only_kernel, while the grid may grow
+constexpr int kCountMaxBlocks = 2048;                         // ... and its largest grid: more keys take further trips of the grid-stride loop
 
-__global__ void __launch_bounds__(256) count_only_kernel(const uint64_t *__restrict__ keys, int64_t n, const unsigned long long *__restrict__ n_dev, int gbits, int pbits,
+__global__ void __launch_bounds__(kCountThreads) count_only_kernel(const uint64_t *__restrict__ keys, int64_t n, const unsigned long long *__restrict__ n_dev, int gbits, int pbits,
                                                          int64_t row_words, int32_t P, uint32_t *__restrict__ bitmap, unsigned long long *__restrict__ motif_hits) {
     __shared__ unsigned int h_hits[kCountBins];
     for (int i = threadIdx.x; i < P; i += blockDim.x) h_hits[i] = 0;
@@ -141,21 +145,21 @@ __global__ void __launch_bounds__(256) count_only_kernel(const uint64_t *__restr
 }
 
 // one block per motif: the regions with a site = the set bits of the motif's row
-__global__ void __launch_bounds__(256) count_rows_kernel(const uint32_t *__restrict__ bitmap, int64_t row_words, unsigned long long *__restrict__ region_counts) {
-    __shared__ unsigned long long part[256];
+__global__ void __launch_bounds__(kCountThreads) count_rows_kernel(const uint32_t *__restrict__ bitmap, int64_t row_words, unsigned long long *__restrict__ region_counts) {
+    __shared__ unsigned long long part[kCountThreads];
     const uint32_t *row = bitmap + (uint64_t) blockIdx.x * (uint64_t) row_words;
     unsigned long long c = 0;
     for (int64_t w = threadIdx.x; w < row_words; w += blockDim.x) c += (unsigned long long) __popc(row[w] & 0x01010101u);      // four flag bytes per word
     part[threadIdx.x] = c;
     __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) { if ((int) threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s]; __syncthreads(); }
+    for (int s = kCountThreads / 2; s > 0; s >>= 1) { if ((int) threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s]; __syncthreads(); }
     if (threadIdx.x == 0) region_counts[blockIdx.x] = part[0];
 }
 
 // motif_first[0 .. P] = exclusive prefix of the per-motif site numbers (one block; P <= kCountBins)
-__global__ void __launch_bounds__(256) motif_prefix_kernel(const unsigned long long *__restrict__ motif_hits, int32_t P, int64_t *__restrict__ motif_first) {
-    __shared__ unsigned long long part[256];
-    const int per = (P + 255) / 256, lo = threadIdx.x * per, hi = lo + per < P ? lo + per : P;
+__global__ void __launch_bounds__(kCountThreads) motif_prefix_kernel(const unsigned long long *__restrict__ motif_hits, int32_t P, int64_t *__restrict__ motif_first) {
+    __shared__ unsigned long long part[kCountThreads];
+    const int per = (P + kCountThreads - 1) / kCountThreads, lo = threadIdx.x * per, hi = lo + per < P ? lo + per : P;
     unsigned long long sum = 0;
     for (int i = lo; i < hi; i++) sum += motif_hits[i];
     part[threadIdx.x] = sum;
@@ -163,7 +167,7 @@ __global__ void __launch_bounds__(256) motif_prefix_kernel(const unsigned long l
     unsigned long long run = 0;
     for (int t = 0; t < (int) threadIdx.x; t++) run += part[t];
     for (int i = lo; i < hi; i++) { motif_first[i] = (int64_t) run; run += motif_hits[i]; }
-    if (threadIdx.x == 255) motif_first[P] = (int64_t) run;     // (the last thread's range ends at P, or is empty and `run` is the total)
+    if (threadIdx.x == kCountThreads - 1) motif_first[P] = (int64_t) run;     // (the last thread's range ends at P, or is empty and `run` is the total)
 }
 
 bool count_only_supported(int32_t P, int64_t R, int pbits) { return pbits > 0 && P > 0 && P <= kCountBins && (double) P * (double) (R + 16) <= 6.0e9; }
@@ -175,13 +179,13 @@ int launch_count_only(const uint64_t *keys, int64_t n, const unsigned long long 
     MS_HIP(hipMemsetAsync(bitmap, 0, count_only_bitmap_words(P, R) * sizeof(uint32_t), st));
     MS_HIP(hipMemsetAsync(motif_hits, 0, (size_t) P * sizeof(unsigned long long), st));
     if (n > 0) {
-        const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(2048, (n + 4095) / 4096));
-        hipLaunchKernelGGL(count_only_kernel, dim3((unsigned) blocks), dim3(256), 0, st, keys, n, n_dev, gbits, pbits, row_words, P, bitmap, motif_hits);
+        const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(kCountMaxBlocks, (n + kCountKeysPerBlock - 1) / kCountKeysPerBlock));
+        hipLaunchKernelGGL(count_only_kernel, dim3((unsigned) blocks), dim3(kCountThreads), 0, st, keys, n, n_dev, gbits, pbits, row_words, P, bitmap, motif_hits);
         MS_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(count_rows_kernel, dim3((unsigned) P), dim3(256), 0, st, bitmap, row_words, region_counts);
+    hipLaunchKernelGGL(count_rows_kernel, dim3((unsigned) P), dim3(kCountThreads), 0, st, bitmap, row_words, region_counts);
     MS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(motif_prefix_kernel, dim3(1), dim3(256), 0, st, motif_hits, P, motif_first);
+    hipLaunchKernelGGL(motif_prefix_kernel, dim3(1), dim3(kCountThreads), 0, st, motif_hits, P, motif_first);
     MS_HIP(hipGetLastError());
     return MS_OK;
 }
@@ -189,6 +193,13 @@ int launch_count_only(const uint64_t *keys, int64_t n, const unsigned long long 
 }  // namespace ms
 
 using namespace ms;
+
+extern "C" int ms_debug_counts_dims(int32_t out[8]) {
+    if (!out) { set_error("out is NULL"); return MS_ERR_INVALID; }
+    const int32_t dims[8] = {kCountBins, kCountThreads, kCountKeysPerBlock, kCountMaxBlocks, kCountsGateRatio, kSweepCountThreads, kSweepCountMaxMotifs, 0};
+    for (int i = 0; i < 8; i++) out[i] = dims[i];
+    return MS_OK;
+}
 
 extern "C" int ms_scan_regions_once(const ms_pwmset *pwms_c, const ms_genome *g, const int32_t *chrom, const int64_t *start,
                                     const int64_t *end, int64_t n_regions, int strand_mask, uint32_t flags, ms_result **out) {

@@ -336,7 +336,7 @@ static int scan_front(ScanCtx &x, const HitOut &H, const BucketOut *B = nullptr)
 // where the sort is the cheaper way to the same counts).  Decided before the result block is sized (a second, exactly-sized run after a
 // failed prediction decides again).
 static bool scan_counts_fast(const ScanCtx &x, size_t n_expected) {
-    return x.counts_ok && (double) x.pwms->P * (double) x.seqs->R <= 50.0 * (double) std::max<size_t>(n_expected, 1);
+    return x.counts_ok && (double) x.pwms->P * (double) x.seqs->R <= (double) kCountsGateRatio * (double) std::max<size_t>(n_expected, 1);
 }
 
 // the complete per-motif offsets are on the device; one copy brings them to the host.  (Not for a scan that is only being

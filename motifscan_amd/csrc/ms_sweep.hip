@@ -107,7 +107,7 @@ __global__ void __launch_bounds__(256) sweep_scatter_kernel(int64_t n, const int
 // position and both ends of a hit's window range are non-decreasing, so hit i is the FIRST site of exactly the windows of its range that
 // the previous hit of the motif does not reach: max(0, hi_i - max(lo_i, prev_hi + 1) + 1).  One read per hit, no site is written
 // (the full hand-out writes 25 bytes per (site, window): 36 GB per pass of a 3 Gbp genome).
-__global__ void __launch_bounds__(256) sweep_countonly_kernel(int64_t n, const int64_t *__restrict__ motif_off, int32_t P,
+__global__ void __launch_bounds__(kSweepCountThreads) sweep_countonly_kernel(int64_t n, const int64_t *__restrict__ motif_off, int32_t P,
                                                               const int32_t *__restrict__ width, const int64_t *__restrict__ pos,
                                                               int32_t window, int32_t stride, int64_t n_windows,
                                                               unsigned long long *__restrict__ region_counts, unsigned long long *__restrict__ n_sites /* [P] */) {
@@ -169,7 +169,7 @@ static int launch_sweep_count(int64_t n, const int64_t *motif_off, int32_t P, co
 static int launch_sweep_countonly(int64_t n, const int64_t *motif_off, int32_t P, const int32_t *width, const int64_t *pos,
                                   int32_t window, int32_t stride, int64_t n_windows, unsigned long long *region_counts, unsigned long long *n_sites, hipStream_t st) {
     if (n == 0) return MS_OK;
-    hipLaunchKernelGGL(sweep_countonly_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, st, n, motif_off, P, width, pos,
+    hipLaunchKernelGGL(sweep_countonly_kernel, dim3((unsigned) ((n + kSweepCountThreads - 1) / kSweepCountThreads)), dim3(kSweepCountThreads), 0, st, n, motif_off, P, width, pos,
                        window, stride, n_windows, region_counts, n_sites);
     MS_HIP(hipGetLastError());
     return MS_OK;
@@ -198,8 +198,8 @@ static int sweep_counts_only(DeviceCtx *c, ms_pwmset *pwms, ms_result *r1, ms_re
     auto fail = [&](int code) { ms_result_free(raw); ms_result_free(r1); return code; };
     // what a counts-only sweep reads of a span: per motif the windows with >= 1 site, and the number of sites -- one pass over the
     // span's hit positions, nothing handed out (sweep_countonly_kernel)
-    if ((size_t) pwms->P > 65536) { set_error("internal: counts-only hand-out with more than 65536 motifs"); return fail(MS_ERR_RUNTIME); }
-    if ((rc = result_block_alloc(c, raw, 1))) return fail(rc);        // (room for >= 65536 words behind the counts)
+    if ((size_t) pwms->P > (size_t) kSweepCountMaxMotifs) { set_error("internal: counts-only hand-out with more than %d motifs", kSweepCountMaxMotifs); return fail(MS_ERR_RUNTIME); }
+    if ((rc = result_block_alloc(c, raw, 1))) return fail(rc);        // (room for >= kSweepCountMaxMotifs words behind the counts)
     raw->counts_only = true;
     const size_t P1 = (size_t) pwms->P + 1;
     unsigned long long *d_sites = reinterpret_cast<unsigned long long *>(raw->d_seq_idx);           // per-motif sites, summed on the host

@@ -14,6 +14,7 @@ The same matrices, sequences and cutoffs feed five more families, one per entry 
 or hands them out by one; a seventh family has no scan in it:
 
   * --sweep     ms_scan_sweep: one chromosome, random window / stride, against the oracle over the windows as separate regions;
+  * --sweep-counts  the same cases as spans of a MS_STREAM_NO_HITS stream: the counts-only hand-out, its per-motif site and window numbers;
   * --variants  ms_scan_variants: single-base substitutions (duplicates, any order, alt letters that add nothing) on a resident genome,
                 against the oracle over the ref and alt flank of every variant -- all-pass for the scores, the real cutoff for the states;
   * --alleles   ms_scan_alleles: alleles of 0..40 bases incl. insertions behind the last base, REF strings on even seeds;
@@ -52,7 +53,7 @@ CONDITIONS holds what the seeds of a family must put on the boundary.
 
 It lives under tests/ because it uses the oracle (test infrastructure).  Run on the GPU box:
     python tests/fuzz_parity.py --cases 200 --seed 0
-    python tests/fuzz_parity.py --variants --cases 30        (likewise --alleles, --best, --sweep, --once, --plot, --genome, --annot; each prints its tallies)
+    python tests/fuzz_parity.py --variants --cases 30        (likewise --alleles, --best, --sweep, --sweep-counts, --once, --plot, --genome, --annot; each prints its tallies)
 `tests/test_gpu_parity.py::test_fuzz_decision_boundary` runs a few cases of ms_scan's family in the GPU suite,
 tests/test_gpu_fuzz_entry_points.py the next four and the plot, genome and annot families, tests/test_gpu_scan_once.py the scan-once family; tests/test_fuzz_cases_host.py checks the cases
 themselves without a GPU.
@@ -204,8 +205,7 @@ def check_round6_paths(seed, _lib, raw, offsets, strand, want, pw, sq):
     or from the ordered path where the flag map does not apply) and the batch stream with the 12-byte copy-out (two batches cut at a random
     region; packing on the scan stage; the second batch counts-only every other seed)."""
     n_motifs = len(want["motif_offsets"]) - 1
-    pair = np.unique((np.repeat(np.arange(n_motifs), np.diff(want["motif_offsets"])).astype(np.int64) << 32) | want["seq_idx"])
-    want_regions = np.bincount(pair >> 32, minlength=n_motifs)
+    want_regions = expected_counts(want, n_motifs)[2]
     co = _lib.scan(pw, sq, strand, _lib.MS_SCAN_COUNTS_ONLY)
     try:
         if co.n_hits != len(want["pos"]) or not np.array_equal(co.motif_offsets, want["motif_offsets"]) or not np.array_equal(co.region_counts(), want_regions):
@@ -333,16 +333,68 @@ def run_sweep_case(seed, oracle, _lib):
             return False, f"sweep seed {seed}: {k} differs ({len(got['pos'])} vs {len(want['pos'])} sites)"
     if not np.array_equal(got["strand"].astype(np.int32), want["strand"].astype(np.int32)):
         return False, f"sweep seed {seed}: strand differs"
-    pair = np.unique((np.repeat(np.arange(n_motifs), np.diff(want["motif_offsets"])).astype(np.int64) << 32) | want["seq_idx"])
-    if not np.array_equal(counts, np.bincount(pair >> 32, minlength=n_motifs)):
+    if not np.array_equal(counts, expected_counts(want, n_motifs)[2]):
         return False, f"sweep seed {seed}: window counts differ"
     return True, len(want["pos"])
+
+
+def span_counts(_lib, pw, span, window, stride, strand, flags):
+    """(n_hits, motif_offsets, region_counts, hits() refused as a counts-only result) of one span through a stream of these flags."""
+    st = _lib.Stream(pw, strand, flags, depth=1)
+    try:
+        st.submit_span(np.frombuffer(span.encode(), dtype=np.uint8), window, stride)
+        res = st.next()
+        try:
+            refused = False
+            try:
+                res.hits()
+            except ValueError as e:
+                refused = "counts-only" in str(e)
+            return res.n_hits, res.motif_offsets.copy(), res.region_counts(), refused
+        finally:
+            res.close()
+    finally:
+        st.close()
+
+
+def run_sweep_counts_case(seed, oracle, _lib, case=None):
+    """The counts-only hand-out of a sweep span (sweep_countonly_kernel, behind MS_STREAM_NO_HITS) on the sweep family's cases: the span
+    chrom[begin:end] through a stream, its n_hits, per-motif site numbers and per-motif window counts against the oracle over the windows
+    as separate regions; all zero where the span holds no window; no site arrays; and the same numbers under MS_STREAM_DEDUP, which
+    leaves a counts-only span as it is.  case: a dict like make_sweep_case's in place of the seed's own."""
+    case = case or make_sweep_case(seed)
+    n_motifs = len(case["mats"])
+    vals, widths, want = expected_sweep(oracle, case)
+    n_hits, offsets, counts = expected_counts(want, n_motifs)
+    span = case["chrom"][case["begin"]:case["end"]]
+    pw = _lib.PwmSet(vals, widths, case["cutoffs"])
+    try:
+        for flags in (_lib.MS_STREAM_NO_HITS, _lib.MS_STREAM_NO_HITS | _lib.MS_STREAM_DEDUP):
+            got = span_counts(_lib, pw, span, case["window"], case["stride"], case["strand"], flags)
+            what = f"sweep-counts seed {seed} (stream flags {flags})"
+            if got[0] != n_hits or not np.array_equal(got[1], offsets):
+                return False, f"{what}: site numbers differ ({got[0]} vs {n_hits} sites)"
+            if not np.array_equal(got[2], counts):
+                return False, f"{what}: window counts differ"
+            if case["n_win"] == 0 and (got[0] or got[1].any() or got[2].any()):
+                return False, f"{what}: counts of a span without a window"
+            if not got[3]:
+                return False, f"{what}: hits() did not refuse a counts-only span"
+    finally:
+        pw.close()
+    return True, n_hits
 
 
 # ------------------------------------------------------------------------------------------------ variants, alleles, best sites
 #
 # Each family: make_<x>_case(seed) builds the inputs, expected_<x>(oracle, case) the expected arrays and a tally dict (neither uses a
 # GPU), run_<x>_case(seed, oracle, _lib) makes the device call.  Every comparison is exact: integers by value, scores by their bits.
+
+def expected_counts(want, P):
+    """counts_cases.expected_counts (imported late: that module reads this one's constants)."""
+    from counts_cases import expected_counts as f
+    return f(want, P)
+
 
 ALL_PASS = -1e30
 NEAR = 2e-10                                            # a scored window is "near" when its score is within this of the motif's cutoff
@@ -2223,6 +2275,7 @@ def main():
     ap.add_argument("--cases", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--sweep", action="store_true", help="fuzz ms_scan_sweep instead of ms_scan")
+    ap.add_argument("--sweep-counts", action="store_true", help="fuzz the counts-only hand-out of a sweep span (MS_STREAM_NO_HITS) instead of ms_scan")
     ap.add_argument("--variants", action="store_true", help="fuzz ms_scan_variants instead of ms_scan")
     ap.add_argument("--alleles", action="store_true", help="fuzz ms_scan_alleles instead of ms_scan")
     ap.add_argument("--best", action="store_true", help="fuzz ms_scan_best instead of ms_scan")
@@ -2235,17 +2288,17 @@ def main():
     oracle.build()
     from motifscan_amd import _lib
     _lib.set_device(0)
-    if a.sweep:
+    if a.sweep or a.sweep_counts:
         bad, total, tally = 0, 0, {}
         for k in range(a.cases):
-            ok, info = run_sweep_case(a.seed + k, oracle, _lib)
+            ok, info = (run_sweep_counts_case if a.sweep_counts else run_sweep_case)(a.seed + k, oracle, _lib)
             if not ok:
                 bad += 1
                 print("MISMATCH", info, flush=True)
             else:
                 total += info
             add_tally(tally, sweep_tally(a.seed + k, oracle))
-        print(f"sweep fuzz: {a.cases} cases from seed {a.seed}: {bad} mismatches, {total} sites compared; tallies {tally}")
+        print(f"{'sweep-counts' if a.sweep_counts else 'sweep'} fuzz: {a.cases} cases from seed {a.seed}: {bad} mismatches, {total} sites compared; tallies {tally}")
         return 1 if bad else 0
     for name, run in FAMILIES.items():
         if getattr(a, name):

@@ -11,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+from counts_cases import expected_counts
 from motifscan_amd import _lib, cscore, dist, formats, scanner, synth
 
 pytestmark = pytest.mark.gpu
@@ -455,8 +456,7 @@ def test_counts_only_scan_equals_the_ordered_scan(oracle, shape):
     sq = _lib.SeqSet(bases, offsets)
     full = _lib.scan(pw, sq, strand)
     want = oracle.scan_arrays(vals, widths, cutoffs, bases.tobytes(), offsets, strand, 8)
-    pair = np.unique((np.repeat(np.arange(len(widths)), np.diff(want["motif_offsets"])).astype(np.int64) << 32) | want["seq_idx"])
-    want_regions = np.bincount(pair >> 32, minlength=len(widths))
+    want_regions = expected_counts(want, len(widths))[2]
     for rep in range(2):                                     # (the second scan takes the predicted-size, one-sync form)
         res = _lib.scan(pw, sq, strand, _lib.MS_SCAN_COUNTS_ONLY)
         assert res.n_hits == full.n_hits == len(want["pos"])
@@ -545,8 +545,7 @@ def test_stream_packs_on_the_scan_stage_and_the_old_form_agrees(oracle, monkeypa
     for mode, (merged, counts) in outs.items():
         for k in ("seq_idx", "pos", "score"):
             assert np.array_equal(merged[k], want[k][sel]), (mode, k)
-        pair = np.unique((np.repeat(np.arange(len(widths)), np.diff(want["motif_offsets"])).astype(np.int64) << 32) | want["seq_idx"])
-        assert np.array_equal(counts, np.bincount(pair >> 32, minlength=len(widths)))
+        assert np.array_equal(counts, expected_counts(want, len(widths))[2])
     # a sweep span through the stream (kind 1) takes the same upload-only path
     g, _ = synth.make_regions(1, 50000, seed=3, frac_n=0.02)
     spans = list(_lib.sweep_stream(pw, [g], 200, 50, 20000, 3))

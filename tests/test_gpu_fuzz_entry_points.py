@@ -1,6 +1,7 @@
 """
 The boundary fuzz of tests/fuzz_parity.py on the four entry points beside ms_scan that judge windows -- ms_scan_variants (ms_variants.hip),
-ms_scan_alleles (ms_alleles.hip), ms_scan_best (ms_best.hip) and ms_scan_sweep (ms_sweep.hip) -- against the pinned oracle: tie-rich
+ms_scan_alleles (ms_alleles.hip), ms_scan_best (ms_best.hip) and ms_scan_sweep (ms_sweep.hip; the full hand-out, and the counts-only one
+of a MS_STREAM_NO_HITS span) -- against the pinned oracle: tie-rich
 matrices, cutoffs on attainable scores and one ulp / 1e-10 either side, huge and tiny magnitudes, max_raw == 0, N runs and lower case.
 The plot family (ms_result_site_histogram, ms_result_rank_profile; ms_plotdata.hip) runs beside them over synthetic hit arrays: centres
 on and around the bin edges, region counts on the rank words' and profile tiles' edges, against numpy alone.  The genome family holds the
@@ -45,4 +46,18 @@ def test_fuzz_sweep(oracle):
         assert tally["sites"] == info
         fuzz_parity.add_tally(total, tally)
     print(f"sweep: seeds {fuzz_parity.SEEDS['sweep']}: {total}")
+    assert not fuzz_parity.unmet_conditions("sweep", total)
+
+
+def test_fuzz_sweep_counts(oracle):
+    """The same seeds as spans of a MS_STREAM_NO_HITS stream: the counts-only hand-out (sweep_countonly_kernel), with and without
+    MS_STREAM_DEDUP; the sweep family's tallies and conditions."""
+    total = {}
+    for seed in fuzz_parity.SEEDS["sweep"]:
+        ok, info = fuzz_parity.run_sweep_counts_case(seed, oracle, _lib)
+        assert ok, info
+        tally = fuzz_parity.sweep_tally(seed, oracle)
+        assert tally["sites"] == info
+        fuzz_parity.add_tally(total, tally)
+    print(f"sweep-counts: seeds {fuzz_parity.SEEDS['sweep']}: {total}")
     assert not fuzz_parity.unmet_conditions("sweep", total)
