@@ -91,6 +91,10 @@
  *   ms_result_site_base_counts   no reference counterpart: how often A, C, G and T stand under each motif column (and the flanks) over a
  *                         result's sites, in the motif's orientation, with the adjacent-column dinucleotide counts -- the observed
  *                         count matrix of the sites found, reduced on the device from the hit arrays and the packed sequence
+ *   ms_track_* / ms_result_site_signal
+ *                         no reference counterpart: a per-base int32 track (cut counts, coverage, conservation in fixed point) resident
+ *                         beside a sequence set, and its sums under each motif column and flank over a result's sites, per strand and
+ *                         in the motif's orientation -- the footprint profile -- with per-site upstream / core / downstream sums
  *   ms_best_rank_sum      no reference counterpart: the rank-sum (Mann-Whitney / AUROC) comparison of two groups of regions by their best
  *                         score per motif, without a cutoff -- the exact integers 2U and the tie sum, from the matrices ms_scan_best left
  *                         on the device
@@ -815,6 +819,52 @@ int ms_result_pair_spacing(const ms_result *res, const ms_pwmset *pwms, int32_t 
 int ms_result_site_base_counts(const ms_result *res, const ms_pwmset *pwms, const ms_seqset *seqs, int32_t flank, int32_t m0, int32_t m1,
                                uint32_t flags /* 0 */, int64_t *counts /* [(m1 - m0)][C][6] */, int64_t *dinuc /* [(m1 - m0)][C][16], or NULL */,
                                int64_t *n_sites /* [m1 - m0], or NULL */, double *device_ms /* or NULL */);
+
+/* ---- signal tracks over sites: footprint profiles and per-site sums (ms_sitesignal.hip) ------------------------- */
+typedef struct ms_track ms_track;
+/* A resident track: one int32 per base of a sequence set, laid out by the same offsets (offsets[n_seqs] values).  Any int32 is a value;
+ * there is no "missing" sentinel.  values: host memory or device memory of the calling thread's device; offsets: host memory, starts at
+ * 0 and does not decrease.  The block comes from the device pool, like a sequence set's, and carries a few zeroed values at either end so
+ * that the 16-byte loads of ms_result_site_signal form no address outside it.  Synchronous.  MS_ERR_RUNTIME without a usable device,
+ * before anything else.  MS_ERR_INVALID: NULL pointers, n_seqs < 0, offsets that do not start at 0 or decrease, values on another device. */
+int  ms_track_create(const int32_t *values, const int64_t *offsets, int64_t n_seqs, ms_track **out);
+int  ms_track_size(const ms_track *t, int64_t *n_seqs, int64_t *n_values);
+/* values [first, first + n) of the track, read back to host memory (tests). */
+int  ms_track_values_host(const ms_track *t, int64_t first, int64_t n, int32_t *out);
+void ms_track_free(ms_track *t);
+
+#define MS_SITESIGNAL_MAX_FLANK 512
+/* For motifs m0 <= m < m1 (row = m - m0) of a result and a track over the sequence set it was made of: the track summed over the motif's
+ * sites, column by column, in the MOTIF's orientation.  C = pwms->max_width + 2 * flank is the column pitch of every row.  The strand index
+ * s is 0 for '+' (result strand 1) and 1 for '-' (result strand 2).  A site (region r of length L, pos, strand) of a motif of width W uses
+ * columns j = 0 .. W + 2 * flank - 1 (column flank + c is motif column c); the columns behind them stay zero.  Column j reads track
+ * position q = pos - flank + j on '+' and q = pos + W - 1 + flank - j on '-': the values are not complemented, only their order is
+ * reversed -- exactly the site stack's column rule (ms_result_site_base_counts).  A column is INSIDE iff 0 <= q < L of its own region,
+ * decided by the region's bounds alone.
+ *   sum[row][s][j]      the sum of value[offsets[r] + q] over the motif's sites of strand s whose column j is inside
+ *   cover[row][s][j]    the number of those sites (may be NULL)
+ *   n_sites[row][s]     the motif's sites of strand s (may be NULL); every column has cover <= n_sites.  The strands are kept apart so
+ *                       that a caller with strand-specific tracks (Tn5 '+' cuts and '-' cuts) can swap tracks for the '-' sites
+ *                       afterwards; the folded profile is sum[row][0] + sum[row][1]
+ *   per_site[k - motif_offsets[m0]][0 .. 2]   for hit k of the selected slice (n_sel = motif_offsets[m1] - motif_offsets[m0] rows, in the
+ *                       result's hit order), over its inside columns only: the upstream sum, columns [0, flank); the core sum, columns
+ *                       [flank, flank + W); the downstream sum, columns [flank + W, W + 2 * flank) -- upstream and downstream in the
+ *                       motif's orientation.  How many of a site's columns are inside is a closed form of (pos, W, L, flank) and is
+ *                       left to the caller.
+ * At least one of sum and per_site must be non-NULL.  The sites are read as they are (de-duplicated or not).  Synchronous; exact int64
+ * sums -- |value| < 2^31 and fewer than 2^32 sites cannot overflow -- the same bytes on every run, additive over shards of the regions.
+ * An empty motif range (m0 == m1) does nothing and returns MS_OK.  Every output is host memory or device memory of the result's device
+ * (then a consumer can all-reduce it where it is).  The library writes a device output on its own stream: work the caller has queued on
+ * that memory on another stream (a fill, a collective) must have finished before the call; the call returns after its own writes are
+ * done.  *device_ms (may be NULL): first launch -> last kernel done.
+ * MS_ERR_RUNTIME without a usable device, before anything else.  MS_ERR_INVALID: NULL handles, sum and per_site both NULL, flags != 0,
+ * flank outside [0, MS_SITESIGNAL_MAX_FLANK], a motif range outside [0, P], pwms->P != the result's P, the track's R != the result's R, a
+ * track or an output on another device, a counts-only result, and a site with a region index outside [0, R), pos < 0 or pos + W > L (a
+ * result of ms_result_from_hits, or the wrong track: checked on the device while reducing, outputs zeroed). */
+int ms_result_site_signal(const ms_result *res, const ms_pwmset *pwms, const ms_track *track, int32_t flank, int32_t m0, int32_t m1,
+                          uint32_t flags /* 0 */, int64_t *sum /* [(m1 - m0)][2][C], or NULL */, int64_t *cover /* [(m1 - m0)][2][C], or NULL */,
+                          int64_t *n_sites /* [(m1 - m0)][2], or NULL */, int64_t *per_site /* [n_sel][3], or NULL */,
+                          double *device_ms /* or NULL */);
 
 /* ---- the score distribution of every window (ms_scorehist.hip) ------------------------------------------------ */
 #define MS_SCOREHIST_MAX_BINS   4096

@@ -168,6 +168,13 @@ int ms_debug_liftmap_stage_ms(const ms_liftmap *m, double out[4]);
  * when dinuc is not asked for (equal to out[2]: one limit).  Tests size their boundary cases from here.  Needs no GPU. */
 int ms_debug_sitestack_dims(int32_t out[4]);
 
+/* The path constants of ms_result_site_signal, as constants of the build: out[0] the threads of a block; out[1] the sites of one block
+ * chunk (a wave takes them 64 at a time; a motif of more sites takes several chunks); out[2] the columns of one panel -- a block holds
+ * the sums of one panel in registers, 4 columns per lane, and a row of more columns (W + 2 * flank) takes several panels in the grid's z,
+ * whose per-site sums are then added with 64-bit atomics instead of stored: the largest row of the one-panel form; out[3] the most blocks
+ * in x, beyond which a block takes several chunks.  Tests size their boundary cases from here.  Needs no GPU. */
+int ms_debug_sitesignal_dims(int32_t out[4]);
+
 /* The path constants of ms_best_rank_sum and ms_best_count_passing, as constants of the build: out[0] the threads of a block; out[1] the
  * cells per block of the gather kernel; out[2] the sorted elements per block of the rank kernel (a group of more takes several blocks, each
  * with its own partial slot); out[3] the cells per block of the count kernel; out[4] the default element budget of a batch of motif rows;

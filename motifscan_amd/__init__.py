@@ -12,6 +12,8 @@ motifscan_amd -- MI355X-native drop-in for ONE hot path of shao-lab/MotifScan: t
     motifscan_amd.synth     seeded synthetic workloads (bench.py, tests)
     motifscan_amd.shuffle   the sequential restatement of ms_seqset_shuffle (mono- and dinucleotide shuffled controls), numpy only
     motifscan_amd.kmers     k-mer codes, the restatement of ms_seqset_kmer_counts, Markov backgrounds, k-mer enrichment, seed matrices
+    motifscan_amd.footprint signal tracks over sites: host Track constructors, footprint profiles and per-site flank / core sums
+                            (ms_result_site_signal), and their sequential restatement
 
 There is no CPU fallback anywhere in this package.
 """

@@ -161,6 +161,12 @@ def lib():
         "ms_result_pair_spacing": (c_int, [vp, vp, c_i32, c_i32, c_i32, c_i32, pi64, pi64]),
         "ms_result_site_base_counts": (c_int, [vp, vp, vp, c_i32, c_i32, c_i32, c_u32, vp, vp, vp, pd]),
         "ms_debug_sitestack_dims": (c_int, [pi32]),
+        "ms_track_create": (c_int, [vp, pi64, c_i64, pvp]),
+        "ms_track_size": (c_int, [vp, pi64, pi64]),
+        "ms_track_values_host": (c_int, [vp, c_i64, c_i64, pi32]),
+        "ms_track_free": (None, [vp]),
+        "ms_result_site_signal": (c_int, [vp, vp, vp, c_i32, c_i32, c_i32, c_u32, vp, vp, vp, vp, pd]),
+        "ms_debug_sitesignal_dims": (c_int, [pi32]),
         "ms_debug_pair_lds_bins": (c_int, []),
         "ms_debug_cooc_chunk_regions": (c_int, []),
         "ms_debug_plot_dims": (c_int, [pi32]),
@@ -598,6 +604,51 @@ def shuffle_stage_ms():
     out = np.zeros(4, dtype=np.float64)
     check(lib().ms_debug_shuffle_stage_ms(ptr(out, ctypes.c_double)))
     return out
+
+
+class Track:
+    """A resident signal track (ms_track): one int32 per base of a sequence set, laid out by the same offsets -- what
+    ScanResult.site_signal sums over the sites of a scan."""
+
+    def __init__(self, values, offsets):
+        """values: an int32 numpy array of offsets[-1] entries, or the device pointer of one (an int, e.g. a torch int32 tensor's
+        data_ptr() on the current device); offsets: n_seqs + 1 entries on the host."""
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if self.offsets.ndim != 1 or self.offsets.size < 1:
+            raise ValueError("offsets must have n_seqs + 1 entries")
+        if isinstance(values, int):
+            src = values
+        else:
+            values = np.ascontiguousarray(values)
+            if values.dtype != np.int32 or values.ndim != 1:
+                raise ValueError("values must be a flat int32 array (footprint.Track.from_float turns floats into fixed point)")
+            if values.size != int(self.offsets[-1]):
+                raise ValueError("offsets[-1] must equal the number of values")
+            src = values.ctypes.data
+        h = ctypes.c_void_p()
+        check(lib().ms_track_create(ctypes.c_void_p(src), ptr(self.offsets, ctypes.c_int64), self.offsets.size - 1, ctypes.byref(h)))
+        self.h = h
+        n_seqs, n_values = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(lib().ms_track_size(self.h, ctypes.byref(n_seqs), ctypes.byref(n_values)))
+        self.n_seqs, self.n_values = n_seqs.value, n_values.value
+
+    @classmethod
+    def from_values(cls, values, offsets):
+        return cls(values, offsets)
+
+    def values(self, first=0, n=None):
+        """The values [first, first + n) read back from the device (ms_track_values_host)."""
+        n = self.n_values - int(first) if n is None else int(n)
+        out = np.zeros(max(n, 0), dtype=np.int32)
+        check(lib().ms_track_values_host(self.h, int(first), n, ptr(out, ctypes.c_int32)))
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ms_track_free(self.h)
+            self.h = None
+
+    __del__ = close
 
 
 class ResidentGenome:
@@ -1090,6 +1141,47 @@ class ScanResult:
         ms = ctypes.c_double(0.0)
         check(lib().ms_result_site_base_counts(self.h, pwmset.h, seqset.h, flank, m0, m1, int(flags), dst[0], dst[1], dst[2], ctypes.byref(ms)))
         self.site_base_counts_ms = ms.value
+        return tuple(arrs)
+
+    def site_signal(self, pwmset, track, flank=0, m0=0, m1=None, profile=True, per_site=False, out=None, flags=0):
+        """ms_result_site_signal: (sum int64 [m1 - m0][2][C], cover int64 [m1 - m0][2][C], n_sites int64 [m1 - m0][2], per_site int64
+        [n_sel][3]) of the sites of motifs m0 .. m1 - 1 over a Track laid out as the sequence set the result was made of, C = the set's
+        widest motif + 2 * flank: per strand ('+' 0, '-' 1) and column of the motif (column flank + c is motif column c, in the motif's
+        orientation) the track summed over the sites whose column lies inside the region, and the number of those sites; per selected
+        hit, in hit order, the sums over its upstream flank, core and downstream flank.  profile=False leaves sum and cover out (None),
+        per_site=False the last.  out: None, or (sum, cover, n_sites, per_site), each an int64 numpy array of that shape, None (a new
+        one) or the device pointer of a torch tensor as an int (then it is returned).  The call's device_ms is left in
+        self.site_signal_ms.  The library checks every argument."""
+        m1 = self.n_pwms if m1 is None else int(m1)
+        m0, flank = int(m0), int(flank)
+        rows = max(m1 - m0, 0)
+        fits = 0 <= flank <= 512                                 # what the library refuses is refused before it writes
+        C = (int(pwmset.widths.max()) if pwmset.n else 0) + 2 * flank if fits else 1
+        in_range = 0 <= m0 <= m1 <= self.n_pwms
+        n_sel = int(self.motif_offsets[m1] - self.motif_offsets[m0]) if in_range and per_site else 0
+        shapes = ((rows, 2, C), (rows, 2, C), (rows, 2), (n_sel, 3))
+        given = (None, None, None, None) if out is None else tuple(out)
+        if len(given) != 4:
+            raise ValueError("out must be (sum, cover, n_sites, per_site)")
+        arrs, dst = [], []
+        for a, shape, want in zip(given, shapes, (bool(profile), bool(profile), True, bool(per_site))):
+            if not want:
+                if a is not None:
+                    raise ValueError("an output array was given for a part that was not asked for")
+                p = None
+            elif isinstance(a, int):
+                p = a
+            else:
+                if a is None:
+                    a = np.zeros(shape, dtype=np.int64)
+                if a.dtype != np.int64 or a.shape != shape or not a.flags.c_contiguous:
+                    raise ValueError("out arrays must be C-contiguous int64 of shapes (m1 - m0, 2, C), (m1 - m0, 2, C), (m1 - m0, 2) and (n_sel, 3)")
+                p = a.ctypes.data
+            arrs.append(a)
+            dst.append(ctypes.c_void_p(p))
+        ms = ctypes.c_double(0.0)
+        check(lib().ms_result_site_signal(self.h, pwmset.h, track.h, flank, m0, m1, int(flags), dst[0], dst[1], dst[2], dst[3], ctypes.byref(ms)))
+        self.site_signal_ms = ms.value
         return tuple(arrs)
 
     def close(self):
@@ -1673,6 +1765,14 @@ def sitestack_dims():
     out = np.zeros(4, dtype=np.int32)
     check(lib().ms_debug_sitestack_dims(ptr(out, ctypes.c_int32)))
     return dict(zip(("threads", "chunk_hits", "lds_columns", "lds_columns_no_dinuc"), out.tolist()))
+
+
+def sitesignal_dims():
+    """ms_debug_sitesignal_dims: the path constants of ms_result_site_signal -- dict(threads, chunk_sites, panel_columns, max_blocks_x).
+    Constants of the build; no device."""
+    out = np.zeros(4, dtype=np.int32)
+    check(lib().ms_debug_sitesignal_dims(ptr(out, ctypes.c_int32)))
+    return dict(zip(("threads", "chunk_sites", "panel_columns", "max_blocks_x"), out.tolist()))
 
 
 def cooc_chunk_regions():

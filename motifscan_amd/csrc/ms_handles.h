@@ -5,7 +5,7 @@
 // ms_personal.hip (a variant set spliced into a new resident genome, and the lift map between the two), ms_sitestack.hip (base counts per
 // motif column over a result's sites), ms_ranksum.hip (rank sums and passing-region counts over best-site matrices), ms_affinity.hip (the
 // summed likelihood ratio of every cell), ms_shuffle.hip (a sequence set shuffled into a new one: mono- and dinucleotide controls),
-// ms_kmers.hip (the k-mer counts of a sequence set or a genome),
+// ms_kmers.hip (the k-mer counts of a sequence set or a genome), ms_sitesignal.hip (a resident per-base track and its sums over a result's sites),
 // ms_variants.hip and ms_alleles.hip (the record scans over variants: one placement driver, place_records, and one handle head, RecHead).
 #pragma once
 #include <sched.h>
@@ -296,7 +296,22 @@ struct ms_affinity {                                  // ms_scan_affinity: the s
     double device_ms = 0.0;                           // first launch -> last kernel done
 };
 
+struct ms_track {                                     // ms_track_create: one int32 per base of a sequence set
+    int device = 0;
+    int64_t R = 0;
+    int64_t n_values = 0;
+    std::vector<int64_t> offsets;                     // host copy [R+1]
+    void *block = nullptr;                            // one pooled device block: [pad][values][pad] | offsets
+    size_t block_bytes = 0;
+    int32_t *d_values = nullptr;                      // the first value, kTrackPad zeroed values behind the block's start (ms_sitesignal.hip)
+    int64_t *d_offsets = nullptr;                     // [R+1]
+};
+
 namespace ms {
+
+// 1: device memory of `device`; 0: host memory; -1: device memory of another device (*other) -- where an output or an input array of the
+// caller's lies (ms_sitestack.hip)
+MS_HIDDEN int pointer_place(const void *p, int device, int *other);
 
 // What the handles of the two record scans begin with (ms_varscan, ms_allelescan): the placement's output (place_records) and the one
 // implementation of the accessors that only read it.

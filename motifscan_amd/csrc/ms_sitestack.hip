@@ -154,8 +154,9 @@ __global__ __launch_bounds__(kStackThreads) void sitestack_kernel(StackArgs A) {
             if (h[n_cnt + i]) atomicAdd(&out_d[i], (unsigned long long) h[n_cnt + i]);
 }
 
+}  // namespace
 
-// 1: device memory of `device`; 0: host memory; -1: device memory of another device (*other)
+// 1: device memory of `device`; 0: host memory; -1: device memory of another device (*other).  Shared with ms_sitesignal.hip (ms_handles.h).
 int pointer_place(const void *p, int device, int *other) {
     hipPointerAttribute_t attr;
     std::memset(&attr, 0, sizeof(attr));
@@ -166,7 +167,6 @@ int pointer_place(const void *p, int device, int *other) {
     return attr.device == device ? 1 : -1;
 }
 
-}  // namespace
 }  // namespace ms
 
 using namespace ms;

@@ -5,6 +5,7 @@ motifscan_amd.formats -- the on-disk formats either side of the scan path (SURVE
        read_bg_freq(path) / write_bg_freq(path, bg)   background frequencies   genome/__init__.py:223-269
        read_motifscan_pwms(path)              built PWMs + cutoffs       motif/__init__.py:219-319
        write_motifscan_pwms(path, pwms)                                  motif/__init__.py:200-217
+       read_bedgraph(path)                    bedGraph text (a signal track) as four arrays; no reference counterpart
   out  write_sites_table(dir, pwms, regions, ...)   motif_sites_number.xls / motif_sites_score.xls  io/__init__.py:12-38
        write_sites_bed(dir, pwms, regions, ...)     motif_sites/<motif>_sites.bed                   io/__init__.py:41-54
        write_enrich_table(dir, results)             motif_enrichment.xls                            io/__init__.py:57-71
@@ -177,6 +178,30 @@ def read_bg_freq(path):
 
 
 # ------------------------------------------------------------------------ result writers --
+
+def read_bedgraph(path):
+    """(chrom str array, start int64, end int64, value float64) of a bedGraph file: four whitespace-separated columns per row, half-open
+    0-based intervals; blank lines, '#' comments and 'track' / 'browser' lines are skipped.  Anything else raises a ValueError with the
+    1-based line number.  footprint.Track.from_intervals paints the rows onto regions (integer values; scale floats first)."""
+    chrom, start, end, value = [], [], [], []
+    for num, line in _numbered_lines(path):
+        if line is None or line.startswith(("#", "track", "browser")):
+            continue
+        f = line.split()
+        try:
+            if len(f) != 4:
+                raise ValueError
+            s, e, v = int(f[1]), int(f[2]), float(f[3])
+            if s < 0 or e < s:
+                raise ValueError
+        except ValueError:
+            raise ValueError(f"Invalid bedGraph format at line {num}: {line!r}") from None
+        chrom.append(f[0])
+        start.append(s)
+        end.append(e)
+        value.append(v)
+    return np.array(chrom, dtype=str), np.array(start, dtype=np.int64), np.array(end, dtype=np.int64), np.array(value, dtype=np.float64)
+
 
 def _motif_label(pwm):
     return pwm.matrix_id + "," + pwm.name

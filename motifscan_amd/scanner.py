@@ -21,6 +21,7 @@ and the questions the reference cannot answer from its site lists:
     Scanner.affinity_rank_sum(pwms, control) -> enrich.RankSum: rank_sum with that sum in place of the best score.
     Scanner.score_histogram(pwms, ...) -> scoredist.ScoreHistogram: the score distribution of all windows, per motif.
     Scanner.site_base_counts(pwms, ...) -> sitestack.SiteStack: the base counts per motif column over the sites found.
+    Scanner.site_signal(pwms, track, ...) -> footprint.SiteSignal: a per-base track summed per motif column over the sites found.
 
 `genome` is any object with `chrom_sizes[chrom]` and `fetch_sequence(chrom, start, end)`;
 `regions` any objects with `.chrom .start .end .summit` -- i.e. the reference's own
@@ -495,6 +496,33 @@ class Scanner:
         finally:
             pw.close()
         return sitestack.SiteStack(counts, di, n_sites, np.asarray(lengths, dtype=np.int64), int(flank))
+
+    def site_signal(self, pwms, track, flank=0, per_site=False):
+        """A per-base signal track read over the sites of a scan, as a footprint.SiteSignal: per motif, strand and column of the motif,
+        with `flank` columns either side and in the motif's orientation, the track summed over the sites whose column lies inside the
+        region and the number of those sites (ms_result_site_signal); per_site adds every site's upstream, core and downstream sum.
+        track: a footprint.Track (uploaded for the call) or a _lib.Track over the scanner's regions, in their order and of their lengths.
+        One scan of the scanner's own sequence set with its `strand` and `p_value`, de-duplicated if `remove_dup`, read where it lies:
+        no hit leaves the device."""
+        from . import footprint
+        matrices, cutoffs, lengths = self._marshal(pwms)
+        pw = _lib.PwmSet.from_matrices(matrices, cutoffs)
+        tr, tr_owned = None, False
+        try:
+            tr, tr_owned = footprint._track(track)
+            res = _lib.scan(pw, self._seqset(), _STRAND_FLAG[self.strand])
+            try:
+                if self.remove_dup:
+                    res.dedup(pw)
+                total, cover, n_sites, ps = res.site_signal(pw, tr, int(flank), per_site=per_site)
+                site_offsets = np.asarray(res.motif_offsets, dtype=np.int64).copy()
+            finally:
+                res.close()
+        finally:
+            if tr_owned:
+                tr.close()
+            pw.close()
+        return footprint.SiteSignal(total, cover, n_sites, ps, site_offsets, np.asarray(lengths, dtype=np.int64), int(flank))
 
     def kmer_counts(self, k, canonical=True, sel=None):
         """The k-mer spectrum of the scanner's regions as a kmers.KmerCounts (ms_seqset_kmer_counts on the scanner's own device set, so a
