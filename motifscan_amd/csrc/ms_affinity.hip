@@ -212,16 +212,6 @@ __global__ void __launch_bounds__(256) affinity_fill_kernel(const AffArgs A, con
     put_cell(A, (int64_t) motifs[blockIdx.y] * A.R + r, 0.0, 0.0, 0);
 }
 
-
-// a motif with a NaN or +inf entry has an empty row; every other one is scored, max_raw <= 0 included
-bool affinity_scored(const ms_pwmset *p, int32_t m) {
-    const double *v = p->values.data() + p->val_off[(size_t) m];
-    const int64_t n = 4 * (int64_t) p->widths[(size_t) m];
-    for (int64_t i = 0; i < n; i++)
-        if (std::isnan(v[i]) || v[i] == std::numeric_limits<double>::infinity()) return false;
-    return true;
-}
-
 }  // namespace
 
 }  // namespace ms
@@ -244,12 +234,7 @@ int ms_debug_affinity_dims(int32_t out[8]) {
 }
 
 void ms_affinity_free(ms_affinity *a) {
-    if (!a) return;
-    if (a->block) {
-        (void) hipSetDevice(a->device);
-        DeviceCtx *c = nullptr;
-        if (get_ctx(a->device, &c) == MS_OK) pool_free(c, a->block, a->block_bytes); else (void) hipFree(a->block);
-    }
+    dense_release(a);
     delete a;
 }
 
@@ -265,29 +250,20 @@ int ms_scan_affinity(const ms_pwmset *pwms_c, const ms_seqset *seqs, int strand_
     ms_pwmset *pwms = const_cast<ms_pwmset *>(pwms_c);
     const int32_t P = pwms->P;
     const int64_t R = seqs->R;
-    const int64_t *off = seqs->offsets.data();
-    for (int64_t r = 0; r < R; r++)
-        if (off[r + 1] - off[r] >= (1LL << 31)) {
-            set_error("region %lld has %lld bases: n_terms is 32-bit, cut it into regions of fewer than 2^31", (long long) r, (long long) (off[r + 1] - off[r]));
-            return MS_ERR_INVALID;
-        }
-    DeviceCtx *c;
-    int rc = get_ctx(seqs->device, &c);
+    int rc = dense_regions_fit(seqs, "n_terms is");
     if (rc) return rc;
+    DeviceCtx *c;
+    if ((rc = get_ctx(seqs->device, &c))) return rc;
     std::unique_ptr<ms_affinity> res(new (std::nothrow) ms_affinity());
     if (!res) { set_error("out of host memory"); return MS_ERR_NOMEM; }
     res->device = c->device;
     res->P = P;
     res->R = R;
 
-    // ---- the plan, on the host: segments of the regions, tiles of the motifs (dense_plan, ms_best_dev.h)
+    // ---- the plan, on the host: segments of the regions, tiles of the motifs (ms_dense_plan.h); a motif whose max_raw is <= 0 is walked
     DensePlan plan;
-    try {
-        dense_plan(pwms, off, R, [&](int32_t m) { return affinity_scored(pwms, m); }, &plan);
-    } catch (const std::bad_alloc &) { set_error("out of host memory"); return MS_ERR_NOMEM; }
-    const int32_t n_lds_tiles = (int32_t) plan.tile_first.size() - 1, n_wide = (int32_t) plan.wide_first.size() - 1, n_mot = (int32_t) plan.mot.size();
-    const int64_t n_long = (int64_t) plan.long_regions.size(), n_seg = plan.n_seg, n_part = plan.n_part;
-    if (n_long > 0x7FFFFFFFLL || (n_seg + kBestWaves - 1) / kBestWaves > 0x7FFFFFFFLL) { set_error("too many segments for one launch"); return MS_ERR_INVALID; }
+    if ((rc = dense_plan_for(kBestGeom, pwms, seqs, kBestWaves, [&](int32_t m) { return entries_scorable(pwms, m); }, &plan))) return rc;
+    const int64_t n_seg = plan.n_seg, n_part = plan.n_part, n_mot = (int64_t) plan.mot.size();
 
     // ---- 28 bytes per cell, 24 per partial: both blocks are allocated before anything is launched, and a failure there is the MS_ERR_NOMEM
     // of the header (the test here only keeps the byte counts below inside size_t)
@@ -299,122 +275,78 @@ int ms_scan_affinity(const ms_pwmset *pwms_c, const ms_seqset *seqs, int strand_
     std::lock_guard<std::mutex> lk_dev(c->mu);
     std::lock_guard<std::mutex> lk_pwm(pwms->mu);
     MS_HIP(hipSetDevice(c->device));
-    {
-        void *blk = nullptr;
-        size_t got = 0;
-        if ((rc = pool_alloc(c, 3 * up256(8 * cz) + up256(4 * cz), &blk, &got))) return rc;
-        res->block = blk;
-        res->block_bytes = got;
-        char *p = static_cast<char *>(blk);
-        res->d_peak = reinterpret_cast<double *>(p); p += up256(8 * cz);
-        res->d_sum = reinterpret_cast<double *>(p); p += up256(8 * cz);
-        res->d_log_mean = reinterpret_cast<double *>(p); p += up256(8 * cz);
-        res->d_n_terms = reinterpret_cast<int32_t *>(p);
-    }
+    Carve rv;
+    const auto s_peak = rv.add<double>(cz), s_sum = rv.add<double>(cz), s_log_mean = rv.add<double>(cz);
+    const auto s_n_terms = rv.add<int32_t>(cz);
+    if ((rc = pool_alloc(c, rv.bytes(), &res->block, &res->block_bytes))) return rc;
+    res->d_peak = Carve::at(res->block, s_peak);
+    res->d_sum = Carve::at(res->block, s_sum);
+    res->d_log_mean = Carve::at(res->block, s_log_mean);
+    res->d_n_terms = Carve::at(res->block, s_n_terms);
     ms_affinity *raw = res.release();
     if (cells == 0) { *out = raw; return MS_OK; }
 
-    const size_t b_seg = plan.seg_first.empty() ? 0 : up256(8 * plan.seg_first.size()), b_long = up256(8 * std::max<size_t>(plan.long_regions.size(), 1)),
-                 b_mot = up256(4 * std::max<size_t>(plan.mot.size(), 1)), b_tile = up256(4 * plan.tile_first.size()), b_wide = up256(4 * plan.wide_first.size()),
-                 b_skip = up256(4 * std::max<size_t>(plan.skipped.size(), 1)), b_part = up256(sizeof(AffPart) * std::max<size_t>((size_t) P * (size_t) n_part, 1));
+    Carve cv;
+    const DenseSlots ds = dense_slots(cv, plan);
+    const auto s_part = cv.add<AffPart>((size_t) P * (size_t) n_part);
     void *wblk = nullptr;
     size_t wgot = 0;
-    if ((rc = pool_alloc(c, 2 * b_seg + b_long + b_mot + b_tile + b_wide + b_skip + b_part, &wblk, &wgot))) { ms_affinity_free(raw); return rc; }
+    if ((rc = pool_alloc(c, cv.bytes(), &wblk, &wgot))) { ms_affinity_free(raw); return rc; }
     auto fail = [&](int code) { pool_free(c, wblk, wgot); ms_affinity_free(raw); return code; };
-    auto hip_fail = [&](hipError_t e, const char *what) { set_error("%s failed: %s", what, hipGetErrorString(e)); return fail(e == hipErrorOutOfMemory ? MS_ERR_NOMEM : MS_ERR_RUNTIME); };
-    char *b = static_cast<char *>(wblk);
-    int64_t *d_seg = reinterpret_cast<int64_t *>(b); b += b_seg;
-    int64_t *d_pfirst = reinterpret_cast<int64_t *>(b); b += b_seg;
-    int64_t *d_long = reinterpret_cast<int64_t *>(b); b += b_long;
-    int32_t *d_mot = reinterpret_cast<int32_t *>(b); b += b_mot;
-    int32_t *d_tile = reinterpret_cast<int32_t *>(b); b += b_tile;
-    int32_t *d_wide = reinterpret_cast<int32_t *>(b); b += b_wide;
-    int32_t *d_skip = reinterpret_cast<int32_t *>(b); b += b_skip;
-    AffPart *d_part = reinterpret_cast<AffPart *>(b);
 
     const hipStream_t st = c->stream;
     if ((rc = pwmset_upload(pwms, c->device, st))) return fail(rc);
     if ((rc = seqset_pack_pending(seqs, st))) return fail(rc);
     const size_t lds = (plan.max_tile + 1) * sizeof(double2);
-    hipError_t he = hipSuccess;
-    if (lds > 48 * 1024) {
-        he = hipFuncSetAttribute(reinterpret_cast<const void *>(affinity_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) ((kBestTileEntries + 1) * sizeof(double2)));
-        if (he != hipSuccess) return hip_fail(he, "raising the LDS limit");
-    }
-    if (!plan.seg_first.empty()) {
-        he = hipMemcpyAsync(d_seg, plan.seg_first.data(), 8 * plan.seg_first.size(), hipMemcpyHostToDevice, st);
-        if (he == hipSuccess) he = hipMemcpyAsync(d_pfirst, plan.part_first.data(), 8 * plan.part_first.size(), hipMemcpyHostToDevice, st);
-        if (he == hipSuccess && n_long > 0) he = hipMemcpyAsync(d_long, plan.long_regions.data(), 8 * plan.long_regions.size(), hipMemcpyHostToDevice, st);
-    }
-    if (he == hipSuccess && n_mot > 0) he = hipMemcpyAsync(d_mot, plan.mot.data(), 4 * plan.mot.size(), hipMemcpyHostToDevice, st);
-    if (he == hipSuccess) he = hipMemcpyAsync(d_tile, plan.tile_first.data(), 4 * plan.tile_first.size(), hipMemcpyHostToDevice, st);
-    if (he == hipSuccess) he = hipMemcpyAsync(d_wide, plan.wide_first.data(), 4 * plan.wide_first.size(), hipMemcpyHostToDevice, st);
-    if (he == hipSuccess && !plan.skipped.empty()) he = hipMemcpyAsync(d_skip, plan.skipped.data(), 4 * plan.skipped.size(), hipMemcpyHostToDevice, st);
-    if (he != hipSuccess) return hip_fail(he, "upload of the plan");
+    if ((rc = dense_raise_lds(c, reinterpret_cast<const void *>(affinity_kernel<true>), lds, (kBestTileEntries + 1) * sizeof(double2)))) return fail(rc);
+    DenseDev d;
+    if ((rc = dense_upload(plan, ds, wblk, st, &d))) return fail(rc);
 
     AffArgs A;
     A.codes = seqs->d_codes; A.nmask = seqs->d_nmask; A.offsets = seqs->d_offsets; A.R = R;
-    A.seg_first = plan.seg_first.empty() ? nullptr : d_seg;
-    A.part_first = plan.seg_first.empty() ? nullptr : d_pfirst;
+    A.seg_first = d.seg_first; A.part_first = d.part_first;
     A.n_seg = n_seg; A.n_part = n_part;
-    A.tile_first = d_tile; A.mot = d_mot;
+    A.tile_first = d.tile_first; A.mot = d.mot;
     A.Pw = dev_pwm(pwms);
     A.strand_mask = strand_mask;
     A.max_n = max_n;
     A.scale = scale;
     A.peak = raw->d_peak; A.sum = raw->d_sum; A.log_mean = raw->d_log_mean; A.n_terms = raw->d_n_terms;
-    A.part = d_part;
+    A.part = Carve::at(wblk, s_part);
+    AffArgs Aw = A;                                      // the wide motifs: one "tile" each
+    Aw.tile_first = d.wide_first;
 
     (void) hipEventRecord(c->ev[0], st);
     const unsigned gx = (unsigned) ((n_seg + kBestWaves - 1) / kBestWaves);
-    for (int32_t t0 = 0; t0 < n_lds_tiles; t0 += kBestGridY) {
-        hipLaunchKernelGGL(affinity_kernel<true>, dim3(gx, (unsigned) std::min(kBestGridY, n_lds_tiles - t0)), dim3(kBestThreads), lds, st, A, t0);
-        if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "affinity kernel");
-    }
-    if (n_wide > 0) {
-        AffArgs Aw = A;
-        Aw.tile_first = d_wide;
-        for (int32_t t0 = 0; t0 < n_wide; t0 += kBestGridY) {
-            hipLaunchKernelGGL(affinity_kernel<false>, dim3(gx, (unsigned) std::min(kBestGridY, n_wide - t0)), dim3(kBestThreads), 0, st, Aw, t0);
-            if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "affinity kernel (tables in HBM)");
-        }
-    }
-    for (int32_t kf = 0; n_long > 0 && kf < n_mot; kf += 4 * kBestGridY) {
-        hipLaunchKernelGGL(affinity_reduce_kernel, dim3((unsigned) n_long, (unsigned) std::min(kBestGridY, (n_mot - kf + 3) / 4)), dim3(256), 0, st, A, d_long, kf, n_mot);
-        if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "affinity reduction");
-    }
-    for (size_t u0 = 0; u0 < plan.skipped.size(); u0 += kBestGridY) {
-        hipLaunchKernelGGL(affinity_fill_kernel, dim3((unsigned) ((R + 255) / 256), (unsigned) std::min<size_t>(kBestGridY, plan.skipped.size() - u0)), dim3(256), 0, st, A, d_skip + u0);
-        if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "affinity fill");
-    }
-    (void) hipEventRecord(c->ev[1], st);
-    he = hipStreamSynchronize(st);
-    if (he != hipSuccess) return hip_fail(he, "affinity scan");
-    float ms01 = 0;
-    (void) hipEventElapsedTime(&ms01, c->ev[0], c->ev[1]);
-    raw->device_ms = ms01;
+    rc = dense_chunks((int64_t) plan.tile_first.size() - 1, "affinity kernel", [&](int64_t t0, unsigned ny) {
+        hipLaunchKernelGGL(affinity_kernel<true>, dim3(gx, ny), dim3(kBestThreads), lds, st, A, (int32_t) t0);
+    });
+    if (!rc) rc = dense_chunks((int64_t) plan.wide_first.size() - 1, "affinity kernel (tables in HBM)", [&](int64_t t0, unsigned ny) {
+        hipLaunchKernelGGL(affinity_kernel<false>, dim3(gx, ny), dim3(kBestThreads), 0, st, Aw, (int32_t) t0);
+    });
+    if (!rc && !plan.long_regions.empty()) rc = dense_chunks((n_mot + 3) / 4, "affinity reduction", [&](int64_t g0, unsigned ny) {       // four motifs a block
+        hipLaunchKernelGGL(affinity_reduce_kernel, dim3((unsigned) plan.long_regions.size(), ny), dim3(256), 0, st, A, d.long_regions, (int32_t) (4 * g0), (int32_t) n_mot);
+    });
+    if (!rc) rc = dense_chunks((int64_t) plan.skipped.size(), "affinity fill", [&](int64_t u0, unsigned ny) {
+        hipLaunchKernelGGL(affinity_fill_kernel, dim3((unsigned) ((R + 255) / 256), ny), dim3(256), 0, st, A, d.skipped + u0);
+    });
+    if (!rc) rc = dense_finish(c, "affinity scan", raw);
+    if (rc) return fail(rc);
     pool_free(c, wblk, wgot);
     *out = raw;
     return MS_OK;
 }
 
-int ms_affinity_shape(const ms_affinity *a, int32_t *n_pwms, int64_t *n_seqs) {
-    if (!a) { set_error("NULL argument"); return MS_ERR_INVALID; }
-    if (n_pwms) *n_pwms = a->P;
-    if (n_seqs) *n_seqs = a->R;
-    return MS_OK;
-}
+int ms_affinity_shape(const ms_affinity *a, int32_t *n_pwms, int64_t *n_seqs) { return dense_shape(a, n_pwms, n_seqs); }
+int ms_affinity_device_ms(const ms_affinity *a, double *ms) { return dense_device_ms(a, ms); }
 
 int ms_affinity_cells(const ms_affinity *a, int32_t m0, int32_t m1, double *peak, double *sum, int32_t *n_terms, double *log_mean) {
-    if (!a) { set_error("NULL argument"); return MS_ERR_INVALID; }
-    if (m0 < 0 || m1 > a->P || m0 > m1) { set_error("motif range [%d, %d) outside [0, %d)", m0, m1, a->P); return MS_ERR_INVALID; }
-    const size_t at = (size_t) m0 * (size_t) a->R, n = (size_t) (m1 - m0) * (size_t) a->R;
-    if (n == 0) return MS_OK;
-    MS_HIP(hipSetDevice(a->device));
-    if (peak) MS_HIP(hipMemcpy(peak, a->d_peak + at, 8 * n, hipMemcpyDeviceToHost));
-    if (sum) MS_HIP(hipMemcpy(sum, a->d_sum + at, 8 * n, hipMemcpyDeviceToHost));
-    if (n_terms) MS_HIP(hipMemcpy(n_terms, a->d_n_terms + at, 4 * n, hipMemcpyDeviceToHost));
-    if (log_mean) MS_HIP(hipMemcpy(log_mean, a->d_log_mean + at, 8 * n, hipMemcpyDeviceToHost));
+    size_t at = 0, n = 0;
+    if (int rc = dense_rows(a, m0, m1, &at, &n)) return rc;
+    if (peak && n) MS_HIP(hipMemcpy(peak, a->d_peak + at, 8 * n, hipMemcpyDeviceToHost));
+    if (sum && n) MS_HIP(hipMemcpy(sum, a->d_sum + at, 8 * n, hipMemcpyDeviceToHost));
+    if (n_terms && n) MS_HIP(hipMemcpy(n_terms, a->d_n_terms + at, 4 * n, hipMemcpyDeviceToHost));
+    if (log_mean && n) MS_HIP(hipMemcpy(log_mean, a->d_log_mean + at, 8 * n, hipMemcpyDeviceToHost));
     return MS_OK;
 }
 
@@ -424,12 +356,6 @@ int ms_affinity_cells_device(const ms_affinity *a, void **d_peak, void **d_sum, 
     if (d_sum) *d_sum = a->d_sum;
     if (d_n_terms) *d_n_terms = a->d_n_terms;
     if (d_log_mean) *d_log_mean = a->d_log_mean;
-    return MS_OK;
-}
-
-int ms_affinity_device_ms(const ms_affinity *a, double *ms) {
-    if (!a || !ms) { set_error("NULL argument"); return MS_ERR_INVALID; }
-    *ms = a->device_ms;
     return MS_OK;
 }
 

@@ -22,6 +22,9 @@
 // a partial per segment, and best_reduce_kernel folds them in segment order by the same rule.
 // Motifs wider than kBestTileMaxW read their table from HBM (score_window); unscorable motifs (max_raw not a finite number > 0, a NaN or
 // +inf entry: the reference never reports a site for them) are filled with the "no winner" triple and never scored.
+//
+// Behind ms_scan_best this file also holds the host side that the three dense walks share (declared in ms_handles.h; ms_affinity.hip and
+// ms_scorehist.hip call it): a plan's upload, the LDS limit, the end of a scan, and the accessors of a DenseHead.
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -35,7 +38,7 @@ namespace ms {
 
 namespace {
 
-// (the sizes of the walk -- kBestThreads ... kBestGridY -- are in ms_best_dev.h: ms_affinity.hip walks the same way)
+// (the sizes of the walk -- kBestThreads ... kBestTileEntries -- are in ms_best_dev.h: ms_affinity.hip walks the same way)
 struct BestPart {                                        // a segment's best of one motif
     double q;
     int32_t pos;                                         // -1: no winner
@@ -193,6 +196,84 @@ __global__ void __launch_bounds__(256) best_fill_kernel(const int32_t *__restric
 
 }  // namespace
 
+// ---- the host side of the dense walks (ms_handles.h)
+
+int dense_regions_fit(const ms_seqset *seqs, const char *what) {
+    const int64_t *off = seqs->offsets.data();
+    for (int64_t r = 0; r < seqs->R; r++)
+        if (off[r + 1] - off[r] >= (1LL << 31)) {
+            set_error("region %lld has %lld bases: %s 32-bit, cut it into regions of fewer than 2^31", (long long) r, (long long) (off[r + 1] - off[r]), what);
+            return MS_ERR_INVALID;
+        }
+    return MS_OK;
+}
+
+int dense_upload(const DensePlan &pl, const DenseSlots &s, void *work, hipStream_t st, DenseDev *d) {
+    hipError_t he = hipSuccess;
+    auto up = [&](const auto &v, auto slot) -> decltype(v.data()) {
+        if (v.empty()) return nullptr;
+        auto *p = Carve::at(work, slot);
+        if (he == hipSuccess) he = hipMemcpyAsync(p, v.data(), sizeof(v[0]) * v.size(), hipMemcpyHostToDevice, st);
+        return p;
+    };
+    d->seg_first = up(pl.seg_first, s.seg_first);
+    d->part_first = up(pl.part_first, s.part_first);
+    d->long_regions = up(pl.long_regions, s.long_regions);
+    d->mot = up(pl.mot, s.mot);
+    d->tile_first = up(pl.tile_first, s.tile_first);
+    d->wide_first = up(pl.wide_first, s.wide_first);
+    d->skipped = up(pl.skipped, s.skipped);
+    return he == hipSuccess ? MS_OK : hip_rc(he, "upload of the plan");
+}
+
+int dense_raise_lds(DeviceCtx *c, const void *kernel, size_t need, size_t most) {
+    if (need <= 48 * 1024 || std::find(c->lds_raised.begin(), c->lds_raised.end(), kernel) != c->lds_raised.end()) return MS_OK;
+    const hipError_t he = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) most);
+    if (he != hipSuccess) return hip_rc(he, "raising the LDS limit");
+    c->lds_raised.push_back(kernel);
+    return MS_OK;
+}
+
+int dense_finish(DeviceCtx *c, const char *what, DenseHead *h) {
+    (void) hipEventRecord(c->ev[1], c->stream);
+    const hipError_t he = hipStreamSynchronize(c->stream);
+    if (he != hipSuccess) return hip_rc(he, what);
+    float ms01 = 0;
+    (void) hipEventElapsedTime(&ms01, c->ev[0], c->ev[1]);
+    h->device_ms = ms01;
+    return MS_OK;
+}
+
+void dense_release(DenseHead *h) {
+    if (!h || !h->block) return;
+    (void) hipSetDevice(h->device);
+    DeviceCtx *c = nullptr;
+    if (get_ctx(h->device, &c) == MS_OK) pool_free(c, h->block, h->block_bytes); else (void) hipFree(h->block);
+    h->block = nullptr;
+}
+
+int dense_shape(const DenseHead *h, int32_t *n_pwms, int64_t *n_seqs) {
+    if (!h) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    if (n_pwms) *n_pwms = h->P;
+    if (n_seqs) *n_seqs = h->R;
+    return MS_OK;
+}
+
+int dense_device_ms(const DenseHead *h, double *ms) {
+    if (!h || !ms) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    *ms = h->device_ms;
+    return MS_OK;
+}
+
+int dense_rows(const DenseHead *h, int32_t m0, int32_t m1, size_t *at, size_t *n) {
+    if (!h) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    if (m0 < 0 || m1 > h->P || m0 > m1) { set_error("motif range [%d, %d) outside [0, %d)", m0, m1, h->P); return MS_ERR_INVALID; }
+    *at = (size_t) m0 * (size_t) h->R;
+    *n = (size_t) (m1 - m0) * (size_t) h->R;
+    if (*n > 0) MS_HIP(hipSetDevice(h->device));
+    return MS_OK;
+}
+
 }  // namespace ms
 
 using namespace ms;
@@ -202,12 +283,7 @@ extern "C" {
 int ms_debug_best_segment_windows(void) { return kBestSegWindows; }
 
 void ms_best_free(ms_best *b) {
-    if (!b) return;
-    if (b->block) {
-        (void) hipSetDevice(b->device);
-        DeviceCtx *c = nullptr;
-        if (get_ctx(b->device, &c) == MS_OK) pool_free(c, b->block, b->block_bytes); else (void) hipFree(b->block);
-    }
+    dense_release(b);
     delete b;
 }
 
@@ -221,33 +297,20 @@ int ms_scan_best(const ms_pwmset *pwms_c, const ms_seqset *seqs, int strand_mask
     ms_pwmset *pwms = const_cast<ms_pwmset *>(pwms_c);
     const int32_t P = pwms->P;
     const int64_t R = seqs->R;
-    const int64_t *off = seqs->offsets.data();
-    for (int64_t r = 0; r < R; r++)
-        if (off[r + 1] - off[r] >= (1LL << 31)) {
-            set_error("region %lld has %lld bases: positions are 32-bit, cut it into regions of fewer than 2^31", (long long) r, (long long) (off[r + 1] - off[r]));
-            return MS_ERR_INVALID;
-        }
-    DeviceCtx *c;
-    int rc = get_ctx(seqs->device, &c);
+    int rc = dense_regions_fit(seqs, "positions are");
     if (rc) return rc;
+    DeviceCtx *c;
+    if ((rc = get_ctx(seqs->device, &c))) return rc;
     std::unique_ptr<ms_best> res(new (std::nothrow) ms_best());
     if (!res) { set_error("out of host memory"); return MS_ERR_NOMEM; }
     res->device = c->device;
     res->P = P;
     res->R = R;
 
-    // ---- the plan, on the host: segments of the regions, tiles of the motifs (dense_plan, ms_best_dev.h)
+    // ---- the plan, on the host: segments of the regions, tiles of the motifs (ms_dense_plan.h)
     DensePlan plan;
-    try {
-        dense_plan(pwms, off, R, [&](int32_t m) { return scorable(pwms, m); }, &plan);
-    } catch (const std::bad_alloc &) { set_error("out of host memory"); return MS_ERR_NOMEM; }
-    const std::vector<int64_t> &seg_first = plan.seg_first, &part_first = plan.part_first, &long_regions = plan.long_regions;
-    const std::vector<int32_t> &mot = plan.mot, &tile_first = plan.tile_first, &wide_first = plan.wide_first, &uns = plan.skipped;
-    const int64_t n_seg = plan.n_seg, n_part = plan.n_part;
-    const size_t max_tile = plan.max_tile;
-    const int32_t n_lds_tiles = (int32_t) tile_first.size() - 1, n_wide = (int32_t) wide_first.size() - 1, n_mot = (int32_t) mot.size();
-    const int64_t n_long = (int64_t) long_regions.size();
-    if (n_long > 0x7FFFFFFFLL || (n_seg + kBestWaves - 1) / kBestWaves > 0x7FFFFFFFLL) { set_error("too many segments for one launch"); return MS_ERR_INVALID; }
+    if ((rc = dense_plan_for(kBestGeom, pwms, seqs, kBestWaves, [&](int32_t m) { return scorable(pwms, m); }, &plan))) return rc;
+    const int64_t n_seg = plan.n_seg, n_part = plan.n_part, n_mot = (int64_t) plan.mot.size();
 
     // ---- 13 bytes per cell, 16 per partial: both blocks are allocated before anything is launched, and a failure there is the MS_ERR_NOMEM
     // of the header (the test here only keeps the byte counts below inside size_t)
@@ -259,120 +322,75 @@ int ms_scan_best(const ms_pwmset *pwms_c, const ms_seqset *seqs, int strand_mask
     std::lock_guard<std::mutex> lk_dev(c->mu);
     std::lock_guard<std::mutex> lk_pwm(pwms->mu);
     MS_HIP(hipSetDevice(c->device));
-    {
-        void *blk = nullptr;
-        size_t got = 0;
-        if ((rc = pool_alloc(c, up256(8 * cz) + up256(4 * cz) + up256(cz), &blk, &got))) return rc;
-        res->block = blk;
-        res->block_bytes = got;
-        char *p = static_cast<char *>(blk);
-        res->d_score = reinterpret_cast<double *>(p); p += up256(8 * cz);
-        res->d_pos = reinterpret_cast<int32_t *>(p); p += up256(4 * cz);
-        res->d_strand = reinterpret_cast<int8_t *>(p);
-    }
+    Carve rv;
+    const auto s_score = rv.add<double>(cz);
+    const auto s_pos = rv.add<int32_t>(cz);
+    const auto s_strand = rv.add<int8_t>(cz);
+    if ((rc = pool_alloc(c, rv.bytes(), &res->block, &res->block_bytes))) return rc;
+    res->d_score = Carve::at(res->block, s_score);
+    res->d_pos = Carve::at(res->block, s_pos);
+    res->d_strand = Carve::at(res->block, s_strand);
     ms_best *raw = res.release();
     if (cells == 0) { *out = raw; return MS_OK; }
 
-    const size_t b_seg = seg_first.empty() ? 0 : up256(8 * seg_first.size()), b_long = up256(8 * std::max<size_t>(long_regions.size(), 1)),
-                 b_mot = up256(4 * std::max<size_t>(mot.size(), 1)), b_tile = up256(4 * tile_first.size()), b_wide = up256(4 * wide_first.size()),
-                 b_uns = up256(4 * std::max<size_t>(uns.size(), 1)), b_part = up256(sizeof(BestPart) * std::max<size_t>((size_t) P * (size_t) n_part, 1));
+    Carve cv;
+    const DenseSlots ds = dense_slots(cv, plan);
+    const auto s_part = cv.add<BestPart>((size_t) P * (size_t) n_part);
     void *wblk = nullptr;
     size_t wgot = 0;
-    if ((rc = pool_alloc(c, 2 * b_seg + b_long + b_mot + b_tile + b_wide + b_uns + b_part, &wblk, &wgot))) { ms_best_free(raw); return rc; }
+    if ((rc = pool_alloc(c, cv.bytes(), &wblk, &wgot))) { ms_best_free(raw); return rc; }
     auto fail = [&](int code) { pool_free(c, wblk, wgot); ms_best_free(raw); return code; };
-    auto hip_fail = [&](hipError_t e, const char *what) { set_error("%s failed: %s", what, hipGetErrorString(e)); return fail(e == hipErrorOutOfMemory ? MS_ERR_NOMEM : MS_ERR_RUNTIME); };
-    char *b = static_cast<char *>(wblk);
-    int64_t *d_seg = reinterpret_cast<int64_t *>(b); b += b_seg;
-    int64_t *d_pfirst = reinterpret_cast<int64_t *>(b); b += b_seg;
-    int64_t *d_long = reinterpret_cast<int64_t *>(b); b += b_long;
-    int32_t *d_mot = reinterpret_cast<int32_t *>(b); b += b_mot;
-    int32_t *d_tile = reinterpret_cast<int32_t *>(b); b += b_tile;
-    int32_t *d_wide = reinterpret_cast<int32_t *>(b); b += b_wide;
-    int32_t *d_uns = reinterpret_cast<int32_t *>(b); b += b_uns;
-    BestPart *d_part = reinterpret_cast<BestPart *>(b);
 
     const hipStream_t st = c->stream;
     if ((rc = pwmset_upload(pwms, c->device, st))) return fail(rc);
     if ((rc = seqset_pack_pending(seqs, st))) return fail(rc);
-    const size_t lds = (max_tile + 1) * sizeof(double2);
-    hipError_t he = hipSuccess;
-    if (lds > 48 * 1024 && !c->best_lds_set) {
-        he = hipFuncSetAttribute(reinterpret_cast<const void *>(best_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) ((kBestTileEntries + 1) * sizeof(double2)));
-        if (he != hipSuccess) return hip_fail(he, "raising the LDS limit");
-        c->best_lds_set = true;
-    }
-    if (!seg_first.empty()) {
-        he = hipMemcpyAsync(d_seg, seg_first.data(), 8 * seg_first.size(), hipMemcpyHostToDevice, st);
-        if (he == hipSuccess) he = hipMemcpyAsync(d_pfirst, part_first.data(), 8 * part_first.size(), hipMemcpyHostToDevice, st);
-        if (he == hipSuccess && n_long > 0) he = hipMemcpyAsync(d_long, long_regions.data(), 8 * long_regions.size(), hipMemcpyHostToDevice, st);
-    }
-    if (he == hipSuccess && n_mot > 0) he = hipMemcpyAsync(d_mot, mot.data(), 4 * mot.size(), hipMemcpyHostToDevice, st);
-    if (he == hipSuccess) he = hipMemcpyAsync(d_tile, tile_first.data(), 4 * tile_first.size(), hipMemcpyHostToDevice, st);
-    if (he == hipSuccess) he = hipMemcpyAsync(d_wide, wide_first.data(), 4 * wide_first.size(), hipMemcpyHostToDevice, st);
-    if (he == hipSuccess && !uns.empty()) he = hipMemcpyAsync(d_uns, uns.data(), 4 * uns.size(), hipMemcpyHostToDevice, st);
-    if (he != hipSuccess) return hip_fail(he, "upload of the plan");
+    const size_t lds = (plan.max_tile + 1) * sizeof(double2);
+    if ((rc = dense_raise_lds(c, reinterpret_cast<const void *>(best_kernel<true>), lds, (kBestTileEntries + 1) * sizeof(double2)))) return fail(rc);
+    DenseDev d;
+    if ((rc = dense_upload(plan, ds, wblk, st, &d))) return fail(rc);
 
     BestArgs A;
     A.codes = seqs->d_codes; A.nmask = seqs->d_nmask; A.offsets = seqs->d_offsets; A.R = R;
-    A.seg_first = seg_first.empty() ? nullptr : d_seg;
-    A.part_first = seg_first.empty() ? nullptr : d_pfirst;
+    A.seg_first = d.seg_first; A.part_first = d.part_first;
     A.n_seg = n_seg; A.n_part = n_part;
-    A.tile_first = d_tile; A.mot = d_mot;
+    A.tile_first = d.tile_first; A.mot = d.mot;
     A.Pw = dev_pwm(pwms);
     A.strand_mask = strand_mask;
     A.score = raw->d_score; A.pos = raw->d_pos; A.strand = raw->d_strand;
-    A.part = d_part;
+    A.part = Carve::at(wblk, s_part);
+    BestArgs Aw = A;                                     // the wide motifs: one "tile" each
+    Aw.tile_first = d.wide_first;
 
     (void) hipEventRecord(c->ev[0], st);
     const unsigned gx = (unsigned) ((n_seg + kBestWaves - 1) / kBestWaves);
-    for (int32_t t0 = 0; t0 < n_lds_tiles; t0 += kBestGridY) {
-        hipLaunchKernelGGL(best_kernel<true>, dim3(gx, (unsigned) std::min(kBestGridY, n_lds_tiles - t0)), dim3(kBestThreads), lds, st, A, t0);
-        if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "best-site kernel");
-    }
-    if (n_wide > 0) {
-        BestArgs Aw = A;
-        Aw.tile_first = d_wide;
-        for (int32_t t0 = 0; t0 < n_wide; t0 += kBestGridY) {
-            hipLaunchKernelGGL(best_kernel<false>, dim3(gx, (unsigned) std::min(kBestGridY, n_wide - t0)), dim3(kBestThreads), 0, st, Aw, t0);
-            if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "best-site kernel (tables in HBM)");
-        }
-    }
-    for (int32_t kf = 0; n_long > 0 && kf < n_mot; kf += 4 * kBestGridY) {
-        hipLaunchKernelGGL(best_reduce_kernel, dim3((unsigned) n_long, (unsigned) std::min(kBestGridY, (n_mot - kf + 3) / 4)), dim3(256), 0, st, A, d_long, kf, n_mot);
-        if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "best-site reduction");
-    }
-    for (size_t u0 = 0; u0 < uns.size(); u0 += kBestGridY) {
-        hipLaunchKernelGGL(best_fill_kernel, dim3((unsigned) ((R + 255) / 256), (unsigned) std::min<size_t>(kBestGridY, uns.size() - u0)), dim3(256), 0, st,
-                           d_uns + u0, R, raw->d_score, raw->d_pos, raw->d_strand);
-        if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "best-site fill");
-    }
-    (void) hipEventRecord(c->ev[1], st);
-    he = hipStreamSynchronize(st);
-    if (he != hipSuccess) return hip_fail(he, "best-site scan");
-    float ms01 = 0;
-    (void) hipEventElapsedTime(&ms01, c->ev[0], c->ev[1]);
-    raw->device_ms = ms01;
+    rc = dense_chunks((int64_t) plan.tile_first.size() - 1, "best-site kernel", [&](int64_t t0, unsigned ny) {
+        hipLaunchKernelGGL(best_kernel<true>, dim3(gx, ny), dim3(kBestThreads), lds, st, A, (int32_t) t0);
+    });
+    if (!rc) rc = dense_chunks((int64_t) plan.wide_first.size() - 1, "best-site kernel (tables in HBM)", [&](int64_t t0, unsigned ny) {
+        hipLaunchKernelGGL(best_kernel<false>, dim3(gx, ny), dim3(kBestThreads), 0, st, Aw, (int32_t) t0);
+    });
+    if (!rc && !plan.long_regions.empty()) rc = dense_chunks((n_mot + 3) / 4, "best-site reduction", [&](int64_t g0, unsigned ny) {      // four motifs a block
+        hipLaunchKernelGGL(best_reduce_kernel, dim3((unsigned) plan.long_regions.size(), ny), dim3(256), 0, st, A, d.long_regions, (int32_t) (4 * g0), (int32_t) n_mot);
+    });
+    if (!rc) rc = dense_chunks((int64_t) plan.skipped.size(), "best-site fill", [&](int64_t u0, unsigned ny) {
+        hipLaunchKernelGGL(best_fill_kernel, dim3((unsigned) ((R + 255) / 256), ny), dim3(256), 0, st, d.skipped + u0, R, raw->d_score, raw->d_pos, raw->d_strand);
+    });
+    if (!rc) rc = dense_finish(c, "best-site scan", raw);
+    if (rc) return fail(rc);
     pool_free(c, wblk, wgot);
     *out = raw;
     return MS_OK;
 }
 
-int ms_best_shape(const ms_best *b, int32_t *n_pwms, int64_t *n_seqs) {
-    if (!b) { set_error("NULL argument"); return MS_ERR_INVALID; }
-    if (n_pwms) *n_pwms = b->P;
-    if (n_seqs) *n_seqs = b->R;
-    return MS_OK;
-}
+int ms_best_shape(const ms_best *b, int32_t *n_pwms, int64_t *n_seqs) { return dense_shape(b, n_pwms, n_seqs); }
+int ms_best_device_ms(const ms_best *b, double *ms) { return dense_device_ms(b, ms); }
 
 int ms_best_sites(const ms_best *b, int32_t m0, int32_t m1, double *score, int32_t *pos, int8_t *strand) {
-    if (!b) { set_error("NULL argument"); return MS_ERR_INVALID; }
-    if (m0 < 0 || m1 > b->P || m0 > m1) { set_error("motif range [%d, %d) outside [0, %d)", m0, m1, b->P); return MS_ERR_INVALID; }
-    const size_t at = (size_t) m0 * (size_t) b->R, n = (size_t) (m1 - m0) * (size_t) b->R;
-    if (n == 0) return MS_OK;
-    MS_HIP(hipSetDevice(b->device));
-    if (score) MS_HIP(hipMemcpy(score, b->d_score + at, 8 * n, hipMemcpyDeviceToHost));
-    if (pos) MS_HIP(hipMemcpy(pos, b->d_pos + at, 4 * n, hipMemcpyDeviceToHost));
-    if (strand) MS_HIP(hipMemcpy(strand, b->d_strand + at, n, hipMemcpyDeviceToHost));
+    size_t at = 0, n = 0;
+    if (int rc = dense_rows(b, m0, m1, &at, &n)) return rc;
+    if (score && n) MS_HIP(hipMemcpy(score, b->d_score + at, 8 * n, hipMemcpyDeviceToHost));
+    if (pos && n) MS_HIP(hipMemcpy(pos, b->d_pos + at, 4 * n, hipMemcpyDeviceToHost));
+    if (strand && n) MS_HIP(hipMemcpy(strand, b->d_strand + at, n, hipMemcpyDeviceToHost));
     return MS_OK;
 }
 
@@ -381,12 +399,6 @@ int ms_best_sites_device(const ms_best *b, void **d_score, void **d_pos, void **
     if (d_score) *d_score = b->d_score;
     if (d_pos) *d_pos = b->d_pos;
     if (d_strand) *d_strand = b->d_strand;
-    return MS_OK;
-}
-
-int ms_best_device_ms(const ms_best *b, double *ms) {
-    if (!b || !ms) { set_error("NULL argument"); return MS_ERR_INVALID; }
-    *ms = b->device_ms;
     return MS_OK;
 }
 

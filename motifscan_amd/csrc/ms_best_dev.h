@@ -1,15 +1,16 @@
-// ms_best_dev.h -- what the "best window of a cell" kernels share (ms_best.hip: per region; ms_allelebest.hip: per variant haplotype):
-// the total-order wave reduction and the test for a motif the reference never reports a site of; with ms_scorehist.hip (the score
-// histogram walks the windows as ms_best.hip does), the column loop over an LDS tile of tables; and with ms_affinity.hip (the same
-// walk, another reduction at its end) the dense walk of ms_best.hip: its sizes, the host's plan of segments and motif tiles, and the
-// walk's three steps as functions -- the staging of a tile, a segment's words into registers, the raw sums of one strip of window starts.
-// best_kernel keeps these three steps written out in its own body: called through the functions, hipcc schedules its LDS form
-// differently (its disassembly changes), and that kernel's code is to stay as measured.  A change to a step is made in both places.
+// ms_best_dev.h -- the DEVICE helpers of the kernels that score every window of a cell, and the test for a motif the reference never
+// reports a site of (scorable).  With ms_allelebest.hip (per variant haplotype) ms_best.hip shares the total-order wave reduction; the
+// three dense walks (best_kernel, affinity_kernel, scorehist_kernel) share the walk's kBest* sizes, the column loop over an LDS tile of
+// tables, and the walk's three steps as functions -- the staging of a tile, a segment's words into registers, the raw sums of one strip
+// of window starts.  best_kernel keeps these three steps written out in its own body: called through the functions, hipcc schedules its
+// LDS form differently (its disassembly changes), and that kernel's code is to stay as measured.  A change to a step is made in both places.
+// The HOST side of the three walks is not here: the plan (DenseGeom, dense_plan) and its layout in a work block are ms_dense_plan.h,
+// plain C++; its upload, the chunked launches, the LDS limit and the head of the two result handles (DenseHead) are declared in
+// ms_handles.h and implemented once, in ms_best.hip.
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <limits>
-#include <vector>
 
 #include "ms_device.h"
 #include "ms_handles.h"
@@ -27,7 +28,7 @@ constexpr int kBestStrips = 8;                           // strips of 64 window 
 constexpr int kBestSegWindows = 64 * kBestStrips;
 constexpr int kBestTileMaxW = 1024;                      // (= kExactTileMaxW, ms_fp64.hip) widest motif whose table fits a tile
 constexpr int kBestTileEntries = kBestTileMaxW * 4;      // 64 KB of tab2 entries per tile (+ the zero entry): two blocks share a CU's 160 KB
-constexpr int kBestGridY = 32768;
+constexpr DenseGeom kBestGeom = {kBestSegWindows, kBestTileMaxW, kBestTileEntries, true};      // what the host plans with: partials for long regions
 
 // (q, key) of the wave's lanes -> the winner in every lane: the greater q, equal q to the smaller key = pos << 2 | strand
 __device__ __forceinline__ void wave_best(double &q, uint64_t &key) {
@@ -106,10 +107,8 @@ __device__ __forceinline__ void dense_strip_sums(const double2 *__restrict__ lds
     }
 }
 
-// the reference never reports a site of such a motif: max_raw is not a finite number > 0, or an entry is NaN or +inf
-inline bool scorable(const ms_pwmset *p, int32_t m) {
-    const double mr = p->max_raw[(size_t) m];
-    if (!(std::isfinite(mr) && mr > 0.0)) return false;
+// no entry of the motif is NaN or +inf (ms_scan_affinity scores every such motif; one that fails has an empty row)
+inline bool entries_scorable(const ms_pwmset *p, int32_t m) {
     const double *v = p->values.data() + p->val_off[(size_t) m];
     const int64_t n = 4 * (int64_t) p->widths[(size_t) m];
     for (int64_t i = 0; i < n; i++)
@@ -117,59 +116,10 @@ inline bool scorable(const ms_pwmset *p, int32_t m) {
     return true;
 }
 
-// The plan of a dense walk, made on the host: segments of the regions, tiles of the motifs.
-struct DensePlan {
-    std::vector<int64_t> seg_first;                      // [R + 1] first segment of the region (every region has at least one); empty: one segment per region
-    std::vector<int64_t> part_first;                     // [R + 1] first partial of the region (regions of one segment have none); empty with seg_first
-    std::vector<int64_t> long_regions;                   // the regions of more than one segment
-    std::vector<int32_t> mot;                            // the motifs that are walked: the LDS tiles' one after the other, then the wide ones
-    std::vector<int32_t> tile_first;                     // [LDS tiles + 1] into mot
-    std::vector<int32_t> wide_first;                     // [wide motifs + 1] into mot: one "tile" per motif of more than kBestTileMaxW columns
-    std::vector<int32_t> skipped;                        // the motifs that are not walked: their rows are filled
-    int64_t n_seg = 0, n_part = 0;
-    size_t max_tile = 0;                                 // entries of the largest LDS tile
-};
-
-// walked(m): motif m is scored.  LDS tiles first: runs of consecutive walked motifs of <= kBestTileMaxW columns whose entries fit a tile
-// (consecutive motifs are consecutive in tab2: one contiguous copy stages a tile); then one tile per wider motif.  May throw std::bad_alloc.
-template <typename Walked>
-inline void dense_plan(const ms_pwmset *pwms, const int64_t *off, int64_t R, Walked walked, DensePlan *pl) {
-    const int32_t P = pwms->P;
-    pl->n_seg = R;
-    pl->n_part = 0;
-    bool any_long = false;
-    for (int64_t r = 0; r < R && !any_long; r++) any_long = off[r + 1] - off[r] > kBestSegWindows;
-    if (any_long) {
-        pl->seg_first.resize((size_t) R + 1);
-        pl->part_first.resize((size_t) R + 1);
-        pl->n_seg = 0;
-        for (int64_t r = 0; r < R; r++) {
-            const int64_t n = std::max<int64_t>(1, (off[r + 1] - off[r] + kBestSegWindows - 1) / kBestSegWindows);
-            pl->seg_first[(size_t) r] = pl->n_seg;
-            pl->part_first[(size_t) r] = pl->n_part;
-            pl->n_seg += n;
-            if (n > 1) { pl->n_part += n; pl->long_regions.push_back(r); }
-        }
-        pl->seg_first[(size_t) R] = pl->n_seg;
-        pl->part_first[(size_t) R] = pl->n_part;
-    }
-    pl->tile_first.push_back(0);
-    size_t in_tile = 0;
-    int32_t prev = -2;
-    for (int32_t m = 0; m < P; m++) {
-        if (!walked(m)) { pl->skipped.push_back(m); continue; }
-        const size_t e = (size_t) pwms->widths[(size_t) m] * 4;
-        if (pwms->widths[(size_t) m] > kBestTileMaxW) continue;
-        if (in_tile > 0 && (prev != m - 1 || in_tile + e > (size_t) kBestTileEntries)) { pl->tile_first.push_back((int32_t) pl->mot.size()); in_tile = 0; }
-        pl->mot.push_back(m);
-        in_tile += e;
-        pl->max_tile = std::max(pl->max_tile, in_tile);
-        prev = m;
-    }
-    if (in_tile > 0) pl->tile_first.push_back((int32_t) pl->mot.size());
-    pl->wide_first.push_back((int32_t) pl->mot.size());
-    for (int32_t m = 0; m < P; m++)
-        if (pwms->widths[(size_t) m] > kBestTileMaxW && walked(m)) { pl->mot.push_back(m); pl->wide_first.push_back((int32_t) pl->mot.size()); }
+// the reference never reports a site of a motif that fails this: max_raw is not a finite number > 0, or an entry is NaN or +inf
+inline bool scorable(const ms_pwmset *p, int32_t m) {
+    const double mr = p->max_raw[(size_t) m];
+    return std::isfinite(mr) && mr > 0.0 && entries_scorable(p, m);
 }
 
 }  // namespace

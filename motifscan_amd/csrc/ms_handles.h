@@ -7,6 +7,9 @@
 // summed likelihood ratio of every cell), ms_shuffle.hip (a sequence set shuffled into a new one: mono- and dinucleotide controls),
 // ms_kmers.hip (the k-mer counts of a sequence set or a genome), ms_sitesignal.hip (a resident per-base track and its sums over a result's sites),
 // ms_variants.hip and ms_alleles.hip (the record scans over variants: one placement driver, place_records, and one handle head, RecHead).
+// The three dense walks -- ms_best.hip, ms_affinity.hip, ms_scorehist.hip -- plan on the host with ms_dense_plan.h and share the dense_*
+// helpers below (the plan's upload, the chunked launches, the LDS limit; DenseHead, what ms_best and ms_affinity begin with), which
+// ms_best.hip implements.
 #pragma once
 #include <sched.h>
 #include <atomic>
@@ -20,6 +23,7 @@
 #include <thread>
 #include <vector>
 
+#include "ms_dense_plan.h"
 #include "ms_kernels.h"
 #include "ms_place.h"
 
@@ -93,7 +97,7 @@ struct DeviceCtx {
     std::atomic<int> n_streams{0};           // live batch streams on this device
     size_t lds_max = 0;
     bool rc_lds_set = false;                // rescore_carry_kernel's dynamic-LDS attribute raised
-    bool best_lds_set = false;              // best_kernel's (ms_best.hip)
+    std::vector<const void *> lds_raised;   // the dense walks' kernels whose attribute dense_raise_lds has raised
     size_t lds_set[3] = {};                 // dynamic-LDS attribute already raised to this, per pre-filter kernel (parked, dense, wide)
     Scratch sc;
     std::mutex mu;               // one scan at a time per device (shared scratch)
@@ -271,29 +275,37 @@ struct ms_result {
     ms_scan_stats stats;
 };
 
-struct ms_best {                                      // ms_scan_best: the best window of every (motif, region) cell
+namespace ms {
+
+// What the handles of the two dense [P][R] results begin with (ms_best, ms_affinity), and the one implementation of what only reads it
+// (ms_best.hip).
+struct DenseHead {
     int device = 0;
     int32_t P = 0;
     int64_t R = 0;
-    void *block = nullptr;                            // one pooled device block holding the three [P][R] arrays
+    void *block = nullptr;                            // one pooled device block holding the [P][R] planes
     size_t block_bytes = 0;
+    double device_ms = 0.0;                           // first launch -> last kernel done
+};
+MS_HIDDEN void dense_release(DenseHead *h);           // the block back to its device's pool
+MS_HIDDEN int dense_shape(const DenseHead *h, int32_t *n_pwms, int64_t *n_seqs);
+MS_HIDDEN int dense_device_ms(const DenseHead *h, double *ms);
+// the motif rows [m0, m1) of a plane, checked: they are the *n cells from cell *at on; with *n > 0 the calling thread is on the handle's device
+MS_HIDDEN int dense_rows(const DenseHead *h, int32_t m0, int32_t m1, size_t *at, size_t *n);
+
+}  // namespace ms
+
+struct ms_best : ms::DenseHead {                      // ms_scan_best: the best window of every (motif, region) cell; three planes
     double *d_score = nullptr;                        // NaN: no winner
     int32_t *d_pos = nullptr;                         // relative to the region start, -1: no winner
     int8_t *d_strand = nullptr;                       // 1 '+', 2 '-', 0: no winner
-    double device_ms = 0.0;                           // first launch -> last kernel done
 };
 
-struct ms_affinity {                                  // ms_scan_affinity: the summed likelihood ratio of every (motif, region) cell
-    int device = 0;
-    int32_t P = 0;
-    int64_t R = 0;
-    void *block = nullptr;                            // one pooled device block holding the four [P][R] planes
-    size_t block_bytes = 0;
+struct ms_affinity : ms::DenseHead {                  // ms_scan_affinity: the summed likelihood ratio of every (motif, region) cell; four planes
     double *d_peak = nullptr;                         // the greatest raw sum over the terms; NaN: no term
     double *d_sum = nullptr;                          // sum of exp(scale * (raw - peak))
     double *d_log_mean = nullptr;                     // scale * peak + log(sum / n_terms): the plane ms_affinity_rank_sum ranks
     int32_t *d_n_terms = nullptr;
-    double device_ms = 0.0;                           // first launch -> last kernel done
 };
 
 struct ms_track {                                     // ms_track_create: one int32 per base of a sequence set
@@ -355,6 +367,47 @@ struct PlaceCalls {
 // caller has recorded in front of its upload).  `tile`: variants per block of the caller's kernel; `what` names the scan in the error
 // texts.  The caller holds c->mu; on an error it synchronises the stream before it gives `work` back.
 MS_HIDDEN int place_records(DeviceCtx *c, const PlaceChunks &ch, int tile, void *work, const PlaceSlots &s, const char *what, const PlaceCalls &calls, RecHead *h);
+
+// ---- the host side of a dense walk (ms_best.hip; the plan itself is ms_dense_plan.h)
+// the code of a failed HIP call, with the error text "<what> failed: <HIP's text>" set
+inline int hip_rc(hipError_t e, const char *what) {
+    set_error("%s failed: %s", what, hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? MS_ERR_NOMEM : MS_ERR_RUNTIME;
+}
+// MS_ERR_INVALID for a region of 2^31 bases or more: `what` ("positions are", "n_terms is") is 32-bit in the result
+MS_HIDDEN int dense_regions_fit(const ms_seqset *seqs, const char *what);
+// dense_plan of a PWM set over a sequence set, with the two ways it fails: out of host memory, and more long regions or blocks of
+// segs_per_block segments than the x of one grid holds
+template <typename Walked>
+inline int dense_plan_for(const DenseGeom &g, const ms_pwmset *pwms, const ms_seqset *seqs, int segs_per_block, Walked walked, DensePlan *pl) {
+    try { dense_plan(g, pwms->widths.data(), pwms->P, seqs->offsets.data(), seqs->R, walked, pl); }
+    catch (const std::bad_alloc &) { set_error("out of host memory"); return MS_ERR_NOMEM; }
+    if (pl->long_regions.size() > 0x7FFFFFFFull || (pl->n_seg + segs_per_block - 1) / segs_per_block > 0x7FFFFFFFLL) { set_error("too many segments for one launch"); return MS_ERR_INVALID; }
+    return MS_OK;
+}
+// A plan's arrays on the device, in the work block they were given slots in (dense_slots): nullptr where the plan has none.
+struct DenseDev {
+    const int64_t *seg_first = nullptr, *part_first = nullptr, *long_regions = nullptr;
+    const int32_t *mot = nullptr, *tile_first = nullptr, *wide_first = nullptr, *skipped = nullptr;
+};
+MS_HIDDEN int dense_upload(const DensePlan &pl, const DenseSlots &s, void *work, hipStream_t st, DenseDev *d);
+// The dynamic-LDS limit of a dense walk's kernel raised to `most` bytes, the first time a launch on this device needs more than the
+// 48 KB every kernel may have: once per device and kernel (DeviceCtx::lds_raised), as ms_scan_best always did.
+MS_HIDDEN int dense_raise_lds(DeviceCtx *c, const void *kernel, size_t need, size_t most);
+// Rows [0, n) of a grid's y -- tiles, groups of motifs -- in chunks of at most kDenseGridY: launch(first, count) queues one chunk, and
+// `what` names the kernel in the error text of a launch that fails.
+constexpr int64_t kDenseGridY = 32768;
+template <typename Launch>
+inline int dense_chunks(int64_t n, const char *what, Launch launch) {
+    for (int64_t y0 = 0; y0 < n; y0 += kDenseGridY) {
+        launch(y0, (unsigned) std::min(kDenseGridY, n - y0));
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return hip_rc(e, what);
+    }
+    return MS_OK;
+}
+// c->ev[1] behind the last launch, the wait for the stream, and h->device_ms since c->ev[0]
+MS_HIDDEN int dense_finish(DeviceCtx *c, const char *what, DenseHead *h);
 
 // One [P][R] plane of doubles per group, ranked per motif row (ms_ranksum.hip): what ms_best_rank_sum (the score plane of two ms_best) and
 // ms_affinity_rank_sum (the log_mean plane of two ms_affinity) both are.  `what` names the handles in the error texts.

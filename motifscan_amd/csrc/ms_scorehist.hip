@@ -70,7 +70,7 @@ constexpr int kHistBlockSegs = kHistWaves * kHistSegsPerWave;
 constexpr int kHistTileMaxW = 928;                       // widest motif whose table is staged in LDS
 constexpr int kHistTileEntries = kHistTileMaxW * 4;      // 58 KB of tab2 entries per tile (+ the zero entry) + 16 KB of counters + 3 KB of segments: two blocks share a CU's 160 KB
 constexpr int kHistSlots = MS_SCOREHIST_MAX_BINS + 2;
-constexpr int kHistGridY = 32768;
+constexpr DenseGeom kHistGeom = {kHistSegWindows, kHistTileMaxW, kHistTileEntries, false};      // what the host plans with: counts are added, no partials
 
 struct HistSeg {                                         // a segment of the block: its region's first base and length, its first window start
     int64_t beg, len, p0;
@@ -283,96 +283,58 @@ int ms_scan_score_histogram(const ms_pwmset *pwms_c, const ms_seqset *seqs, int 
     DeviceCtx *c;
     int rc = get_ctx(seqs->device, &c);
     if (rc) return rc;
-    const int64_t *off = seqs->offsets.data();
 
-    // ---- the plan, on the host: segments of the regions, tiles of the motifs, the raw-space thresholds
-    std::vector<int64_t> seg_first;
-    std::vector<int32_t> mot, tile_first, wide_first;
+    // ---- the plan, on the host: segments of the regions, tiles of the motifs (ms_dense_plan.h), the raw-space thresholds
+    DensePlan plan;
+    if ((rc = dense_plan_for(kHistGeom, pwms, seqs, kHistBlockSegs, [&](int32_t m) { return scorable(pwms, m); }, &plan))) return rc;
+    plan.skipped.clear();                              // (their rows stay as cleared: nothing of them goes to the device)
     std::vector<double> bins;
-    int64_t n_seg = R;
-    size_t max_tile = 0;
     try {
-        bool any_long = false;
-        for (int64_t r = 0; r < R && !any_long; r++) any_long = off[r + 1] - off[r] > kHistSegWindows;
-        if (any_long) {
-            seg_first.resize((size_t) R + 1);
-            n_seg = 0;
-            for (int64_t r = 0; r < R; r++) {
-                seg_first[(size_t) r] = n_seg;
-                n_seg += std::max<int64_t>(1, (off[r + 1] - off[r] + kHistSegWindows - 1) / kHistSegWindows);
-            }
-            seg_first[(size_t) R] = n_seg;
-        }
         bins.assign(4 * (size_t) P, 0.0);
-        tile_first.push_back(0);
-        size_t in_tile = 0;
-        int32_t prev = -2;
-        for (int32_t m = 0; m < P; m++) {
-            if (!scorable(pwms, m)) continue;
-            bins[4 * (size_t) m] = lo[m];
-            bins[4 * (size_t) m + 1] = inv_width[m];
-            bins[4 * (size_t) m + 2] = raw_threshold(pwms->max_raw[(size_t) m], lo[m], inv_width[m], 0.0);
-            bins[4 * (size_t) m + 3] = raw_threshold(pwms->max_raw[(size_t) m], lo[m], inv_width[m], (double) n_bins);
-            const size_t e = (size_t) pwms->widths[(size_t) m] * 4;
-            if (pwms->widths[(size_t) m] > kHistTileMaxW) continue;
-            if (in_tile > 0 && (prev != m - 1 || in_tile + e > (size_t) kHistTileEntries)) { tile_first.push_back((int32_t) mot.size()); in_tile = 0; }
-            mot.push_back(m);
-            in_tile += e;
-            max_tile = std::max(max_tile, in_tile);
-            prev = m;
-        }
-        if (in_tile > 0) tile_first.push_back((int32_t) mot.size());
-        wide_first.push_back((int32_t) mot.size());
-        for (int32_t m = 0; m < P; m++)
-            if (pwms->widths[(size_t) m] > kHistTileMaxW && scorable(pwms, m)) { mot.push_back(m); wide_first.push_back((int32_t) mot.size()); }
     } catch (const std::bad_alloc &) { set_error("out of host memory"); return MS_ERR_NOMEM; }
-    const int32_t n_lds_tiles = (int32_t) tile_first.size() - 1, n_wide = (int32_t) wide_first.size() - 1;
-    const int64_t gx64 = (n_seg + kHistBlockSegs - 1) / kHistBlockSegs;
-    if (gx64 > 0x7FFFFFFFLL) { set_error("too many segments for one launch"); return MS_ERR_INVALID; }
+    for (const int32_t m : plan.mot) {
+        bins[4 * (size_t) m] = lo[m];
+        bins[4 * (size_t) m + 1] = inv_width[m];
+        bins[4 * (size_t) m + 2] = raw_threshold(pwms->max_raw[(size_t) m], lo[m], inv_width[m], 0.0);
+        bins[4 * (size_t) m + 3] = raw_threshold(pwms->max_raw[(size_t) m], lo[m], inv_width[m], (double) n_bins);
+    }
 
     std::lock_guard<std::mutex> lk_dev(c->mu);
     std::lock_guard<std::mutex> lk_pwm(pwms->mu);
     MS_HIP(hipSetDevice(c->device));
-    const size_t b_seg = seg_first.empty() ? 0 : up256(8 * seg_first.size()), b_mot = up256(4 * std::max<size_t>(mot.size(), 1)), b_tile = up256(4 * tile_first.size()),
-                 b_wide = up256(4 * wide_first.size()), b_bins = up256(8 * bins.size()), b_out = out_on_device ? 0 : up256(out_bytes);
+    Carve cv;
+    const DenseSlots ds = dense_slots(cv, plan);
+    const auto s_bins = cv.add<double>(bins.size());
+    const auto s_out = cv.add<unsigned long long>(out_on_device ? 0 : (size_t) P * (size_t) n_slots);
     void *wblk = nullptr;
     size_t wgot = 0;
-    if ((rc = pool_alloc(c, b_seg + b_mot + b_tile + b_wide + b_bins + b_out, &wblk, &wgot))) return rc;
+    if ((rc = pool_alloc(c, cv.bytes(), &wblk, &wgot))) return rc;
     auto fail = [&](int code) { pool_free(c, wblk, wgot); return code; };
-    auto hip_fail = [&](hipError_t e, const char *what) { set_error("%s failed: %s", what, hipGetErrorString(e)); return fail(e == hipErrorOutOfMemory ? MS_ERR_NOMEM : MS_ERR_RUNTIME); };
-    char *b = static_cast<char *>(wblk);
-    int64_t *d_seg = reinterpret_cast<int64_t *>(b); b += b_seg;
-    int32_t *d_mot = reinterpret_cast<int32_t *>(b); b += b_mot;
-    int32_t *d_tile = reinterpret_cast<int32_t *>(b); b += b_tile;
-    int32_t *d_wide = reinterpret_cast<int32_t *>(b); b += b_wide;
-    double *d_bins = reinterpret_cast<double *>(b); b += b_bins;
-    unsigned long long *d_out = out_on_device ? reinterpret_cast<unsigned long long *>(out) : reinterpret_cast<unsigned long long *>(b);
+    double *d_bins = Carve::at(wblk, s_bins);
+    unsigned long long *d_out = out_on_device ? reinterpret_cast<unsigned long long *>(out) : Carve::at(wblk, s_out);
 
     const hipStream_t st = c->stream;
     hipError_t he = hipMemsetAsync(d_out, 0, out_bytes, st);
-    if (he != hipSuccess) return hip_fail(he, "clearing the histogram");
+    if (he != hipSuccess) return fail(hip_rc(he, "clearing the histogram"));
     float ms01 = 0;
-    if (R > 0 && !mot.empty()) {
+    const bool walk = R > 0 && !plan.mot.empty();
+    if (walk) {
         if ((rc = pwmset_upload(pwms, c->device, st))) return fail(rc);
         if ((rc = seqset_pack_pending(seqs, st))) return fail(rc);
-        const size_t lds_fixed = kHistSegBytes + hist_counter_bytes(n_bins), lds = lds_fixed + (max_tile + 1) * sizeof(double2);
-        if (lds > 48 * 1024) {
-            he = hipFuncSetAttribute(reinterpret_cast<const void *>(scorehist_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int) (kHistSegBytes + hist_counter_bytes(MS_SCOREHIST_MAX_BINS) + (kHistTileEntries + 1) * sizeof(double2)));
-            if (he != hipSuccess) return hip_fail(he, "raising the LDS limit");
-        }
-        if (!seg_first.empty()) he = hipMemcpyAsync(d_seg, seg_first.data(), 8 * seg_first.size(), hipMemcpyHostToDevice, st);
-        if (he == hipSuccess) he = hipMemcpyAsync(d_mot, mot.data(), 4 * mot.size(), hipMemcpyHostToDevice, st);
-        if (he == hipSuccess) he = hipMemcpyAsync(d_tile, tile_first.data(), 4 * tile_first.size(), hipMemcpyHostToDevice, st);
-        if (he == hipSuccess) he = hipMemcpyAsync(d_wide, wide_first.data(), 4 * wide_first.size(), hipMemcpyHostToDevice, st);
-        if (he == hipSuccess) he = hipMemcpyAsync(d_bins, bins.data(), 8 * bins.size(), hipMemcpyHostToDevice, st);
-        if (he != hipSuccess) return hip_fail(he, "upload of the plan");
+        const size_t lds_fixed = kHistSegBytes + hist_counter_bytes(n_bins), lds = lds_fixed + (plan.max_tile + 1) * sizeof(double2);
+        if ((rc = dense_raise_lds(c, reinterpret_cast<const void *>(scorehist_kernel<true>), lds,
+                                  kHistSegBytes + hist_counter_bytes(MS_SCOREHIST_MAX_BINS) + (kHistTileEntries + 1) * sizeof(double2))))
+            return fail(rc);
+        DenseDev d;
+        if ((rc = dense_upload(plan, ds, wblk, st, &d))) return fail(rc);
+        he = hipMemcpyAsync(d_bins, bins.data(), 8 * bins.size(), hipMemcpyHostToDevice, st);
+        if (he != hipSuccess) return fail(hip_rc(he, "upload of the plan"));
 
         HistArgs A;
         A.codes = seqs->d_codes; A.nmask = seqs->d_nmask; A.offsets = seqs->d_offsets; A.R = R;
-        A.seg_first = seg_first.empty() ? nullptr : d_seg;
-        A.n_seg = n_seg;
-        A.tile_first = d_tile; A.mot = d_mot;
+        A.seg_first = d.seg_first;
+        A.n_seg = plan.n_seg;
+        A.tile_first = d.tile_first; A.mot = d.mot;
         A.Pw = dev_pwm(pwms);
         A.bins = d_bins;
         A.strand_mask = strand_mask;
@@ -380,30 +342,27 @@ int ms_scan_score_histogram(const ms_pwmset *pwms_c, const ms_seqset *seqs, int 
         A.n_bins = n_bins;
         A.max_n = max_n;
         A.out = d_out;
+        HistArgs Aw = A;                                 // the wide motifs: one "tile" each
+        Aw.tile_first = d.wide_first;
 
         (void) hipEventRecord(c->ev[0], st);
-        const unsigned gx = (unsigned) gx64;
-        for (int32_t t0 = 0; t0 < n_lds_tiles; t0 += kHistGridY) {
-            hipLaunchKernelGGL(scorehist_kernel<true>, dim3(gx, (unsigned) std::min(kHistGridY, n_lds_tiles - t0)), dim3(kHistThreads), lds, st, A, t0);
-            if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "score-histogram kernel");
-        }
-        if (n_wide > 0) {
-            HistArgs Aw = A;
-            Aw.tile_first = d_wide;
-            for (int32_t t0 = 0; t0 < n_wide; t0 += kHistGridY) {
-                hipLaunchKernelGGL(scorehist_kernel<false>, dim3(gx, (unsigned) std::min(kHistGridY, n_wide - t0)), dim3(kHistThreads), lds_fixed, st, Aw, t0);
-                if ((he = hipGetLastError()) != hipSuccess) return hip_fail(he, "score-histogram kernel (tables in HBM)");
-            }
-        }
+        const unsigned gx = (unsigned) ((plan.n_seg + kHistBlockSegs - 1) / kHistBlockSegs);
+        rc = dense_chunks((int64_t) plan.tile_first.size() - 1, "score-histogram kernel", [&](int64_t t0, unsigned ny) {
+            hipLaunchKernelGGL(scorehist_kernel<true>, dim3(gx, ny), dim3(kHistThreads), lds, st, A, (int32_t) t0);
+        });
+        if (!rc) rc = dense_chunks((int64_t) plan.wide_first.size() - 1, "score-histogram kernel (tables in HBM)", [&](int64_t t0, unsigned ny) {
+            hipLaunchKernelGGL(scorehist_kernel<false>, dim3(gx, ny), dim3(kHistThreads), lds_fixed, st, Aw, (int32_t) t0);
+        });
+        if (rc) return fail(rc);
         (void) hipEventRecord(c->ev[1], st);
     }
     if (!out_on_device) {
         he = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st);
-        if (he != hipSuccess) return hip_fail(he, "copy of the histogram");
+        if (he != hipSuccess) return fail(hip_rc(he, "copy of the histogram"));
     }
     he = hipStreamSynchronize(st);
-    if (he != hipSuccess) return hip_fail(he, "score histogram");
-    if (R > 0 && !mot.empty()) (void) hipEventElapsedTime(&ms01, c->ev[0], c->ev[1]);
+    if (he != hipSuccess) return fail(hip_rc(he, "score histogram"));
+    if (walk) (void) hipEventElapsedTime(&ms01, c->ev[0], c->ev[1]);
     if (device_ms) *device_ms = ms01;
     pool_free(c, wblk, wgot);
     return MS_OK;
