@@ -8,8 +8,10 @@ tests/test_host_cabi.py calls check() on the object the shipped library was link
 instantiations of prefilter_f6_kernel (<2, parked>, <2, dense>, <4, parked>):
 
   * <= 128 vector registers (four waves per SIMD);
-  * in the narrow kernels (<2, *>: every JASPAR-like set runs on them) no scalar spills, <= 16 spilled vector registers, <= 64 bytes
-    of scratch, and no scratch traffic between the first and the last matrix instruction.
+  * in the narrow kernels (<2, *>: every JASPAR-like set runs on them) no spilled register, scalar or vector, and no scratch memory at all
+    (a spill in a pass's set-up is reloaded in front of the sequence prefetch, behind a wait that exposes the loads' latency; the rule
+    from before, no scratch traffic between the first and the last matrix instruction, stays and follows from this one).
+The wide kernel (<4, parked>) may spill.
 """
 import os
 import re
@@ -72,7 +74,7 @@ def check_code(funcs, notes):
         mf = [i for i, l in enumerate(body) if l.startswith("v_mfma")]
         _need(len(mf) >= 12, k, "holds only", len(mf), "matrix instructions")
         if "ILi2E" in k:                                            # the double-pass kernels (plans without a wide tile)
-            _need(num["sgpr_spill_count"] == 0 and num["vgpr_spill_count"] <= 16 and num["private_segment_fixed_size"] <= 64, k, "spills:", num)
+            _need(num["sgpr_spill_count"] == 0 and num["vgpr_spill_count"] == 0 and num["private_segment_fixed_size"] == 0, k, "spills:", num)
             _need(not [l for l in body[mf[0]:mf[-1] + 1] if l.startswith("scratch_")], k, "spill traffic inside the pass body")
         summary.append(f"{k[k.index('ILi'):][:8]}: {num['vgpr_count']} vgprs, {num['vgpr_spill_count']} spilled")
     return "; ".join(summary)

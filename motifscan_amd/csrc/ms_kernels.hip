@@ -765,24 +765,29 @@ __global__ void __launch_bounds__(kPfThreads, 4) prefilter_f6_kernel(const PfArg
     const char *lds = reinterpret_cast<const char *>(lds4);
     const char *lut = reinterpret_cast<const char *>(lut4);
     const int n_classes = T->n_classes;
+    // The wave's number in its block: the same in all its lanes, which the compiler cannot know of threadIdx.x >> 6 -- read from the first
+    // lane, it and everything made of it (the wave's LDS spaces, its units) live in scalar registers.  (Left in vector registers -- a dozen
+    // of them, live through every pass -- they were what the narrow kernels spilled: rounds 5-13 ran with 11 / 13 spilled registers, reloaded
+    // in front of every pass's sequence loads.)
+    const uint32_t wv = (uint32_t) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
     // every wave OWNS a first block of the candidate list (no atomic: 4096 waves reserving their first block on one counter word
     // cost 45 us, the whole fixed cost of a small scan); further blocks come from the counter, behind the static ones
     MfWave W;
-    W.rq = (uint32_t) (uintptr_t) (__attribute__((address_space(3))) void *) (lds4 + A.rare_off16) + (threadIdx.x >> 6) * (A.rare_cap * (uint32_t) (kRareEntryWords * 4));
+    W.rq = (uint32_t) (uintptr_t) (__attribute__((address_space(3))) void *) (lds4 + A.rare_off16) + wv * (A.rare_cap * (uint32_t) (kRareEntryWords * 4));
     W.rq_cap = A.rare_cap;
     W.rq_flush = A.rare_cap - (A.rare_cap > 32u ? A.rare_cap / 4u : 8u);
     W.rq_n = 0;
-    PfEmit *em = reinterpret_cast<PfEmit *>(reinterpret_cast<uint32_t *>(lds4 + A.emit_off16) + (threadIdx.x >> 6) * (uint32_t) kPfEmitWords);
+    PfEmit *em = reinterpret_cast<PfEmit *>(reinterpret_cast<uint32_t *>(lds4 + A.emit_off16) + wv * (uint32_t) kPfEmitWords);
     const uint32_t em_lds = (uint32_t) (uintptr_t) (__attribute__((address_space(3))) void *) em;
     const uint32_t rq_lds = W.rq;
     if ((threadIdx.x & 63u) == 0) {
-        em->base = ((unsigned long long) blockIdx.y * gridDim.x + blockIdx.x) * (NT / 64) * A.cand_block + (unsigned long long) (threadIdx.x >> 6) * A.cand_block;
+        em->base = ((unsigned long long) blockIdx.y * gridDim.x + blockIdx.x) * (NT / 64) * A.cand_block + (unsigned long long) wv * A.cand_block;
         em->left = A.cand_block;
         em->cand = A.cand; em->n_cand = A.n_cand; em->cand_cap = A.cand_cap; em->cand_static = A.cand_static; em->cand_block = A.cand_block;
     }
     PfOut O;                                                                    // DENSE: the wave's place in the candidate list, in scalar registers
     {
-        const uint32_t wave = (uint32_t) __builtin_amdgcn_readfirstlane((int) (((uint32_t) blockIdx.y * gridDim.x + blockIdx.x) * (uint32_t) (NT / 64) + (threadIdx.x >> 6)));
+        const uint32_t wave = (uint32_t) __builtin_amdgcn_readfirstlane((int) (((uint32_t) blockIdx.y * gridDim.x + blockIdx.x) * (uint32_t) (NT / 64) + wv));
         O.base = (unsigned long long) wave * A.cand_block;
         O.left = A.cand_block;
     }
@@ -793,16 +798,16 @@ __global__ void __launch_bounds__(kPfThreads, 4) prefilter_f6_kernel(const PfArg
     // 0 ... 23 (11) fetch -- for the NEXT pass, before the current one is scanned, so that the global loads' latency hides behind a
     // pass of matrix work -- and every lane then cuts its own windows (double pass: its entries of the one-hot array) out of the staged words (rounds 1-2: ten global loads per lane and pass, their
     // latency exposed once per pass: a third of the kernel's time on inputs with few row tiles per pass, profiles/r03_c2_latency.log).
-    uint32_t *stg = reinterpret_cast<uint32_t *>(lds4 + A.stage_off16) + (threadIdx.x >> 6) * kPfStageWords;
+    uint32_t *stg = reinterpret_cast<uint32_t *>(lds4 + A.stage_off16) + wv * kPfStageWords;
     constexpr bool SH = MAXNK == 2;                                             // the double pass with its one-hot array: kernels without wide classes
-    const uint32_t hw_lds = (uint32_t) (uintptr_t) (__attribute__((address_space(3))) void *) (lds4 + A.onehot_off16) + (threadIdx.x >> 6) * (uint32_t) (kOnehotEntries * 16);
+    const uint32_t hw_lds = (uint32_t) (uintptr_t) (__attribute__((address_space(3))) void *) (lds4 + A.onehot_off16) + wv * (uint32_t) (kOnehotEntries * 16);
     // (32-bit word indices: a set holds <= 2^34 bases = 2^30 code words; the loads then take a scalar base and a 32-bit lane offset)
     const uint32_t n_code_words = (uint32_t) (2 * ((A.n_bases + 31) / 32) + kPadWords), n_mask_words = (uint32_t) ((A.n_bases + 31) / 32 + kPadWords);
     // A pass = PW window starts: 128 in the kernels without wide classes (the double pass: 16 code words and 8 non-ACGT words are staged,
     // 168 bases and their 6 words are needed), 64 in the others (8 + 4 words staged)
     constexpr uint32_t PW = SH ? 128u : 64u, CWP = PW / 16u, NWP = PW / 32u;      // window starts / code words / non-ACGT words per pass
     struct PassWords { uint32_t c, n; };                                        // what lane l loaded: code word l & (2 CWP - 1) and non-ACGT word l & (2 NWP - 1) of the pass
-    auto fetch = [&](uint32_t pass) -> PassWords {                              // pass = pass0 / PW
+    auto fetch = [&](uint32_t pass, uint32_t ln) -> PassWords {                 // pass = pass0 / PW; ln = the lane's number (the caller's copy: below)
         // every lane loads from both arrays -- the same few cache lines -- through a SCALAR base (the pass is wave-uniform) and a small
         // lane offset: a per-lane 64-bit address costs a register pair that the kernel has not got.  The two results stay two
         // registers until they are staged: choosing between them here would make the wave wait for the loads here
@@ -814,7 +819,7 @@ __global__ void __launch_bounds__(kPfThreads, 4) prefilter_f6_kernel(const PfArg
             const uint64_t a = reinterpret_cast<uint64_t>(q);
             return (gptr) (((uint64_t) (uint32_t) __builtin_amdgcn_readfirstlane((int) (a >> 32)) << 32) | (uint64_t) (uint32_t) __builtin_amdgcn_readfirstlane((int) a));
         };
-        return PassWords{uniform(A.codes + bc)[lane & (2u * CWP - 1u)], uniform(A.nmask + bn)[lane & (2u * NWP - 1u)]};
+        return PassWords{uniform(A.codes + bc)[ln & (2u * CWP - 1u)], uniform(A.nmask + bn)[ln & (2u * NWP - 1u)]};
     };
     auto scan_pass = [&](int64_t pass0) {                                    // 64 window starts of this wave (pass0 ... + 63, wave-uniform) against every class
         // (32-bit: what is left of the input from pass0 on is wave-uniform; a 64-bit position per lane costs two register pairs)
@@ -879,16 +884,29 @@ __global__ void __launch_bounds__(kPfThreads, 4) prefilter_f6_kernel(const PfArg
         {
             // the pass's one-hot array (above PassSeq's helpers): lane l makes entries l, 64 + l and 128 + (l & 31) -- the 8 bases from pass0 + entry on,
             // cut out of the staged words with funnel shifts; a non-ACGT base is an all-zero column (any_n: rare, wave-uniform)
-            auto entry = [&](uint32_t x) {
-                const uint32_t w = x >> 4;
-                i32x8 e = onehot_f4(lut, __builtin_amdgcn_alignbit(stg[w + 1], stg[w], (x & 15u) * 2u) & 0xFFFFu);
-                if (any_n) clear_n(e, __builtin_amdgcn_alignbit(stn[(x >> 5) + 1], stn[x >> 5], x & 31u) & 0xFFu);
-                return i32x4{e[0], e[1], e[2], e[3]};
-            };
+            // The three entries do not depend on each other, so they are made side by side, stage by stage: the staged words of all three,
+            // then their six table reads, then the three writes -- two LDS round trips where making them one after the other, each behind the
+            // non-ACGT branch of the one before, took six.  (The image made arithmetically instead -- word r = the packed 16-bit shift of {2, 2}
+            // by four times the codes of bases 2r and 2r + 1, a dozen vector instructions per entry and one round trip -- was measured beside
+            // this form in round 14 and is slower: 15.76 against 15.66 ms per 500 Mbase)
+            // (the entries' numbers from a copy of the lane's number made here: the addresses of their staged words are five registers if
+            // the compiler may carry them from pass to pass)
+            uint32_t lq = lane;
+            asm volatile("" : "+v"(lq));
+            const uint32_t x[3] = {lq, 64u + lq, 128u + (lq & 31u)};
+            uint32_t c16[3];
+#pragma unroll
+            for (int k = 0; k < 3; k++) c16[k] = __builtin_amdgcn_alignbit(stg[(x[k] >> 4) + 1], stg[x[k] >> 4], (x[k] & 15u) * 2u) & 0xFFFFu;
+            i32x8 e[3];
+#pragma unroll
+            for (int k = 0; k < 3; k++) e[k] = onehot_f4(lut, c16[k]);
+            if (any_n) {
+#pragma unroll
+                for (int k = 0; k < 3; k++) clear_n(e[k], __builtin_amdgcn_alignbit(stn[(x[k] >> 5) + 1], stn[x[k] >> 5], x[k] & 31u) & 0xFFu);
+            }
             lds_i32x4 *hq = (lds_i32x4 *) (uintptr_t) hw_lds;
-            hq[lane] = entry(lane);
-            hq[64u + lane] = entry(64u + lane);
-            hq[128u + r] = entry(128u + r);
+#pragma unroll
+            for (int k = 0; k < 3; k++) hq[x[k]] = i32x4{e[k][0], e[k][1], e[k][2], e[k][3]};
         }
         if (any_n && A.skip_alln) {
             // a window whose bases are ALL non-ACGT (the tile's motifs span <= 32 bases) scores 0 on every motif and none reports that (plan:
@@ -932,13 +950,18 @@ __global__ void __launch_bounds__(kPfThreads, 4) prefilter_f6_kernel(const PfArg
         // wave's first unit in its word's group is its own number there; the words start at 0 and the waves add their group's
         // size themselves.
         const bool dyn = A.use_counters != 0;
-        const uint32_t K = !dyn ? 1u : (gridDim.x < (uint32_t) kPfCounters ? gridDim.x : (uint32_t) kPfCounters);     // every word needs a block
-        const uint32_t g = blockIdx.x % K;
-        const uint32_t waves_g = ((gridDim.x - g + K - 1) / K) * wpb;
-        const uint32_t units_g = n_units > g ? (n_units - g + K - 1) / K : 0u;
-        unsigned int *word = A.chunk_counter + ((size_t) blockIdx.y * kPfCounters + g) * 16;
-        uint32_t v = (uint32_t) __builtin_amdgcn_readfirstlane((int) ((blockIdx.x / K) * wpb + (threadIdx.x >> 6)));     // wave-uniform: everything derived from it lives in scalar registers
-        PassWords words = v < units_g ? fetch((v * K + g) * wave_passes) : PassWords{0u, 0u};
+        // (a uniform value INTO a scalar register: the divisions by K below are done by the vector unit, and what follows from them would stay
+        // there -- the compiler knows it uniform and drops a readfirstlane as redundant.  Behind the empty statement it knows nothing of the
+        // value, and the builtin stays; the instruction is still the compiler's own, with the wait states it wants around it)
+        auto sgpr = [](uint32_t x) { asm volatile("" : "+v"(x)); return (uint32_t) __builtin_amdgcn_readfirstlane((int) x); };
+        const uint32_t K = sgpr(!dyn ? 1u : (gridDim.x < (uint32_t) kPfCounters ? gridDim.x : (uint32_t) kPfCounters));     // every word needs a block
+        const uint32_t g = sgpr(blockIdx.x % K);
+        const uint32_t waves_g = sgpr(((gridDim.x - g + K - 1) / K) * wpb);
+        const uint32_t units_g = sgpr(n_units > g ? (n_units - g + K - 1) / K : 0u);
+        const uint32_t word_idx = sgpr(((uint32_t) blockIdx.y * (uint32_t) kPfCounters + g) * 16u);      // (<= 2^16 tiles: 32 bits hold it)
+        unsigned int *word = A.chunk_counter + word_idx;
+        uint32_t v = sgpr((blockIdx.x / K) * wpb + wv);                             // wave-uniform: everything derived from it lives in scalar registers
+        PassWords words = v < units_g ? fetch((v * K + g) * wave_passes, lane) : PassWords{0u, 0u};
         while (v < units_g) {
             uint32_t next = 0xFFFFFFFFu;
             // the next unit: asked for before this one is scanned, looked at in its last pass
@@ -946,16 +969,28 @@ __global__ void __launch_bounds__(kPfThreads, 4) prefilter_f6_kernel(const PfArg
             const uint32_t uid = v * K + g;                                       // the unit: window starts [uid, uid + 1) * PW * wave_passes
             const uint32_t p0 = uid * wave_passes;
             for (uint32_t j = 0; j < wave_passes; j++) {                          // passes past the end scan dead lanes (last unit only)
-                if (lane < 3u * CWP) stg[lane] = lane < 2u * CWP ? words.c : words.n;       // (the wave's LDS operations execute in order: no barrier)
-                [[maybe_unused]] const bool pass_any_n = SH && __any((lane & (2u * NWP - 1u)) < 6u && words.n != 0u);      // (double pass: a non-ACGT base among the 192 staged)
+                // The lane's number, made anew in every pass: what the set-up makes of it -- the staging's and the hand-out's lane conditions, the
+                // two lane offsets of fetch() -- costs an instruction apiece, but carried through the pass (the compiler hoists all of it out of
+                // the unit loop) a register or a pair of scalar registers apiece, which the scan has not got: the offsets came back from scratch
+                // in front of either load, each behind a wait of its own
+                uint32_t ln = lane;
+                asm volatile("" : "+v"(ln));
+                if (ln < 3u * CWP) stg[ln] = ln < 2u * CWP ? words.c : words.n;             // (the wave's LDS operations execute in order: no barrier)
+                [[maybe_unused]] const bool pass_any_n = SH && __any((ln & (2u * NWP - 1u)) < 6u && words.n != 0u);        // (double pass: a non-ACGT base among the 192 staged)
                 // (behind the staging, which waits for every vector-memory operation in flight)
-                if (j == 0 && dyn && lane == 0) u = atomicAdd(word, 1u);
+                // (the counter word through a scalar base and a lane offset of 0 that the compiler cannot see through: of an atomic on an address it
+                // knows uniform it makes a wave-wide reduction, whose result it reads -- and waits for -- on the spot)
+                if (j == 0 && dyn && ln == 0) {
+                    uint32_t zero = 0;
+                    asm volatile("" : "+v"(zero));
+                    u = atomicAdd(word + zero, 1u);
+                }
                 // the next pass's words -- of this unit, or the first of the wave's NEXT unit (its number arrived long ago) -- are in
                 // flight while this pass is scanned
-                if (j + 1 < wave_passes) words = fetch(p0 + j + 1);
+                if (j + 1 < wave_passes) words = fetch(p0 + j + 1, ln);
                 else {
-                    if (dyn) next = waves_g + (uint32_t) __builtin_amdgcn_readfirstlane((int) u);
-                    if (next < units_g) words = fetch((next * K + g) * wave_passes);
+                    if (dyn) next = waves_g + sgpr(u);
+                    if (next < units_g) words = fetch((next * K + g) * wave_passes, ln);
                 }
                 if constexpr (SH) scan_pass2((int64_t) (p0 + j) * 128, pass_any_n);
                 else scan_pass((int64_t) (p0 + j) * 64);
@@ -967,9 +1002,13 @@ __global__ void __launch_bounds__(kPfThreads, 4) prefilter_f6_kernel(const PfArg
     {                                                                             // the unused rest of the last block: empty records
         const unsigned long long base = DENSE ? O.base : em->base;
         const uint32_t left = DENSE ? O.left : em->left;
+        // (parked form: the list and its size from the wave's PfEmit as well -- taken from the arguments they are four scalar registers kept
+        // through the whole scan for this loop, which the scan has not got)
+        uint64_t *const cand = DENSE ? A.cand : em->cand;
+        const uint64_t cand_cap = DENSE ? A.cand_cap : em->cand_cap;
         for (uint32_t i = 0; i < left; i += 64) {
             const unsigned long long j = base + i + lane;
-            if (i + lane < left && j < A.cand_cap) A.cand[j] = 0ULL;
+            if (i + lane < left && j < cand_cap) cand[j] = 0ULL;
         }
     }
 }
