@@ -104,6 +104,10 @@
  *                         no reference counterpart: the sum of exp(raw window score) over ALL windows of a region -- total binding
  *                         affinity (TRAP, AME's avg / sum scoring) per (motif, region) cell, dense, without a hit per window;
  *                         ms_affinity_rank_sum ranks it as ms_best_rank_sum ranks the best score
+ *   ms_affinity_expected_counts
+ *                         no reference counterpart: the E-step of MEME-style expectation maximisation -- per motif column the A, C, G, T
+ *                         weight under it over ALL windows, each weighted by its posterior probability of being the site (ZOOPS / OOPS);
+ *                         the posterior-weighted counterpart of ms_result_site_base_counts, without a cutoff
  *   ms_seqset_shuffle / ms_seqset_packed_host
  *                         no reference counterpart: the input sequences shuffled on the device, keeping base composition or exact
  *                         dinucleotide counts per run of ACGT -- the composition-matched control set of AME / HOMER, as another sequence set
@@ -640,6 +644,47 @@ int  ms_affinity_rank_sum(const ms_affinity *a, const uint8_t *sel_a /* [Ra] or 
                           int32_t m0, int32_t m1, uint32_t flags /* 0 */,
                           int64_t *u2 /* [m1 - m0] */, uint64_t *ties /* [m1 - m0][2]: low word, high word */,
                           int64_t *n /* [2]: na, nb; may be NULL */, double *device_ms /* or NULL */);
+
+/* ---- expected base counts per motif column: the E-step of a motif refinement, on the affinity's terms (ms_expcounts.hip) ---------- */
+#define MS_EXPECTED_MAX_WIDTH 256
+/* For motifs m0 <= m < m1 (row = m - m0): how much A, C, G, T weight stands under every motif column over ALL windows of all regions,
+ * every window weighted by its posterior probability of being the site.  aff must be the result of ms_scan_affinity(pwms, seqs, ...):
+ * strand_mask, scale and max_n are read from the handle.  The unit of every output is U = 2^-32.
+ *   TERMS     of cell (m, r): exactly ms_scan_affinity's -- window start 0 .. L - W, the strands of the mask, the max_n filter -- and
+ *             their raw sums x formed exactly as there (the same column order, +0.0 for a non-ACGT base).
+ *   pi(m, r)  the cell's responsibility: 1 if prior_logit is +inf (OOPS, "one site per region"; no arithmetic is done); 0 if
+ *             n_terms == 0, if log_mean is -inf or if prior_logit is -inf; otherwise 1 / (1 + exp(-(log_mean + prior_logit))), each
+ *             operation rounded once.  This is the ZOOPS posterior that region r holds a site of m when a fraction g of the regions
+ *             does, prior_logit = log(g / (1 - g)): g A / (1 - g + g A) with A = exp(log_mean), the mean likelihood ratio.
+ *   w(term)   for x > -inf: v = pi * exp(scale * (x - peak)) / sum with peak and sum of the cell's planes -- subtract, multiply, exp,
+ *             multiply, divide, each rounded once -- clamped: w = 1 unless v < 1, 0 unless v > 0 (the clamp never acts on planes that
+ *             belong to these inputs, where 0 <= v <= 1; with any other it keeps the conversion defined, and the result is meaningless).
+ *             q = (int64) rint(w * 2^32), round half to even.  A term of x = -inf has q = 0.
+ *   SLOTS     the term adds q to ONE slot of EVERY motif column c = 0 .. W - 1: on '+' that of the base at pos + c, on '-' that of the
+ *             base at pos + W - 1 - c, complemented; slots 0 .. 3 are A, C, G, T in the motif's orientation, slot 4 a non-ACGT base
+ *             (a bit of the non-ACGT plane).  ms_result_site_base_counts' orientation rule, without flanks.
+ *   counts[row][c][s]  the sum of those q; the column pitch of a row is pwms->max_width, the columns behind W are zero.
+ *   total[row]         (may be NULL) the sum of q over all terms: every used column of counts sums to it exactly.
+ *   n_regions[row]     (may be NULL) the regions with n_terms > 0.
+ * A motif with an empty row in aff (a NaN or +inf entry) has all three zero.
+ * Why 2^-32: a weight is in [0, 1], so a region adds at most 2^32 in OOPS and an int64 holds 2^31 regions per motif; rounding a term
+ * costs at most 2^-33; and integer sums do not depend on the order of summation.  PROMISES: the same bytes on every run; a row's bytes
+ * depend only on its motif, the regions and the affinity call's arguments -- not on the motif range, on the other motifs of the set or on
+ * how the work is split; counts, total and n_regions over a sequence set equal the sums over any partition of it into shards (each with
+ * its own ms_scan_affinity), exactly.  No floating-point atomics.
+ * MS_EXPECTED_MAX_WIDTH is not a measured limit: the accumulators and tables of a tile of motifs are kept in LDS together, real
+ * matrices have under 40 columns, and this walk has no path for tables in HBM.
+ * Synchronous.  An empty motif range (m0 == m1) does nothing and returns MS_OK.  Every output is host memory or device memory of the
+ * handle's device; the stream rule is ms_result_site_base_counts': the library writes a device output on its own stream, work the caller
+ * has queued on that memory must have finished before the call, and the call returns after its own writes are done.  *device_ms (may be
+ * NULL): first launch -> last kernel done.
+ * MS_ERR_RUNTIME ("no CPU fallback") without a usable device, before anything else.  MS_ERR_INVALID, before anything is launched: NULL
+ * handles or a NULL counts, flags != 0, prior_logit NaN, a motif range outside [0, P], pwms->P != the handle's P, seqs->R != the handle's
+ * R or seqs on another device, a motif of more than MS_EXPECTED_MAX_WIDTH columns INSIDE the range, an output on another device. */
+int ms_affinity_expected_counts(const ms_affinity *aff, const ms_pwmset *pwms, const ms_seqset *seqs, double prior_logit, int32_t m0,
+                                int32_t m1, uint32_t flags /* 0 */, int64_t *counts /* [(m1 - m0)][pwms->max_width][5] */,
+                                int64_t *total /* [m1 - m0], or NULL */, int64_t *n_regions /* [m1 - m0], or NULL */,
+                                double *device_ms /* or NULL */);
 
 /* The hit arrays in COMPACT form in library-owned pinned host memory: coord[i] = seq_idx << 32 | pos << 1 | (strand - 1),
  * score[i] -- 16 bytes per hit on the host link instead of 25.  Needs seq_idx < 2^32 and pos < 2^31 (MS_ERR_INVALID

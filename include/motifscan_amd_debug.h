@@ -193,6 +193,17 @@ int ms_debug_ranksum_budget(int64_t elems, int64_t *previous);
  * reserved, 0.  Tests size their boundary cases from here.  Needs no GPU. */
 int ms_debug_affinity_dims(int32_t out[8]);
 
+/* The sizes of ms_affinity_expected_counts' walk, as constants of the build: out[0] the window starts per segment; out[1] the widest motif
+ * it takes (MS_EXPECTED_MAX_WIDTH); out[2] the table entries (motif columns x 4) of one LDS tile -- a motif range of more starts a second
+ * tile; out[3] the waves (= segments) per block; out[4] the strips of 64 window starts per segment; out[5] the bytes of LDS accumulator
+ * per motif column; out[6] the default cap of the grid's x (blocks per tile: a block takes further groups of out[3] segments in a
+ * grid-stride loop); out[7] reserved, 0.  Needs no GPU. */
+int ms_debug_expected_dims(int32_t out[8]);
+
+/* The cap of the grid's x for the ms_affinity_expected_counts calls that follow in this process; 0 gives it back to the library.  With a
+ * cap of 1 or 2 a small case makes the grid-stride loop take several trips.  The result does not depend on it.  Needs no GPU. */
+int ms_debug_expected_grid_cap(int32_t blocks);
+
 /* The sizes at which ms_seqset_shuffle changes path, as constants of the build: out[0] the longest run handled by one lane and out[1] the
  * longest run handled by one wave in LDS -- equal, the mapping has no lane tier: every run of up to out[1] bases takes one wave, a longer
  * one takes one block with its keys in pooled global scratch; out[2] the bases per block of the stage that writes the mask plane, clears

@@ -14,6 +14,8 @@ motifscan_amd -- MI355X-native drop-in for ONE hot path of shao-lab/MotifScan: t
     motifscan_amd.kmers     k-mer codes, the restatement of ms_seqset_kmer_counts, Markov backgrounds, k-mer enrichment, seed matrices
     motifscan_amd.footprint signal tracks over sites: host Track constructors, footprint profiles and per-site flank / core sums
                             (ms_result_site_signal), and their sequential restatement
+    motifscan_amd.em        motif refinement without a cutoff: expected base counts per motif column over all windows
+                            (ms_affinity_expected_counts, the E-step), their numpy restatement and mpmath reference, the M-step, the loop
 
 There is no CPU fallback anywhere in this package.
 """

@@ -5,8 +5,10 @@ The shared library is built in-tree by motifscan_amd/csrc/Makefile (hipcc, gfx95
 no CPU implementation behind it: if the library is missing, or no MI355X is visible when a
 compute entry point is called, the call raises -- it never falls back.
 """
+import contextlib
 import ctypes
 import importlib.util
+import math
 import os
 import subprocess
 
@@ -231,6 +233,9 @@ def lib():
         "ms_affinity_free": (None, [vp]),
         "ms_affinity_rank_sum": (c_int, [vp, pu8, vp, pu8, c_i32, c_i32, c_u32, pi64, ctypes.POINTER(ctypes.c_uint64), pi64, pd]),
         "ms_debug_affinity_dims": (c_int, [pi32]),
+        "ms_affinity_expected_counts": (c_int, [vp, vp, vp, ctypes.c_double, c_i32, c_i32, c_u32, vp, vp, vp, pd]),
+        "ms_debug_expected_dims": (c_int, [pi32]),
+        "ms_debug_expected_grid_cap": (c_int, [c_i32]),
         "ms_debug_key_layout": (c_int, [c_i64, c_i64, c_i64, c_i32, c_i32, pi32, pi32]),
         "ms_scan_score_histogram": (c_int, [vp, vp, c_int, c_u32, pd, pd, c_i32, c_i32, vp, pd]),
         "ms_debug_scorehist_dims": (c_int, [pi32]),
@@ -1611,6 +1616,7 @@ class Affinity:
         check(lib().ms_affinity_shape(self.h, ctypes.byref(p), ctypes.byref(r)))
         self.n_pwms, self.n_seqs = p.value, r.value
         self._full = None
+        self.expected_counts_ms = None                   # device_ms of the last expected_counts call
 
     @property
     def shape(self):
@@ -1657,6 +1663,44 @@ class Affinity:
         planes: (u2 int64 [m1 - m0], ties as a list of Python ints, na, nb) -- BestSites.rank_sum's form.  The planes stay on the device."""
         return _rank_sum(lib().ms_affinity_rank_sum, self, other, sel, sel_other, m0, m1, timing)
 
+    def expected_counts(self, pwms, seqs, prior_logit=math.inf, motifs=slice(None), out=None):
+        """ms_affinity_expected_counts on this result, which must come from scan_affinity(pwms, seqs, ...): (counts int64
+        [rows][max width][5], total int64 [rows], n_regions int64 [rows]) of the motifs of the slice `motifs` (step 1), in units of
+        2^-32 -- em.ExpectedCounts reads them.  prior_logit = log(gamma / (1 - gamma)) of the ZOOPS prior, +inf for OOPS.  out: None, or
+        (counts, total, n_regions), each a C-contiguous int64 array of that shape, None (a new one), or the device pointer of a torch
+        tensor as an int (then it is returned).  The call's device_ms is left in self.expected_counts_ms.  The library checks the rest."""
+        if self.h is None:
+            raise ValueError("the result is closed")
+        prior_logit = float(prior_logit)
+        if math.isnan(prior_logit):
+            raise ValueError("prior_logit is NaN")
+        if not isinstance(motifs, slice) or motifs.step not in (None, 1):
+            raise ValueError("motifs must be a slice of step 1")
+        m0, m1, _ = motifs.indices(self.n_pwms)
+        m1 = max(m1, m0)
+        rows = m1 - m0
+        C = int(pwms.widths.max()) if pwms.n else 0
+        shapes = ((rows, C, 5), (rows,), (rows,))
+        given = (None, None, None) if out is None else tuple(out)
+        if len(given) != 3:
+            raise ValueError("out must be (counts, total, n_regions)")
+        arrs, dst = [], []
+        for a, shape in zip(given, shapes):
+            if isinstance(a, int):
+                p = a
+            else:
+                if a is None:
+                    a = np.zeros(shape, dtype=np.int64)
+                if a.dtype != np.int64 or a.shape != shape or not a.flags.c_contiguous:
+                    raise ValueError("out arrays must be C-contiguous int64 of shapes (rows, max width, 5), (rows,) and (rows,)")
+                p = a.ctypes.data
+            arrs.append(a)
+            dst.append(ctypes.c_void_p(p))
+        ms = ctypes.c_double(0.0)
+        check(lib().ms_affinity_expected_counts(self.h, pwms.h, seqs.h, prior_logit, m0, m1, 0, dst[0], dst[1], dst[2], ctypes.byref(ms)))
+        self.expected_counts_ms = ms.value
+        return tuple(arrs)
+
     def close(self):
         if getattr(self, "h", None):
             lib().ms_affinity_free(self.h)
@@ -1687,6 +1731,25 @@ def affinity_dims():
     out = np.zeros(8, dtype=np.int32)
     check(lib().ms_debug_affinity_dims(ptr(out, ctypes.c_int32)))
     return dict(zip(("segment_windows", "tile_max_width", "tile_entries", "waves", "strips", "part_bytes"), out.tolist()))
+
+
+def expected_dims():
+    """ms_debug_expected_dims: dict(segment_windows, max_width, tile_entries, waves, strips, acc_bytes_per_column, grid_cap) -- the sizes
+    of ms_affinity_expected_counts' walk.  Constants of the build; no device."""
+    out = np.zeros(8, dtype=np.int32)
+    check(lib().ms_debug_expected_dims(ptr(out, ctypes.c_int32)))
+    return dict(zip(("segment_windows", "max_width", "tile_entries", "waves", "strips", "acc_bytes_per_column", "grid_cap"), out.tolist()))
+
+
+@contextlib.contextmanager
+def expected_grid_cap(blocks):
+    """ms_debug_expected_grid_cap for the body of a `with`: the blocks per tile of ms_affinity_expected_counts' grid (0 = the library's
+    own), given back at the end.  The result does not depend on it.  Tests only."""
+    check(lib().ms_debug_expected_grid_cap(int(blocks)))
+    try:
+        yield
+    finally:
+        check(lib().ms_debug_expected_grid_cap(0))
 
 
 def histogram_binning(n_pwms, lo, hi, n_bins):

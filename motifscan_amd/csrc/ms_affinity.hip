@@ -259,6 +259,9 @@ int ms_scan_affinity(const ms_pwmset *pwms_c, const ms_seqset *seqs, int strand_
     res->device = c->device;
     res->P = P;
     res->R = R;
+    res->strand_mask = strand_mask;
+    res->scale = scale;
+    res->max_n = max_n;
 
     // ---- the plan, on the host: segments of the regions, tiles of the motifs (ms_dense_plan.h); a motif whose max_raw is <= 0 is walked
     DensePlan plan;

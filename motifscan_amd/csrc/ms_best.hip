@@ -23,8 +23,8 @@
 // Motifs wider than kBestTileMaxW read their table from HBM (score_window); unscorable motifs (max_raw not a finite number > 0, a NaN or
 // +inf entry: the reference never reports a site for them) are filled with the "no winner" triple and never scored.
 //
-// Behind ms_scan_best this file also holds the host side that the three dense walks share (declared in ms_handles.h; ms_affinity.hip and
-// ms_scorehist.hip call it): a plan's upload, the LDS limit, the end of a scan, and the accessors of a DenseHead.
+// Behind ms_scan_best this file also holds the host side that the dense walks share (declared in ms_handles.h; ms_affinity.hip,
+// ms_scorehist.hip and ms_expcounts.hip call it): a plan's upload, the LDS limit, the end of a scan, and the accessors of a DenseHead.
 #include <algorithm>
 #include <cmath>
 #include <limits>

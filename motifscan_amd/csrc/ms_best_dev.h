@@ -1,10 +1,12 @@
 // ms_best_dev.h -- the DEVICE helpers of the kernels that score every window of a cell, and the test for a motif the reference never
 // reports a site of (scorable).  With ms_allelebest.hip (per variant haplotype) ms_best.hip shares the total-order wave reduction; the
-// three dense walks (best_kernel, affinity_kernel, scorehist_kernel) share the walk's kBest* sizes, the column loop over an LDS tile of
+// four dense walks (best_kernel, affinity_kernel, scorehist_kernel, and expcounts_kernel of ms_expcounts.hip: the affinity walk taken a
+// second time) share the walk's kBest* sizes, the column loop over an LDS tile of
 // tables, and the walk's three steps as functions -- the staging of a tile, a segment's words into registers, the raw sums of one strip
 // of window starts.  best_kernel keeps these three steps written out in its own body: called through the functions, hipcc schedules its
-// LDS form differently (its disassembly changes), and that kernel's code is to stay as measured.  A change to a step is made in both places.
-// The HOST side of the three walks is not here: the plan (DenseGeom, dense_plan) and its layout in a work block are ms_dense_plan.h,
+// LDS form differently (its disassembly changes), and that kernel's code is to stay as measured.  A change to a step is made in both
+// places -- the functions here, which affinity_kernel, scorehist_kernel and expcounts_kernel call, and best_kernel's body.
+// The HOST side of the walks is not here: the plan (DenseGeom, dense_plan) and its layout in a work block are ms_dense_plan.h,
 // plain C++; its upload, the chunked launches, the LDS limit and the head of the two result handles (DenseHead) are declared in
 // ms_handles.h and implemented once, in ms_best.hip.
 #pragma once

@@ -4,10 +4,10 @@
 // host-streamed sweeps), ms_best.hip (best window per cell), ms_allelebest.hip (best window per variant haplotype), ms_pairs.hip (motif pairs over a result's hits), ms_scorehist.hip (score histogram of every window),
 // ms_personal.hip (a variant set spliced into a new resident genome, and the lift map between the two), ms_sitestack.hip (base counts per
 // motif column over a result's sites), ms_ranksum.hip (rank sums and passing-region counts over best-site matrices), ms_affinity.hip (the
-// summed likelihood ratio of every cell), ms_shuffle.hip (a sequence set shuffled into a new one: mono- and dinucleotide controls),
+// summed likelihood ratio of every cell), ms_expcounts.hip (the expected base counts per motif column on an affinity's terms), ms_shuffle.hip (a sequence set shuffled into a new one: mono- and dinucleotide controls),
 // ms_kmers.hip (the k-mer counts of a sequence set or a genome), ms_sitesignal.hip (a resident per-base track and its sums over a result's sites),
 // ms_variants.hip and ms_alleles.hip (the record scans over variants: one placement driver, place_records, and one handle head, RecHead).
-// The three dense walks -- ms_best.hip, ms_affinity.hip, ms_scorehist.hip -- plan on the host with ms_dense_plan.h and share the dense_*
+// The four dense walks -- ms_best.hip, ms_affinity.hip, ms_scorehist.hip, ms_expcounts.hip -- plan on the host with ms_dense_plan.h and share the dense_*
 // helpers below (the plan's upload, the chunked launches, the LDS limit; DenseHead, what ms_best and ms_affinity begin with), which
 // ms_best.hip implements.
 #pragma once
@@ -306,6 +306,9 @@ struct ms_affinity : ms::DenseHead {                  // ms_scan_affinity: the s
     double *d_sum = nullptr;                          // sum of exp(scale * (raw - peak))
     double *d_log_mean = nullptr;                     // scale * peak + log(sum / n_terms): the plane ms_affinity_rank_sum ranks
     int32_t *d_n_terms = nullptr;
+    int strand_mask = 0;                              // the scan's arguments, for ms_affinity_expected_counts (ms_expcounts.hip): the second walk
+    double scale = 0.0;                               // over the same terms reads them here, so they cannot disagree with the planes
+    int32_t max_n = -1;
 };
 
 struct ms_track {                                     // ms_track_create: one int32 per base of a sequence set

@@ -19,6 +19,9 @@ and the questions the reference cannot answer from its site lists:
     Scanner.count_regions_passing(pwms, cutoffs) -> the regions with >= 1 site at several cutoffs per motif, from one scan.
     Scanner.affinity(pwms) -> affinity.AffinityArrays: the likelihood ratio summed over ALL windows of every (motif, region).
     Scanner.affinity_rank_sum(pwms, control) -> enrich.RankSum: rank_sum with that sum in place of the best score.
+    Scanner.expected_counts(pwms, gamma) -> em.ExpectedCounts: per motif column the A, C, G, T weight over ALL windows, each weighted by
+                                            its posterior probability of being the site (the E-step of a motif refinement).
+    Scanner.refine_motifs(pwms, ...) -> em.Refinement: expectation maximisation of the matrices over the regions, without a cutoff.
     Scanner.score_histogram(pwms, ...) -> scoredist.ScoreHistogram: the score distribution of all windows, per motif.
     Scanner.site_base_counts(pwms, ...) -> sitestack.SiteStack: the base counts per motif column over the sites found.
     Scanner.site_signal(pwms, track, ...) -> footprint.SiteSignal: a per-base track summed per motif column over the sites found.
@@ -430,6 +433,35 @@ class Scanner:
                 res.close()
         finally:
             pw.close()
+
+    def expected_counts(self, pwms, gamma=None, scale=1.0, max_n=-1):
+        """The E-step of a motif refinement over this scanner's regions, without a cutoff: an em.ExpectedCounts -- per motif column the
+        A, C, G, T weight under it over ALL windows, every window weighted by its posterior probability of being the site
+        (ms_scan_affinity, then ms_affinity_expected_counts on its handle).  gamma: the fraction of regions that hold a site (ZOOPS);
+        None: one site per region (OOPS).  Honours the scanner's `strand`, as `affinity` does."""
+        from . import affinity, em
+        scale, max_n = affinity.check_args(scale, max_n)
+        prior = em.prior_logit_of(gamma)
+        matrices = [np.asarray(pwm.matrix, dtype=np.float64) for pwm in pwms]
+        pw = _lib.PwmSet.from_matrices(matrices)
+        try:
+            res = self._scan_affinity(pw, scale, max_n)
+            try:
+                return em.ExpectedCounts(*res.expected_counts(pw, self._seqset(), prior), [m.shape[1] for m in matrices])
+            finally:
+                res.close()
+        finally:
+            pw.close()
+
+    def refine_motifs(self, pwms, iters=10, gamma=0.5, update_gamma=True, scale=1.0, max_n=-1, bg=None, pseudo=0.01):
+        """em.refine of the PWMs' matrices over this scanner's regions, on the device: an em.Refinement (the matrices, the gamma values
+        and the log-likelihood trace per iteration).  Honours the scanner's `strand`."""
+        from . import affinity, em
+        scale, max_n = affinity.check_args(scale, max_n)
+        matrices = [np.asarray(pwm.matrix, dtype=np.float64) for pwm in pwms]
+        em.check_gamma(gamma, len(matrices))
+        return em.refine(matrices, self._seqset(), iters=iters, gamma=gamma, update_gamma=update_gamma, strand=_STRAND_FLAG[self.strand], scale=scale,
+                         max_n=max_n, bg=bg, pseudo=pseudo, device=True)
 
     def affinity_rank_sum(self, pwms, control, sel=None, sel_control=None, scale=1.0, max_n=-1):
         """rank_sum with the region's mean likelihood ratio over all windows (affinity's log_mean) in place of its best score: an
