@@ -239,6 +239,26 @@ int ms_debug_counts_dims(int32_t out[8]);
  * is how a test gets one.  Every scan entry point takes it and packs it; free it with ms_seqset_free.  Needs a GPU. */
 int ms_debug_seqset_upload_only(const char *bases, const int64_t *offsets, int64_t n_seqs, ms_seqset **out);
 
+/* The 16 words that follow the code plane and the 16 that follow the mask plane of a built sequence set (a genome handle is one: cast it):
+ * the kernels' window reads run into them, and every way of making a set leaves them zero.  MS_ERR_INVALID for a set whose planes are not
+ * on the device yet.  Needs a GPU. */
+int ms_debug_seqset_pad_words(const ms_seqset *seqs, uint32_t codes_pad[16], uint32_t nmask_pad[16]);
+
+/* What a block holds when the library hands it out. Device working memory, result blocks and pinned host blocks are recycled, and a
+ * recycled block still holds what the previous call left in it; a fresh one holds whatever the driver gives.  byte = 0..255: from now on
+ * every block handed out in this process -- a device allocation, a block of the device cache on a hit and on a miss, a block of the pinned
+ * host cache on a hit and on a miss -- is filled with that byte over its whole granted size before its caller sees it (device blocks: the
+ * device is synchronised, filled and synchronised again, so the fill is complete on every stream).  byte = -1 (the default) turns it off:
+ * the allocation paths then make no call they did not make before.  Anything else is MS_ERR_INVALID.  *previous (may be NULL) = the value
+ * before.  No result depends on it: tests/test_gpu_recycled_memory.py proves that, entry point by entry point, with 0x00, 0xFF and 0xA5.
+ * Set by this call only, never from the environment.  The call itself needs no GPU. */
+int ms_debug_alloc_fill(int32_t byte, int32_t *previous);
+
+/* Give every block of the calling thread's device cache (ms_device_pool_stats) back to the driver, so that the allocations that follow are
+ * misses: a test that wants fresh memory AND recycled memory under ms_debug_alloc_fill gets both in a chosen order.  *bytes (may be
+ * NULL) = the bytes released.  Blocks that handles own are not touched.  Needs a GPU. */
+int ms_debug_pool_trim(uint64_t *bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -236,6 +236,9 @@ def lib():
         "ms_affinity_expected_counts": (c_int, [vp, vp, vp, ctypes.c_double, c_i32, c_i32, c_u32, vp, vp, vp, pd]),
         "ms_debug_expected_dims": (c_int, [pi32]),
         "ms_debug_expected_grid_cap": (c_int, [c_i32]),
+        "ms_debug_alloc_fill": (c_int, [c_i32, pi32]),
+        "ms_debug_seqset_pad_words": (c_int, [vp, pu32, pu32]),
+        "ms_debug_pool_trim": (c_int, [ctypes.POINTER(ctypes.c_uint64)]),
         "ms_debug_key_layout": (c_int, [c_i64, c_i64, c_i64, c_i32, c_i32, pi32, pi32]),
         "ms_scan_score_histogram": (c_int, [vp, vp, c_int, c_u32, pd, pd, c_i32, c_i32, vp, pd]),
         "ms_debug_scorehist_dims": (c_int, [pi32]),
@@ -1276,6 +1279,14 @@ def pool_stats():
 _warned_exact_only = set()
 
 
+def pool_trim():
+    """ms_debug_pool_trim: every cached block of the calling thread's device back to the driver; returns the bytes released.  The
+    allocations that follow are misses.  Tests only."""
+    n = ctypes.c_uint64()
+    check(lib().ms_debug_pool_trim(ctypes.byref(n)))
+    return n.value
+
+
 def _fence_exact_only(res, pwms, flags=0):
     """motifs the pre-filter cannot take -- wider than 63 columns, max_raw <= 0, non-finite entries, a cutoff under the
     quantiser's floor -- are scored in fp64 at EVERY window (exact_tiled_kernel: correct, the reference's arithmetic, the motif's table in LDS --
@@ -1752,6 +1763,19 @@ def expected_grid_cap(blocks):
         check(lib().ms_debug_expected_grid_cap(0))
 
 
+@contextlib.contextmanager
+def alloc_fill(byte):
+    """ms_debug_alloc_fill for the body of a `with`: every device and pinned block the library hands out is filled with `byte` (0..255)
+    over its whole size before its caller sees it; -1 turns the fill off.  The value before is put back at the end.  No result depends on
+    it.  Tests only."""
+    before = ctypes.c_int32(-1)
+    check(lib().ms_debug_alloc_fill(int(byte), ctypes.byref(before)))
+    try:
+        yield before.value
+    finally:
+        check(lib().ms_debug_alloc_fill(before.value, None))
+
+
 def histogram_binning(n_pwms, lo, hi, n_bins):
     """(lo [P], inv_width [P]) of a score histogram: scalars broadcast, inv_width = n_bins / (hi - lo) as one float64 division each.
     Pure numpy."""
@@ -1872,6 +1896,14 @@ def seqset_planes(seqs):
     check(lib().ms_debug_seqset_planes(seqs.h, ptr(codes, ctypes.c_uint32), ptr(nmask, ctypes.c_uint32), ptr(blk2reg, ctypes.c_int32),
                                        ptr(blkinfo, ctypes.c_int32)))
     return codes, nmask, blk2reg, blkinfo
+
+
+def seqset_pad_words(seqs):
+    """ms_debug_seqset_pad_words: (codes_pad [16], nmask_pad [16]) -- the words behind the two planes of a SeqSet or a ResidentGenome as
+    they are on the device.  Every maker of a set leaves them zero."""
+    codes_pad, nmask_pad = np.empty(16, dtype=np.uint32), np.empty(16, dtype=np.uint32)
+    check(lib().ms_debug_seqset_pad_words(seqs.h, ptr(codes_pad, ctypes.c_uint32), ptr(nmask_pad, ctypes.c_uint32)))
+    return codes_pad, nmask_pad
 
 
 def score_rank_budget(elems):

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdarg>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -27,6 +28,23 @@ void set_error(const char *fmt, ...) {
     vsnprintf(buf, sizeof(buf), fmt, ap);
     va_end(ap);
     g_err = buf;
+}
+
+// ------------------------------------------------------------ ms_debug_alloc_fill --
+
+std::atomic<int> g_alloc_fill{-1};
+
+int alloc_fill_device(void *p, size_t bytes, int byte, int device) {
+    int here = -1;
+    hipError_t e = hipGetDevice(&here);
+    const bool move = e == hipSuccess && device >= 0 && device != here;
+    if (e == hipSuccess && move) e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemset(p, byte, bytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (move) (void) hipSetDevice(here);
+    if (e != hipSuccess) { set_error("ms_debug_alloc_fill: filling %zu bytes failed: %s", bytes, hipGetErrorString(e)); return MS_ERR_RUNTIME; }
+    return MS_OK;
 }
 
 // ----------------------------------------------------------------- per-device state --
@@ -88,6 +106,12 @@ int get_ctx(int device, DeviceCtx **out) {
     MS_HIP(hipMalloc(&c->sc.counters, 8 * sizeof(unsigned long long)));
     MS_HIP(hipMalloc(&c->sc.bucket_tab, kBucketTabWords * sizeof(unsigned long long)));
     MS_HIP(hipHostMalloc(&c->sc.h_counters, 8 * sizeof(unsigned long long)));
+    if (const int fill = alloc_fill_setting(); fill >= 0) {      // (not dev_alloc: its out-of-memory path takes g_ctx_mu, held here)
+        // (a fill that fails here is let go: the context stays whole, and the first allocation through dev_alloc reports the device's state)
+        (void) alloc_fill_device(c->sc.counters, 8 * sizeof(unsigned long long), fill, -1);
+        (void) alloc_fill_device(c->sc.bucket_tab, kBucketTabWords * sizeof(unsigned long long), fill, -1);
+        memset(c->sc.h_counters, fill, 8 * sizeof(unsigned long long));
+    }
     {
         size_t mem_free = 0, mem_total = 0;
         if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && mem_total > 0) c->pool.max_bytes = mem_total / 3;
@@ -112,6 +136,7 @@ static uint64_t now_ns() {
 
 int pool_alloc(DeviceCtx *c, size_t bytes, void **out, size_t *got) {
     const size_t want = pool_class(bytes);
+    bool hit = false;
     {
         std::lock_guard<std::mutex> lk(c->pool.mu);
         size_t best = (size_t) -1;
@@ -125,8 +150,15 @@ int pool_alloc(DeviceCtx *c, size_t bytes, void **out, size_t *got) {
             c->pool.bytes -= *got;
             c->pool.free_.erase(c->pool.free_.begin() + (long) best);
             c->pool.n_hit++;
-            return MS_OK;
+            hit = true;
         }
+    }
+    if (hit) {
+        const int fill = alloc_fill_setting();
+        if (fill < 0) return MS_OK;
+        const int rc = alloc_fill_device(*out, *got, fill, c->device);
+        if (rc) { pool_free(c, *out, *got); *out = nullptr; *got = 0; }      // a failed call hands nothing out
+        return rc;
     }
     const uint64_t t0 = now_ns();
     char *p = nullptr;
@@ -153,6 +185,7 @@ static uint64_t g_pin_stats[4] = {0, 0, 0, 0};            // served from the lis
 
 void *pinned_alloc(size_t bytes, size_t *got) {
     const size_t want = pool_class(bytes);
+    void *hit = nullptr;
     {
         std::lock_guard<std::mutex> lk(g_pin_mu);
         for (size_t i = g_pin_free.size(); i-- > 0;)
@@ -161,8 +194,13 @@ void *pinned_alloc(size_t bytes, size_t *got) {
                 *got = want;
                 g_pin_free.erase(g_pin_free.begin() + (long) i);
                 g_pin_stats[0]++;
-                return p;
+                hit = p;
+                break;
             }
+    }
+    if (hit) {
+        if (const int fill = alloc_fill_setting(); fill >= 0) memset(hit, fill, want);
+        return hit;
     }
     void *p = nullptr;
     const uint64_t t0 = now_ns();
@@ -173,6 +211,7 @@ void *pinned_alloc(size_t bytes, size_t *got) {
         g_pin_stats[3] += now_ns() - t0;
     }
     if (!ok) { (void) hipGetLastError(); return nullptr; }
+    if (const int fill = alloc_fill_setting(); fill >= 0) memset(p, fill, want);
     *got = want;
     return p;
 }
@@ -386,6 +425,23 @@ int ms_host_alloc(size_t bytes, void **out) {
 }
 
 void ms_host_free(void *p) { if (p) (void) hipHostFree(p); }
+
+int ms_debug_alloc_fill(int32_t byte, int32_t *previous) {
+    if (byte < -1 || byte > 255) { set_error("byte must be -1 (off) or 0..255"); return MS_ERR_INVALID; }
+    const int before = g_alloc_fill.exchange((int) byte, std::memory_order_relaxed);
+    if (previous) *previous = before;
+    return MS_OK;
+}
+
+// Every cached block of the calling thread's device back to the driver: the allocations that follow are misses (fresh memory).
+int ms_debug_pool_trim(uint64_t *bytes) {
+    DeviceCtx *c;
+    int rc = get_ctx(g_device, &c);
+    if (rc) return rc;
+    const size_t freed = pool_trim_current_device();
+    if (bytes) *bytes = freed;
+    return MS_OK;
+}
 
 // Free the calling thread's device work buffers (they are grow-only otherwise); lets a test
 // exercise the "buffer too small -> grow -> second pass" path deterministically.

@@ -131,6 +131,15 @@ int seqset_create_upload_only(const char *bases, const int64_t *offsets, int64_t
 int seqset_pack_pending(const ms_seqset *s, hipStream_t st);
 int seqset_create_hostpacked(const char *bases, const int64_t *offsets, int64_t n_seqs, int n_threads, void **stage_io, size_t *stage_bytes_io, ms_seqset **out);
 
+// ms_debug_alloc_fill (ms_context.hip; tests only): -1 = off, 0..255 = every block handed out -- by dev_alloc, by pool_alloc on a hit and on
+// a miss, by pinned_alloc on a hit and on a miss -- is filled with that byte over its whole granted size before the caller sees it, so
+// that a test decides what "recycled memory" holds.  Off, it costs the one relaxed load below and no HIP call.
+extern std::atomic<int> g_alloc_fill;
+inline int alloc_fill_setting() { return g_alloc_fill.load(std::memory_order_relaxed); }
+// `bytes` of device memory at p, on `device` (-1: the calling thread's current one), set to `byte`: hipDeviceSynchronize, hipMemset,
+// hipDeviceSynchronize -- the library's streams are non-blocking, and the fill has to be complete on every one of them
+MS_HIDDEN int alloc_fill_device(void *p, size_t bytes, int byte, int device);
+
 template <typename T>
 inline int dev_alloc(T **p, size_t n) {
     *p = nullptr;
@@ -143,6 +152,9 @@ inline int dev_alloc(T **p, size_t n) {
     if (e != hipSuccess) {
         set_error("hipMalloc of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
         return e == hipErrorOutOfMemory ? MS_ERR_NOMEM : MS_ERR_RUNTIME;
+    }
+    if (const int fill = alloc_fill_setting(); fill >= 0) {
+        if (const int rc = alloc_fill_device(*p, n * sizeof(T), fill, -1)) { (void) hipFree(*p); *p = nullptr; return rc; }
     }
     return MS_OK;
 }

@@ -368,16 +368,14 @@ int ms_score_ranks(const ms_pwmset *pwms_c, const ms_seqset *seqs, int strand_ma
     const int32_t batch = (int32_t) std::max<size_t>(1, std::min<size_t>((size_t) pwms->P, budget / R));
     double *d_scores = nullptr, *d_sorted = nullptr, *d_out = nullptr;
     int64_t *d_ranks = nullptr;
-    void *d_tmp = nullptr;
+    unsigned char *d_tmp = nullptr;
     size_t tmp_bytes = 0;
-    auto cleanup = [&]() { dev_free(d_scores); dev_free(d_sorted); dev_free(d_out); dev_free(d_ranks); if (d_tmp) (void) hipFree(d_tmp); };
+    auto cleanup = [&]() { dev_free(d_scores); dev_free(d_sorted); dev_free(d_out); dev_free(d_ranks); dev_free(d_tmp); };
     if ((rc = dev_alloc(&d_scores, (size_t) batch * R)) || (rc = dev_alloc(&d_sorted, R)) ||
         (rc = dev_alloc(&d_out, (size_t) pwms->P * (size_t) n_ranks)) || (rc = dev_alloc(&d_ranks, (size_t) n_ranks))) { cleanup(); return rc; }
     hipError_t he = hipMemcpyAsync(d_ranks, ranks, (size_t) n_ranks * sizeof(int64_t), hipMemcpyHostToDevice, c->stream);
-    if (he == hipSuccess && (rc = sort_doubles_desc(nullptr, &tmp_bytes, d_scores, d_sorted, R, c->stream)) == MS_OK) {
-        he = hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 1);
-        if (he != hipSuccess) { set_error("hipMalloc (sort) failed: %s", hipGetErrorString(he)); rc = MS_ERR_NOMEM; }
-    }
+    if (he == hipSuccess && (rc = sort_doubles_desc(nullptr, &tmp_bytes, d_scores, d_sorted, R, c->stream)) == MS_OK)
+        rc = dev_alloc(&d_tmp, tmp_bytes);
     const DevSeq S = dev_seq(seqs);
     for (int32_t p0 = 0; rc == MS_OK && he == hipSuccess && p0 < pwms->P; p0 += batch) {
         const int32_t n = std::min(batch, pwms->P - p0);

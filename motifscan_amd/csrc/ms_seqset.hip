@@ -498,6 +498,18 @@ int ms_debug_seqset_planes(const ms_seqset *s, uint32_t *codes, uint32_t *nmask,
     return MS_OK;
 }
 
+// the kPadWords words behind each of the two planes of a built set: zero, whichever way the set was made
+int ms_debug_seqset_pad_words(const ms_seqset *s, uint32_t *codes_pad, uint32_t *nmask_pad) {
+    if (!s || !codes_pad || !nmask_pad) { set_error("NULL argument"); return MS_ERR_INVALID; }
+    if (!s->built || s->pack_pending || !s->block) { set_error("the set's planes are not on the device yet (packed by its first scan)"); return MS_ERR_INVALID; }
+    static_assert(kPadWords == 16, "include/motifscan_amd_debug.h promises 16 words per plane");
+    const size_t n_units = (size_t) ((s->n_bases + 31) / 32);
+    MS_HIP(hipSetDevice(s->device));
+    MS_HIP(hipMemcpy(codes_pad, s->d_codes + 2 * n_units, kPadWords * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    MS_HIP(hipMemcpy(nmask_pad, s->d_nmask + n_units, kPadWords * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return MS_OK;
+}
+
 // the two planes of a built set on the host, in ms_genome_create_packed's layout (the public counterpart of ms_genome_packed_host)
 int ms_seqset_packed_host(const ms_seqset *s, uint32_t *codes, uint32_t *nmask) {
     if (!s) { set_error("NULL argument"); return MS_ERR_INVALID; }

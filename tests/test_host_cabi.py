@@ -640,3 +640,39 @@ def test_numa_lookups_against_a_fake_sysfs(tmp_path):
     _lib.check(L.ms_debug_numa_probe(b"", b"0000:00:00.0", ctypes.byref(node), ctypes.byref(n_cpus), ctypes.byref(n_nodes)))
     assert n_nodes.value >= 1 and node.value >= -1
 
+
+
+def test_alloc_fill_hook_checks_its_argument_and_round_trips_without_a_device():
+    """ms_debug_alloc_fill (tests/test_gpu_recycled_memory.py fills every block the library hands out with it): off by default, -1 and
+    0 .. 255 are taken and anything else refused with the setting left as it was, `previous` is the value before (NULL is allowed),
+    the `with` form puts the value before back -- after an exception too -- and neither needs a device."""
+    L = _lib.lib()
+    prev = ctypes.c_int32(99)
+    assert L.ms_debug_alloc_fill(-1, ctypes.byref(prev)) == _lib.MS_OK and prev.value == -1          # the default: off
+    header = open(os.path.join(ROOT, "include", "motifscan_amd_debug.h")).read()
+    assert "int ms_debug_alloc_fill(int32_t byte, int32_t *previous);" in header
+    try:
+        for byte in (0, 0xA5, 255):
+            assert L.ms_debug_alloc_fill(byte, ctypes.byref(prev)) == _lib.MS_OK
+            assert L.ms_debug_alloc_fill(byte, ctypes.byref(prev)) == _lib.MS_OK and prev.value == byte
+        for bad in (-2, 256, -(1 << 31), (1 << 31) - 1):
+            prev.value = 77
+            assert L.ms_debug_alloc_fill(bad, ctypes.byref(prev)) == _lib.MS_ERR_INVALID and prev.value == 77      # nothing written
+            assert b"0..255" in L.ms_last_error()
+        assert L.ms_debug_alloc_fill(-1, ctypes.byref(prev)) == _lib.MS_OK and prev.value == 255     # a refused call changed nothing
+        assert L.ms_debug_alloc_fill(7, None) == _lib.MS_OK                                         # previous may be NULL
+        with _lib.alloc_fill(-1) as before:
+            assert before == 7
+            with _lib.alloc_fill(0xFF) as inner:
+                assert inner == -1
+            with pytest.raises(ValueError):
+                with _lib.alloc_fill(300):
+                    pass
+            with pytest.raises(KeyError):
+                with _lib.alloc_fill(1):
+                    raise KeyError("the body failed")
+            assert L.ms_debug_alloc_fill(-1, ctypes.byref(prev)) == _lib.MS_OK and prev.value == -1
+        assert L.ms_debug_alloc_fill(-1, ctypes.byref(prev)) == _lib.MS_OK and prev.value == 7       # the `with` put 7 back
+    finally:
+        assert L.ms_debug_alloc_fill(-1, None) == _lib.MS_OK
+    assert L.ms_debug_alloc_fill(-1, ctypes.byref(prev)) == _lib.MS_OK and prev.value == -1          # and it ends off
