@@ -116,6 +116,10 @@
  *                         whole genome or a region set: the counts behind a Markov background of order k - 1 (FIMO's --bgfile, HOMER's
  *                         background).  nseq -- the sequences that hold a k-mer at least once, HOMER's way of counting a k-mer's
  *                         enrichment -- has no reference counterpart
+ *   ms_pwmset_score_distribution
+ *                         no reference counterpart: the ANALYTIC distribution of a window's score under a Markov background of order
+ *                         0 .. 5 (FIMO / MOODS / TFM-Pvalue style P-values): from a matrix and a conditional table alone, without a
+ *                         sequence -- the column-by-column convolution of the discretised score over the background's contexts
  */
 #ifndef MOTIFSCAN_AMD_H
 #define MOTIFSCAN_AMD_H
@@ -130,6 +134,7 @@ extern "C" {
 #define MS_ERR_INVALID   1   /* bad argument / shape           -> ValueError   */
 #define MS_ERR_NOMEM     2   /* host or device allocation      -> MemoryError  */
 #define MS_ERR_RUNTIME   3   /* HIP failure, no usable device  -> RuntimeError */
+#define MS_ERR_INTERNAL  4   /* an invariant of the library's own plan does not hold -> RuntimeError */
 
 #define MS_STRAND_FWD    1   /* same bit mask as cscore.c:319 */
 #define MS_STRAND_REV    2
@@ -985,6 +990,57 @@ int ms_seqset_kmer_counts(const ms_seqset *seqs, int32_t k, uint32_t flags, cons
  * is k = 1 without the flag, summed over the chromosomes. */
 int ms_genome_kmer_counts(const ms_genome *genome, int32_t k, uint32_t flags, const uint8_t *sel_chrom /* [n_chroms] or NULL */,
                           int64_t *occ, int64_t *nseq, int64_t *totals, double *device_ms);
+
+/* ---- the analytic score distribution under a Markov background (ms_scoredist.hip) ------------------------------- */
+#define MS_SCOREDIST_MAX_ORDER 5
+#define MS_SCOREDIST_MAX_BINS  (1 << 20)
+/* The distribution of a window's score from the matrix and a background model alone, no sequence: for every motif the probability of
+ * each INTEGER score of a window of W ACGT bases whose `order` preceding bases are distributed as init and whose every base is drawn by
+ * cond.  cond [4^order][4] is the conditional table of the background (row = the code of the last `order` bases, oldest base most
+ * significant: the k-mer code rule of ms_seqset_kmer_counts, so cond is KmerCounts.markov() of the (order + 1)-mer counts); init
+ * [4^order] the distribution of the context in front of the window.  C = 4^order contexts.  Neither is normalised or checked to sum to 1.
+ *
+ * THE SCORE GRID, made on the host in plain fp64, per motif m of width W with entries M[b][c]:
+ *   unscorable   max_raw (get_max_raw_score, cscore.c:36-48) is not a finite number > 0, an entry is NaN or +inf, or a column has no
+ *                finite entry: step[m] = 0, s0[m] = 0 and the row of mass is all +0.0.
+ *   range        over the finite entries only: hi = sum_c max_b M[b][c], lo = sum_c min_b M[b][c], columns in order, one rounded add
+ *                each.  step = (hi - lo) / (n_bins - W - 2) (one subtraction, one divide), or 1.0 when hi == lo.
+ *   entries      q[b][c] = (int64) floor(M[b][c] / step): one rounded divide, then floor.  An entry of -inf is ABSENT: the mass that
+ *                would pass through it is dropped.  s0 = sum_c min_b q[b][c] and d[b][c] = q[b][c] - min_b' q[b'][c] >= 0 (the minima
+ *                over the column's present entries).
+ *   fit          sum_c max_b d[b][c] < n_bins follows from the choice of step; the plan asserts it and the call returns
+ *                MS_ERR_INTERNAL where it does not hold (entries so large against their range that q leaves the int64 range).
+ *   strand 2     the same q, d, step and s0, run through the columns of M'[b][c] = M[3 - b][W - 1 - c].
+ *
+ * THE RECURRENCE, over arrays [C][n_bins] of doubles: old[ctx][0] = init[ctx], every other entry +0.0.  For each column c = 0 .. W - 1,
+ * each new context x and each i in [0, n_bins), with b = x & 3 and the predecessors p_a = a * 4^(order - 1) + (x >> 2), a = A, C, G, T:
+ *     new[x][i] = ((t_A + t_C) + t_G) + t_T,     t_a = old[p_a][i - d[b][c]] * cond[p_a][b],
+ * t_a = +0.0 where i - d[b][c] < 0 or the entry (b, c) is absent.  At order 0 there is one context and the four terms run over
+ * b = A, C, G, T, each with its own shift: t_b = old[0][i - d[b][c]] * cond[0][b].  Every product and every sum is ONE IEEE fp64
+ * operation (no FMA).  mass[m][i] = the sum of the last column's new[x][i] over x = 0 .. C - 1, left to right: the probability that the
+ * window's integer score sum_c q[b_c][c] is s0[m] + i.  1 - the row's sum is the probability of a score of -inf.  Every element is this
+ * expression whatever path, tile, batch or budget computes it: the same bytes on every run, and the bytes of the Python restatement
+ * (motifscan_amd.pvalues.restate_distribution).
+ *
+ * How a raw sum R of the scan (fp64, columns in order) relates to the integer score S of the same window: step (S - 1) <= R <=
+ * step (S + W + 1) for every n_bins up to MS_SCOREDIST_MAX_BINS (DESIGN.md 4 has the proof), which is what P-value bounds and
+ * conservative cutoffs are made of (motifscan_amd/pvalues.py).
+ *
+ * Two paths, the same bytes: a motif whose two buffers (2 C n_bins 8 bytes) fit the LDS of a CU runs all its columns in ONE launch,
+ * one block per motif; otherwise the buffers lie in pooled device scratch and every column is one launch over all motifs of a batch,
+ * followed by one launch for the context sum.  The motifs are taken in batches whose buffers fit a work budget (256 MiB; on either
+ * path, so that the status does not depend on the path).
+ *
+ * step, s0: [P] host.  mass: [P][n_bins] doubles, host memory or device memory of the calling thread's device (ms_set_device), written
+ * under the stream rule ms_scan_score_histogram documents.  device_ms (may be NULL): first launch -> last kernel done.  P = 0 is valid.
+ * MS_ERR_RUNTIME ("no CPU fallback") without a device, before anything else is looked at.  MS_ERR_INVALID: NULL handles or arrays, strand
+ * outside {1, 2}, order outside [0, MS_SCOREDIST_MAX_ORDER], n_bins outside [max_width + 3, MS_SCOREDIST_MAX_BINS], a cond or init entry
+ * that is negative or not finite, a device mass on another device.  MS_ERR_NOMEM, with nothing launched, when one motif's two buffers do
+ * not fit the work budget. */
+int ms_pwmset_score_distribution(const ms_pwmset *pwms, int strand /* 1 forward, 2 reverse */, int32_t order,
+                                 const double *cond /* [4^order][4] host */, const double *init /* [4^order] host */,
+                                 int32_t n_bins, double *step /* [P] host */, int64_t *s0 /* [P] host */,
+                                 double *mass /* [P][n_bins], host or device */, double *device_ms /* or NULL */);
 
 #ifdef __cplusplus
 }

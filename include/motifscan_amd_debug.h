@@ -234,6 +234,19 @@ int ms_debug_kmer_bitmap_budget(int64_t bytes, int64_t *previous);
  * Tests size their boundary cases from here.  Needs no GPU. */
 int ms_debug_counts_dims(int32_t out[8]);
 
+/* The path constants of ms_pwmset_score_distribution, as constants of the build: out[0] the threads of a block of the global path's
+ * kernels; out[1] the bins of one block tile of the global path; out[2] the largest C x n_bins (contexts x bins) the LDS path takes -- both
+ * buffers of such a motif fit the 160 KiB of LDS of a gfx950 CU; out[3] the default work budget in MiB.  Tests size their boundary cases
+ * from here.  Needs no GPU. */
+int ms_debug_scoredist_dims(int32_t out[4]);
+/* The motifs of a score distribution are taken in batches of (budget / (2 C n_bins 8), none: MS_ERR_NOMEM) motifs: bytes > 0 sets the
+ * budget for the calls that follow in this process, 0 gives it back to the library.  *previous (may be NULL) = the value before.  The
+ * result does not depend on it.  Needs no GPU. */
+int ms_debug_scoredist_budget(int64_t bytes, int64_t *previous);
+/* on != 0: the calls that follow in this process take the global path even where the LDS path applies; 0 gives the choice back to the
+ * library.  *previous (may be NULL) = the value before.  The result does not depend on it.  Needs no GPU. */
+int ms_debug_scoredist_force_global(int32_t on, int32_t *previous);
+
 /* A set as a batch stream's upload stage leaves it: ASCII and offsets in HBM, the planes still to be packed by its first scan.  The entry
  * points that read the planes directly (ms_seqset_kmer_counts, ms_seqset_shuffle, ms_seqset_packed_host) refuse it with MS_ERR_INVALID: this
  * is how a test gets one.  Every scan entry point takes it and packs it; free it with ms_seqset_free.  Needs a GPU. */

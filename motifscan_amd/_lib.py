@@ -18,6 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmotifscan_amd.so")
 
 MS_OK, MS_ERR_INVALID, MS_ERR_NOMEM, MS_ERR_RUNTIME = 0, 1, 2, 3
+MS_ERR_INTERNAL = 4
 MS_SCAN_DEFAULT, MS_SCAN_EXACT_ONLY, MS_SCAN_COUNTS_ONLY = 0, 1, 2
 MS_STREAM_DEDUP, MS_STREAM_NO_HITS, MS_STREAM_EXACT_ONLY, MS_STREAM_PACKED, MS_STREAM_HOST_PACK, MS_STREAM_PACKED12 = 1, 2, 4, 8, 16, 32
 MS_PROFILE_UNSMOOTHED = 1
@@ -262,6 +263,10 @@ def lib():
         "ms_debug_kmer_bitmap_budget": (c_int, [c_i64, pi64]),
         "ms_debug_counts_dims": (c_int, [pi32]),
         "ms_debug_seqset_upload_only": (c_int, [ctypes.c_char_p, pi64, c_i64, pvp]),
+        "ms_pwmset_score_distribution": (c_int, [vp, c_int, c_i32, pd, pd, c_i32, pd, pi64, vp, pd]),
+        "ms_debug_scoredist_dims": (c_int, [pi32]),
+        "ms_debug_scoredist_budget": (c_int, [c_i64, pi64]),
+        "ms_debug_scoredist_force_global": (c_int, [c_i32, pi32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1818,6 +1823,63 @@ def scorehist_dims():
     out = np.zeros(4, dtype=np.int32)
     check(lib().ms_debug_scorehist_dims(ptr(out, ctypes.c_int32)))
     return dict(zip(("segment_windows", "tile_max_width", "lds_slots", "flush_windows"), out.tolist()))
+
+
+MS_SCOREDIST_MAX_ORDER, MS_SCOREDIST_MAX_BINS = 5, 1 << 20
+
+
+def score_distribution(pwms, strand, order, cond, init, n_bins, out=None, timing=None):
+    """ms_pwmset_score_distribution: (mass float64 [P][n_bins], step float64 [P], s0 int64 [P]) -- per motif the probability of every
+    integer score s0 + i of a window under the Markov background (cond [4^order][4], init [4^order]); the definition is in
+    include/motifscan_amd.h and motifscan_amd.pvalues.restate_distribution restates it.  strand: 1 forward, 2 reverse.  out: a float64
+    numpy array (P, n_bins), or None (a new one); the device pointer of a torch tensor may be passed as an int instead (then it is
+    returned).  timing: a dict that receives 'device_ms'.  The library checks every argument."""
+    n_bins, order = int(n_bins), int(order)
+    n_ctx = 4 ** order if 0 <= order <= MS_SCOREDIST_MAX_ORDER else 1          # (an invalid order: the library refuses it before it reads)
+    cond = np.ascontiguousarray(cond, dtype=np.float64)
+    init = np.ascontiguousarray(init, dtype=np.float64)
+    if cond.size != 4 * n_ctx or init.size != n_ctx:
+        raise ValueError(f"cond must hold {n_ctx} x 4 entries and init {n_ctx}")
+    shape = (pwms.n, max(n_bins, 0))
+    if isinstance(out, int):
+        dst = out
+    else:
+        if out is None:
+            out = np.zeros(shape, dtype=np.float64)
+        if out.dtype != np.float64 or out.shape != shape or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous float64 array of shape (P, n_bins)")
+        dst = out.ctypes.data
+    step, s0 = np.zeros(pwms.n, dtype=np.float64), np.zeros(pwms.n, dtype=np.int64)
+    ms = ctypes.c_double()
+    check(lib().ms_pwmset_score_distribution(pwms.h, int(strand), order, ptr(cond, ctypes.c_double), ptr(init, ctypes.c_double), n_bins,
+                                             ptr(step, ctypes.c_double), ptr(s0, ctypes.c_int64), ctypes.c_void_p(dst), ctypes.byref(ms)))
+    if timing is not None:
+        timing["device_ms"] = ms.value
+    return out, step, s0
+
+
+def scoredist_dims():
+    """ms_debug_scoredist_dims: dict(threads, tile_bins, lds_elems, budget_mib) -- the sizes at which ms_pwmset_score_distribution changes
+    path: the bins per block of the global path, and the largest contexts x bins the LDS path takes.  Constants of the build; no device."""
+    out = np.zeros(4, dtype=np.int32)
+    check(lib().ms_debug_scoredist_dims(ptr(out, ctypes.c_int32)))
+    return dict(zip(("threads", "tile_bins", "lds_elems", "budget_mib"), out.tolist()))
+
+
+def scoredist_budget(nbytes):
+    """ms_debug_scoredist_budget: the bytes of ping-pong buffers a score distribution holds at once for the calls that follow (0 = the
+    library's own); returns the value before."""
+    prev = ctypes.c_int64()
+    check(lib().ms_debug_scoredist_budget(int(nbytes), ctypes.byref(prev)))
+    return prev.value
+
+
+def scoredist_force_global(on):
+    """ms_debug_scoredist_force_global: the calls that follow take the global path even where the LDS path applies (False gives the
+    choice back); returns the value before."""
+    prev = ctypes.c_int32()
+    check(lib().ms_debug_scoredist_force_global(1 if on else 0, ctypes.byref(prev)))
+    return bool(prev.value)
 
 
 def best_segment_windows():

@@ -507,6 +507,16 @@ class Scanner:
             pw.close()
         return scoredist.ScoreHistogram.from_range(counts, lo, hi, n_bins)
 
+    def score_distribution(self, pwms, order=0, n_bins=65536, pseudocount=1.0):
+        """The ANALYTIC score distribution of the motifs under a Markov background of `order` counted on the scanner's own regions, as a
+        pvalues.ScoreDistribution (ms_seqset_kmer_counts for the (order + 1)-mer counts, ms_pwmset_score_distribution for the
+        distribution; the scanner's `strand`).  No window of the regions is scored: .p_value_bounds gives the P-value of a site,
+        .cutoffs conservative cutoffs, from the matrix and the background alone."""
+        from . import pvalues
+        cond, init = pvalues.background_from_counts(self.kmer_counts(int(order) + 1, canonical=False), pseudocount)
+        matrices = [np.asarray(pwm.matrix, dtype=np.float64) for pwm in pwms]
+        return pvalues.score_distribution(matrices, cond, init, n_bins, _STRAND_FLAG[self.strand])
+
     def site_base_counts(self, pwms, flank=0, dinuc=False):
         """What the sites of a scan look like, as a sitestack.SiteStack: per motif and per column of the motif, with `flank` columns
         either side, how many sites have A, C, G, T there in the motif's orientation, a non-ACGT base, or lie outside the region there
