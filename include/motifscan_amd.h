@@ -120,6 +120,8 @@
  *                         no reference counterpart: the ANALYTIC distribution of a window's score under a Markov background of order
  *                         0 .. 5 (FIMO / MOODS / TFM-Pvalue style P-values): from a matrix and a conditional table alone, without a
  *                         sequence -- the column-by-column convolution of the discretised score over the background's contexts
+ *   ms_motifs_compare     no reference counterpart: two motif sets compared with each other, matrix against matrix (Tomtom) -- per pair
+ *                         the best ungapped alignment in both orientations and its P-value under a null of the target set's own columns
  */
 #ifndef MOTIFSCAN_AMD_H
 #define MOTIFSCAN_AMD_H
@@ -1041,6 +1043,67 @@ int ms_pwmset_score_distribution(const ms_pwmset *pwms, int strand /* 1 forward,
                                  const double *cond /* [4^order][4] host */, const double *init /* [4^order] host */,
                                  int32_t n_bins, double *step /* [P] host */, int64_t *s0 /* [P] host */,
                                  double *mass /* [P][n_bins], host or device */, double *device_ms /* or NULL */);
+
+/* ---- motif sets compared with each other: best alignment and P-value per pair (ms_compare.hip) ------------------- */
+#define MS_COMPARE_PEARSON 0
+#define MS_COMPARE_SW      1      /* Sandelin-Wasserman: 2 - sum of squared differences */
+#define MS_COMPARE_ED      2      /* minus the Euclidean distance */
+#define MS_COMPARE_MAX_WIDTH 64
+#define MS_COMPARE_MAX_BINS  256
+/* Which target motif does a query motif resemble, at which offset and in which orientation, and how likely is so good a match by
+ * chance: the Tomtom procedure (Gupta et al., Genome Biology 2007).  Every ungapped alignment of the two matrices is scored column
+ * against column, each alignment score becomes a P-value under a null built from the target set's own columns, the best alignment is
+ * kept.  q_values / t_values are the matrices concatenated, each row-major [4][width] with rows A, C, G, T (ms_pwmset_create's layout):
+ * probability columns, but nothing is checked beyond "finite".
+ *
+ * THE COLUMNS AS THE DEVICE SEES THEM, prepared on the host in plain fp64, one rounded operation per step.  For a column x:
+ *   pearson   mean = (((x0 + x1) + x2) + x3) * 0.25;  c_b = x_b - mean;  n = sqrt(((c0 c0 + c1 c1) + c2 c2) + c3 c3);  u_b = c_b / n, or all
+ *             +0.0 where n > 0 does not hold
+ *   sw, ed    u = x
+ * The REVERSE orientation of a target is made from the prepared vectors: column j of the reversed target is prepared column Wt - 1 - j
+ * with its four entries in reverse order.  (Not "prepare the reverse complement": the order of the mean's additions would differ.)
+ *
+ * THE COLUMN SCORE, on the device, every product, sum, difference and square root one IEEE fp64 operation (no FMA), for a query vector u
+ * and a target vector v:
+ *   pearson   g = ((u0 v0 + u1 v1) + u2 v2) + u3 v3
+ *   sw, ed    d_b = u_b - v_b;  ssd = ((d0 d0 + d1 d1) + d2 d2) + d3 d3;  sw: g = 2.0 - ssd;  ed: g = -sqrt(ssd), correctly rounded
+ * and the integer score k = (int) floor((g - lo) * scale), clamped to [0, bins - 1] (a NaN gives 0), with the host doubles
+ *   pearson lo = -1.0, scale = bins * 0.5;   sw lo = 0.0, scale = bins * 0.5;   ed lo = -sqrt(2.0), scale = bins / sqrt(2.0).
+ *
+ * THE NULL OF ONE QUERY COLUMN i: H_i[k] = the number of target columns c with score(i, c) = k, over all sum Wt forward columns of the
+ * whole target set, and over their reversed forms as well when orientations == 3; N is that number of columns (sum Wt <= 2^30), H exact
+ * uint32.  f_i[k] = (double) H_i[k] * invN with invN = 1.0 / (double) N made on the host: one multiply.
+ *
+ * THE TABLES OF ONE QUERY of width W: for every start a and length L with a + L <= W, over the scores s in [0, L (bins - 1)],
+ *   pm_{a,1} = f_a
+ *   pm_{a,L}[s] = the sum over k = 0 .. bins - 1 with 0 <= s - k <= (L - 1)(bins - 1) of pm_{a,L-1}[s - k] * f_{a+L-1}[k], the terms in
+ *                 ascending k, each product and each sum one rounded operation, starting from +0.0
+ *   tail_{a,L}[top] = pm_{a,L}[top],  tail_{a,L}[s] = tail_{a,L}[s + 1] + pm_{a,L}[s]: summed from the top down, sequentially.
+ * They depend on the query and on the whole target set, not on q0, q1, batches or paths.
+ *
+ * THE ALIGNMENT of query q (width Wq) and target t (width Wt): offset o runs over [-(Wt - 1), Wq - 1]; target column j lies under query
+ * column i = j + o; the overlap is a = max(0, o) to e = min(Wq, Wt + o), L = e - a; an alignment is admissible when
+ * L >= min(min_overlap, Wq, Wt).  S = the sum of the L integer column scores, p = tail_{a,L}[S].  Over all admissible (orientation, o)
+ * the least key (p, -L, orientation [forward first], o) is kept.  Per pair: p_min the kept p (the table's bytes), offset the kept o,
+ * overlap the kept L, score the kept S, orient 0 forward / 1 reverse, n_offsets the number of admissible alignments (always >= 1).  The
+ * correction 1 - (1 - p_min)^n_offsets, E-values and q-values are host arithmetic (motifscan_amd/compare.py).
+ *
+ * The six outputs are host planes [(q1 - q0)][n_t] for the queries [q0, q1).  Every element is the expressions above whatever tile or
+ * batch computes it: the same bytes on every run, and the bytes of the Python restatement (motifscan_amd.compare.restate_compare).  The
+ * queries are taken in batches whose tables fit a work budget (256 MiB); a query of width W holds sum over n = 1 .. W of
+ * ((bins - 1) n (n + 1) / 2 + n) doubles, 89 MiB at the caps.  device_ms (may be NULL): first launch -> last kernel done.
+ *
+ * MS_ERR_RUNTIME ("no CPU fallback") without a device, before anything else is looked at.  MS_ERR_INVALID: NULL arrays where a count is
+ * non-zero, a negative count, a width outside [1, MS_COMPARE_MAX_WIDTH], an entry that is not finite, a metric outside 0..2, bins outside
+ * [2, MS_COMPARE_MAX_BINS], min_overlap < 1, orientations not 1 or 3, q0 < 0, q1 > n_q or q0 > q1, sum Wt > 2^30 (or more than 2^30 query
+ * columns in [q0, q1)).  n_q == 0, n_t == 0 and q0 == q1 are valid and write nothing.  MS_ERR_NOMEM, with nothing launched, if one
+ * query's tables do not fit the work budget.  No status writes to the outputs. */
+int ms_motifs_compare(const double *q_values, const int32_t *q_widths, int32_t n_q,
+                      const double *t_values, const int32_t *t_widths, int32_t n_t,
+                      int metric, int32_t bins, int32_t min_overlap, int orientations /* 1 forward, 3 both */,
+                      int32_t q0, int32_t q1,
+                      double *p_min, int32_t *offset, int32_t *overlap, int32_t *score, int32_t *n_offsets, int8_t *orient,
+                      double *device_ms /* or NULL */);
 
 #ifdef __cplusplus
 }

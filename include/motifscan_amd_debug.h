@@ -247,6 +247,22 @@ int ms_debug_scoredist_budget(int64_t bytes, int64_t *previous);
  * library.  *previous (may be NULL) = the value before.  The result does not depend on it.  Needs no GPU. */
 int ms_debug_scoredist_force_global(int32_t on, int32_t *previous);
 
+/* The path constants of ms_motifs_compare, as constants of the build: out[0] the threads of a block of its three kernels; out[1] the target
+ * columns of one tile of the histogram kernel; out[2] the targets of one block of the alignment kernel; out[3] the default work budget
+ * in MiB; out[4] the most queries of one batch; out[5] the most histogram tiles side by side in a grid (a block takes further tiles that
+ * far apart); out[6] the largest W x bins of an LDS-resident tables variant: 0, there is none; out[7] reserved, 0.  Tests size their
+ * boundary cases from here.  Needs no GPU. */
+int ms_debug_compare_dims(int32_t out[8]);
+/* The queries of a comparison are taken in batches whose tables fit a budget (a query whose tables do not fit alone: MS_ERR_NOMEM):
+ * bytes > 0 sets the budget for the calls that follow in this process, 0 gives it back to the library.  *previous (may be NULL) = the
+ * value before.  The result does not depend on it.  Needs no GPU. */
+int ms_debug_compare_budget(int64_t bytes, int64_t *previous);
+/* The null of one query as ms_motifs_compare builds it from the same inputs: H uint32 [Wq][bins], and tail, all tables of the query flat
+ * in (start a ascending, length L ascending) order, L (bins - 1) + 1 doubles each.  Statuses as ms_motifs_compare's; also
+ * MS_ERR_INVALID for a query outside [0, n_q), for n_t < 1 and for NULL outputs.  Needs a GPU. */
+int ms_debug_compare_null(const double *q_values, const int32_t *q_widths, int32_t n_q, const double *t_values, const int32_t *t_widths,
+                          int32_t n_t, int metric, int32_t bins, int orientations, int32_t query, uint32_t *H, double *tail);
+
 /* A set as a batch stream's upload stage leaves it: ASCII and offsets in HBM, the planes still to be packed by its first scan.  The entry
  * points that read the planes directly (ms_seqset_kmer_counts, ms_seqset_shuffle, ms_seqset_packed_host) refuse it with MS_ERR_INVALID: this
  * is how a test gets one.  Every scan entry point takes it and packs it; free it with ms_seqset_free.  Needs a GPU. */

@@ -267,6 +267,10 @@ def lib():
         "ms_debug_scoredist_dims": (c_int, [pi32]),
         "ms_debug_scoredist_budget": (c_int, [c_i64, pi64]),
         "ms_debug_scoredist_force_global": (c_int, [c_i32, pi32]),
+        "ms_motifs_compare": (c_int, [pd, pi32, c_i32, pd, pi32, c_i32, c_int, c_i32, c_i32, c_int, c_i32, c_i32, pd, pi32, pi32, pi32, pi32, pi8, pd]),
+        "ms_debug_compare_dims": (c_int, [pi32]),
+        "ms_debug_compare_budget": (c_int, [c_i64, pi64]),
+        "ms_debug_compare_null": (c_int, [pd, pi32, c_i32, pd, pi32, c_i32, c_int, c_i32, c_int, c_i32, pu32, pd]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1880,6 +1884,79 @@ def scoredist_force_global(on):
     prev = ctypes.c_int32()
     check(lib().ms_debug_scoredist_force_global(1 if on else 0, ctypes.byref(prev)))
     return bool(prev.value)
+
+
+MS_COMPARE_PEARSON, MS_COMPARE_SW, MS_COMPARE_ED = 0, 1, 2
+MS_COMPARE_MAX_WIDTH, MS_COMPARE_MAX_BINS = 64, 256
+COMPARE_PLANES = (("p_min", np.float64), ("offset", np.int32), ("overlap", np.int32), ("score", np.int32), ("n_offsets", np.int32), ("orient", np.int8))
+
+
+def _flat_set(values, widths):
+    """(values float64 [sum 4 W], widths int32 [n]) contiguous, with the one check the library cannot make: the two agree in size."""
+    values = np.ascontiguousarray(values, dtype=np.float64).ravel()
+    widths = np.ascontiguousarray(widths, dtype=np.int32).ravel()
+    if values.size != 4 * int(widths.astype(np.int64).sum()):
+        raise ValueError("values must hold 4 * width doubles per matrix")
+    return values, widths
+
+
+def compare_motifs(q_values, q_widths, t_values, t_widths, metric=MS_COMPARE_PEARSON, bins=100, min_overlap=5, orientations=3, q0=0, q1=None,
+                   timing=None):
+    """ms_motifs_compare: dict of the six host planes [(q1 - q0)][n_t] -- p_min float64, offset, overlap, score, n_offsets int32, orient
+    int8 -- of the queries [q0, q1) against all targets; the definition is in include/motifscan_amd.h and
+    motifscan_amd.compare.restate_compare restates it.  values / widths: the matrices concatenated, row-major [4][W] each
+    (MotifSet.flat()).  timing: a dict to whose 'device_ms' this call's is ADDED (a caller that tiles the queries gets the sum).  The
+    library checks every argument."""
+    q_values, q_widths = _flat_set(q_values, q_widths)
+    t_values, t_widths = _flat_set(t_values, t_widths)
+    n_q, n_t = len(q_widths), len(t_widths)
+    q1 = n_q if q1 is None else int(q1)
+    rows = max(q1 - int(q0), 0)
+    out = {name: np.zeros((rows, n_t), dtype=dt) for name, dt in COMPARE_PLANES}
+    ms = ctypes.c_double()
+    check(lib().ms_motifs_compare(ptr(q_values, ctypes.c_double), ptr(q_widths, ctypes.c_int32), n_q, ptr(t_values, ctypes.c_double),
+                                  ptr(t_widths, ctypes.c_int32), n_t, int(metric), int(bins), int(min_overlap), int(orientations), int(q0), q1,
+                                  ptr(out["p_min"], ctypes.c_double), ptr(out["offset"], ctypes.c_int32), ptr(out["overlap"], ctypes.c_int32),
+                                  ptr(out["score"], ctypes.c_int32), ptr(out["n_offsets"], ctypes.c_int32), ptr(out["orient"], ctypes.c_int8),
+                                  ctypes.byref(ms)))
+    if timing is not None:
+        timing["device_ms"] = timing.get("device_ms", 0.0) + ms.value
+    return out
+
+
+def compare_dims():
+    """ms_debug_compare_dims: dict(threads, hist_tile, align_tile, budget_mib, batch_cap, hist_grid_y, lds_limit) -- the sizes at which
+    ms_motifs_compare changes tile or batch (lds_limit 0: the tables have one path).  Constants of the build; no device."""
+    out = np.zeros(8, dtype=np.int32)
+    check(lib().ms_debug_compare_dims(ptr(out, ctypes.c_int32)))
+    return dict(zip(("threads", "hist_tile", "align_tile", "budget_mib", "batch_cap", "hist_grid_y", "lds_limit"), out.tolist()))
+
+
+def compare_budget(nbytes):
+    """ms_debug_compare_budget: the bytes of tables a comparison holds at once for the calls that follow (0 = the library's own); returns
+    the value before."""
+    prev = ctypes.c_int64()
+    check(lib().ms_debug_compare_budget(int(nbytes), ctypes.byref(prev)))
+    return prev.value
+
+
+def compare_null(q_values, q_widths, t_values, t_widths, metric, bins, orientations, query):
+    """ms_debug_compare_null: (H uint32 [Wq][bins], tail float64 flat: every table of the query in (a ascending, L ascending) order) as
+    ms_motifs_compare builds them for query `query`.  Tests only."""
+    q_values, q_widths = _flat_set(q_values, q_widths)
+    t_values, t_widths = _flat_set(t_values, t_widths)
+    query, bins = int(query), int(bins)
+    W = int(q_widths[query]) if 0 <= query < len(q_widths) else 1
+    if not (1 <= W <= MS_COMPARE_MAX_WIDTH and 2 <= bins <= MS_COMPARE_MAX_BINS):      # (the library refuses these before it writes)
+        W, bins_h = 1, 1
+    else:
+        bins_h = bins
+    n_tail = sum((bins_h - 1) * n * (n + 1) // 2 + n for n in range(1, W + 1))
+    H, tail = np.zeros((W, bins_h), dtype=np.uint32), np.zeros(n_tail, dtype=np.float64)
+    check(lib().ms_debug_compare_null(ptr(q_values, ctypes.c_double), ptr(q_widths, ctypes.c_int32), len(q_widths), ptr(t_values, ctypes.c_double),
+                                      ptr(t_widths, ctypes.c_int32), len(t_widths), int(metric), bins, int(orientations), query,
+                                      ptr(H, ctypes.c_uint32), ptr(tail, ctypes.c_double)))
+    return H, tail
 
 
 def best_segment_windows():

@@ -305,7 +305,8 @@ def refine(mats, seqs, iters=10, gamma=0.5, update_gamma=True, strand=3, scale=1
     """Expectation maximisation of every matrix of `mats` on its own (ZOOPS; gamma=None: OOPS) over the regions `seqs` (a list of str,
     or with device=True a _lib.SeqSet): per iteration scan_affinity, expected_counts, m_step, and with update_gamma gamma <- the
     occupancy clipped to [1e-4, 1 - 1e-4].  Every motif runs with its own gamma, so the expected counts are asked for one motif row at
-    a time (a row's bytes do not depend on the range).  device=False runs the same loop over affinity_host and expected_counts_host."""
+    a time (a row's bytes do not depend on the range).  device=False runs the same loop over affinity_host and expected_counts_host.
+    Which known motif a refined matrix resembles: compare.compare (the matrices as a 'ppm' MotifSet against a library)."""
     if strand not in (1, 2, 3):
         raise ValueError("invalid strand mask")
     scale, max_n = affinity.check_args(scale, max_n)

@@ -175,6 +175,12 @@ class MotifSet:
             sq.close()
             pw.close()
 
+    def compare(self, targets, **kw):
+        """compare.compare(self, targets, **kw): every motif of this set against every motif of `targets` on the GPU (`ms_motifs_compare`) --
+        best alignment and P-value per pair, a compare.Comparison."""
+        from . import compare
+        return compare.compare(self, targets, **kw)
+
 
 class Motif:
     """Motif i of a set: the attribute surface the scanner, the writers and the reference's call sites read."""
