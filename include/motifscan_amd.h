@@ -81,7 +81,10 @@
  *   ms_scan_best / ms_best_*
  *                         no reference counterpart: the maximum of cscore.c:336-390 over a region -- the best-scoring window of every
  *                         (motif, region) cell, the dense score matrix behind "max motif score per peak"
- *   ms_result_cooccurrence    no reference counterpart: the motif x motif matrix of "regions that hold a site of both", reduced on the
+ *   ms_dimodelset_* / ms_scan_best_dimodels
+ *                         no reference counterpart: the same best-site matrix for FIRST-ORDER models, whose column scores depend on the
+ *                         base of the column before (dinucleotide weight matrices, first-order BaMMs, TFFMs) -- into the same ms_best handle
+ *   ms_result_cooccurrence   no reference counterpart: the motif x motif matrix of "regions that hold a site of both", reduced on the
  *                         device from the hit arrays a result holds (has-site bit rows, a tiled popcount product)
  *   ms_result_pair_spacing    no reference counterpart: for one anchor motif against every partner motif, the histogram of the
  *                         centre-to-centre distances of their sites in the same region by relative orientation (SpaMo-style spacing)
@@ -572,6 +575,48 @@ int  ms_best_sites_device(const ms_best *b, void **d_score, void **d_pos, void *
 /* Device time of the call that made the result: first launch -> last kernel done (HIP events on the library's stream). */
 int  ms_best_device_ms(const ms_best *b, double *ms);
 void ms_best_free(ms_best *b);
+
+/* ---- first-order models: the best-scoring window of every (model, region) cell (ms_dimodel.hip) ---------------------- */
+/* A FIRST-ORDER MODEL of width W >= 1 is values[W][16] of fp64, bases coded A, C, G, T = 0 .. 3.  Row 0 holds start[b] = values[0][b] for
+ * b = 0 .. 3 (its entries 4 .. 15 are never read); row j >= 1 holds trans[j][4 a + b], the score of base b at column j given base a at
+ * column j - 1.  For a window with the bases x_0 .. x_{W-1}, all of them ACGT (lower case included, as everywhere):
+ *     forward raw sum   S+ = 0.0; S+ += start[x_0]; then S+ += trans[j][4 x_{j-1} + x_j] for j = 1, .., W - 1 in that order;
+ *     reverse raw sum   with y_j = 3 - x_{W-1-j}, the window read on the other strand: S- = 0.0; S- += trans[j][4 y_{j-1} + y_j] for
+ *                       j = W - 1 down to 1 in that order; S- += start[y_0] last.
+ * The reverse order is model columns descending, that is genome columns ascending: the order in which ms_scan adds its reverse terms
+ * (M[3 - b][W - 1 - c] at step c).  A model with trans[j][4 a + b] = M[b][j] and start[b] = M[b][0] therefore gives ms_scan_best's raw
+ * sums of M on both strands, bit for bit, on a window without a non-ACGT base.  Every "+=" is one rounded IEEE fp64 addition.
+ * A window that holds ANY non-ACGT base has no score and never wins.  This departs from the PWM walks, where such a base adds +0.0, on
+ * purpose: a pair term with an unknown neighbour has no sensible value.
+ *     max_raw   the Viterbi maximum in the same arithmetic: v_0[b] = start[b]; v_j[b] = max over a of (v_{j-1}[a] + trans[j][4 a + b]);
+ *               max_raw = max over b of v_{W-1}[b].  A rounded addition is monotone, so this IS the greatest forward raw sum over all
+ *               4^W windows, and the best possible site scores exactly 1.0.
+ *     score     raw / max_raw, one IEEE fp64 divide.
+ * The BEST SITE of a cell is ms_scan_best's: the windows pos = 0 .. L - W are walked pos ascending, '+' before '-', over the strands of
+ * strand_mask, from best = -inf, a window replacing the best iff its score is GREATER -- ties keep the earlier window, -inf never wins.  A
+ * cell without a winner (L < W, a non-ACGT base or a forbidden transition in every window) holds score = NaN, pos = -1, strand = 0.
+ * A model is SCORABLE iff max_raw is a finite number > 0 and no entry that is read is NaN or +inf; entries of -inf are allowed and mean a
+ * forbidden transition (the window's raw sum is -inf).  Every cell of an unscorable model holds the no-winner triple.
+ *
+ * ms_dimodelset_create copies values (the models' [W][16] rows one after the other) and widths[n_models]; it needs no device, and a model
+ * set is not bound to one: the scan uploads the set's tables to the sequence set's device per call (4 (4 W - 3) entries of 16 bytes per
+ * model), so there is no "handles on different devices" error, as in ms_scan_best.  MS_ERR_INVALID: out NULL, n_models < 0, NULL arrays
+ * with n_models > 0, a width < 1, a width above the cap ms_debug_dimodel_dims reports (256: the widest model whose table fits one LDS
+ * tile).  ms_dimodelset_max_raw writes max_raw[n_models], whether a model is scorable or not.
+ *
+ * ms_scan_best_dimodels returns an ordinary ms_best with n_pwms = the number of models: ms_best_shape, ms_best_sites,
+ * ms_best_sites_device, ms_best_device_ms, ms_best_rank_sum, ms_best_count_passing and ms_best_free take it as they take ms_scan_best's.
+ * The bytes of all three planes are the same on every run, and a cell does not depend on which other models and regions share the call.
+ * Work memory: the set's tables, and ms_scan_best's 16 bytes per (model, segment) of the regions of more than one segment.
+ * MS_ERR_INVALID: out NULL, NULL handles, a strand mask outside 1..3, flags != 0, a region of 2^31 bases or more.  MS_ERR_NOMEM: the 13 bytes
+ * per cell do not fit the device (nothing has been launched then).  n_models = 0 and n_seqs = 0 are valid and give empty results.  Without a
+ * device: MS_ERR_RUNTIME ("no CPU fallback") before anything else. */
+typedef struct ms_dimodelset ms_dimodelset;
+int  ms_dimodelset_create(const double *values /* [sum of W][16] */, const int32_t *widths /* [n_models] */, int32_t n_models, ms_dimodelset **out);
+int  ms_dimodelset_size(const ms_dimodelset *models, int32_t *n_models);
+int  ms_dimodelset_max_raw(const ms_dimodelset *models, double *out /* [n_models] */);
+void ms_dimodelset_free(ms_dimodelset *models);
+int  ms_scan_best_dimodels(const ms_dimodelset *models, const ms_seqset *seqs, int strand_mask, uint32_t flags /* 0 */, ms_best **out);
 
 /* ---- cutoff-free enrichment over best-site matrices that stay on the device (ms_ranksum.hip) ------------------------- */
 /* ORDER OF CELL VALUES, for both calls: a cell without a winner (score NaN, strand 0) ranks below every number; all cells without a winner

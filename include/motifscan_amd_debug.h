@@ -263,6 +263,15 @@ int ms_debug_compare_budget(int64_t bytes, int64_t *previous);
 int ms_debug_compare_null(const double *q_values, const int32_t *q_widths, int32_t n_q, const double *t_values, const int32_t *t_widths,
                           int32_t n_t, int metric, int32_t bins, int orientations, int32_t query, uint32_t *H, double *tail);
 
+/* The path constants of ms_scan_best_dimodels, as constants of the build: out[0] the threads of a block of its walk; out[1] the window
+ * starts per segment of a region (one wave each; a region of more than one segment goes through the partials and their reduction);
+ * out[2] the table entries of one LDS tile (a model of W columns takes 4 (4 W - 3): a run of consecutive scorable models shares a tile
+ * while their entries fit); out[3] the width cap, the widest model whose table fits a tile alone (wider: MS_ERR_INVALID from
+ * ms_dimodelset_create); out[4] the strips of 64 window starts a lane keeps in registers; out[5] the steps one packed word serves (a model
+ * of more than out[5] + 1 columns reads further words per window); out[6], out[7] reserved, 0.  Tests size their boundary cases from
+ * here.  Needs no GPU. */
+int ms_debug_dimodel_dims(int32_t out[8]);
+
 /* A set as a batch stream's upload stage leaves it: ASCII and offsets in HBM, the planes still to be packed by its first scan.  The entry
  * points that read the planes directly (ms_seqset_kmer_counts, ms_seqset_shuffle, ms_seqset_packed_host) refuse it with MS_ERR_INVALID: this
  * is how a test gets one.  Every scan entry point takes it and packs it; free it with ms_seqset_free.  Needs a GPU. */

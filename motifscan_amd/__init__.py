@@ -16,6 +16,8 @@ motifscan_amd -- MI355X-native drop-in for ONE hot path of shao-lab/MotifScan: t
                             (ms_result_site_signal), and their sequential restatement
     motifscan_amd.em        motif refinement without a cutoff: expected base counts per motif column over all windows
                             (ms_affinity_expected_counts, the E-step), their numpy restatement and mpmath reference, the M-step, the loop
+    motifscan_amd.dimodel   first-order motif models (a column's score depends on the base before it): DiModel and its constructors from a
+                            PWM, from counts and from a site stack, and the numpy restatement of ms_scan_best_dimodels
 
 There is no CPU fallback anywhere in this package.
 """

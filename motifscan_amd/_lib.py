@@ -271,6 +271,12 @@ def lib():
         "ms_debug_compare_dims": (c_int, [pi32]),
         "ms_debug_compare_budget": (c_int, [c_i64, pi64]),
         "ms_debug_compare_null": (c_int, [pd, pi32, c_i32, pd, pi32, c_i32, c_int, c_i32, c_int, c_i32, pu32, pd]),
+        "ms_dimodelset_create": (c_int, [pd, pi32, c_i32, pvp]),
+        "ms_dimodelset_size": (c_int, [vp, pi32]),
+        "ms_dimodelset_max_raw": (c_int, [vp, pd]),
+        "ms_dimodelset_free": (None, [vp]),
+        "ms_scan_best_dimodels": (c_int, [vp, vp, c_int, c_u32, pvp]),
+        "ms_debug_dimodel_dims": (c_int, [pi32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1622,6 +1628,64 @@ def scan_best(pwms, seqs, strand_mask=3, flags=0):
     h = ctypes.c_void_p()
     check(lib().ms_scan_best(pwms.h, seqs.h, strand_mask, int(flags), ctypes.byref(h)))
     return BestSites(h)
+
+
+class DiModelSet:
+    """A set of first-order models as the library holds it (ms_dimodelset_create; include/motifscan_amd.h has the definition).  values:
+    float64 [sum of W][16], the models' rows one after the other; widths int32 [P].  Needs no device: the scan uploads the tables."""
+
+    def __init__(self, values, widths):
+        self.values = np.ascontiguousarray(values, dtype=np.float64)
+        self.widths = np.ascontiguousarray(widths, dtype=np.int32).reshape(-1)
+        self.n = len(self.widths)
+        if self.n and int(self.widths.min()) >= 1 and self.values.size != 16 * int(self.widths.astype(np.int64).sum()):
+            raise ValueError("values must hold 16 * width doubles per model")
+        h = ctypes.c_void_p()
+        check(lib().ms_dimodelset_create(ptr(self.values, ctypes.c_double), ptr(self.widths, ctypes.c_int32), self.n, ctypes.byref(h)))
+        self.h = h
+
+    @classmethod
+    def from_models(cls, models):
+        """From dimodel.DiModel objects, or a dimodel.DiModelSet."""
+        from . import dimodel
+        ms = models if isinstance(models, dimodel.DiModelSet) else dimodel.DiModelSet(models)
+        return cls(ms.values, ms.widths)
+
+    def __len__(self):
+        return self.n
+
+    def max_raw(self):
+        out = np.zeros(self.n, dtype=np.float64)
+        check(lib().ms_dimodelset_max_raw(self.h, ptr(out, ctypes.c_double)))
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ms_dimodelset_free(self.h)
+            self.h = None
+
+    __del__ = close
+
+
+def scan_best_dimodels(models, seqs, strand_mask=3, flags=0):
+    """ms_scan_best_dimodels: the best window of every (first-order model, region) cell of a DiModelSet x SeqSet.  Returns a BestSites:
+    rank_sum, count_passing and the device pointers work on it as on ms_scan_best's."""
+    strand_mask = int(strand_mask)
+    if strand_mask not in (1, 2, 3):
+        raise ValueError(f"invalid strand mask {strand_mask!r} (1 '+', 2 '-', 3 both)")
+    if int(flags) != 0:
+        raise ValueError(f"unknown first-order best-site scan flags {flags!r}")
+    h = ctypes.c_void_p()
+    check(lib().ms_scan_best_dimodels(models.h, seqs.h, strand_mask, int(flags), ctypes.byref(h)))
+    return BestSites(h)
+
+
+def dimodel_dims():
+    """ms_debug_dimodel_dims: dict(threads, seg_windows, tile_entries, max_width, strips, word_steps) -- the sizes at which
+    ms_scan_best_dimodels changes segment, tile or word.  Constants of the build; no device."""
+    out = np.zeros(8, dtype=np.int32)
+    check(lib().ms_debug_dimodel_dims(ptr(out, ctypes.c_int32)))
+    return dict(zip(("threads", "seg_windows", "tile_entries", "max_width", "strips", "word_steps"), (int(v) for v in out[:6])))
 
 
 class Affinity:

@@ -391,14 +391,19 @@ inline int hip_rc(hipError_t e, const char *what) {
 }
 // MS_ERR_INVALID for a region of 2^31 bases or more: `what` ("positions are", "n_terms is") is 32-bit in the result
 MS_HIDDEN int dense_regions_fit(const ms_seqset *seqs, const char *what);
-// dense_plan of a PWM set over a sequence set, with the two ways it fails: out of host memory, and more long regions or blocks of
-// segs_per_block segments than the x of one grid holds
+// dense_plan of widths[P] over a sequence set, with the two ways it fails: out of host memory, and more long regions or blocks of
+// segs_per_block segments than the x of one grid holds.  The widths are a PWM set's, or the pseudo-widths of a first-order model set
+// (ms_dimodel.hip).
 template <typename Walked>
-inline int dense_plan_for(const DenseGeom &g, const ms_pwmset *pwms, const ms_seqset *seqs, int segs_per_block, Walked walked, DensePlan *pl) {
-    try { dense_plan(g, pwms->widths.data(), pwms->P, seqs->offsets.data(), seqs->R, walked, pl); }
+inline int dense_plan_for(const DenseGeom &g, const int32_t *widths, int32_t P, const ms_seqset *seqs, int segs_per_block, Walked walked, DensePlan *pl) {
+    try { dense_plan(g, widths, P, seqs->offsets.data(), seqs->R, walked, pl); }
     catch (const std::bad_alloc &) { set_error("out of host memory"); return MS_ERR_NOMEM; }
     if (pl->long_regions.size() > 0x7FFFFFFFull || (pl->n_seg + segs_per_block - 1) / segs_per_block > 0x7FFFFFFFLL) { set_error("too many segments for one launch"); return MS_ERR_INVALID; }
     return MS_OK;
+}
+template <typename Walked>
+inline int dense_plan_for(const DenseGeom &g, const ms_pwmset *pwms, const ms_seqset *seqs, int segs_per_block, Walked walked, DensePlan *pl) {
+    return dense_plan_for(g, pwms->widths.data(), pwms->P, seqs, segs_per_block, walked, pl);
 }
 // A plan's arrays on the device, in the work block they were given slots in (dense_slots): nullptr where the plan has none.
 struct DenseDev {

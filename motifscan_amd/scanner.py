@@ -397,6 +397,43 @@ class Scanner:
         finally:
             pw.close()
 
+    def _scan_best_dimodels(self, ms):
+        return _lib.scan_best_dimodels(ms, self._seqset(), _STRAND_FLAG[self.strand])
+
+    def best_sites_dimodels(self, models):
+        """best_sites for first-order models (dimodel.DiModel objects or a dimodel.DiModelSet): the best-scoring window of every
+        (model, region) cell as a BestSiteArrays (ms_scan_best_dimodels).  A window that holds a non-ACGT base has no score; the walk
+        and the tie rule are best_sites'.  Honours the scanner's `strand`."""
+        ms = _lib.DiModelSet.from_models(models)
+        try:
+            res = self._scan_best_dimodels(ms)
+            try:
+                score, pos, strand = res.sites()
+            finally:
+                res.close()
+        finally:
+            ms.close()
+        return BestSiteArrays(score, best_site_starts(pos, self.seq_starts), strand)
+
+    def rank_sum_dimodels(self, models, control, sel=None, sel_control=None):
+        """rank_sum for first-order models: is each model enriched in this scanner's regions against `control`'s, by the best score per
+        region and without a cutoff?  An enrich.RankSum.  Both region lists are scanned with ms_scan_best_dimodels, each with its
+        scanner's `strand`; the matrices stay on the device and are reduced there (ms_best_rank_sum)."""
+        from . import enrich
+        ms = _lib.DiModelSet.from_models(models)
+        try:
+            mine = self._scan_best_dimodels(ms)
+            try:
+                theirs = control._scan_best_dimodels(ms)
+                try:
+                    return enrich.rank_sum(mine, theirs, sel, sel_control)
+                finally:
+                    theirs.close()
+            finally:
+                mine.close()
+        finally:
+            ms.close()
+
     def count_regions_passing(self, pwms, cutoffs):
         """int64 [n_pwms][K]: the number of this scanner's regions that hold >= 1 site of each motif at each of its K cutoffs
         (cutoffs [n_pwms][K]) -- count_regions_with_sites at K cutoffs from ONE best-site scan (ms_best_count_passing) instead of K

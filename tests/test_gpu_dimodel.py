@@ -1,0 +1,338 @@
+"""
+ms_scan_best_dimodels (ms_dimodel.hip) on the GPU: the best-scoring window of every (first-order model, region) cell, every plane
+compared byte for byte with `dimodel.best_sites_host` (which tests/test_dimodel_host.py pins to a scalar loop) at the smallest shapes that
+can go wrong -- the widths around the 32-base word edges and the cap, regions around every width and around a segment, tiles that break
+at an unscorable model, non-ACGT bases on and beside a window's ends, ties, forbidden transitions --, tied to ms_scan_best through the
+degenerate model of a PWM, held to the exact maximum, followed downstream into the rank sums, and run end to end on the planted case.
+The cases are tests/dimodel_cases.py's, sized by ms_debug_dimodel_dims.
+
+One of the issue's MS_ERR_INVALID cases is not exercised, as in tests/test_gpu_best.py and for its reason: a region of 2^31 bases or
+more needs 2 GiB of host bytes, their upload and the pack kernel for one comparison of two integers (dense_regions_fit, shared with
+ms_scan_best).  And there is no "device mismatch" to provoke: a model set is not bound to a device (include/motifscan_amd.h).
+"""
+import ctypes
+
+import numpy as np
+import pytest
+
+import dimodel_cases as dc
+from motifscan_amd import _lib, dimodel, enrich, scanner, sitestack
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _device():
+    if _lib.device_count() < 1:
+        pytest.fail("no HIP device visible")
+    _lib.set_device(0)
+
+
+def run(models, seqs, mask=3, sq=None):
+    ms = _lib.DiModelSet.from_models(models)
+    own = sq is None
+    if own:
+        sq = _lib.SeqSet.from_strings(seqs)
+    try:
+        res = _lib.scan_best_dimodels(ms, sq, mask)
+        try:
+            assert res.shape == (len(models), len(seqs))
+            return res.sites()
+        finally:
+            res.close()
+    finally:
+        if own:
+            sq.close()
+        ms.close()
+
+
+# ------------------------------------------------------------------------------------------------ 1. the smallest shapes
+
+@pytest.fixture(scope="module")
+def world():
+    d = _lib.dimodel_dims()
+    cap, seg = d["max_width"], d["seg_windows"]
+    small = dc.small_models()                              # widths 1 .. 65, each plain and with forbidden transitions
+    neg = [dc.negative_model(w, 40 + w) for w in (4, 9, 2, 5, 6)]
+    # unscorable first and last; one between two scorable ones (it breaks the tile run); the widest models together overflow one tile
+    # (two tiles and more); one cap model stands alone between two unscorable ones, the other is followed by a model of three columns
+    # that no longer fits its tile (the split on the tile's size), which shares the next tile with a model of one column
+    models = ([neg[0]] + small[:9] + [neg[1]] + small[9:] + [neg[2], dc.random_model(cap, 4000, holes=2), neg[3], dc.random_model(cap, 4001),
+              dc.random_model(3, 4003), dc.random_model(1, 4002), neg[4]])
+    entries = [4 * (4 * m.width - 3) for m in small[9:]]
+    assert sum(entries) > 2 * d["tile_entries"]
+    assert 4 * (4 * cap - 3) + 4 * (4 * 3 - 3) > d["tile_entries"] >= 4 * (4 * 3 - 3) + 4 * (4 * 1 - 3)
+    rng = np.random.default_rng(31)
+    seqs = dc.small_regions()
+    seqs += [dc.random_dna(rng, n) for n in (cap - 1, cap, cap + 1, seg, seg + 1, seg + 32, seg + 33)]     # the cap; one segment exactly, one window more
+    long_one = bytearray(dc.random_dna(rng, 2 * seg + 17).encode())                                          # three segments ...
+    long_one[seg - 9:seg + 12] = b"N" * 21                                                                   # ... an N run across a segment (and word) edge
+    seqs.append(long_one.decode())
+    seqs.append(dc.random_dna(rng, 3 * seg))
+    return {"models": models, "seqs": seqs, "dims": d, "want": {}}
+
+
+def want_of(world, mask):
+    if mask not in world["want"]:
+        world["want"][mask] = dimodel.best_sites_host(world["models"], world["seqs"], mask)
+    return world["want"][mask]
+
+
+@pytest.mark.parametrize("mask", (1, 2, 3))
+def test_smallest_shapes_equal_the_restatement_byte_for_byte(world, mask):
+    want = want_of(world, mask)
+    got = run(world["models"], world["seqs"], mask)
+    dc.same_planes(got, want)
+    score, pos, strand = got
+    unscorable = [i for i, m in enumerate(world["models"]) if not dimodel.scorable_host(m)]
+    assert unscorable[0] == 0 and unscorable[-1] == len(world["models"]) - 1 and len(unscorable) == 5 and np.isnan(score[unscorable]).all()
+    scorable = [i for i in range(len(world["models"])) if i not in unscorable]
+    assert np.isfinite(score[scorable]).sum() > 500 and np.isnan(score[scorable]).sum() > 100     # (the cases hold what they are meant to hold)
+    if mask == 3:
+        assert (strand == 1).any() and (strand == 2).any()
+    cap = world["dims"]["max_width"]
+    k = [i for i, m in enumerate(world["models"]) if m.width == cap][-1]
+    by_len = {len(s): r for r, s in enumerate(world["seqs"])}
+    assert np.isnan(score[k, by_len[cap - 1]]) and pos[k, by_len[cap]] == 0 and pos[k, by_len[cap + 1]] in (0, 1)
+    assert pos[scorable].max() > 2 * world["dims"]["seg_windows"]                                # a winner in the third segment
+
+
+def test_a_region_whose_every_window_holds_an_n_has_no_winner(world):
+    models = [m for m in world["models"] if m.width >= 2 and dimodel.scorable_host(m)][:6]
+    seqs = [dc.with_n(dc.random_dna(np.random.default_rng(2), 700), *range(0, 700, 2)), "N" * 90]
+    score, pos, strand = run(models, seqs)
+    assert np.isnan(score).all() and (pos == -1).all() and (strand == 0).all()
+    one = run([dc.random_model(1, 4002)], seqs)            # a model of one column still finds the odd positions
+    dc.same_planes(one, dimodel.best_sites_host([dc.random_model(1, 4002)], seqs, 3))
+    assert one[1][0, 0] % 2 == 1 and one[1][0, 1] == -1
+
+
+def test_width_above_the_cap_is_invalid(world):
+    cap = world["dims"]["max_width"]
+    wide = dc.random_model(cap + 1, 1)
+    with pytest.raises(ValueError, match="at most %d columns" % cap):
+        _lib.DiModelSet.from_models([dc.random_model(3, 1), wide])
+
+
+# ------------------------------------------------------------------------------------------------ 2. ties, forbidden transitions
+
+@pytest.mark.parametrize("mask", (1, 2, 3))
+def test_ties_keep_the_earliest_window_and_the_plus_strand(mask):
+    models, seqs = dc.tie_cases()
+    got = run(models, seqs, mask)
+    dc.same_planes(got, dimodel.best_sites_host(models, seqs, mask))
+    score, pos, strand = got
+    assert pos[0, 0] < 12 and pos[1, 1] == 4 and score[1, 1] == 1.0
+    if mask == 3:
+        assert (strand[1] == 1).all()
+
+
+def test_forbidden_transitions_and_a_region_where_every_window_is_forbidden():
+    m = dimodel.DiModel([1.0, 1.0, 1.0, 1.0], np.full((2, 16), 0.5))
+    m.trans[0, 0] = -np.inf                                # A after A at column 1, T after T at column 2: "AAAA" is barred on both strands
+    m.trans[1, 15] = -np.inf
+    seqs = ["AAAAAA", "AAACAA", "A" * 600, "A" * 590 + "CA"]
+    got = run([m, dc.random_model(7, 5, holes=3)], seqs)
+    dc.same_planes(got, dimodel.best_sites_host([m, dc.random_model(7, 5, holes=3)], seqs, 3))
+    score, pos, strand = got
+    assert np.isnan(score[0, [0, 2]]).all() and (pos[0, 1], strand[0, 1], score[0, 1]) == (2, 1, 1.0) and pos[0, 3] == 589
+
+
+# ------------------------------------------------------------------------------------------------ 3. the tie to ms_scan_best, the exact maximum
+
+@pytest.mark.parametrize("mask", (1, 2, 3))
+def test_the_degenerate_model_of_a_pwm_equals_ms_scan_best(mask):
+    rng = np.random.default_rng(77)
+    widths = [1, 2, 3, 5, 8, 8, 10, 12, 15, 19, 24, 31, 32, 33, 34, 40, 63, 64, 65, 70]
+    mats = [dc.random_pwm(w, 600 + i) for i, w in enumerate(widths)]
+    seqs = [dc.random_dna(rng, n) for n in (0, 7, 33, 64, 65, 130, 513, 1100)]
+    pw, sq = _lib.PwmSet.from_matrices(mats), _lib.SeqSet.from_strings(seqs)
+    try:
+        res = _lib.scan_best(pw, sq, mask)
+        want = res.sites()
+        res.close()
+        got = run([dimodel.DiModel.from_pwm(m) for m in mats], seqs, mask, sq=sq)
+    finally:
+        sq.close()
+        pw.close()
+    dc.same_planes(got, want)
+    assert np.isfinite(got[0]).sum() > 100
+
+
+def test_the_viterbi_sequence_scores_exactly_one(world):
+    """max_raw is the greatest FORWARD raw sum, attained by the Viterbi sequence on '+' (the reverse strand adds the same terms in the
+    other order and may round differently, so the exact 1.0 is a statement about '+')."""
+    rng = np.random.default_rng(9)
+    models = [m for m in world["models"] if dimodel.scorable_host(m)]
+    seqs = [dc.random_dna(rng, 5) + dc.viterbi_sequence(m) + dc.random_dna(rng, 9) for m in models]
+    n = len(models)
+    score, pos, strand = run(models, seqs, 1)
+    dc.same_planes((score, pos, strand), dimodel.best_sites_host(models, seqs, 1))
+    for i in range(n):
+        assert score[i, i] == 1.0 and strand[i, i] == 1 and pos[i, i] <= 5
+    assert sum(int(pos[i, i]) == 5 for i in range(n)) >= n - 2          # (an earlier window may attain the maximum too)
+    assert score[np.isfinite(score)].max() == 1.0
+
+
+# ------------------------------------------------------------------------------------------------ 4. downstream: the handles are ordinary ms_best
+
+def test_rank_sum_and_count_passing_take_the_handles(world):
+    rng = np.random.default_rng(13)
+    models = world["models"][:14]
+    a = [dc.random_dna(rng, int(n)) for n in rng.integers(1, 90, 130)]
+    b = [dc.random_dna(rng, int(n)) for n in rng.integers(1, 90, 77)]
+    ms, sa, sb = _lib.DiModelSet.from_models(models), _lib.SeqSet.from_strings(a), _lib.SeqSet.from_strings(b)
+    try:
+        ha, hb = _lib.scan_best_dimodels(ms, sa, 3), _lib.scan_best_dimodels(ms, sb, 3)
+        try:
+            xa, xb = dimodel.best_sites_host(models, a, 3)[0], dimodel.best_sites_host(models, b, 3)[0]
+            u2, ties, na, nb = ha.rank_sum(hb)
+            want = enrich.rank_sum_host(xa, xb)
+            assert np.array_equal(u2, want.u2) and [int(t) for t in ties] == want.ties and (na, nb) == (130, 77)
+            sel = rng.random(130) < 0.5
+            u2, ties, na, nb = ha.rank_sum(hb, sel)
+            want = enrich.rank_sum_host(xa[:, sel], xb)
+            assert np.array_equal(u2, want.u2) and [int(t) for t in ties] == want.ties and (na, nb) == (int(sel.sum()), 77)
+            cut = np.tile([0.2, 0.5, 0.8, 1.0], (len(models), 1))
+            assert np.array_equal(ha.count_passing(cut), enrich.count_passing_host(xa, cut))
+            dptr = ha.device_pointers()
+            assert all(dptr) and ha.device_ms() > 0
+        finally:
+            ha.close()
+            hb.close()
+    finally:
+        sa.close()
+        sb.close()
+        ms.close()
+
+
+# ------------------------------------------------------------------------------------------------ 5. end to end on the planted case
+
+def test_planted_case_end_to_end():
+    inputs, controls, pwm_matrix = dc.planted_case()
+    chroms = {"in": "".join(inputs), "ctl": "".join(controls)}
+
+    class Genome:
+        chrom_sizes = {k: len(v) for k, v in chroms.items()}
+
+        def fetch_sequence(self, chrom, start, end):
+            return chroms[chrom][start:end]
+
+    class Region:
+        def __init__(self, chrom, start, end):
+            self.chrom, self.start, self.end, self.summit = chrom, start, end, (start + end) // 2
+
+    class Pwm:
+        matrix, length, cutoffs = pwm_matrix, 8, {"planted": dc.PLANTED_CUTOFF}
+    sc = scanner.Scanner(Genome(), [Region("in", 120 * i, 120 * i + 120) for i in range(300)], p_value="planted", remove_dup=False)
+    ctl = scanner.Scanner(Genome(), [Region("ctl", 120 * i, 120 * i + 120) for i in range(300)], p_value="planted", remove_dup=False)
+    try:
+        assert list(sc.sequences) == inputs and list(ctl.sequences) == controls
+        sites = sc.scan_motifs([Pwm])
+        try:
+            stack = sitestack.site_base_counts(sites, [Pwm], sc._seqset(), dinuc=True)
+        finally:
+            sites.close()
+        host_stack = sitestack.site_base_counts_host(*dc.planted_hits_host(pwm_matrix, inputs), [8], inputs, 0, dinuc=True)
+        assert np.array_equal(stack.counts, host_stack.counts) and np.array_equal(stack.dinuc, host_stack.dinuc)
+        cond, init = sc._seqset().kmer_counts(2).markov(), sc._seqset().kmer_counts(1).markov()[0]
+        model = dimodel.DiModel.from_site_stack(stack, 0, cond, init, 1.0)
+        got = sc.rank_sum_dimodels([model], ctl)
+        want = enrich.rank_sum_host(dimodel.best_sites_host([model], inputs, 3)[0], dimodel.best_sites_host([model], controls, 3)[0])
+        assert isinstance(got, enrich.RankSum) and np.array_equal(got.u2, want.u2) and got.ties == want.ties and (got.na, got.nb) == (300, 300)
+        best = sc.best_sites_dimodels([model])
+        assert best.score.shape == (1, 300) and np.array_equal(best.strand, dimodel.best_sites_host([model], inputs, 3)[2])
+        from_pwm = sc.rank_sum([Pwm], ctl)
+        print(f"planted case: first-order AUROC {got.auroc()[0]:.4f}, PWM AUROC {from_pwm.auroc()[0]:.4f}")
+        assert got.auroc()[0] >= 0.9 and from_pwm.auroc()[0] <= 0.7
+    finally:
+        sc.close()
+        ctl.close()
+
+
+# ------------------------------------------------------------------------------------------------ 6. recycled memory, determinism, independence
+
+def representative(world):
+    seg = world["dims"]["seg_windows"]
+    rng = np.random.default_rng(21)
+    models = world["models"][7:16] + world["models"][-6:]               # three unscorable ones among them (one of them last), the cap's models
+    seqs = [dc.random_dna(rng, n) for n in (0, 5, 64, 300, seg + 40, 2 * seg + 3)] + [dc.with_n(dc.random_dna(rng, 90), 31, 32, 70)]
+    return models, seqs
+
+
+def test_recycled_memory_does_not_reach_the_result(world):
+    models, seqs = representative(world)
+    want = dimodel.best_sites_host(models, seqs, 3)
+    other = (world["models"][1:5], [dc.random_dna(np.random.default_rng(3), 150)] * 3)
+    plain = run(models, seqs)
+    dc.same_planes(plain, want)
+    try:
+        for byte in (0xFF, 0xA5):
+            with _lib.alloc_fill(byte):
+                run(*other)                                # another call in between: its blocks are what the next one is handed
+                filled = run(models, seqs)
+            for g, p in zip(filled, plain):
+                assert g.tobytes() == p.tobytes(), hex(byte)
+            dc.same_planes(filled, want)
+    finally:
+        _lib.check(_lib.lib().ms_debug_alloc_fill(-1, None))
+    again = run(models, seqs)
+    assert all(g.tobytes() == p.tobytes() for g, p in zip(again, plain))
+
+
+def test_two_runs_give_the_same_bytes_and_a_cell_does_not_depend_on_its_company(world):
+    models, seqs = representative(world)
+    first, second = run(models, seqs), run(models, seqs)
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(first, second))
+    rows, cols = [0, 3, 4, 9, 12, 14], [1, 4, 5, 6]                    # (the subset, too, ends on an unscorable model)
+    sub = run([models[i] for i in rows], [seqs[r] for r in cols])
+    for plane, part in zip(first, sub):
+        assert np.ascontiguousarray(plane[np.ix_(rows, cols)]).tobytes() == part.tobytes()
+    alone = run([models[9]], [seqs[5]])
+    assert all(np.ascontiguousarray(p[9:10, 5:6]).tobytes() == a.tobytes() for p, a in zip(first, alone))
+
+
+# ------------------------------------------------------------------------------------------------ 7. empty sets, invalid arguments
+
+def test_empty_model_set_and_empty_region_set():
+    score, pos, strand = run([], ["ACGT", "AC"])
+    assert score.shape == pos.shape == strand.shape == (0, 2)
+    score, pos, strand = run([dc.random_model(3, 1), dc.random_model(2, 2)], [])
+    assert score.shape == pos.shape == strand.shape == (2, 0)
+    assert run([], [])[0].shape == (0, 0)
+
+
+def test_every_invalid_argument_raises_with_the_librarys_message():
+    L = _lib.lib()
+    ms, sq = _lib.DiModelSet.from_models([dc.random_model(3, 1)]), _lib.SeqSet.from_strings(["ACGTACGT"])
+    h = ctypes.c_void_p()
+
+    def raw(models, seqs, mask, flags, out=h):
+        return L.ms_scan_best_dimodels(models, seqs, mask, flags, ctypes.byref(out) if out is not None else None)
+    try:
+        for args, text in (((None, sq.h, 3, 0), "NULL handle"), ((ms.h, None, 3, 0), "NULL handle"), ((ms.h, sq.h, 0, 0), "invalid strand mask 0"),
+                           ((ms.h, sq.h, 4, 0), "invalid strand mask 4"), ((ms.h, sq.h, 3, 1), "unknown first-order best-site scan flags 0x1")):
+            rc = raw(*args)
+            assert rc == _lib.MS_ERR_INVALID and not h.value
+            with pytest.raises(ValueError, match=text):
+                _lib.check(rc)
+        rc = raw(ms.h, sq.h, 3, 0, out=None)
+        assert rc == _lib.MS_ERR_INVALID
+        with pytest.raises(ValueError, match="out is NULL"):
+            _lib.check(rc)
+        for mask in (0, 4):
+            with pytest.raises(ValueError, match="strand mask"):
+                _lib.scan_best_dimodels(ms, sq, mask)
+        with pytest.raises(ValueError, match="flags"):
+            _lib.scan_best_dimodels(ms, sq, 3, flags=2)
+        for widths, text in (([0], "width 0"), ([_lib.dimodel_dims()["max_width"] + 1], "at most")):
+            with pytest.raises(ValueError, match=text):
+                _lib.DiModelSet(np.zeros((max(widths[0], 1), 16)), widths)
+        res = _lib.scan_best_dimodels(ms, sq, 3)            # ... and the handles still work
+        assert res.shape == (1, 1) and res.pos[0, 0] >= 0
+        with pytest.raises(ValueError, match="motif range"):
+            res.sites(0, 2)
+        res.close()
+    finally:
+        sq.close()
+        ms.close()
