@@ -241,91 +241,71 @@ void ms_affinity_free(ms_affinity *a) {
 int ms_scan_affinity(const ms_pwmset *pwms_c, const ms_seqset *seqs, int strand_mask, double scale, int32_t max_n, uint32_t flags, ms_affinity **out) {
     if (!out) { set_error("out is NULL"); return MS_ERR_INVALID; }
     *out = nullptr;
-    if (!require_device()) return MS_ERR_RUNTIME;
-    if (!pwms_c || !seqs) { set_error("NULL handle"); return MS_ERR_INVALID; }
-    if (strand_mask < 1 || strand_mask > 3) { set_error("invalid strand mask %d (1 '+', 2 '-', 3 both)", strand_mask); return MS_ERR_INVALID; }
+    int rc = dense_check(pwms_c, seqs, strand_mask);
+    if (rc) return rc;
     if (flags != 0u) { set_error("unknown affinity scan flags 0x%x", flags); return MS_ERR_INVALID; }
     if (!(std::isfinite(scale) && scale > 0.0)) { set_error("scale must be a finite number > 0"); return MS_ERR_INVALID; }
     if (max_n < -1) { set_error("max_n must be >= -1 (-1: every window is a term)"); return MS_ERR_INVALID; }
     ms_pwmset *pwms = const_cast<ms_pwmset *>(pwms_c);
     const int32_t P = pwms->P;
     const int64_t R = seqs->R;
-    int rc = dense_regions_fit(seqs, "n_terms is");
-    if (rc) return rc;
-    DeviceCtx *c;
-    if ((rc = get_ctx(seqs->device, &c))) return rc;
-    std::unique_ptr<ms_affinity> res(new (std::nothrow) ms_affinity());
+    std::unique_ptr<ms_affinity, void (*)(ms_affinity *)> res(nullptr, ms_affinity_free);      // (in front of the run: freed behind the run's wait for the stream)
+    DenseRun run;
+    // a motif whose max_raw is <= 0 is walked
+    if ((rc = dense_open(&run, kBestGeom, pwms->widths.data(), P, &pwms->mu, seqs, "n_terms is", [&](int32_t m) { return entries_scorable(pwms, m); }))) return rc;
+    const DensePlan &plan = run.plan;
+
+    // ---- 28 bytes per cell, 24 per partial: both blocks are allocated before anything is launched, and a failure there is the MS_ERR_NOMEM
+    // of the header (the test here only keeps the byte counts below inside size_t)
+    if (28.0 * (double) P * (double) R + (double) sizeof(AffPart) * (double) P * (double) plan.n_part >= 0.5 * (double) std::numeric_limits<size_t>::max()) {
+        set_error("%d x %lld cells do not fit the device", P, (long long) R);
+        return MS_ERR_NOMEM;
+    }
+    res.reset(new (std::nothrow) ms_affinity());
     if (!res) { set_error("out of host memory"); return MS_ERR_NOMEM; }
-    res->device = c->device;
+    res->device = run.c->device;
     res->P = P;
     res->R = R;
     res->strand_mask = strand_mask;
     res->scale = scale;
     res->max_n = max_n;
-
-    // ---- the plan, on the host: segments of the regions, tiles of the motifs (ms_dense_plan.h); a motif whose max_raw is <= 0 is walked
-    DensePlan plan;
-    if ((rc = dense_plan_for(kBestGeom, pwms, seqs, kBestWaves, [&](int32_t m) { return entries_scorable(pwms, m); }, &plan))) return rc;
-    const int64_t n_seg = plan.n_seg, n_part = plan.n_part, n_mot = (int64_t) plan.mot.size();
-
-    // ---- 28 bytes per cell, 24 per partial: both blocks are allocated before anything is launched, and a failure there is the MS_ERR_NOMEM
-    // of the header (the test here only keeps the byte counts below inside size_t)
-    if (28.0 * (double) P * (double) R + (double) sizeof(AffPart) * (double) P * (double) n_part >= 0.5 * (double) std::numeric_limits<size_t>::max()) {
-        set_error("%d x %lld cells do not fit the device", P, (long long) R);
-        return MS_ERR_NOMEM;
-    }
     const size_t cells = (size_t) P * (size_t) R, cz = std::max<size_t>(cells, 1);
-    std::lock_guard<std::mutex> lk_dev(c->mu);
-    std::lock_guard<std::mutex> lk_pwm(pwms->mu);
-    MS_HIP(hipSetDevice(c->device));
     Carve rv;
     const auto s_peak = rv.add<double>(cz), s_sum = rv.add<double>(cz), s_log_mean = rv.add<double>(cz);
     const auto s_n_terms = rv.add<int32_t>(cz);
-    if ((rc = pool_alloc(c, rv.bytes(), &res->block, &res->block_bytes))) return rc;
+    if ((rc = pool_alloc(run.c, rv.bytes(), &res->block, &res->block_bytes))) return rc;
     res->d_peak = Carve::at(res->block, s_peak);
     res->d_sum = Carve::at(res->block, s_sum);
     res->d_log_mean = Carve::at(res->block, s_log_mean);
     res->d_n_terms = Carve::at(res->block, s_n_terms);
-    ms_affinity *raw = res.release();
-    if (cells == 0) { *out = raw; return MS_OK; }
+    if (cells == 0) { *out = res.release(); return MS_OK; }
 
-    Carve cv;
-    const DenseSlots ds = dense_slots(cv, plan);
-    const auto s_part = cv.add<AffPart>((size_t) P * (size_t) n_part);
-    void *wblk = nullptr;
-    size_t wgot = 0;
-    if ((rc = pool_alloc(c, cv.bytes(), &wblk, &wgot))) { ms_affinity_free(raw); return rc; }
-    auto fail = [&](int code) { pool_free(c, wblk, wgot); ms_affinity_free(raw); return code; };
+    const auto s_part = run.cv.add<AffPart>((size_t) P * (size_t) plan.n_part);
+    if ((rc = dense_start(&run, pwms, seqs, reinterpret_cast<const void *>(affinity_kernel<true>)))) return rc;
 
-    const hipStream_t st = c->stream;
-    if ((rc = pwmset_upload(pwms, c->device, st))) return fail(rc);
-    if ((rc = seqset_pack_pending(seqs, st))) return fail(rc);
-    const size_t lds = (plan.max_tile + 1) * sizeof(double2);
-    if ((rc = dense_raise_lds(c, reinterpret_cast<const void *>(affinity_kernel<true>), lds, (kBestTileEntries + 1) * sizeof(double2)))) return fail(rc);
-    DenseDev d;
-    if ((rc = dense_upload(plan, ds, wblk, st, &d))) return fail(rc);
-
+    const DenseDev &d = run.d;
     AffArgs A;
     A.codes = seqs->d_codes; A.nmask = seqs->d_nmask; A.offsets = seqs->d_offsets; A.R = R;
     A.seg_first = d.seg_first; A.part_first = d.part_first;
-    A.n_seg = n_seg; A.n_part = n_part;
+    A.n_seg = plan.n_seg; A.n_part = plan.n_part;
     A.tile_first = d.tile_first; A.mot = d.mot;
     A.Pw = dev_pwm(pwms);
     A.strand_mask = strand_mask;
     A.max_n = max_n;
     A.scale = scale;
-    A.peak = raw->d_peak; A.sum = raw->d_sum; A.log_mean = raw->d_log_mean; A.n_terms = raw->d_n_terms;
-    A.part = Carve::at(wblk, s_part);
+    A.peak = res->d_peak; A.sum = res->d_sum; A.log_mean = res->d_log_mean; A.n_terms = res->d_n_terms;
+    A.part = Carve::at(run.work.p, s_part);
     AffArgs Aw = A;                                      // the wide motifs: one "tile" each
     Aw.tile_first = d.wide_first;
 
-    (void) hipEventRecord(c->ev[0], st);
-    const unsigned gx = (unsigned) ((n_seg + kBestWaves - 1) / kBestWaves);
+    const hipStream_t st = run.st;
+    const int64_t n_mot = (int64_t) plan.mot.size();
+    (void) hipEventRecord(run.c->ev[0], st);
     rc = dense_chunks((int64_t) plan.tile_first.size() - 1, "affinity kernel", [&](int64_t t0, unsigned ny) {
-        hipLaunchKernelGGL(affinity_kernel<true>, dim3(gx, ny), dim3(kBestThreads), lds, st, A, (int32_t) t0);
+        hipLaunchKernelGGL(affinity_kernel<true>, dim3(run.gx, ny), dim3(kBestThreads), run.lds, st, A, (int32_t) t0);
     });
     if (!rc) rc = dense_chunks((int64_t) plan.wide_first.size() - 1, "affinity kernel (tables in HBM)", [&](int64_t t0, unsigned ny) {
-        hipLaunchKernelGGL(affinity_kernel<false>, dim3(gx, ny), dim3(kBestThreads), 0, st, Aw, (int32_t) t0);
+        hipLaunchKernelGGL(affinity_kernel<false>, dim3(run.gx, ny), dim3(kBestThreads), 0, st, Aw, (int32_t) t0);
     });
     if (!rc && !plan.long_regions.empty()) rc = dense_chunks((n_mot + 3) / 4, "affinity reduction", [&](int64_t g0, unsigned ny) {       // four motifs a block
         hipLaunchKernelGGL(affinity_reduce_kernel, dim3((unsigned) plan.long_regions.size(), ny), dim3(256), 0, st, A, d.long_regions, (int32_t) (4 * g0), (int32_t) n_mot);
@@ -333,10 +313,9 @@ int ms_scan_affinity(const ms_pwmset *pwms_c, const ms_seqset *seqs, int strand_
     if (!rc) rc = dense_chunks((int64_t) plan.skipped.size(), "affinity fill", [&](int64_t u0, unsigned ny) {
         hipLaunchKernelGGL(affinity_fill_kernel, dim3((unsigned) ((R + 255) / 256), ny), dim3(256), 0, st, A, d.skipped + u0);
     });
-    if (!rc) rc = dense_finish(c, "affinity scan", raw);
-    if (rc) return fail(rc);
-    pool_free(c, wblk, wgot);
-    *out = raw;
+    if (!rc) rc = dense_end(&run, "affinity scan", res.get());
+    if (rc) return rc;
+    *out = res.release();
     return MS_OK;
 }
 

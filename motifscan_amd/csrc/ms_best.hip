@@ -23,8 +23,10 @@
 // Motifs wider than kBestTileMaxW read their table from HBM (score_window); unscorable motifs (max_raw not a finite number > 0, a NaN or
 // +inf entry: the reference never reports a site for them) are filled with the "no winner" triple and never scored.
 //
-// Behind ms_scan_best this file also holds the host side that the dense walks share (declared in ms_handles.h; ms_affinity.hip,
-// ms_scorehist.hip and ms_expcounts.hip call it): a plan's upload, the LDS limit, the end of a scan, and the accessors of a DenseHead.
+// Behind ms_scan_best this file also holds the host side that the five dense walks share (declared in ms_handles.h; ms_affinity.hip,
+// ms_scorehist.hip, ms_expcounts.hip and ms_dimodel.hip call it): a plan's upload, the LDS limit, the accessors of a DenseHead, the
+// driver of the three walks that fill a matrix (dense_check, dense_open, dense_start, dense_end), and the tail of the two best-site
+// walks -- the allocation of an ms_best and the reduce and fill kernels, which ms_scan_best_dimodels ends in as well.
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -38,13 +40,7 @@ namespace ms {
 
 namespace {
 
-// (the sizes of the walk -- kBestThreads ... kBestTileEntries -- are in ms_best_dev.h: ms_affinity.hip walks the same way)
-struct BestPart {                                        // a segment's best of one motif
-    double q;
-    int32_t pos;                                         // -1: no winner
-    int32_t strand;
-};
-
+// (the sizes of the walk -- kBestThreads ... kBestTileEntries --, BestPart and put_best are in ms_best_dev.h: the other walks use them)
 struct BestArgs {
     const uint32_t *codes, *nmask;
     const int64_t *offsets;                              // [R + 1]
@@ -62,12 +58,16 @@ struct BestArgs {
     BestPart *part;                                      // [P][n_part]
 };
 
-__device__ __forceinline__ void put_best(double *__restrict__ score, int32_t *__restrict__ pos, int8_t *__restrict__ strand, int64_t cell, double q, uint64_t key) {
-    const bool won = key != kNoKey;
-    score[cell] = won ? q : __builtin_nan("");
-    pos[cell] = won ? (int32_t) (key >> 2) : -1;
-    strand[cell] = won ? (int8_t) (key & 3u) : (int8_t) 0;
-}
+struct BestTail {                                        // what the reduce and fill kernels read, whichever walk wrote the partials
+    const int64_t *seg_first, *part_first;               // [R + 1]
+    int64_t n_part;
+    const int32_t *mot;                                  // the scorable motifs (or models)
+    int64_t R;
+    double *score;                                       // [P][R]
+    int32_t *pos;
+    int8_t *strand;
+    const BestPart *part;                                // [P][n_part]
+};
 
 // grid = (ceil(segments / kBestWaves), tiles).  LDS: the tile's tables in LDS; !LDS: one motif per tile, its table in HBM.
 template <bool LDS>
@@ -167,7 +167,7 @@ __global__ void __launch_bounds__(kBestThreads, 4) best_kernel(const BestArgs A,
 }
 
 // grid = (regions of more than one segment, ceil(scorable motifs / 4)): a wave folds the partials of one (motif, region) in segment order
-__global__ void __launch_bounds__(256) best_reduce_kernel(const BestArgs A, const int64_t *__restrict__ long_regions, int32_t k_first, int32_t n_mot) {
+__global__ void __launch_bounds__(256) best_reduce_kernel(const BestTail A, const int64_t *__restrict__ long_regions, int32_t k_first, int32_t n_mot) {
     const int32_t k = k_first + (int32_t) blockIdx.y * 4 + (int32_t) (threadIdx.x >> 6);
     if (k >= n_mot) return;
     const int lane = (int) (threadIdx.x & 63u);
@@ -186,13 +186,11 @@ __global__ void __launch_bounds__(256) best_reduce_kernel(const BestArgs A, cons
 }
 
 // grid = (ceil(R / 256), unscorable motifs): their rows hold no winner
-__global__ void __launch_bounds__(256) best_fill_kernel(const int32_t *__restrict__ motifs, int64_t R, double *__restrict__ score, int32_t *__restrict__ pos,
-                                                        int8_t *__restrict__ strand) {
+__global__ void __launch_bounds__(256) best_fill_kernel(const BestTail A, const int32_t *__restrict__ motifs) {
     const int64_t r = (int64_t) blockIdx.x * 256 + threadIdx.x;
-    if (r >= R) return;
-    put_best(score, pos, strand, (int64_t) motifs[blockIdx.y] * R + r, 0.0, kNoKey);
+    if (r >= A.R) return;
+    put_best(A.score, A.pos, A.strand, (int64_t) motifs[blockIdx.y] * A.R + r, 0.0, kNoKey);
 }
-
 
 }  // namespace
 
@@ -234,14 +232,90 @@ int dense_raise_lds(DeviceCtx *c, const void *kernel, size_t need, size_t most) 
     return MS_OK;
 }
 
-int dense_finish(DeviceCtx *c, const char *what, DenseHead *h) {
-    (void) hipEventRecord(c->ev[1], c->stream);
-    const hipError_t he = hipStreamSynchronize(c->stream);
-    if (he != hipSuccess) return hip_rc(he, what);
-    float ms01 = 0;
-    (void) hipEventElapsedTime(&ms01, c->ev[0], c->ev[1]);
-    h->device_ms = ms01;
+int dense_check(const void *set, const ms_seqset *seqs, int strand_mask) {
+    if (!require_device()) return MS_ERR_RUNTIME;
+    if (!set || !seqs) { set_error("NULL handle"); return MS_ERR_INVALID; }
+    if (strand_mask < 1 || strand_mask > 3) { set_error("invalid strand mask %d (1 '+', 2 '-', 3 both)", strand_mask); return MS_ERR_INVALID; }
     return MS_OK;
+}
+
+int dense_open(DenseRun *run, const DenseGeom &g, const int32_t *widths, int32_t P, std::mutex *set_mu, const ms_seqset *seqs, const char *fit_what,
+               const std::function<bool(int32_t)> &walked) {
+    int rc = dense_regions_fit(seqs, fit_what);
+    if (rc) return rc;
+    if ((rc = get_ctx(seqs->device, &run->c))) return rc;
+    // ---- the plan, on the host: segments of the regions, tiles of the motifs (ms_dense_plan.h)
+    if ((rc = dense_plan_for(g, widths, P, seqs, kBestWaves, walked, &run->plan))) return rc;
+    run->gx = (unsigned) ((run->plan.n_seg + kBestWaves - 1) / kBestWaves);
+    run->ds = dense_slots(run->cv, run->plan);
+    run->lds = (run->plan.max_tile + 1) * sizeof(double2);
+    run->lds_most = ((size_t) g.tile_entries + 1) * sizeof(double2);
+    DeviceCtx *c = run->c;
+    run->lk_dev = std::unique_lock<std::mutex>(c->mu);
+    if (set_mu) run->lk_set = std::unique_lock<std::mutex>(*set_mu);
+    MS_HIP(hipSetDevice(c->device));
+    run->st = c->stream;
+    return MS_OK;
+}
+
+int dense_start(DenseRun *run, ms_pwmset *pwms, const ms_seqset *seqs, const void *kernel) {
+    int rc = run->work.alloc(run->c, run->st, run->cv.bytes());
+    if (rc) return rc;
+    if (pwms && (rc = pwmset_upload(pwms, run->c->device, run->st))) return rc;
+    if ((rc = seqset_pack_pending(seqs, run->st))) return rc;
+    if ((rc = dense_raise_lds(run->c, kernel, run->lds, run->lds_most))) return rc;
+    return dense_upload(run->plan, run->ds, run->work.p, run->st, &run->d);
+}
+
+int dense_end(DenseRun *run, const char *what, DenseHead *h) {
+    (void) hipEventRecord(run->c->ev[1], run->st);
+    if (const int rc = run->work.wait(what)) return rc;
+    float ms01 = 0;
+    (void) hipEventElapsedTime(&ms01, run->c->ev[0], run->c->ev[1]);
+    h->device_ms = ms01;
+    run->work.release();
+    return MS_OK;
+}
+
+int best_alloc(const DenseRun &run, int32_t P, int64_t R, BestPtr *res) {
+    // ---- 13 bytes per cell, 16 per partial: both blocks are allocated before anything is launched, and a failure there is the MS_ERR_NOMEM
+    // of the header (the test here only keeps the byte counts below inside size_t)
+    if (13.0 * (double) P * (double) R + 16.0 * (double) P * (double) run.plan.n_part >= 0.5 * (double) std::numeric_limits<size_t>::max()) {
+        set_error("%d x %lld cells do not fit the device", P, (long long) R);
+        return MS_ERR_NOMEM;
+    }
+    ms_best *b = new (std::nothrow) ms_best();
+    if (!b) { set_error("out of host memory"); return MS_ERR_NOMEM; }
+    res->reset(b);
+    b->device = run.c->device;
+    b->P = P;
+    b->R = R;
+    const size_t cz = std::max<size_t>((size_t) P * (size_t) R, 1);
+    Carve rv;
+    const auto s_score = rv.add<double>(cz);
+    const auto s_pos = rv.add<int32_t>(cz);
+    const auto s_strand = rv.add<int8_t>(cz);
+    if (const int rc = pool_alloc(run.c, rv.bytes(), &b->block, &b->block_bytes)) return rc;
+    b->d_score = Carve::at(b->block, s_score);
+    b->d_pos = Carve::at(b->block, s_pos);
+    b->d_strand = Carve::at(b->block, s_strand);
+    return MS_OK;
+}
+
+int best_tail(const DenseRun &run, const char *what, const BestPart *part, ms_best *b) {
+    const DensePlan &plan = run.plan;
+    const int64_t n_mot = (int64_t) plan.mot.size();
+    const hipStream_t st = run.st;
+    const BestTail A = {run.d.seg_first, run.d.part_first, plan.n_part, run.d.mot, b->R, b->d_score, b->d_pos, b->d_strand, part};
+    const std::string reduce = std::string(what) + " reduction", fill = std::string(what) + " fill";
+    int rc = MS_OK;
+    if (!plan.long_regions.empty()) rc = dense_chunks((n_mot + 3) / 4, reduce.c_str(), [&](int64_t g0, unsigned ny) {                  // four motifs a block
+        hipLaunchKernelGGL(best_reduce_kernel, dim3((unsigned) plan.long_regions.size(), ny), dim3(256), 0, st, A, run.d.long_regions, (int32_t) (4 * g0), (int32_t) n_mot);
+    });
+    if (!rc) rc = dense_chunks((int64_t) plan.skipped.size(), fill.c_str(), [&](int64_t u0, unsigned ny) {
+        hipLaunchKernelGGL(best_fill_kernel, dim3((unsigned) ((b->R + 255) / 256), ny), dim3(256), 0, st, A, run.d.skipped + u0);
+    });
+    return rc;
 }
 
 void dense_release(DenseHead *h) {
@@ -290,95 +364,46 @@ void ms_best_free(ms_best *b) {
 int ms_scan_best(const ms_pwmset *pwms_c, const ms_seqset *seqs, int strand_mask, uint32_t flags, ms_best **out) {
     if (!out) { set_error("out is NULL"); return MS_ERR_INVALID; }
     *out = nullptr;
-    if (!require_device()) return MS_ERR_RUNTIME;
-    if (!pwms_c || !seqs) { set_error("NULL handle"); return MS_ERR_INVALID; }
-    if (strand_mask < 1 || strand_mask > 3) { set_error("invalid strand mask %d (1 '+', 2 '-', 3 both)", strand_mask); return MS_ERR_INVALID; }
+    int rc = dense_check(pwms_c, seqs, strand_mask);
+    if (rc) return rc;
     if (flags != 0u) { set_error("unknown best-site scan flags 0x%x", flags); return MS_ERR_INVALID; }
     ms_pwmset *pwms = const_cast<ms_pwmset *>(pwms_c);
     const int32_t P = pwms->P;
     const int64_t R = seqs->R;
-    int rc = dense_regions_fit(seqs, "positions are");
-    if (rc) return rc;
-    DeviceCtx *c;
-    if ((rc = get_ctx(seqs->device, &c))) return rc;
-    std::unique_ptr<ms_best> res(new (std::nothrow) ms_best());
-    if (!res) { set_error("out of host memory"); return MS_ERR_NOMEM; }
-    res->device = c->device;
-    res->P = P;
-    res->R = R;
+    BestPtr res(nullptr, ms_best_free);                  // (in front of the run: freed behind the run's wait for the stream)
+    DenseRun run;
+    if ((rc = dense_open(&run, kBestGeom, pwms->widths.data(), P, &pwms->mu, seqs, "positions are", [&](int32_t m) { return scorable(pwms, m); }))) return rc;
+    if ((rc = best_alloc(run, P, R, &res))) return rc;
+    if (P == 0 || R == 0) { *out = res.release(); return MS_OK; }
+    const auto s_part = run.cv.add<BestPart>((size_t) P * (size_t) run.plan.n_part);
+    if ((rc = dense_start(&run, pwms, seqs, reinterpret_cast<const void *>(best_kernel<true>)))) return rc;
 
-    // ---- the plan, on the host: segments of the regions, tiles of the motifs (ms_dense_plan.h)
-    DensePlan plan;
-    if ((rc = dense_plan_for(kBestGeom, pwms, seqs, kBestWaves, [&](int32_t m) { return scorable(pwms, m); }, &plan))) return rc;
-    const int64_t n_seg = plan.n_seg, n_part = plan.n_part, n_mot = (int64_t) plan.mot.size();
-
-    // ---- 13 bytes per cell, 16 per partial: both blocks are allocated before anything is launched, and a failure there is the MS_ERR_NOMEM
-    // of the header (the test here only keeps the byte counts below inside size_t)
-    if (13.0 * (double) P * (double) R + 16.0 * (double) P * (double) n_part >= 0.5 * (double) std::numeric_limits<size_t>::max()) {
-        set_error("%d x %lld cells do not fit the device", P, (long long) R);
-        return MS_ERR_NOMEM;
-    }
-    const size_t cells = (size_t) P * (size_t) R, cz = std::max<size_t>(cells, 1);
-    std::lock_guard<std::mutex> lk_dev(c->mu);
-    std::lock_guard<std::mutex> lk_pwm(pwms->mu);
-    MS_HIP(hipSetDevice(c->device));
-    Carve rv;
-    const auto s_score = rv.add<double>(cz);
-    const auto s_pos = rv.add<int32_t>(cz);
-    const auto s_strand = rv.add<int8_t>(cz);
-    if ((rc = pool_alloc(c, rv.bytes(), &res->block, &res->block_bytes))) return rc;
-    res->d_score = Carve::at(res->block, s_score);
-    res->d_pos = Carve::at(res->block, s_pos);
-    res->d_strand = Carve::at(res->block, s_strand);
-    ms_best *raw = res.release();
-    if (cells == 0) { *out = raw; return MS_OK; }
-
-    Carve cv;
-    const DenseSlots ds = dense_slots(cv, plan);
-    const auto s_part = cv.add<BestPart>((size_t) P * (size_t) n_part);
-    void *wblk = nullptr;
-    size_t wgot = 0;
-    if ((rc = pool_alloc(c, cv.bytes(), &wblk, &wgot))) { ms_best_free(raw); return rc; }
-    auto fail = [&](int code) { pool_free(c, wblk, wgot); ms_best_free(raw); return code; };
-
-    const hipStream_t st = c->stream;
-    if ((rc = pwmset_upload(pwms, c->device, st))) return fail(rc);
-    if ((rc = seqset_pack_pending(seqs, st))) return fail(rc);
-    const size_t lds = (plan.max_tile + 1) * sizeof(double2);
-    if ((rc = dense_raise_lds(c, reinterpret_cast<const void *>(best_kernel<true>), lds, (kBestTileEntries + 1) * sizeof(double2)))) return fail(rc);
-    DenseDev d;
-    if ((rc = dense_upload(plan, ds, wblk, st, &d))) return fail(rc);
-
+    const DensePlan &plan = run.plan;
+    const DenseDev &d = run.d;
     BestArgs A;
     A.codes = seqs->d_codes; A.nmask = seqs->d_nmask; A.offsets = seqs->d_offsets; A.R = R;
     A.seg_first = d.seg_first; A.part_first = d.part_first;
-    A.n_seg = n_seg; A.n_part = n_part;
+    A.n_seg = plan.n_seg; A.n_part = plan.n_part;
     A.tile_first = d.tile_first; A.mot = d.mot;
     A.Pw = dev_pwm(pwms);
     A.strand_mask = strand_mask;
-    A.score = raw->d_score; A.pos = raw->d_pos; A.strand = raw->d_strand;
-    A.part = Carve::at(wblk, s_part);
+    A.score = res->d_score; A.pos = res->d_pos; A.strand = res->d_strand;
+    A.part = Carve::at(run.work.p, s_part);
     BestArgs Aw = A;                                     // the wide motifs: one "tile" each
     Aw.tile_first = d.wide_first;
 
-    (void) hipEventRecord(c->ev[0], st);
-    const unsigned gx = (unsigned) ((n_seg + kBestWaves - 1) / kBestWaves);
+    const hipStream_t st = run.st;
+    (void) hipEventRecord(run.c->ev[0], st);
     rc = dense_chunks((int64_t) plan.tile_first.size() - 1, "best-site kernel", [&](int64_t t0, unsigned ny) {
-        hipLaunchKernelGGL(best_kernel<true>, dim3(gx, ny), dim3(kBestThreads), lds, st, A, (int32_t) t0);
+        hipLaunchKernelGGL(best_kernel<true>, dim3(run.gx, ny), dim3(kBestThreads), run.lds, st, A, (int32_t) t0);
     });
     if (!rc) rc = dense_chunks((int64_t) plan.wide_first.size() - 1, "best-site kernel (tables in HBM)", [&](int64_t t0, unsigned ny) {
-        hipLaunchKernelGGL(best_kernel<false>, dim3(gx, ny), dim3(kBestThreads), 0, st, Aw, (int32_t) t0);
+        hipLaunchKernelGGL(best_kernel<false>, dim3(run.gx, ny), dim3(kBestThreads), 0, st, Aw, (int32_t) t0);
     });
-    if (!rc && !plan.long_regions.empty()) rc = dense_chunks((n_mot + 3) / 4, "best-site reduction", [&](int64_t g0, unsigned ny) {      // four motifs a block
-        hipLaunchKernelGGL(best_reduce_kernel, dim3((unsigned) plan.long_regions.size(), ny), dim3(256), 0, st, A, d.long_regions, (int32_t) (4 * g0), (int32_t) n_mot);
-    });
-    if (!rc) rc = dense_chunks((int64_t) plan.skipped.size(), "best-site fill", [&](int64_t u0, unsigned ny) {
-        hipLaunchKernelGGL(best_fill_kernel, dim3((unsigned) ((R + 255) / 256), ny), dim3(256), 0, st, d.skipped + u0, R, raw->d_score, raw->d_pos, raw->d_strand);
-    });
-    if (!rc) rc = dense_finish(c, "best-site scan", raw);
-    if (rc) return fail(rc);
-    pool_free(c, wblk, wgot);
-    *out = raw;
+    if (!rc) rc = best_tail(run, "best-site", A.part, res.get());
+    if (!rc) rc = dense_end(&run, "best-site scan", res.get());
+    if (rc) return rc;
+    *out = res.release();
     return MS_OK;
 }
 

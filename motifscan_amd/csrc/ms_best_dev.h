@@ -1,14 +1,18 @@
 // ms_best_dev.h -- the DEVICE helpers of the kernels that score every window of a cell, and the test for a motif the reference never
 // reports a site of (scorable).  With ms_allelebest.hip (per variant haplotype) ms_best.hip shares the total-order wave reduction; the
-// four dense walks (best_kernel, affinity_kernel, scorehist_kernel, and expcounts_kernel of ms_expcounts.hip: the affinity walk taken a
-// second time) share the walk's kBest* sizes, the column loop over an LDS tile of
-// tables, and the walk's three steps as functions -- the staging of a tile, a segment's words into registers, the raw sums of one strip
-// of window starts.  best_kernel keeps these three steps written out in its own body: called through the functions, hipcc schedules its
+// five dense walks (best_kernel, affinity_kernel, scorehist_kernel, expcounts_kernel of ms_expcounts.hip: the affinity walk taken a
+// second time, and dimodel_best_kernel of ms_dimodel.hip: the best-site walk over first-order models) share the walk's kBest* sizes and
+// the walk's steps as functions -- the staging of a tile, a segment's words into registers and, for the PWM walks, the column loop over
+// an LDS tile of tables and the raw sums of one strip of window starts.  The two best-site walks also share what a cell ends in: a
+// segment's partial (BestPart) and the write of a cell (put_best); the kernels behind them that fold the partials of long regions and
+// fill the rows that are not scored are compiled once, in ms_best.hip (best_tail, ms_handles.h).
+// best_kernel keeps the three steps written out in its own body: called through the functions, hipcc schedules its
 // LDS form differently (its disassembly changes), and that kernel's code is to stay as measured.  A change to a step is made in both
 // places -- the functions here, which affinity_kernel, scorehist_kernel and expcounts_kernel call, and best_kernel's body.
 // The HOST side of the walks is not here: the plan (DenseGeom, dense_plan) and its layout in a work block are ms_dense_plan.h,
-// plain C++; its upload, the chunked launches, the LDS limit and the head of the two result handles (DenseHead) are declared in
-// ms_handles.h and implemented once, in ms_best.hip.
+// plain C++; the driver of the three matrix walks (DenseRun), the owner of a work block (WorkBlock), the plan's upload, the chunked
+// launches, the LDS limit and the head of the two result handles (DenseHead) are declared in ms_handles.h and implemented once, in
+// ms_best.hip.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -18,6 +22,12 @@
 #include "ms_handles.h"
 
 namespace ms {
+
+struct BestPart {                                        // a segment's best of one motif or model (declared in ms_handles.h)
+    double q;
+    int32_t pos;                                         // -1: no winner
+    int32_t strand;
+};
 
 namespace {
 
@@ -40,6 +50,14 @@ __device__ __forceinline__ void wave_best(double &q, uint64_t &key) {
         const unsigned long long ok = __shfl_xor((unsigned long long) key, d);
         if (oq > q || (oq == q && ok < key)) { q = oq; key = ok; }
     }
+}
+
+// a cell of the three best-site planes: the winner (q, key = pos << 2 | strand), or the "no winner" triple for kNoKey
+__device__ __forceinline__ void put_best(double *__restrict__ score, int32_t *__restrict__ pos, int8_t *__restrict__ strand, int64_t cell, double q, uint64_t key) {
+    const bool won = key != kNoKey;
+    score[cell] = won ? q : __builtin_nan("");
+    pos[cell] = won ? (int32_t) (key >> 2) : -1;
+    strand[cell] = won ? (int8_t) (key & 3u) : (int8_t) 0;
 }
 
 // (the dense walks over an LDS tile of tables: best_kernel, scorehist_kernel) up to 32 columns out of the registers: table entries tb + 4 c of the LDS tile, in column order; bit c of skip: the column adds entry 0

@@ -1,4 +1,4 @@
-// ms_dense_plan.h -- the host's plan of a dense walk (ms_scan_best, ms_scan_affinity, ms_scan_score_histogram, ms_affinity_expected_counts: every window of every
+// ms_dense_plan.h -- the host's plan of a dense walk (ms_scan_best, ms_scan_affinity, ms_scan_score_histogram, ms_affinity_expected_counts, ms_scan_best_dimodels: every window of every
 // (motif, region) cell) and its layout in a work block: segments of the regions, tiles of the motifs.  Plain C++, no HIP include, so
 // that it is checked on the CPU (tests/sanitize/dense_plan_asan.cpp), as ms_place.h is.
 #pragma once

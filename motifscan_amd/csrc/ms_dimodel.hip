@@ -19,7 +19,9 @@
 //
 // A window that holds a non-ACGT base has no score (one test of the mask word per chunk) and never wins -- unlike the PWM walks, where
 // such a base adds +0.0.  The divide, the tie rule, the total-order wave reduction, the partials of long regions and the "no winner"
-// triple are ms_scan_best's, argued in ms_best.hip's header; best_kernel itself is not touched.
+// triple are ms_scan_best's, argued in ms_best.hip's header; best_kernel itself is not touched.  Only the walk's kernel is here: the host
+// driver (DenseRun), the allocation of the ms_best and the kernels that fold the partials and fill the unscorable rows (best_alloc,
+// best_tail) are ms_best.hip's, through ms_handles.h.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -49,12 +51,6 @@ namespace {
 static_assert(sizeof(DiEntry) == sizeof(double2), "the host's entry is the device's double2");
 constexpr DenseGeom kDiGeom = {kBestSegWindows, kDiTileEntries / 4, kDiTileEntries, true};
 
-struct DiPart {                                          // a segment's best of one model
-    double q;
-    int32_t pos;                                         // -1: no winner
-    int32_t strand;
-};
-
 struct DiArgs {
     const uint32_t *codes, *nmask;
     const int64_t *offsets;                              // [R + 1]
@@ -72,15 +68,8 @@ struct DiArgs {
     double *score;                                       // [P][R]
     int32_t *pos;
     int8_t *strand;
-    DiPart *part;                                        // [P][n_part]
+    BestPart *part;                                      // [P][n_part]
 };
-
-__device__ __forceinline__ void di_put(double *__restrict__ score, int32_t *__restrict__ pos, int8_t *__restrict__ strand, int64_t cell, double q, uint64_t key) {
-    const bool won = key != kNoKey;
-    score[cell] = won ? q : __builtin_nan("");
-    pos[cell] = won ? (int32_t) (key >> 2) : -1;
-    strand[cell] = won ? (int8_t) (key & 3u) : (int8_t) 0;
-}
 
 // n <= 31 steps of one chunk: the entries pb + 16 i + (four bits of the pair) of the LDS tile, added in step order; a step from n on adds entry 0
 __device__ __forceinline__ void di_steps31(const double2 *__restrict__ lds, uint32_t pb, int n, uint64_t cw, double &fwd, double &rev) {
@@ -171,9 +160,9 @@ __global__ void __launch_bounds__(kBestThreads, 4) dimodel_best_kernel(const DiA
         }
         wave_best(best_q, best_key);
         if (lane == 0) {
-            if (whole) di_put(A.score, A.pos, A.strand, (int64_t) m * A.R + r, best_q, best_key);
+            if (whole) put_best(A.score, A.pos, A.strand, (int64_t) m * A.R + r, best_q, best_key);
             else {
-                DiPart p;
+                BestPart p;
                 p.q = best_q;
                 p.pos = best_key != kNoKey ? (int32_t) (best_key >> 2) : -1;
                 p.strand = best_key != kNoKey ? (int32_t) (best_key & 3u) : 0;
@@ -181,33 +170,6 @@ __global__ void __launch_bounds__(kBestThreads, 4) dimodel_best_kernel(const DiA
             }
         }
     }
-}
-
-// grid = (regions of more than one segment, ceil(scorable models / 4)): a wave folds the partials of one (model, region) in segment order
-__global__ void __launch_bounds__(256) dimodel_reduce_kernel(const DiArgs A, const int64_t *__restrict__ long_regions, int32_t k_first, int32_t n_mot) {
-    const int32_t k = k_first + (int32_t) blockIdx.y * 4 + (int32_t) (threadIdx.x >> 6);
-    if (k >= n_mot) return;
-    const int lane = (int) (threadIdx.x & 63u);
-    const int32_t m = A.mot[k];
-    const int64_t r = long_regions[blockIdx.x];
-    const int64_t n = A.seg_first[r + 1] - A.seg_first[r];
-    const DiPart *__restrict__ part = A.part + (int64_t) m * A.n_part + A.part_first[r];
-    double best_q = -std::numeric_limits<double>::infinity();
-    uint64_t best_key = kNoKey;
-    for (int64_t s = lane; s < n; s += 64) {              // ascending: an equal q keeps the earlier segment
-        const DiPart p = part[s];
-        if (p.pos >= 0 && p.q > best_q) { best_q = p.q; best_key = ((uint64_t) (uint32_t) p.pos << 2) | (uint32_t) p.strand; }
-    }
-    wave_best(best_q, best_key);
-    if (lane == 0) di_put(A.score, A.pos, A.strand, (int64_t) m * A.R + r, best_q, best_key);
-}
-
-// grid = (ceil(R / 256), unscorable models): their rows hold no winner
-__global__ void __launch_bounds__(256) dimodel_fill_kernel(const int32_t *__restrict__ models, int64_t R, double *__restrict__ score, int32_t *__restrict__ pos,
-                                                           int8_t *__restrict__ strand) {
-    const int64_t r = (int64_t) blockIdx.x * 256 + threadIdx.x;
-    if (r >= R) return;
-    di_put(score, pos, strand, (int64_t) models[blockIdx.y] * R + r, 0.0, kNoKey);
 }
 
 }  // namespace
@@ -284,101 +246,58 @@ void ms_dimodelset_free(ms_dimodelset *p) { delete p; }
 int ms_scan_best_dimodels(const ms_dimodelset *models, const ms_seqset *seqs, int strand_mask, uint32_t flags, ms_best **out) {
     if (!out) { set_error("out is NULL"); return MS_ERR_INVALID; }
     *out = nullptr;
-    if (!require_device()) return MS_ERR_RUNTIME;
-    if (!models || !seqs) { set_error("NULL handle"); return MS_ERR_INVALID; }
-    if (strand_mask < 1 || strand_mask > 3) { set_error("invalid strand mask %d (1 '+', 2 '-', 3 both)", strand_mask); return MS_ERR_INVALID; }
+    int rc = dense_check(models, seqs, strand_mask);
+    if (rc) return rc;
     if (flags != 0u) { set_error("unknown first-order best-site scan flags 0x%x", flags); return MS_ERR_INVALID; }
     const int32_t P = models->P;
     const int64_t R = seqs->R;
-    int rc = dense_regions_fit(seqs, "positions are");
-    if (rc) return rc;
-    DeviceCtx *c;
-    if ((rc = get_ctx(seqs->device, &c))) return rc;
-    std::unique_ptr<ms_best> res(new (std::nothrow) ms_best());
-    if (!res) { set_error("out of host memory"); return MS_ERR_NOMEM; }
-    res->device = c->device;
-    res->P = P;
-    res->R = R;
-
-    // ---- the plan, on the host: segments of the regions, tiles of the models by their pseudo-widths (ms_dense_plan.h)
-    DensePlan plan;
-    if ((rc = dense_plan_for(kDiGeom, models->pseudo.data(), P, seqs, kBestWaves, [&](int32_t m) { return models->ok[(size_t) m] != 0; }, &plan))) return rc;
-    const int64_t n_seg = plan.n_seg, n_part = plan.n_part, n_mot = (int64_t) plan.mot.size();
-
-    // ---- 13 bytes per cell, 16 per partial: both blocks are allocated before anything is launched (ms_scan_best's rule)
-    if (13.0 * (double) P * (double) R + 16.0 * (double) P * (double) n_part >= 0.5 * (double) std::numeric_limits<size_t>::max()) {
-        set_error("%d x %lld cells do not fit the device", P, (long long) R);
-        return MS_ERR_NOMEM;
-    }
-    const size_t cells = (size_t) P * (size_t) R, cz = std::max<size_t>(cells, 1);
-    std::lock_guard<std::mutex> lk_dev(c->mu);
-    MS_HIP(hipSetDevice(c->device));
-    Carve rv;
-    const auto s_score = rv.add<double>(cz);
-    const auto s_pos = rv.add<int32_t>(cz);
-    const auto s_strand = rv.add<int8_t>(cz);
-    if ((rc = pool_alloc(c, rv.bytes(), &res->block, &res->block_bytes))) return rc;
-    res->d_score = Carve::at(res->block, s_score);
-    res->d_pos = Carve::at(res->block, s_pos);
-    res->d_strand = Carve::at(res->block, s_strand);
-    ms_best *raw = res.release();
-    if (cells == 0) { *out = raw; return MS_OK; }
+    BestPtr res(nullptr, ms_best_free);                  // (in front of the run: freed behind the run's wait for the stream)
+    DenseRun run;
+    // the tiles of the models go by their pseudo-widths (ms_dense_plan.h)
+    if ((rc = dense_open(&run, kDiGeom, models->pseudo.data(), P, nullptr, seqs, "positions are", [&](int32_t m) { return models->ok[(size_t) m] != 0; }))) return rc;
+    if ((rc = best_alloc(run, P, R, &res))) return rc;
+    if (P == 0 || R == 0) { *out = res.release(); return MS_OK; }
+    const DensePlan &plan = run.plan;
 
     // ---- the work block: the plan, the set's tables and per-model arrays (a model set keeps no device copy: a few KB per model, uploaded
     // per call in front of the timed launches), the partials
-    Carve cv;
-    const DenseSlots ds = dense_slots(cv, plan);
+    Carve &cv = run.cv;
     const auto s_tab = cv.add<double2>(models->tab.size());
     const auto s_tab_off = cv.add<int64_t>((size_t) P);
     const auto s_width = cv.add<int32_t>((size_t) P);
     const auto s_max_raw = cv.add<double>((size_t) P);
-    const auto s_part = cv.add<DiPart>((size_t) P * (size_t) n_part);
-    void *wblk = nullptr;
-    size_t wgot = 0;
-    if ((rc = pool_alloc(c, cv.bytes(), &wblk, &wgot))) { ms_best_free(raw); return rc; }
-    auto fail = [&](int code) { (void) hipStreamSynchronize(c->stream); pool_free(c, wblk, wgot); ms_best_free(raw); return code; };
-
-    const hipStream_t st = c->stream;
-    if ((rc = seqset_pack_pending(seqs, st))) return fail(rc);
-    const size_t lds = (plan.max_tile + 1) * sizeof(double2);
-    if ((rc = dense_raise_lds(c, reinterpret_cast<const void *>(dimodel_best_kernel), lds, ((size_t) kDiTileEntries + 1) * sizeof(double2)))) return fail(rc);
-    DenseDev d;
-    if ((rc = dense_upload(plan, ds, wblk, st, &d))) return fail(rc);
+    const auto s_part = cv.add<BestPart>((size_t) P * (size_t) plan.n_part);
+    if ((rc = dense_start(&run, nullptr, seqs, reinterpret_cast<const void *>(dimodel_best_kernel)))) return rc;
+    const hipStream_t st = run.st;
     hipError_t he = hipSuccess;
     auto up = [&](const auto &v, auto slot) {
-        auto *p = Carve::at(wblk, slot);
+        auto *p = Carve::at(run.work.p, slot);
         if (he == hipSuccess) he = hipMemcpyAsync(p, v.data(), sizeof(v[0]) * v.size(), hipMemcpyHostToDevice, st);
         return p;
     };
+    const DenseDev &d = run.d;
     DiArgs A;
     A.tab = reinterpret_cast<const double2 *>(up(models->tab, s_tab));
     A.tab_off = up(models->tab_off, s_tab_off);
     A.width = up(models->widths, s_width);
     A.max_raw = up(models->max_raw, s_max_raw);
-    if (he != hipSuccess) return fail(hip_rc(he, "upload of the models"));
+    if (he != hipSuccess) return hip_rc(he, "upload of the models");
     A.codes = seqs->d_codes; A.nmask = seqs->d_nmask; A.offsets = seqs->d_offsets; A.R = R;
     A.seg_first = d.seg_first; A.part_first = d.part_first;
-    A.n_seg = n_seg; A.n_part = n_part;
+    A.n_seg = plan.n_seg; A.n_part = plan.n_part;
     A.tile_first = d.tile_first; A.mot = d.mot;
     A.strand_mask = strand_mask;
-    A.score = raw->d_score; A.pos = raw->d_pos; A.strand = raw->d_strand;
-    A.part = Carve::at(wblk, s_part);
+    A.score = res->d_score; A.pos = res->d_pos; A.strand = res->d_strand;
+    A.part = Carve::at(run.work.p, s_part);
 
-    (void) hipEventRecord(c->ev[0], st);
-    const unsigned gx = (unsigned) ((n_seg + kBestWaves - 1) / kBestWaves);
+    (void) hipEventRecord(run.c->ev[0], st);
     rc = dense_chunks((int64_t) plan.tile_first.size() - 1, "first-order best-site kernel", [&](int64_t t0, unsigned ny) {
-        hipLaunchKernelGGL(dimodel_best_kernel, dim3(gx, ny), dim3(kBestThreads), lds, st, A, (int32_t) t0);
+        hipLaunchKernelGGL(dimodel_best_kernel, dim3(run.gx, ny), dim3(kBestThreads), run.lds, st, A, (int32_t) t0);
     });
-    if (!rc && !plan.long_regions.empty()) rc = dense_chunks((n_mot + 3) / 4, "first-order best-site reduction", [&](int64_t g0, unsigned ny) {      // four models a block
-        hipLaunchKernelGGL(dimodel_reduce_kernel, dim3((unsigned) plan.long_regions.size(), ny), dim3(256), 0, st, A, d.long_regions, (int32_t) (4 * g0), (int32_t) n_mot);
-    });
-    if (!rc) rc = dense_chunks((int64_t) plan.skipped.size(), "first-order best-site fill", [&](int64_t u0, unsigned ny) {
-        hipLaunchKernelGGL(dimodel_fill_kernel, dim3((unsigned) ((R + 255) / 256), ny), dim3(256), 0, st, d.skipped + u0, R, raw->d_score, raw->d_pos, raw->d_strand);
-    });
-    if (!rc) rc = dense_finish(c, "first-order best-site scan", raw);
-    if (rc) return fail(rc);
-    pool_free(c, wblk, wgot);
-    *out = raw;
+    if (!rc) rc = best_tail(run, "first-order best-site", A.part, res.get());
+    if (!rc) rc = dense_end(&run, "first-order best-site scan", res.get());
+    if (rc) return rc;
+    *out = res.release();
     return MS_OK;
 }
 

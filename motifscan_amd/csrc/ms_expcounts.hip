@@ -287,26 +287,25 @@ int ms_affinity_expected_counts(const ms_affinity *aff, const ms_pwmset *pwms_c,
     const DenseSlots ds = dense_slots(cv, plan);
     const auto s_counts = cv.add<unsigned long long>(on_dev[0] ? 0 : out_bytes[0] / 8);
     const auto s_total = cv.add<unsigned long long>((size_t) rows), s_nreg = cv.add<unsigned long long>((size_t) rows);
-    void *wblk = nullptr;
-    size_t wgot = 0;
-    if ((rc = pool_alloc(c, cv.bytes() + 256, &wblk, &wgot))) return rc;
     const hipStream_t st = c->stream;
-    auto fail = [&](int code) { (void) hipStreamSynchronize(st); pool_free(c, wblk, wgot); return code; };
+    WorkBlock work;                                    // (behind the locks: it goes back behind a wait for the stream, whichever way this returns)
+    if ((rc = work.alloc(c, st, cv.bytes() + 256))) return rc;
+    void *const wblk = work.p;
     unsigned long long *d_counts = on_dev[0] ? reinterpret_cast<unsigned long long *>(counts) : Carve::at(wblk, s_counts);
     unsigned long long *d_total = Carve::at(wblk, s_total), *d_nreg = Carve::at(wblk, s_nreg);
 
     hipError_t he = hipMemsetAsync(d_counts, 0, out_bytes[0], st);
-    if (he != hipSuccess) return fail(hip_rc(he, "clearing the expected counts"));
+    if (he != hipSuccess) return hip_rc(he, "clearing the expected counts");
     (void) hipEventRecord(c->ev[0], st);
     if (n_tiles > 0 && n_groups > 0) {
-        if ((rc = pwmset_upload(pwms, c->device, st))) return fail(rc);
-        if ((rc = seqset_pack_pending(seqs, st))) return fail(rc);
+        if ((rc = pwmset_upload(pwms, c->device, st))) return rc;
+        if ((rc = seqset_pack_pending(seqs, st))) return rc;
         const size_t lds_tab = plan.max_tile + 1;
         const size_t lds = lds_tab * sizeof(double2) + (plan.max_tile / 4) * (size_t) kExpAccBytesPerColumn;
         const size_t lds_most = (size_t) (kExpTileEntries + 1) * sizeof(double2) + (size_t) (kExpTileEntries / 4) * (size_t) kExpAccBytesPerColumn;
-        if ((rc = dense_raise_lds(c, reinterpret_cast<const void *>(expcounts_kernel), lds, lds_most))) return fail(rc);
+        if ((rc = dense_raise_lds(c, reinterpret_cast<const void *>(expcounts_kernel), lds, lds_most))) return rc;
         DenseDev d;
-        if ((rc = dense_upload(plan, ds, wblk, st, &d))) return fail(rc);
+        if ((rc = dense_upload(plan, ds, wblk, st, &d))) return rc;
         ExpArgs A;
         A.codes = seqs->d_codes; A.nmask = seqs->d_nmask; A.offsets = seqs->d_offsets; A.R = R;
         A.seg_first = d.seg_first;
@@ -326,20 +325,19 @@ int ms_affinity_expected_counts(const ms_affinity *aff, const ms_pwmset *pwms_c,
         rc = dense_chunks(n_tiles, "expected-counts kernel", [&](int64_t t0, unsigned ny) {
             hipLaunchKernelGGL(expcounts_kernel, dim3(gx, ny), dim3(kBestThreads), lds, st, A, (int32_t) t0);
         });
-        if (rc) return fail(rc);
+        if (rc) return rc;
     }
     hipLaunchKernelGGL(expcounts_finish_kernel, dim3((unsigned) rows), dim3(256), 0, st, aff->d_n_terms, R, m0, d_counts, C, d_total, d_nreg);
-    if ((he = hipGetLastError()) != hipSuccess) return fail(hip_rc(he, "expected-counts finish kernel"));
+    if ((he = hipGetLastError()) != hipSuccess) return hip_rc(he, "expected-counts finish kernel");
     (void) hipEventRecord(c->ev[1], st);
     if (!on_dev[0]) he = hipMemcpyAsync(counts, d_counts, out_bytes[0], hipMemcpyDeviceToHost, st);
     if (he == hipSuccess && total) he = hipMemcpyAsync(total, d_total, out_bytes[1], on_dev[1] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st);
     if (he == hipSuccess && n_regions) he = hipMemcpyAsync(n_regions, d_nreg, out_bytes[2], on_dev[2] ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st);
-    if (he == hipSuccess) he = hipStreamSynchronize(st);
-    if (he != hipSuccess) return fail(hip_rc(he, "expected counts"));
+    if (he != hipSuccess) return hip_rc(he, "expected counts");
+    if ((rc = work.wait("expected counts"))) return rc;
     float ms01 = 0;
     (void) hipEventElapsedTime(&ms01, c->ev[0], c->ev[1]);
     if (device_ms) *device_ms = ms01;
-    pool_free(c, wblk, wgot);
     return MS_OK;
 }
 

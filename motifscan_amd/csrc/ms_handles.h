@@ -7,9 +7,11 @@
 // summed likelihood ratio of every cell), ms_expcounts.hip (the expected base counts per motif column on an affinity's terms), ms_shuffle.hip (a sequence set shuffled into a new one: mono- and dinucleotide controls),
 // ms_kmers.hip (the k-mer counts of a sequence set or a genome), ms_sitesignal.hip (a resident per-base track and its sums over a result's sites),
 // ms_variants.hip and ms_alleles.hip (the record scans over variants: one placement driver, place_records, and one handle head, RecHead).
-// The four dense walks -- ms_best.hip, ms_affinity.hip, ms_scorehist.hip, ms_expcounts.hip -- plan on the host with ms_dense_plan.h and share the dense_*
-// helpers below (the plan's upload, the chunked launches, the LDS limit; DenseHead, what ms_best and ms_affinity begin with), which
-// ms_best.hip implements.
+// The five dense walks -- ms_best.hip, ms_affinity.hip, ms_scorehist.hip, ms_expcounts.hip, ms_dimodel.hip (the best window per first-order
+// model) -- plan on the host with ms_dense_plan.h and share the dense_* helpers below (the plan's upload, the chunked launches, the LDS limit;
+// DenseHead, what ms_best and ms_affinity begin with) and WorkBlock, the one place a work block goes back to the pool from.  The three that
+// fill a [P][R] matrix (ms_scan_best, ms_scan_affinity, ms_scan_best_dimodels) run through one driver, DenseRun, and the two best-site walks
+// end in one tail (best_alloc, best_tail).  ms_best.hip implements all of it.
 #pragma once
 #include <sched.h>
 #include <atomic>
@@ -426,8 +428,65 @@ inline int dense_chunks(int64_t n, const char *what, Launch launch) {
     }
     return MS_OK;
 }
-// c->ev[1] behind the last launch, the wait for the stream, and h->device_ms since c->ev[0]
-MS_HIDDEN int dense_finish(DeviceCtx *c, const char *what, DenseHead *h);
+// A work block from the device's pool and the stream its readers and writers are queued on: the ONE place such a block goes back from.
+// The pool is not stream-ordered (pool_free hands the block on at once, pool_alloc may fill it from elsewhere), so release() waits for the
+// stream first unless wait() has succeeded: on every early return nothing queued may still touch the block.  Its owner declares it
+// BEHIND its lock guards (the wait runs under them) and behind the result handle the queued work fills (freed after it).
+struct WorkBlock {
+    DeviceCtx *c = nullptr;
+    hipStream_t st = nullptr;
+    void *p = nullptr;
+    size_t bytes = 0;
+    bool idle = false;                                // wait() has succeeded: nothing queued is left
+    WorkBlock() = default;
+    WorkBlock(const WorkBlock &) = delete;
+    ~WorkBlock() { release(); }
+    int alloc(DeviceCtx *ctx, hipStream_t stream, size_t n) { c = ctx; st = stream; return pool_alloc(c, n, &p, &bytes); }
+    int wait(const char *what) {                      // the owner's last synchronisation; `what` names it in the error text
+        const hipError_t e = hipStreamSynchronize(st);
+        idle = e == hipSuccess;
+        return idle ? MS_OK : hip_rc(e, what);
+    }
+    void release() {
+        if (p && !idle) (void) hipStreamSynchronize(st);
+        pool_free(c, p, bytes);
+        p = nullptr;
+    }
+};
+// The driver of the three walks that fill a [P][R] matrix (ms_scan_best, ms_scan_affinity, ms_scan_best_dimodels): what one keeps from its
+// checks to its last launch.  An entry point runs dense_check, its own checks, dense_open, allocates its result, adds its slots to cv,
+// runs dense_start, launches, and dense_end.  Whichever way it returns the work block goes back first, the locks are released last.
+struct DenseRun {
+    DeviceCtx *c = nullptr;
+    hipStream_t st = nullptr;
+    DensePlan plan;
+    Carve cv;                                         // the work block's layout: the plan's slots, then the caller's
+    DenseSlots ds;
+    DenseDev d;                                       // the plan's arrays in the work block
+    unsigned gx = 0;                                  // blocks of kBestWaves segments: the x of the walk's grid
+    size_t lds = 0, lds_most = 0;                     // bytes of the plan's largest tile behind its zero entry, and of a full tile
+    std::unique_lock<std::mutex> lk_dev, lk_set;      // the device's lock, and the PWM set's where there is one
+    WorkBlock work;
+};
+// require_device, then the checks the three share, with their texts: a NULL handle (`set`: the PWM or model set), the strand mask
+MS_HIDDEN int dense_check(const void *set, const ms_seqset *seqs, int strand_mask);
+// dense_regions_fit(fit_what), the device's context, the plan of widths[P] by the walk's geometry, the locks, the thread on the device
+MS_HIDDEN int dense_open(DenseRun *run, const DenseGeom &g, const int32_t *widths, int32_t P, std::mutex *set_mu, const ms_seqset *seqs, const char *fit_what,
+                         const std::function<bool(int32_t)> &walked);
+// the work block of layout cv, then on the stream: the PWM set's device copies (pwms may be nullptr), a pending pack of the sequence
+// set, `kernel`'s LDS limit (dense_raise_lds), the plan into run->d
+MS_HIDDEN int dense_start(DenseRun *run, ms_pwmset *pwms, const ms_seqset *seqs, const void *kernel);
+// c->ev[1] behind the last launch, the wait for the stream, h->device_ms since c->ev[0], the work block back to the pool
+MS_HIDDEN int dense_end(DenseRun *run, const char *what, DenseHead *h);
+
+// The tail of the two best-site walks (ms_scan_best, ms_scan_best_dimodels), which fill the same handle.
+struct BestPart;                                      // a segment's best of one motif (ms_best_dev.h)
+using BestPtr = std::unique_ptr<ms_best, void (*)(ms_best *)>;
+// an ms_best of P x R cells on the run's device, three planes carved from one pooled block (a cell's worth for an empty matrix)
+MS_HIDDEN int best_alloc(const DenseRun &run, int32_t P, int64_t R, BestPtr *res);
+// queues "reduce the long regions, fill the skipped rows" behind the walk's kernels; part[P][n_part]: the segments' partials; `what`
+// ("best-site") names the walk in the error text of a launch that fails
+MS_HIDDEN int best_tail(const DenseRun &run, const char *what, const BestPart *part, ms_best *b);
 
 // One [P][R] plane of doubles per group, ranked per motif row (ms_ranksum.hip): what ms_best_rank_sum (the score plane of two ms_best) and
 // ms_affinity_rank_sum (the log_mean plane of two ms_affinity) both are.  `what` names the handles in the error texts.

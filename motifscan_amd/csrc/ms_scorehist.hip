@@ -306,29 +306,28 @@ int ms_scan_score_histogram(const ms_pwmset *pwms_c, const ms_seqset *seqs, int 
     const DenseSlots ds = dense_slots(cv, plan);
     const auto s_bins = cv.add<double>(bins.size());
     const auto s_out = cv.add<unsigned long long>(out_on_device ? 0 : (size_t) P * (size_t) n_slots);
-    void *wblk = nullptr;
-    size_t wgot = 0;
-    if ((rc = pool_alloc(c, cv.bytes(), &wblk, &wgot))) return rc;
-    auto fail = [&](int code) { pool_free(c, wblk, wgot); return code; };
+    const hipStream_t st = c->stream;
+    WorkBlock work;                                    // (behind the locks: it goes back behind a wait for the stream, whichever way this returns)
+    if ((rc = work.alloc(c, st, cv.bytes()))) return rc;
+    void *const wblk = work.p;
     double *d_bins = Carve::at(wblk, s_bins);
     unsigned long long *d_out = out_on_device ? reinterpret_cast<unsigned long long *>(out) : Carve::at(wblk, s_out);
 
-    const hipStream_t st = c->stream;
     hipError_t he = hipMemsetAsync(d_out, 0, out_bytes, st);
-    if (he != hipSuccess) return fail(hip_rc(he, "clearing the histogram"));
+    if (he != hipSuccess) return hip_rc(he, "clearing the histogram");
     float ms01 = 0;
     const bool walk = R > 0 && !plan.mot.empty();
     if (walk) {
-        if ((rc = pwmset_upload(pwms, c->device, st))) return fail(rc);
-        if ((rc = seqset_pack_pending(seqs, st))) return fail(rc);
+        if ((rc = pwmset_upload(pwms, c->device, st))) return rc;
+        if ((rc = seqset_pack_pending(seqs, st))) return rc;
         const size_t lds_fixed = kHistSegBytes + hist_counter_bytes(n_bins), lds = lds_fixed + (plan.max_tile + 1) * sizeof(double2);
         if ((rc = dense_raise_lds(c, reinterpret_cast<const void *>(scorehist_kernel<true>), lds,
                                   kHistSegBytes + hist_counter_bytes(MS_SCOREHIST_MAX_BINS) + (kHistTileEntries + 1) * sizeof(double2))))
-            return fail(rc);
+            return rc;
         DenseDev d;
-        if ((rc = dense_upload(plan, ds, wblk, st, &d))) return fail(rc);
+        if ((rc = dense_upload(plan, ds, wblk, st, &d))) return rc;
         he = hipMemcpyAsync(d_bins, bins.data(), 8 * bins.size(), hipMemcpyHostToDevice, st);
-        if (he != hipSuccess) return fail(hip_rc(he, "upload of the plan"));
+        if (he != hipSuccess) return hip_rc(he, "upload of the plan");
 
         HistArgs A;
         A.codes = seqs->d_codes; A.nmask = seqs->d_nmask; A.offsets = seqs->d_offsets; A.R = R;
@@ -353,18 +352,16 @@ int ms_scan_score_histogram(const ms_pwmset *pwms_c, const ms_seqset *seqs, int 
         if (!rc) rc = dense_chunks((int64_t) plan.wide_first.size() - 1, "score-histogram kernel (tables in HBM)", [&](int64_t t0, unsigned ny) {
             hipLaunchKernelGGL(scorehist_kernel<false>, dim3(gx, ny), dim3(kHistThreads), lds_fixed, st, Aw, (int32_t) t0);
         });
-        if (rc) return fail(rc);
+        if (rc) return rc;
         (void) hipEventRecord(c->ev[1], st);
     }
     if (!out_on_device) {
         he = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st);
-        if (he != hipSuccess) return fail(hip_rc(he, "copy of the histogram"));
+        if (he != hipSuccess) return hip_rc(he, "copy of the histogram");
     }
-    he = hipStreamSynchronize(st);
-    if (he != hipSuccess) return fail(hip_rc(he, "score histogram"));
+    if ((rc = work.wait("score histogram"))) return rc;
     if (walk) (void) hipEventElapsedTime(&ms01, c->ev[0], c->ev[1]);
     if (device_ms) *device_ms = ms01;
-    pool_free(c, wblk, wgot);
     return MS_OK;
 }
 

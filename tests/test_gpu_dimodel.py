@@ -159,6 +159,28 @@ def test_the_degenerate_model_of_a_pwm_equals_ms_scan_best(mask):
     assert np.isfinite(got[0]).sum() > 100
 
 
+def test_ties_across_more_than_a_wave_of_segments(world):
+    """Regions of more than 64 segments: a lane of the reduce kernel that this walk shares with ms_scan_best folds several partials, in
+    segment order, before the wave is reduced.  Poly-A and a short repeat tie in every segment; the first window keeps the cell, and
+    the degenerate models of two PWMs give ms_scan_best's planes."""
+    seg = world["dims"]["seg_windows"]
+    mats = [dc.random_pwm(5, 11), dc.random_pwm(9, 12)]
+    unit = "ACGGTCA"
+    seqs = ["A" * (65 * seg + 40), (unit * (130 * seg // len(unit) + 1))[:129 * seg + 3], unit * 3]
+    pw, sq = _lib.PwmSet.from_matrices(mats), _lib.SeqSet.from_strings(seqs)
+    try:
+        for mask in (1, 3):
+            res = _lib.scan_best(pw, sq, mask)
+            want = res.sites()
+            res.close()
+            got = run([dimodel.DiModel.from_pwm(m) for m in mats], seqs, mask, sq=sq)
+            dc.same_planes(got, want)
+            assert np.all(got[1][:, 0] == 0) and np.all(got[1][:, 1] < len(unit)) and np.isfinite(got[0]).all()
+    finally:
+        sq.close()
+        pw.close()
+
+
 def test_the_viterbi_sequence_scores_exactly_one(world):
     """max_raw is the greatest FORWARD raw sum, attained by the Viterbi sequence on '+' (the reverse strand adds the same terms in the
     other order and may round differently, so the exact 1.0 is a statement about '+')."""
