@@ -84,6 +84,10 @@
  *   ms_dimodelset_* / ms_scan_best_dimodels
  *                         no reference counterpart: the same best-site matrix for FIRST-ORDER models, whose column scores depend on the
  *                         base of the column before (dinucleotide weight matrices, first-order BaMMs, TFFMs) -- into the same ms_best handle
+ *   ms_scan_best_bipartite / ms_best_gaps*
+ *                         no reference counterpart: the best site of two half-sites of the set with a spacer of variable length in a
+ *                         fixed relative orientation (nuclear-receptor repeats, p53, composite elements) -- into the same ms_best handle,
+ *                         with the winner's gap as a fourth plane
  *   ms_result_cooccurrence   no reference counterpart: the motif x motif matrix of "regions that hold a site of both", reduced on the
  *                         device from the hit arrays a result holds (has-site bit rows, a tiled popcount product)
  *   ms_result_pair_spacing    no reference counterpart: for one anchor motif against every partner motif, the histogram of the
@@ -617,6 +621,44 @@ int  ms_dimodelset_size(const ms_dimodelset *models, int32_t *n_models);
 int  ms_dimodelset_max_raw(const ms_dimodelset *models, double *out /* [n_models] */);
 void ms_dimodelset_free(ms_dimodelset *models);
 int  ms_scan_best_dimodels(const ms_dimodelset *models, const ms_seqset *seqs, int strand_mask, uint32_t flags /* 0 */, ms_best **out);
+
+/* ---- bipartite motifs: the best site of two half-sites with a variable spacer (ms_bipartite.hip) ---------------------- */
+/* A BIPARTITE SPEC over a PWM set is (a, b, flip, g_min, g_max): a and b are motif indices of the set (a == b is allowed), flip is 0 or 1,
+ * and 0 <= g_min <= g_max <= G (G = 64; both elements have at most 64 columns; ms_debug_bipartite_dims reports the caps).  For motif m of
+ * width W_m and window start p of a region:
+ *     F_m(p), R_m(p)   the forward and the reverse raw sum of the window exactly as ms_scan_best forms them: S = 0.0, then for the columns
+ *                      c = 0 .. W_m - 1 in that order F += M[x][c] and R += M[3 - x][W_m - 1 - c] for the base x at p + c; a non-ACGT base
+ *                      adds nothing.  Every "+=" is one rounded IEEE fp64 addition.
+ * For a gap g the site spans S = W_a + g + W_b bases and is placed at p, 0 <= p <= L - S, on either strand:
+ *     '+'  raw = F_a(p) + Y(p + W_a + g)      with Y  = F_b for flip == 0 and R_b for flip == 1;
+ *     '-'  raw = Y'(p) + R_a(p + W_b + g)     with Y' = R_b for flip == 0 and F_b for flip == 1: the same composite read on the other strand,
+ *                                             so on the forward strand b's half comes first.
+ * Each raw is ONE rounded fp64 addition of the two element sums, left operand first as written.  The bases of the spacer are never read.
+ *     denominator   D = max_raw_a + max_raw_b, one rounded addition of the set's two max_raw values (ms_pwmset_max_raw);
+ *     score         raw / D, one IEEE fp64 divide.
+ * The BEST SITE of a cell (spec, region): p is walked ascending; at each p '+' comes before '-' over the strands of strand_mask; within a
+ * strand g ascends from g_min to g_max; from best = -inf a placement replaces the best iff its score is GREATER -- ties keep the earlier
+ * placement, -inf never wins.  Per cell the result holds score (fp64), pos (int32: the leftmost base of the whole site, relative to the
+ * region), strand (int8: 1 or 2) and gap (int16); a cell without a winner holds NaN, -1, 0, -1.
+ * A spec is SCORABLE iff no entry of either element is NaN or +inf and D is a finite number > 0 -- the rule is on the sum, so a partner
+ * whose columns are all zero is legal.  Every cell of an unscorable spec holds the no-winner values.  An entry of -inf is ordinary: the
+ * placement's raw sum is -inf.
+ *
+ * ms_scan_best_bipartite returns an ordinary ms_best with n_pwms = n_specs: ms_best_shape, ms_best_sites, ms_best_sites_device,
+ * ms_best_device_ms, ms_best_rank_sum, ms_best_count_passing and ms_best_free take it as they take ms_scan_best's.  The handle carries a
+ * fourth plane, the gaps: ms_best_gaps copies the rows m0 <= m < m1 of it to host memory, ms_best_gaps_device gives its device address
+ * (valid until ms_best_free); on a handle from any other scan both return MS_ERR_INVALID.  The bytes of all four planes are the same on
+ * every run, and a cell does not depend on which other specs and regions share the call.  The PWM set's cutoffs are not read, and the set
+ * is not bound to a device by this call: the specs' tables (4 (W_a + W_b) entries of 16 bytes each) are uploaded per call.
+ * Work memory: those tables, and 18 bytes per (spec, segment) of the regions of more than one segment.
+ * MS_ERR_RUNTIME ("no CPU fallback") without a device, before anything else.  MS_ERR_INVALID: out NULL, NULL handles, NULL arrays with
+ * n_specs > 0, n_specs < 0, an index outside the set, flip > 1, g_min < 0, g_min > g_max, g_max > G, an element wider than the cap, a strand
+ * mask outside 1..3, flags != 0, a region of 2^31 bases or more.  MS_ERR_NOMEM: the 15 bytes per cell or the work block do not fit the device
+ * (nothing has been launched then).  n_specs = 0 and n_seqs = 0 are valid and give empty results. */
+int  ms_scan_best_bipartite(const ms_pwmset *pwms, const int32_t *a, const int32_t *b, const uint8_t *flip, const int32_t *gap_min, const int32_t *gap_max,
+                            int32_t n_specs, const ms_seqset *seqs, int strand_mask, uint32_t flags /* 0 */, ms_best **out);
+int  ms_best_gaps(const ms_best *b, int32_t m0, int32_t m1, int16_t *gap /* [m1 - m0][n_seqs] */);
+int  ms_best_gaps_device(const ms_best *b, void **d_gap);
 
 /* ---- cutoff-free enrichment over best-site matrices that stay on the device (ms_ranksum.hip) ------------------------- */
 /* ORDER OF CELL VALUES, for both calls: a cell without a winner (score NaN, strand 0) ranks below every number; all cells without a winner

@@ -272,6 +272,14 @@ int ms_debug_compare_null(const double *q_values, const int32_t *q_widths, int32
  * here.  Needs no GPU. */
 int ms_debug_dimodel_dims(int32_t out[8]);
 
+/* The path constants of ms_scan_best_bipartite, as constants of the build: out[0] the threads of a block of its walk; out[1] the window
+ * starts per segment of a region (one wave each; a region of more than one segment goes through the partials, their reduction and the
+ * gather of the winner's gap); out[2] the table entries of one LDS tile (a spec takes 4 (W_a + W_b): a run of consecutive scorable specs
+ * shares a tile while their entries fit); out[3] the width cap of an element and out[4] the gap cap G (above either: MS_ERR_INVALID);
+ * out[5] the halo strips of 64 window starts a wave sums behind its segment (64 out[5] >= out[3] + out[4]); out[6] the LDS bytes of a
+ * block, the tile and the waves' rings; out[7] reserved, 0.  Tests size their boundary cases from here.  Needs no GPU. */
+int ms_debug_bipartite_dims(int32_t out[8]);
+
 /* A set as a batch stream's upload stage leaves it: ASCII and offsets in HBM, the planes still to be packed by its first scan.  The entry
  * points that read the planes directly (ms_seqset_kmer_counts, ms_seqset_shuffle, ms_seqset_packed_host) refuse it with MS_ERR_INVALID: this
  * is how a test gets one.  Every scan entry point takes it and packs it; free it with ms_seqset_free.  Needs a GPU. */

@@ -18,6 +18,8 @@ motifscan_amd -- MI355X-native drop-in for ONE hot path of shao-lab/MotifScan: t
                             (ms_affinity_expected_counts, the E-step), their numpy restatement and mpmath reference, the M-step, the loop
     motifscan_amd.dimodel   first-order motif models (a column's score depends on the base before it): DiModel and its constructors from a
                             PWM, from counts and from a site stack, and the numpy restatement of ms_scan_best_dimodels
+    motifscan_amd.bipartite bipartite motifs (two half-sites of a PWM set, a spacer of variable length, a fixed relative orientation): the
+                            Bipartite spec, specs from a pair-spacing histogram, and the numpy restatement of ms_scan_best_bipartite
 
 There is no CPU fallback anywhere in this package.
 """

@@ -277,6 +277,10 @@ def lib():
         "ms_dimodelset_free": (None, [vp]),
         "ms_scan_best_dimodels": (c_int, [vp, vp, c_int, c_u32, pvp]),
         "ms_debug_dimodel_dims": (c_int, [pi32]),
+        "ms_scan_best_bipartite": (c_int, [vp, pi32, pi32, pu8, pi32, pi32, c_i32, vp, c_int, c_u32, pvp]),
+        "ms_best_gaps": (c_int, [vp, c_i32, c_i32, ctypes.POINTER(ctypes.c_int16)]),
+        "ms_best_gaps_device": (c_int, [vp, pvp]),
+        "ms_debug_bipartite_dims": (c_int, [pi32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1567,6 +1571,24 @@ class BestSites:
         check(lib().ms_best_sites_device(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         return a.value, b.value, c.value
 
+    def gaps(self, m0=0, m1=None):
+        """ms_best_gaps: the winners' gaps of the rows m0 <= m < m1 as a fresh int16 (m1 - m0, R) array, -1 where no placement wins.  Only
+        a result of scan_best_bipartite holds them: every other one raises ValueError."""
+        if self.h is None:
+            raise ValueError("the result is closed")
+        m0, m1 = self._motif_range(m0, m1)
+        if m0 < 0 or m1 > self.n_pwms or m0 > m1:
+            raise ValueError(f"motif range [{m0}, {m1}) outside [0, {self.n_pwms})")
+        gap = np.zeros((m1 - m0, self.n_seqs), dtype=np.int16)
+        check(lib().ms_best_gaps(self.h, m0, m1, ptr(gap, ctypes.c_int16)))
+        return gap
+
+    def gaps_device_pointer(self):
+        """ms_best_gaps_device: the device address of the full (P, R) int16 gap plane, valid until close()."""
+        a = ctypes.c_void_p()
+        check(lib().ms_best_gaps_device(self.h, ctypes.byref(a)))
+        return a.value
+
     def device_ms(self):
         ms = ctypes.c_double()
         check(lib().ms_best_device_ms(self.h, ctypes.byref(ms)))
@@ -1678,6 +1700,31 @@ def scan_best_dimodels(models, seqs, strand_mask=3, flags=0):
     h = ctypes.c_void_p()
     check(lib().ms_scan_best_dimodels(models.h, seqs.h, strand_mask, int(flags), ctypes.byref(h)))
     return BestSites(h)
+
+
+def scan_best_bipartite(pwms, specs, seqs, strand_mask=3, flags=0):
+    """ms_scan_best_bipartite: the best site of every (bipartite spec, region) cell of a PwmSet x SeqSet; specs: bipartite.Bipartite objects
+    or (a, b, flip, gap_min, gap_max) tuples.  Returns a BestSites whose gaps() holds the fourth plane: rank_sum, count_passing and the
+    device pointers work on it as on ms_scan_best's."""
+    from . import bipartite
+    strand_mask = int(strand_mask)
+    if strand_mask not in (1, 2, 3):
+        raise ValueError(f"invalid strand mask {strand_mask!r} (1 '+', 2 '-', 3 both)")
+    if int(flags) != 0:
+        raise ValueError(f"unknown bipartite best-site scan flags {flags!r}")
+    a, b, flip, g0, g1 = bipartite.spec_arrays(specs)
+    h = ctypes.c_void_p()
+    check(lib().ms_scan_best_bipartite(pwms.h, ptr(a, ctypes.c_int32), ptr(b, ctypes.c_int32), ptr(flip, ctypes.c_uint8), ptr(g0, ctypes.c_int32),
+                                       ptr(g1, ctypes.c_int32), len(a), seqs.h, strand_mask, int(flags), ctypes.byref(h)))
+    return BestSites(h)
+
+
+def bipartite_dims():
+    """ms_debug_bipartite_dims: dict(threads, seg_windows, tile_entries, max_width, max_gap, halo_strips, lds_bytes) -- the sizes at which
+    ms_scan_best_bipartite changes segment or tile, and its caps.  Constants of the build; no device."""
+    out = np.zeros(8, dtype=np.int32)
+    check(lib().ms_debug_bipartite_dims(ptr(out, ctypes.c_int32)))
+    return dict(zip(("threads", "seg_windows", "tile_entries", "max_width", "max_gap", "halo_strips", "lds_bytes"), (int(v) for v in out[:7])))
 
 
 def dimodel_dims():

@@ -277,10 +277,10 @@ int dense_end(DenseRun *run, const char *what, DenseHead *h) {
     return MS_OK;
 }
 
-int best_alloc(const DenseRun &run, int32_t P, int64_t R, BestPtr *res) {
-    // ---- 13 bytes per cell, 16 per partial: both blocks are allocated before anything is launched, and a failure there is the MS_ERR_NOMEM
-    // of the header (the test here only keeps the byte counts below inside size_t)
-    if (13.0 * (double) P * (double) R + 16.0 * (double) P * (double) run.plan.n_part >= 0.5 * (double) std::numeric_limits<size_t>::max()) {
+int best_alloc(const DenseRun &run, int32_t P, int64_t R, BestPtr *res, bool gaps) {
+    // ---- 13 bytes per cell (15 with the gap plane), 16 per partial (18): both blocks are allocated before anything is launched, and a failure
+    // there is the MS_ERR_NOMEM of the header (the test here only keeps the byte counts below inside size_t)
+    if ((gaps ? 15.0 : 13.0) * (double) P * (double) R + (gaps ? 18.0 : 16.0) * (double) P * (double) run.plan.n_part >= 0.5 * (double) std::numeric_limits<size_t>::max()) {
         set_error("%d x %lld cells do not fit the device", P, (long long) R);
         return MS_ERR_NOMEM;
     }
@@ -295,10 +295,12 @@ int best_alloc(const DenseRun &run, int32_t P, int64_t R, BestPtr *res) {
     const auto s_score = rv.add<double>(cz);
     const auto s_pos = rv.add<int32_t>(cz);
     const auto s_strand = rv.add<int8_t>(cz);
+    const auto s_gap = rv.add<int16_t>(gaps ? cz : 0);
     if (const int rc = pool_alloc(run.c, rv.bytes(), &b->block, &b->block_bytes)) return rc;
     b->d_score = Carve::at(b->block, s_score);
     b->d_pos = Carve::at(b->block, s_pos);
     b->d_strand = Carve::at(b->block, s_strand);
+    if (gaps) b->d_gap = Carve::at(b->block, s_gap);
     return MS_OK;
 }
 

@@ -11,7 +11,8 @@
 // model) -- plan on the host with ms_dense_plan.h and share the dense_* helpers below (the plan's upload, the chunked launches, the LDS limit;
 // DenseHead, what ms_best and ms_affinity begin with) and WorkBlock, the one place a work block goes back to the pool from.  The three that
 // fill a [P][R] matrix (ms_scan_best, ms_scan_affinity, ms_scan_best_dimodels) run through one driver, DenseRun, and the two best-site walks
-// end in one tail (best_alloc, best_tail).  ms_best.hip implements all of it.
+// end in one tail (best_alloc, best_tail).  ms_best.hip implements all of it.  ms_bipartite.hip (the best site of two half-sites with a
+// variable spacer) is a sixth walk on the same driver and tail; it adds the gap plane to ms_best.
 #pragma once
 #include <sched.h>
 #include <atomic>
@@ -313,6 +314,7 @@ struct ms_best : ms::DenseHead {                      // ms_scan_best: the best 
     double *d_score = nullptr;                        // NaN: no winner
     int32_t *d_pos = nullptr;                         // relative to the region start, -1: no winner
     int8_t *d_strand = nullptr;                       // 1 '+', 2 '-', 0: no winner
+    int16_t *d_gap = nullptr;                         // ms_scan_best_bipartite only (nullptr from every other scan): the winner's gap, -1: no winner
 };
 
 struct ms_affinity : ms::DenseHead {                  // ms_scan_affinity: the summed likelihood ratio of every (motif, region) cell; four planes
@@ -479,11 +481,12 @@ MS_HIDDEN int dense_start(DenseRun *run, ms_pwmset *pwms, const ms_seqset *seqs,
 // c->ev[1] behind the last launch, the wait for the stream, h->device_ms since c->ev[0], the work block back to the pool
 MS_HIDDEN int dense_end(DenseRun *run, const char *what, DenseHead *h);
 
-// The tail of the two best-site walks (ms_scan_best, ms_scan_best_dimodels), which fill the same handle.
+// The tail of the three best-site walks (ms_scan_best, ms_scan_best_dimodels, ms_scan_best_bipartite), which fill the same handle.
 struct BestPart;                                      // a segment's best of one motif (ms_best_dev.h)
 using BestPtr = std::unique_ptr<ms_best, void (*)(ms_best *)>;
-// an ms_best of P x R cells on the run's device, three planes carved from one pooled block (a cell's worth for an empty matrix)
-MS_HIDDEN int best_alloc(const DenseRun &run, int32_t P, int64_t R, BestPtr *res);
+// an ms_best of P x R cells on the run's device, three planes carved from one pooled block (a cell's worth for an empty matrix); gaps:
+// with the fourth plane d_gap (ms_scan_best_bipartite), 15 bytes per cell
+MS_HIDDEN int best_alloc(const DenseRun &run, int32_t P, int64_t R, BestPtr *res, bool gaps = false);
 // queues "reduce the long regions, fill the skipped rows" behind the walk's kernels; part[P][n_part]: the segments' partials; `what`
 // ("best-site") names the walk in the error text of a launch that fails
 MS_HIDDEN int best_tail(const DenseRun &run, const char *what, const BestPart *part, ms_best *b);

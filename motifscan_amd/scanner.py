@@ -17,6 +17,8 @@ and the questions the reference cannot answer from its site lists:
     Scanner.best_sites(pwms) -> BestSiteArrays: the best-scoring window of every (motif, region), cutoff or not.
     Scanner.rank_sum(pwms, control) -> enrich.RankSum: cutoff-free enrichment of the best scores against a control scanner's.
     Scanner.count_regions_passing(pwms, cutoffs) -> the regions with >= 1 site at several cutoffs per motif, from one scan.
+    Scanner.best_sites_bipartite(pwms, specs) -> bipartite.BipartiteSites: the best placement of two half-sites with a variable spacer.
+    Scanner.rank_sum_bipartite(pwms, specs, control) -> enrich.RankSum: rank_sum over those best placements.
     Scanner.affinity(pwms) -> affinity.AffinityArrays: the likelihood ratio summed over ALL windows of every (motif, region).
     Scanner.affinity_rank_sum(pwms, control) -> enrich.RankSum: rank_sum with that sum in place of the best score.
     Scanner.expected_counts(pwms, gamma) -> em.ExpectedCounts: per motif column the A, C, G, T weight over ALL windows, each weighted by
@@ -433,6 +435,48 @@ class Scanner:
                 mine.close()
         finally:
             ms.close()
+
+    def _scan_best_bipartite(self, pw, specs):
+        return _lib.scan_best_bipartite(pw, specs, self._seqset(), _STRAND_FLAG[self.strand])
+
+    def best_sites_bipartite(self, pwms, specs):
+        """best_sites for bipartite motifs (bipartite.Bipartite specs over `pwms`: two half-sites with a spacer of gap_min .. gap_max
+        bases): the best placement of every (spec, region) cell as a bipartite.BipartiteSites (ms_scan_best_bipartite) -- start is the
+        leftmost base of the whole site, gap the winner's spacer length.  The halves are scored as best_sites scores them; the first
+        placement in the walk's order (start ascending, '+' before '-', gap ascending) keeps a tie.  Honours the scanner's `strand`."""
+        from . import bipartite
+        matrices = [np.asarray(pwm.matrix, dtype=np.float64) for pwm in pwms]
+        pw = _lib.PwmSet.from_matrices(matrices)
+        try:
+            res = self._scan_best_bipartite(pw, specs)
+            try:
+                score, pos, strand = res.sites()
+                gap = res.gaps()
+            finally:
+                res.close()
+        finally:
+            pw.close()
+        return bipartite.BipartiteSites(score, best_site_starts(pos, self.seq_starts), strand, gap)
+
+    def rank_sum_bipartite(self, pwms, specs, control, sel=None, sel_control=None):
+        """rank_sum for bipartite motifs: is each spec enriched in this scanner's regions against `control`'s, by the best score per
+        region and without a cutoff?  An enrich.RankSum.  Both region lists are scanned with ms_scan_best_bipartite, each with its
+        scanner's `strand`; the matrices stay on the device and are reduced there (ms_best_rank_sum)."""
+        from . import enrich
+        matrices = [np.asarray(pwm.matrix, dtype=np.float64) for pwm in pwms]
+        pw = _lib.PwmSet.from_matrices(matrices)
+        try:
+            mine = self._scan_best_bipartite(pw, specs)
+            try:
+                theirs = control._scan_best_bipartite(pw, specs)
+                try:
+                    return enrich.rank_sum(mine, theirs, sel, sel_control)
+                finally:
+                    theirs.close()
+            finally:
+                mine.close()
+        finally:
+            pw.close()
 
     def count_regions_passing(self, pwms, cutoffs):
         """int64 [n_pwms][K]: the number of this scanner's regions that hold >= 1 site of each motif at each of its K cutoffs
